@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X Qwen3-TTS hot path (BASELINE.json metric: RTF + 12 Hz codec-tokens/s).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step, rtf, ...); --full adds
+everything else the benchmark measures or checks (result check against the oracle fixture, rooflines, other legs, CPU
+baseline), each in runs of its own after the timed steps.
 
 N > 1: one process per GPU.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a
 rank; started plainly with --gpus N it first re-launches itself as N ranks through torch.distributed.run (before
@@ -77,7 +81,17 @@ def parse():
                          "(the line is marked data=stub and is not a measurement)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--cache", default=os.environ.get("Q3_BENCH_CACHE", "/tmp/q3_bench_cache"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the result check against the oracle fixture, the frame graph and the vocoder alone, "
+                         "the rooflines, the split-arithmetic vocoder, the batch-1, long-form and natural-length legs, the CPU "
+                         "baseline and the in-graph timeline (the --no-* options trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's): DIR/codes.npy = the codec ids "
+                         "[frames][batch][16] and DIR/waveform.npy = the vocoder's samples [batch][chunk samples], float32")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def make_pack(cache, seed, rank, barrier):
@@ -223,12 +237,12 @@ def run_leg(eng, voc, prefixes, n_text, pad, frames, steps, warmup, sync_all):
         pending = one_step(pending, last=(i == steps - 1))
         frame_ms.append(eng.last_run_ms / frames)
         prefill_ms.append(eng.last_prefill_ms)
-    if pending is not None:
-        pending.result()
+    wave = pending.result() if pending is not None else None
     sync_all()
     dt = time.perf_counter() - t0
     pool.shutdown()
     run_leg.last_codes = eng.codes()[0].copy()      # what the LAST timed step computed (checked outside the timed region)
+    run_leg.last_wave = wave.copy() if wave is not None else None     # (a view of the vocoder's buffer: the next decode reuses it)
     return dt, float(np.mean(frame_ms)), float(np.mean(prefill_ms)), float(np.mean(voc.ms)) if voc is not None else 0.0
 
 
@@ -610,6 +624,31 @@ def aggregate_value(world, B, frames, steps, dt_max):
     return world * B * frames * steps / dt_max
 
 
+def headline(a, world, B, F, dt, prefill_ms, voc_ms_step):
+    """The result line's figures that come from the timed steps alone (dt = max over the ranks)."""
+    return {
+        "metric": "12Hz codec-tokens/s (codec frames/s, 16 codes each) + RTF, Qwen3-TTS-0.6B",
+        "value": round(aggregate_value(world, B, F, a.steps, dt), 1), "unit": "codec_frames/s", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f16 weights/KV, f32 accumulate (talker+CP); vocoder exact fp32 (f32 MFMA)", "data": "synthetic (random-init weights of the "
+        "0.6B architecture, seeded prefix embeddings, greedy, EOS suppressed)",
+        "config": {"workload": f"configs[2]/[3]: batch={B} mixed ru/en prompts per GPU, {F} frames/utterance/step "
+                               f"(prefill + hipGraph decode loop), utterance-sharded DP over {world} GPU(s)",
+                   "batch_per_gpu": B, "frames_per_step": F, "prompt_tokens": "5-40 (fixed set)"},
+        "rtf": round((dt / a.steps) / (F * FRAME_SEC), 5),
+        "rtf_aggregate": round((dt / a.steps) / (world * B * F * FRAME_SEC), 6),
+        "prefill_ms": round(prefill_ms, 3), "vocoder_ms_per_step": round(voc_ms_step, 3),
+    }
+
+
+def dump_outputs(d, codes, wave):
+    """--dump-outputs: what the last timed step handed its caller, as float32 arrays (ids < 2^24 are exact)."""
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "codes.npy"), codes.astype(np.float32))
+    if wave is not None:
+        np.save(os.path.join(d, "waveform.npy"), wave.astype(np.float32))
+
+
 def relaunch_as_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N ranks (one per GPU) through torch.distributed.run
     BEFORE this process touches a GPU, relay their output (rank 0 prints the JSON line) and exit with their code."""
@@ -640,6 +679,8 @@ def main():
     if a.stub_engine:
         eng = StubEngine(max_frames=F)
         dt, frame_ms, _, _ = run_leg(eng, None, prefixes, n_text, pad, F, a.steps, a.warmup, sync_all)
+        if a.dump_outputs and rank == 0:
+            dump_outputs(a.dump_outputs, run_leg.last_codes, None)
         dt = R.max_over_ranks(dt)
         if rank == 0:
             print(json.dumps({"metric": "12Hz codec-tokens/s (codec frames/s, 16 codes each) + RTF, Qwen3-TTS-0.6B",
@@ -677,6 +718,17 @@ def main():
         # (fp32-grade against float64) is reported beside it as an option
         lib.voc_set_exact_fp32(1)
     dt, frame_ms_step, prefill_ms, voc_ms = run_leg(eng, voc, prefixes, n_text, pad, F, a.steps, a.warmup, sync_all)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, run_leg.last_codes, run_leg.last_wave)
+    if not a.full:
+        if voc is not None:
+            voc.close()
+        eng.destroy()
+        dt = R.max_over_ranks(dt)
+        if rank == 0:
+            print(json.dumps(headline(a, world, B, F, dt, prefill_ms, voc_ms)), flush=True)
+        R.close()
+        return
     verified = verify_against_fixture(run_leg.last_codes, B, F, a.seed, world, prefixes, n_text, pad, rank, R)
     # the frame graph alone on the chip (inside a step the previous step's vocoder chunk runs beside it and the two
     # share the machine; the kernel-quality figure is this one)
@@ -695,22 +747,10 @@ def main():
         voc_ms = float(voc.ms[-1])
     step_w_bytes = eng.step_weight_bytes
     dt = R.max_over_ranks(dt)
-    value = aggregate_value(world, B, F, a.steps, dt)
-    ms_per_step = dt / a.steps * 1e3
     algo_bytes = step_w_bytes + kv_bytes_per_step(n_text, F, cfg)
     achieved = algo_bytes / (frame_ms * 1e-3) / 1e9
     out = {
-        "metric": "12Hz codec-tokens/s (codec frames/s, 16 codes each) + RTF, Qwen3-TTS-0.6B",
-        "value": round(value, 1), "unit": "codec_frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f16 weights/KV, f32 accumulate (talker+CP); vocoder exact fp32 (f32 MFMA)", "data": "synthetic (random-init weights of the "
-        "0.6B architecture, seeded prefix embeddings, greedy, EOS suppressed)",
-        "config": {"workload": f"configs[2]/[3]: batch={B} mixed ru/en prompts per GPU, {F} frames/utterance/step "
-                               f"(prefill + hipGraph decode loop), utterance-sharded DP over {world} GPU(s)",
-                   "batch_per_gpu": B, "frames_per_step": F, "prompt_tokens": "5-40 (fixed set)"},
-        "rtf": round((dt / a.steps) / (F * FRAME_SEC), 5),
-        "rtf_aggregate": round((dt / a.steps) / (world * B * F * FRAME_SEC), 6),
-        "prefill_ms": round(prefill_ms, 3), "vocoder_ms_per_step": round(voc_ms_step, 3),
+        **headline(a, world, B, F, dt, prefill_ms, voc_ms_step),
         "verified": verified,
         "roofline": None,
         "roofline_step": {"kernel": "frame-step hipGraph (talker 28L + 15 code-predictor passes + heads, 553 nodes)",

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 fail() { echo "$1 failed"; find $O -name "*.db" -size +20M -delete; find $O -name "*_kernel_trace.csv" -size +20M -delete; exit 1; }
 # 1. per-kernel time of the benchmark command, eager launches (rocprofv3's kernel trace cannot follow the graph replay);
 #    the profiler run keeps the runtime's four hardware queues (it hangs with one)
-GPU_MAX_HW_QUEUES=4 Q3_NO_GRAPH=1 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python3 $R/bench.py --steps 3 --warmup 1 --no-timeline --no-cpu --no-longform --no-ragged > $O/bench_prof.log 2> $O/bench_prof.err || { tail -3 $O/bench_prof.err; fail "kernel trace"; }
+GPU_MAX_HW_QUEUES=4 Q3_NO_GRAPH=1 timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $O/prof -o bench -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-timeline --no-cpu --no-longform --no-ragged > $O/bench_prof.log 2> $O/bench_prof.err || { tail -3 $O/bench_prof.err; fail "kernel trace"; }
 echo "kernel trace done"
 # 2. PMC passes: HBM traffic of the weight-streaming kernels and of the vocoder, MFMA utilisation of the vocoder
 for c in FETCH_SIZE WRITE_SIZE; do
@@ -31,7 +31,7 @@ python scripts/frame_timeline.py --batch 32 --csv $O/frame_nodes_b32.csv > $O/tl
 python scripts/frame_timeline.py --batch 1 --csv $O/frame_nodes_b1.csv > $O/tl1.log 2>&1 || fail "timeline 1"
 echo "timeline done"
 python scripts/voc_profile.py --batch 32 --exact 1 > $O/voc_per_op.log 2>&1 || fail "voc per-op"
-# 4. the benchmark line itself, default flags (what the driver runs)
-python bench.py > $O/bench_default.log 2> $O/bench_default.err || { tail -5 $O/bench_default.err; fail "bench"; }
+# 4. the benchmark line with every leg and check (--full)
+python bench.py --full > $O/bench_default.log 2> $O/bench_default.err || { tail -5 $O/bench_default.err; fail "bench"; }
 echo "bench done"
 tail -c 600 $O/bench_default.log

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -65,13 +66,13 @@ def test_dealing_balances_config4():
     assert sorted(len(r) for r in ragged) == [2, 2, 3]
 
 
-def test_bench_gpus_2_starts_two_ranks_itself():
+def test_bench_gpus_2_starts_two_ranks_itself(tmp_path):
     """`python bench.py --gpus 2` with no launcher environment must run TWO ranks (round 1 ran one and printed
     n_gpus 1).  CPU: gloo backend and the stand-in engine; the JSON line must say n_gpus 2 and count both ranks'
-    frames."""
+    frames; --dump-outputs leaves rank 0's codec ids of the last timed step."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--batch", "4", "--frames", "8", "--stub-engine", "--backend", "gloo"],
+                          "--batch", "4", "--frames", "8", "--stub-engine", "--backend", "gloo", "--dump-outputs", str(tmp_path)],
                          env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -80,6 +81,8 @@ def test_bench_gpus_2_starts_two_ranks_itself():
     assert j["n_gpus"] == 2 and j["steps"] == 3 and j["warmup"] == 1 and j["scaling"] == "weak"
     assert j["data"].startswith("stub")
     assert abs(j["value"] - 2 * 4 * 8 * 3 / (j["ms_per_step"] * 3e-3)) / j["value"] < 1e-3
+    codes = np.load(tmp_path / "codes.npy")
+    assert codes.dtype == np.float32 and codes.shape == (8, 4, 16)      # [frames][rank 0's batch][16]
     # a mismatch between --gpus and the launched world is an error, not a silent 1-GPU run
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--stub-engine", "--backend", "gloo"],
                          env=dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=120)
