@@ -70,6 +70,44 @@ int64_t voc_synthesize_batch_max_samples(void* v, const int32_t* n_tokens, int U
 float voc_last_batch_ms(void* v);
 int voc_last_batch_chunks(void* v);
 
+/* Streaming chunk walk: the walk of voc_synthesize_batch fed frame by frame, for many utterances ("streams", e.g. one per slot of
+ * the frame loop) at once.  voc_stream_create(voc, max_streams) -> NULL on failure; free the stream object before its vocoder
+ * handle.  Every stream starts empty; voc_stream_reset starts a new utterance in it (dropping an unfinished one).
+ *
+ * voc_stream_push: n entries; entry i gives stream streams[i] (each stream at most once per call) n_new[i] >= 0 more frames --
+ * codes holds the entries' new frames concatenated, [sum n_new][16] -- and finish[i] != 0 ends its utterance (finish may be NULL:
+ * none ends).  Entry i's samples land in out[offsets[i] .. offsets[i+1]) (offsets has n + 1 entries); out_capacity samples of out
+ * are the caller's, voc_stream_push_max_samples() returns how many the same push hands out (<0: the push is invalid).
+ *  - Bits: per stream, the samples of all pushes from a reset to its finish push, joined, are voc_synthesize_f32 (push_f32) /
+ *    voc_synthesize (push) of all its frames, bit for bit, however the frames were split across pushes and whatever other
+ *    streams shared the calls.  On the split arithmetic (voc_set_exact_fp32(0)) a push in which an activation leaves the fp16
+ *    range is redone exact, like one voc_synthesize_batch call -- the samples of earlier pushes stay as they were handed out, so
+ *    the joined result can then differ from a whole-utterance call; on the exact path it never does.
+ *  - Latency: after a push that does not finish a stream, that stream has handed out every sample no later chunk can change:
+ *    the walk assembled so far minus its last 16 * samples_per_token samples (the next chunk's cross-fade), nothing before 64
+ *    frames.  A full chunk_tokens chunk is decoded in the push that completes it; the tail chunk(s) -- the reference's
+ *    redundant short chunk, the plain append of a chunk shorter than the overlap -- in the finish push, which hands out all the
+ *    rest.  A stream that finishes with 0 frames gives 0 samples.
+ *  - Batching: the chunks that become decodable in one push are decoded together across its streams, max_batch per call and
+ *    one decode length per call (voc_synthesize_batch's grouping); a push that completes no chunk decodes nothing.  The
+ *    unfinished tail of every stream stays on the device; placement, cross-fade, the int16 rule and the packing run there.
+ *  - Errors (<0): a bad stream index or one named twice, n_new < 0, a push to a finished stream without a reset, out_capacity
+ *    below what the push hands out.  Nothing is written to out and no stream changes: the same push can be retried.
+ *  - Threads: one caller thread at a time per vocoder handle and its stream objects; entry points bind the thread to the
+ *    handle's device. */
+void* voc_stream_create(void* voc, int max_streams);
+void voc_stream_free(void* s);
+int voc_stream_reset(void* s, int stream);
+int64_t voc_stream_push_max_samples(void* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish);
+int voc_stream_push(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                    int16_t* out, int64_t out_capacity, int64_t* offsets);
+int voc_stream_push_f32(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                        float* out, int64_t out_capacity, int64_t* offsets);
+/* the last push: decode calls, chunks decoded, GPU milliseconds of its decodes and placement */
+int voc_stream_last_decodes(void* s);
+int voc_stream_last_chunks(void* s);
+float voc_stream_last_ms(void* s);
+
 /* Arithmetic of the convolutions.  Default (0): split precision -- every f32 operand (weights once at load,
  * activations in the producing kernel's epilogue) is carried as two fp16 terms (22 mantissa bits) and each
  * product costs three fp16 MFMAs with f32 accumulation.  1: the exact-f32 MFMA (v_mfma_f32_32x32x2_f32)

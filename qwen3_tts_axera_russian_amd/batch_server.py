@@ -14,6 +14,18 @@ utterance.  Extension of the wire protocol, same conventions (little-endian, u32
 
 One process per GPU (HIP_VISIBLE_DEVICES), like the other servers.
 
+Streamed reply (the request carries "stream": true): the same synthesis, handed out while the frame loop runs, as records on
+the same connection (in the order they are ready; `utt` indexes the request's utterances):
+
+              i32 1, i32 utt, i32 n, i16[n]                  PCM of utterance utt: the next n samples
+              i32 2, i32 utt, i32 n_frames, i32[n_frames*16]  utterance utt has ended: all its codes
+              i32 -1                                          the request is done   (i32 -2: error, as above)
+
+Every check_every frames the new frames of every live slot go to the vocoder's streaming chunk walk (voc_stream_push, on one
+worker thread with one vocoder workgroup per compute unit, as in --pipeline); a full 64-frame chunk is decoded as soon as its
+frames exist, and all samples no later cross-fade can change go out at once.  An utterance's PCM records joined, and its codes,
+are bit for bit what the unstreamed reply carries.
+
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
 vocoder then launches one persistent workgroup per compute unit (voc_set_max_workgroups(-1)), which leaves the frame loop's
@@ -63,6 +75,8 @@ class BatchSynthesisServer:
             raise RuntimeError(f"voc_load failed: {vocoder_path}")
         self.pipeline = bool(pipeline)
         self._pool = None
+        self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
+        self._vstream = None           # streaming chunk walk: one stream per slot of the frame loop
         if self.pipeline:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=1)       # ONE worker: the vocoder handle has one caller, replies keep their order
@@ -82,8 +96,8 @@ class BatchSynthesisServer:
             raise RuntimeError("no tokenizer configured (--tokenizer DIR) and the request has no token_ids")
         return [self.tokenizer.encode(t, add_special_tokens=False) for t in msg.get("texts", [])]
 
-    def generate(self, token_ids, max_tokens=None):
-        """The frame loop of a request -> list of codes int32 [n_frames][16] per utterance."""
+    def _queue(self, token_ids, max_tokens):
+        """A request's prefixes -> (prefixes, n_text, max_tokens, order): order[k] = request index of the queue's k-th utterance."""
         B = len(token_ids)
         if B == 0:
             raise ValueError("a request needs at least one utterance")
@@ -94,10 +108,16 @@ class BatchSynthesisServer:
         if max(p.shape[0] for p in prefixes) + max_tokens > self.n_ctx:
             raise ValueError("prefix + max_tokens exceed n_ctx")
         n_text = [len(ids) for ids in token_ids]
+        # more utterances than slots: continuous batching -- a finished utterance's slot takes the next one of the request
+        # (q3e_refill), longest expected first (3 frames per text token, llamacpp_talker_server.py:174)
+        order = sorted(range(B), key=lambda i: -n_text[i]) if B > self.max_batch else list(range(B))
+        return prefixes, n_text, max_tokens, order
+
+    def generate(self, token_ids, max_tokens=None):
+        """The frame loop of a request -> list of codes int32 [n_frames][16] per utterance."""
+        prefixes, n_text, max_tokens, order = self._queue(token_ids, max_tokens)
+        B = len(token_ids)
         if B > self.max_batch:
-            # more utterances than slots: continuous batching -- a finished utterance's slot takes the next one of the
-            # request (q3e_refill), longest expected first (3 frames per text token, llamacpp_talker_server.py:174)
-            order = sorted(range(B), key=lambda i: -n_text[i])
             got = self.eng.generate_queue([prefixes[i] for i in order], [n_text[i] for i in order], max_tokens)
             per_utt = [None] * B
             for k, i in enumerate(order):
@@ -132,6 +152,131 @@ class BatchSynthesisServer:
     def synthesize(self, token_ids, max_tokens=None):
         """-> list of (codes int32 [n_frames][16], pcm int16) per utterance."""
         return self.vocode(self.generate(token_ids, max_tokens))
+
+    def _push(self, conn, state, resets, entries):
+        """Worker side of a streamed request: start the refilled slots' streams, push every live slot's new frames to the
+        streaming chunk walk, send the PCM that became final and the end records.  entries: (slot, utt, new frames,
+        finished, all codes of the utterance when finished)."""
+        if state["failed"]:
+            return
+        try:
+            lib, vs = self._lib, self._vstream
+            for b in resets:
+                if lib.voc_stream_reset(vs, b) != 0:
+                    raise RuntimeError("voc_stream_reset failed")
+            if entries:
+                streams = np.array([e[0] for e in entries], np.int32)
+                n_new = np.array([e[2].shape[0] for e in entries], np.int32)
+                fin = np.array([int(e[3]) for e in entries], np.int32)
+                cat = np.ascontiguousarray(np.concatenate([e[2] for e in entries], axis=0), dtype=np.int64).reshape(-1, 16)
+                args = (vs, len(entries), hiplib.iptr(streams))
+                cap = int(lib.voc_stream_push_max_samples(*args, hiplib.iptr(n_new), hiplib.iptr(fin)))
+                if cap < 0:
+                    raise RuntimeError("voc_stream_push: invalid push")
+                buf = np.empty(max(cap, 1), np.int16)
+                off = np.zeros(len(entries) + 1, np.int64)
+                if lib.voc_stream_push(*args, cat.ctypes.data_as(hiplib.i64p), hiplib.iptr(n_new), hiplib.iptr(fin),
+                                       buf.ctypes.data_as(hiplib.i16p), cap, off.ctypes.data_as(hiplib.i64p)) != 0:
+                    raise RuntimeError("voc_stream_push failed")
+                out = []
+                for k, (_, utt, _, finished, codes) in enumerate(entries):
+                    if off[k + 1] > off[k]:
+                        out.append(pack_stream_audio(utt, buf[off[k]:off[k + 1]]))
+                    if finished:
+                        out.append(pack_stream_end(utt, codes))
+                if out:
+                    conn.sendall(b"".join(out))
+        except Exception as e:
+            state["failed"] = True
+            print(f"Error: {e}")
+            try:
+                conn.sendall(P.pack_sentinel(P.SENTINEL_ERROR))
+            except OSError:
+                pass
+
+    def _close_stream(self, conn, state, t0):
+        """Worker side: the last record of a streamed request, then its connection closes."""
+        try:
+            if not state["failed"]:
+                conn.sendall(P.pack_sentinel(P.SENTINEL_DONE))
+                print(f"  {state['n']} utterances, {state['frames']} frames streamed in {time.time() - t0:.3f}s")
+        except OSError:
+            pass
+        finally:
+            conn.close()
+
+    def synthesize_stream(self, conn, token_ids, max_tokens=None, t0=None):
+        """A streamed request: the frame loop runs here (generate_queue), the vocoder's pushes and every write to `conn` on the
+        worker thread, at most one push in flight.  -> the worker's future of the request's last record (it closes conn)."""
+        t0 = time.time() if t0 is None else t0
+        state = {"failed": False, "n": len(token_ids), "frames": 0}
+        if self._pool is not None:
+            pool = self._pool
+        else:
+            if self._stream_pool is None:
+                from concurrent.futures import ThreadPoolExecutor
+                self._stream_pool = ThreadPoolExecutor(max_workers=1)
+            pool = self._stream_pool
+        fut = None
+        try:
+            prefixes, n_text, max_tokens, order = self._queue(token_ids, max_tokens)
+            if self._vstream is None:
+                self._vstream = self._lib.voc_stream_create(self.voc, self.max_batch)
+                if not self._vstream:
+                    raise RuntimeError("voc_stream_create failed")
+            if self._pool is None:
+                self._lib.voc_set_max_workgroups(-1)     # the pushes run beside the frame loop (restored when the request ends)
+            slot_utt = [None] * self.max_batch           # queue index each slot's stream holds
+            pushed = [0] * self.max_batch
+
+            def on_frames(codes, per, owner, ended):
+                nonlocal fut
+                resets, entries = [], []
+                for b, o in enumerate(owner):
+                    if o is None:
+                        continue
+                    if slot_utt[b] != o:
+                        slot_utt[b], pushed[b] = o, 0
+                        resets.append(b)
+                    n, fin = int(per[b]), b in ended
+                    if n > pushed[b] or fin:
+                        new = np.ascontiguousarray(codes[pushed[b]:n, b, :])
+                        whole = np.ascontiguousarray(codes[:n, b, :], dtype=np.int32) if fin else None
+                        entries.append((b, order[o], new, fin, whole))
+                        pushed[b] = n
+                        if fin:
+                            state["frames"] += n
+                if not (resets or entries):
+                    return
+                if fut is not None:
+                    fut.result()                         # one push in flight
+                if state["failed"]:
+                    raise RuntimeError("streamed request failed on the vocoder side")
+                fut = pool.submit(self._push, conn, state, resets, entries)
+
+            self.eng.generate_queue([prefixes[i] for i in order], [n_text[i] for i in order], max_tokens, on_frames=on_frames)
+        except Exception as e:
+            if fut is not None:
+                fut.result()
+            if not state["failed"]:
+                print(f"Error: {e}")
+                state["failed"] = True
+                pool.submit(self._send_error, conn)
+        finally:
+            if fut is not None:
+                fut.result()
+            last = pool.submit(self._close_stream, conn, state, t0)
+            if self._pool is None:
+                last.result()
+                self._lib.voc_set_max_workgroups(0)
+        return last
+
+    @staticmethod
+    def _send_error(conn):
+        try:
+            conn.sendall(P.pack_sentinel(P.SENTINEL_ERROR))
+        except OSError:
+            pass
 
     def _finish(self, conn, cs, t0):
         """Worker side of the pipelined mode: vocode, reply on the request's own connection, close it."""
@@ -170,6 +315,12 @@ class BatchSynthesisServer:
                 if msg is None:
                     continue
                 t0 = time.time()
+                if msg.get("stream"):
+                    # streamed reply: the worker writes every record and closes the connection
+                    ids = self._token_ids(msg)
+                    handed_over = True
+                    self.synthesize_stream(conn, ids, msg.get("max_tokens"), t0)
+                    continue
                 if self._pool is not None:
                     # pipelined: this request's vocoder runs on the worker while the loop accepts and generates the next one
                     cs = self.generate(self._token_ids(msg), msg.get("max_tokens"))
@@ -189,9 +340,10 @@ class BatchSynthesisServer:
             finally:
                 if not handed_over:
                     conn.close()
-        if self._pool is not None:
-            self._pool.shutdown(wait=True)       # replies in flight go out before the socket disappears
-            self._pool = None
+        for pool in (self._pool, self._stream_pool):
+            if pool is not None:
+                pool.shutdown(wait=True)         # replies in flight go out before the socket disappears
+        self._pool = self._stream_pool = None
         sock.close()
         if os.path.exists(self.socket_path):
             os.unlink(self.socket_path)
@@ -201,6 +353,8 @@ class BatchSynthesisServer:
         if self._pool is not None:
             self._pool.shutdown(wait=True)
             self._pool = None
+        self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
+        self._vstream = None           # streaming chunk walk: one stream per slot of the frame loop
         if self.pipeline:
             self._lib.voc_set_max_workgroups(0)
         if self.voc:
@@ -209,9 +363,11 @@ class BatchSynthesisServer:
         self.eng.destroy()
 
 
-def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None) -> bytes:
+def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False) -> bytes:
     import json
     msg = {"language": language}
+    if stream:
+        msg["stream"] = True
     if token_ids is not None:
         msg["token_ids"] = [[int(t) for t in ids] for ids in token_ids]
     else:
@@ -247,6 +403,58 @@ def read_batch_reply(conn):
         pcm = np.frombuffer(P.recv_exact(conn, ns * 2), dtype="<i2")
         out.append((codes, pcm))
     return out
+
+
+REC_AUDIO, REC_END = 1, 2
+
+
+def pack_stream_audio(utt, pcm) -> bytes:
+    a = np.ascontiguousarray(pcm, dtype="<i2").reshape(-1)
+    return struct.pack("<iii", REC_AUDIO, int(utt), a.shape[0]) + a.tobytes()
+
+
+def pack_stream_end(utt, codes) -> bytes:
+    c = np.ascontiguousarray(codes, dtype="<i4").reshape(-1, 16)
+    return struct.pack("<iii", REC_END, int(utt), c.shape[0]) + c.tobytes()
+
+
+def read_stream_record(conn):
+    """One record of a streamed reply -> ("audio", utt, pcm int16) / ("end", utt, codes [n][16] int32) / ("done",); raises on
+    the error sentinel, an unknown record or a short read."""
+    def exact(n):
+        b = P.recv_exact(conn, n)
+        if len(b) < n:
+            raise RuntimeError("connection closed inside a streamed reply")
+        return b
+    (kind,) = struct.unpack("<i", exact(4))
+    if kind == P.SENTINEL_DONE:
+        return ("done",)
+    if kind == P.SENTINEL_ERROR:
+        raise RuntimeError(f"server error ({kind})")
+    if kind not in (REC_AUDIO, REC_END):
+        raise RuntimeError(f"unknown record {kind} in a streamed reply")
+    utt, n = struct.unpack("<ii", exact(8))
+    if n < 0:
+        raise RuntimeError(f"record of {n} entries")
+    if kind == REC_AUDIO:
+        return ("audio", utt, np.frombuffer(exact(n * 2), dtype="<i2"))
+    return ("end", utt, np.frombuffer(exact(n * 16 * 4), dtype="<i4").reshape(n, 16))
+
+
+def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None):
+    """Client side of the streamed request: yields its records as they arrive -- ("audio", utt, pcm) and ("end", utt, codes)
+    -- until the request is done; raises on the error sentinel."""
+    s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
+    s.connect(socket_path)
+    try:
+        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True))
+        while True:
+            rec = read_stream_record(s)
+            if rec[0] == "done":
+                return
+            yield rec
+    finally:
+        s.close()
 
 
 def synthesize_batch(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None):

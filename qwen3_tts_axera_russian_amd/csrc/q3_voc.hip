@@ -1260,12 +1260,49 @@ __global__ void __launch_bounds__(256) voc_place_blend_kernel(const float* __res
 }
 
 // np.clip(audio * 32767, -32768, 32767).astype(np.int16) (vocoder_server.py:175): float32 product, truncation toward zero
+__device__ __forceinline__ int16_t voc_int16(float x) {
+    float v = __fmul_rn(x, 32767.0f);
+    v = v < -32768.0f ? -32768.0f : (v > 32767.0f ? 32767.0f : v);
+    return (int16_t)v;
+}
+__device__ __forceinline__ void voc_store(float* y, long long i, float x) { y[i] = x; }
+__device__ __forceinline__ void voc_store(int16_t* y, long long i, float x) { y[i] = voc_int16(x); }
+
 __global__ void __launch_bounds__(256) voc_to_int16_kernel(const float* __restrict__ x, int16_t* __restrict__ y, long long n) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    float v = __fmul_rn(x[i], 32767.0f);
-    v = v < -32768.0f ? -32768.0f : (v > 32767.0f ? 32767.0f : v);
-    y[i] = (int16_t)v;
+    y[i] = voc_int16(x[i]);
+}
+
+// ---------------------------------------------------------------------------
+// Streaming chunk walk (voc_stream_*): between pushes each stream keeps only the last OV assembled samples -- the ones the
+// next chunk's cross-fade may still change -- in its slot of `tail` ([max_streams][OV] on the device).  A push lays every
+// stream it touches out as one window of its work buffer: the kept tail first (load), then the chunks the push decodes,
+// placed by voc_place_copy/blend at window coordinates; emit hands [0, n_out) of the window to the caller's packed output
+// (f32, or the int16 rule) and keeps [n_out, n_out + tail_out) as the stream's new tail.
+// ---------------------------------------------------------------------------
+struct StreamWin {
+    long long win;      // first sample of the stream's window in the work buffer
+    long long out;      // first sample of its part of the packed output
+    long long n_out;    // samples handed out
+    int stream;         // tail slot
+    int tail_in;        // samples of the kept tail loaded to the window's front (0 or OV)
+    int tail_out;       // samples kept after the handed-out ones (0 when the stream finishes, else OV)
+};
+
+__global__ void __launch_bounds__(256) voc_stream_load_kernel(const float* __restrict__ tail, int OV, const StreamWin* __restrict__ w,
+                                                              float* __restrict__ work) {
+    const StreamWin p = w[blockIdx.y];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < p.tail_in; i += gridDim.x * 256) work[p.win + i] = tail[(size_t)p.stream * OV + i];
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) voc_stream_emit_kernel(const float* __restrict__ work, const StreamWin* __restrict__ w,
+                                                              float* __restrict__ tail, int OV, T* __restrict__ out) {
+    const StreamWin p = w[blockIdx.y];
+    for (long long i = blockIdx.x * 256 + threadIdx.x; i < p.n_out; i += gridDim.x * 256) voc_store(out, p.out + i, work[p.win + i]);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < p.tail_out; i += gridDim.x * 256)
+        tail[(size_t)p.stream * OV + i] = work[p.win + p.n_out + i];
 }
 
 struct VocOp {
@@ -2199,6 +2236,82 @@ size_t plan_walk(const Voc* v, int u, int n, long long base, std::vector<WalkChu
     return have;
 }
 
+extern "C++" {   // (the walk helpers sit inside the extern "C" block of the entry points)
+// Decodes the chunks of a walk max_batch at a time -- one decode length per call: full chunks first, then the tail chunks by
+// length (voc_decode_frames) -- and places each into `wave` at its dst (voc_place_copy/blend).  chunk_codes(c) -> the first frame
+// of walk[c].  restore() runs before each attempt: a call in which an activation leaves the fp16 range on the split path has the
+// whole walk redone on the exact-fp32 path (voc_decode's rule), so restore() must put back whatever the blends read of `wave`.
+// -> 0 and *n_calls decodes (of the attempt that stands), GPU time between v->e0 and v->e1; <0 on error.
+template <class ChunkCodes, class Restore>
+int decode_walk(Voc* v, const std::vector<WalkChunk>& walk, ChunkCodes chunk_codes, float* wave, Restore restore, int* n_calls) {
+    const int CH = v->chunk, OV = 16 * v->upsample;
+    std::vector<int> order(walk.size()), frames(walk.size());
+    for (size_t i = 0; i < walk.size(); i++) order[i] = (int)i, frames[i] = voc_decode_frames(v, walk[i].len);
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return frames[x] > frames[y]; });
+    std::vector<int64_t> padded((size_t)v->max_batch * CH * 16);
+    std::vector<ChunkPlace> place(v->max_batch);
+    bool redo_exact = false;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        Q3_HIP(hipEventRecord(v->e0, v->s), -1);
+        if (restore()) return -1;
+        int calls = 0;
+        for (size_t c0 = 0; c0 < walk.size();) {
+            const int T = frames[order[c0]];
+            int B = 0;
+            while (c0 + B < walk.size() && B < v->max_batch && frames[order[c0 + B]] == T) B++;
+            std::fill(padded.begin(), padded.begin() + (size_t)B * T * 16, 0);
+            for (int b = 0; b < B; b++) {
+                const WalkChunk& w = walk[order[c0 + b]];
+                memcpy(padded.data() + (size_t)b * T * 16, chunk_codes(order[c0 + b]), sizeof(int64_t) * 16 * w.len);
+                place[b] = {b, (int)w.cl, w.head, w.dst};
+            }
+            Q3_HIP(hipMemcpyAsync(v->d_codes, padded.data(), sizeof(int64_t) * 16 * (size_t)T * B, hipMemcpyHostToDevice, v->s), -1);
+            Q3_HIP(hipMemcpyAsync(v->d_place, place.data(), sizeof(ChunkPlace) * B, hipMemcpyHostToDevice, v->s), -1);
+            float* res = nullptr;
+            long LL = 0;
+            if (voc_run(v, B, &res, -1, nullptr, &LL, nullptr, redo_exact, T)) return -1;
+            for (int b = 0; b < B; b++)
+                if ((long)place[b].len > LL) {
+                    Q3_LOG("vocoder chunk walk: a decode of %d frames yields %ld samples, fewer than the %d kept", T, LL, place[b].len);
+                    return -1;
+                }
+            const int pitch = (int)pitch4(LL);
+            hipLaunchKernelGGL(voc_place_copy_kernel, dim3(64, B), dim3(256), 0, v->s, res, pitch, v->d_place, wave);
+            hipLaunchKernelGGL(voc_place_blend_kernel, dim3(32, B), dim3(256), 0, v->s, res, pitch, v->d_place, wave, OV);
+            Q3_HIP(hipGetLastError(), -1);
+            Q3_HIP(hipStreamSynchronize(v->s), -1);   // the staging vectors are reused by the next batch
+            c0 += B;
+            calls++;
+        }
+        Q3_HIP(hipEventRecord(v->e1, v->s), -1);
+        int ovf = 0;
+        if (g_voc_split && !redo_exact) Q3_HIP(hipMemcpyAsync(&ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
+        Q3_HIP(hipStreamSynchronize(v->s), -1);
+        *n_calls = calls;
+        if (!ovf) break;
+        // an activation beyond the fp16 range: the whole walk is redone on the exact-fp32 path
+        if (!v->warned_ovf) Q3_LOG("vocoder: activation outside the fp16 range, decoding this request with the exact-fp32 path");
+        v->warned_ovf = true;
+        Q3_HIP(hipMemsetAsync(v->d_ovf, 0, sizeof(int), v->s), -1);
+        redo_exact = true;
+    }
+    return 0;
+}
+
+// grows a device buffer to hold n elements of T (contents not kept)
+template <typename T>
+int grow(T** p, size_t* cap, size_t n) {
+    if (n <= *cap) return 0;
+    if (*p) hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    Q3_HIP(hipMalloc((void**)p, sizeof(T) * n), -1);
+    *cap = n;
+    return 0;
+}
+
+}  // extern "C++"
+
 int synth_batch(Voc* v, const int64_t* codes, const int32_t* n_tokens, int U, int64_t* offsets, bool want16, void* out, int64_t cap) {
     voc_bind(v);
     if (!v || !codes || !n_tokens || !offsets || !out || U <= 0) return -1;
@@ -2226,78 +2339,208 @@ int synth_batch(Voc* v, const int64_t* codes, const int32_t* n_tokens, int U, in
         Q3_LOG("voc_synthesize_batch: %lld samples do not fit the caller's buffer of %lld", total, (long long)cap);
         return -1;
     }
-    if ((size_t)total > v->wave_cap) {
-        if (v->d_wave) hipFree(v->d_wave);
-        v->d_wave = nullptr;
-        v->wave_cap = 0;
-        Q3_HIP(hipMalloc((void**)&v->d_wave, sizeof(float) * (size_t)total), -1);
-        v->wave_cap = (size_t)total;
-    }
-    const int OV = 16 * v->upsample;
-    // chunks of one decode length run together: full chunks first, then the tail chunks by length (voc_decode_frames)
-    std::vector<int> order(walk.size()), frames(walk.size());
-    for (size_t i = 0; i < walk.size(); i++) order[i] = (int)i, frames[i] = voc_decode_frames(v, walk[i].len);
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return frames[x] > frames[y]; });
-    std::vector<int64_t> padded((size_t)v->max_batch * CH * 16);
-    std::vector<ChunkPlace> place(v->max_batch);
-    bool redo_exact = false;
-    for (int attempt = 0; attempt < 2; attempt++) {
-        Q3_HIP(hipEventRecord(v->e0, v->s), -1);
-        for (size_t c0 = 0; c0 < walk.size();) {
-            const int T = frames[order[c0]];
-            int B = 0;
-            while (c0 + B < walk.size() && B < v->max_batch && frames[order[c0 + B]] == T) B++;
-            std::fill(padded.begin(), padded.begin() + (size_t)B * T * 16, 0);
-            for (int b = 0; b < B; b++) {
-                const WalkChunk& w = walk[order[c0 + b]];
-                memcpy(padded.data() + (size_t)b * T * 16, codes + code_off[w.utt] + (size_t)w.start * 16, sizeof(int64_t) * 16 * w.len);
-                place[b] = {b, (int)w.cl, w.head, w.dst};
-            }
-            Q3_HIP(hipMemcpyAsync(v->d_codes, padded.data(), sizeof(int64_t) * 16 * (size_t)T * B, hipMemcpyHostToDevice, v->s), -1);
-            Q3_HIP(hipMemcpyAsync(v->d_place, place.data(), sizeof(ChunkPlace) * B, hipMemcpyHostToDevice, v->s), -1);
-            float* res = nullptr;
-            long LL = 0;
-            if (voc_run(v, B, &res, -1, nullptr, &LL, nullptr, redo_exact, T)) return -1;
-            for (int b = 0; b < B; b++)
-                if ((long)place[b].len > LL) {
-                    Q3_LOG("voc_synthesize_batch: a decode of %d frames yields %ld samples, fewer than the %d kept", T, LL, place[b].len);
-                    return -1;
-                }
-            const int pitch = (int)pitch4(LL);
-            hipLaunchKernelGGL(voc_place_copy_kernel, dim3(64, B), dim3(256), 0, v->s, res, pitch, v->d_place, v->d_wave);
-            hipLaunchKernelGGL(voc_place_blend_kernel, dim3(32, B), dim3(256), 0, v->s, res, pitch, v->d_place, v->d_wave, OV);
-            Q3_HIP(hipGetLastError(), -1);
-            Q3_HIP(hipStreamSynchronize(v->s), -1);   // the staging vectors are reused by the next batch
-            c0 += B;
-        }
-        Q3_HIP(hipEventRecord(v->e1, v->s), -1);
-        int ovf = 0;
-        if (g_voc_split && !redo_exact) Q3_HIP(hipMemcpyAsync(&ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
-        Q3_HIP(hipStreamSynchronize(v->s), -1);
-        if (!ovf) break;
-        // an activation beyond the fp16 range: the whole request is redone on the exact-fp32 path (voc_decode's rule)
-        if (!v->warned_ovf) Q3_LOG("vocoder: activation outside the fp16 range, decoding this request with the exact-fp32 path");
-        v->warned_ovf = true;
-        Q3_HIP(hipMemsetAsync(v->d_ovf, 0, sizeof(int), v->s), -1);
-        redo_exact = true;
-    }
+    if (grow(&v->d_wave, &v->wave_cap, (size_t)total)) return -1;
+    int calls = 0;
+    if (decode_walk(v, walk, [&](int c) { return codes + code_off[walk[c].utt] + (size_t)walk[c].start * 16; }, v->d_wave,
+                    [] { return 0; }, &calls))
+        return -1;
     hipEventElapsedTime(&v->batch_ms, v->e0, v->e1);
     v->batch_chunks = (int)walk.size();
     if (!want16) {
         Q3_HIP(hipMemcpyAsync(out, v->d_wave, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, v->s), -1);
     } else {
-        if ((size_t)total > v->wave16_cap) {
-            if (v->d_wave16) hipFree(v->d_wave16);
-            v->d_wave16 = nullptr;
-            v->wave16_cap = 0;
-            Q3_HIP(hipMalloc((void**)&v->d_wave16, sizeof(int16_t) * (size_t)total), -1);
-            v->wave16_cap = (size_t)total;
-        }
+        if (grow(&v->d_wave16, &v->wave16_cap, (size_t)total)) return -1;
         hipLaunchKernelGGL(voc_to_int16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->s, v->d_wave, v->d_wave16, total);
         Q3_HIP(hipGetLastError(), -1);
         Q3_HIP(hipMemcpyAsync(out, v->d_wave16, sizeof(int16_t) * (size_t)total, hipMemcpyDeviceToHost, v->s), -1);
     }
     Q3_HIP(hipStreamSynchronize(v->s), -1);
+    return 0;
+}
+
+// ---- streaming chunk walk (voc_stream_*) ----
+struct StreamState {
+    int n_frames = 0;          // frames pushed since the reset
+    int n_chunks = 0;          // chunks of the walk decoded and placed
+    long long have = 0;        // samples the walk has assembled so far
+    long long emitted = 0;     // of which handed out (the rest, have - emitted <= OV, is the device tail)
+    bool finished = false;
+    int frame_base = 0;        // frames[0] is frame frame_base (earlier ones no future chunk reads)
+    std::vector<int64_t> frames;
+};
+
+struct VocStream {
+    Voc* v = nullptr;
+    int max_streams = 0;
+    std::vector<StreamState> st;
+    float* d_tail = nullptr;          // [max_streams][OV]
+    float* d_work = nullptr;          // the push's windows
+    size_t work_cap = 0;
+    float* d_out = nullptr;           // packed output of a push (f32)
+    int16_t* d_out16 = nullptr;       // (int16)
+    size_t out_cap = 0, out16_cap = 0;
+    StreamWin* d_win = nullptr;       // [max_streams]
+    int last_calls = 0, last_chunks = 0;
+    float last_ms = 0.f;
+};
+
+// What a push would do, worked out without touching the streams: the chunks it decodes (walk[].utt = entry index, dst in the
+// stream's own sample coordinates), and per entry the walk's new assembled length and the samples handed out.
+struct PushPlan {
+    std::vector<WalkChunk> walk;
+    std::vector<long long> have, n_out;
+    std::vector<int> n_chunks;
+};
+
+int plan_push(const VocStream* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish, PushPlan& p) {
+    const Voc* v = s->v;
+    const int CH = v->chunk;
+    const long long OV = 16LL * v->upsample;
+    if (n < 0 || (n > 0 && (!streams || !n_new))) return -1;
+    p.walk.clear();
+    p.have.assign(n, 0);
+    p.n_out.assign(n, 0);
+    p.n_chunks.assign(n, 0);
+    std::vector<char> seen(s->max_streams, 0);
+    std::vector<WalkChunk> full;
+    for (int i = 0; i < n; i++) {
+        const int k = streams[i];
+        if (k < 0 || k >= s->max_streams || seen[k] || n_new[i] < 0) {
+            Q3_LOG("voc_stream_push: entry %d: bad stream %d (or named twice) or %d new frames", i, k, n_new[i]);
+            return -1;
+        }
+        seen[k] = 1;
+        const StreamState& t = s->st[k];
+        if (t.finished) {
+            Q3_LOG("voc_stream_push: stream %d has finished (voc_stream_reset starts the next utterance)", k);
+            return -1;
+        }
+        const bool fin = finish && finish[i];
+        const int N = t.n_frames + n_new[i];
+        if (N > CH && CH <= 32) {
+            Q3_LOG("voc_stream_push: chunk_tokens=%d is too short for the 16-frame overlap walk (need > 32)", CH);
+            return -1;
+        }
+        p.have[i] = t.have;
+        p.n_chunks[i] = t.n_chunks;
+        if (N > 0) {
+            // the walk of the N frames so far; its first chunks are final once all their frames are here (a full chunk whatever
+            // follows), the rest only when the utterance ends
+            full.clear();
+            const long long total = (long long)plan_walk(v, i, N, 0, full);
+            int c = t.n_chunks;
+            for (; c < (int)full.size() && (fin || full[c].start + CH <= N); c++) {
+                p.walk.push_back(full[c]);
+                p.have[i] = full[c].dst + (long long)full[c].cl;
+            }
+            p.n_chunks[i] = c;
+            if (fin && p.have[i] != total) return -1;
+        }
+        p.n_out[i] = fin ? p.have[i] - t.emitted : std::max(0LL, p.have[i] - OV - t.emitted);
+    }
+    return 0;
+}
+
+int stream_push(VocStream* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                bool want16, void* out, int64_t cap, int64_t* offsets) {
+    if (!s || !offsets) return -1;
+    Voc* v = s->v;
+    voc_bind(v);
+    const int CH = v->chunk, OV = 16 * v->upsample;
+    PushPlan p;
+    if (plan_push(s, n, streams, n_new, finish, p)) return -1;
+    long long total = 0;
+    for (int i = 0; i < n; i++) offsets[i] = total, total += p.n_out[i];
+    offsets[n] = total;
+    if (total > cap || (total > 0 && !out)) {
+        Q3_LOG("voc_stream_push: %lld samples do not fit the caller's buffer of %lld", total, (long long)cap);
+        return -1;
+    }
+    // one window per stream that decodes a chunk or hands samples out: [kept tail | this push's samples]
+    std::vector<StreamWin> win;
+    std::vector<long long> win_of(n, -1);
+    long long work = 0;
+    for (int i = 0; i < n; i++) {
+        const StreamState& t = s->st[streams[i]];
+        const bool fin = finish && finish[i];
+        if (p.n_chunks[i] == t.n_chunks && p.n_out[i] == 0) continue;
+        const long long size = p.have[i] - t.emitted;
+        win_of[i] = work;
+        win.push_back({work, offsets[i], p.n_out[i], streams[i], (int)(t.have - t.emitted), fin ? 0 : OV});
+        if (!fin && size - p.n_out[i] != OV) return -1;
+        work += size;
+    }
+    for (WalkChunk& c : p.walk) {
+        const StreamState& t = s->st[streams[c.utt]];
+        if (c.dst < t.emitted || c.dst + (long long)c.cl > p.have[c.utt]) return -1;   // (plan_walk's rules keep every chunk inside)
+        c.dst = win_of[c.utt] + (c.dst - t.emitted);
+    }
+    size_t need = 0;
+    for (int i = 0; i < n; i++) need += (size_t)n_new[i];
+    if (need > 0 && !codes) return -1;
+    // the push is valid: the streams take their new frames
+    size_t coff = 0;
+    for (int i = 0; i < n; i++) {
+        StreamState& t = s->st[streams[i]];
+        t.frames.insert(t.frames.end(), codes + coff, codes + coff + (size_t)n_new[i] * 16);
+        t.n_frames += n_new[i];
+        coff += (size_t)n_new[i] * 16;
+    }
+    s->last_calls = 0;
+    s->last_chunks = (int)p.walk.size();
+    s->last_ms = 0.f;
+    if (!win.empty()) {
+        if (grow(&s->d_work, &s->work_cap, (size_t)work)) return -1;
+        Q3_HIP(hipMemcpyAsync(s->d_win, win.data(), sizeof(StreamWin) * win.size(), hipMemcpyHostToDevice, v->s), -1);
+        const dim3 grid(64, (unsigned)win.size());
+        auto load = [&]() -> int {
+            hipLaunchKernelGGL(voc_stream_load_kernel, grid, dim3(256), 0, v->s, s->d_tail, OV, s->d_win, s->d_work);
+            Q3_HIP(hipGetLastError(), -1);
+            return 0;
+        };
+        if (p.walk.empty()) {
+            if (load()) return -1;
+        } else {
+            auto chunk_codes = [&](int c) {
+                const WalkChunk& w = p.walk[c];
+                const StreamState& t = s->st[streams[w.utt]];
+                return t.frames.data() + (size_t)(w.start - t.frame_base) * 16;
+            };
+            if (decode_walk(v, p.walk, chunk_codes, s->d_work, load, &s->last_calls)) return -1;
+            hipEventElapsedTime(&s->last_ms, v->e0, v->e1);
+        }
+        if (total > 0 && want16) {
+            if (grow(&s->d_out16, &s->out16_cap, (size_t)total)) return -1;
+            hipLaunchKernelGGL(voc_stream_emit_kernel<int16_t>, grid, dim3(256), 0, v->s, s->d_work, s->d_win, s->d_tail, OV, s->d_out16);
+        } else if (total > 0) {
+            if (grow(&s->d_out, &s->out_cap, (size_t)total)) return -1;
+            hipLaunchKernelGGL(voc_stream_emit_kernel<float>, grid, dim3(256), 0, v->s, s->d_work, s->d_win, s->d_tail, OV, s->d_out);
+        } else {
+            hipLaunchKernelGGL(voc_stream_emit_kernel<float>, grid, dim3(256), 0, v->s, s->d_work, s->d_win, s->d_tail, OV, (float*)nullptr);
+        }
+        Q3_HIP(hipGetLastError(), -1);
+        if (total > 0)
+            Q3_HIP(hipMemcpyAsync(out, want16 ? (void*)s->d_out16 : (void*)s->d_out, (want16 ? sizeof(int16_t) : sizeof(float)) * (size_t)total,
+                                  hipMemcpyDeviceToHost, v->s), -1);
+        Q3_HIP(hipStreamSynchronize(v->s), -1);
+    }
+    for (int i = 0; i < n; i++) {
+        StreamState& t = s->st[streams[i]];
+        t.have = p.have[i];
+        t.emitted += p.n_out[i];
+        t.n_chunks = p.n_chunks[i];
+        if (finish && finish[i]) {
+            t.finished = true;
+            std::vector<int64_t>().swap(t.frames);
+            continue;
+        }
+        // the next chunk of the walk starts at frame n_chunks * (CH - 16): earlier frames are never read again
+        const int keep_from = t.n_chunks * (CH - 16);
+        if (keep_from > t.frame_base) {
+            t.frames.erase(t.frames.begin(), t.frames.begin() + (size_t)(keep_from - t.frame_base) * 16);
+            t.frame_base = keep_from;
+        }
+    }
     return 0;
 }
 }  // namespace
@@ -2319,6 +2562,64 @@ int voc_synthesize_batch(void* vv, const int64_t* codes, const int32_t* n_tokens
                          int64_t* offsets) {
     return synth_batch((Voc*)vv, codes, n_tokens, U, offsets, true, out, out_capacity);
 }
+
+void* voc_stream_create(void* vv, int max_streams) {
+    Voc* v = (Voc*)vv;
+    if (!v || max_streams <= 0) return nullptr;
+    voc_bind(v);
+    VocStream* s = new VocStream;
+    s->v = v;
+    s->max_streams = max_streams;
+    s->st.resize(max_streams);
+    const size_t OV = (size_t)16 * v->upsample;
+    if (hipMalloc((void**)&s->d_tail, sizeof(float) * OV * max_streams) != hipSuccess ||
+        hipMalloc((void**)&s->d_win, sizeof(StreamWin) * max_streams) != hipSuccess) {
+        Q3_LOG("voc_stream_create: device allocation failed");
+        voc_stream_free(s);
+        return nullptr;
+    }
+    return s;
+}
+
+void voc_stream_free(void* ss) {
+    VocStream* s = (VocStream*)ss;
+    if (!s) return;
+    voc_bind(s->v);
+    hipStreamSynchronize(s->v->s);
+    for (void* p : {(void*)s->d_tail, (void*)s->d_work, (void*)s->d_out, (void*)s->d_out16, (void*)s->d_win})
+        if (p) hipFree(p);
+    delete s;
+}
+
+int voc_stream_reset(void* ss, int stream) {
+    VocStream* s = (VocStream*)ss;
+    if (!s || stream < 0 || stream >= s->max_streams) return -1;
+    s->st[stream] = StreamState();
+    return 0;
+}
+
+int64_t voc_stream_push_max_samples(void* ss, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish) {
+    VocStream* s = (VocStream*)ss;
+    PushPlan p;
+    if (!s || plan_push(s, n, streams, n_new, finish, p)) return -1;
+    int64_t t = 0;
+    for (int i = 0; i < n; i++) t += p.n_out[i];
+    return t;
+}
+
+int voc_stream_push(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                    int16_t* out, int64_t out_capacity, int64_t* offsets) {
+    return stream_push((VocStream*)s, n, streams, codes, n_new, finish, true, out, out_capacity, offsets);
+}
+
+int voc_stream_push_f32(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                        float* out, int64_t out_capacity, int64_t* offsets) {
+    return stream_push((VocStream*)s, n, streams, codes, n_new, finish, false, out, out_capacity, offsets);
+}
+
+int voc_stream_last_decodes(void* s) { return s ? ((VocStream*)s)->last_calls : -1; }
+int voc_stream_last_chunks(void* s) { return s ? ((VocStream*)s)->last_chunks : -1; }
+float voc_stream_last_ms(void* s) { return s ? ((VocStream*)s)->last_ms : -1.f; }
 
 float voc_last_batch_ms(void* vv) { return vv ? ((Voc*)vv)->batch_ms : -1.f; }
 int voc_last_batch_chunks(void* vv) { return vv ? ((Voc*)vv)->batch_chunks : 0; }

@@ -102,11 +102,15 @@ class FrameEngine:
         if rc != 0:
             raise RuntimeError(f"q3e_refill failed: {rc}")
 
-    def generate_queue(self, prefixes, n_text, max_frames, ignore_eos=False, check_every=8, on_done=None):
+    def generate_queue(self, prefixes, n_text, max_frames, ignore_eos=False, check_every=8, on_done=None, on_frames=None):
         """Continuous batching over a queue of utterances: the first max_batch of them start together; every
         `check_every` frames the finished slots hand over their codes and take the next utterance of the queue
         (q3e_refill), so the frame loop never steps a batch of mostly finished rows.  -> list of int32 [frames][16] in
-        queue order.  on_done(index, codes) is called as each utterance finishes (e.g. to hand it to the vocoder)."""
+        queue order.  on_done(index, codes) is called as each utterance finishes (e.g. to hand it to the vocoder).
+        on_frames(codes, per, owner, ended) is called at every check, before the finished slots are handed over and
+        refilled: codes[f][slot][16] and per[slot] as codes() returns them, owner[slot] = queue index of the utterance in
+        the slot (None: the slot is idle), ended = the slots whose utterance has ended at this check (e.g. to stream its
+        frames to the vocoder as they come)."""
         n = len(prefixes)
         assert n == len(n_text) and n > 0
         B = min(self.max_batch, n)
@@ -119,11 +123,16 @@ class FrameEngine:
             done, per = self.done()
             # an utterance that used its whole frame budget without an EOS has ended too (q3e_get_done reports it)
             fin = [b for b in range(B) if owner[b] is not None and (done[b] or per[b] >= max_frames)]
+            codes = None
+            if on_frames is not None:
+                codes, _ = self.codes()
+                on_frames(codes, per, list(owner), fin)
             if not fin:
                 if ran == 0:
                     raise RuntimeError("generate_queue: the engine ran no frame and no utterance finished")
                 continue
-            codes, _ = self.codes()
+            if codes is None:
+                codes, _ = self.codes()
             for b in fin:
                 res = np.ascontiguousarray(codes[:int(per[b]), b, :])
                 out[owner[b]] = res

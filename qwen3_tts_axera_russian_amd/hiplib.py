@@ -99,6 +99,15 @@ def load(path: str | None = None):
     _sig(lib, "voc_synthesize_batch_max_samples", ctypes.c_int64, [c_void_p, i32p, c_int])
     _sig(lib, "voc_last_batch_ms", c_float, [c_void_p])
     _sig(lib, "voc_last_batch_chunks", c_int, [c_void_p])
+    _sig(lib, "voc_stream_create", c_void_p, [c_void_p, c_int])
+    _sig(lib, "voc_stream_free", None, [c_void_p])
+    _sig(lib, "voc_stream_reset", c_int, [c_void_p, c_int])
+    _sig(lib, "voc_stream_push_max_samples", ctypes.c_int64, [c_void_p, c_int, i32p, i32p, i32p])
+    _sig(lib, "voc_stream_push", c_int, [c_void_p, c_int, i32p, i64p, i32p, i32p, i16p, ctypes.c_int64, i64p_])
+    _sig(lib, "voc_stream_push_f32", c_int, [c_void_p, c_int, i32p, i64p, i32p, i32p, f32p, ctypes.c_int64, i64p_])
+    _sig(lib, "voc_stream_last_decodes", c_int, [c_void_p])
+    _sig(lib, "voc_stream_last_chunks", c_int, [c_void_p])
+    _sig(lib, "voc_stream_last_ms", c_float, [c_void_p])
     # include/qwen3tts_text.h
     _sig(lib, "tfe_load", c_void_p, [c_char_p, c_char_p, c_int])
     _sig(lib, "tfe_free", None, [c_void_p])
