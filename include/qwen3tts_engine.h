@@ -91,6 +91,52 @@ int q3e_get_codes(void* e, int32_t* out, int max_out_frames, int32_t* n_frames_p
 int q3e_get_done(void* e, int32_t* done /*[B]*/, int32_t* frames /*[B] or NULL*/);
 int q3e_refill(void* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text);
 
+/* Per-slot mode: utterances of different requests in one running frame loop.
+ *
+ * q3e_open: begin a batch of B slots that are all idle (ended, no frame, no prefix).  Idle slots still step through
+ * the captured frame with the others, on zeroed caches and activations.  Every row then reads its own frame budget,
+ * sampling settings and draw stream from a device array (one entry per slot), and the frame's dynamic LDS is sized for
+ * the sampler's sort path, so admitting an utterance never recaptures the graph.  ignore_eos as for q3e_start.
+ *
+ * q3e_admit: put n new utterances into the given slots (as q3e_refill: the slots' counters, token history and codes
+ * column restart; prefix / n_rows / n_text as for q3e_start, in the order of `slots`), each with its parameter block.
+ * Every utterance is prefilled in a pass of its own, so its prefix sums do not depend on what is admitted beside it.
+ * Requires 1 <= max_frames <= the max_frames of q3e_create and n_rows + max_frames <= n_ctx per utterance, finite
+ * temperatures >= 0 and top_p in (0, 1].
+ *
+ * Seed contract: the utterance with index `utt` of a request with seed s draws from the stream mix(s, utt), mix = the
+ * splitmix64 step (z = s + 0x9E3779B97F4A7C15 * (utt + 1), then the splitmix64 finaliser); every draw is keyed by
+ * (stream, frame, group) -- group 0 the talker, 1 + g the code predictor's group g -- and NOT by the slot.  The same
+ * utterance with the same seed therefore samples the same codes in any slot, beside any other utterances, after any
+ * number of earlier admissions.  (q3e_start / q3e_refill keep their own derivation, with the row in the key.)
+ *
+ * q3e_release: mark n slots ended (cancellation); their rows go idle at the next step.
+ *
+ * A per-slot batch may step for the life of a server: no device or host counter grows with the number of steps (an ended
+ * row's frame counter stops just past the codes array).
+ *
+ * In this mode q3e_get_done reports an utterance as ended once it has emitted its own budget, q3e_run never steps
+ * past the largest budget a live slot has left and returns early once every admitted utterance has ended, and
+ * q3e_get_codes returns rows up to the frame count of the slot admitted longest ago (column b = slot b's utterance
+ * from its own start).  q3e_refill and q3e_set_forced_codes refuse a per-slot batch; q3e_start leaves the mode.
+ * 0 ok / <0 error. */
+typedef struct q3e_slot_params {
+    int32_t max_frames;     /* frame budget of the utterance (the server's per-request max_tokens) */
+    float temperature;      /* talker: <= 1e-6 arg-max, else top-k / temperature / top-p draws */
+    int32_t top_k;          /* <= 0 or >= the vocabulary: every entry */
+    float top_p;            /* (0, 1]; 1 keeps every entry */
+    float cp_temperature;   /* code predictor: temperature and top-k */
+    int32_t cp_top_k;
+    uint64_t seed;          /* the request's seed ... */
+    int32_t utt;            /* ... and the utterance's index in its request: the draw stream is mix(seed, utt) */
+    int32_t reserved;       /* 0 */
+} q3e_slot_params;
+
+int q3e_open(void* e, int B, int ignore_eos);
+int q3e_admit(void* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+              const q3e_slot_params* params);
+int q3e_release(void* e, int n, const int32_t* slots);
+
 /* Talker hidden state of every utterance after the last executed step ([B][hidden]). */
 int q3e_get_hidden(void* e, float* out);
 

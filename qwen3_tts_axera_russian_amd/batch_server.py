@@ -26,6 +26,21 @@ worker thread with one vocoder workgroup per compute unit, as in --pipeline); a 
 frames exist, and all samples no later cross-fade can change go out at once.  An utterance's PCM records joined, and its codes,
 are bit for bit what the unstreamed reply carries.
 
+`--concurrent`: utterances of different requests share ONE running frame loop.  An accept thread reads and checks every
+request (a malformed one, or one that would take the queue past max_queue utterances, gets -2 at once) and queues its
+utterances; the engine thread -- the only caller of the engine -- opens max_batch slots once (q3e_open) and every check_every
+frames admits queued utterances into free slots (FIFO across requests; within a request longest first, as above), each with
+its own frame budget (the request's max_tokens), sampling settings and seed (q3e_admit), runs the loop, polls which slots
+ended, and releases the slots of a client that went away; one vocoder worker -- the only caller of the vocoder -- streams the
+new frames of streamed requests (one voc_stream per slot, reset on admission) and answers an unstreamed request with one
+voc_synthesize_batch over its utterances once its last one ended.  Requests may carry the keys "temperature", "top_k", "top_p",
+"cp_temperature", "cp_top_k" and "seed" (a missing key takes the server's value; the other modes keep the server's settings
+and ignore them).  Determinism contract: a request's reply, codes and PCM, depends only on the request, its seed and the
+server's configuration -- not on what else is in flight nor on which slots it gets.  The loop always steps max_batch rows (a
+row's f32 sums depend on the row count of the pass), every utterance is prefilled in a pass of its own (the ragged prefill's
+tiles depend on the rows of the pass), and utterance u of a request with seed s draws from the stream mix(s, u), keyed by
+(stream, frame, group) and not by the slot (include/qwen3tts_engine.h).
+
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
 vocoder then launches one persistent workgroup per compute unit (voc_set_max_workgroups(-1)), which leaves the frame loop's
@@ -34,17 +49,21 @@ workgroups room beside it (244 -> 209 ms per 32 x 64-frame 
 from __future__ import annotations
 
 import argparse
+import collections
+import dataclasses
 import os
+import select
 import signal
 import socket
 import struct
+import threading
 import time
 
 import numpy as np
 
 from . import hiplib
 from . import protocol as P
-from .engine import FrameEngine
+from .engine import FrameEngine, SlotParams
 from .frontend import TextFrontEnd
 from .weights import ModelConfig, read_pack
 
@@ -52,8 +71,21 @@ from .weights import ModelConfig, read_pack
 class BatchSynthesisServer:
     def __init__(self, model_path, vocoder_path, socket_path="/tmp/qwen3_batch.sock", max_batch=32, n_ctx=512,
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
-                 install_signal_handlers=True, max_request=None, pipeline=False):
+                 install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
+                 cp_top_k=None, check_every=8, send_timeout=30.0):
+        if concurrent and pipeline:
+            raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens = socket_path, max_batch, max_tokens
+        cp_top_k = top_k if cp_top_k is None else cp_top_k
+        # the settings a request of --concurrent inherits for every key it leaves out
+        self.defaults = SlotParams(max_frames=max_tokens, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
+                                   cp_temperature=float(cp_temperature), cp_top_k=int(cp_top_k), seed=int(seed))
+        self.defaults.check(max_tokens)
+        self.concurrent = bool(concurrent)
+        self.max_queue = int(max_queue) if max_queue else 16 * max_batch
+        self.check_every = int(check_every)
+        self.send_timeout = float(send_timeout)
+        self.sched = None
         # utterances one request may queue (the server is single-threaded: an unbounded request holds it indefinitely)
         self.max_request = int(max_request) if max_request else 8 * max_batch
         meta, t = read_pack(model_path)
@@ -67,7 +99,7 @@ class BatchSynthesisServer:
             self.tokenizer = ByteLevelBPE.from_dir(tokenizer)
         self.eng = FrameEngine(model_path, max_batch=max_batch, n_ctx=n_ctx, max_frames=max_tokens)
         self.eng.set_pad_embed(self.front.tts_pad_embed)
-        self.eng.set_sampling(temperature, top_k, 0.95, cp_temperature, top_k, seed)
+        self.eng.set_sampling(temperature, top_k, top_p, cp_temperature, cp_top_k, seed)
         self.n_ctx = n_ctx
         self._lib = hiplib.load()
         self.voc = self._lib.voc_load(str(vocoder_path).encode(), 64, min(max_batch, 32))
@@ -278,6 +310,14 @@ class BatchSynthesisServer:
         except OSError:
             pass
 
+    def _prepare(self, msg):
+        """--concurrent, accept side: a request -> its utterances in queue order as (request index, prefix, n_text,
+        SlotParams); raises on anything malformed, before any of it is queued."""
+        ids = self._token_ids(msg)
+        base = request_slot_params(msg, self.defaults, self.max_tokens)
+        prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames)
+        return [(i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i)) for i in order]
+
     def _finish(self, conn, cs, t0):
         """Worker side of the pipelined mode: vocode, reply on the request's own connection, close it."""
         try:
@@ -298,9 +338,12 @@ class BatchSynthesisServer:
             os.unlink(self.socket_path)
         sock = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
         sock.bind(self.socket_path)
-        sock.listen(1)
+        sock.listen(128 if self.concurrent else 1)
         sock.settimeout(1.0)
         os.chmod(self.socket_path, 0o666)
+        if self.concurrent:
+            self._serve_concurrent(sock)
+            return
         print(f"Batch synthesis server listening on {self.socket_path} ({self.max_batch} slots; longer requests run through them by continuous batching)")
         while self._running:
             try:
@@ -348,6 +391,47 @@ class BatchSynthesisServer:
         if os.path.exists(self.socket_path):
             os.unlink(self.socket_path)
 
+    def _serve_concurrent(self, sock):
+        """--concurrent: this thread accepts and checks requests; the scheduler's engine thread and vocoder worker do the rest."""
+        if self._vstream is None:
+            self._vstream = self._lib.voc_stream_create(self.voc, self.max_batch)
+            if not self._vstream:
+                raise RuntimeError("voc_stream_create failed")
+        self._lib.voc_set_max_workgroups(-1)     # the vocoder runs beside the frame loop: one workgroup per CU
+        self.sched = ConcurrentScheduler(self.eng, self.max_batch, self.max_queue, self._prepare, self._finish, self._push,
+                                         self._close_stream, self._send_error, check_every=self.check_every,
+                                         send_timeout=self.send_timeout)
+        self.sched.start()
+        print(f"Batch synthesis server listening on {self.socket_path} (--concurrent: {self.max_batch} slots shared by every "
+              f"request, up to {self.max_queue} queued utterances)")
+        try:
+            while self._running and self.sched.alive:
+                try:
+                    conn, _ = sock.accept()
+                except socket.timeout:
+                    continue
+                except OSError:
+                    break
+                try:
+                    conn.settimeout(10.0)            # a client that never finishes its request cannot hold the accept thread
+                    msg = P.read_talker_request(conn)
+                    if msg is None:
+                        conn.close()
+                        continue
+                    conn.settimeout(None)
+                except Exception as e:
+                    print(f"Error: {e}")
+                    self._send_error(conn)
+                    conn.close()
+                    continue
+                self.sched.submit(conn, msg, time.time())
+        finally:
+            self.sched.stop()
+            self._lib.voc_set_max_workgroups(0)
+            sock.close()
+            if os.path.exists(self.socket_path):
+                os.unlink(self.socket_path)
+
     def close(self):
         self._running = False
         if self._pool is not None:
@@ -363,7 +447,240 @@ class BatchSynthesisServer:
         self.eng.destroy()
 
 
-def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False) -> bytes:
+class _Request:
+    """A request of --concurrent in flight: its connection and what has come back so far."""
+
+    def __init__(self, conn, items, stream, t0):
+        self.conn, self.stream, self.t0 = conn, bool(stream), t0
+        self.n = len(items)
+        self.left = self.n                      # utterances that have not ended
+        self.codes = [None] * self.n            # per request index
+        self.state = {"failed": False, "n": self.n, "frames": 0}   # the push worker's view (BatchSynthesisServer._push)
+        self.gone = False                       # the client went away or the request failed: its slots are released
+
+
+class ConcurrentScheduler:
+    """The engine and vocoder sides of `--concurrent` (module docstring).  `eng` has the FrameEngine surface open / admit /
+    release / run / done / codes; the callables are the server's: prepare(msg) -> [(request index, prefix, n_text,
+    SlotParams)] in queue order (raises on a malformed request), reply(conn, codes per utterance, t0) answers and closes an
+    unstreamed request, push(conn, state, resets, entries) and close_stream(conn, state, t0) stream records and end a streamed
+    one, send_error(conn) writes -2.  The engine thread is the only caller of `eng`, the one worker thread the only caller of
+    reply / push / close_stream.
+
+    A client is gone once it has closed its connection (POLLHUP); a client that only shuts down its sending side after the
+    request (shutdown(SHUT_WR)) still gets its reply.  Every write to a request's connection is bounded by send_timeout
+    seconds (SO_SNDTIMEO): a client that stays connected but stops reading fails its own request -- the writer's error marks
+    it failed, the engine then releases its slots -- instead of holding the one worker, and with it every other request."""
+
+    def __init__(self, eng, max_batch, max_queue, prepare, reply, push, close_stream, send_error, check_every=8,
+                 send_timeout=30.0):
+        from concurrent.futures import ThreadPoolExecutor
+        self.eng, self.B, self.max_queue, self.check_every = eng, int(max_batch), int(max_queue), int(check_every)
+        self._prepare, self._reply, self._push, self._close_stream, self._send_error = prepare, reply, push, close_stream, send_error
+        self._cv = threading.Condition()
+        self._queue = collections.deque()       # (request, (utt, prefix, n_text, params)) in admission order
+        self._running = False
+        self._pool = ThreadPoolExecutor(max_workers=1)
+        self._thread = None
+        self.alive = True                       # False once the engine thread has stopped on an error
+        self.frame_steps = 0                    # frame steps the engine has run
+        self.send_timeout = float(send_timeout)
+
+    # ---- accept side ----
+    def submit(self, conn, msg, t0=None):
+        """Check a request and queue its utterances, or answer -2 on its own connection and close it.  -> True if queued."""
+        sec = int(self.send_timeout)
+        conn.setsockopt(socket.SOL_SOCKET, socket.SO_SNDTIMEO,
+                        struct.pack("ll", sec, int(round((self.send_timeout - sec) * 1e6))))
+        try:
+            items = self._prepare(msg)
+        except Exception as e:
+            print(f"Error: {e}")
+            return self._refuse(conn)
+        with self._cv:
+            if not self.alive or len(self._queue) + len(items) > self.max_queue:
+                print(f"Error: queue full ({len(self._queue)} of {self.max_queue} utterances queued)" if self.alive else
+                      "Error: the engine has stopped")
+                return self._refuse(conn)
+            req = _Request(conn, items, msg.get("stream"), time.time() if t0 is None else t0)
+            self._queue.extend((req, it) for it in items)
+            self._cv.notify()
+        return True
+
+    def _refuse(self, conn):
+        self._send_error(conn)
+        conn.close()
+        return False
+
+    def start(self):
+        self._running = True
+        self._thread = threading.Thread(target=self._engine_main, name="q3-engine", daemon=True)
+        self._thread.start()
+
+    def stop(self):
+        with self._cv:
+            self._running = False
+            self._cv.notify()
+        if self._thread is not None:
+            self._thread.join()
+        self._pool.shutdown(wait=True)          # replies in flight go out before the server goes
+
+    # ---- engine side ----
+    @staticmethod
+    def _client_gone(req):
+        """The request failed on the writer's side, or its client closed the connection (hang-up; a half-close is not)."""
+        if req.state["failed"]:
+            return True
+        try:
+            p = select.poll()
+            p.register(req.conn.fileno(), select.POLLIN)
+            ev = p.poll(0)
+        except (OSError, ValueError):
+            return True
+        return bool(ev and ev[0][1] & (select.POLLHUP | select.POLLERR | select.POLLNVAL))
+
+    def _drop(self, req):
+        """Engine side: a request that is gone or failed -- its queued utterances are skipped, its connection closes (after
+        whatever the worker still has for it)."""
+        if not req.gone:
+            req.gone = True
+            self._pool.submit(req.conn.close)
+
+    def _engine_main(self):
+        owner = [None] * self.B                 # (request, utt) of each slot
+        try:
+            self._engine_loop(owner)
+        except Exception as e:
+            print(f"Error: the engine thread stopped: {e}")
+            with self._cv:
+                self.alive = False
+                pending = {id(r): r for r, _ in self._queue}
+                self._queue.clear()
+            pending.update({id(o[0]): o[0] for o in owner if o is not None})
+            for req in pending.values():
+                if not req.gone:
+                    req.gone = True
+                    self._pool.submit(self._refuse, req.conn)
+
+    def _engine_loop(self, owner):
+        eng, B = self.eng, self.B
+        eng.open(B)
+        pushed = [0] * B
+        pending_pushes = []
+        while True:
+            with self._cv:
+                while self._running and not self._queue and all(o is None for o in owner):
+                    self._cv.wait()            # nothing live, nothing queued: block (no spinning)
+                if not self._running:
+                    break
+                free = [b for b in range(B) if owner[b] is None]
+                take = []
+                while self._queue and len(take) < len(free):
+                    req, it = self._queue.popleft()
+                    if not req.gone:
+                        take.append((req, it))
+            for req in {id(r): r for r, _ in take}.values():   # a client that left while its request waited
+                if self._client_gone(req):
+                    self._drop(req)
+            take = [(r, it) for r, it in take if not r.gone]
+            if not take and all(o is None for o in owner):
+                continue                       # what was queued has left and nothing is live: back to waiting
+            resets = collections.defaultdict(list)
+            if take:
+                slots = free[:len(take)]
+                eng.admit(slots, [it[1] for _, it in take], [it[2] for _, it in take], [it[3] for _, it in take])
+                for b, (req, it) in zip(slots, take):
+                    owner[b] = (req, it[0])
+                    pushed[b] = 0
+                    if req.stream:
+                        resets[id(req)].append(b)
+            ran = eng.run(self.check_every)
+            self.frame_steps += ran
+            done, per = eng.done()
+            # clients that went away: their slots go idle now
+            live = {id(o[0]): o[0] for o in owner if o is not None}
+            for req in live.values():
+                if self._client_gone(req):
+                    self._drop(req)
+            gone = [b for b in range(B) if owner[b] is not None and owner[b][0].gone]
+            if gone:
+                eng.release(gone)
+                for b in gone:
+                    owner[b] = None
+            fin = [b for b in range(B) if owner[b] is not None and done[b]]
+            streamed = [b for b in range(B) if owner[b] is not None and owner[b][0].stream]
+            if not fin and not streamed:
+                if ran == 0 and not gone and not take:
+                    raise RuntimeError("the engine ran no frame and no utterance ended")
+                continue
+            codes, _ = eng.codes()
+            entries = collections.defaultdict(list)
+            for b in streamed:
+                req, utt = owner[b]
+                n, f = int(per[b]), b in fin
+                if n > pushed[b] or f:
+                    whole = np.ascontiguousarray(codes[:n, b, :], dtype=np.int32) if f else None
+                    entries[id(req)].append((b, utt, np.ascontiguousarray(codes[pushed[b]:n, b, :]), f, whole))
+                    pushed[b] = n
+                    if f:
+                        req.state["frames"] += n
+            for f_ in pending_pushes:                # at most one check's pushes in flight
+                f_.result()
+            pending_pushes = []
+            reqs = {id(owner[b][0]): owner[b][0] for b in streamed}
+            for key, req in reqs.items():
+                if entries[key] or resets[key]:
+                    pending_pushes.append(self._pool.submit(self._push, req.conn, req.state, resets[key], entries[key]))
+            for b in fin:
+                req, utt = owner[b]
+                owner[b] = None
+                req.codes[utt] = np.ascontiguousarray(codes[:int(per[b]), b, :], dtype=np.int32)
+                req.left -= 1
+                if req.left == 0:
+                    if req.stream:
+                        self._pool.submit(self._close_stream, req.conn, req.state, req.t0)
+                    else:
+                        self._pool.submit(self._reply, req.conn, req.codes, req.t0)
+        # shutting down: whatever is still in flight or queued gets -2
+        with self._cv:
+            rest = {id(r): r for r, _ in self._queue}
+            self._queue.clear()
+        rest.update({id(o[0]): o[0] for o in owner if o is not None})
+        for req in rest.values():
+            if not req.gone:
+                req.gone = True
+                self._pool.submit(self._refuse, req.conn)
+
+
+_PARAM_KEYS = ("temperature", "top_k", "top_p", "cp_temperature", "cp_top_k", "seed")   # request keys = SlotParams fields
+
+
+def request_slot_params(msg, defaults, max_tokens_cap):
+    """--concurrent: a request's sampling keys and max_tokens over the server's defaults -> SlotParams (utt 0); raises
+    ValueError on a value out of range or of the wrong type."""
+    kw = {}
+    for field in _PARAM_KEYS:
+        key = field
+        v = msg.get(key)
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{key} must be a number (got {v!r})")
+        if field in ("top_k", "cp_top_k", "seed") and not (isinstance(v, int) or float(v).is_integer()):
+            raise ValueError(f"{key} must be an integer (got {v!r})")
+        kw[field] = int(v) if field in ("top_k", "cp_top_k", "seed") else float(v)
+    mt = msg.get("max_tokens")
+    if mt is not None and (isinstance(mt, bool) or not isinstance(mt, int)):
+        raise ValueError(f"max_tokens must be an integer (got {mt!r})")
+    kw["max_frames"] = min(int(mt), max_tokens_cap) if mt else defaults.max_frames
+    p = dataclasses.replace(defaults, **kw)
+    p.check(max_tokens_cap)
+    return p
+
+
+def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False, temperature=None,
+                       top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None) -> bytes:
+    """The request of the batched protocol; the sampling keys (honoured by --concurrent) are sent only when given."""
     import json
     msg = {"language": language}
     if stream:
@@ -374,6 +691,10 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
         msg["texts"] = list(texts)
     if max_tokens:
         msg["max_tokens"] = int(max_tokens)
+    for key, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("cp_temperature", cp_temperature),
+                   ("cp_top_k", cp_top_k), ("seed", seed)):
+        if v is not None:
+            msg[key] = v
     raw = json.dumps(msg).encode()
     return struct.pack("<I", len(raw)) + raw
 
@@ -441,13 +762,13 @@ def read_stream_record(conn):
     return ("end", utt, np.frombuffer(exact(n * 16 * 4), dtype="<i4").reshape(n, 16))
 
 
-def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None):
+def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, **sampling):
     """Client side of the streamed request: yields its records as they arrive -- ("audio", utt, pcm) and ("end", utt, codes)
-    -- until the request is done; raises on the error sentinel."""
+    -- until the request is done; raises on the error sentinel.  sampling: the optional keys of pack_batch_request."""
     s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     s.connect(socket_path)
     try:
-        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True))
+        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True, **sampling))
         while True:
             rec = read_stream_record(s)
             if rec[0] == "done":
@@ -457,12 +778,12 @@ def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="r
         s.close()
 
 
-def synthesize_batch(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None):
-    """Client side of the batched request."""
+def synthesize_batch(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, **sampling):
+    """Client side of the batched request.  sampling: the optional keys of pack_batch_request."""
     s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     s.connect(socket_path)
     try:
-        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens))
+        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, **sampling))
         return read_batch_reply(s)
     finally:
         s.close()
@@ -481,11 +802,21 @@ def main():
     ap.add_argument("--top_k", type=int, default=50)
     ap.add_argument("--cp_temperature", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--top_p", type=float, default=0.95)
+    ap.add_argument("--cp_top_k", type=int, default=None, help="code predictor's top-k (default: --top_k)")
     ap.add_argument("--pipeline", action="store_true",
                     help="vocode request k on a worker thread while request k + 1 generates (one vocoder workgroup per CU)")
+    ap.add_argument("--concurrent", action="store_true",
+                    help="utterances of concurrent requests share one running frame loop (per-request sampling keys and seed)")
+    ap.add_argument("--max_queue", type=int, default=None, help="--concurrent: utterances that may wait (default 16 x max_batch)")
+    ap.add_argument("--check_every", type=int, default=8, help="--concurrent: frames between two admissions")
+    ap.add_argument("--send_timeout", type=float, default=30.0,
+                    help="--concurrent: seconds one write to a client may block before its request fails")
     a = ap.parse_args()
     srv = BatchSynthesisServer(a.model, a.vocoder, a.socket, a.max_batch, a.n_ctx, a.max_tokens, a.temperature, a.top_k,
-                               a.cp_temperature, a.tokenizer, a.seed, pipeline=a.pipeline)
+                               a.cp_temperature, a.tokenizer, a.seed, pipeline=a.pipeline, concurrent=a.concurrent,
+                               max_queue=a.max_queue, top_p=a.top_p, cp_top_k=a.cp_top_k, check_every=a.check_every,
+                               send_timeout=a.send_timeout)
     try:
         srv.serve()
     finally:

@@ -100,6 +100,7 @@ int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const C
         x.seed = io.seed;
         x.seed_ptr = io.seed_ptr;
         x.forced = io.forced;
+        x.slots = io.slots;
         if (g + 1 < G) {
             x.next_table = m.cp_emb[g];  // group g+1 embeds token g with CP table g (:134)
             x.h_out = w.h;

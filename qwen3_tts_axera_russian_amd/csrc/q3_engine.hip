@@ -7,7 +7,9 @@
 #include "../../include/qwen3tts_engine.h"
 #include "q3_cp.h"
 
+#include <algorithm>
 #include <chrono>
+#include <cmath>
 
 using namespace q3;
 
@@ -48,7 +50,23 @@ struct Engine {
     int n_chains = 1;
     hipStream_t cs[8] = {nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[8] = {nullptr};
+    // per-slot mode (q3e_open / q3e_admit / q3e_release): every row reads its own budget, sampling settings and draw
+    // stream from d_slots; the host keeps each slot's budget and the frame steps run since its admission (capped at
+    // max_frames: no host counter grows with the server's life)
+    bool slot_mode = false;
+    int graph_slots = -1;
+    SlotParams* d_slots = nullptr;          // [max_batch]
+    std::vector<int> h_budget, h_age;       // h_age[b] < 0: the slot holds no utterance
+    std::vector<char> h_live;               // admitted and neither released nor known to have ended
 };
+
+// splitmix64 finaliser of (seed + golden * k): the stream derivations of this file
+unsigned long long mix_seed(unsigned long long seed, unsigned long long k, unsigned long long golden) {
+    unsigned long long z = seed + golden * k;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
 
 int talker_tail(Engine* e, hipStream_t st, int row0, int R) {
     // final norm (+ CP seed copy) and codec head for rows row0..row0+R-1
@@ -111,6 +129,7 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     sa.seed = e->seed;
     sa.seed_ptr = e->d_seed;
     sa.forced = e->forced_on ? e->d_forced : nullptr;
+    sa.slots = e->slot_mode ? e->d_slots : nullptr;
     if (launch_talker_sample(st, sa)) return -1;
     CpFrameIO io;
     io.codes = e->d_codes;
@@ -126,6 +145,7 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     io.seed = e->seed ^ 0x5851F42D4C957F2Dull;
     io.seed_ptr = e->d_seed;   // (the group index separates the talker's and the code predictor's draws)
     io.forced = e->forced_on ? e->d_forced : nullptr;
+    io.slots = e->slot_mode ? e->d_slots : nullptr;
     if (cp_frame(st, m, e->wc, e->kv_c, R, io, row0, e->B)) return -1;
     RowMap rm;
     rm.slot_base = 0;        // row r of the batch owns KV slot r (no table: one dependent load less in front of every attention)
@@ -186,7 +206,7 @@ void q3e_free(void* ee) {
     work_free(e->wt);
     work_free(e->wc);
     void* ps[] = {e->d_tiles, e->d_slot, e->d_pos,  e->d_iota,   e->d_past,    e->d_npast, e->d_ntext, e->d_done,
-                  e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed};
+                  e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots};
     for (void* p : ps)
         if (p) hipFree(p);
     if (e->h_done) hipHostFree(e->h_done);
@@ -284,6 +304,10 @@ int q3e_set_forced_codes(void* ee, const int32_t* forced, int n_frames) {
     Engine* e = (Engine*)ee;
     if (!e) return -1;
     const bool on = forced != nullptr && n_frames > 0;
+    if (on && e->slot_mode) {
+        Q3_LOG("q3e_set_forced_codes: not for a per-slot batch (q3e_open)");
+        return -1;
+    }
     if (on) {
         if (e->B <= 0 || n_frames > e->max_frames) return -1;
         const size_t total = (size_t)e->max_frames * e->max_batch * 16;
@@ -394,6 +418,20 @@ static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, co
     return 0;
 }
 
+// A slot back to "just started" (q3e_refill, q3e_admit): counters, the emitted-token ring, the slot's column of the codes
+// array, its text length and positions (n_rows / n_text: host values that must live until the stream is synchronised)
+static int clear_slot(Engine* e, int b, const int32_t* n_rows, const int32_t* n_text) {
+    Q3_HIP(hipMemsetAsync(e->d_npast + b, 0, sizeof(int), e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_done + b, 0, sizeof(int), e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_nframes + b, 0, sizeof(int), e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_past + 32 * b, 0, sizeof(int) * 32, e->s), -1);
+    Q3_HIP(hipMemset2DAsync(e->d_codes + 16 * (size_t)b, sizeof(int) * 16 * (size_t)e->B, 0xff, sizeof(int) * 16, e->max_frames, e->s), -1);
+    Q3_HIP(hipMemcpyAsync(e->d_ntext + b, n_text, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
+    Q3_HIP(hipMemcpyAsync(e->d_pos0 + b, n_rows, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
+    Q3_HIP(hipMemcpyAsync(e->d_posdec + b, n_rows, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
+    return 0;
+}
+
 // codec head over rows 0..B-1 of the post-norm hidden (rows of running utterances give the logits they already have)
 static int head_all_rows(Engine* e) {
     const Model& m = *e->m;
@@ -430,6 +468,7 @@ int q3e_start(void* ee, int B, const float* prefix, const int32_t* n_rows, const
     e->cap_frames = max_frames;
     e->frames_run = 0;
     e->frames_hi = 0;
+    e->slot_mode = false;
     Q3_HIP(hipMemsetAsync(e->d_npast, 0, sizeof(int) * B, e->s), -1);
     Q3_HIP(hipMemsetAsync(e->d_done, 0, sizeof(int) * B, e->s), -1);
     Q3_HIP(hipMemsetAsync(e->d_nframes, 0, sizeof(int) * B, e->s), -1);
@@ -470,7 +509,12 @@ int q3e_run(void* ee, int n_frames) {
     if (!e || e->B <= 0 || n_frames <= 0) return -1;
     // never step past the frames the batch was started for (nor past the codes array): a further step would
     // have no frame to record into
-    const int room = (e->cap_frames < e->max_frames ? e->cap_frames : e->max_frames) - e->frames_run;
+    int room = (e->cap_frames < e->max_frames ? e->cap_frames : e->max_frames) - e->frames_run;
+    if (e->slot_mode) {   // the live slot with the most budget left
+        room = 0;
+        for (int b = 0; b < e->B; b++)
+            if (e->h_live[b]) room = std::max(room, e->h_budget[b] - e->h_age[b]);
+    }
     if (room <= 0) return 0;
     if (n_frames > room) n_frames = room;
     int done_frames = 0;
@@ -480,7 +524,8 @@ int q3e_run(void* ee, int n_frames) {
     // Q3_NO_GRAPH=1: eager launches (rocprofv3 --kernel-trace crashes on the graph replay)
     static const bool no_graph = getenv("Q3_NO_GRAPH") && atoi(getenv("Q3_NO_GRAPH")) != 0;
     const bool need_capture = !e->graph[0].e || e->graph_B != e->B || e->graph_ignore != e->ignore_eos ||
-                              e->graph_cap != e->cap_frames || e->graph_chains != nc;
+                              e->graph_cap != e->cap_frames || e->graph_chains != nc ||
+                              e->graph_slots != (int)e->slot_mode;
     if (no_graph) {
         for (; done_frames < n_frames; done_frames++)
             if (frame_eager(e)) return -1;
@@ -506,6 +551,7 @@ int q3e_run(void* ee, int n_frames) {
         e->graph_ignore = e->ignore_eos;
         e->graph_cap = e->cap_frames;
         e->graph_chains = nc;
+        e->graph_slots = (int)e->slot_mode;
     }
     const int check_every = 16;
     const auto th0 = std::chrono::steady_clock::now();
@@ -530,6 +576,11 @@ int q3e_run(void* ee, int n_frames) {
     Q3_HIP(hipEventRecord(e->ev1, e->s), -1);
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     hipEventElapsedTime(&e->last_run_ms, e->ev0, e->ev1);
+    if (e->slot_mode) {
+        for (int b = 0; b < e->B; b++)
+            if (e->h_age[b] >= 0) e->h_age[b] = std::min(e->h_age[b] + done_frames, e->max_frames);
+        return done_frames;
+    }
     e->frames_run += done_frames;
     e->frames_hi += done_frames;
     return done_frames;
@@ -543,6 +594,12 @@ int q3e_get_codes(void* ee, int32_t* out, int max_out_frames, int32_t* n_frames_
     Engine* e = (Engine*)ee;
     if (!e || !out || e->B <= 0) return -1;
     int nf = e->frames_hi < e->max_frames ? e->frames_hi : e->max_frames;
+    if (e->slot_mode) {   // up to the frames of the slot admitted first
+        int hi = 0;
+        for (int b = 0; b < e->B; b++)
+            hi = std::max(hi, e->h_age[b]);
+        nf = std::min(hi, e->max_frames);
+    }
     if (nf > max_out_frames) nf = max_out_frames;
     Q3_HIP(hipMemcpy(out, e->d_codes, sizeof(int) * 16 * (size_t)e->B * nf, hipMemcpyDeviceToHost), -1);
     if (n_frames_per_utt) {
@@ -560,7 +617,10 @@ int q3e_get_done(void* ee, int32_t* done, int32_t* frames) {
     // the device raises done[b] on the step AFTER the budget's last frame, a step q3e_run never takes: an utterance
     // that has emitted its whole budget has ended
     for (int b = 0; b < e->B; b++)
-        if (np[b] >= e->cap_frames) done[b] = 1;
+        if (np[b] >= (e->slot_mode ? e->h_budget[b] : e->cap_frames)) done[b] = 1;
+    if (e->slot_mode)
+        for (int b = 0; b < e->B; b++)
+            if (done[b]) e->h_live[b] = 0;
     if (frames) memcpy(frames, np.data(), sizeof(int) * e->B);
     return 0;
 }
@@ -570,6 +630,10 @@ int q3e_refill(void* ee, int n, const int32_t* slots, const float* prefix, const
     if (!e || e->B <= 0 || n <= 0 || n > e->B || !slots || !prefix || !n_rows || !n_text) return -1;
     if (e->forced_on) {
         Q3_LOG("q3e_refill: a teacher-forced batch cannot be refilled");
+        return -1;
+    }
+    if (e->slot_mode) {
+        Q3_LOG("q3e_refill: a per-slot batch (q3e_open) takes new utterances with q3e_admit");
         return -1;
     }
     std::vector<int> ids(slots, slots + n), seen(e->B, 0);
@@ -589,14 +653,7 @@ int q3e_refill(void* ee, int n, const int32_t* slots, const float* prefix, const
     // per-slot state back to "just started": counters, the emitted-token ring, the slot's column of the codes array
     for (int u = 0; u < n; u++) {
         const int b = ids[u];
-        Q3_HIP(hipMemsetAsync(e->d_npast + b, 0, sizeof(int), e->s), -1);
-        Q3_HIP(hipMemsetAsync(e->d_done + b, 0, sizeof(int), e->s), -1);
-        Q3_HIP(hipMemsetAsync(e->d_nframes + b, 0, sizeof(int), e->s), -1);
-        Q3_HIP(hipMemsetAsync(e->d_past + 32 * b, 0, sizeof(int) * 32, e->s), -1);
-        Q3_HIP(hipMemset2DAsync(e->d_codes + 16 * (size_t)b, sizeof(int) * 16 * (size_t)e->B, 0xff, sizeof(int) * 16, e->max_frames, e->s), -1);
-        Q3_HIP(hipMemcpyAsync(e->d_ntext + b, n_text + u, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
-        Q3_HIP(hipMemcpyAsync(e->d_pos0 + b, n_rows + u, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
-        Q3_HIP(hipMemcpyAsync(e->d_posdec + b, n_rows + u, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
+        if (clear_slot(e, b, n_rows + u, n_text + u)) return -1;
         // a fresh draw stream for the new occupant: the counters (frame, group) restart with the slot, so keeping the
         // request's seed would replay the previous occupant's uniforms
         unsigned long long z = e->req_seed + 0xD1B54A32D192ED03ull * ++e->n_refills;
@@ -613,6 +670,130 @@ int q3e_refill(void* ee, int n, const int32_t* slots, const float* prefix, const
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     hipEventElapsedTime(&e->last_prefill_ms, e->ev0, e->ev1);
     e->frames_run = 0;   // the new utterances have their whole frame budget; running ones stop at theirs on the device
+    return 0;
+}
+
+int q3e_open(void* ee, int B, int ignore_eos) {
+    Engine* e = (Engine*)ee;
+    if (!e || B <= 0 || B > e->max_batch) return -1;
+    const Model& m = *e->m;
+    const ModelCfg& c = m.cfg;
+    if (c.talker_vocab > 4096 || c.cp_vocab > 4096) {   // SAMPLE_SORT_CAP: every row may take the sort path
+        Q3_LOG("q3e_open: vocabularies of %d / %d are beyond the per-slot sampler", c.talker_vocab, c.cp_vocab);
+        return -1;
+    }
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    if (!e->d_slots) Q3_HIP(hipMalloc((void**)&e->d_slots, sizeof(SlotParams) * e->max_batch), -1);
+    e->B = B;
+    e->ignore_eos = ignore_eos ? 1 : 0;
+    e->cap_frames = e->max_frames;
+    e->frames_run = 0;
+    e->frames_hi = 0;
+    e->slot_mode = true;
+    e->h_budget.assign(B, 0);
+    e->h_age.assign(B, -1);
+    e->h_live.assign(B, 0);
+    if (e->forced_on) {
+        e->forced_on = false;
+        for (auto& g : e->graph) g.reset();
+    }
+    // idle rows step through the graph with everything else: they have ended (done), their frame counter sits at the end of
+    // the codes array (nothing is recorded), and they run at position 0 of zeroed caches and activations (finite values;
+    // rows are independent, so what an idle row computes never reaches another row)
+    Q3_HIP(hipMemsetAsync(e->d_npast, 0, sizeof(int) * B, e->s), -1);
+    Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_done, 1, B, e->s), -1);
+    Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_nframes, e->max_frames, B, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_past, 0, sizeof(int) * 32 * B, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_ntext, 0, sizeof(int) * B, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_pos0, 0, sizeof(int) * B, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_posdec, 0, sizeof(int) * B, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_lastrow, 0, sizeof(int) * B, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_codes, 0xff, sizeof(int) * 16 * (size_t)B * e->max_frames, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_slots, 0, sizeof(SlotParams) * e->max_batch, e->s), -1);
+    if (kv_zero(e->s, e->kv_t) || kv_zero(e->s, e->kv_c)) return -1;
+    if (work_zero(e->s, e->wt, c, c.talker_ffn, c.talker_vocab) || work_zero(e->s, e->wc, c, c.cp_ffn, c.cp_vocab)) return -1;
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    return 0;
+}
+
+int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+              const q3e_slot_params* params) {
+    Engine* e = (Engine*)ee;
+    if (!e || !e->slot_mode || n <= 0 || n > e->B || !slots || !prefix || !n_rows || !n_text || !params) {
+        if (e && !e->slot_mode) Q3_LOG("q3e_admit: the batch was not opened with q3e_open");
+        return -1;
+    }
+    std::vector<int> ids(slots, slots + n), seen(e->B, 0);
+    std::vector<SlotParams> sp(n);
+    for (int u = 0; u < n; u++) {
+        const int b = ids[u];
+        const q3e_slot_params& p = params[u];
+        if (b < 0 || b >= e->B || seen[b]++) {
+            Q3_LOG("q3e_admit: slot %d is out of range or listed twice (batch of %d)", b, e->B);
+            return -1;
+        }
+        if (p.max_frames <= 0 || p.max_frames > e->max_frames) {
+            Q3_LOG("q3e_admit: utterance %d: a budget of %d frames is outside 1..%d", u, p.max_frames, e->max_frames);
+            return -1;
+        }
+        if (n_rows[u] <= 0 || n_rows[u] > e->prefill_rows || n_rows[u] + p.max_frames > e->n_ctx) {
+            Q3_LOG("q3e_admit: utterance %d: %d prefix rows + %d frames do not fit n_ctx=%d", u, n_rows[u], p.max_frames, e->n_ctx);
+            return -1;
+        }
+        if (!(std::isfinite(p.temperature) && p.temperature >= 0.f) || !(std::isfinite(p.cp_temperature) && p.cp_temperature >= 0.f) ||
+            !(p.top_p > 0.f && p.top_p <= 1.f)) {
+            Q3_LOG("q3e_admit: utterance %d: temperatures must be finite and >= 0, top_p in (0, 1]", u);
+            return -1;
+        }
+        sp[u].max_frames = p.max_frames;
+        sp[u].t_temp = p.temperature;
+        sp[u].t_top_k = p.top_k;
+        sp[u].t_top_p = p.top_p;
+        sp[u].c_temp = p.cp_temperature;
+        sp[u].c_top_k = p.cp_top_k;
+        sp[u].seed = mix_seed(p.seed, (unsigned long long)(uint32_t)p.utt + 1ull, 0x9E3779B97F4A7C15ull);   // mix(seed, utt)
+        sp[u].no_row = 1;
+    }
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    Q3_HIP(hipEventRecord(e->ev0, e->s), -1);
+    for (int u = 0; u < n; u++) {
+        if (clear_slot(e, ids[u], n_rows + u, n_text + u)) return -1;
+        Q3_HIP(hipMemcpyAsync(e->d_slots + ids[u], &sp[u], sizeof(SlotParams), hipMemcpyHostToDevice, e->s), -1);
+    }
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    // one prefill per utterance: the ragged prefill's tiles follow the rows of its pass, so sharing a pass with another
+    // request's utterance would change this one's sums
+    const int H = e->m->cfg.hidden;
+    size_t row_off = 0;
+    for (int u = 0; u < n; u++) {
+        if (prefill_ids(e, 1, &ids[u], prefix + row_off * H, n_rows + u, e->B)) return -1;
+        row_off += n_rows[u];
+    }
+    if (head_all_rows(e)) return -1;
+    Q3_HIP(hipEventRecord(e->ev1, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    hipEventElapsedTime(&e->last_prefill_ms, e->ev0, e->ev1);
+    for (int u = 0; u < n; u++) {
+        e->h_budget[ids[u]] = sp[u].max_frames;
+        e->h_age[ids[u]] = 0;
+        e->h_live[ids[u]] = 1;
+    }
+    return 0;
+}
+
+int q3e_release(void* ee, int n, const int32_t* slots) {
+    Engine* e = (Engine*)ee;
+    if (!e || !e->slot_mode || n < 0 || (n > 0 && !slots)) return -1;
+    for (int u = 0; u < n; u++)
+        if (slots[u] < 0 || slots[u] >= e->B) {
+            Q3_LOG("q3e_release: slot %d is out of range (batch of %d)", slots[u], e->B);
+            return -1;
+        }
+    for (int u = 0; u < n; u++) {
+        Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->d_done + slots[u]), 1, 1, e->s), -1);
+        e->h_live[slots[u]] = 0;
+    }
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
     return 0;
 }
 

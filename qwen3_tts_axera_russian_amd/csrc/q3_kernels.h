@@ -111,6 +111,21 @@ int launch_gather_embed(hipStream_t s, const float* table, int V, int H, const i
                         const int* n_frames, int frame_cap, int col, float* h, float* ssq, int R, int row0 = 0,
                         int R_total = 0, const int* forced = nullptr, half_t* xh = nullptr, const float* gamma = nullptr);
 
+// Per-slot parameters of the frame loop (q3e_open / q3e_admit): one entry per row of the batch.  When a sampling kernel
+// gets a non-null `slots` array it reads the row's entry instead of its scalar fields (frame budget, temperature, top-k,
+// top-p, draw seed); one workgroup handles one row, so every branch these values pick stays uniform in the workgroup.
+struct SlotParams {
+    int max_frames = 0;            // frame budget: the row ends once it has emitted this many frames
+    float t_temp = 0.f;            // talker: temperature (<= 1e-6: arg-max), top-k, top-p
+    int t_top_k = 0;
+    float t_top_p = 1.f;
+    float c_temp = 0.f;            // code predictor: temperature, top-k
+    int c_top_k = 0;
+    unsigned long long seed = 0;   // the row's draw stream
+    int no_row = 1;                // 1: the draw key is (seed, frame, group), without the row index
+    int pad_ = 0;
+};
+
 // Talker sampling (llamacpp_talker_server.py:163-206, greedy form).
 struct TalkerSampleArgs {
     int tl_node = -1;  // diagnostic timeline build only: graph node index
@@ -139,6 +154,9 @@ struct TalkerSampleArgs {
     // teacher forcing (tests): same layout as `codes`; entries >= 0 replace the decision that is FED BACK
     // (ring of past ids, CP input, feedback sum) while `codes` still records what the device decided
     const int* forced = nullptr;
+    // per-slot mode (null: the scalar fields above): budget, temperature, top-k, top-p and draw key of row r come from
+    // slots[r]; the dynamic LDS is then sized for the sort path whatever the row asks for
+    const SlotParams* slots = nullptr;
 };
 int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a);
 
@@ -168,6 +186,7 @@ struct CpArgmaxArgs {
     unsigned long long seed = 0;
     const unsigned long long* seed_ptr = nullptr;  // device array [rows] overriding `seed` (one stream per slot)
     const int* forced = nullptr;                   // teacher forcing (tests), see TalkerSampleArgs
+    const SlotParams* slots = nullptr;             // per-slot mode: temperature, top-k, draw key of row r (see TalkerSampleArgs)
 };
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a);
 

@@ -1888,7 +1888,22 @@ __device__ int block_sample_topk(float* lg, int n, int top_k, float temperature,
     return chosen;
 }
 
-__global__ void talker_sample_kernel(TalkerSampleArgs a) {
+// The row's entry of the per-slot parameter array (q3e_admit writes it before the launch): a scalar load, see uniform_load.
+__device__ __forceinline__ SlotParams uniform_slot(const SlotParams* p, int r) {
+    static_assert(sizeof(SlotParams) % 4 == 0, "SlotParams is read as words");
+    constexpr int NW = (int)(sizeof(SlotParams) / 4);
+    const __attribute__((address_space(4))) int* q = (const __attribute__((address_space(4))) int*)(p + r);
+    int w[NW];
+#pragma unroll
+    for (int i = 0; i < NW; i++) w[i] = q[i];
+    SlotParams sp;
+    __builtin_memcpy(&sp, w, sizeof(sp));
+    return sp;
+}
+
+// SLOTS: per-slot mode -- budget, temperature, top-k, top-p and draw key of the row come from a.slots[r]
+template <bool SLOTS>
+__device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
     Q3_TL(42);
     __shared__ float sv[16];
     __shared__ int si[16];
@@ -1899,6 +1914,15 @@ __global__ void talker_sample_kernel(TalkerSampleArgs a) {
     const int np = uniform_load(a.n_past + r);
     const int nt = uniform_load(a.n_text + r);
     const bool was_done = uniform_load(a.done + r) != 0;
+    float temperature = a.temperature, top_p = a.top_p;
+    int top_k = a.top_k, max_frames = a.max_frames;
+    if constexpr (SLOTS) {
+        const SlotParams sp = uniform_slot(a.slots, r);
+        temperature = sp.t_temp;
+        top_p = sp.t_top_p;
+        top_k = sp.t_top_k;
+        max_frames = sp.max_frames;
+    }
     if (threadIdx.x == 0) nwin = np < 30 ? np : 30;
     if (threadIdx.x < 30 && threadIdx.x < np) {
         // last 30 emitted tokens (ring of 32)
@@ -1925,7 +1949,7 @@ __global__ void talker_sample_kernel(TalkerSampleArgs a) {
     extern __shared__ float slg[];   // [V] processed logits, only when sampling stochastically
     __shared__ float selv[64];
     __shared__ int seli[64];
-    const bool stochastic = a.temperature > 1e-6f;
+    const bool stochastic = temperature > 1e-6f;
     for (int v = threadIdx.x; v < a.V; v += blockDim.x) {
         float l = nan_as_inf(a.logits[(size_t)r * a.V + v]);
         if (v >= a.audio_vocab && v != a.eos) l = -1e10f;
@@ -1944,8 +1968,14 @@ __global__ void talker_sample_kernel(TalkerSampleArgs a) {
     }
     if (stochastic) {
         __syncthreads();
-        const float u = uniform01(a.seed_ptr ? a.seed_ptr[r] : a.seed, (unsigned)r, (unsigned)a.n_frames[r], 0u);
-        bidx = block_sample_topk(slg, a.V, a.top_k, a.temperature, a.top_p, u, sv, si, selv, seli);
+        float u;
+        if constexpr (SLOTS) {
+            const SlotParams sp = uniform_slot(a.slots, r);
+            u = uniform01(sp.seed, sp.no_row ? 0u : (unsigned)r, (unsigned)a.n_frames[r], 0u);
+        } else {
+            u = uniform01(a.seed_ptr ? a.seed_ptr[r] : a.seed, (unsigned)r, (unsigned)a.n_frames[r], 0u);
+        }
+        bidx = block_sample_topk(slg, a.V, top_k, temperature, top_p, u, sv, si, selv, seli);
     } else {
         block_argmax(best, bidx, sv, si);
         if (bidx >= a.V) bidx = a.eos;   // unreachable (the mask leaves finite entries); never index with an invalid winner
@@ -1953,9 +1983,11 @@ __global__ void talker_sample_kernel(TalkerSampleArgs a) {
     if (threadIdx.x == 0) {
         int code = bidx;
         if (force_eos && !a.ignore_eos) code = a.eos;
-        bool fin = was_done || code == a.eos || code >= a.audio_vocab || (a.max_frames > 0 && np >= a.max_frames);
+        bool fin = was_done || code == a.eos || code >= a.audio_vocab || (max_frames > 0 && np >= max_frames);
         const int f = a.n_frames[r];
-        a.n_frames[r] = f + 1;
+        // per-slot batches live as long as the server: an ended row's counter stops one past the codes array (frame_cap + 1,
+        // so the code predictor's frame f - 1 is past it too) instead of counting every step of the server's life
+        if (!SLOTS || !fin || f <= a.frame_cap) a.n_frames[r] = f + 1;
         const bool keep = f < a.frame_cap;     // a frame beyond the codes array is not recorded (q3e_run never asks for one)
         int* fc = a.codes + ((size_t)(keep ? f : 0) * RT + r) * 16;
         // teacher forcing (tests): the decision is recorded, the forced id is what the stream continues with
@@ -1975,17 +2007,29 @@ __global__ void talker_sample_kernel(TalkerSampleArgs a) {
         }
     }
 }
+__global__ void talker_sample_kernel(TalkerSampleArgs a) { talker_sample_row<false>(a); }
+__global__ void talker_sample_kernel_slots(TalkerSampleArgs a) { talker_sample_row<true>(a); }
+
+// per-slot mode: any row may take the sort path, so its LDS is reserved whatever the rows ask for (admitting a request
+// never changes the captured launch)
+static size_t sample_lds_bytes_slots(int n) { return (size_t)sample_sort_len(n) * 8; }
+
 int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a) {
     if (a.R <= 0) return 0;
+    if (a.slots && a.V > SAMPLE_SORT_CAP) {
+        Q3_LOG("talker_sample: a vocabulary of %d is beyond the per-slot sampler (sort cap %d)", a.V, SAMPLE_SORT_CAP);
+        return -1;
+    }
     if (a.temperature > 1e-6f && effective_top_k(a.top_k, a.V) > SAMPLE_SEL_CAP && a.V > SAMPLE_SORT_CAP) {
         Q3_LOG("talker_sample: top_k=%d over a vocabulary of %d is beyond the device sampler (sort cap %d)", a.top_k, a.V,
                SAMPLE_SORT_CAP);
         return -1;
     }
-    const size_t lds = sample_lds_bytes(a.V, a.top_k, a.temperature);
+    const size_t lds = a.slots ? sample_lds_bytes_slots(a.V) : sample_lds_bytes(a.V, a.top_k, a.temperature);
     TalkerSampleArgs a2 = a;
     a2.tl_node = tl_next_node();
-    hipLaunchKernelGGL(talker_sample_kernel, dim3(a.R), dim3(256), lds, s, a2);
+    if (a.slots) hipLaunchKernelGGL(talker_sample_kernel_slots, dim3(a.R), dim3(256), lds, s, a2);
+    else hipLaunchKernelGGL(talker_sample_kernel, dim3(a.R), dim3(256), lds, s, a2);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
 }
@@ -2031,10 +2075,16 @@ __device__ __forceinline__ void feedback_row(const int* codes, int r, const floa
 
 // One workgroup per row: the 2048 logits arrive as two float4 per thread (one round trip), one barrier
 // picks the winner, then the next embedding row is gathered (second round trip).
-__global__ void __launch_bounds__(256) cp_argmax_kernel(CpArgmaxArgs a) {
-    Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
-                  "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
-                  "s"(a.talker_emb), "s"(a.temperature), "s"(a.forced));
+template <bool SLOTS>
+__device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
+    if constexpr (SLOTS)
+        Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
+                      "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
+                      "s"(a.talker_emb), "s"(a.slots), "s"(a.forced));
+    else
+        Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
+                      "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
+                      "s"(a.talker_emb), "s"(a.temperature), "s"(a.forced));
     Q3_TL(43);
     __shared__ float sv[4];
     __shared__ int si[4];
@@ -2048,6 +2098,13 @@ __global__ void __launch_bounds__(256) cp_argmax_kernel(CpArgmaxArgs a) {
     if (tid < n4) l0 = lg[tid];
     if (tid + 256 < n4) l1 = lg[tid + 256];
     const int nf_r = uniform_load(a.n_frames + r);   // independent of the arg-max: a scalar load beside the logits' vector loads
+    float temperature = a.temperature;
+    int top_k = a.top_k;
+    if constexpr (SLOTS) {
+        const SlotParams sp = uniform_slot(a.slots, r);
+        temperature = sp.c_temp;
+        top_k = sp.c_top_k;
+    }
     Q3_PH(0);
     {
         const float e[8] = {nan_as_inf(l0.x), nan_as_inf(l0.y), nan_as_inf(l0.z), nan_as_inf(l0.w),
@@ -2094,7 +2151,7 @@ __global__ void __launch_bounds__(256) cp_argmax_kernel(CpArgmaxArgs a) {
             best = sv[i];
             bidx = si[i];
         }
-    if (a.temperature > 1e-6f) {   // code_predictor_server.py:87-92: top-k, softmax((l-max)/T), categorical draw
+    if (temperature > 1e-6f) {   // code_predictor_server.py:87-92: top-k, softmax((l-max)/T), categorical draw
         extern __shared__ float slg[];
         __shared__ float selv[64];
         __shared__ int seli[64];
@@ -2103,8 +2160,14 @@ __global__ void __launch_bounds__(256) cp_argmax_kernel(CpArgmaxArgs a) {
         __syncthreads();
         for (int v = tid; v < a.V; v += 256) slg[v] = nan_as_inf(a.logits[(size_t)r * a.V + v]);
         __syncthreads();
-        const float u = uniform01(a.seed_ptr ? a.seed_ptr[r] : a.seed, (unsigned)r, (unsigned)nf_r, 1u + (unsigned)a.group);
-        bidx = block_sample_topk(slg, a.V, a.top_k, a.temperature, 0.f, u, sv2, si2, selv, seli);
+        float u;
+        if constexpr (SLOTS) {
+            const SlotParams sp = uniform_slot(a.slots, r);
+            u = uniform01(sp.seed, sp.no_row ? 0u : (unsigned)r, (unsigned)nf_r, 1u + (unsigned)a.group);
+        } else {
+            u = uniform01(a.seed_ptr ? a.seed_ptr[r] : a.seed, (unsigned)r, (unsigned)nf_r, 1u + (unsigned)a.group);
+        }
+        bidx = block_sample_topk(slg, a.V, top_k, temperature, 0.f, u, sv2, si2, selv, seli);
     }
     if (bidx < 0 || bidx >= a.V) bidx = 0;   // every logit -inf: numpy's argmax answers 0; never gather with an invalid winner
     int f = nf_r - 1;
@@ -2126,17 +2189,25 @@ __global__ void __launch_bounds__(256) cp_argmax_kernel(CpArgmaxArgs a) {
         }
     }
 }
+__global__ void __launch_bounds__(256) cp_argmax_kernel(CpArgmaxArgs a) { cp_argmax_row<false>(a); }
+__global__ void __launch_bounds__(256) cp_argmax_kernel_slots(CpArgmaxArgs a) { cp_argmax_row<true>(a); }
+
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a) {
     if (a.R <= 0) return 0;
+    if (a.slots && a.V > SAMPLE_SORT_CAP) {
+        Q3_LOG("cp_argmax: a vocabulary of %d is beyond the per-slot sampler (sort cap %d)", a.V, SAMPLE_SORT_CAP);
+        return -1;
+    }
     if (a.temperature > 1e-6f && effective_top_k(a.top_k, a.V) > SAMPLE_SEL_CAP && a.V > SAMPLE_SORT_CAP) {
         Q3_LOG("cp_argmax: top_k=%d over a vocabulary of %d is beyond the device sampler (sort cap %d)", a.top_k, a.V,
                SAMPLE_SORT_CAP);
         return -1;
     }
-    const size_t lds = sample_lds_bytes(a.V, a.top_k, a.temperature);
+    const size_t lds = a.slots ? sample_lds_bytes_slots(a.V) : sample_lds_bytes(a.V, a.top_k, a.temperature);
     CpArgmaxArgs a2 = a;
     a2.tl_node = tl_next_node();
-    hipLaunchKernelGGL(cp_argmax_kernel, dim3(a.R), dim3(256), lds, s, a2);
+    if (a.slots) hipLaunchKernelGGL(cp_argmax_kernel_slots, dim3(a.R), dim3(256), lds, s, a2);
+    else hipLaunchKernelGGL(cp_argmax_kernel, dim3(a.R), dim3(256), lds, s, a2);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
 }

@@ -53,6 +53,7 @@ struct KVCache {
 };
 int kv_alloc(KVCache& kv, int n_layers, int n_slots, int n_kv, int n_ctx);
 void kv_free(KVCache& kv);
+int kv_zero(hipStream_t s, KVCache& kv);   // every slot's keys and values to 0 (asynchronous on s)
 
 // Activations of one stack pass over up to max_rows rows.
 // host mirror of frag_idx (q3_kernels.hip): position of element (m, k) of a [rows][K] GEMM-input matrix
@@ -76,6 +77,8 @@ struct Work {
 };
 int work_alloc(Work& w, const ModelCfg& c, int max_rows, int ffn, int max_vocab);
 void work_free(Work& w);
+// every activation buffer of w to 0 (asynchronous on s; ffn / max_vocab as for work_alloc): no row reads uninitialised memory
+int work_zero(hipStream_t s, Work& w, const ModelCfg& c, int ffn, int max_vocab);
 
 struct RowMap {            // which (slot, position) each row feeds
     const int* slot = nullptr;  // device [R] or null -> slot_base + r*slot_stride

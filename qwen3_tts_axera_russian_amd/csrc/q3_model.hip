@@ -256,6 +256,29 @@ void kv_free(KVCache& kv) {
     kv.k = kv.v = nullptr;
 }
 
+int kv_zero(hipStream_t s, KVCache& kv) {
+    const size_t bytes = kv.layer_stride() * kv.n_layers * sizeof(half_t);
+    Q3_HIP(hipMemsetAsync(kv.k, 0, bytes, s), -1);
+    Q3_HIP(hipMemsetAsync(kv.v, 0, bytes, s), -1);
+    return 0;
+}
+
+int work_zero(hipStream_t s, Work& w, const ModelCfg& c, int ffn, int max_vocab) {
+    const size_t R = (size_t)w.max_rows;
+    const int qkv_ld = (c.n_heads + 2 * c.n_kv) * c.head_dim;
+    Q3_HIP(hipMemsetAsync(w.rows_in, 0, R * c.hidden * 4, s), -1);
+    Q3_HIP(hipMemsetAsync(w.h, 0, R * c.hidden * 4, s), -1);
+    Q3_HIP(hipMemsetAsync(w.ssq, 0, R * (c.hidden / 16) * 4, s), -1);
+    Q3_HIP(hipMemsetAsync(w.xh, 0, R * c.hidden * 2, s), -1);
+    Q3_HIP(hipMemsetAsync(w.qkv, 0, R * qkv_ld * 4, s), -1);
+    Q3_HIP(hipMemsetAsync(w.attn, 0, R * c.n_heads * c.head_dim * 2, s), -1);
+    Q3_HIP(hipMemsetAsync(w.act, 0, R * ffn * 2, s), -1);
+    Q3_HIP(hipMemsetAsync(w.hidden_f32, 0, R * c.hidden * 4, s), -1);
+    Q3_HIP(hipMemsetAsync(w.hidden_f16, 0, R * c.hidden * 2, s), -1);
+    Q3_HIP(hipMemsetAsync(w.logits, 0, R * max_vocab * 4, s), -1);
+    return 0;
+}
+
 int work_alloc(Work& w, const ModelCfg& c, int max_rows, int ffn, int max_vocab) {
     max_rows = (max_rows + 127) / 128 * 128;   // the largest row tile (gemm_kernel: 128)
     w.max_rows = max_rows;

@@ -4,9 +4,46 @@ Stands where the reference's client closes the loop over sockets (dual_npu/tts_c
 the per-frame work (talker step, 15-group code predictor, feedback sum) stays on the GPU."""
 from __future__ import annotations
 
+import math
+from dataclasses import dataclass
+
 import numpy as np
 
 from . import hiplib
+
+
+@dataclass(frozen=True)
+class SlotParams:
+    """One utterance's settings in a per-slot batch (FrameEngine.open / admit; q3e_slot_params).  The draw stream is
+    mix(seed, utt): the same utterance with the same seed samples the same codes in any slot."""
+    max_frames: int
+    temperature: float = 0.0
+    top_k: int = 50
+    top_p: float = 1.0
+    cp_temperature: float = 0.0
+    cp_top_k: int = 50
+    seed: int = 0
+    utt: int = 0
+
+    def check(self, max_frames):
+        """Raises ValueError unless every field is in range for an engine of `max_frames` frames per utterance."""
+        for name in ("temperature", "cp_temperature"):
+            v = getattr(self, name)
+            if not (isinstance(v, (int, float)) and math.isfinite(v) and v >= 0):
+                raise ValueError(f"{name} must be finite and >= 0 (got {v!r})")
+        if not (isinstance(self.top_p, (int, float)) and 0 < self.top_p <= 1):
+            raise ValueError(f"top_p must be in (0, 1] (got {self.top_p!r})")
+        for name in ("max_frames", "top_k", "cp_top_k", "seed", "utt"):
+            if isinstance(getattr(self, name), bool) or not isinstance(getattr(self, name), (int, np.integer)):
+                raise ValueError(f"{name} must be an integer (got {getattr(self, name)!r})")
+        if not 1 <= self.max_frames <= max_frames:
+            raise ValueError(f"max_frames must be in 1..{max_frames} (got {self.max_frames})")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError(f"seed must fit in a u64 (got {self.seed})")
+        if not 0 <= self.utt < 1 << 31:
+            raise ValueError(f"utt must be in 0..2**31-1 (got {self.utt})")
+        if not (-(1 << 31) <= self.top_k < 1 << 31 and -(1 << 31) <= self.cp_top_k < 1 << 31):
+            raise ValueError("top_k / cp_top_k must fit in an i32")
 
 
 class FrameEngine:
@@ -17,6 +54,7 @@ class FrameEngine:
             raise RuntimeError(f"q3e_create failed: {weights_path}")
         self.max_batch, self.n_ctx, self.max_frames = max_batch, n_ctx, max_frames
         self.B = 0
+        self.frame_steps = 0       # frame steps run() has executed over the engine's life
 
     def set_sampling(self, talker_temperature=0.0, talker_top_k=50, talker_top_p=0.95, cp_temperature=0.0,
                      cp_top_k=50, seed=0):
@@ -59,6 +97,7 @@ class FrameEngine:
         rc = self._lib.q3e_run(self.h, int(n_frames))
         if rc < 0:
             raise RuntimeError(f"q3e_run failed: {rc}")
+        self.frame_steps += rc
         return rc
 
     @property
@@ -147,6 +186,37 @@ class FrameEngine:
                     owner[b] = i
                 nxt += len(take)
         return out
+
+    def open(self, B=None, ignore_eos=False):
+        """Per-slot mode (q3e_open): B (default max_batch) idle slots; utterances come in with admit() and leave when they
+        end or with release()."""
+        B = self.max_batch if B is None else int(B)
+        if self._lib.q3e_open(self.h, B, int(bool(ignore_eos))) != 0:
+            raise RuntimeError("q3e_open failed")
+        self.B = B
+
+    def admit(self, slots, prefixes, n_text, params):
+        """Per-slot mode: put new utterances into `slots` (q3e_admit), each with its SlotParams (checked here first)."""
+        slots = np.ascontiguousarray(np.asarray(slots, np.int32))
+        assert len(slots) == len(prefixes) == len(n_text) == len(params) and len(slots) > 0
+        for p in params:
+            p.check(self.max_frames)
+        cat = np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32) for p in prefixes], axis=0))
+        n_rows = np.array([p.shape[0] for p in prefixes], np.int32)
+        nt = np.ascontiguousarray(np.asarray(n_text, np.int32))
+        arr = (hiplib.SlotParamsC * len(params))(*[
+            hiplib.SlotParamsC(int(p.max_frames), float(p.temperature), int(p.top_k), float(p.top_p), float(p.cp_temperature),
+                               int(p.cp_top_k), int(p.seed), int(p.utt), 0) for p in params])
+        rc = self._lib.q3e_admit(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
+                                 hiplib.iptr(nt), arr)
+        if rc != 0:
+            raise RuntimeError(f"q3e_admit failed: {rc}")
+
+    def release(self, slots):
+        """Per-slot mode: end the utterances in `slots` now (q3e_release; cancellation)."""
+        slots = np.ascontiguousarray(np.asarray(slots, np.int32))
+        if len(slots) and self._lib.q3e_release(self.h, len(slots), hiplib.iptr(slots)) != 0:
+            raise RuntimeError("q3e_release failed")
 
     def hidden(self):
         out = np.empty((self.B, 1024), np.float32)

@@ -17,6 +17,13 @@ u16p = ctypes.POINTER(ctypes.c_uint16)
 i16p = ctypes.POINTER(ctypes.c_int16)
 
 
+class SlotParamsC(ctypes.Structure):
+    """q3e_slot_params (include/qwen3tts_engine.h)."""
+    _fields_ = [("max_frames", ctypes.c_int32), ("temperature", ctypes.c_float), ("top_k", ctypes.c_int32),
+                ("top_p", ctypes.c_float), ("cp_temperature", ctypes.c_float), ("cp_top_k", ctypes.c_int32),
+                ("seed", ctypes.c_uint64), ("utt", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 def _sig(lib, name, restype, argtypes):
     fn = getattr(lib, name)
     fn.restype, fn.argtypes = restype, argtypes
@@ -76,6 +83,9 @@ def load(path: str | None = None):
     _sig(lib, "q3e_get_codes", c_int, [c_void_p, i32p, c_int, i32p])
     _sig(lib, "q3e_get_done", c_int, [c_void_p, i32p, i32p])
     _sig(lib, "q3e_refill", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p])
+    _sig(lib, "q3e_open", c_int, [c_void_p, c_int, c_int])
+    _sig(lib, "q3e_admit", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, ctypes.POINTER(SlotParamsC)])
+    _sig(lib, "q3e_release", c_int, [c_void_p, c_int, i32p])
     _sig(lib, "q3e_get_hidden", c_int, [c_void_p, f32p])
     _sig(lib, "q3e_step_weight_bytes", ctypes.c_double, [c_void_p])
     # include/qwen3tts_voc.h
