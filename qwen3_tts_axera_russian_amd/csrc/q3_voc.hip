@@ -15,6 +15,7 @@
 //                  bias / residual add / clamp in the epilogue.
 #include "../../include/qwen3tts_voc.h"
 #include "q3_common.h"
+#include "q3_voc_ops.h"
 
 #include <algorithm>
 #include <cmath>
@@ -28,35 +29,8 @@ enum { VOP_RVQ = 1, VOP_CONV = 2, VOP_CONVT = 3, VOP_DWCONV = 4, VOP_NORM = 5, V
 enum { VF_SNAKE = 1, VF_RES_ADD = 2, VF_RES_SAVE = 4, VF_CLAMP = 8, VF_GELU = 16 };
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
+__device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }   // ELU, alpha = 1
 
-struct ConvArgs {
-    const float* x = nullptr;   // [B][Cin][Lin]
-    float* y = nullptr;         // [B][Cout][Lin*stride]
-    const float* wk = nullptr;  // [Cin/8][K][8][Mp]: rows contiguous (Mp = M rounded up to 4), M = Cout*stride virtual rows
-    int Mp = 0;
-    const float* bias = nullptr;
-    const float* alpha = nullptr;     // [Cin] Snake: x + inv_beta * sin^2(alpha x), applied to the input
-    const float* inv_beta = nullptr;
-    const float* res = nullptr;       // [B][Cout][L] added in the epilogue
-    int gelu = 0;                     // exact GELU applied to the input (ConvNeXt's second pointwise conv)
-    int Cin = 0, M = 0, K = 0, dil = 1, Lin = 0, stride = 1, Cout = 0, clamp = 0;
-    // Activations are [B][C][ld]: rows of L valid columns at a pitch ld = L rounded up to 32 floats (pitch4()), so that
-    // every row starts on a 128-byte line whatever L is (the transposed convs of the decoder family trim k - s samples at both ends:
-    // 64 frames -> 256 -> 2040 -> 10195 -> 40776 -> 122325 columns).  Pad columns hold junk that only ever feeds pad
-    // columns: every op is causal per column (a GEMM column depends on its own B column only).
-    int ldx = 0, ldy = 0;
-    // transposed conv: virtual row m = co * stride + p of input column l lands at output column l * stride + p - lt
-    // (lt samples trimmed on the left), kept when 0 <= that < Lout; Lc = columns of the polyphase GEMM that reach a
-    // kept output (= Lin for the trims in use; inputs at l >= Lin read as zero)
-    int lt = 0, Lout = 0, Lc = 0;
-    // Lc of this op when the decode runs the full chunk length: the launcher's variant rule looks at it, so that a decode of
-    // fewer frames (voc_run's T) sums every column in the same order as the full-length one (0: use Lc)
-    int Lrule = 0;
-    int n_tiles = 0, tiles_l = 0, tiles_m = 0;  // set by the launcher
-    // one-tap, stride-1 convs (pointwise projections): the columns of all B chunks form ONE axis of B*Lin columns
-    // (a column needs no neighbour), so 128-column tiles stay full when a chunk is only 64 columns long
-    int flat_B = 0;                              // > 0: flattened, B chunks
-};
 
 static int g_voc_split = 1;    // 1 (default): split-precision fp16 MFMA path where Cin % 16 == 0; 0: exact-fp32 MFMA everywhere
 static int g_voc_max_wgs = 0;  // 0 = one workgroup per tile; >0 caps the grid (persistent tile loop)
@@ -80,7 +54,7 @@ __host__ __device__ inline int voc_xpitch(int XW) { return Q3_VOC_XPAD ? ((XW + 
 // Staging goes global -> LDS directly; ~4 workgroups per CU hide its latency (a register-staged software
 // pipeline was tried: 199-256 VGPRs, one workgroup per SIMD, 1.6x slower at 32 chunks).
 // ACT: what is applied to the input while it is staged -- 0 nothing, 1 Snake, 2 exact GELU, 3 decided at run time (a.alpha /
-// a.gelu).  Compiled in for the one-tap convs (round 3, per-op profile at 32 chunks: the Snake 1 x 1 convs that close the 768- /
+// a.gelu), 4 ELU (the speech-tokenizer encoder, a.elu; never chosen at run time, so the other variants compile as before).  Compiled in for the one-tap convs (round 3, per-op profile at 32 chunks: the Snake 1 x 1 convs that close the 768- /
 // 384-channel residual units 0.82 -> 0.75 and 1.27 -> 1.11 ms); for two and more taps the run-time form is the faster one
 // (7-tap 126 vs 124 TFLOP/s, transposed convs 105 vs 99: the specialised kernels are scheduled worse), so those keep it.
 template <int MT, int KT, int KC, bool CT = false, int ACT = 3>   // CT: transposed conv (stride > 1, no residual), stores go through an LDS slab
@@ -187,6 +161,9 @@ __global__ void __launch_bounds__(256, (KC >= 32 && MT >= 3) ? 2 : (MT >= 4 ? 3 
                         if (ACT == 2 || (ACT == 3 && a.gelu)) {
                             v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
                         }
+                        if (ACT == 4) {
+                            v.x = elu1(v.x); v.y = elu1(v.y); v.z = elu1(v.z); v.w = elu1(v.w);
+                        }
                         if (l0 + c4 >= Lcols) v = make_float4(0.f, 0.f, 0.f, 0.f);
                         *(float4*)(Xs + xci * XP + c4) = v;
                     }
@@ -219,6 +196,9 @@ __global__ void __launch_bounds__(256, (KC >= 32 && MT >= 3) ? 2 : (MT >= 4 ? 3 
                         }
                         if (ACT == 2 || (ACT == 3 && a.gelu)) {
                             v.x = gelu_erf(v.x); v.y = gelu_erf(v.y); v.z = gelu_erf(v.z); v.w = gelu_erf(v.w);
+                        }
+                        if (ACT == 4) {
+                            v.x = elu1(v.x); v.y = elu1(v.y); v.z = elu1(v.z); v.w = elu1(v.w);
                         }
                         if (l < 0) v = make_float4(0.f, 0.f, 0.f, 0.f);
                         if (l >= a.Lin) v.x = 0.f;
@@ -326,6 +306,11 @@ static int launch_conv_t(hipStream_t s, const ConvArgs& a, int B) {
         if (a.stride > 1 && a.res == nullptr) return launch_conv_t<MT, KT, KC, true, ACT>(s, a, B);
     }
     if constexpr (ACT < 0) {      // the input activation becomes a template argument
+        if (a.elu) {
+            if constexpr (!CT && KC == 16 && (KT == 1 || KT == 3)) return launch_conv_t<MT, KT, KC, CT, 4>(s, a, B);
+            Q3_LOG("voc conv: ELU input is built for 1- and 3-tap convs at 16 channels per stage only");
+            return -1;
+        }
         if (a.alpha && a.gelu) {
             Q3_LOG("voc conv: Snake and GELU on one input are not built");
             return -1;
@@ -464,6 +449,13 @@ static int launch_conv(hipStream_t s, const ConvArgs& a, int B) {
         Q3_LOG("voc conv: Cin=%d is not a multiple of 8", c);
         return -1;
     }
+    if (a.elu) {   // (ConvArgs::elu: one stage width, whatever the length or batch)
+        if (c % 16 || (a.K != 1 && a.K != 3) || a.stride != 1 || a.alpha || a.gelu) {
+            Q3_LOG("voc conv: ELU input needs a 1- or 3-tap stride-1 conv over a multiple of 16 channels (got %d taps, %d channels)", a.K, c);
+            return -1;
+        }
+        return a.K == 1 ? launch_conv_mt<1, 16>(s, a, B) : launch_conv_mt<3, 16>(s, a, B);
+    }
     static const int out1 = getenv("Q3_VOC_OUT1") ? atoi(getenv("Q3_VOC_OUT1")) : 1;
     if (out1 && a.M == 1 && a.K == 7 && a.dil == 1 && a.stride == 1 && !a.res && !a.gelu && (a.ldx & 3) == 0 &&
         (size_t)B * c * a.ldx < ((size_t)1 << 31)) {
@@ -497,6 +489,8 @@ static int launch_conv(hipStream_t s, const ConvArgs& a, int B) {
             return -1;
     }
 }
+
+int voc_launch_conv(hipStream_t s, const ConvArgs& a, int B) { return launch_conv(s, a, B); }
 
 // ---------------------------------------------------------------------------
 // Fused residual unit of the decoder blocks at 96 / 192 channels (the two HBM-bound stages):
@@ -1166,6 +1160,23 @@ __global__ void __launch_bounds__(256) voc_attn_tile_kernel(const float* __restr
                 if (d < D && (d & 3) == kl) yb[(size_t)d * ld] = o[d] * inv;
         }
     }
+}
+
+int voc_launch_norm(hipStream_t s, const float* x, const float* w, const float* bias, float* y, int C, int L, int ld,
+                    int kind, float eps, int B) {
+    hipLaunchKernelGGL(chan_norm_kernel, dim3((unsigned)((L + 63) / 64), B), dim3(1024), 0, s, x, w, bias, y, C, L, ld, kind, eps);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+
+int voc_launch_attn(hipStream_t s, const float* x, float* y, int H, int D, int L, int ld, int window, float theta, int B) {
+    if (D <= 0 || D > 128 || (D & 1)) {
+        Q3_LOG("voc attention: head_dim %d is not built (even, <= 128)", D);
+        return -1;
+    }
+    hipLaunchKernelGGL(voc_attn_kernel, dim3((unsigned)L, H, B), dim3(64), 0, s, x, y, H, D, L, ld, window, theta);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
 }
 
 // y[c][l] = act(x[c][l]) * x[C + c][l]; act 0 SiLU, 1 GELU

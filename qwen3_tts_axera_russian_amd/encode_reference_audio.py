@@ -1,0 +1,143 @@
+"""Encode a reference WAV into 16-group codec ids for a voice-clone prompt (the reference's
+scripts/encode_reference_audio.py, on the GPU encoder).
+
+    python -m qwen3_tts_axera_russian_amd.encode_reference_audio --audio ref.wav --model enc.q3w --output_dir prompt/ \
+        [--ref_text "..."] [--max_tokens 256] [--decode_back ref_decoded.wav --vocoder voc.q3w]
+
+Writes ref_codec_tokens.npy (int64 [min(T, max_tokens)][16], the semantic id first) to --output, or, with --output_dir,
+a prompt_dir holding ref_codec_tokens.npy and (with --ref_text) ref_text.txt.  --model is an encoder container
+(weights.convert_speech_tokenizer_encoder) or a speech_tokenizer/ directory, converted on the fly.
+
+WAV loading follows the reference's load_wav: int16 / 32768, int32 / 2^31, any other dtype cast to float32 unscaled,
+channels averaged.  Audio at another rate than the encoder's is resampled on the host with scipy.signal.resample_poly;
+qwen_tts's own resampler is not available here, so that step is not pinned to it."""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+import sys
+import tempfile
+import time
+import wave
+
+import numpy as np
+
+
+def load_wav(path):
+    """-> (float32 mono samples, sample rate), the reference's rules."""
+    import scipy.io.wavfile as wavfile
+    sr, data = wavfile.read(path)
+    if data.dtype == np.int16:
+        data = data.astype(np.float32) / 32768.0
+    elif data.dtype == np.int32:
+        data = data.astype(np.float32) / 2147483648.0
+    elif data.dtype != np.float32:
+        data = data.astype(np.float32)
+    if data.ndim > 1:
+        data = data.mean(axis=1)
+    return np.ascontiguousarray(data, dtype=np.float32), int(sr)
+
+
+def resample(x, sr, target):
+    if sr == target:
+        return x
+    from scipy.signal import resample_poly
+    g = math.gcd(int(sr), int(target))
+    return resample_poly(x, target // g, sr // g).astype(np.float32)
+
+
+def open_encoder(model, max_samples):
+    """An encoder container, or a speech_tokenizer/ directory (converted into a temporary container)."""
+    from .encoder import Encoder
+    if os.path.isdir(model):
+        from . import weights as W
+        tmp = tempfile.NamedTemporaryFile(suffix=".q3w", delete=False)
+        tmp.close()
+        try:
+            _, report = W.convert_speech_tokenizer_encoder(model, tmp.name)
+            for line in report:
+                print(f"  {line}")
+            return Encoder(tmp.name, max_batch=1, max_samples=max_samples)
+        finally:
+            os.unlink(tmp.name)
+    return Encoder(model, max_batch=1, max_samples=max_samples)
+
+
+def decode_back(codes, vocoder, out_wav):
+    """The reference's "decode back" step: codes -> voc_synthesize (int16, 24 kHz) -> WAV."""
+    from . import hiplib
+    lib = hiplib.load()
+    h = lib.voc_load(str(vocoder).encode(), 64, 1)
+    if not h:
+        raise RuntimeError(f"voc_load({vocoder}) failed")
+    try:
+        codes = np.ascontiguousarray(codes, np.int64)
+        out = np.zeros(lib.voc_synthesize_max_samples(h, codes.shape[0]), np.int16)
+        n = np.zeros(1, np.int32)
+        if lib.voc_synthesize(h, codes.ctypes.data_as(hiplib.i64p), codes.shape[0], out.ctypes.data_as(hiplib.i16p),
+                              n.ctypes.data_as(hiplib.i32p)) != 0:
+            raise RuntimeError("voc_synthesize failed")
+    finally:
+        lib.voc_free(h)
+    with wave.open(out_wav, "w") as wf:
+        wf.setnchannels(1)
+        wf.setsampwidth(2)
+        wf.setframerate(24000)
+        wf.writeframes(out[:int(n[0])].tobytes())
+    return int(n[0])
+
+
+def main(argv=None, encoder_factory=open_encoder):
+    p = argparse.ArgumentParser(description="Encode reference audio to codec tokens (GPU speech-tokenizer encoder)")
+    p.add_argument("--audio", required=True, help="reference audio WAV file")
+    p.add_argument("--model", "--model_dir", dest="model", required=True,
+                   help="encoder container (.q3w) or a speech_tokenizer/ directory")
+    p.add_argument("--output", default="ref_codec_tokens.npy")
+    p.add_argument("--output_dir", default=None, help="output directory (creates the prompt_dir structure)")
+    p.add_argument("--ref_text", default=None, help="text spoken in the reference audio")
+    p.add_argument("--max_tokens", type=int, default=256)
+    p.add_argument("--decode_back", default=None, help="also decode the saved ids to this WAV through the vocoder")
+    p.add_argument("--vocoder", default=None, help="vocoder container for --decode_back")
+    a = p.parse_args(argv)
+    if a.decode_back and not a.vocoder:
+        p.error("--decode_back needs --vocoder")
+    if a.max_tokens < 1:
+        p.error("--max_tokens must be >= 1")
+    try:
+        x, sr = load_wav(a.audio)
+    except Exception as e:   # (missing, unreadable, not a WAV)
+        print(f"error: cannot read {a.audio}: {e}", file=sys.stderr)
+        return 2
+    if x.size == 0:
+        print(f"error: {a.audio} holds no samples", file=sys.stderr)
+        return 2
+    print(f"Audio: {a.audio}\n  Duration: {x.size / sr:.2f}s, SR: {sr}")
+    x = resample(x, sr, 24000)
+    enc = encoder_factory(a.model, max(int(x.size), 1))
+    if enc.sample_rate != 24000:
+        x = resample(x, 24000, enc.sample_rate)
+    t0 = time.time()
+    codes = enc.encode([x])[0]
+    print(f"Encode time: {time.time() - t0:.3f}s (GPU {enc.last_ms():.2f} ms)")
+    n_tokens, n_groups = codes.shape
+    print(f"Tokens: {n_tokens}, Groups: {n_groups}")
+    keep = np.ascontiguousarray(codes[:min(n_tokens, a.max_tokens)], dtype=np.int64)
+    if a.output_dir:
+        os.makedirs(a.output_dir, exist_ok=True)
+        np.save(os.path.join(a.output_dir, "ref_codec_tokens.npy"), keep)
+        if a.ref_text:
+            with open(os.path.join(a.output_dir, "ref_text.txt"), "w") as f:
+                f.write(a.ref_text)
+        print(f"Saved prompt_dir: {a.output_dir}")
+    else:
+        np.save(a.output, keep)
+        print(f"Saved: {a.output}")
+    if a.decode_back:
+        n = decode_back(keep, a.vocoder, a.decode_back)
+        print(f"Saved decoded: {a.decode_back} ({n} samples)")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

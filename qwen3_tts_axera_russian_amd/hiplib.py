@@ -118,6 +118,17 @@ def load(path: str | None = None):
     _sig(lib, "voc_stream_last_decodes", c_int, [c_void_p])
     _sig(lib, "voc_stream_last_chunks", c_int, [c_void_p])
     _sig(lib, "voc_stream_last_ms", c_float, [c_void_p])
+    # include/qwen3tts_enc.h
+    _sig(lib, "enc_load", c_void_p, [c_char_p, c_int, c_int])
+    _sig(lib, "enc_free", None, [c_void_p])
+    _sig(lib, "enc_num_quantizers", c_int, [c_void_p])
+    _sig(lib, "enc_sample_rate", c_int, [c_void_p])
+    _sig(lib, "enc_samples_per_frame", c_int, [c_void_p])
+    _sig(lib, "enc_frames", c_int, [c_void_p, c_int])
+    _sig(lib, "enc_encode", c_int, [c_void_p, f32p, i32p, c_int, i64p_, c_int, i32p])
+    _sig(lib, "enc_last_ms", c_float, [c_void_p])
+    _sig(lib, "enc_debug_shape", c_int, [c_void_p, i32p, c_int, c_int, i32p, i32p])
+    _sig(lib, "enc_debug_run", c_int, [c_void_p, f32p, i32p, c_int, c_int, f32p, i32p, i32p])
     # include/qwen3tts_text.h
     _sig(lib, "tfe_load", c_void_p, [c_char_p, c_char_p, c_int])
     _sig(lib, "tfe_free", None, [c_void_p])

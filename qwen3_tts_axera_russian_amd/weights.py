@@ -962,3 +962,359 @@ def export_speech_tokenizer_layout(tensors: dict, vc: VocConfig, dst_dir: str, l
             "head_dim": vc.tf_head_dim, "sliding_window": vc.tf_window, "rope_theta": vc.tf_rope_theta,
             "rms_norm_eps": vc.tf_eps_e9 * 1e-9, "dilations": list(vc.dilations), "num_quantizers": vc.n_q,
             "convt_trim": vc.convt_trim}}, f)
+
+
+# ----------------------------------------------------------------------------
+# speech-tokenizer encoder program (include/qwen3tts_enc.h, csrc/q3_enc.hip)
+# ----------------------------------------------------------------------------
+# The encode half of the 12 Hz speech tokenizer: 24 kHz audio -> [frames][16] codec ids.  Its semantics are pinned to
+# transformers' MimiModel.encode(..., num_quantizers=16) (tests/golden/make_mimi_encode_golden.py); that Qwen3-TTS's
+# tokenizer encoder IS that module is recollection (DESIGN.md "Speech tokenizer encoder").  Rows are
+# (op, a, b, c, d, flags, e, f) int32, tensors enc.op{i}.*:
+#   EOP_CONV_IN  [1, 1, cout, k]                    causal conv of the one input channel        weight [cout, 1, k], bias
+#   EOP_CONV     [2, cin, cout, k, dilation, flags]  causal stride-1 conv                        weight [cout, cin, k], bias?
+#   EOP_CONV_S   [3, cin, cout, k, stride, flags]    strided conv, Mimi's padding: k - stride on the left, the right to
+#                                                    whole frames (ceil(L / stride) outputs); zeros, or EF_REPLICATE
+#   EOP_NORM     [4, c, c, 1, eps * 1e9, flags]      LayerNorm over the channels                  weight, bias
+#   EOP_ATTN     [5, 3 H D, H D, H, D, 0, window, theta]  causal sliding-window attention, rotate-half RoPE
+#   EOP_RVQ      [6, 2 dim, n_q, size, dim, 0, n_semantic]  split RVQ encode of [semantic | acoustic] projections
+#                                                    codebook [n_q, size, dim] (embed = embed_sum / usage.clamp(1e-5))
+# flags: EF_ELU the input goes through ELU first; EF_RES_SAVE the op's input is kept as the residual; EF_RES_ADD the
+# residual is added to the output; EF_TO_RES the output replaces the residual and the activation stays (a conv
+# shortcut); EF_GELU exact GELU on the input (fc2).  Linear layers are 1-tap convs; layer scales fold into o_proj / fc2.
+EOP_CONV_IN, EOP_CONV, EOP_CONV_S, EOP_NORM, EOP_ATTN, EOP_RVQ = 1, 2, 3, 4, 5, 6
+EF_ELU, EF_RES_SAVE, EF_RES_ADD, EF_TO_RES, EF_GELU, EF_REPLICATE = 1, 2, 4, 8, 16, 32
+
+
+@dataclass
+class EncConfig:
+    """Shape of the encoder: the defaults are MimiConfig()'s with 16 kept quantizers (1 semantic + 15 acoustic)."""
+    sample_rate: int = 24000
+    num_filters: int = 64
+    ratios: tuple = (8, 6, 5, 4)          # MimiConfig.upsampling_ratios; the encoder walks them reversed
+    num_residual_layers: int = 1
+    kernel_size: int = 7
+    last_kernel_size: int = 3
+    residual_kernel_size: int = 3
+    dilation_growth_rate: int = 2
+    compress: int = 2
+    use_conv_shortcut: bool = False
+    hidden: int = 512
+    layers: int = 8
+    heads: int = 8
+    head_dim: int = 64
+    ffn: int = 2048
+    window: int = 250
+    rope_theta: int = 10000
+    norm_eps_e9: int = 10000              # 1e-5
+    ds_kernel: int = 4                    # the 25 -> 12.5 Hz downsample: kernel 2 * (encodec rate / frame rate), stride 2
+    ds_stride: int = 2
+    codebook_size: int = 2048
+    codebook_dim: int = 256
+    n_q: int = 16
+    n_semantic: int = 1
+
+
+def tiny_enc_config() -> EncConfig:
+    """Every op kind at test size (the smallest widths the ELU convs take: 16-channel residual hidden layers)."""
+    return EncConfig(num_filters=32, hidden=64, layers=2, heads=4, head_dim=16, ffn=96, window=16, codebook_size=64,
+                     codebook_dim=16)
+
+
+def enc_hop(ec: EncConfig) -> int:
+    """Samples per output frame: the product of the strides (1920 at 24 kHz = 12.5 Hz)."""
+    h = ec.ds_stride
+    for r in ec.ratios:
+        h *= r
+    return h
+
+
+def enc_frames(ec: EncConfig, n_samples: int) -> int:
+    """Frames a clip of n_samples gives: every strided conv maps L -> ceil(L / stride) (MimiModel.get_encoded_length)."""
+    L = int(n_samples)
+    for s in tuple(reversed(ec.ratios)) + (ec.ds_stride,):
+        L = -(-L // s)
+    return L
+
+
+def enc_program(ec: EncConfig):
+    """-> (rows, {tensor name: shape}, [(stage name, ops that produce it)])."""
+    prog, shapes, stages = [], {}, []
+
+    def add(row, tens):
+        i = len(prog)
+        prog.append(list(row) + [0] * (8 - len(row)))
+        for n, shp in tens.items():
+            shapes[f"enc.op{i}.{n}"] = shp
+
+    def conv(cin, cout, k, dil, flags, bias=True):
+        t = {"weight": (cout, cin, k)}
+        if bias:
+            t["bias"] = (cout,)
+        add([EOP_CONV, cin, cout, k, dil, flags], t)
+
+    F = ec.num_filters
+    add([EOP_CONV_IN, 1, F, ec.kernel_size], {"weight": (F, 1, ec.kernel_size), "bias": (F,)})
+    stages.append(("conv_in", len(prog)))
+    scale = 1
+    for bi, r in enumerate(reversed(ec.ratios)):
+        C = scale * F
+        hid = C // ec.compress
+        for j in range(ec.num_residual_layers):
+            dil = ec.dilation_growth_rate ** j
+            if ec.use_conv_shortcut:
+                conv(C, C, 1, 1, EF_TO_RES)
+                conv(C, hid, ec.residual_kernel_size, dil, EF_ELU)
+            else:
+                conv(C, hid, ec.residual_kernel_size, dil, EF_ELU | EF_RES_SAVE)
+            conv(hid, C, 1, 1, EF_ELU | EF_RES_ADD)
+            stages.append((f"block{bi}_res{j}", len(prog)))
+        add([EOP_CONV_S, C, 2 * C, 2 * r, r, EF_ELU], {"weight": (2 * C, C, 2 * r), "bias": (2 * C,)})
+        stages.append((f"block{bi}_down", len(prog)))
+        scale *= 2
+    conv(scale * F, ec.hidden, ec.last_kernel_size, 1, EF_ELU)
+    stages.append(("seanet_out", len(prog)))
+    H, nh, hd = ec.hidden, ec.heads, ec.head_dim
+    for l in range(ec.layers):
+        add([EOP_NORM, H, H, 1, ec.norm_eps_e9, EF_RES_SAVE], {"weight": (H,), "bias": (H,)})
+        conv(H, 3 * nh * hd, 1, 1, 0, bias=False)
+        add([EOP_ATTN, 3 * nh * hd, nh * hd, nh, hd, 0, ec.window, ec.rope_theta], {})
+        conv(nh * hd, H, 1, 1, EF_RES_ADD, bias=False)
+        add([EOP_NORM, H, H, 1, ec.norm_eps_e9, EF_RES_SAVE], {"weight": (H,), "bias": (H,)})
+        conv(H, ec.ffn, 1, 1, 0, bias=False)
+        conv(ec.ffn, H, 1, 1, EF_GELU | EF_RES_ADD, bias=False)
+        stages.append((f"tf{l}", len(prog)))
+    add([EOP_CONV_S, H, H, ec.ds_kernel, ec.ds_stride, EF_REPLICATE], {"weight": (H, H, ec.ds_kernel)})
+    stages.append(("embedding", len(prog)))     # the pre-quantizer embedding (12.5 Hz)
+    conv(H, 2 * ec.codebook_dim, 1, 1, 0, bias=False)   # semantic | acoustic input_proj, stacked
+    stages.append(("vq_in", len(prog)))
+    add([EOP_RVQ, 2 * ec.codebook_dim, ec.n_q, ec.codebook_size, ec.codebook_dim, 0, ec.n_semantic],
+        {"codebook": (ec.n_q, ec.codebook_size, ec.codebook_dim)})
+    return prog, shapes, stages
+
+
+def make_synthetic_enc(ec: EncConfig, seed: int = 1234) -> dict:
+    """Random encoder weights whose activations stay O(1) through every stage and whose codes use many ids per group:
+    convs at gain ~1 / sqrt(fan_in) (the residual branch damped), transformer layer scales ~0.2 folded in, codebooks
+    drawn at the scale of the residual they quantise (shrinking stage by stage, as a trained RVQ's do)."""
+    prog, shapes, _ = enc_program(ec)
+    t = {"enc.program": np.asarray(prog, dtype=np.int32)}
+    for n, shp in shapes.items():
+        rng = _rng_for(n, seed)
+        row = prog[int(n.split(".")[1][2:])]
+        if row[0] == EOP_NORM:
+            a = (1.0 + 0.1 * rng.standard_normal(shp)) if n.endswith("weight") else 0.05 * rng.standard_normal(shp)
+        elif n.endswith("bias"):
+            a = 0.02 * rng.standard_normal(shp)
+        elif n.endswith("codebook"):
+            # stage q of each chain (semantic: q < n_semantic; acoustic: the rest, restarted) at 0.85^(its place in the chain)
+            nq = shp[0]
+            place = np.array([q if q < ec.n_semantic else q - ec.n_semantic for q in range(nq)])
+            a = 0.9 * (0.85 ** place)[:, None, None] * rng.standard_normal(shp) / np.sqrt(shp[2])
+        else:
+            fan_in = int(np.prod(shp[1:]))
+            gain = 1.2
+            if row[0] == EOP_CONV and (row[5] & EF_RES_ADD):
+                gain = 0.15 if (row[5] & EF_GELU) or row[3] == 1 and not (row[5] & EF_ELU) else 0.5
+            if row[0] == EOP_CONV and row[3] == 1 and not (row[5] & (EF_ELU | EF_RES_ADD | EF_TO_RES)):
+                gain = 1.0
+            a = gain * rng.standard_normal(shp) / np.sqrt(fan_in)
+        t[n] = np.asarray(a, dtype=np.float32)
+    return t
+
+
+def write_synthetic_enc(path: str, ec: EncConfig, seed: int = 1234) -> dict:
+    t = make_synthetic_enc(ec, seed)
+    write_pack(path, {"enc_sample_rate": float(ec.sample_rate)}, t)
+    return t
+
+
+# ----------------------------------------------------------------------------
+# encoder table from a MimiModel state dict / a speech_tokenizer/ directory
+# ----------------------------------------------------------------------------
+ENC_SKIP_PREFIXES = ("decoder.", "decoder_transformer.", "upsample.")   # the decode half of a full MimiModel
+
+
+def _enc_strip_prefix(T: dict) -> dict:
+    """A speech tokenizer nests the MimiModel under `encoder.` (encoder.encoder.layers..., encoder.quantizer...), beside
+    its own decoder; a bare MimiModel state dict starts at encoder.layers / quantizer.  -> the MimiModel's keys."""
+    if any(k.startswith(("encoder.encoder.", "encoder.quantizer.", "encoder.encoder_transformer.")) for k in T):
+        return {k[len("encoder."):]: v for k, v in T.items() if k.startswith("encoder.")}
+    return dict(T)
+
+
+def enc_config_from_mimi(cfgj: dict, n_q: int = 16) -> EncConfig:
+    """MimiConfig.to_dict() (or the `encoder_config` of a speech tokenizer's config.json) -> EncConfig."""
+    defaults = {"sampling_rate": 24000, "num_filters": 64, "upsampling_ratios": [8, 6, 5, 4], "num_residual_layers": 1,
+                        "kernel_size": 7, "last_kernel_size": 3, "residual_kernel_size": 3, "dilation_growth_rate": 2,
+                        "compress": 2, "use_conv_shortcut": False, "hidden_size": 512, "num_hidden_layers": 8,
+                        "num_attention_heads": 8, "intermediate_size": 2048, "sliding_window": 250, "norm_eps": 1e-5,
+                        "codebook_size": 2048, "codebook_dim": 256, "num_quantizers": 32, "num_semantic_quantizers": 1,
+                        "vector_quantization_hidden_dimension": 256, "pad_mode": "constant", "use_causal_conv": True,
+                        "hidden_act": "gelu", "attention_bias": False}
+    c = dict(defaults, **{k: v for k, v in cfgj.items() if v is not None})
+    if c["pad_mode"] != "constant" or not c["use_causal_conv"] or c["hidden_act"] != "gelu" or c["attention_bias"]:
+        raise ValueError(f"encoder config: pad_mode {c['pad_mode']!r}, causal {c['use_causal_conv']}, act {c['hidden_act']!r}, "
+                         f"attention_bias {c['attention_bias']}: the table has ops for constant padding, causal convs, GELU "
+                         f"and bias-free attention only")
+    rope = c.get("rope_parameters") or {}
+    theta = c.get("rope_theta", rope.get("rope_theta", 10000.0))
+    heads = int(c["num_attention_heads"])
+    hd = int(c.get("head_dim") or c["hidden_size"] // heads)
+    n_q = int(n_q)
+    if not c["num_semantic_quantizers"] <= n_q <= c["num_quantizers"]:
+        raise ValueError(f"{n_q} kept quantizers: needs {c['num_semantic_quantizers']} <= n_q <= {c['num_quantizers']}")
+    fr = c.get("frame_rate")
+    ds_k = 4
+    if fr is not None:
+        hop = int(np.prod(c["upsampling_ratios"]))
+        ds_k = 2 * int((c["sampling_rate"] / hop) / float(fr))
+    return EncConfig(sample_rate=int(c["sampling_rate"]), num_filters=int(c["num_filters"]),
+                     ratios=tuple(int(r) for r in c["upsampling_ratios"]), num_residual_layers=int(c["num_residual_layers"]),
+                     kernel_size=int(c["kernel_size"]), last_kernel_size=int(c["last_kernel_size"]),
+                     residual_kernel_size=int(c["residual_kernel_size"]), dilation_growth_rate=int(c["dilation_growth_rate"]),
+                     compress=int(c["compress"]), use_conv_shortcut=bool(c["use_conv_shortcut"]), hidden=int(c["hidden_size"]),
+                     layers=int(c["num_hidden_layers"]), heads=heads, head_dim=hd, ffn=int(c["intermediate_size"]),
+                     window=int(c["sliding_window"]), rope_theta=int(round(float(theta))),
+                     norm_eps_e9=int(round(float(c["norm_eps"]) * 1e9)), ds_kernel=ds_k, ds_stride=2,
+                     codebook_size=int(c["codebook_size"]), codebook_dim=int(c["vector_quantization_hidden_dimension"]
+                                                                             if c.get("codebook_dim") is None else c["codebook_dim"]),
+                     n_q=n_q, n_semantic=int(c["num_semantic_quantizers"]))
+
+
+def state_to_enc(T: dict, mimi_config_dict: dict | None = None, n_q: int = 16, where: str = "state dict"):
+    """A MimiModel state dict (numpy arrays; bare or under `encoder.`) + its MimiConfig dict -> (EncConfig, table
+    tensors, report).  Layer scales fold into o_proj / fc2, EMA codebooks are divided out, the two input_proj stack
+    into one 1-tap conv.  The decode half (decoder.*, decoder_transformer.*, upsample.*, the quantizers' output_proj)
+    and the acoustic codebooks past the kept ones are skipped; any other tensor the table does not consume is an error."""
+    T = _enc_strip_prefix(T)
+    ec = enc_config_from_mimi(mimi_config_dict or {}, n_q)
+    prog, shapes, _ = enc_program(ec)
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a), dtype=np.float32)
+    used = set()
+
+    def need(k):
+        if k not in T:
+            raise KeyError(f"{where}: tensor {k} not found")
+        used.add(k)
+        return f32(T[k])
+
+    def opt(k):
+        return need(k) if k in T else None
+
+    out = {"enc.program": np.asarray(prog, dtype=np.int32)}
+    it = iter(range(len(prog)))
+
+    def put(i, **tens):
+        for n, a in tens.items():
+            want = shapes.get(f"enc.op{i}.{n}")
+            if want is None or tuple(a.shape) != tuple(want):
+                raise ValueError(f"{where}: enc.op{i}.{n} gets shape {tuple(a.shape)}, the table expects {want}")
+            out[f"enc.op{i}.{n}"] = np.ascontiguousarray(a, dtype=np.float32)
+
+    def conv(i, p, bias=True):
+        t = {"weight": need(p + ".weight")}
+        b = opt(p + ".bias")
+        if bias and b is not None:
+            t["bias"] = b
+        elif b is not None:
+            raise ValueError(f"{where}: {p}.bias has no place in the table")
+        put(i, **t)
+
+    conv(next(it), "encoder.layers.0.conv")
+    idx = 1
+    for r in reversed(ec.ratios):
+        for j in range(ec.num_residual_layers):
+            p = f"encoder.layers.{idx}."
+            if ec.use_conv_shortcut:
+                conv(next(it), p + "shortcut.conv")
+            conv(next(it), p + "block.1.conv")
+            conv(next(it), p + "block.3.conv")
+            idx += 1
+        conv(next(it), f"encoder.layers.{idx + 1}.conv")   # (layers.{idx} is the ELU)
+        idx += 2
+    conv(next(it), f"encoder.layers.{idx + 1}.conv")
+    nh, hd = ec.heads, ec.head_dim
+    for l in range(ec.layers):
+        p = f"encoder_transformer.layers.{l}."
+        put(next(it), weight=need(p + "input_layernorm.weight"), bias=need(p + "input_layernorm.bias"))
+        q, k, v = need(p + "self_attn.q_proj.weight"), need(p + "self_attn.k_proj.weight"), need(p + "self_attn.v_proj.weight")
+        rep = q.shape[0] // k.shape[0]
+        if rep > 1:   # grouped-query attention: query head h reads k/v head h // rep
+            k = np.repeat(k.reshape(-1, hd, k.shape[1]), rep, axis=0).reshape(-1, k.shape[1])
+            v = np.repeat(v.reshape(-1, hd, v.shape[1]), rep, axis=0).reshape(-1, v.shape[1])
+        put(next(it), weight=np.concatenate([q, k, v], 0)[:, :, None])
+        next(it)                                                     # attention: no tensors
+        sa = need(p + "self_attn_layer_scale.scale").reshape(-1)
+        put(next(it), weight=(need(p + "self_attn.o_proj.weight") * sa[:, None])[:, :, None])
+        put(next(it), weight=need(p + "post_attention_layernorm.weight"), bias=need(p + "post_attention_layernorm.bias"))
+        put(next(it), weight=need(p + "mlp.fc1.weight")[:, :, None])
+        sm = need(p + "mlp_layer_scale.scale").reshape(-1)
+        put(next(it), weight=(need(p + "mlp.fc2.weight") * sm[:, None])[:, :, None])
+    conv(next(it), "downsample.conv", bias=False)
+    sem, ac = "quantizer.semantic_residual_vector_quantizer.", "quantizer.acoustic_residual_vector_quantizer."
+    put(next(it), weight=np.concatenate([need(sem + "input_proj.weight"), need(ac + "input_proj.weight")], 0))
+
+    def codebook(p):
+        usage = need(p + "cluster_usage")
+        return need(p + "embed_sum") / np.maximum(usage, np.float32(1e-5))[:, None]
+
+    n_ac = ec.n_q - ec.n_semantic
+    cbs = [codebook(sem + f"layers.{i}.codebook.") for i in range(ec.n_semantic)]
+    cbs += [codebook(ac + f"layers.{i}.codebook.") for i in range(n_ac)]
+    put(next(it), codebook=np.stack(cbs))
+    missing = [n for n in shapes if n not in out]
+    if missing:
+        raise ValueError(f"table tensors without a source: {missing[:5]}")
+    skipped = 0
+
+    def skip(k):
+        if k.startswith(ENC_SKIP_PREFIXES) or k.endswith(("initialized", "rotary_emb.inv_freq")) or ".output_proj." in k:
+            return True
+        if k.startswith(ac + "layers."):
+            return int(k[len(ac + "layers."):].split(".")[0]) >= n_ac   # acoustic codebooks past the kept ones
+        return False
+    unused = []
+    for k in sorted(T):
+        if k in used:
+            continue
+        if skip(k):
+            skipped += 1
+        else:
+            unused.append(k)
+    if unused:
+        raise KeyError(f"{where}: {len(unused)} encoder tensors have no place in the table (first: {unused[:4]})")
+    report = [f"{len(prog)} ops: SEANet {ec.num_filters} filters, ratios {tuple(reversed(ec.ratios))}, "
+              f"{ec.num_residual_layers} residual layer(s){' with conv shortcuts' if ec.use_conv_shortcut else ''} -> {ec.hidden}, "
+              f"{ec.layers} transformer layers ({nh} x {hd}, ffn {ec.ffn}, window {ec.window}), downsample /{ec.ds_stride}, "
+              f"{ec.n_q} of the quantizers ({ec.n_semantic} semantic) x {ec.codebook_size} x {ec.codebook_dim}: "
+              f"{enc_hop(ec)} samples per frame at {ec.sample_rate} Hz; {skipped} decode-side / unkept tensors skipped"]
+    return ec, out, report
+
+
+def convert_speech_tokenizer_encoder(src_dir: str, out_path: str):
+    """speech_tokenizer/ (config.json with `encoder_config` + `encoder_valid_num_quantizers`, *.safetensors with the
+    MimiModel under `encoder.` or bare) -> encoder container for enc_load().  -> (EncConfig, report lines).
+    Parity with a real checkpoint is unpinned (DESIGN.md "Speech tokenizer encoder")."""
+    import json
+    T = _load_safetensors_dir(src_dir)
+    if not T:
+        raise FileNotFoundError(f"no *.safetensors under {src_dir}")
+    cfgj, report = {}, []
+    cj = os.path.join(src_dir, "config.json")
+    n_q = 16
+    if os.path.exists(cj):
+        with open(cj) as f:
+            j = json.load(f)
+        cfgj = j.get("encoder_config", {})
+        if "encoder_valid_num_quantizers" in j:
+            n_q = int(j["encoder_valid_num_quantizers"])
+        else:
+            report.append("config.json has no encoder_valid_num_quantizers: keeping 16 quantizers")
+        if not cfgj:
+            report.append("config.json has no encoder_config: MimiConfig defaults")
+    else:
+        report.append("no config.json: MimiConfig defaults, 16 quantizers")
+    ec, t, rep = state_to_enc(T, cfgj, n_q, where=src_dir)
+    write_pack(out_path, {"enc_sample_rate": float(ec.sample_rate)}, t)
+    return ec, rep + report
