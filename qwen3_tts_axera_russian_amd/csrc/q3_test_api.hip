@@ -2,7 +2,10 @@
 // out).  Built into lib/libqwen3tts_test.so, which links against the product library; NOT part of
 // libqwen3tts.so / llama_wrapper.so.
 #include "q3_model.h"
+#include "q3_voc_ops.h"
 #include <chrono>
+#include <cstring>
+#include <vector>
 
 using namespace q3;
 
@@ -112,6 +115,148 @@ int q3t_linear(int M, int N, int K, const uint16_t* W, int gateup, int pro, int 
         Q3_HIP(hipMemcpy(ap.data(), dact.p, ap.size() * 2, hipMemcpyDeviceToHost), -1);
         for (int m = 0; m < M; m++)
             for (int j = 0; j < N / 2; j++) act_out[(size_t)m * (N / 2) + j] = ap[frag_idx_host(m, j, N / 2)];
+    }
+    return 0;
+}
+
+// One attention call of the talker / code-predictor shape (16 q heads, 8 kv heads, head_dim 128) on host arrays, sent
+// through launch_attn the way run_stack sends it.  mode 0: ATTN_FUSED; mode 1: ATTN_PREP then ATTN_ATTEND (tiles /
+// n_tiles as run_stack passes them: explicit tiles {first row, rows, slot, first position}, or tiles == null with
+// n_tiles = (R + 15) / 16 for one implicit run).  Rows row0 .. row0+R-1 are computed: qkv[R][4096] (f32), slot / pos
+// [R] (or null: *_base + r * *_stride, r counted from row 0) and out[R][2048] (fp16, row-major, in/out: rows the call
+// skips keep what was uploaded) hold those rows; tile rows are absolute (row0 .. row0+R-1).  Caches kc / vc
+// [n_slots][8][n_ctx][128] fp16 are uploaded and returned; rope tables are [max_pos][64].  Every row and tile is
+// checked against the buffers before anything launches (-2); -3: the launch wrote outside rows row0 .. row0+R-1.
+int q3t_attn(int mode, int R, int row0, const float* qkv, const float* q_norm, const float* k_norm, float eps,
+             const float* rope_cos, const float* rope_sin, int max_pos, const int* slot, const int* pos, int slot_base,
+             int slot_stride, int pos_base, int pos_stride, uint16_t* kc, uint16_t* vc, int n_slots, int n_ctx,
+             const int* tiles, int n_tiles, int valid_mod, int valid_n, int threads, uint16_t* out) {
+    constexpr int NH = 16, NKV = 8, D = 128, LD = (NH + 2 * NKV) * D, OW = NH * D;
+    constexpr uint16_t GUARD = 0x7d5au;   // a NaN pattern in the rows outside the call (the kernels never produce it)
+    if (mode != 0 && mode != 1) return -2;
+    if (R <= 0 || row0 < 0 || !qkv || !q_norm || !k_norm || !rope_cos || !rope_sin || !kc || !vc || !out) return -2;
+    if (max_pos <= 0 || n_slots <= 0 || n_ctx <= 0 || threads < 64 || threads > 1024 || threads % 64) return -2;
+    if (valid_mod < 0 || (valid_mod > 0 && (valid_n < 0 || valid_n > valid_mod))) return -2;
+    const int rows = row0 + R;
+    auto skipped = [&](int r) { return valid_mod > 0 && (r % valid_mod) >= valid_n; };
+    auto row_slot = [&](int r) { return slot ? slot[r - row0] : slot_base + r * slot_stride; };
+    auto row_pos = [&](int r) { return pos ? pos[r - row0] : pos_base + r * pos_stride; };
+    // every row the kernels touch: its cache row (written) and its rope row (read)
+    for (int r = row0; r < rows; r++) {
+        if (skipped(r)) continue;
+        const int sl = row_slot(r), p = row_pos(r);
+        if (sl < 0 || sl >= n_slots || p < 0 || p >= n_ctx || p >= max_pos) return -2;
+    }
+    if (mode == 0) {
+        if (n_tiles != 0 || tiles) return -2;
+        // two rows appending to one slot in one FUSED call race (run_stack sends those through PREP + ATTEND)
+        std::vector<char> seen((size_t)n_slots, 0);
+        for (int r = row0; r < rows; r++) {
+            if (skipped(r)) continue;
+            if (seen[(size_t)row_slot(r)]++) return -2;
+        }
+    } else if (n_tiles > 0 && !tiles) {
+        // one implicit run: the form run_stack tiles implicitly, nothing else
+        if (slot || pos || slot_stride != 0 || pos_stride != 1 || valid_mod != 0 || n_tiles != (R + 15) / 16) return -2;
+    } else if (n_tiles > 0) {
+        for (int i = 0; i < n_tiles; i++) {
+            const int* t = tiles + 4 * i;
+            if (t[0] < row0 || t[1] < 1 || t[1] > 16 || t[0] + t[1] > rows) return -2;
+            if (t[2] < 0 || t[2] >= n_slots || t[3] < 0 || t[3] + t[1] > n_ctx) return -2;
+        }
+    } else if (n_tiles < 0 || tiles) {
+        return -2;
+    }
+    hipStream_t s = nullptr;
+    const int Rp = (rows + 15) / 16 * 16;   // the output's fragment order is padded to 16 rows
+    const size_t cache = (size_t)n_slots * NKV * n_ctx * D;
+    std::vector<float> hq((size_t)Rp * LD, 0.f);
+    memcpy(hq.data() + (size_t)row0 * LD, qkv, (size_t)R * LD * 4);
+    std::vector<uint16_t> ho((size_t)Rp * OW, GUARD);
+    for (int r = row0; r < rows; r++)
+        for (int k = 0; k < OW; k++) ho[frag_idx_host(r, k, OW)] = out[(size_t)(r - row0) * OW + k];
+    std::vector<int> hs((size_t)Rp, 0), hp((size_t)Rp, 0);
+    for (int r = row0; r < rows; r++) {
+        if (slot) hs[r] = slot[r - row0];
+        if (pos) hp[r] = pos[r - row0];
+    }
+    DBuf dq, dqn, dkn, dcs, dsn, dkc, dvc, dout, dslot, dpos, dtiles;
+    if (!dq.up(hq.data(), hq.size() * 4) || !dqn.up(q_norm, D * 4) || !dkn.up(k_norm, D * 4) ||
+        !dcs.up(rope_cos, (size_t)max_pos * 64 * 4) || !dsn.up(rope_sin, (size_t)max_pos * 64 * 4) ||
+        !dkc.up(kc, cache * 2) || !dvc.up(vc, cache * 2) || !dout.up(ho.data(), ho.size() * 2) ||
+        !dslot.up(hs.data(), hs.size() * 4) || !dpos.up(hp.data(), hp.size() * 4))
+        return -1;
+    if (tiles && !dtiles.up(tiles, (size_t)n_tiles * 16)) return -1;
+    AttnArgs t;
+    t.qkv = (float*)dq.p;
+    t.ld = LD;
+    t.R = R;
+    t.row0 = row0;
+    t.q_norm = (const float*)dqn.p;
+    t.k_norm = (const float*)dkn.p;
+    t.eps = eps;
+    t.rope_cos = (const float*)dcs.p;
+    t.rope_sin = (const float*)dsn.p;
+    t.slot = slot ? (const int*)dslot.p : nullptr;
+    t.pos = pos ? (const int*)dpos.p : nullptr;
+    t.slot_base = slot_base;
+    t.slot_stride = slot_stride;
+    t.pos_base = pos_base;
+    t.pos_stride = pos_stride;
+    t.kc = (half_t*)dkc.p;
+    t.vc = (half_t*)dvc.p;
+    t.n_ctx = n_ctx;
+    t.n_kv = NKV;
+    t.n_heads = NH;
+    t.out = (half_t*)dout.p;
+    t.scale = 1.0f / sqrtf((float)D);
+    t.threads = threads;
+    t.valid_mod = valid_mod;
+    t.valid_n = valid_n;
+    if (mode == 0) {
+        if (launch_attn(s, t, ATTN_FUSED)) return -1;
+    } else {
+        if (launch_attn(s, t, ATTN_PREP)) return -1;
+        t.tiles = tiles ? (const int*)dtiles.p : nullptr;
+        t.n_tiles = n_tiles;
+        if (launch_attn(s, t, ATTN_ATTEND)) return -1;
+    }
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    Q3_HIP(hipMemcpy(kc, dkc.p, cache * 2, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(vc, dvc.p, cache * 2, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost), -1);
+    for (int r = row0; r < rows; r++)
+        for (int k = 0; k < OW; k++) out[(size_t)(r - row0) * OW + k] = ho[frag_idx_host(r, k, OW)];
+    for (int r = 0; r < Rp; r++) {
+        if (r >= row0 && r < rows) continue;
+        for (int k = 0; k < OW; k++)
+            if (ho[frag_idx_host(r, k, OW)] != GUARD) return -3;
+    }
+    return 0;
+}
+
+// The vocoder's sliding-window RoPE attention on host arrays: x[B][3*H*D][L] (q | k | v, head-major rows of L columns)
+// -> y[B][H*D][L].  kernel 0: voc_attn_kernel (any even D <= 128), 1: voc_attn_tile_kernel (the launcher refuses shapes it
+// does not hold).  The device rows have the vocoder's pitch (L rounded up to 32 floats); -3: a pad column was written.
+int q3t_voc_attn(int kernel, const float* x, float* y, int B, int H, int D, int L, int window, float theta) {
+    constexpr float GUARD = 1234.5f;
+    if ((kernel != 0 && kernel != 1) || !x || !y || B <= 0 || H <= 0 || D <= 0 || D > 128 || (D & 1) || L <= 0 || window <= 0)
+        return -2;
+    const int ld = (L + 31) / 32 * 32;
+    const size_t nx = (size_t)B * 3 * H * D, ny = (size_t)B * H * D;
+    std::vector<float> hx(nx * ld, 0.f), hy(ny * ld, GUARD);
+    for (size_t r = 0; r < nx; r++) memcpy(hx.data() + r * ld, x + r * L, (size_t)L * 4);
+    DBuf dx, dy;
+    if (!dx.up(hx.data(), hx.size() * 4) || !dy.up(hy.data(), hy.size() * 4)) return -1;
+    const int rc = kernel == 0 ? voc_launch_attn(nullptr, (const float*)dx.p, (float*)dy.p, H, D, L, ld, window, theta, B)
+                               : voc_launch_attn_tile(nullptr, (const float*)dx.p, (float*)dy.p, H, D, L, ld, window, theta, B);
+    if (rc) return -2;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    Q3_HIP(hipMemcpy(hy.data(), dy.p, hy.size() * 4, hipMemcpyDeviceToHost), -1);
+    for (size_t r = 0; r < ny; r++) {
+        memcpy(y + r * L, hy.data() + r * ld, (size_t)L * 4);
+        for (int l = L; l < ld; l++)
+            if (hy[r * ld + l] != GUARD) return -3;
     }
     return 0;
 }

@@ -1169,6 +1169,22 @@ int voc_launch_norm(hipStream_t s, const float* x, const float* w, const float* 
     return 0;
 }
 
+int voc_launch_attn_tile(hipStream_t s, const float* x, float* y, int H, int D, int L, int ld, int window, float theta, int B) {
+    const size_t lds = (size_t)3 * L * (D + 1) * sizeof(float);
+    if (D <= 0 || D > 64 || (D & 1) || L <= 0 || lds > 64 * 1024) {
+        Q3_LOG("voc tile attention: head_dim %d at %d columns is not built (even, <= 64, 3 * L * (D + 1) floats <= 64 KiB)", D, L);
+        return -1;
+    }
+    static bool attr = false;
+    if (!attr) {
+        Q3_HIP(hipFuncSetAttribute((const void*)voc_attn_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024), -1);
+        attr = true;
+    }
+    hipLaunchKernelGGL(voc_attn_tile_kernel, dim3(H, B), dim3(256), lds, s, x, y, H, D, L, ld, window, theta);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+
 int voc_launch_attn(hipStream_t s, const float* x, float* y, int H, int D, int L, int ld, int window, float theta, int B) {
     if (D <= 0 || D > 128 || (D & 1)) {
         Q3_LOG("voc attention: head_dim %d is not built (even, <= 128)", D);
@@ -1932,19 +1948,13 @@ static int voc_run(Voc* v, int B, float** out_dev, int n_ops = -1, int* outC = n
                 hipLaunchKernelGGL(chan_norm_kernel, dim3((unsigned)((L + 63) / 64), B), dim3(1024), 0, v->s, in, op.w, op.bias, out, op.cin, (int)L,
                                    ld, op.kind, op.eps);
             else if (op.op == VOP_ATTN) {
-                const size_t tile_lds = (size_t)3 * L * (op.head_dim + 1) * sizeof(float);
-                if (op.head_dim <= 64 && op.head_dim % 2 == 0 && tile_lds <= 64 * 1024) {
-                    static bool attr = false;
-                    if (!attr) {
-                        Q3_HIP(hipFuncSetAttribute((const void*)voc_attn_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   64 * 1024), -1);
-                        attr = true;
-                    }
-                    hipLaunchKernelGGL(voc_attn_tile_kernel, dim3(op.heads, B), dim3(256), tile_lds, v->s, in, out, op.heads,
-                                       op.head_dim, (int)L, ld, op.window, op.theta);
+                // the variant follows the full-length decode's Lf (a short decode runs its model's kernel: same bits per
+                // column); the LDS follows this decode's L <= Lf
+                const size_t tile_lds_full = (size_t)3 * Lf * (op.head_dim + 1) * sizeof(float);
+                if (op.head_dim <= 64 && op.head_dim % 2 == 0 && tile_lds_full <= 64 * 1024) {
+                    if (voc_launch_attn_tile(v->s, in, out, op.heads, op.head_dim, (int)L, ld, op.window, op.theta, B)) return -1;
                 } else {
-                    hipLaunchKernelGGL(voc_attn_kernel, dim3((unsigned)L, op.heads, B), dim3(64), 0, v->s, in, out, op.heads,
-                                       op.head_dim, (int)L, ld, op.window, op.theta);
+                    if (voc_launch_attn(v->s, in, out, op.heads, op.head_dim, (int)L, ld, op.window, op.theta, B)) return -1;
                 }
             }
             else

@@ -46,5 +46,9 @@ int voc_launch_norm(hipStream_t s, const float* x, const float* w, const float* 
 // causal sliding-window attention with rotate-half RoPE, x = [q | k | v] head-major [B][3*H*D][ld] -> y [B][H*D][ld].
 // One wave per (query column, head) walks its keys in order: a column's bits do not depend on L or B.
 int voc_launch_attn(hipStream_t s, const float* x, float* y, int H, int D, int L, int ld, int window, float theta, int B);
+// The same attention with one workgroup per (head, batch entry) holding the head's q, k, v in LDS (voc_attn_tile_kernel,
+// the vocoder's variant for short chunks): head_dim even and <= 64, 3 * L * (D + 1) floats <= 64 KiB; -1 otherwise.
+// Exposed for the kernel-level test hook.
+int voc_launch_attn_tile(hipStream_t s, const float* x, float* y, int H, int D, int L, int ld, int window, float theta, int B);
 
 }  // namespace q3
