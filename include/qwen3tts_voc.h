@@ -46,6 +46,10 @@ int voc_decode(void* v, const int64_t* codes, int B, float* out);
 
 /* VocoderServer.synthesize + int16 conversion for one utterance: codes[n][16] -> out samples.
  * out must hold voc_synthesize_max_samples(n) int16.  Returns 0 and *n_samples, or <0.
+ * It is voc_synthesize_batch with one utterance: the same chunk walk, decodes, placement and int16 rule on the device, so the
+ * two return the same bits for the same utterance.  On the split arithmetic a call in which an activation leaves the fp16
+ * range is redone whole on the exact path (voc_synthesize_batch's rule).  Sets voc_last_batch_ms / voc_last_batch_chunks,
+ * not voc_last_decode_ms.
  * (n > chunk_tokens walks chunks with a 16-frame overlap: needs chunk_tokens > 32.)
  * In the exact-fp32 mode (voc_set_exact_fp32(1)) a chunk of fewer than chunk_tokens frames (an utterance's tail, or a short
  * utterance) is decoded at its own length + 1 pad frame, rounded up to 8, instead of the reference's zero-padded chunk_tokens:
@@ -68,7 +72,7 @@ int voc_synthesize_batch(void* v, const int64_t* codes, const int32_t* n_tokens,
 int voc_synthesize_batch_f32(void* v, const int64_t* codes, const int32_t* n_tokens, int U, float* out, int64_t out_capacity,
                              int64_t* offsets);
 int64_t voc_synthesize_batch_max_samples(void* v, const int32_t* n_tokens, int U);
-/* GPU milliseconds and decoded chunks of the last voc_synthesize_batch* call */
+/* GPU milliseconds and decoded chunks of the last voc_synthesize* or voc_synthesize_batch* call */
 float voc_last_batch_ms(void* v);
 int voc_last_batch_chunks(void* v);
 
@@ -116,8 +120,8 @@ float voc_stream_last_ms(void* s);
  * everywhere.  Measured on MI355X against a float64 evaluation of the same table: max error 2.2e-7 (split)
  * vs 4.0e-7 (exact f32 MFMA) vs 2.1e-7 (torch CPU f32) of full scale -- the split path is fp32-grade, and
  * 2.8x faster at 32 chunks.  Values beyond the fp16 range cannot be split: an op with such a weight stays
- * exact, and a call in which an activation leaves the range is redone on the exact path before voc_decode
- * returns.  Process-wide; env Q3_VOC_EXACT=1 selects the exact path at load. */
+ * exact, and a call in which an activation leaves the range is redone on the exact path before it returns (voc_decode,
+ * voc_synthesize*: the whole call).  Process-wide; env Q3_VOC_EXACT=1 selects the exact path at load. */
 int voc_set_exact_fp32(int on);
 
 /* 1 (default): on the exact-f32 path a residual unit of the 96- / 192-channel decoder blocks (Snake, dilated 7-tap
@@ -135,7 +139,8 @@ int voc_set_fused_units(int on);
  * 234 / 245 ms.  Returns the cap in effect.  Process-wide. */
 int voc_set_max_workgroups(int n);
 
-/* GPU milliseconds of the last voc_decode (HIP events on the library's stream) and its FLOP count. */
+/* GPU milliseconds of the last voc_decode (HIP events on the library's stream; voc_synthesize* leave it alone) and its FLOP
+ * count. */
 float voc_last_decode_ms(void* v);
 double voc_decode_flops(void* v, int B);
 

@@ -65,6 +65,7 @@ from . import hiplib
 from . import protocol as P
 from .engine import FrameEngine, SlotParams
 from .frontend import TextFrontEnd
+from .vocoder import Vocoder
 from .weights import ModelConfig, read_pack
 
 
@@ -102,9 +103,7 @@ class BatchSynthesisServer:
         self.eng.set_sampling(temperature, top_k, top_p, cp_temperature, cp_top_k, seed)
         self.n_ctx = n_ctx
         self._lib = hiplib.load()
-        self.voc = self._lib.voc_load(str(vocoder_path).encode(), 64, min(max_batch, 32))
-        if not self.voc:
-            raise RuntimeError(f"voc_load failed: {vocoder_path}")
+        self.voc = Vocoder(vocoder_path, 64, min(max_batch, 32))
         self.pipeline = bool(pipeline)
         self._pool = None
         self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
@@ -162,24 +161,8 @@ class BatchSynthesisServer:
         return [np.ascontiguousarray(c, dtype=np.int32) for c in per_utt]
 
     def vocode(self, cs):
-        """The vocoder of a request: every utterance's chunk walk in ONE batched call (voc_synthesize_batch: chunks of all
-        utterances decoded together, overlap-crossfade assembled on the device; per utterance = VocoderServer.synthesize +
-        int16) -> list of (codes, pcm int16)."""
-        B = len(cs)
-        live = [b for b in range(B) if cs[b].shape[0] > 0]
-        pcm = {b: np.zeros(0, np.int16) for b in range(B)}
-        if live:
-            n = np.array([cs[b].shape[0] for b in live], np.int32)
-            cat = np.ascontiguousarray(np.concatenate([cs[b] for b in live], axis=0), dtype=np.int64)
-            cap = int(self._lib.voc_synthesize_batch_max_samples(self.voc, hiplib.iptr(n), len(n)))
-            buf = np.empty(cap, np.int16)
-            off = np.zeros(len(n) + 1, np.int64)
-            if self._lib.voc_synthesize_batch(self.voc, cat.ctypes.data_as(hiplib.i64p), hiplib.iptr(n), len(n),
-                                              buf.ctypes.data_as(hiplib.i16p), cap, off.ctypes.data_as(hiplib.i64p)) != 0:
-                raise RuntimeError("voc_synthesize_batch failed")
-            for k, b in enumerate(live):
-                pcm[b] = buf[off[k]:off[k + 1]].copy()
-        return [(cs[b], pcm[b]) for b in range(B)]
+        """The vocoder of a request: every utterance's chunk walk in ONE batched call -> list of (codes, pcm int16)."""
+        return list(zip(cs, self.voc.synthesize_batch(cs)))
 
     def synthesize(self, token_ids, max_tokens=None):
         """-> list of (codes int32 [n_frames][16], pcm int16) per utterance."""
@@ -192,28 +175,14 @@ class BatchSynthesisServer:
         if state["failed"]:
             return
         try:
-            lib, vs = self._lib, self._vstream
             for b in resets:
-                if lib.voc_stream_reset(vs, b) != 0:
-                    raise RuntimeError("voc_stream_reset failed")
+                self._vstream.reset(b)
             if entries:
-                streams = np.array([e[0] for e in entries], np.int32)
-                n_new = np.array([e[2].shape[0] for e in entries], np.int32)
-                fin = np.array([int(e[3]) for e in entries], np.int32)
-                cat = np.ascontiguousarray(np.concatenate([e[2] for e in entries], axis=0), dtype=np.int64).reshape(-1, 16)
-                args = (vs, len(entries), hiplib.iptr(streams))
-                cap = int(lib.voc_stream_push_max_samples(*args, hiplib.iptr(n_new), hiplib.iptr(fin)))
-                if cap < 0:
-                    raise RuntimeError("voc_stream_push: invalid push")
-                buf = np.empty(max(cap, 1), np.int16)
-                off = np.zeros(len(entries) + 1, np.int64)
-                if lib.voc_stream_push(*args, cat.ctypes.data_as(hiplib.i64p), hiplib.iptr(n_new), hiplib.iptr(fin),
-                                       buf.ctypes.data_as(hiplib.i16p), cap, off.ctypes.data_as(hiplib.i64p)) != 0:
-                    raise RuntimeError("voc_stream_push failed")
+                pcm = self._vstream.push([e[0] for e in entries], [e[2] for e in entries], [e[3] for e in entries])
                 out = []
                 for k, (_, utt, _, finished, codes) in enumerate(entries):
-                    if off[k + 1] > off[k]:
-                        out.append(pack_stream_audio(utt, buf[off[k]:off[k + 1]]))
+                    if len(pcm[k]):
+                        out.append(pack_stream_audio(utt, pcm[k]))
                     if finished:
                         out.append(pack_stream_end(utt, codes))
                 if out:
@@ -253,9 +222,7 @@ class BatchSynthesisServer:
         try:
             prefixes, n_text, max_tokens, order = self._queue(token_ids, max_tokens)
             if self._vstream is None:
-                self._vstream = self._lib.voc_stream_create(self.voc, self.max_batch)
-                if not self._vstream:
-                    raise RuntimeError("voc_stream_create failed")
+                self._vstream = self.voc.stream(self.max_batch)
             if self._pool is None:
                 self._lib.voc_set_max_workgroups(-1)     # the pushes run beside the frame loop (restored when the request ends)
             slot_utt = [None] * self.max_batch           # queue index each slot's stream holds
@@ -394,9 +361,7 @@ class BatchSynthesisServer:
     def _serve_concurrent(self, sock):
         """--concurrent: this thread accepts and checks requests; the scheduler's engine thread and vocoder worker do the rest."""
         if self._vstream is None:
-            self._vstream = self._lib.voc_stream_create(self.voc, self.max_batch)
-            if not self._vstream:
-                raise RuntimeError("voc_stream_create failed")
+            self._vstream = self.voc.stream(self.max_batch)
         self._lib.voc_set_max_workgroups(-1)     # the vocoder runs beside the frame loop: one workgroup per CU
         self.sched = ConcurrentScheduler(self.eng, self.max_batch, self.max_queue, self._prepare, self._finish, self._push,
                                          self._close_stream, self._send_error, check_every=self.check_every,
@@ -438,12 +403,10 @@ class BatchSynthesisServer:
             self._pool.shutdown(wait=True)
             self._pool = None
         self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
-        self._vstream = None           # streaming chunk walk: one stream per slot of the frame loop
         if self.pipeline:
             self._lib.voc_set_max_workgroups(0)
-        if self.voc:
-            self._lib.voc_free(self.voc)
-            self.voc = None
+        self.voc.close()               # frees the streaming chunk walk first
+        self._vstream = None
         self.eng.destroy()
 
 

@@ -1249,7 +1249,7 @@ __global__ void __launch_bounds__(256) embmean_kernel(const int64_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------
-// Batched chunk walk (voc_synthesize_batch): the reference assembles an utterance from its 64-frame chunks on the host
+// Chunk walk (voc_synthesize*, voc_synthesize_batch*): the reference assembles an utterance from its 64-frame chunks on the host
 // (vocoder_server.py:84-117: first chunk kept, every next one either cross-faded over 16 frames with the tail of what
 // is there, or -- shorter than the overlap -- appended).  Here the chunks of MANY utterances are decoded max_batch at a
 // time and placed by two launches per batch: every chunk copies its samples behind the blended head to its position,
@@ -1372,13 +1372,12 @@ struct Voc {
     size_t buf_elems = 0;
     float last_ms = 0.f;
     double flops_per_chunk = 0.0;
-    std::vector<float> h_chunk;
-    // batched chunk walk: assembled waveforms of a request (grown on demand) and the per-batch placement table
+    // chunk walk: assembled waveforms of a request (grown on demand) and the per-batch placement table
     float* d_wave = nullptr;
     int16_t* d_wave16 = nullptr;
     size_t wave_cap = 0, wave16_cap = 0;
     ChunkPlace* d_place = nullptr;   // [max_batch]
-    float batch_ms = 0.f;            // GPU time of the last voc_synthesize_batch*
+    float batch_ms = 0.f;            // GPU time of the last voc_synthesize* / voc_synthesize_batch*
     int batch_chunks = 0;            // chunks it decoded
 };
 
@@ -1460,7 +1459,7 @@ void* voc_load(const char* weights, int chunk_tokens, int max_batch) {
         Q3_LOG("%s holds no vocoder program (tensor voc.program int32 [n][8])", weights);
         return nullptr;
     }
-    // (any chunk length decodes; the chunk walk of voc_synthesize needs chunk > 32 and says so itself)
+    // (any chunk length decodes; the chunk walk needs chunk > 32 and says so itself: plan_walk)
     if (const char* ex = getenv("Q3_VOC_EXACT")) g_voc_split = atoi(ex) ? 0 : 1;
     Voc* v = new Voc();
     hipGetDevice(&v->device);
@@ -1777,7 +1776,6 @@ void* voc_load(const char* weights, int chunk_tokens, int max_batch) {
         voc_destroy(v);
         return nullptr;
     }
-    v->h_chunk.resize((size_t)v->chunk_samples);
     return v;
 }
 
@@ -2146,98 +2144,27 @@ int voc_synthesize_max_samples(void* vv, int n) {
     return (n + v->chunk) * v->upsample;  // the reference's redundant tail chunk adds < chunk frames
 }
 
-// VocoderServer.synthesize (vocoder_server.py:73-121), bug-compatible chunk walk, float output.
-int voc_synthesize_f32(void* vv, const int64_t* codes, int n, float* out, int32_t* n_samples) {
-    Voc* v = (Voc*)vv;
-    voc_bind(v);
-    if (!v || !codes || !out || !n_samples || n <= 0) return -1;
-    const int CH = v->chunk, SPT = v->upsample;
-    // numpy slicing, as the reference writes it: `audio[:len * SAMPLES_PER_TOKEN]` of what the model returned --
-    // a decode yields chunk_samples <= CH * SPT samples (the decoder family's transposed convs trim), so a slice is
-    // min(len * SPT, chunk_samples) long (vocoder_server.py:81,98-99)
-    const size_t CS = (size_t)v->chunk_samples;
-    auto sliced = [&](int len) -> size_t { return (size_t)len * SPT < CS ? (size_t)len * SPT : CS; };
-    if (n > CH && CH <= 32) {
-        // the chunk walk steps by chunk - 16 and its output bound (n + chunk) frames needs chunk > 32; the
-        // reference's models are traced at 64 or 256 (scripts/export_vocoder_traced.py)
-        Q3_LOG("voc_synthesize: chunk_tokens=%d is too short for the 16-frame overlap walk (need > 32)", CH);
-        return -1;
-    }
-    std::vector<int64_t> padded((size_t)CH * 16);
-    std::vector<float>& chunk = v->h_chunk;
-    auto run_chunk = [&](int start, int len) -> int {
-        std::fill(padded.begin(), padded.end(), 0);
-        memcpy(padded.data(), codes + (size_t)start * 16, sizeof(int64_t) * 16 * len);
-        const int T = voc_decode_frames(v, len);
-        if (T == CH) return voc_decode(v, padded.data(), 1, chunk.data());
-        // a short chunk: decoded at T frames (same bits for the samples the walk keeps), only those samples come back
-        Q3_HIP(hipMemcpyAsync(v->d_codes, padded.data(), sizeof(int64_t) * 16 * (size_t)T, hipMemcpyHostToDevice, v->s), -1);
-        Q3_HIP(hipEventRecord(v->e0, v->s), -1);
-        float* res = nullptr;
-        long LL = 0;
-        if (voc_run(v, 1, &res, -1, nullptr, &LL, nullptr, false, T)) return -1;
-        Q3_HIP(hipEventRecord(v->e1, v->s), -1);
-        if ((size_t)LL < sliced(len)) {
-            Q3_LOG("voc_synthesize: a decode of %d frames yields %ld samples, fewer than the %zu kept", T, LL, sliced(len));
-            return -1;
-        }
-        Q3_HIP(hipMemcpyAsync(chunk.data(), res, sizeof(float) * sliced(len), hipMemcpyDeviceToHost, v->s), -1);
-        Q3_HIP(hipStreamSynchronize(v->s), -1);
-        hipEventElapsedTime(&v->last_ms, v->e0, v->e1);
-        return 0;
-    };
-    if (n <= CH) {
-        if (run_chunk(0, n)) return -1;
-        memcpy(out, chunk.data(), sizeof(float) * sliced(n));
-        *n_samples = (int32_t)sliced(n);
-        return 0;
-    }
-    const int OVERLAP = 16, OV = OVERLAP * SPT, step = CH - OVERLAP;
-    const size_t capacity = (size_t)voc_synthesize_max_samples(v, n);   // what callers size `out` with
-    size_t have = 0;
-    for (int start = 0; start < n; start += step) {
-        const int len = (start + CH <= n) ? CH : n - start;
-        if (run_chunk(start, len)) return -1;
-        const size_t cl = sliced(len);
-        if (have + cl > capacity) {
-            Q3_LOG("voc_synthesize: chunk walk would pass the output bound (%zu + %zu > %zu)", have, cl, capacity);
-            return -1;
-        }
-        if (start == 0) {
-            memcpy(out, chunk.data(), sizeof(float) * cl);
-            have = cl;
-        } else if (have >= (size_t)OV && cl >= (size_t)OV) {
-            // np.linspace(1, 0, OV, dtype=float32) fade-out, fade-in = 1 - fade-out, blended in float32
-            float* tail = out + have - OV;
-            for (int i = 0; i < OV; i++) {
-                const double stepv = -1.0 / (double)(OV - 1);
-                const float fo = (i == OV - 1) ? 0.0f : (float)(1.0 + (double)i * stepv);
-                const float fi = 1.0f - fo;
-                tail[i] = tail[i] * fo + chunk[i] * fi;
-            }
-            memcpy(out + have, chunk.data() + OV, sizeof(float) * (cl - OV));
-            have += cl - OV;
-        } else {
-            memcpy(out + have, chunk.data(), sizeof(float) * cl);
-            have += cl;
-        }
-    }
-    *n_samples = (int32_t)have;
-    return 0;
-}
-
-// ---- batched VocoderServer.synthesize ----
+// ---- VocoderServer.synthesize (vocoder_server.py:73-121), bug-compatible chunk walk, for U utterances at once ----
 namespace {
 struct WalkChunk { int utt, start, len; size_t cl; int head; long long dst; };
 
 // the reference's walk for one utterance of n frames whose output starts at sample `base` -> its chunks, returns its length
-size_t plan_walk(const Voc* v, int u, int n, long long base, std::vector<WalkChunk>& out) {
+// (<0: the chunk is too short for the walk)
+long long plan_walk(const Voc* v, int u, int n, long long base, std::vector<WalkChunk>& out) {
     const int CH = v->chunk, SPT = v->upsample;
     const size_t CS = (size_t)v->chunk_samples, OV = (size_t)16 * SPT;
+    if (n > CH && CH <= 32) {
+        // the walk steps by chunk - 16 and its output bound (n + chunk) frames needs chunk > 32; the reference's models are
+        // traced at 64 or 256 (scripts/export_vocoder_traced.py)
+        Q3_LOG("vocoder chunk walk: chunk_tokens=%d is too short for the 16-frame overlap walk (need > 32)", CH);
+        return -1;
+    }
+    // numpy slicing, as the reference writes it: `audio[:len * SAMPLES_PER_TOKEN]` of what the model returned -- a decode
+    // yields chunk_samples <= CH * SPT samples (the decoder family's transposed convs trim) (vocoder_server.py:81,98-99)
     auto sliced = [&](int len) -> size_t { return (size_t)len * SPT < CS ? (size_t)len * SPT : CS; };
     if (n <= CH) {
         out.push_back({u, 0, n, sliced(n), 0, base});
-        return sliced(n);
+        return (long long)sliced(n);
     }
     size_t have = 0;
     for (int start = 0; start < n; start += CH - 16) {
@@ -2254,7 +2181,7 @@ size_t plan_walk(const Voc* v, int u, int n, long long base, std::vector<WalkChu
             have += cl;
         }
     }
-    return have;
+    return (long long)have;
 }
 
 extern "C++" {   // (the walk helpers sit inside the extern "C" block of the entry points)
@@ -2336,7 +2263,6 @@ int grow(T** p, size_t* cap, size_t n) {
 int synth_batch(Voc* v, const int64_t* codes, const int32_t* n_tokens, int U, int64_t* offsets, bool want16, void* out, int64_t cap) {
     voc_bind(v);
     if (!v || !codes || !n_tokens || !offsets || !out || U <= 0) return -1;
-    const int CH = v->chunk;
     std::vector<WalkChunk> walk;
     std::vector<size_t> code_off(U);
     long long total = 0;
@@ -2346,14 +2272,12 @@ int synth_batch(Voc* v, const int64_t* codes, const int32_t* n_tokens, int U, in
             Q3_LOG("voc_synthesize_batch: utterance %d has %d frames", u, n_tokens[u]);
             return -1;
         }
-        if (n_tokens[u] > CH && CH <= 32) {
-            Q3_LOG("voc_synthesize_batch: chunk_tokens=%d is too short for the 16-frame overlap walk (need > 32)", CH);
-            return -1;
-        }
+        const long long len = plan_walk(v, u, n_tokens[u], total, walk);
+        if (len < 0) return -1;
         offsets[u] = total;
         code_off[u] = coff;
         coff += (size_t)n_tokens[u] * 16;
-        total += (long long)plan_walk(v, u, n_tokens[u], total, walk);
+        total += len;
     }
     offsets[U] = total;
     if (total > cap) {
@@ -2438,17 +2362,14 @@ int plan_push(const VocStream* s, int n, const int32_t* streams, const int32_t* 
         }
         const bool fin = finish && finish[i];
         const int N = t.n_frames + n_new[i];
-        if (N > CH && CH <= 32) {
-            Q3_LOG("voc_stream_push: chunk_tokens=%d is too short for the 16-frame overlap walk (need > 32)", CH);
-            return -1;
-        }
         p.have[i] = t.have;
         p.n_chunks[i] = t.n_chunks;
         if (N > 0) {
             // the walk of the N frames so far; its first chunks are final once all their frames are here (a full chunk whatever
             // follows), the rest only when the utterance ends
             full.clear();
-            const long long total = (long long)plan_walk(v, i, N, 0, full);
+            const long long total = plan_walk(v, i, N, 0, full);
+            if (total < 0) return -1;
             int c = t.n_chunks;
             for (; c < (int)full.size() && (fin || full[c].start + CH <= N); c++) {
                 p.walk.push_back(full[c]);
@@ -2584,6 +2505,21 @@ int voc_synthesize_batch(void* vv, const int64_t* codes, const int32_t* n_tokens
     return synth_batch((Voc*)vv, codes, n_tokens, U, offsets, true, out, out_capacity);
 }
 
+// one utterance: the batched walk with U = 1
+int voc_synthesize_f32(void* vv, const int64_t* codes, int n, float* out, int32_t* n_samples) {
+    int64_t offsets[2];
+    if (!n_samples || synth_batch((Voc*)vv, codes, &n, 1, offsets, false, out, voc_synthesize_max_samples(vv, n))) return -1;
+    *n_samples = (int32_t)offsets[1];
+    return 0;
+}
+
+int voc_synthesize(void* vv, const int64_t* codes, int n, int16_t* out, int32_t* n_samples) {
+    int64_t offsets[2];
+    if (!n_samples || synth_batch((Voc*)vv, codes, &n, 1, offsets, true, out, voc_synthesize_max_samples(vv, n))) return -1;
+    *n_samples = (int32_t)offsets[1];
+    return 0;
+}
+
 void* voc_stream_create(void* vv, int max_streams) {
     Voc* v = (Voc*)vv;
     if (!v || max_streams <= 0) return nullptr;
@@ -2644,19 +2580,5 @@ float voc_stream_last_ms(void* s) { return s ? ((VocStream*)s)->last_ms : -1.f; 
 
 float voc_last_batch_ms(void* vv) { return vv ? ((Voc*)vv)->batch_ms : -1.f; }
 int voc_last_batch_chunks(void* vv) { return vv ? ((Voc*)vv)->batch_chunks : 0; }
-
-int voc_synthesize(void* vv, const int64_t* codes, int n, int16_t* out, int32_t* n_samples) {
-    Voc* v = (Voc*)vv;
-    if (!v || !out) return -1;
-    std::vector<float> f((size_t)voc_synthesize_max_samples(v, n));
-    if (voc_synthesize_f32(v, codes, n, f.data(), n_samples)) return -1;
-    for (int32_t i = 0; i < *n_samples; i++) {
-        // np.clip(audio * 32767, -32768, 32767).astype(np.int16): float32 product, truncation toward zero
-        float x = f[i] * 32767.0f;
-        x = x < -32768.0f ? -32768.0f : (x > 32767.0f ? 32767.0f : x);
-        out[i] = (int16_t)x;
-    }
-    return 0;
-}
 
 }  // extern "C"

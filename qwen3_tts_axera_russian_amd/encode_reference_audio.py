@@ -66,26 +66,18 @@ def open_encoder(model, max_samples):
 
 def decode_back(codes, vocoder, out_wav):
     """The reference's "decode back" step: codes -> voc_synthesize (int16, 24 kHz) -> WAV."""
-    from . import hiplib
-    lib = hiplib.load()
-    h = lib.voc_load(str(vocoder).encode(), 64, 1)
-    if not h:
-        raise RuntimeError(f"voc_load({vocoder}) failed")
+    from .vocoder import Vocoder
+    voc = Vocoder(vocoder)
     try:
-        codes = np.ascontiguousarray(codes, np.int64)
-        out = np.zeros(lib.voc_synthesize_max_samples(h, codes.shape[0]), np.int16)
-        n = np.zeros(1, np.int32)
-        if lib.voc_synthesize(h, codes.ctypes.data_as(hiplib.i64p), codes.shape[0], out.ctypes.data_as(hiplib.i16p),
-                              n.ctypes.data_as(hiplib.i32p)) != 0:
-            raise RuntimeError("voc_synthesize failed")
+        pcm = voc.synthesize(codes, int16=True)
     finally:
-        lib.voc_free(h)
+        voc.close()
     with wave.open(out_wav, "w") as wf:
         wf.setnchannels(1)
         wf.setsampwidth(2)
         wf.setframerate(24000)
-        wf.writeframes(out[:int(n[0])].tobytes())
-    return int(n[0])
+        wf.writeframes(pcm.tobytes())
+    return len(pcm)
 
 
 def main(argv=None, encoder_factory=open_encoder):

@@ -31,6 +31,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 from qwen3_tts_axera_russian_amd import hiplib  # noqa: E402
 from qwen3_tts_axera_russian_amd.engine import FrameEngine  # noqa: E402
+from qwen3_tts_axera_russian_amd.vocoder import Vocoder  # noqa: E402
 
 
 def pct(xs):
@@ -38,7 +39,7 @@ def pct(xs):
     return {"p50": round(float(np.median(xs)), 1), "max": round(float(xs.max()), 1)} if len(xs) else None
 
 
-def run_stream(lib, eng, vs, pool, prefixes, n_text, frames, ignore_eos):
+def run_stream(eng, vs, pool, prefixes, n_text, frames, ignore_eos):
     U = len(prefixes)
     first, last = [None] * U, [None] * U
     pcm = [[] for _ in range(U)]
@@ -50,28 +51,20 @@ def run_stream(lib, eng, vs, pool, prefixes, n_text, frames, ignore_eos):
     def push(resets, entries):
         ts = time.perf_counter()
         for b in resets:
-            assert lib.voc_stream_reset(vs, b) == 0
-        streams = np.array([e[0] for e in entries], np.int32)
-        n_new = np.array([len(e[2]) for e in entries], np.int32)
-        fin = np.array([int(e[3]) for e in entries], np.int32)
-        cat = np.ascontiguousarray(np.concatenate([e[2] for e in entries]), np.int64).reshape(-1, 16)
-        cap = int(lib.voc_stream_push_max_samples(vs, len(entries), hiplib.iptr(streams), hiplib.iptr(n_new), hiplib.iptr(fin)))
-        buf = np.empty(max(cap, 1), np.int16)
-        off = np.zeros(len(entries) + 1, np.int64)
-        assert lib.voc_stream_push(vs, len(entries), hiplib.iptr(streams), cat.ctypes.data_as(hiplib.i64p), hiplib.iptr(n_new),
-                                   hiplib.iptr(fin), buf.ctypes.data_as(hiplib.i16p), cap, off.ctypes.data_as(hiplib.i64p)) == 0
+            vs.reset(b)
+        got = vs.push([e[0] for e in entries], [e[2] for e in entries], [e[3] for e in entries])
         now = (time.perf_counter() - t0) * 1e3
         for k, (_, u, _, f) in enumerate(entries):
-            if off[k + 1] > off[k]:
-                pcm[u].append(buf[off[k]:off[k + 1]].copy())
+            if len(got[k]):
+                pcm[u].append(got[k])
                 if first[u] is None:
                     first[u] = now
             if f:
                 last[u] = now
         stats["pushes"] += 1
-        stats["decode_calls"] += int(lib.voc_stream_last_decodes(vs))
-        stats["chunks"] += int(lib.voc_stream_last_chunks(vs))
-        stats["push_gpu_ms"] += float(lib.voc_stream_last_ms(vs))
+        stats["decode_calls"] += vs.last_decodes
+        stats["chunks"] += vs.last_chunks
+        stats["push_gpu_ms"] += vs.last_ms
         stats["push_wall_ms"] += (time.perf_counter() - ts) * 1e3
 
     def on_frames(codes, per, owner, ended):
@@ -105,7 +98,7 @@ def run_stream(lib, eng, vs, pool, prefixes, n_text, frames, ignore_eos):
     return got, out, first, last, wall, t_loop, stats
 
 
-def run_batch(lib, eng, voc, prefixes, n_text, frames, ignore_eos):
+def run_batch(eng, voc, prefixes, n_text, frames, ignore_eos):
     U = len(prefixes)
     t0 = time.perf_counter()
     eng.start(prefixes, n_text, ignore_eos=ignore_eos, max_frames=frames)
@@ -113,19 +106,10 @@ def run_batch(lib, eng, voc, prefixes, n_text, frames, ignore_eos):
     codes, per = eng.codes()
     cs = [np.ascontiguousarray(codes[:int(per[b]), b, :]) for b in range(U)]
     t_loop = (time.perf_counter() - t0) * 1e3
-    live = [b for b in range(U) if len(cs[b])]
-    n = np.array([len(cs[b]) for b in live], np.int32)
-    cat = np.ascontiguousarray(np.concatenate([cs[b] for b in live]), np.int64)
-    cap = int(lib.voc_synthesize_batch_max_samples(voc, hiplib.iptr(n), len(n)))
-    buf = np.empty(cap, np.int16)
-    off = np.zeros(len(n) + 1, np.int64)
-    assert lib.voc_synthesize_batch(voc, cat.ctypes.data_as(hiplib.i64p), hiplib.iptr(n), len(n), buf.ctypes.data_as(hiplib.i16p),
-                                    cap, off.ctypes.data_as(hiplib.i64p)) == 0
+    out = voc.synthesize_batch(cs)
     wall = (time.perf_counter() - t0) * 1e3
-    out = [np.zeros(0, np.int16)] * U
-    for k, b in enumerate(live):
-        out[b] = buf[off[k]:off[k + 1]].copy()
-    stats = {"decode_calls": None, "chunks": int(lib.voc_last_batch_chunks(voc)), "vocoder_gpu_ms": round(float(lib.voc_last_batch_ms(voc)), 1)}
+    chunks, ms = voc.last_batch()
+    stats = {"decode_calls": None, "chunks": chunks, "vocoder_gpu_ms": round(ms, 1)}
     return cs, out, [wall] * U, [wall] * U, wall, t_loop, stats
 
 
@@ -148,9 +132,8 @@ def main():
     eng = FrameEngine(path, max_batch=U, n_ctx=max(p.shape[0] for p in prefixes) + a.frames + 8, max_frames=a.frames)
     eng.set_pad_embed(pad)
     lib.voc_set_exact_fp32(1)
-    voc = lib.voc_load(voc_path.encode(), 64, min(U, 32))
-    vs = lib.voc_stream_create(voc, U)
-    assert voc and vs
+    voc = Vocoder(voc_path, 64, min(U, 32))
+    vs = voc.stream(U)
     pool = ThreadPoolExecutor(max_workers=1)
     result = {"what": "first / last final sample per utterance of one request, streaming chunk walk vs generate-then-vocode",
               "utterances": U, "max_frames": a.frames, "repeats": a.repeats, "vocoder": "full table, exact fp32, int16 out",
@@ -162,10 +145,10 @@ def main():
                 for mode in ("stream", "batch"):
                     if mode == "stream":
                         lib.voc_set_max_workgroups(-1)
-                        r = run_stream(lib, eng, vs, pool, prefixes, n_text, a.frames, ignore_eos)
+                        r = run_stream(eng, vs, pool, prefixes, n_text, a.frames, ignore_eos)
                     else:
                         lib.voc_set_max_workgroups(0)
-                        r = run_batch(lib, eng, voc, prefixes, n_text, a.frames, ignore_eos)
+                        r = run_batch(eng, voc, prefixes, n_text, a.frames, ignore_eos)
                     if rep > 0:
                         runs[mode].append(r)
             # the two paths give the same codes and the same PCM, bit for bit
@@ -200,8 +183,7 @@ def main():
         pool.shutdown()
         lib.voc_set_max_workgroups(0)
         lib.voc_set_exact_fp32(0)
-        lib.voc_stream_free(vs)
-        lib.voc_free(voc)
+        voc.close()
         eng.destroy()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -435,6 +435,25 @@ def test_split_arithmetic_falls_back_when_out_of_fp16_range(gpu_lib, tiny_voc, t
             np.testing.assert_array_equal(outs[0], outs[1])        # the whole call was redone exactly
         else:
             assert np.abs(outs[0] - outs[1]).max() < 2e-4          # that op exact, the others split
+    # the chunk walk of a multi-chunk utterance: on the split path the whole call is redone exactly, by the single-utterance
+    # entry point and the batched one alike
+    utt = np.random.default_rng(18).integers(0, 2048, size=(150, 16)).astype(np.int64)
+    walks = {}
+    for exact in (1, 0):
+        gpu_lib.voc_set_exact_fp32(exact)
+        v = Voc(gpu_lib, p_act, max_batch=2)
+        walks[exact] = v.synth_f32(utt).copy()
+        if not exact:
+            nn = np.array([150], np.int32)
+            out = np.empty(gpu_lib.voc_synthesize_max_samples(v.h, 150), np.float32)
+            off = np.zeros(2, np.int64)
+            assert gpu_lib.voc_synthesize_batch_f32(v.h, utt.ctypes.data_as(hiplib.i64p), hiplib.iptr(nn), 1, hiplib.fptr(out),
+                                                    len(out), off.ctypes.data_as(hiplib.i64p)) == 0
+            np.testing.assert_array_equal(walks[0], out[off[0]:off[1]])
+        v.close()
+    gpu_lib.voc_set_exact_fp32(0)
+    assert np.isfinite(walks[0]).all()
+    np.testing.assert_array_equal(walks[0], walks[1])
 
 
 @pytest.mark.parametrize("trim", ["both", "right"])
