@@ -172,6 +172,14 @@ int launch_pack_linear(hipStream_t s, const half_t* src, int N, int K, half_t* d
     return 0;
 }
 
+// Which instantiation the last launch_linear call picked ("" when it launched nothing): the kernel-level tests assert
+// the dispatch instead of guessing it.  Every launcher below formats its name once and stores the pointer per launch.
+static const char* g_last_variant = "";
+const char* last_linear_variant() { return g_last_variant; }
+static const char* pro_name(int pro) { return pro == PRO_NORM ? "NORM" : "F16"; }
+static const char* epi_name(int epi) { return epi == EPI_STORE ? "STORE" : epi == EPI_RESID ? "RESID" : "SWIGLU"; }
+static int env_int(const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; }
+
 // ---------------------------------------------------------------------------
 // linear_kernel<NB16, MT16, KBW, NW, PRO, EPI, NT>
 //   workgroup = NW waves; it owns NB16 column tiles (16 weight rows each) for
@@ -385,6 +393,10 @@ static int launch_linear_nt(hipStream_t s, const LinArgs& a) {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), -1);
         attr_set = true;
     }
+    static char name[64];
+    if (!name[0])
+        snprintf(name, sizeof(name), "linear<%d,%d,%d,%d,%s,%s,%s>", NB16, MT16, KBW, NW, pro_name(PRO), epi_name(EPI), NT ? "nt" : "t");
+    g_last_variant = name;
     LinArgs b = a;
     b.tl_node = tl_next_node();
     const unsigned nt_ = a.N / (16 * NB16), nr_ = (a.M - a.m_begin + MR - 1) / MR;
@@ -686,20 +698,11 @@ __global__ void __launch_bounds__(512) gemm_glds_kernel(LinArgs a) {
 }
 
 // 1 (default): operand stream by LDS-DMA into a 4-stage ring (gemm_glds_kernel); 0: register-staged double buffer
-static int g_gemm_glds = getenv("Q3_GEMM_GLDS") ? atoi(getenv("Q3_GEMM_GLDS")) : 1;
+static int g_gemm_glds = env_int("Q3_GEMM_GLDS", 1);
 int set_gemm_glds(int on) { g_gemm_glds = on; return 0; }
 
 template <int BM, int BN, int PRO, int EPI>
 static int launch_gemm_t(hipStream_t s, const LinArgs& a) {
-    constexpr int KS = 1024 / (BM + BN);    // 128 x 128: 4 k-blocks (128 k) per stage; 64 x 64: 8
-    constexpr size_t lds = (size_t)2 * ((BM + BN) / 16) * KS * 1024;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (lds > 48 * 1024)
-            Q3_HIP(hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, KS, PRO, EPI>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), -1);
-        attr_set = true;
-    }
     LinArgs b = a;
     b.tl_node = tl_next_node();
     dim3 grid(((a.M - a.m_begin + BM - 1) / BM) * (a.N / BN));   // 1-D: the kernels map it to tiles XCD by XCD
@@ -722,9 +725,30 @@ static int launch_gemm_t(hipStream_t s, const LinArgs& a) {
             Q3_LOG("launch_gemm: K=%d is no multiple of %d", a.K, 32 * KS2);
             return -1;
         }
+        static char name[64];
+        if (!name[0])
+            snprintf(name, sizeof(name), "gemm_glds<%d,%d,%d,%s,%s,%d>", BM, BN, NBUF, pro_name(PRO), epi_name(EPI), KS2);
+        g_last_variant = name;
         hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, NBUF, PRO, EPI, KS2>), grid, dim3(512), lds2, s, b);
-    } else {
+    } else if constexpr (BM + BN <= 256) {
+        constexpr int KS = 1024 / (BM + BN);    // 128 x 128: 4 k-blocks (128 k) per stage; 64 x 64: 8
+        constexpr size_t lds = (size_t)2 * ((BM + BN) / 16) * KS * 1024;
+        static bool attr_set = false;
+        if (!attr_set) {
+            if (lds > 48 * 1024)
+                Q3_HIP(hipFuncSetAttribute((const void*)gemm_kernel<BM, BN, KS, PRO, EPI>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), -1);
+            attr_set = true;
+        }
+        static char name[64];
+        if (!name[0]) snprintf(name, sizeof(name), "gemm<%d,%d,%d,%s,%s>", BM, BN, KS, pro_name(PRO), epi_name(EPI));
+        g_last_variant = name;
         hipLaunchKernelGGL((gemm_kernel<BM, BN, KS, PRO, EPI>), grid, dim3(256), lds, s, b);
+    } else {
+        // the 128 x 192 tile exists for the LDS-DMA ring only (launch_gemm picks it only with g_gemm_glds): no
+        // register-staged instantiation of it is compiled
+        Q3_LOG("launch_gemm: no register-staged %d x %d tile", BM, BN);
+        return -1;
     }
     Q3_HIP(hipGetLastError(), -1);
     return 0;
@@ -770,6 +794,7 @@ int set_linear_wide_tiles(int on) { g_wide_tiles = on; return 0; }
 static int g_split_rows_narrow = 1;
 int set_linear_split_rows(int on) { g_split_rows_narrow = on; return 0; }
 // k-blocks per wave by [K = 1024, 2048, 3072][rows <= 16, <= 32, more]
+static const int g_tune_kbw_default[3][3] = {{4, 4, 4}, {16, 8, 8}, {12, 6, 6}};
 static int g_tune_kbw[3][3] = {{4, 4, 4}, {16, 8, 8}, {12, 6, 6}};
 int set_linear_tuning(int K, int mt16, int kbw) {
     int i = K == 1024 ? 0 : K == 2048 ? 1 : K == 3072 ? 2 : -1;
@@ -861,13 +886,19 @@ __global__ void __launch_bounds__(NW * 64)
     }
 }
 
-static int g_narrow8 = getenv("Q3_LINEAR_NARROW8") ? atoi(getenv("Q3_LINEAR_NARROW8")) : 1;
+static int g_narrow8 = env_int("Q3_LINEAR_NARROW8", 1);
 int set_linear_narrow8(int on) { g_narrow8 = on; return 0; }
 
 template <int KBW, int NW>
 static int launch_linear_narrow_t(hipStream_t s, const LinArgs& a) {
     const int groups = (a.M - a.m_begin + 7) / 8;
     const int node = tl_next_node();
+    static char name[2][32];
+    if (!name[0][0]) {
+        snprintf(name[0], sizeof(name[0]), "narrow<%d,%d,t>", KBW, NW);
+        snprintf(name[1], sizeof(name[1]), "narrow<%d,%d,nt>", KBW, NW);
+    }
+    g_last_variant = name[a.nt ? 1 : 0];
     if (a.nt)
         hipLaunchKernelGGL((linear_narrow_kernel<KBW, NW, true>), dim3(64, groups), dim3(NW * 64), 0, s, a.wp, a.x16, a.h_out, a.gamma,
                            a.ssq_out, a.xh_out, a.M, a.m_begin, node);
@@ -887,7 +918,19 @@ static int launch_linear_narrow_t(hipStream_t s, const LinArgs& a) {
     Q3_LIN_CASE(NB16_, 2, KBW_, NW_, PRO_, EPI_) \
     Q3_LIN_CASE(NB16_, 4, KBW_, NW_, PRO_, EPI_)
 
+// every dispatch knob of launch_linear back to what a fresh process starts with (the two environment defaults re-read)
+int reset_linear_knobs() {
+    memcpy(g_tune_kbw, g_tune_kbw_default, sizeof(g_tune_kbw));
+    g_wide_tiles = 0;
+    g_split_rows_narrow = 1;
+    g_gemm_min_rows = 65;
+    g_narrow8 = env_int("Q3_LINEAR_NARROW8", 1);
+    g_gemm_glds = env_int("Q3_GEMM_GLDS", 1);
+    return 0;
+}
+
 int launch_linear(hipStream_t s, const LinArgs& a, int pro, int epi) {
+    g_last_variant = "";
     const int rows = a.M - a.m_begin;
     if (rows <= 0) return 0;
     if (rows >= g_gemm_min_rows) return launch_gemm(s, a, pro, epi);

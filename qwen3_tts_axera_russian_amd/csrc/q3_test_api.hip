@@ -17,6 +17,8 @@ int set_linear_wide_tiles(int on);
 int set_attn_short(int on);
 int set_gemm_min_rows(int n);
 int set_gemm_glds(int on);
+int reset_linear_knobs();
+const char* last_linear_variant();
 }
 
 namespace {
@@ -41,6 +43,10 @@ int q3t_set_attn_short(int on) { return set_attn_short(on); }
 int q3t_set_gemm_min_rows(int n) { return set_gemm_min_rows(n); }
 // 1: LDS-DMA ring GEMM (default), 0: the register-staged double-buffer GEMM
 int q3t_set_gemm_glds(int on) { return set_gemm_glds(on); }
+// every launch_linear dispatch knob back to its start-up value (Q3_LINEAR_NARROW8 / Q3_GEMM_GLDS re-read from the environment)
+int q3t_reset_linear_knobs() { return reset_linear_knobs(); }
+// the instantiation the last launch_linear call picked, e.g. "linear<1,2,4,8,NORM,STORE,nt>" ("" = it launched nothing)
+const char* q3t_last_linear_variant() { return last_linear_variant(); }
 
 // One linear launch.  W is row-major fp16 [N][K]; gateup != 0 means rows [0,N/2) are gate and
 // [N/2,N) up (tile-interleaved on the device like the model loader does).
@@ -117,6 +123,155 @@ int q3t_linear(int M, int N, int K, const uint16_t* W, int gateup, int pro, int 
             for (int j = 0; j < N / 2; j++) act_out[(size_t)m * (N / 2) + j] = ap[frag_idx_host(m, j, N / 2)];
     }
     return 0;
+}
+
+// One linear launch with the whole LinArgs surface, sent through launch_linear the way run_stack sends it: rows
+// [m_begin, M) of an M-row buffer are computed.  W is row-major fp16 [N][K] (gateup: rows [0, N/2) gate, [N/2, N) up,
+// tile-interleaved on the device like the model loader does).  Host arrays hold rows [0, M), row-major:
+//   pro 0 (PRO_F16):  x16[M][K] in.   pro 1 (PRO_NORM): h[M][K], gamma[K] in; launch_ssq_rows produces the GEMM input, and
+//                     what it left on the device comes back in pro_h[M][K], pro_ssq[M][K/16], pro_xh[M][K]
+//   epi 0: y[M][ldy] out.  epi 1: h_io[M][N] in/out, ssq_out[M][N/16] out, xh_out[M][N] out when gamma_next[N] is given
+//   (xh_out without gamma_next, or gamma_next without xh_out: -2).  epi 2: act[M][N/2] out.
+// Padding rows of the inputs (>= M) hold finite poison; every output buffer is filled with a NaN sentinel over its
+// padded extent first, and -3 is returned when anything outside rows [m_begin, M) x columns [0, N) changed (rows of
+// h_io inside keep the caller's values as their start).  Rows [m_begin, M) come back; the others are left as the
+// caller passed them.  -2: arguments launch_linear's callers never pass, or no instantiation -- checked before the
+// linear launch; -1: a HIP error.
+int q3t_linear_case(int M, int m_begin, int N, int K, const uint16_t* W, int gateup, int pro, int epi, int nt, float eps,
+                    int ldy, const uint16_t* x16, const float* h, const float* gamma, const float* gamma_next,
+                    float* pro_h, float* pro_ssq, uint16_t* pro_xh, float* y, float* h_io, float* ssq_out,
+                    uint16_t* xh_out, uint16_t* act) {
+    constexpr uint32_t GUARD32 = 0x7fc5a5a5u;   // NaN patterns no kernel produces
+    constexpr uint16_t GUARD16 = 0x7d5au;
+    constexpr uint16_t POISON16 = 0x7753u;      // fp16 30000: what an unused padding row of an activation may hold
+    if (M <= 0 || m_begin < 0 || m_begin >= M || m_begin % 16 || !W) return -2;
+    if ((K != 1024 && K != 2048 && K != 3072) || N <= 0 || N % 32) return -2;
+    if ((pro != PRO_F16 && pro != PRO_NORM) || (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_SWIGLU)) return -2;
+    if (nt != 0 && nt != 1) return -2;
+    if (pro == PRO_F16 && !x16) return -2;
+    if (pro == PRO_NORM && (!h || !gamma || K != 1024 || !pro_h || !pro_ssq || !pro_xh)) return -2;   // 64 partials per row
+    if (epi == EPI_STORE && (!y || ldy < N || gateup)) return -2;
+    if (epi == EPI_RESID && (!h_io || !ssq_out || gateup || (xh_out != nullptr) != (gamma_next != nullptr))) return -2;
+    if (epi == EPI_SWIGLU && (!act || !gateup || N % 64)) return -2;
+    if (epi != EPI_RESID && (xh_out || gamma_next)) return -2;
+    hipStream_t s = nullptr;
+    const int Mp = m_begin + (M - m_begin + 127) / 128 * 128;   // every row tile of every kernel starts at m_begin
+    const int NA = N / 2;
+    DBuf dW, dWp, dx, dhrows, dh, dssq, dg, dgn, dy, dho, dso, dxo, dact;
+    if (!dW.up(W, (size_t)N * K * 2) || !dWp.alloc((size_t)N * K * 2)) return -1;
+    if (gateup) {
+        if (launch_pack_linear(s, (const half_t*)dW.p, N / 2, K, (half_t*)dWp.p, 0, 2)) return -1;
+        if (launch_pack_linear(s, (const half_t*)dW.p + (size_t)(N / 2) * K, N / 2, K, (half_t*)dWp.p, 1, 2)) return -1;
+    } else {
+        if (launch_pack_linear(s, (const half_t*)dW.p, N, K, (half_t*)dWp.p, 0, 1)) return -1;
+    }
+    LinArgs a;
+    a.wp = (const half_t*)dWp.p;
+    a.N = N;
+    a.K = K;
+    a.M = M;
+    a.m_begin = m_begin;
+    a.nt = nt;
+    std::vector<uint16_t> xp((size_t)Mp * K, POISON16);
+    if (pro == PRO_F16) {
+        for (int m = 0; m < M; m++)
+            for (int k = 0; k < K; k++) xp[frag_idx_host(m, k, K)] = x16[(size_t)m * K + k];
+        if (!dx.up(xp.data(), xp.size() * 2)) return -1;
+        a.x16 = (const half_t*)dx.p;
+    } else {
+        std::vector<float> hpz((size_t)Mp * K, 3.0e4f), sqz((size_t)Mp * (K / 16), 1.0e9f);
+        if (!dhrows.up(h, (size_t)M * K * 4) || !dh.up(hpz.data(), hpz.size() * 4) || !dssq.up(sqz.data(), sqz.size() * 4) ||
+            !dx.up(xp.data(), xp.size() * 2) || !dg.up(gamma, (size_t)K * 4))
+            return -1;
+        // the producer's side of the folded RMSNorm: h, its sum-of-squares partials and xh = fp16((h*gamma)/16)
+        if (launch_ssq_rows(s, (const float*)dhrows.p, (float*)dh.p, (float*)dssq.p, M, K, (half_t*)dx.p, (const float*)dg.p)) return -1;
+        Q3_HIP(hipDeviceSynchronize(), -1);
+        Q3_HIP(hipMemcpy(hpz.data(), dh.p, hpz.size() * 4, hipMemcpyDeviceToHost), -1);
+        Q3_HIP(hipMemcpy(xp.data(), dx.p, xp.size() * 2, hipMemcpyDeviceToHost), -1);
+        Q3_HIP(hipMemcpy(pro_ssq, dssq.p, (size_t)M * (K / 16) * 4, hipMemcpyDeviceToHost), -1);
+        for (int m = 0; m < M; m++)
+            for (int k = 0; k < K; k++) {
+                pro_h[(size_t)m * K + k] = hpz[frag_idx_host(m, k, K)];
+                pro_xh[(size_t)m * K + k] = xp[frag_idx_host(m, k, K)];
+            }
+        a.x16 = (const half_t*)dx.p;
+        a.ssq = (const float*)dssq.p;
+        a.ssq_parts = K / 16;
+        a.eps = eps;
+    }
+    std::vector<uint32_t> hy, hh, hs;
+    std::vector<uint16_t> hx, ha;
+    if (epi == EPI_STORE) {
+        hy.assign((size_t)Mp * ldy, GUARD32);
+        if (!dy.up(hy.data(), hy.size() * 4)) return -1;
+        a.y = (float*)dy.p;
+        a.ldy = ldy;
+    } else if (epi == EPI_RESID) {
+        hh.assign((size_t)Mp * N, GUARD32);
+        hs.assign((size_t)Mp * (N / 16), GUARD32);
+        for (int m = m_begin; m < M; m++)
+            for (int n = 0; n < N; n++) memcpy(&hh[frag_idx_host(m, n, N)], &h_io[(size_t)m * N + n], 4);
+        if (!dho.up(hh.data(), hh.size() * 4) || !dso.up(hs.data(), hs.size() * 4)) return -1;
+        a.h_out = (float*)dho.p;
+        a.ssq_out = (float*)dso.p;
+        if (xh_out) {
+            hx.assign((size_t)Mp * N, GUARD16);
+            if (!dxo.up(hx.data(), hx.size() * 2) || !dgn.up(gamma_next, (size_t)N * 4)) return -1;
+            a.xh_out = (half_t*)dxo.p;
+            a.gamma = (const float*)dgn.p;
+        }
+    } else {
+        ha.assign((size_t)Mp * NA, GUARD16);
+        if (!dact.up(ha.data(), ha.size() * 2)) return -1;
+        a.act = (half_t*)dact.p;
+    }
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (launch_linear(s, a, pro, epi)) {
+        // refused before its launch (no instantiation for this shape under the current knobs): nothing ran
+        if (!last_linear_variant()[0] && hipGetLastError() == hipSuccess) return -2;
+        return -1;
+    }
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    auto inside = [&](int m) { return m >= m_begin && m < M; };
+    int outside = 0;
+    if (epi == EPI_STORE) {
+        Q3_HIP(hipMemcpy(hy.data(), dy.p, hy.size() * 4, hipMemcpyDeviceToHost), -1);
+        for (int m = 0; m < Mp; m++)
+            for (int n = 0; n < ldy; n++) {
+                const uint32_t v = hy[(size_t)m * ldy + n];
+                if (inside(m) && n < N) memcpy(&y[(size_t)m * ldy + n], &v, 4);
+                else if (v != GUARD32) outside++;
+            }
+    } else if (epi == EPI_RESID) {
+        Q3_HIP(hipMemcpy(hh.data(), dho.p, hh.size() * 4, hipMemcpyDeviceToHost), -1);
+        Q3_HIP(hipMemcpy(hs.data(), dso.p, hs.size() * 4, hipMemcpyDeviceToHost), -1);
+        if (xh_out) Q3_HIP(hipMemcpy(hx.data(), dxo.p, hx.size() * 2, hipMemcpyDeviceToHost), -1);
+        for (int m = 0; m < Mp; m++) {
+            for (int n = 0; n < N; n++) {
+                const size_t fi = frag_idx_host(m, n, N);
+                if (inside(m)) {
+                    memcpy(&h_io[(size_t)m * N + n], &hh[fi], 4);
+                    if (xh_out) xh_out[(size_t)m * N + n] = hx[fi];
+                } else if (hh[fi] != GUARD32 || (xh_out && hx[fi] != GUARD16)) {
+                    outside++;
+                }
+            }
+            for (int p = 0; p < N / 16; p++) {
+                const uint32_t v = hs[(size_t)m * (N / 16) + p];
+                if (inside(m)) memcpy(&ssq_out[(size_t)m * (N / 16) + p], &v, 4);
+                else if (v != GUARD32) outside++;
+            }
+        }
+    } else {
+        Q3_HIP(hipMemcpy(ha.data(), dact.p, ha.size() * 2, hipMemcpyDeviceToHost), -1);
+        for (int m = 0; m < Mp; m++)
+            for (int j = 0; j < NA; j++) {
+                const uint16_t v = ha[frag_idx_host(m, j, NA)];
+                if (inside(m)) act[(size_t)m * NA + j] = v;
+                else if (v != GUARD16) outside++;
+            }
+    }
+    return outside ? -3 : 0;
 }
 
 // One attention call of the talker / code-predictor shape (16 q heads, 8 kv heads, head_dim 128) on host arrays, sent

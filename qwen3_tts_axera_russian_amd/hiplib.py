@@ -158,6 +158,10 @@ def load_test():
     _sig(lib, "q3t_set_linear_tuning", c_int, [c_int, c_int, c_int])
     _sig(lib, "q3t_linear", c_int, [c_int, c_int, c_int, u16p, c_int, c_int, c_int, u16p, f32p, f32p, c_float,
                                     f32p, f32p, u16p, c_int])
+    _sig(lib, "q3t_linear_case", c_int, [c_int, c_int, c_int, c_int, u16p, c_int, c_int, c_int, c_int, c_float, c_int,
+                                         u16p, f32p, f32p, f32p, f32p, f32p, u16p, f32p, f32p, f32p, u16p, u16p])
+    _sig(lib, "q3t_reset_linear_knobs", c_int, [])
+    _sig(lib, "q3t_last_linear_variant", c_char_p, [])
     _sig(lib, "q3t_talker_sample", c_int, [f32p, c_int, i32p, c_int, c_int, c_int])
     _sig(lib, "q3t_attn", c_int, [c_int, c_int, c_int, f32p, f32p, f32p, c_float, f32p, f32p, c_int, i32p, i32p, c_int,
                                   c_int, c_int, c_int, u16p, u16p, c_int, c_int, i32p, c_int, c_int, c_int, c_int, u16p])
