@@ -114,6 +114,53 @@ int voc_stream_last_decodes(void* s);
 int voc_stream_last_chunks(void* s);
 float voc_stream_last_ms(void* s);
 
+/* Carry-state incremental decode: the third way to drive the vocoder, next to voc_decode and the chunk walk.  The decoder is run
+ * as a stateful stream -- every op with a receptive field keeps, per stream, the last columns of its input on the device (convs
+ * (k - 1) * dilation columns, transposed convs k / s - 1, attention the last window - 1 columns of k | v and the stream's absolute
+ * position for RoPE) -- so a push decodes only its new frames and hands their samples out at once.  Joined, a stream's samples
+ * are ONE seamless whole-utterance decode of all its frames, of any length: no chunks, no overlap decoded twice, no cross-fade.
+ * This is NOT what voc_synthesize* returns for more than chunk_tokens frames (the reference's walk cross-fades chunks that each
+ * start from silence); up to chunk_tokens frames the two agree to rounding.
+ * voc_incr_create(voc, max_streams) -> NULL on failure (also: a table whose transposed convs do not trim k - s samples on the
+ * right cannot be streamed; the 'both' and 'right' trims can).  Free it before its vocoder handle.  Entries, codes, finish, out,
+ * out_capacity and offsets are voc_stream_push's.
+ *  - Samples per push: let S(n) = voc_incr_samples(voc, n) be the length of a whole decode of n frames -- the table's convt_out
+ *    chain applied to n (each transposed conv turns L columns into (L - 1) * s + k - lt - rt), 0 where that is not positive; at
+ *    the default table with both trims S(8) = 14 805 and S(64) = 122 325.  After pushes totalling n frames a stream has handed
+ *    out exactly S(n) samples: an identity of the table, not a measurement.  The finish push adds none (the model defines nothing
+ *    past S(N)); a stream that finishes with 0 frames gives 0 samples.
+ *  - Invariance: joined per stream, the samples are the same bits for any split of the frames across pushes, any n_new pattern,
+ *    any set of other streams in the same calls, and any stream index: every launcher rule that looks at a length reads the
+ *    full-chunk length, and a column's sums depend on neither its tile nor its batch.
+ *  - Arithmetic: the exact-fp32 kernels only, whatever voc_set_exact_fp32 selects process-wide (the split planes and their
+ *    per-call overflow redo are not carried between pushes); voc_set_fused_units applies.
+ *  - Limits: 0 <= n_new <= chunk_tokens per entry and push; frames per stream unbounded (2^31, the RoPE position).  Device memory
+ *    is constant: per stream the carried columns, voc_incr_state_bytes() = 5 193 984 B (4.95 MiB) at the default table (of which
+ *    4.44 MiB are the eight attention windows); per handle work buffers for one push of chunk_tokens frames x max_batch entries
+ *    and the packed output of max_streams entries, all allocated by voc_incr_create (voc_incr_device_bytes(): the total).
+ *  - Batching: entries of one push with the same n_new are decoded together, up to max_batch per launch sequence; distinct
+ *    n_new values run one after another, and so do a stream's first frames (its first transposed-conv outputs fall before
+ *    sample 0, so it takes fewer columns than a running stream).  Packing and the int16 rule run on the device.
+ *  - Errors (<0): a bad stream index or one named twice, n_new outside 0..chunk_tokens, a push to a finished stream without a
+ *    reset, out_capacity below what the push hands out.  Nothing is written to out and no stream changes: the same push can be
+ *    retried.
+ *  - Threads: one caller thread at a time per vocoder handle and the objects on it; entry points bind the thread to the handle's
+ *    device. */
+void* voc_incr_create(void* voc, int max_streams);
+void voc_incr_free(void* s);
+int voc_incr_reset(void* s, int stream);
+int64_t voc_incr_push_max_samples(void* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish);
+int voc_incr_push(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                  int16_t* out, int64_t out_capacity, int64_t* offsets);
+int voc_incr_push_f32(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                      float* out, int64_t out_capacity, int64_t* offsets);
+/* the last push: GPU milliseconds and kernel launches */
+float voc_incr_last_ms(void* s);
+int voc_incr_last_launches(void* s);
+int64_t voc_incr_samples(void* voc, int64_t n_frames);   /* S(n); <0: bad arguments */
+int64_t voc_incr_state_bytes(void* s);    /* device bytes one stream's carried state takes */
+int64_t voc_incr_device_bytes(void* s);   /* device bytes the object holds: fixed by voc_incr_create */
+
 /* Arithmetic of the convolutions.  Default (0): split precision -- every f32 operand (weights once at load,
  * activations in the producing kernel's epilogue) is carried as two fp16 terms (22 mantissa bits) and each
  * product costs three fp16 MFMAs with f32 accumulation.  1: the exact-f32 MFMA (v_mfma_f32_32x32x2_f32)

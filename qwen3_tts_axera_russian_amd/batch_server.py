@@ -21,6 +21,10 @@ the same connection (in the order they are ready; `utt` indexes the request's ut
               i32 2, i32 utt, i32 n_frames, i32[n_frames*16]  utterance utt has ended: all its codes
               i32 -1                                          the request is done   (i32 -2: error, as above)
 
+A request may carry "vocoder": "incremental" (default "walk"; any other value is answered with -2): its PCM then comes from the
+carry-state incremental decode (voc_incr_push: the samples of every check's new frames at once, one seamless decode per
+utterance) instead of the chunk walk -- streamed, or unstreamed through Vocoder.synthesize_incremental, the same bits either way.
+Records, framing and the single-writer worker are the same.
 Every check_every frames the new frames of every live slot go to the vocoder's streaming chunk walk (voc_stream_push, on one
 worker thread with one vocoder workgroup per compute unit, as in --pipeline); a full 64-frame chunk is decoded as soon as its
 frames exist, and all samples no later cross-fade can change go out at once.  An utterance's PCM records joined, and its codes,
@@ -108,6 +112,7 @@ class BatchSynthesisServer:
         self._pool = None
         self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
         self._vstream = None           # streaming chunk walk: one stream per slot of the frame loop
+        self._istream = None           # carry-state incremental decode ("vocoder": "incremental"): made by the worker on first use
         if self.pipeline:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=1)       # ONE worker: the vocoder handle has one caller, replies keep their order
@@ -160,13 +165,37 @@ class BatchSynthesisServer:
             per_utt = [codes[:int(per[b]), b, :] for b in range(B)]
         return [np.ascontiguousarray(c, dtype=np.int32) for c in per_utt]
 
-    def vocode(self, cs):
-        """The vocoder of a request: every utterance's chunk walk in ONE batched call -> list of (codes, pcm int16)."""
+    def vocode(self, cs, vocoder="walk"):
+        """The vocoder of a request: every utterance's chunk walk in ONE batched call -> list of (codes, pcm int16).
+        vocoder="incremental": the carry-state decode per utterance -- the bits a streamed reply in that mode carries."""
+        if vocoder == "incremental":
+            return [(c, self.voc.synthesize_incremental(c, int16=True)) for c in cs]
         return list(zip(cs, self.voc.synthesize_batch(cs)))
 
-    def synthesize(self, token_ids, max_tokens=None):
+    def synthesize(self, token_ids, max_tokens=None, vocoder="walk"):
         """-> list of (codes int32 [n_frames][16], pcm int16) per utterance."""
-        return self.vocode(self.generate(token_ids, max_tokens))
+        return self.vocode(self.generate(token_ids, max_tokens), vocoder)
+
+    def _stream_pcm(self, state, resets, entries):
+        """Worker side: the PCM a push's entries hand out, from the request's vocoder mode -- the streaming chunk walk, or the
+        carry-state decode, which takes at most chunk_tokens frames per stream and call."""
+        if state.get("vocoder", "walk") != "incremental":
+            for b in resets:
+                self._vstream.reset(b)
+            return self._vstream.push([e[0] for e in entries], [e[2] for e in entries], [e[3] for e in entries]) if entries else []
+        if self._istream is None:
+            self._istream = self.voc.incremental(self.max_batch)
+        for b in resets:
+            self._istream.reset(b)
+        ch, parts, j = self.voc.chunk_tokens, [[] for _ in entries], 0
+        while entries and (j == 0 or any(len(e[2]) > j * ch for e in entries)):
+            sel = [k for k, e in enumerate(entries) if j == 0 or len(e[2]) > j * ch]
+            pcm = self._istream.push([entries[k][0] for k in sel], [entries[k][2][j * ch:(j + 1) * ch] for k in sel],
+                                     [entries[k][3] and len(entries[k][2]) <= (j + 1) * ch for k in sel])
+            for k, a in zip(sel, pcm):
+                parts[k].append(a.copy())
+            j += 1
+        return [np.concatenate(p) for p in parts]
 
     def _push(self, conn, state, resets, entries):
         """Worker side of a streamed request: start the refilled slots' streams, push every live slot's new frames to the
@@ -175,10 +204,8 @@ class BatchSynthesisServer:
         if state["failed"]:
             return
         try:
-            for b in resets:
-                self._vstream.reset(b)
+            pcm = self._stream_pcm(state, resets, entries)
             if entries:
-                pcm = self._vstream.push([e[0] for e in entries], [e[2] for e in entries], [e[3] for e in entries])
                 out = []
                 for k, (_, utt, _, finished, codes) in enumerate(entries):
                     if len(pcm[k]):
@@ -206,11 +233,11 @@ class BatchSynthesisServer:
         finally:
             conn.close()
 
-    def synthesize_stream(self, conn, token_ids, max_tokens=None, t0=None):
+    def synthesize_stream(self, conn, token_ids, max_tokens=None, t0=None, vocoder="walk"):
         """A streamed request: the frame loop runs here (generate_queue), the vocoder's pushes and every write to `conn` on the
         worker thread, at most one push in flight.  -> the worker's future of the request's last record (it closes conn)."""
         t0 = time.time() if t0 is None else t0
-        state = {"failed": False, "n": len(token_ids), "frames": 0}
+        state = {"failed": False, "n": len(token_ids), "frames": 0, "vocoder": vocoder}
         if self._pool is not None:
             pool = self._pool
         else:
@@ -281,14 +308,15 @@ class BatchSynthesisServer:
         """--concurrent, accept side: a request -> its utterances in queue order as (request index, prefix, n_text,
         SlotParams); raises on anything malformed, before any of it is queued."""
         ids = self._token_ids(msg)
+        request_vocoder(msg)
         base = request_slot_params(msg, self.defaults, self.max_tokens)
         prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames)
         return [(i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i)) for i in order]
 
-    def _finish(self, conn, cs, t0):
+    def _finish(self, conn, cs, t0, vocoder="walk"):
         """Worker side of the pipelined mode: vocode, reply on the request's own connection, close it."""
         try:
-            res = self.vocode(cs)
+            res = self.vocode(cs, vocoder)
             conn.sendall(pack_batch_reply(res))
             print(f"  {len(res)} utterances, {sum(len(c) for c, _ in res)} frames in {time.time() - t0:.3f}s")
         except Exception as e:
@@ -325,19 +353,20 @@ class BatchSynthesisServer:
                 if msg is None:
                     continue
                 t0 = time.time()
+                vocoder = request_vocoder(msg)
                 if msg.get("stream"):
                     # streamed reply: the worker writes every record and closes the connection
                     ids = self._token_ids(msg)
                     handed_over = True
-                    self.synthesize_stream(conn, ids, msg.get("max_tokens"), t0)
+                    self.synthesize_stream(conn, ids, msg.get("max_tokens"), t0, vocoder)
                     continue
                 if self._pool is not None:
                     # pipelined: this request's vocoder runs on the worker while the loop accepts and generates the next one
                     cs = self.generate(self._token_ids(msg), msg.get("max_tokens"))
-                    self._pool.submit(self._finish, conn, cs, t0)
+                    self._pool.submit(self._finish, conn, cs, t0, vocoder)
                     handed_over = True
                     continue
-                res = self.synthesize(self._token_ids(msg), msg.get("max_tokens"))
+                res = self.synthesize(self._token_ids(msg), msg.get("max_tokens"), vocoder)
                 conn.sendall(pack_batch_reply(res))
                 frames = sum(len(c) for c, _ in res)
                 print(f"  {len(res)} utterances, {frames} frames in {time.time() - t0:.3f}s")
@@ -406,7 +435,7 @@ class BatchSynthesisServer:
         if self.pipeline:
             self._lib.voc_set_max_workgroups(0)
         self.voc.close()               # frees the streaming chunk walk first
-        self._vstream = None
+        self._vstream = self._istream = None
         self.eng.destroy()
 
 
@@ -466,6 +495,7 @@ class ConcurrentScheduler:
                       "Error: the engine has stopped")
                 return self._refuse(conn)
             req = _Request(conn, items, msg.get("stream"), time.time() if t0 is None else t0)
+            req.state["vocoder"] = request_vocoder(msg)      # (prepare has checked it)
             self._queue.extend((req, it) for it in items)
             self._cv.notify()
         return True
@@ -602,8 +632,10 @@ class ConcurrentScheduler:
                 if req.left == 0:
                     if req.stream:
                         self._pool.submit(self._close_stream, req.conn, req.state, req.t0)
-                    else:
+                    elif req.state["vocoder"] == "walk":
                         self._pool.submit(self._reply, req.conn, req.codes, req.t0)
+                    else:
+                        self._pool.submit(self._reply, req.conn, req.codes, req.t0, req.state["vocoder"])
         # shutting down: whatever is still in flight or queued gets -2
         with self._cv:
             rest = {id(r): r for r, _ in self._queue}
@@ -613,6 +645,18 @@ class ConcurrentScheduler:
             if not req.gone:
                 req.gone = True
                 self._pool.submit(self._refuse, req.conn)
+
+
+VOCODER_MODES = ("walk", "incremental")
+
+
+def request_vocoder(msg):
+    """A request's "vocoder" key -> "walk" (the default: the reference's chunk walk) or "incremental" (the carry-state decode,
+    include/qwen3tts_voc.h voc_incr_*); raises ValueError on any other value (the request is then answered with -2)."""
+    v = msg.get("vocoder", "walk")
+    if not isinstance(v, str) or v not in VOCODER_MODES:
+        raise ValueError(f"vocoder must be one of {VOCODER_MODES} (got {v!r})")
+    return v
 
 
 _PARAM_KEYS = ("temperature", "top_k", "top_p", "cp_temperature", "cp_top_k", "seed")   # request keys = SlotParams fields
@@ -642,8 +686,9 @@ def request_slot_params(msg, defaults, max_tokens_cap):
 
 
 def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False, temperature=None,
-                       top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None) -> bytes:
-    """The request of the batched protocol; the sampling keys (honoured by --concurrent) are sent only when given."""
+                       top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None) -> bytes:
+    """The request of the batched protocol; the sampling keys (honoured by --concurrent) and the vocoder mode ("walk" /
+    "incremental") are sent only when given."""
     import json
     msg = {"language": language}
     if stream:
@@ -655,7 +700,7 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
     if max_tokens:
         msg["max_tokens"] = int(max_tokens)
     for key, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("cp_temperature", cp_temperature),
-                   ("cp_top_k", cp_top_k), ("seed", seed)):
+                   ("cp_top_k", cp_top_k), ("seed", seed), ("vocoder", vocoder)):
         if v is not None:
             msg[key] = v
     raw = json.dumps(msg).encode()
@@ -725,13 +770,14 @@ def read_stream_record(conn):
     return ("end", utt, np.frombuffer(exact(n * 16 * 4), dtype="<i4").reshape(n, 16))
 
 
-def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, **sampling):
+def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, vocoder=None, **sampling):
     """Client side of the streamed request: yields its records as they arrive -- ("audio", utt, pcm) and ("end", utt, codes)
-    -- until the request is done; raises on the error sentinel.  sampling: the optional keys of pack_batch_request."""
+    -- until the request is done; raises on the error sentinel.  vocoder="incremental": the carry-state decode (audio from the
+    first check on) instead of the chunk walk.  sampling: the optional keys of pack_batch_request."""
     s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     s.connect(socket_path)
     try:
-        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True, **sampling))
+        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True, vocoder=vocoder, **sampling))
         while True:
             rec = read_stream_record(s)
             if rec[0] == "done":

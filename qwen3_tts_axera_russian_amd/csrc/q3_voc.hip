@@ -1332,6 +1332,105 @@ __global__ void __launch_bounds__(256) voc_stream_emit_kernel(const float* __res
         tail[(size_t)p.stream * OV + i] = work[p.win + p.n_out + i];
 }
 
+// ---------------------------------------------------------------------------
+// Carry-state incremental decode (voc_incr_*): every op with a receptive field keeps, per stream, the last H columns of its
+// input ([max_streams][C][H] on the device, zero at the start of a stream = the causal padding the kernels assume).  A push
+// lays [history | new columns] out in the work buffer, runs the op's ordinary kernel over it and drops the history's outputs.
+// ---------------------------------------------------------------------------
+// Columns [skip, skip + n) of channels [c0, c0 + C) of src ([B][src_C][src_ld]) -> dst [B][C][dst_ld] behind the H history
+// columns of the entry's stream; the last H columns of [history | new] become the stream's new history.  One workgroup
+// (blockIdx.x == 0) owns a row's history: it reads all of it before it writes any (H <= 256, the launcher's rule).
+__global__ void __launch_bounds__(256) voc_incr_prepend_kernel(const float* __restrict__ src, int src_C, int c0, int src_ld, int skip,
+                                                               float* __restrict__ dst, int C, int dst_ld, float* __restrict__ hist,
+                                                               int H, int n, long long state_floats, const int* __restrict__ streams) {
+    const int c = blockIdx.y, b = blockIdx.z;
+    const float* s = src + ((size_t)b * src_C + c0 + c) * src_ld + skip;
+    float* d = dst + ((size_t)b * C + c) * dst_ld;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) d[H + j] = s[j];
+    if (blockIdx.x == 0 && H > 0) {
+        float* h = hist + (size_t)streams[b] * state_floats + (size_t)c * H;
+        const int i = threadIdx.x;
+        float old = 0.f, nw = 0.f;
+        if (i < H) {
+            old = h[i];
+            nw = (i + n < H) ? h[i + n] : s[i + n - H];
+        }
+        __syncthreads();
+        if (i < H) {
+            d[i] = old;
+            h[i] = nw;
+        }
+    }
+}
+
+// voc_attn_kernel for the incremental decode: queries are the n new columns of x ([B][3*H*D][x_ld], at column skip + i), keys
+// and values come from kv = [carried window | new] ([B][2*H*D][kv_ld], k rows then v rows, new column i at Hk + i), and the
+// window is placed by the ABSOLUTE column pos0[b] + i of the stream.  RoPE scores depend on the distance of query and key only:
+// both are rotated by their offset from the first key of the query's window (= their absolute column while the stream is
+// shorter than the window), so the angles stay below `window` and their rounding does not grow with the stream's length.
+// One wave per (query, head) walks its keys in order, so a column's bits depend on nothing but its own window: not on the
+// push it arrives in, nor on the batch.  No LDS: the [window - 1 + n] columns of a head (up to 135 x 64 x 2 floats) come from L2.
+__global__ void __launch_bounds__(64) voc_attn_incr_kernel(const float* __restrict__ x, int x_ld, int skip, const float* __restrict__ kv,
+                                                           int kv_ld, int Hk, float* __restrict__ y, int H, int D, int window,
+                                                           float theta, const int* __restrict__ pos0) {
+    const int i = blockIdx.x, h = blockIdx.y, b = blockIdx.z, j = threadIdx.x;
+    const int half = D / 2, HD = H * D;
+    const bool on = j < half;
+    const int p0 = pos0[b], pos = p0 + i;
+    const float inv_freq = on ? __powf(theta, -2.0f * (float)j / (float)D) : 0.f;
+    auto rope = [&](const float* base, int ld, int col, int at, float& a, float& c) {   // rows (j, j+half) of a head
+        float x0 = 0.f, x1 = 0.f;
+        if (on) {
+            x0 = base[(size_t)j * ld + col];
+            x1 = base[(size_t)(j + half) * ld + col];
+        }
+        float sn, cs;
+        __sincosf((float)at * inv_freq, &sn, &cs);
+        a = x0 * cs - x1 * sn;
+        c = x1 * cs + x0 * sn;
+    };
+    const int t0 = pos - window + 1 > 0 ? pos - window + 1 : 0;
+    float q0, q1;
+    rope(x + ((size_t)b * 3 * HD + h * D) * x_ld, x_ld, skip + i, pos - t0, q0, q1);
+    const float* kb = kv + ((size_t)b * 2 * HD + h * D) * kv_ld;
+    const float* vb = kb + (size_t)HD * kv_ld;
+    const float scale = 1.0f / sqrtf((float)D);
+    float m = -INFINITY, lsum = 0.f, o0 = 0.f, o1 = 0.f;
+    for (int t = t0; t <= pos; t++) {
+        const int col = Hk + (t - p0);       // >= 0: t >= pos - (window - 1) >= p0 - Hk
+        float k0, k1;
+        rope(kb, kv_ld, col, t - t0, k0, k1);
+        float sc = q0 * k0 + q1 * k1;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sc += __shfl_xor(sc, o, 64);
+        sc *= scale;
+        const float mn = fmaxf(m, sc), corr = __expf(m - mn), p = __expf(sc - mn);
+        float v0 = 0.f, v1 = 0.f;
+        if (on) {
+            v0 = vb[(size_t)j * kv_ld + col];
+            v1 = vb[(size_t)(j + half) * kv_ld + col];
+        }
+        lsum = lsum * corr + p;
+        o0 = o0 * corr + p * v0;
+        o1 = o1 * corr + p * v1;
+        m = mn;
+    }
+    if (on) {
+        float* yb = y + ((size_t)b * HD + h * D) * x_ld + skip + i;
+        yb[(size_t)j * x_ld] = o0 / lsum;
+        yb[(size_t)(j + half) * x_ld] = o1 / lsum;
+    }
+}
+
+// the n samples of every entry (row b of y, from column skip) -> the caller's packed output (f32, or the int16 rule)
+template <typename T>
+__global__ void __launch_bounds__(256) voc_incr_emit_kernel(const float* __restrict__ y, int ld, int skip, int n,
+                                                            const long long* __restrict__ out_off, T* __restrict__ out) {
+    const int b = blockIdx.y;
+    const long long o = out_off[b];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) voc_store(out, o + i, y[(size_t)b * ld + skip + i]);
+}
+
 struct VocOp {
     int op = 0, cin = 0, cout = 0, k = 0, p0 = 0, flags = 0, nq = 0, cb = 0;
     float *w = nullptr, *bias = nullptr, *alpha = nullptr, *inv_beta = nullptr;  // device
@@ -2580,5 +2679,528 @@ float voc_stream_last_ms(void* s) { return s ? ((VocStream*)s)->last_ms : -1.f; 
 
 float voc_last_batch_ms(void* vv) { return vv ? ((Voc*)vv)->batch_ms : -1.f; }
 int voc_last_batch_chunks(void* vv) { return vv ? ((Voc*)vv)->batch_chunks : 0; }
+
+}  // extern "C"
+
+// ---- carry-state incremental decode (voc_incr_*) ----
+namespace {
+
+struct VocIncr {
+    Voc* v = nullptr;
+    int max_streams = 0;
+    std::vector<long long> n_frames;      // frames a stream has taken since its reset
+    std::vector<char> finished;
+    std::vector<int> H;                   // per op: history columns (0: the op carries nothing)
+    std::vector<size_t> hoff;             // per op: offset of its [C][H] block inside a stream's state
+    size_t state_floats = 0;              // one stream's state
+    float* d_hist = nullptr;              // [max_streams][state_floats]
+    float* buf[3] = {nullptr, nullptr, nullptr};   // work buffers (voc_run's ping-pong + residual), sized for chunk frames x max_batch
+    float* d_kv = nullptr;                // attention: [carried window | new] k and v rows
+    int64_t* d_codes = nullptr;           // [max_batch][chunk][16]
+    int* d_meta = nullptr;                // [1 + n_ops][max_batch]: the entries' streams, then per op the columns each had consumed
+    long long* d_off = nullptr;           // [max_batch]: where each entry's samples start in the packed output
+    float* d_out = nullptr;               // packed output of a push
+    int16_t* d_out16 = nullptr;
+    size_t out_cap = 0, device_bytes = 0;
+    float last_ms = 0.f;
+    int last_launches = 0;
+};
+
+int incr_hist_cols(const VocOp& op) {
+    switch (op.op) {
+        case VOP_CONV: return (op.k - 1) * op.p0;
+        case VOP_CONVT: return op.k / op.p0 - 1;      // taps of the polyphase GEMM - 1
+        case VOP_DWCONV: return op.k - 1;
+        case VOP_ATTN: return op.window - 1;
+        default: return 0;
+    }
+}
+int incr_hist_chans(const VocOp& op) { return op.op == VOP_ATTN ? 2 * op.heads * op.head_dim : op.cin; }
+
+// in[i]: columns op i has consumed once its stream has taken n frames; in[n_ops]: samples handed out = S(n).  A transposed
+// conv whose right trim is k - s (voc_incr_create's rule) turns L columns into L * s - lt: the convt_out chain, 0 where the
+// model defines no sample yet.
+void incr_chain(const Voc* v, long long n, std::vector<long long>& in) {
+    in.resize(v->ops.size() + 1);
+    long long L = n;
+    for (size_t i = 0; i < v->ops.size(); i++) {
+        in[i] = L;
+        const VocOp& op = v->ops[i];
+        if (op.op == VOP_CONVT) L = std::max(0LL, L * op.p0 - op.lt);
+    }
+    in[v->ops.size()] = L;
+}
+
+// What decides the launches of one entry: per op the new columns it takes (nc, n_ops + 1 values, the last = new samples) and,
+// per transposed conv, how many of its first outputs fall before sample 0 (only in a stream's first push).  Entries of a push
+// with the same key are decoded together.
+void incr_key(const Voc* v, long long prev, long long now, std::vector<long long>& key) {
+    std::vector<long long> a, b;
+    incr_chain(v, prev, a);
+    incr_chain(v, now, b);
+    const size_t n = v->ops.size();
+    key.assign(2 * n + 1, 0);
+    for (size_t i = 0; i <= n; i++) key[i] = b[i] - a[i];
+    for (size_t i = 0; i < n; i++)
+        if (v->ops[i].op == VOP_CONVT) key[n + 1 + i] = std::max(0LL, (long long)v->ops[i].lt - a[i] * v->ops[i].p0);
+}
+
+// One launch sequence: B entries with the same key through the op table, exact-fp32 kernels only (voc_run's exact branch with
+// [history | new] in place of the chunk).  An activation is buf[cur], [B][C][pitch4(skip + n)]: `skip` leading columns are the
+// outputs of history columns (dropped: nothing reads them), n are the new ones.  dry: no launch, *need / *need_kv take the
+// largest work buffer / k|v buffer (floats per entry) the sequence asks for.
+int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, size_t* need, size_t* need_kv, int* launches,
+              float** out_buf, int* out_ld, int* out_skip) {
+    Voc* v = s->v;
+    const size_t nops = v->ops.size();
+    const long long* nc = key.data();
+    const long long* extra = key.data() + nops + 1;
+    int cur = 0, skip = 0, C = 0;
+    long long n = nc[0];
+    long Lf = v->chunk;
+    float* res = nullptr;
+    bool have_res = false;
+    int res_ld = -1, res_skip = -1;
+    const int mb = v->max_batch;
+    auto note = [&](int ch, long long cols) {
+        const size_t e = (size_t)ch * pitch4(cols);
+        if (need && e > *need) *need = e;
+    };
+    // buf[cur] columns [skip, skip + n) of channels [c0, c0 + Cc) -> dst = [history | new]; the stream's history moves on
+    auto prepend = [&](size_t i, int Cc, int c0, int srcC, float* dst) -> int {
+        const int H = s->H[i];
+        if (!dry) {
+            const unsigned gx = (unsigned)std::min<long long>(64, (n + 255) / 256);
+            hipLaunchKernelGGL(voc_incr_prepend_kernel, dim3(gx, Cc, B), dim3(256), 0, v->s, s->buf[cur], srcC, c0, (int)pitch4(skip + n), skip,
+                               dst, Cc, (int)pitch4(H + n), s->d_hist + s->hoff[i], H, (int)n, (long long)s->state_floats, s->d_meta);
+            Q3_HIP(hipGetLastError(), -1);
+        }
+        (*launches)++;
+        return 0;
+    };
+    auto prepend_act = [&](size_t i) -> int {     // the whole activation: it becomes buf[cur] = [history | new]
+        if (s->H[i] == 0) return 0;
+        note(C, s->H[i] + n);
+        if (prepend(i, C, 0, C, dry ? nullptr : s->buf[cur ^ 1])) return -1;
+        cur ^= 1;
+        skip = s->H[i];
+        return 0;
+    };
+    auto save_res = [&]() {                       // voc_run: the unit's input becomes buf[2], out of the ping-pong
+        std::swap(s->buf[2], s->buf[cur]);
+        res = s->buf[2];
+        have_res = true;
+        res_ld = (int)pitch4(skip + n);
+        res_skip = skip;
+    };
+    size_t i = 0;
+    for (; i < nops; i++) {
+        const VocOp& op = v->ops[i];
+        if (n != nc[i]) return -1;
+        if (n == 0) break;                        // no sample of this push reaches further (a stream's very first columns)
+        if (op.op == VOP_RVQ || op.op == VOP_EMBMEAN) {
+            const int ld = (int)pitch4(n);
+            note(op.cout, n);
+            if (!dry) {
+                if (op.op == VOP_RVQ)
+                    hipLaunchKernelGGL(rvq_kernel, dim3((unsigned)n, B), dim3(256), 2 * op.cin * sizeof(float), v->s, s->d_codes, op.w, op.p_sem,
+                                       op.p_ac, s->buf[cur ^ 1], (int)n, ld, op.nq, op.cb, op.cin, op.cout);
+                else
+                    hipLaunchKernelGGL(embmean_kernel, dim3((unsigned)n, B), dim3(256), 0, v->s, s->d_codes, op.w, s->buf[cur ^ 1], (int)n, ld,
+                                       op.nq, 16, op.cb, op.cout);
+                Q3_HIP(hipGetLastError(), -1);
+            }
+            (*launches)++;
+            C = op.cout;
+            cur ^= 1;
+            skip = 0;
+        } else if (op.op == VOP_DWCONV || op.op == VOP_NORM || op.op == VOP_GLU) {
+            if (op.op == VOP_DWCONV && prepend_act(i)) return -1;
+            if (op.flags & VF_RES_SAVE) save_res();
+            const long long cols = skip + n;
+            const int ld = (int)pitch4(cols);
+            note(op.cout, cols);
+            if (!dry) {
+                const float* in = (op.flags & VF_RES_SAVE) ? res : s->buf[cur];
+                float* out = s->buf[cur ^ 1];
+                const unsigned lb = (unsigned)((cols + 255) / 256);
+                if (op.op == VOP_DWCONV)
+                    hipLaunchKernelGGL(dwconv_kernel, dim3(lb, op.cin, B), dim3(256), 0, v->s, in, op.w, op.bias, out, op.cin, (int)cols, ld, op.k);
+                else if (op.op == VOP_NORM)
+                    hipLaunchKernelGGL(chan_norm_kernel, dim3((unsigned)((cols + 63) / 64), B), dim3(1024), 0, v->s, in, op.w, op.bias, out,
+                                       op.cin, (int)cols, ld, op.kind, op.eps);
+                else
+                    hipLaunchKernelGGL(glu_kernel, dim3(lb, op.cout, B), dim3(256), 0, v->s, in, out, op.cout, (int)cols, ld, op.kind);
+                Q3_HIP(hipGetLastError(), -1);
+            }
+            (*launches)++;
+            C = op.cout;
+            cur ^= 1;
+        } else if (op.op == VOP_ATTN) {
+            // k | v rows of the new columns join the carried window in d_kv; q stays where it is, the output keeps the
+            // input's columns (the residual saved before the q/k/v projection lines up with it)
+            const int HD = op.heads * op.head_dim, Hk = s->H[i];
+            if (need_kv) *need_kv = std::max(*need_kv, (size_t)2 * HD * pitch4(Hk + n));
+            if (prepend(i, 2 * HD, HD, 3 * HD, dry ? nullptr : s->d_kv)) return -1;
+            note(HD, skip + n);
+            if (!dry) {
+                hipLaunchKernelGGL(voc_attn_incr_kernel, dim3((unsigned)n, op.heads, B), dim3(64), 0, v->s, s->buf[cur], (int)pitch4(skip + n), skip,
+                                   s->d_kv, (int)pitch4(Hk + n), Hk, s->buf[cur ^ 1], op.heads, op.head_dim, op.window, op.theta,
+                                   s->d_meta + (1 + i) * mb);
+                Q3_HIP(hipGetLastError(), -1);
+            }
+            (*launches)++;
+            C = op.cout;
+            cur ^= 1;
+        } else if (g_voc_fuse && op.op == VOP_CONV && op.k == 7 && (op.flags & VF_RES_SAVE) && (op.flags & VF_SNAKE) &&
+                   op.cin == op.cout && resunit_channels(op.cin) && i + 1 < nops && v->ops[i + 1].w1p) {
+            const VocOp& op1 = v->ops[i + 1];
+            if (prepend_act(i)) return -1;
+            const long long cols = skip + n;
+            if (!dry) {
+                ResUnitArgs ra;
+                ra.x = s->buf[cur];
+                ra.y = s->buf[cur ^ 1];
+                ra.w7 = op.w;
+                ra.w1p = op1.w1p;
+                ra.b7 = op.bias;
+                ra.b1 = op1.bias;
+                ra.al7 = op.alpha;
+                ra.ib7 = op.inv_beta;
+                ra.al1 = op1.alpha;
+                ra.ib1 = op1.inv_beta;
+                ra.Lin = (int)cols;
+                ra.ld = (int)pitch4(cols);
+                ra.dil = op.p0;
+                if (launch_resunit(v->s, ra, op.cin, B)) return -1;
+            }
+            (*launches)++;
+            cur ^= 1;
+            i++;   // the 1x1 conv is done
+            if (nc[i] != n) return -1;
+        } else {
+            if (prepend_act(i)) return -1;
+            if (op.flags & VF_RES_SAVE) save_res();
+            const long long cols = skip + n;
+            ConvArgs a;
+            a.wk = op.w;
+            a.bias = op.bias;
+            a.alpha = op.alpha;
+            a.inv_beta = op.inv_beta;
+            a.Cin = op.cin;
+            a.Cout = op.cout;
+            a.Lin = (int)cols;
+            a.clamp = (op.flags & VF_CLAMP) ? 1 : 0;
+            a.gelu = (op.flags & VF_GELU) ? 1 : 0;
+            a.ldx = (int)pitch4(cols);
+            long long n_next = n;
+            int skip_next = skip;
+            if (op.op == VOP_CONV) {
+                a.K = op.k;
+                a.dil = op.p0;
+                a.stride = 1;
+                a.M = op.cout;
+                a.Lout = a.Lc = (int)cols;
+                a.Lrule = (int)Lf;
+            } else {
+                // buffer column skip + j is the stream's column prev + j; its virtual row p is the stream's output sample
+                // (prev + j) * s + p - lt, i.e. new sample number (skip + j) * s + p - a.lt of this push
+                n_next = nc[i + 1];
+                skip_next = 0;
+                a.K = op.k / op.p0;
+                a.dil = 1;
+                a.stride = op.p0;
+                a.M = op.cout * op.p0;
+                a.lt = skip * op.p0 + (int)extra[i];
+                a.Lout = (int)n_next;
+                a.Lc = (int)cols;
+                a.Lrule = (int)convt_cols(op, Lf);
+                Lf = convt_out(op, Lf);
+                if (n_next == 0) {   // every output of these columns lies before sample 0: the history has moved on, nothing to compute
+                    n = 0;
+                    i++;
+                    break;
+                }
+            }
+            a.ldy = (int)pitch4(a.Lout);
+            note(op.cout, a.Lout);
+            if (op.flags & VF_RES_ADD) {
+                if (!have_res || res_ld != a.ldy || res_skip != skip_next || op.op != VOP_CONV) {
+                    Q3_LOG("voc incremental: op %zu adds a residual that is not aligned with its output", i);
+                    return -1;
+                }
+                a.res = res;
+            }
+            if (!dry) {
+                a.x = (op.flags & VF_RES_SAVE) ? res : s->buf[cur];
+                a.y = s->buf[cur ^ 1];
+                if (launch_conv(v->s, a, B)) return -1;
+            }
+            (*launches)++;
+            C = op.cout;
+            cur ^= 1;
+            n = n_next;
+            skip = skip_next;
+        }
+    }
+    if (i == nops && n != nc[nops]) return -1;
+    if (i < nops && nc[nops] != 0) return -1;
+    if (out_buf) *out_buf = s->buf[cur];
+    if (out_ld) *out_ld = (int)pitch4(skip + n);
+    if (out_skip) *out_skip = skip;
+    return 0;
+}
+
+struct IncrPlan {
+    std::vector<long long> n_out;                       // per entry
+    std::vector<std::vector<long long>> keys;           // per group
+    std::vector<std::vector<int>> members;              // per group: entry indices
+};
+
+int incr_plan(const VocIncr* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish, IncrPlan& p) {
+    const Voc* v = s->v;
+    if (n < 0 || (n > 0 && (!streams || !n_new))) return -1;
+    p.n_out.assign(n, 0);
+    p.keys.clear();
+    p.members.clear();
+    std::vector<char> seen(s->max_streams, 0);
+    std::vector<long long> key;
+    const size_t nops = v->ops.size();
+    for (int i = 0; i < n; i++) {
+        const int k = streams[i];
+        if (k < 0 || k >= s->max_streams || seen[k] || n_new[i] < 0 || n_new[i] > v->chunk) {
+            Q3_LOG("voc_incr_push: entry %d: bad stream %d (or named twice) or %d new frames (0..%d)", i, k, n_new[i], v->chunk);
+            return -1;
+        }
+        seen[k] = 1;
+        if (s->finished[k]) {
+            Q3_LOG("voc_incr_push: stream %d has finished (voc_incr_reset starts the next utterance)", k);
+            return -1;
+        }
+        if (n_new[i] == 0) continue;      // (a finish push adds no sample: the model defines nothing past S(N))
+        if (s->n_frames[k] + n_new[i] > 0x7fffffffLL) {
+            Q3_LOG("voc_incr_push: stream %d is beyond 2^31 frames", k);
+            return -1;
+        }
+        incr_key(v, s->n_frames[k], s->n_frames[k] + n_new[i], key);
+        p.n_out[i] = key[nops];
+        size_t g = 0;
+        while (g < p.keys.size() && (p.keys[g] != key || (int)p.members[g].size() >= v->max_batch)) g++;
+        if (g == p.keys.size()) {
+            p.keys.push_back(key);
+            p.members.emplace_back();
+        }
+        p.members[g].push_back(i);
+    }
+    (void)finish;
+    return 0;
+}
+
+int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+              bool want16, void* out, int64_t cap, int64_t* offsets) {
+    if (!s || !offsets) return -1;
+    Voc* v = s->v;
+    voc_bind(v);
+    IncrPlan p;
+    if (incr_plan(s, n, streams, n_new, finish, p)) return -1;
+    long long total = 0;
+    size_t frames = 0;
+    std::vector<size_t> coff(n, 0);
+    for (int i = 0; i < n; i++) {
+        offsets[i] = total;
+        total += p.n_out[i];
+        coff[i] = frames * 16;
+        frames += (size_t)n_new[i];
+    }
+    offsets[n] = total;
+    if (total > cap || (total > 0 && !out) || (frames > 0 && !codes) || (size_t)total > s->out_cap) {
+        Q3_LOG("voc_incr_push: %lld samples do not fit the caller's buffer of %lld (or no codes given)", total, (long long)cap);
+        return -1;
+    }
+    // the push is valid
+    const size_t nops = v->ops.size();
+    const int mb = v->max_batch;
+    std::vector<int64_t> hcodes;
+    std::vector<int> meta((1 + nops) * mb);
+    std::vector<long long> off(mb), before;
+    s->last_launches = 0;
+    s->last_ms = 0.f;
+    if (!p.keys.empty()) Q3_HIP(hipEventRecord(v->e0, v->s), -1);
+    for (size_t g = 0; g < p.keys.size(); g++) {
+        const std::vector<int>& mem = p.members[g];
+        const int B = (int)mem.size(), T = n_new[mem[0]];
+        hcodes.resize((size_t)B * T * 16);
+        std::fill(meta.begin(), meta.end(), 0);
+        for (int b = 0; b < B; b++) {
+            const int e = mem[b], k = streams[e];
+            memcpy(hcodes.data() + (size_t)b * T * 16, codes + coff[e], sizeof(int64_t) * 16 * T);
+            incr_chain(v, s->n_frames[k], before);
+            meta[b] = k;
+            for (size_t i = 0; i < nops; i++) meta[(1 + i) * mb + b] = (int)before[i];
+            off[b] = offsets[e];
+        }
+        Q3_HIP(hipMemcpyAsync(s->d_codes, hcodes.data(), sizeof(int64_t) * hcodes.size(), hipMemcpyHostToDevice, v->s), -1);
+        Q3_HIP(hipMemcpyAsync(s->d_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, v->s), -1);
+        Q3_HIP(hipMemcpyAsync(s->d_off, off.data(), sizeof(long long) * B, hipMemcpyHostToDevice, v->s), -1);
+        float* y = nullptr;
+        int ld = 0, skip = 0;
+        if (incr_walk(s, p.keys[g], B, false, nullptr, nullptr, &s->last_launches, &y, &ld, &skip)) return -1;
+        const long long ns = p.keys[g][nops];
+        if (ns > 0) {
+            const dim3 grid((unsigned)std::min<long long>(64, (ns + 255) / 256), B);
+            if (want16)
+                hipLaunchKernelGGL(voc_incr_emit_kernel<int16_t>, grid, dim3(256), 0, v->s, y, ld, skip, (int)ns, s->d_off, s->d_out16);
+            else
+                hipLaunchKernelGGL(voc_incr_emit_kernel<float>, grid, dim3(256), 0, v->s, y, ld, skip, (int)ns, s->d_off, s->d_out);
+            Q3_HIP(hipGetLastError(), -1);
+            s->last_launches++;
+        }
+        Q3_HIP(hipStreamSynchronize(v->s), -1);   // the staging vectors are reused by the next group
+    }
+    if (!p.keys.empty()) {
+        Q3_HIP(hipEventRecord(v->e1, v->s), -1);
+        if (total > 0)
+            Q3_HIP(hipMemcpyAsync(out, want16 ? (void*)s->d_out16 : (void*)s->d_out, (want16 ? sizeof(int16_t) : sizeof(float)) * (size_t)total,
+                                  hipMemcpyDeviceToHost, v->s), -1);
+        Q3_HIP(hipStreamSynchronize(v->s), -1);
+        hipEventElapsedTime(&s->last_ms, v->e0, v->e1);
+    }
+    for (int i = 0; i < n; i++) {
+        s->n_frames[streams[i]] += n_new[i];
+        if (finish && finish[i]) s->finished[streams[i]] = 1;
+    }
+    return 0;
+}
+
+void incr_destroy(VocIncr* s) {
+    if (!s) return;
+    for (void* p : {(void*)s->d_hist, (void*)s->buf[0], (void*)s->buf[1], (void*)s->buf[2], (void*)s->d_kv, (void*)s->d_codes,
+                    (void*)s->d_meta, (void*)s->d_off, (void*)s->d_out, (void*)s->d_out16})
+        if (p) hipFree(p);
+    delete s;
+}
+}  // namespace
+
+extern "C" {
+
+int64_t voc_incr_samples(void* vv, int64_t n_frames) {
+    const Voc* v = (const Voc*)vv;
+    if (!v || n_frames < 0) return -1;
+    std::vector<long long> in;
+    incr_chain(v, n_frames, in);
+    return in.back();
+}
+
+void voc_incr_free(void* ss) {
+    VocIncr* s = (VocIncr*)ss;
+    if (!s) return;
+    voc_bind(s->v);
+    hipStreamSynchronize(s->v->s);
+    incr_destroy(s);
+}
+
+void* voc_incr_create(void* vv, int max_streams) {
+    Voc* v = (Voc*)vv;
+    if (!v || max_streams <= 0) return nullptr;
+    voc_bind(v);
+    VocIncr* s = new VocIncr;
+    s->v = v;
+    s->max_streams = max_streams;
+    s->n_frames.assign(max_streams, 0);
+    s->finished.assign(max_streams, 0);
+    const size_t nops = v->ops.size();
+    s->H.assign(nops, 0);
+    s->hoff.assign(nops, 0);
+    for (size_t i = 0; i < nops; i++) {
+        const VocOp& op = v->ops[i];
+        // a stream can only run on a table whose transposed convs never emit a sample that a later column changes: the right
+        // trim takes the k - s outputs the next input column still adds to ('both' and 'right' trims, and k = s untrimmed)
+        if (op.op == VOP_CONVT && (op.rt != op.k - op.p0 || op.lt > op.p0)) {
+            Q3_LOG("voc_incr_create: op %zu: a transposed conv k=%d s=%d trimmed %d + %d cannot be streamed (right trim must be k - s)", i,
+                   op.k, op.p0, op.lt, op.rt);
+            delete s;
+            return nullptr;
+        }
+        s->H[i] = incr_hist_cols(op);
+        if (s->H[i] > 256 || (op.op == VOP_ATTN && op.head_dim > 128)) {
+            Q3_LOG("voc_incr_create: op %zu carries %d columns, more than the 256 the history kernel holds", i, s->H[i]);
+            delete s;
+            return nullptr;
+        }
+        s->hoff[i] = s->state_floats;
+        s->state_floats += (size_t)s->H[i] * incr_hist_chans(op);
+    }
+    // work buffers: the largest activation [history | new] of a push of chunk_tokens frames, first push or later
+    size_t need = 0, need_kv = 0;
+    std::vector<long long> key;
+    bool ok = true;
+    for (long long prev : {0LL, (long long)v->chunk}) {
+        int launches = 0;
+        incr_key(v, prev, prev + v->chunk, key);
+        ok = ok && incr_walk(s, key, v->max_batch, true, &need, &need_kv, &launches, nullptr, nullptr, nullptr) == 0;
+    }
+    if (!ok) {
+        Q3_LOG("voc_incr_create: the vocoder program cannot be run incrementally");
+        delete s;
+        return nullptr;
+    }
+    const size_t mb = (size_t)v->max_batch;
+    const size_t buf_elems = need * mb + 1024, kv_elems = need_kv * mb + 1024;   // (+ slack: float4 groups past a row's last column)
+    s->out_cap = (size_t)max_streams * v->chunk * v->upsample;
+    auto alloc = [&](void** p, size_t bytes, bool zero) {
+        if (!ok) return;
+        ok = hipMalloc(p, bytes) == hipSuccess && (!zero || hipMemset(*p, 0, bytes) == hipSuccess);
+        if (ok) s->device_bytes += bytes;
+    };
+    alloc((void**)&s->d_hist, sizeof(float) * std::max<size_t>(1, s->state_floats * max_streams), true);
+    for (int i = 0; i < 3; i++) alloc((void**)&s->buf[i], sizeof(float) * buf_elems, true);   // (zeroed once: dropped columns start finite)
+    alloc((void**)&s->d_kv, sizeof(float) * kv_elems, true);
+    alloc((void**)&s->d_codes, sizeof(int64_t) * 16 * v->chunk * mb, false);
+    alloc((void**)&s->d_meta, sizeof(int) * (1 + nops) * mb, false);
+    alloc((void**)&s->d_off, sizeof(long long) * mb, false);
+    alloc((void**)&s->d_out, sizeof(float) * s->out_cap, false);
+    alloc((void**)&s->d_out16, sizeof(int16_t) * s->out_cap, false);
+    if (!ok) {
+        Q3_LOG("voc_incr_create: device allocation failed");
+        incr_destroy(s);
+        return nullptr;
+    }
+    return s;
+}
+
+int voc_incr_reset(void* ss, int stream) {
+    VocIncr* s = (VocIncr*)ss;
+    if (!s || stream < 0 || stream >= s->max_streams) return -1;
+    voc_bind(s->v);
+    if (s->state_floats)   // the stream's history is the zero padding again (ordered before the next push on the handle's stream)
+        Q3_HIP(hipMemsetAsync(s->d_hist + (size_t)stream * s->state_floats, 0, sizeof(float) * s->state_floats, s->v->s), -1);
+    s->n_frames[stream] = 0;
+    s->finished[stream] = 0;
+    return 0;
+}
+
+int64_t voc_incr_push_max_samples(void* ss, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish) {
+    VocIncr* s = (VocIncr*)ss;
+    IncrPlan p;
+    if (!s || incr_plan(s, n, streams, n_new, finish, p)) return -1;
+    int64_t t = 0;
+    for (int i = 0; i < n; i++) t += p.n_out[i];
+    return t;
+}
+
+int voc_incr_push(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                  int16_t* out, int64_t out_capacity, int64_t* offsets) {
+    return incr_push((VocIncr*)s, n, streams, codes, n_new, finish, true, out, out_capacity, offsets);
+}
+
+int voc_incr_push_f32(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
+                      float* out, int64_t out_capacity, int64_t* offsets) {
+    return incr_push((VocIncr*)s, n, streams, codes, n_new, finish, false, out, out_capacity, offsets);
+}
+
+float voc_incr_last_ms(void* s) { return s ? ((VocIncr*)s)->last_ms : -1.f; }
+int voc_incr_last_launches(void* s) { return s ? ((VocIncr*)s)->last_launches : -1; }
+int64_t voc_incr_state_bytes(void* s) { return s ? (int64_t)(((VocIncr*)s)->state_floats * sizeof(float)) : -1; }
+int64_t voc_incr_device_bytes(void* s) { return s ? (int64_t)((VocIncr*)s)->device_bytes : -1; }
 
 }  // extern "C"

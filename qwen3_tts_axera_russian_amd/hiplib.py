@@ -118,6 +118,17 @@ def load(path: str | None = None):
     _sig(lib, "voc_stream_last_decodes", c_int, [c_void_p])
     _sig(lib, "voc_stream_last_chunks", c_int, [c_void_p])
     _sig(lib, "voc_stream_last_ms", c_float, [c_void_p])
+    _sig(lib, "voc_incr_create", c_void_p, [c_void_p, c_int])
+    _sig(lib, "voc_incr_free", None, [c_void_p])
+    _sig(lib, "voc_incr_reset", c_int, [c_void_p, c_int])
+    _sig(lib, "voc_incr_push_max_samples", ctypes.c_int64, [c_void_p, c_int, i32p, i32p, i32p])
+    _sig(lib, "voc_incr_push", c_int, [c_void_p, c_int, i32p, i64p, i32p, i32p, i16p, ctypes.c_int64, i64p_])
+    _sig(lib, "voc_incr_push_f32", c_int, [c_void_p, c_int, i32p, i64p, i32p, i32p, f32p, ctypes.c_int64, i64p_])
+    _sig(lib, "voc_incr_last_ms", c_float, [c_void_p])
+    _sig(lib, "voc_incr_last_launches", c_int, [c_void_p])
+    _sig(lib, "voc_incr_samples", ctypes.c_int64, [c_void_p, ctypes.c_int64])
+    _sig(lib, "voc_incr_state_bytes", ctypes.c_int64, [c_void_p])
+    _sig(lib, "voc_incr_device_bytes", ctypes.c_int64, [c_void_p])
     # include/qwen3tts_enc.h
     _sig(lib, "enc_load", c_void_p, [c_char_p, c_int, c_int])
     _sig(lib, "enc_free", None, [c_void_p])

@@ -32,6 +32,7 @@ class Vocoder:
         self.chunk_samples = self.lib.voc_chunk_samples(self.h)     # one decode's output (<= chunk_tokens * samples_per_token)
         self.samples_per_token = self.lib.voc_samples_per_token(self.h)
         self._streams = []
+        self._incr1 = None               # synthesize_incremental's one-stream object
 
     def decode(self, codes):
         """codes [B][chunk_tokens][16] -> f32 [B][chunk_samples] (the reference's ONNX call, vocoder_server.py:67-71)"""
@@ -74,7 +75,29 @@ class Vocoder:
         self._streams.append(VocoderStream(self.lib, self.h, max_streams))
         return self._streams[-1]
 
+    def incremental(self, max_streams):
+        """-> an IncrementalStream of max_streams utterances on this handle (freed by its close() or by this handle's)"""
+        self._streams.append(IncrementalStream(self.lib, self.h, max_streams))
+        return self._streams[-1]
+
+    def incremental_samples(self, n_frames):
+        """S(n): the samples of a whole carry-state decode of n_frames frames (voc_incr_samples)"""
+        return int(self.lib.voc_incr_samples(self.h, int(n_frames)))
+
+    def synthesize_incremental(self, codes, int16=False):
+        """codes [n][16] -> the carry-state decode of the whole utterance (voc_incr_*): one stream, pushed in chunk_tokens
+        pieces.  One seamless decode of all n frames -- not synthesize()'s cross-faded chunk walk -- and bit for bit what
+        any other split of the frames across pushes gives."""
+        c = _cat([codes])
+        if self._incr1 is None:
+            self._incr1 = self.incremental(1)
+        self._incr1.reset(0)
+        parts = [self._incr1.push([0], [c[f:f + self.chunk_tokens]], [f + self.chunk_tokens >= len(c)], int16)[0].copy()
+                 for f in range(0, len(c), self.chunk_tokens)]
+        return np.concatenate(parts + [np.zeros(0, np.int16 if int16 else np.float32)])
+
     def close(self):
+        self._incr1 = None
         for s in self._streams:          # every stream before the handle it runs on
             s.close()
         if self.h:
@@ -122,4 +145,46 @@ class VocoderStream:
     def close(self):
         if self.h:
             self.lib.voc_stream_free(self.h)
+            self.h = None
+
+
+class IncrementalStream:
+    """The carry-state incremental decode, for up to max_streams utterances at once (voc_incr_*): every push hands out the
+    samples of its new frames; joined, a stream's samples are one whole-utterance decode whatever the split."""
+
+    def __init__(self, lib, voc, max_streams):
+        self.lib, self.h = lib, lib.voc_incr_create(voc, int(max_streams))
+        if not self.h:
+            raise RuntimeError("voc_incr_create failed (see the log)")
+        self.last_launches, self.last_ms = 0, 0.0    # of the last push
+        self.state_bytes = int(lib.voc_incr_state_bytes(self.h))     # per stream, constant
+
+    def device_bytes(self):
+        """device memory the object holds (fixed at creation)"""
+        return int(self.lib.voc_incr_device_bytes(self.h))
+
+    def reset(self, k):
+        """stream k starts a new utterance"""
+        if self.lib.voc_incr_reset(self.h, int(k)) != 0:
+            raise RuntimeError("voc_incr_reset failed")
+
+    def push(self, streams, new_codes, finish, int16=True):
+        """streams[i] takes the frames new_codes[i] [k][16] (0 <= k <= chunk_tokens), and its utterance ends if finish[i] ->
+        per entry the samples of its new frames."""
+        st = np.array(streams, np.int32)
+        n_new = np.array([len(c) for c in new_codes], np.int32)
+        fin = np.array([int(f) for f in finish], np.int32)
+        cap = int(self.lib.voc_incr_push_max_samples(self.h, len(st), hiplib.iptr(st), hiplib.iptr(n_new), hiplib.iptr(fin)))
+        if cap < 0:
+            raise RuntimeError("voc_incr_push: invalid push")
+        args = (self.h, len(st), hiplib.iptr(st), _cat(new_codes).ctypes.data_as(hiplib.i64p), hiplib.iptr(n_new), hiplib.iptr(fin))
+        fn = self.lib.voc_incr_push if int16 else self.lib.voc_incr_push_f32
+        pcm = _packed(fn, args, len(st), cap, int16)
+        self.last_launches = int(self.lib.voc_incr_last_launches(self.h))
+        self.last_ms = float(self.lib.voc_incr_last_ms(self.h))
+        return pcm
+
+    def close(self):
+        if self.h:
+            self.lib.voc_incr_free(self.h)
             self.h = None

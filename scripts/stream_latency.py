@@ -9,11 +9,16 @@ ways in one process, alternating, `--repeats` times after one untimed pass of ea
           batch server does for {"stream": true};
   batch   the current reply: the frame loop to the end (q3e_start + q3e_run), then one voc_synthesize_batch call (uncapped grid).
 
+  incremental  (--incremental) the stream leg with the carry-state decode (voc_incr_push) in place of the chunk walk: every
+          check's new frames become samples at once -- what the batch server does for {"stream": true, "vocoder": "incremental"}.
+          Its joined PCM is checked against Vocoder.synthesize_incremental per utterance, bit for bit.
+
 Both exact fp32, int16 out.  Per utterance: time from the request's start to its first and to its last final sample (batch: the
 reply goes out once everything is done, so both are the request's end).  Fixed lengths (EOS off, --frames frames) and natural
 lengths (EOS on).  The joined streamed PCM of every utterance is checked against the batch reply, bit for bit.
 
     python scripts/stream_latency.py --out profiles/stream_latency.json
+    python scripts/stream_latency.py --incremental --out profiles/stream_latency_incremental.json
 """
 from __future__ import annotations
 
@@ -43,7 +48,7 @@ def run_stream(eng, vs, pool, prefixes, n_text, frames, ignore_eos):
     U = len(prefixes)
     first, last = [None] * U, [None] * U
     pcm = [[] for _ in range(U)]
-    stats = {"pushes": 0, "decode_calls": 0, "chunks": 0, "push_gpu_ms": 0.0, "push_wall_ms": 0.0, "loop_wait_ms": 0.0}
+    stats = {"pushes": 0, "decode_calls": 0, "chunks": 0, "launches": 0, "push_gpu_ms": 0.0, "push_wall_ms": 0.0, "loop_wait_ms": 0.0}
     slot_utt, pushed = [None] * eng.max_batch, [0] * eng.max_batch
     fut = [None]
     t0 = time.perf_counter()
@@ -62,8 +67,9 @@ def run_stream(eng, vs, pool, prefixes, n_text, frames, ignore_eos):
             if f:
                 last[u] = now
         stats["pushes"] += 1
-        stats["decode_calls"] += vs.last_decodes
-        stats["chunks"] += vs.last_chunks
+        stats["decode_calls"] += getattr(vs, "last_decodes", 0)      # (the chunk walk's counters)
+        stats["chunks"] += getattr(vs, "last_chunks", 0)
+        stats["launches"] += getattr(vs, "last_launches", 0)         # (the incremental decode's)
         stats["push_gpu_ms"] += vs.last_ms
         stats["push_wall_ms"] += (time.perf_counter() - ts) * 1e3
 
@@ -120,6 +126,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--cache", default=os.environ.get("Q3_BENCH_CACHE", "/tmp/q3_bench_cache"))
+    ap.add_argument("--incremental", action="store_true", help="add the carry-state incremental leg (voc_incr_push)")
     ap.add_argument("--out", default=None, help="write the JSON result here too")
     a = ap.parse_args()
     lib = hiplib.load()
@@ -134,6 +141,7 @@ def main():
     lib.voc_set_exact_fp32(1)
     voc = Vocoder(voc_path, 64, min(U, 32))
     vs = voc.stream(U)
+    vi = voc.incremental(U) if a.incremental else None
     pool = ThreadPoolExecutor(max_workers=1)
     result = {"what": "first / last final sample per utterance of one request, streaming chunk walk vs generate-then-vocode",
               "utterances": U, "max_frames": a.frames, "repeats": a.repeats, "vocoder": "full table, exact fp32, int16 out",
@@ -141,11 +149,13 @@ def main():
     try:
         for leg, ignore_eos in (("fixed", True), ("natural", False)):
             runs = {"stream": [], "batch": []}
+            if a.incremental:
+                runs["incremental"] = []
             for rep in range(a.repeats + 1):
-                for mode in ("stream", "batch"):
-                    if mode == "stream":
+                for mode in runs:
+                    if mode != "batch":
                         lib.voc_set_max_workgroups(-1)
-                        r = run_stream(eng, vs, pool, prefixes, n_text, a.frames, ignore_eos)
+                        r = run_stream(eng, vs if mode == "stream" else vi, pool, prefixes, n_text, a.frames, ignore_eos)
                     else:
                         lib.voc_set_max_workgroups(0)
                         r = run_batch(eng, voc, prefixes, n_text, a.frames, ignore_eos)
@@ -158,6 +168,12 @@ def main():
             frames_total = int(sum(len(c) for c in bc))
             out = {"frames_total": frames_total, "frames_min_max": [int(min(len(c) for c in bc)), int(max(len(c) for c in bc))],
                    "bit_identical": bool(identical)}
+            if a.incremental:
+                ic, ip = runs["incremental"][-1][0], runs["incremental"][-1][1]
+                lib.voc_set_max_workgroups(0)
+                out["incremental_bit_identical_to_synthesize_incremental"] = bool(
+                    all(np.array_equal(x, y) for x, y in zip(ic, bc)) and
+                    all(np.array_equal(p, voc.synthesize_incremental(c, int16=True)) for c, p in zip(ic, ip)))
             for mode, rs in runs.items():
                 walls = [r[4] for r in rs]
                 out[mode] = {
@@ -172,6 +188,11 @@ def main():
                 if mode == "stream":
                     out[mode].update({"pushes": st["pushes"], "decode_calls": st["decode_calls"], "chunks": st["chunks"],
                                       "chunks_per_call": round(st["chunks"] / max(st["decode_calls"], 1), 2),
+                                      "push_gpu_ms": round(st["push_gpu_ms"], 1), "push_wall_ms": round(st["push_wall_ms"], 1),
+                                      "frame_loop_wait_for_push_ms": round(st["loop_wait_ms"], 1)})
+                elif mode == "incremental":
+                    out[mode].update({"pushes": st["pushes"], "launches": st["launches"],
+                                      "launches_per_push": round(st["launches"] / max(st["pushes"], 1), 1),
                                       "push_gpu_ms": round(st["push_gpu_ms"], 1), "push_wall_ms": round(st["push_wall_ms"], 1),
                                       "frame_loop_wait_for_push_ms": round(st["loop_wait_ms"], 1)})
                 else:
