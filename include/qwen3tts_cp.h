@@ -20,6 +20,12 @@
  *
  * Buffers are caller-owned host memory; calls are synchronous; one caller
  * thread per handle.  No CPU fallback.
+ *
+ * Device memory: besides the weights, cp_load builds a table of layer 0's q|k|v
+ * projection of every embedding row of groups 0..13 (14 x 2048 x 4096 f32 =
+ * 470 MB; positions 2..15 of cp_predict read a row instead of running that
+ * projection; same results bit for bit).  Q3_CP_QKV_TABLE=0 in the environment
+ * when the model is loaded leaves the table out.
  */
 #ifndef QWEN3TTS_CP_H
 #define QWEN3TTS_CP_H

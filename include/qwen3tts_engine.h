@@ -140,7 +140,9 @@ int q3e_release(void* e, int n, const int32_t* slots);
 /* Talker hidden state of every utterance after the last executed step ([B][hidden]). */
 int q3e_get_hidden(void* e, float* out);
 
-/* Algorithmic weight bytes one frame step streams (talker stack + head + 16 CP passes + 15 heads). */
+/* Algorithmic weight bytes one frame step streams (talker stack + head + 16 CP passes + 15 heads).  With the code
+ * predictor's layer-0 q|k|v table (the default; Q3_CP_QKV_TABLE=0 at load turns it off and saves its 470 MB of device
+ * memory) 14 of those passes read one 16 KB table row per utterance instead of layer 0's q|k|v weights. */
 double q3e_step_weight_bytes(void* e);
 
 #ifdef __cplusplus

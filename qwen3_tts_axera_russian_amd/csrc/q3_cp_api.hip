@@ -64,9 +64,13 @@ int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const C
         rm.pos_base = 1;
         if (run_stack(s, m, m.cp, w, kv, R, rm, 256, row0)) return -1;
     }
+    // positions 2..: the input is row code_g of cp_emb[g-1], so layer 0's q|k|v comes from the table built at load
+    // (copied by the arg-max launch that gathers the embedding row) where this row count sums K as the table did
+    const bool qkv_tab = m.cp_qkv_serves(R);
     for (int g = 0; g < G; g++) {
         if (g > 0) {
             rm.pos_base = g + 1;
+            rm.skip_qkv0 = qkv_tab;
             if (run_stack(s, m, m.cp, w, kv, R, rm, 256, row0)) return -1;
         }
         // final RMSNorm folded into the head GEMV's prologue (code_predictor_server.py:129,136)
@@ -107,6 +111,11 @@ int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const C
             x.ssq_out = w.ssq;
             x.xh_out = w.xh;
             x.gamma_next = m.cp.L[0].in_ln;
+            if (qkv_tab) {
+                x.next_qkv = m.cp_qkv_rows(g);
+                x.qkv_out = w.qkv;
+                x.qkv_ld = (c.n_heads + 2 * c.n_kv) * c.head_dim;
+            }
         } else if (io.fb_h) {
             x.talker_emb = m.talker_emb;
             x.talker_vocab = c.talker_vocab;

@@ -809,8 +809,16 @@ double q3e_step_weight_bytes(void* ee) {
     if (!e) return 0.0;
     const ModelCfg& c = e->m->cfg;
     const double head = 2.0 * c.hidden;
-    return (double)e->m->talker.weight_bytes + head * c.talker_vocab +
-           (double)(c.cp_groups + 1) * (double)e->m->cp.weight_bytes + head * c.cp_vocab * c.cp_groups;
+    double bytes = (double)e->m->talker.weight_bytes + head * c.talker_vocab +
+                   (double)(c.cp_groups + 1) * (double)e->m->cp.weight_bytes + head * c.cp_vocab * c.cp_groups;
+    int row0 = 0, R = e->B;
+    if (e->B > 0) chain_rows(e, 0, row0, R);
+    if (R > 0 && e->m->cp_qkv_serves(R)) {
+        // positions 2.. of the code predictor take layer 0's q|k|v from the table: one f32 row per utterance instead of the weights
+        const double qkv_ld = (double)(c.n_heads + 2 * c.n_kv) * c.head_dim;
+        bytes -= (double)(c.cp_groups - 1) * (qkv_ld * c.hidden * 2.0 - 4.0 * qkv_ld * e->B);
+    }
+    return bytes;
 }
 
 }  // extern "C"

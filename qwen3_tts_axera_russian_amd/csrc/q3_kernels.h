@@ -42,6 +42,10 @@ struct LinArgs {
     half_t* act = nullptr;
 };
 int launch_linear(hipStream_t s, const LinArgs& a, int pro, int epi);
+// How launch_linear's weight-streaming kernels would split K for `rows` rows of an N-column projection: k-blocks of 32 per
+// wave (the waves' partial sums are added in wave order), or 0 where the rows go to the tiled GEMM / no kernel exists.
+// Two row counts with the same answer add the products of one row in the same order: bit-identical rows.
+int linear_decode_kbw(int K, int N, int rows);
 
 // Repack a row-major fp16 matrix src[N][K] into fragment order inside dst:
 // source 16-row tile ts lands at destination tile (tile_off + ts*tile_stride).
@@ -175,6 +179,11 @@ struct CpArgmaxArgs {
     float* ssq_out = nullptr;
     half_t* xh_out = nullptr;           // pre-scaled GEMM input for the layer that consumes h_out ...
     const float* gamma_next = nullptr;  // ... whose input norm weight this is
+    // with next_table: row `token` of next_qkv (f32 [V][qkv_ld], Model::cp_qkv_tab of this group: layer 0's q|k|v of every
+    // row of next_table) is copied into row r of qkv_out ([rows][qkv_ld], LinArgs::y / ldy of that launch); null = none
+    const float* next_qkv = nullptr;
+    float* qkv_out = nullptr;
+    int qkv_ld = 0;
     // feedback (when talker_emb != null): h_out = talker_emb[code0] + sum_g cp_tables[g][code_{g+1}] + pad
     const float* talker_emb = nullptr;
     int talker_vocab = 0;

@@ -929,6 +929,22 @@ int reset_linear_knobs() {
     return 0;
 }
 
+// row tile of linear_kernel (in 16-row blocks) for `rows` rows of an N-column projection
+static int decode_mt16(int rows, int N) {
+    int mt16 = rows <= 16 ? 1 : rows <= 32 ? 2 : 4;
+    // narrow outputs (o/down, N = 1024) have only N/16 = 64 column tiles: split the rows over two
+    // workgroups per tile instead (same XCD under round-robin placement, the weights come once from HBM)
+    if (rows > 16 && rows <= 32 && ((g_split_rows_narrow == 1 && N <= 1024) || g_split_rows_narrow == 2)) mt16 = 1;
+    return mt16;
+}
+
+int linear_decode_kbw(int K, int N, int rows) {
+    const int ki = K == 1024 ? 0 : K == 2048 ? 1 : K == 3072 ? 2 : -1;
+    if (rows <= 0 || rows >= g_gemm_min_rows || ki < 0 || N % 32) return 0;
+    const int mt16 = decode_mt16(rows, N);
+    return g_tune_kbw[ki][mt16 == 1 ? 0 : mt16 == 2 ? 1 : 2];
+}
+
 int launch_linear(hipStream_t s, const LinArgs& a, int pro, int epi) {
     g_last_variant = "";
     const int rows = a.M - a.m_begin;
@@ -946,10 +962,7 @@ int launch_linear(hipStream_t s, const LinArgs& a, int pro, int epi) {
         if (K == 2048) return launch_linear_narrow_t<16, 4>(s, a);
         if (K == 3072) return launch_linear_narrow_t<12, 8>(s, a);
     }
-    int mt16 = rows <= 16 ? 1 : rows <= 32 ? 2 : 4;
-    // narrow outputs (o/down, N = 1024) have only N/16 = 64 column tiles: split the rows over two
-    // workgroups per tile instead (same XCD under round-robin placement, the weights come once from HBM)
-    if (rows > 16 && rows <= 32 && ((g_split_rows_narrow == 1 && a.N <= 1024) || g_split_rows_narrow == 2)) mt16 = 1;
+    const int mt16 = decode_mt16(rows, a.N);
     const int kbw = g_tune_kbw[ki][mt16 == 1 ? 0 : mt16 == 2 ? 1 : 2];
     const int nw = K / 32 / kbw;
     // two column tiles per workgroup halve the activation traffic through L2 (it is the larger stream
@@ -2123,11 +2136,11 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     if constexpr (SLOTS)
         Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
                       "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
-                      "s"(a.talker_emb), "s"(a.slots), "s"(a.forced));
+                      "s"(a.talker_emb), "s"(a.slots), "s"(a.forced), "s"(a.next_qkv), "s"(a.qkv_out), "s"(a.qkv_ld));
     else
         Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
                       "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
-                      "s"(a.talker_emb), "s"(a.temperature), "s"(a.forced));
+                      "s"(a.talker_emb), "s"(a.temperature), "s"(a.forced), "s"(a.next_qkv), "s"(a.qkv_out), "s"(a.qkv_ld));
     Q3_TL(43);
     __shared__ float sv[4];
     __shared__ int si[4];
@@ -2226,9 +2239,54 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
         feedback_row(fc, r, a.talker_emb, a.talker_vocab, a.cp_tables, a.V, a.n_groups, a.pad_embed,
                      a.h_out, a.ssq_out, a.H, a.group, bidx, fz, a.xh_out, a.gamma_next);
     } else if (a.next_table) {
-        for (int k4 = tid; k4 < a.H / 4; k4 += 256) {
-            const float4 v = *(const float4*)(a.next_table + (size_t)bidx * a.H + k4 * 4);
-            store_row_ssq(a.h_out, a.ssq_out, r, a.H, k4, v, a.xh_out, a.gamma_next);
+        // a forced id beyond the vocabulary embeds as zeros (gather_embed_kernel's rule) and reads neither table; the
+        // loads below are unconditional at a clamped index, so that none of them sits behind a branch of its own
+        const bool ok = bidx < a.V;
+        const int t = ok ? bidx : 0;
+        const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+        const float* erow = a.next_table + (size_t)t * a.H;
+        const int ne4 = a.H / 4;
+        if (a.next_qkv) {
+            // layer 0's q|k|v of this token comes from the table of the group (a pure function of the token: cp_frame
+            // launches no q|k|v GEMV for this pass): its loads go out together with the embedding row's, one round trip
+            constexpr int QV = 4;                       // float4 per thread held in registers: 4096 columns
+            const int nq4 = a.qkv_ld / 4;
+            const float4* tq = (const float4*)(a.next_qkv + (size_t)t * a.qkv_ld);
+            float4* dq = (float4*)(a.qkv_out + (size_t)r * a.qkv_ld);
+            float4 ev = *(const float4*)(erow + (tid < ne4 ? tid : 0) * 4);
+            float4 qv[QV];
+#pragma unroll
+            for (int j = 0; j < QV; j++) {
+                const int i = tid + 256 * j;
+                qv[j] = tq[i < nq4 ? i : 0];
+            }
+            if (!ok) {   // (uniform)
+                ev = zero;
+#pragma unroll
+                for (int j = 0; j < QV; j++) qv[j] = zero;
+            }
+            if (tid < ne4) store_row_ssq(a.h_out, a.ssq_out, r, a.H, tid, ev, a.xh_out, a.gamma_next);
+#pragma unroll
+            for (int j = 0; j < QV; j++) {
+                const int i = tid + 256 * j;
+                if (i < nq4) dq[i] = qv[j];
+            }
+            for (int k4 = tid + 256; k4 < ne4; k4 += 256) {   // rows beyond 1024 / 4096 columns
+                float4 v = *(const float4*)(erow + k4 * 4);
+                if (!ok) v = zero;
+                store_row_ssq(a.h_out, a.ssq_out, r, a.H, k4, v, a.xh_out, a.gamma_next);
+            }
+            for (int i = tid + 256 * QV; i < nq4; i += 256) {
+                float4 v = tq[i];
+                if (!ok) v = zero;
+                dq[i] = v;
+            }
+        } else {
+            for (int k4 = tid; k4 < ne4; k4 += 256) {
+                float4 v = *(const float4*)(erow + k4 * 4);
+                if (!ok) v = zero;
+                store_row_ssq(a.h_out, a.ssq_out, r, a.H, k4, v, a.xh_out, a.gamma_next);
+            }
         }
     }
 }

@@ -35,6 +35,20 @@ struct Model {
     std::vector<float*> cp_emb;   // f32 [cp_vocab][hidden] each
     std::vector<DevLinear> cp_head;
     const float** d_cp_emb_ptrs = nullptr;  // device array of the cp_emb pointers
+    // Layer 0's q|k|v of the code predictor for every row of cp_emb[0 .. cp_groups-2]: f32 [cp_groups-1][cp_vocab][qkv_ld],
+    // the exact bits of run_stack's PRO_NORM / EPI_STORE launch on that embedding row, built at load by that launch
+    // itself (positions 2.. of a frame embed a code-predictor token, so this launch is a function of (group, token)).
+    // Null with Q3_CP_QKV_TABLE=0.  cp_qkv_kbw: the K split (linear_decode_kbw) its rows were summed with -- a pass whose
+    // row count would split K differently keeps the live launch.
+    float* cp_qkv_tab = nullptr;
+    int cp_qkv_kbw = 0;
+    const float* cp_qkv_rows(int group) const {   // table of the tokens of cp_emb[group]
+        return cp_qkv_tab + (size_t)group * cfg.cp_vocab * ((cfg.n_heads + 2 * cfg.n_kv) * cfg.head_dim);
+    }
+    // whether a pass of `rows` rows may take layer 0's q|k|v from the table
+    bool cp_qkv_serves(int rows) const {
+        return cp_qkv_tab && linear_decode_kbw(cfg.hidden, (cfg.n_heads + 2 * cfg.n_kv) * cfg.head_dim, rows) == cp_qkv_kbw;
+    }
     float *rope_cos = nullptr, *rope_sin = nullptr;  // [max_pos][head_dim/2]
     int max_pos = 0;
     std::vector<void*> allocs;
@@ -90,6 +104,9 @@ struct RowMap {            // which (slot, position) each row feeds
     // rows, slot, first position); without a table a pass with slot_stride 0 / pos_stride 1 is tiled implicitly
     const int* tiles = nullptr;
     int n_tiles = 0;
+    // layer 0's q|k|v rows already sit in w.qkv (cp_frame: copied from Model::cp_qkv_tab by the producer of h): that
+    // launch is left out
+    bool skip_qkv0 = false;
 };
 
 // Run every layer of `st` over R rows whose residual stream (+ssq partials) sits in w.h / w.ssq.

@@ -138,6 +138,64 @@ struct Loader {
         st.final_norm = up_f32(std::string(prefix) + ".norm", 1, H);
         return ok;
     }
+    // Model::cp_qkv_tab: for every group's embedding table, the gather's own h / ssq / xh of all cp_vocab rows, then layer
+    // 0's q|k|v launch over them, in passes of as many rows as the weight-streaming kernel takes
+    bool build_cp_qkv_table() {
+        static const bool on = !(getenv("Q3_CP_QKV_TABLE") && atoi(getenv("Q3_CP_QKV_TABLE")) == 0);
+        const ModelCfg& c = m->cfg;
+        const int H = c.hidden, V = c.cp_vocab, G = c.cp_groups, ld = (c.n_heads + 2 * c.n_kv) * c.head_dim;
+        if (!on || G < 2) return true;
+        int pass = 64;
+        while (pass >= 16 && !linear_decode_kbw(H, ld, pass)) pass /= 2;
+        if (pass < 16) {
+            Q3_LOG("code predictor: no q|k|v table (launch_linear has no weight-streaming kernel for K=%d)", H);
+            return true;
+        }
+        const size_t Vp = ((size_t)V + 63) / 64 * 64, bytes = (size_t)(G - 1) * V * ld * sizeof(float);
+        float* tab = (float*)dalloc(bytes);
+        int* ids = nullptr;
+        float *h = nullptr, *ssq = nullptr;
+        half_t* xh = nullptr;
+        bool good = tab && hipMalloc((void**)&ids, Vp * 4) == hipSuccess && hipMalloc((void**)&h, Vp * H * 4) == hipSuccess &&
+                    hipMalloc((void**)&ssq, Vp * (H / 16) * 4) == hipSuccess && hipMalloc((void**)&xh, Vp * H * 2) == hipSuccess;
+        if (good) {
+            std::vector<int> iota(Vp, -1);   // (rows beyond the vocabulary: zeros, computed by no pass)
+            for (int t = 0; t < V; t++) iota[t] = t;
+            good = hipMemcpy(ids, iota.data(), Vp * 4, hipMemcpyHostToDevice) == hipSuccess;
+        }
+        for (int g = 0; g + 1 < G && good; g++) {
+            good = launch_gather_embed(s, m->cp_emb[g], V, H, ids, 1, nullptr, 0, 0, h, ssq, (int)Vp, 0, 0, nullptr, xh,
+                                       m->cp.L[0].in_ln) == 0;
+            for (int r0 = 0; r0 < V && good; r0 += pass) {
+                LinArgs a;   // run_stack's q/k/v launch
+                a.wp = m->cp.L[0].qkv.wp;
+                a.N = m->cp.L[0].qkv.N;
+                a.K = H;
+                a.M = r0 + pass < V ? r0 + pass : V;
+                a.m_begin = r0;
+                a.nt = m->cp.nt;
+                a.x16 = xh;
+                a.ssq = ssq;
+                a.ssq_parts = H / 16;
+                a.eps = c.eps;
+                a.y = tab + (size_t)g * V * ld;
+                a.ldy = ld;
+                good = launch_linear(s, a, PRO_NORM, EPI_STORE) == 0;
+            }
+        }
+        good = good && hipStreamSynchronize(s) == hipSuccess;
+        for (void* d : {(void*)ids, (void*)h, (void*)ssq, (void*)xh})
+            if (d) hipFree(d);
+        if (!good) {
+            Q3_LOG("code predictor: building the q|k|v table failed");
+            ok = false;
+            return false;
+        }
+        m->cp_qkv_tab = tab;
+        m->cp_qkv_kbw = linear_decode_kbw(H, ld, pass);
+        Q3_LOG("code predictor: layer-0 q|k|v table, %d groups x %d tokens x %d columns f32 = %zu bytes", G - 1, V, ld, bytes);
+        return true;
+    }
 };
 
 }  // namespace
@@ -201,6 +259,7 @@ Model* model_load(const char* path, bool want_talker, bool want_cp, const char* 
             Q3_LOG("weight file lacks talker.codec_embedding (code_0 embedding of the code predictor)");
             L.ok = false;
         }
+        if (L.ok) L.build_cp_qkv_table();
         m->has_cp = L.ok;
     }
     // RoPE tables, float32 arithmetic like the HF rotary embedding (inv_freq = 1/theta^(2i/d))
@@ -342,7 +401,7 @@ int run_stack(hipStream_t s, const Model& m, const DevStack& st, Work& w, KVCach
         a.eps = c.eps;
         a.y = w.qkv;
         a.ldy = qkv_ld;
-        if (launch_linear(s, a, PRO_NORM, EPI_STORE)) return -1;
+        if (!(li == 0 && rm.skip_qkv0) && launch_linear(s, a, PRO_NORM, EPI_STORE)) return -1;
         // attention
         AttnArgs t;
         t.qkv = w.qkv;

@@ -598,3 +598,63 @@ extern "C" int q3t_inspect_weights(const char* path, const char* aux_dir, char* 
     }
     return (int)p.tensors.size();
 }
+
+// ---- the code predictor's layer-0 q|k|v table (Model::cp_qkv_tab) against the launch it replaces ----
+// A model with the code-predictor stack (and whatever Q3_CP_QKV_TABLE made of the table); null on failure.
+extern "C" void* q3t_cp_model_load(const char* path) { return model_load(path, false, true); }
+extern "C" void q3t_cp_model_free(void* m) { model_free((Model*)m); }
+// q|k|v columns of a row; 0 when the model carries no table
+extern "C" int q3t_cp_qkv_ld(void* mm) {
+    const Model* m = (const Model*)mm;
+    return m && m->cp_qkv_tab ? (m->cfg.n_heads + 2 * m->cfg.n_kv) * m->cfg.head_dim : 0;
+}
+// 1 when a code-predictor pass of `rows` rows takes layer 0's q|k|v from the table (cp_frame's own predicate)
+extern "C" int q3t_cp_qkv_serves(void* mm, int rows) { return mm && ((const Model*)mm)->cp_qkv_serves(rows) ? 1 : 0; }
+// out[i][ld] = table row toks[i] of `group` (the tokens of cp.codec_emb.<group>); ids outside the vocabulary: -2
+extern "C" int q3t_cp_qkv_tab(void* mm, int group, const int* toks, int n, float* out) {
+    const Model* m = (const Model*)mm;
+    const int ld = q3t_cp_qkv_ld(mm);
+    if (!ld || group < 0 || group + 1 >= m->cfg.cp_groups) return -1;
+    for (int i = 0; i < n; i++) {
+        if (toks[i] < 0 || toks[i] >= m->cfg.cp_vocab) return -2;
+        Q3_HIP(hipMemcpy(out + (size_t)i * ld, m->cp_qkv_rows(group) + (size_t)toks[i] * ld, (size_t)ld * 4, hipMemcpyDeviceToHost), -1);
+    }
+    return 0;
+}
+// The live launch at R rows: the embedding gather of rows toks[0..R) of cp.codec_emb.<group> into a pass's workspace
+// (h, ssq partials, xh), then run_stack's layer-0 q|k|v launch over rows [row0, row0 + R); out[R][ld].  The variant the
+// launch took is in q3t_last_linear_variant().
+extern "C" int q3t_cp_qkv_live(void* mm, int group, const int* toks, int R, int row0, float* out) {
+    const Model* m = (const Model*)mm;
+    if (!m || !m->has_cp || group < 0 || group >= m->cfg.cp_groups || R <= 0 || row0 % 16) return -1;
+    const ModelCfg& c = m->cfg;
+    const int H = c.hidden, ld = (c.n_heads + 2 * c.n_kv) * c.head_dim;
+    Work w;
+    DBuf dt;
+    std::vector<int> tk((size_t)row0 + R, -1);
+    for (int i = 0; i < R; i++) tk[row0 + i] = toks[i];
+    int rc = -1;
+    if (work_alloc(w, c, row0 + R, c.cp_ffn, c.cp_vocab) == 0 && dt.up(tk.data(), tk.size() * 4) &&
+        work_zero(nullptr, w, c, c.cp_ffn, c.cp_vocab) == 0 &&
+        launch_gather_embed(nullptr, m->cp_emb[group], c.cp_vocab, H, (const int*)dt.p, 1, nullptr, 0, 0, w.h, w.ssq, R, row0, 0,
+                            nullptr, w.xh, m->cp.L[0].in_ln) == 0) {
+        LinArgs a;   // as run_stack builds it
+        a.wp = m->cp.L[0].qkv.wp;
+        a.N = m->cp.L[0].qkv.N;
+        a.K = H;
+        a.M = row0 + R;
+        a.m_begin = row0;
+        a.nt = m->cp.nt;
+        a.x16 = w.xh;
+        a.ssq = w.ssq;
+        a.ssq_parts = H / 16;
+        a.eps = c.eps;
+        a.y = w.qkv;
+        a.ldy = ld;
+        if (launch_linear(nullptr, a, PRO_NORM, EPI_STORE) == 0 && hipDeviceSynchronize() == hipSuccess &&
+            hipMemcpy(out, w.qkv + (size_t)row0 * ld, (size_t)R * ld * 4, hipMemcpyDeviceToHost) == hipSuccess)
+            rc = 0;
+    }
+    work_free(w);
+    return rc;
+}

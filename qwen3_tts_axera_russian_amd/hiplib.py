@@ -186,6 +186,12 @@ def load_test():
     _sig(lib, "q3t_inspect_weights", c_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, c_int])
     _sig(lib, "q3t_bench_linear", c_float, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int])
     _sig(lib, "q3t_bench_chain", c_float, [c_int, c_int, c_int, c_int, c_int, c_int])
+    _sig(lib, "q3t_cp_model_load", c_void_p, [c_char_p])
+    _sig(lib, "q3t_cp_model_free", None, [c_void_p])
+    _sig(lib, "q3t_cp_qkv_ld", c_int, [c_void_p])
+    _sig(lib, "q3t_cp_qkv_serves", c_int, [c_void_p, c_int])
+    _sig(lib, "q3t_cp_qkv_tab", c_int, [c_void_p, c_int, i32p, c_int, f32p])
+    _sig(lib, "q3t_cp_qkv_live", c_int, [c_void_p, c_int, i32p, c_int, c_int, f32p])
     _test_lib = lib
     return lib
 
