@@ -53,7 +53,10 @@ int q3e_set_forced_codes(void* e, const int32_t* forced, int n_frames);
 /* Split every frame step into n (1..8) independent row groups that run as parallel branches of the
  * captured graph: hides per-kernel launch latency behind the other groups' work at the price of
  * streaming the weights n times.  Default 1 (env Q3_CHAINS overrides): on ROCm 7.2 the
- * per-chain graphs were measured NOT to overlap, so more chains only re-stream the weights. */
+ * per-chain graphs were measured NOT to overlap, so more chains only re-stream the weights.
+ * One chain runs on the engine's own stream; the per-chain streams and events are created by the first
+ * call (or Q3_CHAINS) that asks for more than one, so the default engine holds one hardware queue.
+ * Any chain count gives the same codes, and it may change between two q3e_run calls of a running batch. */
 int q3e_set_chains(void* e, int n);
 
 /* tts_pad embedding added to every feedback (tts_client.py:207-208); zeros until set. */

@@ -12,10 +12,14 @@ static bool two_row_enabled() {
 }
 
 int cp_seed_row0(const Work& w, int R, int row0, int R_total) {
+    (void)R;
+    (void)row0;
     if (R_total <= 0) R_total = R;
-    const int R16 = (R + 15) / 16 * 16;
-    const bool two = two_row_enabled() && row0 == 0 && R_total == R && 2 * R16 <= w.max_rows;
-    return two ? R16 : 0;
+    // the same place for a whole batch and for a row group of it (row r of the batch at B16 + r), so the chain count can
+    // change between two frames of a running batch
+    const int B16 = (R_total + 15) / 16 * 16;
+    const bool two = two_row_enabled() && 2 * B16 <= w.max_rows;
+    return two ? B16 : 0;
 }
 
 int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const CpFrameIO& io, int row0, int R_total) {
@@ -27,7 +31,26 @@ int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const C
     rm.slot_base = 0;
     rm.slot_stride = 1;  // row r owns KV slot r
     rm.pos_stride = 0;
-    if (seed0 > 0) {
+    if (seed0 > 0 && (row0 != 0 || R_total != R)) {
+        // a row group of a split batch (parallel chains): positions 0 and 1 as two passes, each through the kernels the
+        // one-pass form below runs -- K/V appended by the prep launch, then the attend launch -- so a row computes the
+        // bits it computes in the whole batch's pass (rows are independent; every linear kernel of these row counts
+        // sums K in one order).  Position 0 reads the talker hidden where the whole-batch form keeps it: row seed0 + r.
+        RowMap r0;
+        r0.slot_base = -seed0;   // row seed0 + r owns KV slot r
+        r0.slot_stride = 1;
+        r0.pos_base = 0;
+        r0.pos_stride = 0;
+        r0.same_slot_rows = true;
+        if (run_stack(s, m, m.cp, w, kv, R, r0, 256, seed0 + row0)) return -1;
+        if (launch_gather_embed(s, m.talker_emb, c.talker_vocab, H, io.codes, 0, io.n_frames, io.frame_cap, 0, w.h, w.ssq, R,
+                                row0, R_total, io.forced, w.xh, m.cp.L[0].in_ln))
+            return -1;
+        RowMap r1 = rm;
+        r1.pos_base = 1;
+        r1.same_slot_rows = true;
+        if (run_stack(s, m, m.cp, w, kv, R, r1, 256, row0)) return -1;
+    } else if (seed0 > 0) {
         // positions 0 and 1 in ONE pass: rows [0, R) = position 1 (the TALKER codec embedding of code_0,
         // code_predictor_server.py:97-98), rows [R16, R16 + R) = position 0 (the talker hidden); position 1 attends
         // to both through the cache (prep, then attend).  What follows continues in rows [0, R).
@@ -160,20 +183,28 @@ void* cp_load(const char* weights, const char* embeddings_dir, int max_batch) {
     // natively) with `embeddings_dir` = its --embeddings_dir (codec_embedding.npy): code_predictor_server.py:43-51
     if (!weights) return nullptr;
     if (max_batch <= 0) max_batch = 1;
-    Model* m = model_load(weights, false, true, embeddings_dir);
-    if (!m) return nullptr;
+    // one stream for the handle's whole life: the loader and the allocators' zeroing borrow it, so the handle occupies one
+    // hardware queue and nothing of it runs on the null stream
+    hipStream_t s = nullptr;
+    if (hipStreamCreate(&s) != hipSuccess) return nullptr;
+    Model* m = model_load(weights, false, true, embeddings_dir, s);
+    if (!m) {
+        hipStreamDestroy(s);
+        return nullptr;
+    }
     CpHandle* h = new CpHandle();
     h->m = m;
+    h->s = s;
     h->max_batch = max_batch;
     const ModelCfg& c = m->cfg;
-    bool ok = hipStreamCreate(&h->s) == hipSuccess;
-    ok = ok && kv_alloc(h->kv, c.cp_layers, max_batch, c.n_kv, c.cp_groups + 1) == 0;
-    ok = ok && work_alloc(h->w, c, 2 * ((max_batch + 15) / 16 * 16), c.cp_ffn, c.cp_vocab) == 0;   // two rows per utterance in the first pass
+    bool ok = kv_alloc(h->kv, c.cp_layers, max_batch, c.n_kv, c.cp_groups + 1, h->s) == 0;
+    ok = ok && work_alloc(h->w, c, 2 * ((max_batch + 15) / 16 * 16), c.cp_ffn, c.cp_vocab, h->s) == 0;   // two rows per utterance in the first pass
     ok = ok && hipMalloc((void**)&h->d_codes, sizeof(int) * 16 * max_batch) == hipSuccess;
     ok = ok && hipMalloc((void**)&h->d_nframes, sizeof(int) * max_batch) == hipSuccess;
     if (ok) {
         std::vector<int> ones(max_batch, 1);
-        ok = hipMemcpy(h->d_nframes, ones.data(), sizeof(int) * max_batch, hipMemcpyHostToDevice) == hipSuccess;
+        ok = hipMemcpyAsync(h->d_nframes, ones.data(), sizeof(int) * max_batch, hipMemcpyHostToDevice, h->s) == hipSuccess &&
+             hipStreamSynchronize(h->s) == hipSuccess;
     }
     if (!ok) {
         Q3_LOG("cp_load: allocation failed");

@@ -37,17 +37,21 @@ struct Engine {
     // run state
     int B = 0, ignore_eos = 0, cap_frames = 0, frames_run = 0;
     int frames_hi = 0;    // frames any slot may have recorded since q3e_start (q3e_refill restarts frames_run, not this)
-    GraphExec graph[8];   // one captured frame per chain, replayed on the chain's own stream (own HW queue)
+    GraphExec graph[8];   // one captured frame per chain: a single chain replays on s, parallel chains on their cs[c]
     int graph_B = 0, graph_ignore = -1, graph_cap = -1, graph_chains = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_run_ms = 0.f, last_prefill_ms = 0.f, last_host_launch_ms = 0.f;
     int* h_done = nullptr;  // pinned [max_batch]
+    int* h_read = nullptr;  // pinned [max_batch + max_frames * max_batch * 16]: n_past and the codes on their way to the caller
     // sampling (0 temperature = greedy, the reference's --temperature 0 limit)
     float t_temp = 0.f, t_top_p = 0.95f, c_temp = 0.f;
     int t_top_k = 50, c_top_k = 50;
     unsigned long long seed = 0;
     // independent row groups of one frame run as parallel branches of the graph (latency hiding)
+    // (one chain is the default and runs on s: the chain streams and their events exist only once more than one was asked for)
     int n_chains = 1;
+    bool use_prio = false;
+    int prio_hi = 0;
     hipStream_t cs[8] = {nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[8] = {nullptr};
     // per-slot mode (q3e_open / q3e_admit / q3e_release): every row reads its own budget, sampling settings and draw
@@ -151,6 +155,7 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     rm.slot_base = 0;        // row r of the batch owns KV slot r (no table: one dependent load less in front of every attention)
     rm.slot_stride = 1;
     rm.pos = e->d_posdec;
+    rm.rows_total = e->B;    // a chain of a split batch launches its attention as the whole batch would
     if (run_stack(st, m, m.talker, e->wt, e->kv_t, R, rm, 1024, row0)) return -1;
     return talker_tail(e, st, row0, R);
 }
@@ -168,24 +173,47 @@ void chain_rows(const Engine* e, int c, int& row0, int& R) {
     R = e->B / nc + (c < e->B % nc ? 1 : 0);
 }
 
+bool make_stream(const Engine* e, hipStream_t* st) {
+    return (e->use_prio ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, e->prio_hi)
+                        : hipStreamCreateWithFlags(st, hipStreamNonBlocking)) == hipSuccess;
+}
+
+// streams and events of n parallel chains (n > 1 only: a stream that exists occupies a hardware queue of the process)
+int ensure_chains(Engine* e, int n) {
+    if (n < 2) return 0;
+    if (!e->ev_fork) Q3_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming), -1);
+    for (int c = 0; c < n; c++) {
+        if (!e->cs[c] && !make_stream(e, &e->cs[c])) return -1;
+        if (!e->ev_join[c]) Q3_HIP(hipEventCreateWithFlags(&e->ev_join[c], hipEventDisableTiming), -1);
+    }
+    return 0;
+}
+
+// the stream chain c of the current batch runs on: the engine's own for a single chain
+hipStream_t chain_stream(const Engine* e, int c) { return n_chains_eff(e) == 1 ? e->s : e->cs[c]; }
+
 // one frame of every chain, eagerly, each on its own stream
 int frame_eager(Engine* e) {
     const int nc = n_chains_eff(e);
     for (int c = 0; c < nc; c++) {
         int row0, R;
         chain_rows(e, c, row0, R);
-        if (frame_chain(e, e->cs[c], row0, R)) return -1;
+        if (frame_chain(e, chain_stream(e, c), row0, R)) return -1;
     }
     return 0;
 }
 
-int fork_chains(Engine* e) {   // chain streams start after everything queued on the main stream
+int fork_chains(Engine* e) {   // chain streams start after everything queued on the main stream (a single chain IS the main stream)
+    const int nc = n_chains_eff(e);
+    if (nc == 1) return 0;
     Q3_HIP(hipEventRecord(e->ev_fork, e->s), -1);
-    for (int c = 0; c < n_chains_eff(e); c++) Q3_HIP(hipStreamWaitEvent(e->cs[c], e->ev_fork, 0), -1);
+    for (int c = 0; c < nc; c++) Q3_HIP(hipStreamWaitEvent(e->cs[c], e->ev_fork, 0), -1);
     return 0;
 }
 int join_chains(Engine* e) {   // the main stream continues after every chain stream
-    for (int c = 0; c < n_chains_eff(e); c++) {
+    const int nc = n_chains_eff(e);
+    if (nc == 1) return 0;
+    for (int c = 0; c < nc; c++) {
         Q3_HIP(hipEventRecord(e->ev_join[c], e->cs[c]), -1);
         Q3_HIP(hipStreamWaitEvent(e->s, e->ev_join[c], 0), -1);
     }
@@ -210,6 +238,7 @@ void q3e_free(void* ee) {
     for (void* p : ps)
         if (p) hipFree(p);
     if (e->h_done) hipHostFree(e->h_done);
+    if (e->h_read) hipHostFree(e->h_read);
     for (int c = 0; c < 8; c++) {
         if (e->cs[c]) hipStreamDestroy(e->cs[c]);
         if (e->ev_join[c]) hipEventDestroy(e->ev_join[c]);
@@ -224,41 +253,44 @@ void q3e_free(void* ee) {
 
 void* q3e_create(const char* weights, int max_batch, int n_ctx, int max_frames) {
     if (!weights || max_batch <= 0 || n_ctx <= 0 || max_frames <= 0) return nullptr;
-    Model* m = model_load(weights, true, true);
-    if (!m) return nullptr;
-    if (n_ctx > m->max_pos) {
-        Q3_LOG("q3e_create: n_ctx=%d exceeds the RoPE table (%d)", n_ctx, m->max_pos);
-        model_free(m);
+    Engine* e = new Engine();
+    // the frame loop is a latency-bound dependent chain: its stream gets the highest priority so that its short kernels
+    // are placed ahead of throughput work (Q3_STREAM_PRIO=0: the default priority; the vocoder's stream: q3_voc.hip)
+    int prio_lo = 0, prio_hi = 0;
+    e->use_prio = !(getenv("Q3_STREAM_PRIO") && atoi(getenv("Q3_STREAM_PRIO")) == 0) &&
+                  hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess && prio_lo != prio_hi;
+    e->prio_hi = prio_hi;
+    // ONE stream: uploads, prefill, the frame graph and the read-backs (the loader borrows it too), so the engine
+    // occupies one hardware queue of the process and nothing of it runs on the null stream
+    if (!make_stream(e, &e->s)) {
+        Q3_LOG("q3e_create: no stream");
+        q3e_free(e);
         return nullptr;
     }
-    Engine* e = new Engine();
+    Model* m = model_load(weights, true, true, nullptr, e->s);
+    if (!m) {
+        q3e_free(e);
+        return nullptr;
+    }
     e->m = m;
+    if (n_ctx > m->max_pos) {
+        Q3_LOG("q3e_create: n_ctx=%d exceeds the RoPE table (%d)", n_ctx, m->max_pos);
+        q3e_free(e);
+        return nullptr;
+    }
     e->max_batch = max_batch;
     e->n_ctx = n_ctx;
     e->max_frames = max_frames;
     const ModelCfg& c = m->cfg;
     e->prefill_rows = max_batch > 2048 ? max_batch : 2048;
-    // the frame loop is a latency-bound dependent chain: its queues get the highest priority so that its
-    // short kernels are placed ahead of throughput work (the vocoder stream asks for the lowest)
-    int prio_lo = 0, prio_hi = 0;
-    const bool use_prio = !(getenv("Q3_STREAM_PRIO") && atoi(getenv("Q3_STREAM_PRIO")) == 0) &&
-                          hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) == hipSuccess && prio_lo != prio_hi;
-    auto mkstream = [&](hipStream_t* st) {
-        return (use_prio ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_hi)
-                         : hipStreamCreateWithFlags(st, hipStreamNonBlocking)) == hipSuccess;
-    };
-    bool ok = mkstream(&e->s);
-    ok = ok && hipEventCreate(&e->ev0) == hipSuccess && hipEventCreate(&e->ev1) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) == hipSuccess;
-    for (int c = 0; c < 8 && ok; c++)
-        ok = mkstream(&e->cs[c]) &&
-             hipEventCreateWithFlags(&e->ev_join[c], hipEventDisableTiming) == hipSuccess;
+    bool ok = hipEventCreate(&e->ev0) == hipSuccess && hipEventCreate(&e->ev1) == hipSuccess;
     if (const char* nc = getenv("Q3_CHAINS")) e->n_chains = atoi(nc) < 1 ? 1 : atoi(nc) > 8 ? 8 : atoi(nc);
     else e->n_chains = 1;  // measured on MI355X/ROCm 7.2: graphs on separate streams do not overlap here
-    ok = ok && kv_alloc(e->kv_t, c.talker_layers, max_batch, c.n_kv, n_ctx) == 0;
-    ok = ok && kv_alloc(e->kv_c, c.cp_layers, max_batch, c.n_kv, c.cp_groups + 1) == 0;
-    ok = ok && work_alloc(e->wt, c, e->prefill_rows, c.talker_ffn, c.talker_vocab) == 0;
-    ok = ok && work_alloc(e->wc, c, 2 * ((max_batch + 15) / 16 * 16), c.cp_ffn, c.cp_vocab) == 0;   // two rows per utterance in the CP's first pass
+    ok = ok && ensure_chains(e, e->n_chains) == 0;
+    ok = ok && kv_alloc(e->kv_t, c.talker_layers, max_batch, c.n_kv, n_ctx, e->s) == 0;
+    ok = ok && kv_alloc(e->kv_c, c.cp_layers, max_batch, c.n_kv, c.cp_groups + 1, e->s) == 0;
+    ok = ok && work_alloc(e->wt, c, e->prefill_rows, c.talker_ffn, c.talker_vocab, e->s) == 0;
+    ok = ok && work_alloc(e->wc, c, 2 * ((max_batch + 15) / 16 * 16), c.cp_ffn, c.cp_vocab, e->s) == 0;   // two rows per utterance in the CP's first pass
     auto ialloc = [&](int** p, size_t n) { return hipMalloc((void**)p, sizeof(int) * n) == hipSuccess; };
     ok = ok && ialloc(&e->d_slot, e->prefill_rows) && ialloc(&e->d_pos, e->prefill_rows);
     ok = ok && ialloc(&e->d_tiles, (size_t)4 * e->prefill_rows);
@@ -269,13 +301,15 @@ void* q3e_create(const char* weights, int max_batch, int n_ctx, int max_frames) 
     ok = ok && ialloc(&e->d_codes, (size_t)max_frames * max_batch * 16);
     ok = ok && hipMalloc((void**)&e->d_pad, sizeof(float) * c.hidden) == hipSuccess;
     ok = ok && hipMalloc((void**)&e->d_seed, sizeof(unsigned long long) * max_batch) == hipSuccess;
-    ok = ok && hipMemset(e->d_seed, 0, sizeof(unsigned long long) * max_batch) == hipSuccess;
+    ok = ok && hipMemsetAsync(e->d_seed, 0, sizeof(unsigned long long) * max_batch, e->s) == hipSuccess;
     ok = ok && hipHostMalloc((void**)&e->h_done, sizeof(int) * max_batch, 0) == hipSuccess;
+    ok = ok && hipHostMalloc((void**)&e->h_read, sizeof(int) * ((size_t)max_batch + (size_t)max_frames * max_batch * 16), 0) == hipSuccess;
     if (ok) {
         std::vector<int> iota(max_batch);
         for (int i = 0; i < max_batch; i++) iota[i] = i;
-        ok = hipMemcpy(e->d_iota, iota.data(), sizeof(int) * max_batch, hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemset(e->d_pad, 0, sizeof(float) * c.hidden) == hipSuccess;
+        ok = hipMemcpyAsync(e->d_iota, iota.data(), sizeof(int) * max_batch, hipMemcpyHostToDevice, e->s) == hipSuccess;
+        ok = ok && hipMemsetAsync(e->d_pad, 0, sizeof(float) * c.hidden, e->s) == hipSuccess;
+        ok = hipStreamSynchronize(e->s) == hipSuccess && ok;   // (iota is a local)
     }
     if (!ok) {
         Q3_LOG("q3e_create: allocation failed");
@@ -312,8 +346,9 @@ int q3e_set_forced_codes(void* ee, const int32_t* forced, int n_frames) {
         if (e->B <= 0 || n_frames > e->max_frames) return -1;
         const size_t total = (size_t)e->max_frames * e->max_batch * 16;
         if (!e->d_forced) Q3_HIP(hipMalloc((void**)&e->d_forced, sizeof(int) * total), -1);
-        Q3_HIP(hipMemset(e->d_forced, 0xff, sizeof(int) * total), -1);   // -1 = free-running
-        Q3_HIP(hipMemcpy(e->d_forced, forced, sizeof(int) * 16 * (size_t)e->B * n_frames, hipMemcpyHostToDevice), -1);
+        Q3_HIP(hipMemsetAsync(e->d_forced, 0xff, sizeof(int) * total, e->s), -1);   // -1 = free-running
+        Q3_HIP(hipMemcpyAsync(e->d_forced, forced, sizeof(int) * 16 * (size_t)e->B * n_frames, hipMemcpyHostToDevice, e->s), -1);
+        Q3_HIP(hipStreamSynchronize(e->s), -1);   // the caller's array is its own again on return
     }
     if (on != e->forced_on) {
         e->forced_on = on;
@@ -326,6 +361,7 @@ int q3e_set_chains(void* ee, int n) {
     Engine* e = (Engine*)ee;
     if (!e || n < 1 || n > 8) return -1;
     if (n != e->n_chains) {
+        if (ensure_chains(e, n)) return -1;
         e->n_chains = n;
         for (auto& g : e->graph) g.reset();  // the captured frames cover the old row ranges
     }
@@ -335,7 +371,8 @@ int q3e_set_chains(void* ee, int n) {
 int q3e_set_pad_embed(void* ee, const float* pad) {
     Engine* e = (Engine*)ee;
     if (!e || !pad) return -1;
-    Q3_HIP(hipMemcpy(e->d_pad, pad, sizeof(float) * e->m->cfg.hidden, hipMemcpyHostToDevice), -1);
+    Q3_HIP(hipMemcpyAsync(e->d_pad, pad, sizeof(float) * e->m->cfg.hidden, hipMemcpyHostToDevice, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
     return 0;
 }
 
@@ -406,9 +443,9 @@ static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, co
             f.out_copy_ssq = e->wc.ssq;
             f.out_copy_xh = e->wc.xh;
             f.out_copy_gamma = m.cp.L[0].in_ln;
-            // the first frame's code predictor pass reads its position-0 rows where cp_frame expects them; with
-            // parallel chains (rows split over several frame chains) that is the sequential layout, offset 0
-            f.out_copy_row_off = n_chains_eff(e) == 1 ? cp_seed_row0(e->wc, B_total, 0, B_total) : 0;
+            // the first frame's code predictor pass reads its position-0 rows where cp_frame expects them (the same
+            // place for one chain and for parallel chains)
+            f.out_copy_row_off = cp_seed_row0(e->wc, B_total, 0, B_total);
             if (launch_final_norm(e->s, f)) return -1;
         }
         Q3_HIP(hipStreamSynchronize(e->s), -1);  // host staging vectors are reused by the next group
@@ -455,6 +492,7 @@ int q3e_start(void* ee, int B, const float* prefix, const int32_t* n_rows, const
     const int H = m.cfg.hidden;
     if (max_frames <= 0 || max_frames > e->max_frames) max_frames = e->max_frames;
     std::vector<int> pos0(B);
+    std::vector<unsigned long long> seeds;   // (host staging of this call's uploads: alive until the stream is synchronised)
     for (int b = 0; b < B; b++) {
         if (n_rows[b] <= 0 || n_rows[b] > e->prefill_rows || n_rows[b] + max_frames > e->n_ctx) {
             Q3_LOG("q3e_start: utterance %d: %d prefix rows + %d frames do not fit n_ctx=%d", b, n_rows[b], max_frames,
@@ -480,8 +518,8 @@ int q3e_start(void* ee, int B, const float* prefix, const int32_t* n_rows, const
         z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
         e->req_seed = e->n_requests == 1 ? e->seed : (z ^ (z >> 31));
         e->n_refills = 0;
-        std::vector<unsigned long long> seeds(B, e->req_seed);   // (the row index separates the slots' draws)
-        Q3_HIP(hipMemcpy(e->d_seed, seeds.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice), -1);
+        seeds.assign(B, e->req_seed);   // (the row index separates the slots' draws)
+        Q3_HIP(hipMemcpyAsync(e->d_seed, seeds.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice, e->s), -1);
     }
     if (e->forced_on) {   // forcing belongs to the batch it was set for
         e->forced_on = false;
@@ -533,14 +571,14 @@ int q3e_run(void* ee, int n_frames) {
         // first frame eagerly (real work; also sets the kernels' LDS attributes), then capture per chain
         if (frame_eager(e)) return -1;
         done_frames++;
-        for (int c = 0; c < nc; c++) Q3_HIP(hipStreamSynchronize(e->cs[c]), -1);
+        for (int c = 0; c < nc; c++) Q3_HIP(hipStreamSynchronize(chain_stream(e, c)), -1);
         for (int c = 0; c < nc; c++) {
             int row0, R;
             chain_rows(e, c, row0, R);
             e->graph[c].reset();
-            Q3_HIP(hipStreamBeginCapture(e->cs[c], hipStreamCaptureModeRelaxed), -1);
-            int rc = frame_chain(e, e->cs[c], row0, R);
-            hipError_t er = hipStreamEndCapture(e->cs[c], &e->graph[c].g);
+            Q3_HIP(hipStreamBeginCapture(chain_stream(e, c), hipStreamCaptureModeRelaxed), -1);
+            int rc = frame_chain(e, chain_stream(e, c), row0, R);
+            hipError_t er = hipStreamEndCapture(chain_stream(e, c), &e->graph[c].g);
             if (rc || er != hipSuccess) {
                 Q3_LOG("q3e_run: graph capture failed");
                 return -1;
@@ -559,7 +597,7 @@ int q3e_run(void* ee, int n_frames) {
         int chunk = n_frames - done_frames;
         if (!e->ignore_eos && chunk > check_every) chunk = check_every;
         for (int i = 0; i < chunk; i++)
-            for (int c = 0; c < nc; c++) Q3_HIP(hipGraphLaunch(e->graph[c].e, e->cs[c]), -1);
+            for (int c = 0; c < nc; c++) Q3_HIP(hipGraphLaunch(e->graph[c].e, chain_stream(e, c)), -1);
         done_frames += chunk;
         if (!e->ignore_eos && done_frames < n_frames) {
             if (join_chains(e)) return -1;
@@ -601,19 +639,26 @@ int q3e_get_codes(void* ee, int32_t* out, int max_out_frames, int32_t* n_frames_
         nf = std::min(hi, e->max_frames);
     }
     if (nf > max_out_frames) nf = max_out_frames;
-    Q3_HIP(hipMemcpy(out, e->d_codes, sizeof(int) * 16 * (size_t)e->B * nf, hipMemcpyDeviceToHost), -1);
-    if (n_frames_per_utt) {
-        Q3_HIP(hipMemcpy(n_frames_per_utt, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost), -1);
-    }
+    // through the pinned staging on the engine's own stream: a pageable destination would go through the runtime's staging
+    int* h_np = e->h_read;
+    int* h_codes = e->h_read + e->max_batch;
+    const size_t n_codes = 16 * (size_t)e->B * (nf > 0 ? nf : 0);
+    if (n_codes) Q3_HIP(hipMemcpyAsync(h_codes, e->d_codes, sizeof(int) * n_codes, hipMemcpyDeviceToHost, e->s), -1);
+    if (n_frames_per_utt) Q3_HIP(hipMemcpyAsync(h_np, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    if (n_codes) memcpy(out, h_codes, sizeof(int) * n_codes);
+    if (n_frames_per_utt) memcpy(n_frames_per_utt, h_np, sizeof(int) * e->B);
     return nf;
 }
 
 int q3e_get_done(void* ee, int32_t* done, int32_t* frames) {
     Engine* e = (Engine*)ee;
     if (!e || !done || e->B <= 0) return -1;
-    Q3_HIP(hipMemcpy(done, e->d_done, sizeof(int) * e->B, hipMemcpyDeviceToHost), -1);
-    std::vector<int> np(e->B);
-    Q3_HIP(hipMemcpy(np.data(), e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpyAsync(e->h_done, e->d_done, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
+    Q3_HIP(hipMemcpyAsync(e->h_read, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    memcpy(done, e->h_done, sizeof(int) * e->B);
+    std::vector<int> np(e->h_read, e->h_read + e->B);
     // the device raises done[b] on the step AFTER the budget's last frame, a step q3e_run never takes: an utterance
     // that has emitted its whole budget has ended
     for (int b = 0; b < e->B; b++)
@@ -800,7 +845,8 @@ int q3e_release(void* ee, int n, const int32_t* slots) {
 int q3e_get_hidden(void* ee, float* out) {
     Engine* e = (Engine*)ee;
     if (!e || !out || e->B <= 0) return -1;
-    Q3_HIP(hipMemcpy(out, e->wt.hidden_f32, sizeof(float) * (size_t)e->B * e->m->cfg.hidden, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpyAsync(out, e->wt.hidden_f32, sizeof(float) * (size_t)e->B * e->m->cfg.hidden, hipMemcpyDeviceToHost, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
     return 0;
 }
 

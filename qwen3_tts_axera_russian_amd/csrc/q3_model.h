@@ -55,8 +55,10 @@ struct Model {
     size_t device_bytes = 0;
 };
 
-// `path`: a Q3TTSW1 container, or the reference's own files (Pack::open_auto); `aux_dir`: its --embeddings_dir
-Model* model_load(const char* path, bool want_talker, bool want_cp, const char* aux_dir = nullptr);
+// `path`: a Q3TTSW1 container, or the reference's own files (Pack::open_auto); `aux_dir`: its --embeddings_dir.  `s`: the
+// stream the uploads and the repacking kernels run on (synchronised before the return); null = a stream of the loader's
+// own, destroyed when loading ends.  An owner that passes its stream keeps loading off every other hardware queue.
+Model* model_load(const char* path, bool want_talker, bool want_cp, const char* aux_dir = nullptr, hipStream_t s = nullptr);
 void model_free(Model* m);
 
 struct KVCache {
@@ -65,7 +67,7 @@ struct KVCache {
     size_t layer_stride() const { return (size_t)n_slots * n_kv * n_ctx * head_dim; }
     size_t bytes() const { return layer_stride() * n_layers * sizeof(half_t) * 2; }
 };
-int kv_alloc(KVCache& kv, int n_layers, int n_slots, int n_kv, int n_ctx);
+int kv_alloc(KVCache& kv, int n_layers, int n_slots, int n_kv, int n_ctx, hipStream_t s = nullptr);   // zeroed on s, synchronised
 void kv_free(KVCache& kv);
 int kv_zero(hipStream_t s, KVCache& kv);   // every slot's keys and values to 0 (asynchronous on s)
 
@@ -89,7 +91,7 @@ struct Work {
     int *map_slot = nullptr, *map_pos = nullptr;
     int map_R16 = 0;
 };
-int work_alloc(Work& w, const ModelCfg& c, int max_rows, int ffn, int max_vocab);
+int work_alloc(Work& w, const ModelCfg& c, int max_rows, int ffn, int max_vocab, hipStream_t s = nullptr);   // zeroed on s, synchronised
 void work_free(Work& w);
 // every activation buffer of w to 0 (asynchronous on s; ffn / max_vocab as for work_alloc): no row reads uninitialised memory
 int work_zero(hipStream_t s, Work& w, const ModelCfg& c, int ffn, int max_vocab);
@@ -107,6 +109,9 @@ struct RowMap {            // which (slot, position) each row feeds
     // layer 0's q|k|v rows already sit in w.qkv (cp_frame: copied from Model::cp_qkv_tab by the producer of h): that
     // launch is left out
     bool skip_qkv0 = false;
+    // rows of the whole step when this pass covers one row group of it (parallel chains): the attention launch is shaped
+    // for that many rows, so a row sums its cached positions in the same order whichever group it runs in.  0 = R.
+    int rows_total = 0;
 };
 
 // Run every layer of `st` over R rows whose residual stream (+ssq partials) sits in w.h / w.ssq.

@@ -16,6 +16,10 @@ struct Loader {
     std::vector<uint16_t> host16;
     bool ok = true;
 
+    // host -> device on the loader's stream, complete on return (the source may be a temporary)
+    bool up(void* d, const void* src, size_t bytes) {
+        return hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    }
     void* dalloc(size_t bytes) {
         void* d = nullptr;
         if (hipMalloc(&d, bytes) != hipSuccess) {
@@ -50,7 +54,7 @@ struct Loader {
         float* d = (float*)dalloc(ne * 4);
         if (!d) return nullptr;
         if (t->dtype == F32) {
-            if (hipMemcpy(d, t->data, ne * 4, hipMemcpyHostToDevice) != hipSuccess) ok = false;
+            if (!up(d, t->data, ne * 4)) ok = false;
         } else {
             std::vector<float> tmp(ne);
             const uint16_t* src = (const uint16_t*)t->data;
@@ -58,7 +62,7 @@ struct Loader {
                 for (size_t i = 0; i < ne; i++) tmp[i] = bf16_to_f32(src[i]);
             else
                 for (size_t i = 0; i < ne; i++) tmp[i] = h2f(src[i]);
-            if (hipMemcpy(d, tmp.data(), ne * 4, hipMemcpyHostToDevice) != hipSuccess) ok = false;
+            if (!up(d, tmp.data(), ne * 4)) ok = false;
         }
         return d;
     }
@@ -88,7 +92,7 @@ struct Loader {
             for (size_t i = 0; i < ne; i++) host16[i] = f2h_sat(bf16_to_f32(b[i]));
             src = host16.data();
         }
-        if (hipMemcpy(stage, src, ne * 2, hipMemcpyHostToDevice) != hipSuccess) {
+        if (!up(stage, src, ne * 2)) {
             ok = false;
             return false;
         }
@@ -161,7 +165,7 @@ struct Loader {
         if (good) {
             std::vector<int> iota(Vp, -1);   // (rows beyond the vocabulary: zeros, computed by no pass)
             for (int t = 0; t < V; t++) iota[t] = t;
-            good = hipMemcpy(ids, iota.data(), Vp * 4, hipMemcpyHostToDevice) == hipSuccess;
+            good = up(ids, iota.data(), Vp * 4);
         }
         for (int g = 0; g + 1 < G && good; g++) {
             good = launch_gather_embed(s, m->cp_emb[g], V, H, ids, 1, nullptr, 0, 0, h, ssq, (int)Vp, 0, 0, nullptr, xh,
@@ -200,7 +204,7 @@ struct Loader {
 
 }  // namespace
 
-Model* model_load(const char* path, bool want_talker, bool want_cp, const char* aux_dir) {
+Model* model_load(const char* path, bool want_talker, bool want_cp, const char* aux_dir, hipStream_t stream) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
         Q3_LOG("no HIP device available -- this library has no CPU path");
@@ -219,7 +223,8 @@ Model* model_load(const char* path, bool want_talker, bool want_cp, const char* 
     }
     hipGetDevice(&m->device);
     Loader L{m, p};
-    if (hipStreamCreate(&L.s) != hipSuccess) {
+    L.s = stream;
+    if (!stream && hipStreamCreateWithFlags(&L.s, hipStreamNonBlocking) != hipSuccess) {   // (every copy below is on L.s: nothing to order against the null stream)
         delete m;
         return nullptr;
     }
@@ -250,10 +255,7 @@ Model* model_load(const char* path, bool want_talker, bool want_cp, const char* 
         }
         if (L.ok) {
             m->d_cp_emb_ptrs = (const float**)L.dalloc(sizeof(float*) * c.cp_groups);
-            if (m->d_cp_emb_ptrs &&
-                hipMemcpy((void*)m->d_cp_emb_ptrs, m->cp_emb.data(), sizeof(float*) * c.cp_groups,
-                          hipMemcpyHostToDevice) != hipSuccess)
-                L.ok = false;
+            if (m->d_cp_emb_ptrs && !L.up((void*)m->d_cp_emb_ptrs, m->cp_emb.data(), sizeof(float*) * c.cp_groups)) L.ok = false;
         }
         if (!m->talker_emb) {
             Q3_LOG("weight file lacks talker.codec_embedding (code_0 embedding of the code predictor)");
@@ -278,12 +280,13 @@ Model* model_load(const char* path, bool want_talker, bool want_cp, const char* 
         m->rope_cos = (float*)L.dalloc(cs.size() * 4);
         m->rope_sin = (float*)L.dalloc(sn.size() * 4);
         if (L.ok) {
-            if (hipMemcpy(m->rope_cos, cs.data(), cs.size() * 4, hipMemcpyHostToDevice) != hipSuccess) L.ok = false;
-            if (hipMemcpy(m->rope_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice) != hipSuccess) L.ok = false;
+            if (!L.up(m->rope_cos, cs.data(), cs.size() * 4)) L.ok = false;
+            if (!L.up(m->rope_sin, sn.data(), sn.size() * 4)) L.ok = false;
         }
     }
+    hipStreamSynchronize(L.s);
     if (L.stage) hipFree(L.stage);
-    hipStreamDestroy(L.s);
+    if (!stream) hipStreamDestroy(L.s);   // the loader's own stream ends with the load: it holds no hardware queue afterwards
     if (!L.ok) {
         model_free(m);
         return nullptr;
@@ -297,7 +300,7 @@ void model_free(Model* m) {
     delete m;
 }
 
-int kv_alloc(KVCache& kv, int n_layers, int n_slots, int n_kv, int n_ctx) {
+int kv_alloc(KVCache& kv, int n_layers, int n_slots, int n_kv, int n_ctx, hipStream_t s) {
     kv.n_layers = n_layers;
     kv.n_slots = n_slots;
     kv.n_kv = n_kv;
@@ -305,8 +308,9 @@ int kv_alloc(KVCache& kv, int n_layers, int n_slots, int n_kv, int n_ctx) {
     const size_t bytes = kv.layer_stride() * n_layers * sizeof(half_t);
     Q3_HIP(hipMalloc((void**)&kv.k, bytes), -1);
     Q3_HIP(hipMalloc((void**)&kv.v, bytes), -1);
-    Q3_HIP(hipMemset(kv.k, 0, bytes), -1);
-    Q3_HIP(hipMemset(kv.v, 0, bytes), -1);
+    Q3_HIP(hipMemsetAsync(kv.k, 0, bytes, s), -1);
+    Q3_HIP(hipMemsetAsync(kv.v, 0, bytes, s), -1);
+    Q3_HIP(hipStreamSynchronize(s), -1);
     return 0;
 }
 void kv_free(KVCache& kv) {
@@ -338,7 +342,7 @@ int work_zero(hipStream_t s, Work& w, const ModelCfg& c, int ffn, int max_vocab)
     return 0;
 }
 
-int work_alloc(Work& w, const ModelCfg& c, int max_rows, int ffn, int max_vocab) {
+int work_alloc(Work& w, const ModelCfg& c, int max_rows, int ffn, int max_vocab, hipStream_t s) {
     max_rows = (max_rows + 127) / 128 * 128;   // the largest row tile (gemm_kernel: 128)
     w.max_rows = max_rows;
     w.hidden = c.hidden;
@@ -346,21 +350,22 @@ int work_alloc(Work& w, const ModelCfg& c, int max_rows, int ffn, int max_vocab)
     const int qkv_ld = (c.n_heads + 2 * c.n_kv) * c.head_dim;
     Q3_HIP(hipMalloc((void**)&w.rows_in, R * c.hidden * 4), -1);
     Q3_HIP(hipMalloc((void**)&w.h, R * c.hidden * 4), -1);
-    Q3_HIP(hipMemset(w.h, 0, R * c.hidden * 4), -1);
+    Q3_HIP(hipMemsetAsync(w.h, 0, R * c.hidden * 4, s), -1);
     Q3_HIP(hipMalloc((void**)&w.ssq, R * (c.hidden / 16) * 4), -1);
     Q3_HIP(hipMalloc((void**)&w.xh, R * c.hidden * 2), -1);
-    Q3_HIP(hipMemset(w.xh, 0, R * c.hidden * 2), -1);
+    Q3_HIP(hipMemsetAsync(w.xh, 0, R * c.hidden * 2, s), -1);
     Q3_HIP(hipMalloc((void**)&w.qkv, R * qkv_ld * 4), -1);
     Q3_HIP(hipMalloc((void**)&w.attn, R * c.n_heads * c.head_dim * 2), -1);
-    Q3_HIP(hipMemset(w.attn, 0, R * c.n_heads * c.head_dim * 2), -1);
+    Q3_HIP(hipMemsetAsync(w.attn, 0, R * c.n_heads * c.head_dim * 2, s), -1);
     Q3_HIP(hipMalloc((void**)&w.act, R * ffn * 2), -1);
-    Q3_HIP(hipMemset(w.act, 0, R * ffn * 2), -1);
+    Q3_HIP(hipMemsetAsync(w.act, 0, R * ffn * 2, s), -1);
     Q3_HIP(hipMalloc((void**)&w.hidden_f32, R * c.hidden * 4), -1);
     Q3_HIP(hipMalloc((void**)&w.hidden_f16, R * c.hidden * 2), -1);
-    Q3_HIP(hipMemset(w.hidden_f16, 0, R * c.hidden * 2), -1);
+    Q3_HIP(hipMemsetAsync(w.hidden_f16, 0, R * c.hidden * 2, s), -1);
     Q3_HIP(hipMalloc((void**)&w.logits, R * max_vocab * 4), -1);
     Q3_HIP(hipMalloc((void**)&w.map_slot, R * 4), -1);
     Q3_HIP(hipMalloc((void**)&w.map_pos, R * 4), -1);
+    Q3_HIP(hipStreamSynchronize(s), -1);
     w.map_R16 = 0;
     return 0;
 }
@@ -427,6 +432,11 @@ int run_stack(hipStream_t s, const Model& m, const DevStack& st, Work& w, KVCach
         t.out = w.attn;
         t.scale = 1.0f / sqrtf((float)D);
         t.threads = attn_threads;
+        if (rm.rows_total > R) {   // launch_attn's own rule (~64K threads per launch), applied to the whole step's rows
+            const int fit = 65536 / (rm.rows_total * c.n_kv);
+            if (t.threads > fit) t.threads = fit / 64 * 64;
+            if (t.threads < 256) t.threads = 256;
+        }
         t.valid_mod = rm.valid_mod;
         t.valid_n = rm.valid_n;
         if (rm.same_slot_rows && R > 1) {

@@ -104,8 +104,8 @@ void* wrapper_create_context_slots(void* model, int n_ctx, int n_batch, int n_sl
     c->n_used.assign(n_slots, 0);
     const ModelCfg& cfg = tm->m->cfg;
     bool ok = hipStreamCreate(&c->s) == hipSuccess;
-    ok = ok && kv_alloc(c->kv, cfg.talker_layers, n_slots, cfg.n_kv, n_ctx) == 0;
-    ok = ok && work_alloc(c->w, cfg, c->n_batch, cfg.talker_ffn, cfg.talker_vocab) == 0;
+    ok = ok && kv_alloc(c->kv, cfg.talker_layers, n_slots, cfg.n_kv, n_ctx, c->s) == 0;   // (zeroed on the context's own stream)
+    ok = ok && work_alloc(c->w, cfg, c->n_batch, cfg.talker_ffn, cfg.talker_vocab, c->s) == 0;
     ok = ok && hipMalloc((void**)&c->d_slot, sizeof(int) * c->n_batch) == hipSuccess;
     ok = ok && hipMalloc((void**)&c->d_pos, sizeof(int) * c->n_batch) == hipSuccess;
     ok = ok && hipHostMalloc((void**)&c->h_pinned, sizeof(float) * cfg.hidden * 2, 0) == hipSuccess;
@@ -296,7 +296,8 @@ int wrapper_state_save_file(void* ctx, const char* path) {
                 const half_t* base = (kvsel ? c->kv.v : c->kv.k) + l * c->kv.layer_stride() +
                                      ((size_t)0 * c->kv.n_kv + g) * (size_t)c->kv.n_ctx * D;
                 if (n_pos > 0) {
-                    ok = hipMemcpy(buf.data(), base, buf.size() * 2, hipMemcpyDeviceToHost) == hipSuccess;
+                    ok = hipMemcpyAsync(buf.data(), base, buf.size() * 2, hipMemcpyDeviceToHost, c->s) == hipSuccess &&
+                         hipStreamSynchronize(c->s) == hipSuccess;
                     ok = ok && fwrite(buf.data(), 2, buf.size(), f) == buf.size();
                 }
             }
@@ -336,7 +337,8 @@ int wrapper_state_load_file(void* ctx, const char* path) {
                                ((size_t)0 * c->kv.n_kv + g) * (size_t)c->kv.n_ctx * D;
                 if (n_pos > 0) {
                     ok = fread(buf.data(), 2, buf.size(), f) == buf.size();
-                    ok = ok && hipMemcpy(base, buf.data(), buf.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+                    ok = ok && hipMemcpyAsync(base, buf.data(), buf.size() * 2, hipMemcpyHostToDevice, c->s) == hipSuccess &&
+                         hipStreamSynchronize(c->s) == hipSuccess;   // (buf is refilled by the next read)
                 }
             }
     fclose(f);

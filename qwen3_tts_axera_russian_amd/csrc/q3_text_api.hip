@@ -71,7 +71,7 @@ struct TextFE {
 void* dal(TextFE* t, size_t bytes) {
     void* p = nullptr;
     if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) return nullptr;
-    hipMemset(p, 0, bytes ? bytes : 16);
+    hipMemsetAsync(p, 0, bytes ? bytes : 16, t->s);   // (the handle's own stream: loading opens no other hardware queue)
     t->allocs.push_back(p);
     return p;
 }
@@ -98,7 +98,8 @@ half_t* upload_f16(TextFE* t, const PackTensor* pt) {
             } else return nullptr;
             src = buf.data();
         }
-        if (hipMemcpy(d + o, src, n * 2, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+        if (hipMemcpyAsync(d + o, src, n * 2, hipMemcpyHostToDevice, t->s) != hipSuccess || hipStreamSynchronize(t->s) != hipSuccess)
+            return nullptr;   // (buf is refilled by the next slice)
     }
     return d;
 }
@@ -114,7 +115,7 @@ float* upload_f32(TextFE* t, const PackTensor* pt) {
         for (size_t i = 0; i < ne; i++) tmp[i] = pt->dtype == BF16 ? bf16_to_f32(u[i]) : h2f(u[i]);
         src = tmp.data();
     }
-    return hipMemcpy(d, src, ne * 4, hipMemcpyHostToDevice) == hipSuccess ? d : nullptr;
+    return hipMemcpyAsync(d, src, ne * 4, hipMemcpyHostToDevice, t->s) == hipSuccess && hipStreamSynchronize(t->s) == hipSuccess ? d : nullptr;
 }
 bool pack_linear(TextFE* t, const PackTensor* pt, DevLinear& L) {
     L.N = (int)pt->shape[0];
@@ -229,6 +230,7 @@ void* tfe_load(const char* weights, const char* embeddings_dir, int max_tokens) 
     ok = ok && (t->h1 = (float*)dal(t, Rp * mid * 4)) && (t->h2 = (float*)dal(t, Rp * t->H * 4));
     ok = ok && (t->ssq = (float*)dal(t, Rp * (mid / 16) * 4)) && (t->out = (float*)dal(t, Rp * t->H * 4));
     ok = ok && (t->d_ids = (int*)dal(t, Rp * 4)) && (t->d_src = (int*)dal(t, Rp * 4)) && (t->d_cod = (int*)dal(t, Rp * 4));
+    ok = ok && hipStreamSynchronize(t->s) == hipSuccess;   // the zeroing of dal()
     if (!ok) {
         Q3_LOG("tfe_load: upload failed");
         tfe_free(t);

@@ -1478,7 +1478,28 @@ struct Voc {
     ChunkPlace* d_place = nullptr;   // [max_batch]
     float batch_ms = 0.f;            // GPU time of the last voc_synthesize* / voc_synthesize_batch*
     int batch_chunks = 0;            // chunks it decoded
+    // pinned staging of every read-back (voc_read_back): one decode of max_batch chunks; h_ovf: the split path's overflow flag
+    char* h_stage = nullptr;
+    size_t h_stage_bytes = 0;
+    int* h_ovf = nullptr;
 };
+
+// host -> device on the handle's stream, complete on return (loading: the source may be a temporary)
+static bool voc_upload(Voc* v, void* d, const void* src, size_t bytes) {
+    return hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, v->s) == hipSuccess && hipStreamSynchronize(v->s) == hipSuccess;
+}
+
+// device -> the caller's (pageable) memory, complete on return: DMA into the pinned staging on the handle's stream, then a
+// host copy -- a pageable destination would be chunked through the runtime's own staging buffers instead
+static int voc_read_back(Voc* v, void* out, const void* dev, size_t bytes) {
+    for (size_t o = 0; o < bytes; o += v->h_stage_bytes) {
+        const size_t n = bytes - o < v->h_stage_bytes ? bytes - o : v->h_stage_bytes;
+        Q3_HIP(hipMemcpyAsync(v->h_stage, (const char*)dev + o, n, hipMemcpyDeviceToHost, v->s), -1);
+        Q3_HIP(hipStreamSynchronize(v->s), -1);
+        memcpy((char*)out + o, v->h_stage, n);
+    }
+    return 0;
+}
 
 static float* voc_up(Voc* v, const PackTensor* t) {
     size_t ne = t->numel();
@@ -1494,7 +1515,7 @@ static float* voc_up(Voc* v, const PackTensor* t) {
     float* d = nullptr;
     if (hipMalloc((void**)&d, ne * 4) != hipSuccess) return nullptr;
     v->allocs.push_back(d);
-    if (hipMemcpy(d, src, ne * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    if (!voc_upload(v, d, src, ne * 4)) return nullptr;
     return d;
 }
 
@@ -1502,7 +1523,7 @@ static float* voc_up_host(Voc* v, const std::vector<float>& h) {
     float* d = nullptr;
     if (hipMalloc((void**)&d, h.size() * 4) != hipSuccess) return nullptr;
     v->allocs.push_back(d);
-    if (hipMemcpy(d, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    if (!voc_upload(v, d, h.data(), h.size() * 4)) return nullptr;
     return d;
 }
 
@@ -1519,6 +1540,8 @@ static void voc_destroy(Voc* v) {
     if (v->d_wave16) hipFree(v->d_wave16);
     if (v->d_place) hipFree(v->d_place);
     if (v->d_ovf) hipFree(v->d_ovf);
+    if (v->h_stage) hipHostFree(v->h_stage);
+    if (v->h_ovf) hipHostFree(v->h_ovf);
     if (v->e0) hipEventDestroy(v->e0);
     if (v->e1) hipEventDestroy(v->e1);
     if (v->s) hipStreamDestroy(v->s);
@@ -1567,9 +1590,10 @@ void* voc_load(const char* weights, int chunk_tokens, int max_batch) {
     bool ok = true;
     {
         // lowest queue priority: the vocoder is throughput work that runs beside the latency-bound frame
-        // loop (highest priority, q3_engine.hip); Q3_STREAM_PRIO=0 creates both at the default priority
+        // loop (highest priority, q3_engine.hip); Q3_STREAM_PRIO=0 creates both at the default priority, =2 this one only
         int lo = 0, hi = 0;
-        const bool prio = !(getenv("Q3_STREAM_PRIO") && atoi(getenv("Q3_STREAM_PRIO")) == 0);
+        const int mode = getenv("Q3_STREAM_PRIO") ? atoi(getenv("Q3_STREAM_PRIO")) : 1;
+        const bool prio = mode != 0 && mode != 2;
         if (prio && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi)
             ok = hipStreamCreateWithPriority(&v->s, hipStreamNonBlocking, lo) == hipSuccess;
         else
@@ -1713,8 +1737,7 @@ void* voc_load(const char* weights, int chunk_tokens, int max_batch) {
                     }
                     v->allocs.push_back(dh);
                     v->allocs.push_back(dl);
-                    ok = hipMemcpy(dh, hi.data(), hi.size() * 2, hipMemcpyHostToDevice) == hipSuccess &&
-                         hipMemcpy(dl, lo.data(), lo.size() * 2, hipMemcpyHostToDevice) == hipSuccess;
+                    ok = voc_upload(v, dh, hi.data(), hi.size() * 2) && voc_upload(v, dl, lo.data(), lo.size() * 2);
                     op.w_hi = (_Float16*)dh;
                     op.w_lo = (_Float16*)dl;
                     op.Mp128 = Mp;
@@ -1864,11 +1887,17 @@ void* voc_load(const char* weights, int chunk_tokens, int max_batch) {
         v->flops_per_chunk = flops;
         v->buf_elems = max_elems * v->max_batch;
         for (int i = 0; i < 3 && ok; i++)     // (zeroed once: pad columns start finite)
-            ok = hipMalloc((void**)&v->buf[i], v->buf_elems * 4) == hipSuccess && hipMemset(v->buf[i], 0, v->buf_elems * 4) == hipSuccess;
+            ok = hipMalloc((void**)&v->buf[i], v->buf_elems * 4) == hipSuccess && hipMemsetAsync(v->buf[i], 0, v->buf_elems * 4, v->s) == hipSuccess;
         for (int i = 0; i < 4 && ok; i++) ok = hipMalloc((void**)&v->plane[i], v->buf_elems * 2) == hipSuccess;
         ok = ok && hipMalloc((void**)&v->d_codes, sizeof(int64_t) * 16 * v->chunk * v->max_batch) == hipSuccess;
-        ok = ok && hipMalloc((void**)&v->d_ovf, 16) == hipSuccess && hipMemset(v->d_ovf, 0, 16) == hipSuccess;
+        ok = ok && hipMalloc((void**)&v->d_ovf, 16) == hipSuccess && hipMemsetAsync(v->d_ovf, 0, 16, v->s) == hipSuccess;
         ok = ok && hipMalloc((void**)&v->d_place, sizeof(ChunkPlace) * v->max_batch) == hipSuccess;
+        // every read-back goes through this pinned block on the handle's stream: one decode of max_batch chunks fits whole
+        v->h_stage_bytes = sizeof(float) * (size_t)v->chunk_samples * v->max_batch;
+        if (v->h_stage_bytes < 4096) v->h_stage_bytes = 4096;
+        ok = ok && hipHostMalloc((void**)&v->h_stage, v->h_stage_bytes, 0) == hipSuccess;
+        ok = ok && hipHostMalloc((void**)&v->h_ovf, 16, 0) == hipSuccess;
+        ok = ok && hipStreamSynchronize(v->s) == hipSuccess;   // the zeroing above
     }
     if (!ok) {
         Q3_LOG("voc_load failed");
@@ -2177,13 +2206,13 @@ int voc_decode(void* vv, const int64_t* codes, int B, float* out) {
     float* res = nullptr;
     if (voc_run(v, B, &res)) return -1;
     Q3_HIP(hipEventRecord(v->e1, v->s), -1);
-    int ovf = 0;
-    if (g_voc_split) Q3_HIP(hipMemcpyAsync(&ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
-    // rows of chunk_samples floats at the device pitch -> dense out[B][chunk_samples]
+    *v->h_ovf = 0;
+    if (g_voc_split) Q3_HIP(hipMemcpyAsync(v->h_ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
+    // rows of chunk_samples floats at the device pitch -> dense [B][chunk_samples] in the pinned staging -> out
     const size_t row = sizeof(float) * (size_t)v->chunk_samples, dpitch = sizeof(float) * (size_t)pitch4(v->chunk_samples);
-    Q3_HIP(hipMemcpy2DAsync(out, row, res, dpitch, row, (size_t)B, hipMemcpyDeviceToHost, v->s), -1);
+    Q3_HIP(hipMemcpy2DAsync(v->h_stage, row, res, dpitch, row, (size_t)B, hipMemcpyDeviceToHost, v->s), -1);
     Q3_HIP(hipStreamSynchronize(v->s), -1);
-    if (ovf) {
+    if (*v->h_ovf) {
         // an activation beyond +-65504 (or a NaN): two fp16 terms cannot carry it -- this call is redone on the
         // exact-fp32 MFMA path, so the split arithmetic never degrades a result silently
         if (!v->warned_ovf) Q3_LOG("vocoder: activation outside the fp16 range, decoding this call with the exact-fp32 path");
@@ -2192,9 +2221,10 @@ int voc_decode(void* vv, const int64_t* codes, int B, float* out) {
         Q3_HIP(hipEventRecord(v->e0, v->s), -1);
         if (voc_run(v, B, &res, -1, nullptr, nullptr, nullptr, true)) return -1;
         Q3_HIP(hipEventRecord(v->e1, v->s), -1);
-        Q3_HIP(hipMemcpy2DAsync(out, row, res, dpitch, row, (size_t)B, hipMemcpyDeviceToHost, v->s), -1);
+        Q3_HIP(hipMemcpy2DAsync(v->h_stage, row, res, dpitch, row, (size_t)B, hipMemcpyDeviceToHost, v->s), -1);
         Q3_HIP(hipStreamSynchronize(v->s), -1);
     }
+    memcpy(out, v->h_stage, row * (size_t)B);
     hipEventElapsedTime(&v->last_ms, v->e0, v->e1);
     return 0;
 }
@@ -2331,11 +2361,11 @@ int decode_walk(Voc* v, const std::vector<WalkChunk>& walk, ChunkCodes chunk_cod
             calls++;
         }
         Q3_HIP(hipEventRecord(v->e1, v->s), -1);
-        int ovf = 0;
-        if (g_voc_split && !redo_exact) Q3_HIP(hipMemcpyAsync(&ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
+        *v->h_ovf = 0;
+        if (g_voc_split && !redo_exact) Q3_HIP(hipMemcpyAsync(v->h_ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
         Q3_HIP(hipStreamSynchronize(v->s), -1);
         *n_calls = calls;
-        if (!ovf) break;
+        if (!*v->h_ovf) break;
         // an activation beyond the fp16 range: the whole walk is redone on the exact-fp32 path
         if (!v->warned_ovf) Q3_LOG("vocoder: activation outside the fp16 range, decoding this request with the exact-fp32 path");
         v->warned_ovf = true;
@@ -2391,12 +2421,12 @@ int synth_batch(Voc* v, const int64_t* codes, const int32_t* n_tokens, int U, in
     hipEventElapsedTime(&v->batch_ms, v->e0, v->e1);
     v->batch_chunks = (int)walk.size();
     if (!want16) {
-        Q3_HIP(hipMemcpyAsync(out, v->d_wave, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost, v->s), -1);
+        if (voc_read_back(v, out, v->d_wave, sizeof(float) * (size_t)total)) return -1;
     } else {
         if (grow(&v->d_wave16, &v->wave16_cap, (size_t)total)) return -1;
         hipLaunchKernelGGL(voc_to_int16_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->s, v->d_wave, v->d_wave16, total);
         Q3_HIP(hipGetLastError(), -1);
-        Q3_HIP(hipMemcpyAsync(out, v->d_wave16, sizeof(int16_t) * (size_t)total, hipMemcpyDeviceToHost, v->s), -1);
+        if (voc_read_back(v, out, v->d_wave16, sizeof(int16_t) * (size_t)total)) return -1;
     }
     Q3_HIP(hipStreamSynchronize(v->s), -1);
     return 0;
@@ -2561,8 +2591,8 @@ int stream_push(VocStream* s, int n, const int32_t* streams, const int64_t* code
         }
         Q3_HIP(hipGetLastError(), -1);
         if (total > 0)
-            Q3_HIP(hipMemcpyAsync(out, want16 ? (void*)s->d_out16 : (void*)s->d_out, (want16 ? sizeof(int16_t) : sizeof(float)) * (size_t)total,
-                                  hipMemcpyDeviceToHost, v->s), -1);
+            if (voc_read_back(v, out, want16 ? (void*)s->d_out16 : (void*)s->d_out, (want16 ? sizeof(int16_t) : sizeof(float)) * (size_t)total))
+                return -1;
         Q3_HIP(hipStreamSynchronize(v->s), -1);
     }
     for (int i = 0; i < n; i++) {
@@ -3060,8 +3090,8 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
     if (!p.keys.empty()) {
         Q3_HIP(hipEventRecord(v->e1, v->s), -1);
         if (total > 0)
-            Q3_HIP(hipMemcpyAsync(out, want16 ? (void*)s->d_out16 : (void*)s->d_out, (want16 ? sizeof(int16_t) : sizeof(float)) * (size_t)total,
-                                  hipMemcpyDeviceToHost, v->s), -1);
+            if (voc_read_back(v, out, want16 ? (void*)s->d_out16 : (void*)s->d_out, (want16 ? sizeof(int16_t) : sizeof(float)) * (size_t)total))
+                return -1;
         Q3_HIP(hipStreamSynchronize(v->s), -1);
         hipEventElapsedTime(&s->last_ms, v->e0, v->e1);
     }
@@ -3149,7 +3179,7 @@ void* voc_incr_create(void* vv, int max_streams) {
     s->out_cap = (size_t)max_streams * v->chunk * v->upsample;
     auto alloc = [&](void** p, size_t bytes, bool zero) {
         if (!ok) return;
-        ok = hipMalloc(p, bytes) == hipSuccess && (!zero || hipMemset(*p, 0, bytes) == hipSuccess);
+        ok = hipMalloc(p, bytes) == hipSuccess && (!zero || hipMemsetAsync(*p, 0, bytes, v->s) == hipSuccess);
         if (ok) s->device_bytes += bytes;
     };
     alloc((void**)&s->d_hist, sizeof(float) * std::max<size_t>(1, s->state_floats * max_streams), true);
@@ -3160,6 +3190,7 @@ void* voc_incr_create(void* vv, int max_streams) {
     alloc((void**)&s->d_off, sizeof(long long) * mb, false);
     alloc((void**)&s->d_out, sizeof(float) * s->out_cap, false);
     alloc((void**)&s->d_out16, sizeof(int16_t) * s->out_cap, false);
+    ok = ok && hipStreamSynchronize(v->s) == hipSuccess;   // the zeroing above
     if (!ok) {
         Q3_LOG("voc_incr_create: device allocation failed");
         incr_destroy(s);
