@@ -4,7 +4,7 @@
 // encoder") whose semantics are pinned to transformers' MimiModel.encode.  Activations are [B][C][ld] f32 with a row
 // pitch ld = L rounded up to 32 floats, one row per clip and channel, L = the longest clip's columns at that stage.
 //
-// Shared with the vocoder (q3_voc_ops.h): the exact-fp32 MFMA conv (with ELU applied while the input is staged),
+// Shared with the vocoder (q3_voc_ops.h, defined in q3_voc_kernels.hip): the exact-fp32 MFMA conv (with ELU applied while the input is staged),
 // the channel norm and the sliding-window attention.  Own kernels:
 //   enc_conv_in_kernel   the first conv, ONE input channel (a dot product of k taps per output: no MFMA tile)
 //   enc_unfold_kernel    strided conv input -> [Cin * k][ceil(L / s)] columns (im2col), Mimi's padding per clip: zeros
