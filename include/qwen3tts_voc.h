@@ -132,8 +132,8 @@ float voc_stream_last_ms(void* s);
  *  - Invariance: joined per stream, the samples are the same bits for any split of the frames across pushes, any n_new pattern,
  *    any set of other streams in the same calls, and any stream index: every launcher rule that looks at a length reads the
  *    full-chunk length, and a column's sums depend on neither its tile nor its batch.
- *  - Arithmetic: the exact-fp32 kernels only, whatever voc_set_exact_fp32 selects process-wide (the split planes and their
- *    per-call overflow redo are not carried between pushes); voc_set_fused_units applies.
+ *  - Arithmetic: the exact-fp32 kernels by default, whatever voc_set_exact_fp32 selects process-wide; voc_set_fused_units applies.
+ *    voc_incr_set_arithmetic (below) moves one object to the split-fp16 convolutions.
  *  - Limits: 0 <= n_new <= chunk_tokens per entry and push; frames per stream unbounded (2^31, the RoPE position).  Device memory
  *    is constant: per stream the carried columns, voc_incr_state_bytes() = 5 193 984 B (4.95 MiB) at the default table (of which
  *    4.44 MiB are the eight attention windows); per handle work buffers for one push of chunk_tokens frames x max_batch entries
@@ -159,7 +159,30 @@ float voc_incr_last_ms(void* s);
 int voc_incr_last_launches(void* s);
 int64_t voc_incr_samples(void* voc, int64_t n_frames);   /* S(n); <0: bad arguments */
 int64_t voc_incr_state_bytes(void* s);    /* device bytes one stream's carried state takes */
-int64_t voc_incr_device_bytes(void* s);   /* device bytes the object holds: fixed by voc_incr_create */
+int64_t voc_incr_device_bytes(void* s);   /* device bytes the object holds: fixed by voc_incr_create (+ the first switch to split) */
+
+/* Arithmetic of ONE incremental object, independent of voc_set_exact_fp32: 0 (default) the exact-fp32 kernels, 1 the split-fp16
+ * convolutions (voc_set_exact_fp32's note) wherever a conv is built for them; embedding, depthwise conv, norm, GLU and attention
+ * are f32 in both, a conv with a weight beyond the fp16 range stays exact, and a residual unit runs as its two convs.
+ * voc_incr_set_arithmetic is accepted only while every stream of the object is idle (fresh, reset, or finished): otherwise it
+ * returns <0 and changes nothing.  -> the mode in effect.  The first switch to 1 allocates the second history buffer, the fp16
+ * planes and the per-entry flags (voc_incr_device_bytes grows once; an object that never switches holds what it always held).
+ * The carried history stays f32 -- voc_incr_state_bytes keeps its value -- and the planes are rebuilt from it every push.
+ *  - Invariance: as long as no entry is redone, a stream's joined samples are the same bits for any split of the frames, any
+ *    n_new pattern, any neighbours and any stream index, as in exact mode (a column's sums depend on neither tile nor batch).
+ *  - Overflow: a push is a transaction per entry.  The history is double-buffered per stream; every kernel that writes planes
+ *    flags the entry whose value leaves +-65504 (or is a NaN).  An unflagged entry commits.  A flagged entry's push is dropped
+ *    and decoded again, from the same uncommitted history, on the exact-fp32 kernels (logged once per object), and then commits:
+ *    the split arithmetic never degrades a result silently.  An entry's bits never depend on whether a neighbour overflowed.
+ *    After a redo the stream's joined result depends on which push was redone (split and exact columns differ in rounding):
+ *    voc_stream_push's rule for the split path.  The flags also cover columns a push computes and drops (the outputs of history
+ *    columns in front of a one-tap conv's new ones): a redo can come from those alone; it costs time, never accuracy.
+ * voc_incr_last_split_launches: conv launches of the last push that ran on the fp16 MFMA path (0 in exact mode);
+ * voc_incr_last_redone: entries of the last push that were redone on the exact path. */
+int voc_incr_set_arithmetic(void* s, int split);
+int voc_incr_arithmetic(void* s);
+int voc_incr_last_split_launches(void* s);
+int voc_incr_last_redone(void* s);
 
 /* Arithmetic of the convolutions.  Default (0): split precision -- every f32 operand (weights once at load,
  * activations in the producing kernel's epilogue) is carried as two fp16 terms (22 mantissa bits) and each

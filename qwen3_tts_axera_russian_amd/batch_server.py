@@ -24,6 +24,8 @@ the same connection (in the order they are ready; `utt` indexes the request's ut
 A request may carry "vocoder": "incremental" (default "walk"; any other value is answered with -2): its PCM then comes from the
 carry-state incremental decode (voc_incr_push: the samples of every check's new frames at once, one seamless decode per
 utterance) instead of the chunk walk -- streamed, or unstreamed through Vocoder.synthesize_incremental, the same bits either way.
+Such a request may also carry "vocoder_arithmetic": "exact" (the default) or "split" (the split-fp16 convolutions,
+voc_incr_set_arithmetic); any other value, or the key on a request that is not "vocoder": "incremental", is answered with -2.
 Records, framing and the single-writer worker are the same.
 Every check_every frames the new frames of every live slot go to the vocoder's streaming chunk walk (voc_stream_push, on one
 worker thread with one vocoder workgroup per compute unit, as in --pipeline); a full 64-frame chunk is decoded as soon as its
@@ -112,7 +114,8 @@ class BatchSynthesisServer:
         self._pool = None
         self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
         self._vstream = None           # streaming chunk walk: one stream per slot of the frame loop
-        self._istream = None           # carry-state incremental decode ("vocoder": "incremental"): made by the worker on first use
+        self._istreams = {}            # carry-state incremental decode ("vocoder": "incremental"): one object per arithmetic,
+                                       # made by the worker on first use
         if self.pipeline:
             from concurrent.futures import ThreadPoolExecutor
             self._pool = ThreadPoolExecutor(max_workers=1)       # ONE worker: the vocoder handle has one caller, replies keep their order
@@ -165,16 +168,17 @@ class BatchSynthesisServer:
             per_utt = [codes[:int(per[b]), b, :] for b in range(B)]
         return [np.ascontiguousarray(c, dtype=np.int32) for c in per_utt]
 
-    def vocode(self, cs, vocoder="walk"):
+    def vocode(self, cs, vocoder="walk", arithmetic="exact"):
         """The vocoder of a request: every utterance's chunk walk in ONE batched call -> list of (codes, pcm int16).
-        vocoder="incremental": the carry-state decode per utterance -- the bits a streamed reply in that mode carries."""
+        vocoder="incremental": the carry-state decode per utterance, in the request's arithmetic -- the bits a streamed reply in
+        that mode carries."""
         if vocoder == "incremental":
-            return [(c, self.voc.synthesize_incremental(c, int16=True)) for c in cs]
+            return [(c, self.voc.synthesize_incremental(c, int16=True, arithmetic=arithmetic)) for c in cs]
         return list(zip(cs, self.voc.synthesize_batch(cs)))
 
-    def synthesize(self, token_ids, max_tokens=None, vocoder="walk"):
+    def synthesize(self, token_ids, max_tokens=None, vocoder="walk", arithmetic="exact"):
         """-> list of (codes int32 [n_frames][16], pcm int16) per utterance."""
-        return self.vocode(self.generate(token_ids, max_tokens), vocoder)
+        return self.vocode(self.generate(token_ids, max_tokens), vocoder, arithmetic)
 
     def _stream_pcm(self, state, resets, entries):
         """Worker side: the PCM a push's entries hand out, from the request's vocoder mode -- the streaming chunk walk, or the
@@ -183,14 +187,16 @@ class BatchSynthesisServer:
             for b in resets:
                 self._vstream.reset(b)
             return self._vstream.push([e[0] for e in entries], [e[2] for e in entries], [e[3] for e in entries]) if entries else []
-        if self._istream is None:
-            self._istream = self.voc.incremental(self.max_batch)
+        arithmetic = state.get("vocoder_arithmetic", "exact")
+        if arithmetic not in self._istreams:
+            self._istreams[arithmetic] = self.voc.incremental(self.max_batch, arithmetic)
+        istream = self._istreams[arithmetic]
         for b in resets:
-            self._istream.reset(b)
+            istream.reset(b)
         ch, parts, j = self.voc.chunk_tokens, [[] for _ in entries], 0
         while entries and (j == 0 or any(len(e[2]) > j * ch for e in entries)):
             sel = [k for k, e in enumerate(entries) if j == 0 or len(e[2]) > j * ch]
-            pcm = self._istream.push([entries[k][0] for k in sel], [entries[k][2][j * ch:(j + 1) * ch] for k in sel],
+            pcm = istream.push([entries[k][0] for k in sel], [entries[k][2][j * ch:(j + 1) * ch] for k in sel],
                                      [entries[k][3] and len(entries[k][2]) <= (j + 1) * ch for k in sel])
             for k, a in zip(sel, pcm):
                 parts[k].append(a.copy())
@@ -233,11 +239,11 @@ class BatchSynthesisServer:
         finally:
             conn.close()
 
-    def synthesize_stream(self, conn, token_ids, max_tokens=None, t0=None, vocoder="walk"):
+    def synthesize_stream(self, conn, token_ids, max_tokens=None, t0=None, vocoder="walk", arithmetic="exact"):
         """A streamed request: the frame loop runs here (generate_queue), the vocoder's pushes and every write to `conn` on the
         worker thread, at most one push in flight.  -> the worker's future of the request's last record (it closes conn)."""
         t0 = time.time() if t0 is None else t0
-        state = {"failed": False, "n": len(token_ids), "frames": 0, "vocoder": vocoder}
+        state = {"failed": False, "n": len(token_ids), "frames": 0, "vocoder": vocoder, "vocoder_arithmetic": arithmetic}
         if self._pool is not None:
             pool = self._pool
         else:
@@ -308,15 +314,15 @@ class BatchSynthesisServer:
         """--concurrent, accept side: a request -> its utterances in queue order as (request index, prefix, n_text,
         SlotParams); raises on anything malformed, before any of it is queued."""
         ids = self._token_ids(msg)
-        request_vocoder(msg)
+        request_vocoder_arithmetic(msg)      # (checks "vocoder" too)
         base = request_slot_params(msg, self.defaults, self.max_tokens)
         prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames)
         return [(i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i)) for i in order]
 
-    def _finish(self, conn, cs, t0, vocoder="walk"):
+    def _finish(self, conn, cs, t0, vocoder="walk", arithmetic="exact"):
         """Worker side of the pipelined mode: vocode, reply on the request's own connection, close it."""
         try:
-            res = self.vocode(cs, vocoder)
+            res = self.vocode(cs, vocoder, arithmetic)
             conn.sendall(pack_batch_reply(res))
             print(f"  {len(res)} utterances, {sum(len(c) for c, _ in res)} frames in {time.time() - t0:.3f}s")
         except Exception as e:
@@ -353,20 +359,20 @@ class BatchSynthesisServer:
                 if msg is None:
                     continue
                 t0 = time.time()
-                vocoder = request_vocoder(msg)
+                vocoder, arithmetic = request_vocoder(msg), request_vocoder_arithmetic(msg)
                 if msg.get("stream"):
                     # streamed reply: the worker writes every record and closes the connection
                     ids = self._token_ids(msg)
                     handed_over = True
-                    self.synthesize_stream(conn, ids, msg.get("max_tokens"), t0, vocoder)
+                    self.synthesize_stream(conn, ids, msg.get("max_tokens"), t0, vocoder, arithmetic)
                     continue
                 if self._pool is not None:
                     # pipelined: this request's vocoder runs on the worker while the loop accepts and generates the next one
                     cs = self.generate(self._token_ids(msg), msg.get("max_tokens"))
-                    self._pool.submit(self._finish, conn, cs, t0, vocoder)
+                    self._pool.submit(self._finish, conn, cs, t0, vocoder, arithmetic)
                     handed_over = True
                     continue
-                res = self.synthesize(self._token_ids(msg), msg.get("max_tokens"), vocoder)
+                res = self.synthesize(self._token_ids(msg), msg.get("max_tokens"), vocoder, arithmetic)
                 conn.sendall(pack_batch_reply(res))
                 frames = sum(len(c) for c, _ in res)
                 print(f"  {len(res)} utterances, {frames} frames in {time.time() - t0:.3f}s")
@@ -435,7 +441,8 @@ class BatchSynthesisServer:
         if self.pipeline:
             self._lib.voc_set_max_workgroups(0)
         self.voc.close()               # frees the streaming chunk walk first
-        self._vstream = self._istream = None
+        self._vstream = None
+        self._istreams = {}
         self.eng.destroy()
 
 
@@ -455,7 +462,7 @@ class ConcurrentScheduler:
     """The engine and vocoder sides of `--concurrent` (module docstring).  `eng` has the FrameEngine surface open / admit /
     release / run / done / codes; the callables are the server's: prepare(msg) -> [(request index, prefix, n_text,
     SlotParams)] in queue order (raises on a malformed request), reply(conn, codes per utterance, t0) answers and closes an
-    unstreamed request, push(conn, state, resets, entries) and close_stream(conn, state, t0) stream records and end a streamed
+    unstreamed request (a request that does not use the chunk walk: reply(conn, codes, t0, vocoder, arithmetic)), push(conn, state, resets, entries) and close_stream(conn, state, t0) stream records and end a streamed
     one, send_error(conn) writes -2.  The engine thread is the only caller of `eng`, the one worker thread the only caller of
     reply / push / close_stream.
 
@@ -486,6 +493,7 @@ class ConcurrentScheduler:
                         struct.pack("ll", sec, int(round((self.send_timeout - sec) * 1e6))))
         try:
             items = self._prepare(msg)
+            vocoder, arithmetic = request_vocoder(msg), request_vocoder_arithmetic(msg)
         except Exception as e:
             print(f"Error: {e}")
             return self._refuse(conn)
@@ -495,7 +503,7 @@ class ConcurrentScheduler:
                       "Error: the engine has stopped")
                 return self._refuse(conn)
             req = _Request(conn, items, msg.get("stream"), time.time() if t0 is None else t0)
-            req.state["vocoder"] = request_vocoder(msg)      # (prepare has checked it)
+            req.state["vocoder"], req.state["vocoder_arithmetic"] = vocoder, arithmetic
             self._queue.extend((req, it) for it in items)
             self._cv.notify()
         return True
@@ -634,8 +642,8 @@ class ConcurrentScheduler:
                         self._pool.submit(self._close_stream, req.conn, req.state, req.t0)
                     elif req.state["vocoder"] == "walk":
                         self._pool.submit(self._reply, req.conn, req.codes, req.t0)
-                    else:
-                        self._pool.submit(self._reply, req.conn, req.codes, req.t0, req.state["vocoder"])
+                    else:      # (reply's documented form is (conn, codes, t0); another vocoder adds its mode and arithmetic)
+                        self._pool.submit(self._reply, req.conn, req.codes, req.t0, req.state["vocoder"], req.state["vocoder_arithmetic"])
         # shutting down: whatever is still in flight or queued gets -2
         with self._cv:
             rest = {id(r): r for r, _ in self._queue}
@@ -657,6 +665,24 @@ def request_vocoder(msg):
     if not isinstance(v, str) or v not in VOCODER_MODES:
         raise ValueError(f"vocoder must be one of {VOCODER_MODES} (got {v!r})")
     return v
+
+
+VOCODER_ARITHMETICS = ("exact", "split")
+
+
+def request_vocoder_arithmetic(msg):
+    """A request's "vocoder_arithmetic" key -> "exact" (the default) or "split" (the incremental decode's split-fp16
+    convolutions, voc_incr_set_arithmetic); raises ValueError on any other value, and on the key in a request that is not
+    "vocoder": "incremental" (the request is then answered with -2)."""
+    vocoder = request_vocoder(msg)
+    if "vocoder_arithmetic" not in msg:
+        return "exact"
+    a = msg["vocoder_arithmetic"]
+    if not isinstance(a, str) or a not in VOCODER_ARITHMETICS:
+        raise ValueError(f"vocoder_arithmetic must be one of {VOCODER_ARITHMETICS} (got {a!r})")
+    if vocoder != "incremental":
+        raise ValueError('vocoder_arithmetic needs "vocoder": "incremental"')
+    return a
 
 
 _PARAM_KEYS = ("temperature", "top_k", "top_p", "cp_temperature", "cp_top_k", "seed")   # request keys = SlotParams fields
@@ -686,9 +712,10 @@ def request_slot_params(msg, defaults, max_tokens_cap):
 
 
 def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False, temperature=None,
-                       top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None) -> bytes:
-    """The request of the batched protocol; the sampling keys (honoured by --concurrent) and the vocoder mode ("walk" /
-    "incremental") are sent only when given."""
+                       top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None,
+                       vocoder_arithmetic=None) -> bytes:
+    """The request of the batched protocol; the sampling keys (honoured by --concurrent), the vocoder mode ("walk" /
+    "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given."""
     import json
     msg = {"language": language}
     if stream:
@@ -700,7 +727,7 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
     if max_tokens:
         msg["max_tokens"] = int(max_tokens)
     for key, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("cp_temperature", cp_temperature),
-                   ("cp_top_k", cp_top_k), ("seed", seed), ("vocoder", vocoder)):
+                   ("cp_top_k", cp_top_k), ("seed", seed), ("vocoder", vocoder), ("vocoder_arithmetic", vocoder_arithmetic)):
         if v is not None:
             msg[key] = v
     raw = json.dumps(msg).encode()
@@ -770,14 +797,17 @@ def read_stream_record(conn):
     return ("end", utt, np.frombuffer(exact(n * 16 * 4), dtype="<i4").reshape(n, 16))
 
 
-def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, vocoder=None, **sampling):
+def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, vocoder=None,
+                            vocoder_arithmetic=None, **sampling):
     """Client side of the streamed request: yields its records as they arrive -- ("audio", utt, pcm) and ("end", utt, codes)
     -- until the request is done; raises on the error sentinel.  vocoder="incremental": the carry-state decode (audio from the
-    first check on) instead of the chunk walk.  sampling: the optional keys of pack_batch_request."""
+    first check on) instead of the chunk walk, vocoder_arithmetic="split": on its split-fp16 convolutions.  sampling: the optional
+    keys of pack_batch_request."""
     s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     s.connect(socket_path)
     try:
-        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True, vocoder=vocoder, **sampling))
+        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True, vocoder=vocoder,
+                                     vocoder_arithmetic=vocoder_arithmetic, **sampling))
         while True:
             rec = read_stream_record(s)
             if rec[0] == "done":
@@ -788,7 +818,8 @@ def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="r
 
 
 def synthesize_batch(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, **sampling):
-    """Client side of the batched request.  sampling: the optional keys of pack_batch_request."""
+    """Client side of the batched request.  sampling: the optional keys of pack_batch_request (vocoder and vocoder_arithmetic
+    among them)."""
     s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     s.connect(socket_path)
     try:

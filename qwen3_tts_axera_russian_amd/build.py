@@ -40,7 +40,7 @@ def _newer(dst: str, srcs) -> bool:
 # HBM traffic (round 1 shipped a 96-channel conv variant with 12 spilled registers = +0.19 GB per launch)
 NO_SPILL = ("resunit_kernel", "linear_kernelILi1ELi1E", "linear_kernelILi1ELi2E", "linear_kernelILi2ELi1E",
             "linear_kernelILi2ELi2E", "attn_kernel", "attn_short_kernel", "cp_argmax_kernel", "talker_sample_kernel",
-            "voc_attn_incr_kernel", "voc_incr_prepend_kernel", "voc_incr_emit_kernel")
+            "voc_attn_incr_kernel", "voc_incr_prepend_kernel", "voc_incr_emit_kernel", "voc_incr_prepend_split_kernel")
 
 
 def kernel_resources(lib_path: str):

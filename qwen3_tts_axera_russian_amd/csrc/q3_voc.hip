@@ -528,6 +528,40 @@ bool voc_fused_unit(const Voc* v, size_t i, size_t n_ops) {
            resunit_channels(op.cin) && i + 1 < n_ops && v->ops[i + 1].w1p;
 }
 
+bool voc_split_capable(const VocOp& op) { return (op.op == VOP_CONV || op.op == VOP_CONVT) && op.w_hi != nullptr; }
+
+// (a GELU consumer takes its planes from the separate pass: erf in the conv's epilogue costs every conv registers)
+bool voc_split_emits_planes(const VocOp& op, const VocOp* next) {
+    return next && voc_split_capable(*next) && op.op == VOP_CONV && op.cout % 16 == 0 && !(next->flags & VF_GELU);
+}
+
+SplitArgs voc_split_args(const VocOp& op, long cols) {
+    const ConvGeom g = voc_conv_geom(op, cols);
+    SplitArgs sa;
+    sa.w_hi = op.w_hi;
+    sa.w_lo = op.w_lo;
+    sa.bias = op.bias;
+    sa.Cin = op.cin;
+    sa.Cout = op.cout;
+    sa.Mp = op.Mp128;
+    sa.Lin = (int)cols;
+    sa.clamp = (op.flags & VF_CLAMP) ? 1 : 0;
+    sa.dil = g.dil, sa.stride = g.stride, sa.M = g.M, sa.lt = g.lt, sa.Lout = g.Lout, sa.Lc = g.Lc;
+    sa.ldy = (int)pitch4(sa.Lout);
+    return sa;
+}
+
+void voc_split_out_planes(SplitArgs& sa, const VocOp& next, _Float16* oh, _Float16* ol) {
+    sa.oh = oh;
+    sa.ol = ol;
+    if (next.flags & VF_SNAKE) {
+        sa.oalpha = next.alpha;
+        sa.oinv_beta = next.inv_beta;
+    }
+}
+
+int voc_split_taps(const VocOp& op) { return voc_conv_geom(op, 1).K; }
+
 // Split path of one conv op.  State carried between ops: which f32 buffer holds the newest f32 activation
 // (and whether it is the current one), and which plane set (if any) already holds the current activation in
 // the next conv's input form.
@@ -538,7 +572,6 @@ struct SplitState {
     float* res = nullptr;  // residual-unit input (f32)
 };
 
-static bool split_capable(const VocOp& op) { return (op.op == VOP_CONV || op.op == VOP_CONVT) && op.w_hi != nullptr; }
 
 static int voc_conv_split(Voc* v, const VocOp& op, const VocOp* next, bool last, int B, long L, SplitState& st) {
     int in_set = st.planes;
@@ -553,25 +586,13 @@ static int voc_conv_split(Voc* v, const VocOp& op, const VocOp* next, bool last,
         if (!st.f32_cur) return -1;   // the producer keeps an f32 copy whenever its consumer saves a residual
         st.res = v->buf[st.f32_idx];
     }
-    // (a GELU consumer takes its planes from the separate pass: erf in this epilogue costs every conv registers)
-    const bool want_planes = next && split_capable(*next) && op.op == VOP_CONV && op.cout % 16 == 0 && !(next->flags & VF_GELU);
+    const bool want_planes = voc_split_emits_planes(op, next);
     const bool want_f32 = !want_planes || last || (next->flags & VF_RES_SAVE);
-    const ConvGeom g = voc_conv_geom(op, L);
-    SplitArgs sa;
+    SplitArgs sa = voc_split_args(op, L);
     sa.xh = v->plane[2 * in_set];
     sa.xl = v->plane[2 * in_set + 1];
-    sa.w_hi = op.w_hi;
-    sa.w_lo = op.w_lo;
-    sa.bias = op.bias;
     sa.ovf = v->d_ovf;
     sa.res = (op.flags & VF_RES_ADD) ? st.res : nullptr;
-    sa.Cin = op.cin;
-    sa.Cout = op.cout;
-    sa.Mp = op.Mp128;
-    sa.Lin = (int)L;
-    sa.clamp = (op.flags & VF_CLAMP) ? 1 : 0;
-    sa.dil = g.dil, sa.stride = g.stride, sa.M = g.M, sa.lt = g.lt, sa.Lout = g.Lout, sa.Lc = g.Lc;
-    sa.ldy = (int)pitch4(sa.Lout);
     int out_f32 = st.f32_idx;
     if (want_f32) {
         // never the buffer the residual (or a still-current f32 input) lives in
@@ -579,15 +600,8 @@ static int voc_conv_split(Voc* v, const VocOp& op, const VocOp* next, bool last,
         if (sa.res == v->buf[out_f32]) return -1;
         sa.y = v->buf[out_f32];
     }
-    if (want_planes) {
-        sa.oh = v->plane[2 * (in_set ^ 1)];
-        sa.ol = v->plane[2 * (in_set ^ 1) + 1];
-        if (next->flags & VF_SNAKE) {
-            sa.oalpha = next->alpha;
-            sa.oinv_beta = next->inv_beta;
-        }
-    }
-    if (launch_conv_split(v->s, sa, g.K, B)) return -1;
+    if (want_planes) voc_split_out_planes(sa, *next, v->plane[2 * (in_set ^ 1)], v->plane[2 * (in_set ^ 1) + 1]);
+    if (launch_conv_split(v->s, sa, voc_split_taps(op), B)) return -1;
     if (want_f32) {
         st.f32_idx = out_f32;
         st.f32_cur = true;

@@ -670,7 +670,7 @@ typedef _Float16 hv8 __attribute__((ext_vector_type(8)));
 __global__ void __launch_bounds__(256) snake_split_kernel(const float* __restrict__ x, const float* __restrict__ alpha,
                                                           const float* __restrict__ inv_beta, _Float16* __restrict__ xh,
                                                           _Float16* __restrict__ xl, int C, int L, int ld, int gelu,
-                                                          int* __restrict__ ovf) {
+                                                          int* __restrict__ ovf, int ovf_stride) {
     const int l = blockIdx.x * 256 + threadIdx.x, cg = blockIdx.y, b = blockIdx.z;   // cg: 8-channel group
     if (l >= L) return;
     const float* xp = x + ((size_t)b * C + cg * 8) * ld + l;     // f32 rows at pitch ld; the planes are dense in L
@@ -700,13 +700,13 @@ __global__ void __launch_bounds__(256) snake_split_kernel(const float* __restric
     const size_t o = (((size_t)b * (C >> 3) + cg) * L + l) * 8;
     *(hv8*)(xh + o) = h;
     *(hv8*)(xl + o) = lo;
-    if (big) *ovf = 1;
+    if (big) ovf[(size_t)b * ovf_stride] = 1;   // (stride 0: one flag for the call)
 }
 
 int voc_launch_snake_split(hipStream_t s, const float* x, const float* alpha, const float* inv_beta, _Float16* xh, _Float16* xl, int C,
-                           int L, int ld, int gelu, int* ovf, int B) {
+                           int L, int ld, int gelu, int* ovf, int B, int ovf_stride) {
     hipLaunchKernelGGL(snake_split_kernel, dim3((unsigned)((L + 255) / 256), C / 8, B), dim3(256), 0, s, x, alpha, inv_beta, xh, xl, C, L, ld,
-                       gelu, ovf);
+                       gelu, ovf, ovf_stride);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
 }
@@ -864,7 +864,7 @@ __global__ void __launch_bounds__(256, NJ == 1 ? 3 : 2) conv_split_kernel(SplitA
                                 vh[q] = hi;
                                 vl[q] = (_Float16)((t - (float)hi) * 2048.0f);
                             }
-                            if (big) *a.ovf = 1;
+                            if (big) a.ovf[(size_t)b * a.ovf_stride] = 1;
                             const size_t o = (((size_t)b * (a.Cout >> 3) + (mg >> 3)) * a.Lin + l) * 8 + (mg & 7);
                             *(hv4*)(a.oh + o) = vh;
                             *(hv4*)(a.ol + o) = vl;
@@ -1333,15 +1333,21 @@ int voc_launch_stream_emit(hipStream_t s, const float* work, const StreamWin* w,
 // Columns [skip, skip + n) of channels [c0, c0 + C) of src ([B][src_C][src_ld]) -> dst [B][C][dst_ld] behind the H history
 // columns of the entry's stream; the last H columns of [history | new] become the stream's new history.  One workgroup
 // (blockIdx.x == 0) owns a row's history: it reads all of it before it writes any (H <= 256, the launcher's rule).
+// parity (null: the history lives in hist0 and moves on in place): entry b reads hist{parity[b]} and writes the other buffer,
+// so that a push can be dropped per entry (the split arithmetic's redo).
 __global__ void __launch_bounds__(256) voc_incr_prepend_kernel(const float* __restrict__ src, int src_C, int c0, int src_ld, int skip,
-                                                               float* __restrict__ dst, int C, int dst_ld, float* __restrict__ hist,
-                                                               int H, int n, long long state_floats, const int* __restrict__ streams) {
+                                                               float* __restrict__ dst, int C, int dst_ld, float* hist0, float* hist1,
+                                                               const int* __restrict__ parity, int H, int n, long long state_floats,
+                                                               const int* __restrict__ streams) {
     const int c = blockIdx.y, b = blockIdx.z;
     const float* s = src + ((size_t)b * src_C + c0 + c) * src_ld + skip;
     float* d = dst + ((size_t)b * C + c) * dst_ld;
     for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) d[H + j] = s[j];
     if (blockIdx.x == 0 && H > 0) {
-        float* h = hist + (size_t)streams[b] * state_floats + (size_t)c * H;
+        const size_t ho = (size_t)streams[b] * state_floats + (size_t)c * H;
+        const int par = parity ? parity[b] : 0;
+        const float* h = (par ? hist1 : hist0) + ho;
+        float* hw = (parity ? (par ? hist0 : hist1) : hist0) + ho;
         const int i = threadIdx.x;
         float old = 0.f, nw = 0.f;
         if (i < H) {
@@ -1351,15 +1357,87 @@ __global__ void __launch_bounds__(256) voc_incr_prepend_kernel(const float* __re
         __syncthreads();
         if (i < H) {
             d[i] = old;
-            h[i] = nw;
+            hw[i] = nw;
         }
     }
 }
 
 int voc_launch_incr_prepend(hipStream_t s, const float* src, int src_C, int c0, int src_ld, int skip, float* dst, int C, int dst_ld,
-                            float* hist, int H, int n, long long state_floats, const int* streams, int B) {
+                            float* hist0, float* hist1, const int* parity, int H, int n, long long state_floats, const int* streams, int B) {
     hipLaunchKernelGGL(voc_incr_prepend_kernel, dim3((unsigned)std::min(64, (n + 255) / 256), C, B), dim3(256), 0, s, src, src_C, c0, src_ld,
-                       skip, dst, C, dst_ld, hist, H, n, state_floats, streams);
+                       skip, dst, C, dst_ld, hist0, hist1, parity, H, n, state_floats, streams);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+
+// The same assembly for a conv that runs on the split-precision path: columns [skip, skip + n) of src ([B][C][src_ld]) join the H
+// history columns of the entry's stream, and [history | new] (L = H + n columns) goes out as the consuming conv's input planes --
+// its Snake / GELU applied, {hi, lo} fp16 [B][C/8][L][8], split as snake_split_kernel splits -- and, where dst is given (the
+// consumer saves a residual: the residual IS this buffer), as f32 [B][C][dst_ld].  The history itself stays f32 (the planes are
+// a pure function of it, rebuilt every push; Snake(0) = GELU(0) = 0 keeps the causal zero padding valid) and always moves from
+// hist{parity[b]} to the other buffer, so no thread reads what another writes and H is not bounded by a workgroup.
+// snake_split_kernel's access pattern: lanes run along the columns (each row read is a run of consecutive floats), a lane owns the
+// 8 channels of one column and stores one 16-byte record per plane.  ovf[b] = 1 when a plane value of entry b leaves +-65504
+// or is a NaN.
+__global__ void __launch_bounds__(256) voc_incr_prepend_split_kernel(const float* __restrict__ src, int src_ld, int skip,
+                                                                     _Float16* __restrict__ xh, _Float16* __restrict__ xl,
+                                                                     float* __restrict__ dst, int dst_ld, int C,
+                                                                     const float* __restrict__ alpha, const float* __restrict__ inv_beta,
+                                                                     int gelu, float* hist0, float* hist1,
+                                                                     const int* __restrict__ parity, int H, int n, long long state_floats,
+                                                                     const int* __restrict__ streams, int* __restrict__ ovf) {
+    const int l = blockIdx.x * 256 + threadIdx.x, cg = blockIdx.y, b = blockIdx.z;   // cg: 8-channel group
+    const int L = H + n;
+    if (l >= L) return;
+    const size_t ho = (size_t)streams[b] * state_floats + (size_t)cg * 8 * H;
+    const int par = parity[b];
+    const float* hr = (par ? hist1 : hist0) + ho;
+    float* hw = (par ? hist0 : hist1) + ho;
+    const float* sp = src + ((size_t)b * C + cg * 8) * src_ld + skip;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = l < H ? hr[(size_t)j * H + l] : sp[(size_t)j * src_ld + (l - H)];
+    if (l >= n) {   // the last H columns of [history | new] are the stream's next history
+#pragma unroll
+        for (int j = 0; j < 8; j++) hw[(size_t)j * H + (l - n)] = v[j];
+    }
+    if (dst) {
+        float* dp = dst + ((size_t)b * C + cg * 8) * dst_ld + l;
+#pragma unroll
+        for (int j = 0; j < 8; j++) dp[(size_t)j * dst_ld] = v[j];
+    }
+    if (alpha) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            const float sn = __sinf(alpha[cg * 8 + j] * v[j]);
+            v[j] = v[j] + inv_beta[cg * 8 + j] * (sn * sn);
+        }
+    }
+    if (gelu) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) v[j] = gelu_erf(v[j]);
+    }
+    hv8 h, lo;
+    bool big = false;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        big |= !(fabsf(v[j]) <= 65504.f);
+        const _Float16 hi = (_Float16)fminf(fmaxf(v[j], -65504.f), 65504.f);
+        h[j] = hi;
+        lo[j] = (_Float16)((v[j] - (float)hi) * 2048.0f);
+    }
+    const size_t o = (((size_t)b * (C >> 3) + cg) * L + l) * 8;
+    *(hv8*)(xh + o) = h;
+    *(hv8*)(xl + o) = lo;
+    if (big) ovf[b] = 1;
+}
+
+int voc_launch_incr_prepend_split(hipStream_t s, const float* src, int src_ld, int skip, _Float16* xh, _Float16* xl, float* dst, int dst_ld,
+                                  int C, const float* alpha, const float* inv_beta, int gelu, float* hist0, float* hist1, const int* parity,
+                                  int H, int n, long long state_floats, const int* streams, int* ovf, int B) {
+    if (C % 8 || H <= 0 || n <= 0 || !hist1 || !parity || !ovf) return -1;
+    hipLaunchKernelGGL(voc_incr_prepend_split_kernel, dim3((unsigned)((H + n + 255) / 256), C / 8, B), dim3(256), 0, s, src, src_ld, skip, xh,
+                       xl, dst, dst_ld, C, alpha, inv_beta, gelu, hist0, hist1, parity, H, n, state_floats, streams, ovf);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
 }

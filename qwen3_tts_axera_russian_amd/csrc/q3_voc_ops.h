@@ -82,15 +82,17 @@ struct SplitArgs {
     const float* oalpha = nullptr;
     const float* oinv_beta = nullptr;
     int* ovf = nullptr;                  // set to 1 when an output plane value leaves the fp16 range
+    int ovf_stride = 0;                  // entry b raises ovf[b * ovf_stride]: 0 = one flag for the call, 1 = a flag per entry
     int Cin = 0, M = 0, Mp = 0, dil = 1, Lin = 0, stride = 1, Cout = 0, clamp = 0, B = 0;
     int ldy = 0, lt = 0, Lout = 0, Lc = 0;   // f32 output pitch, left trim / kept outputs / GEMM columns (ConvArgs)
     int n_tiles = 0, tiles_l = 0, tiles_m = 0;
     int my_fast = 0;   // tile order, see conv_split_kernel
 };
 int launch_conv_split(hipStream_t s, const SplitArgs& a, int K, int B);
-// x f32 [B][C][ld] -> Snake / GELU -> the planes a split conv reads; *ovf = 1 when a value leaves the fp16 range
+// x f32 [B][C][ld] -> Snake / GELU -> the planes a split conv reads; ovf[b * ovf_stride] = 1 when a value of entry b leaves the
+// fp16 range (SplitArgs::ovf_stride)
 int voc_launch_snake_split(hipStream_t s, const float* x, const float* alpha, const float* inv_beta, _Float16* xh, _Float16* xl, int C,
-                           int L, int ld, int gelu, int* ovf, int B);
+                           int L, int ld, int gelu, int* ovf, int B, int ovf_stride = 0);
 
 // the small f32 ops over x [B][C][ld] (L columns), and the two code-id front ends (codes [B][T][16])
 int voc_launch_dwconv(hipStream_t s, const float* x, const float* w, const float* bias, float* y, int C, int L, int ld, int K, int B);
@@ -121,9 +123,15 @@ struct StreamWin {
 int voc_launch_stream_load(hipStream_t s, const float* tail, int OV, const StreamWin* w, float* work, int n);
 int voc_launch_stream_emit(hipStream_t s, const float* work, const StreamWin* w, float* tail, int OV, void* out, bool want16, int n);
 
-// incremental decode: [history | new] assembly, attention over the carried window, packed output (int16 or f32)
+// incremental decode: [history | new] assembly, attention over the carried window, packed output (int16 or f32).  The history
+// of entry b is read from hist{parity[b]} and written to the other buffer; parity == nullptr: hist0, in place.
 int voc_launch_incr_prepend(hipStream_t s, const float* src, int src_C, int c0, int src_ld, int skip, float* dst, int C, int dst_ld,
-                            float* hist, int H, int n, long long state_floats, const int* streams, int B);
+                            float* hist0, float* hist1, const int* parity, int H, int n, long long state_floats, const int* streams, int B);
+// [history | new] of all C channels as the consuming split conv's input planes (its Snake / GELU applied), and as f32 where dst
+// is given; ovf[b] = 1 when a plane value of entry b leaves the fp16 range.  Two history buffers only (parity given).
+int voc_launch_incr_prepend_split(hipStream_t s, const float* src, int src_ld, int skip, _Float16* xh, _Float16* xl, float* dst, int dst_ld,
+                                  int C, const float* alpha, const float* inv_beta, int gelu, float* hist0, float* hist1, const int* parity,
+                                  int H, int n, long long state_floats, const int* streams, int* ovf, int B);
 int voc_launch_incr_attn(hipStream_t s, const float* x, int x_ld, int skip, const float* kv, int kv_ld, int Hk, float* y, int H, int D,
                          int window, float theta, const int* pos0, int n, int B);
 int voc_launch_incr_emit(hipStream_t s, const float* y, int ld, int skip, int n, const long long* out_off, void* out, bool want16, int B);

@@ -87,6 +87,14 @@ int voc_op_pointwise(const Voc* v, const VocOp& op, const float* in, float* out,
 // VOP_CONV / VOP_CONVT over `cols` input columns: everything but x, y, res.  Lf: the op's input length in a full-chunk decode
 // (ConvArgs::Lrule).  A transposed conv gets the whole-chunk geometry (lt = op.lt, Lout = convt_out, Lc = convt_cols).
 ConvArgs voc_conv_args(const VocOp& op, long cols, long Lf);
+// The split-precision path of a conv op (launch_conv_split), for voc_run and the incremental walk alike:
+bool voc_split_capable(const VocOp& op);                               // built for it: 16 | Cin and every weight inside the fp16 range
+// does the split conv `op` hand its result to `next` (the op after it in this walk; null at its end) as input planes from its
+// own epilogue?  (The caller adds what only it knows: the incremental walk needs f32 where `next` prepends a history.)
+bool voc_split_emits_planes(const VocOp& op, const VocOp* next);
+SplitArgs voc_split_args(const VocOp& op, long cols);                  // everything but the planes, y, res and ovf (whole-chunk geometry)
+void voc_split_out_planes(SplitArgs& sa, const VocOp& next, _Float16* oh, _Float16* ol);   // the epilogue's planes, next's Snake applied
+int voc_split_taps(const VocOp& op);                                   // launch_conv_split's K
 // the residual unit op (7 taps) + op1 (the 1x1 conv that closes it) in one launch
 ResUnitArgs voc_resunit_args(const VocOp& op, const VocOp& op1, const float* in, float* out, long cols);
 // does op i open a residual unit that runs fused (launch_resunit, then skip op i + 1) in a walk of the first n_ops ops?

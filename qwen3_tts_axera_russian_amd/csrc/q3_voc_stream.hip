@@ -475,6 +475,18 @@ struct VocIncr {
     size_t out_cap = 0, device_bytes = 0;
     float last_ms = 0.f;
     int last_launches = 0;
+    // split-fp16 arithmetic (voc_incr_set_arithmetic), allocated by the first switch to it.  The history is then double-buffered:
+    // stream k's committed state is d_hist{parity[k]}, a push writes the other buffer and an entry commits by flipping its bit.
+    int split = 0;
+    size_t buf_elems = 0;                 // floats of one work buffer
+    float* d_hist1 = nullptr;
+    _Float16* plane[4] = {nullptr, nullptr, nullptr, nullptr};   // two {hi, lo} plane sets, buf_elems halves each
+    int* d_par = nullptr;                 // [max_batch]: the entries' parities
+    int* d_ovf = nullptr;                 // [max_batch]: an entry's plane value left the fp16 range
+    int* h_ovf = nullptr;                 // (pinned)
+    std::vector<char> parity;             // per stream
+    bool warned_ovf = false;
+    int last_split = 0, last_redone = 0;
 };
 
 int incr_hist_cols(const VocOp& op) {
@@ -516,12 +528,18 @@ void incr_key(const Voc* v, long long prev, long long now, std::vector<long long
         if (v->ops[i].op == VOP_CONVT) key[n + 1 + i] = std::max(0LL, (long long)v->ops[i].lt - a[i] * v->ops[i].p0);
 }
 
-// One launch sequence: B entries with the same key through the op table, exact-fp32 kernels only: voc_run's exact branch (the same
-// op -> launch layer, q3_voc_program.h) with [history | new] in place of the chunk.  An activation is buf[cur],
+// One launch sequence: B entries with the same key through the op table: voc_run's branches (the same op -> launch layer,
+// q3_voc_program.h) with [history | new] in place of the chunk.  split = false: exact-fp32 kernels only.  split = true: a
+// split-capable conv runs launch_conv_split on {hi, lo} planes -- of [history | new] from voc_incr_prepend_split_kernel where it
+// carries a history, from its producer's epilogue (voc_run's rule) or voc_launch_snake_split where it carries none -- a residual
+// unit runs as its two convs, every other op stays f32; every kernel that writes planes flags its entry in s->d_ovf.
+// No launcher rule of the split conv changes the order in which a column's products are summed: conv_split_kernel adds 16-channel
+// steps in channel order and taps in tap order inside each, whatever the tile shape (MW, NJ), stage count (KS) and tile order
+// (my_fast) launch_conv_split picks from Lc and B -- so nothing needs pinning to the full-chunk length here.  An activation is buf[cur],
 // [B][C][pitch4(skip + n)]: `skip` leading columns are the outputs of history columns (dropped: nothing reads them), n are the
 // new ones.  dry: no launch, *need / *need_kv take the largest work buffer / k|v buffer (floats per entry) the sequence asks for.
 int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, size_t* need, size_t* need_kv, int* launches,
-              float** out_buf, int* out_ld, int* out_skip) {
+              float** out_buf, int* out_ld, int* out_skip, bool split = false) {
     Voc* v = s->v;
     const size_t nops = v->ops.size();
     const long long* nc = key.data();
@@ -542,8 +560,11 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
         const int H = s->H[i];
         (*launches)++;
         return dry ? 0 : voc_launch_incr_prepend(v->s, s->buf[cur], srcC, c0, (int)pitch4(skip + n), skip, dst, Cc, (int)pitch4(H + n),
-                                                 s->d_hist + s->hoff[i], H, (int)n, (long long)s->state_floats, s->d_meta, B);
+                                                 s->d_hist + s->hoff[i], s->d_hist1 ? s->d_hist1 + s->hoff[i] : nullptr,
+                                                 s->d_hist1 ? s->d_par : nullptr, H, (int)n, (long long)s->state_floats, s->d_meta, B);
     };
+    int planes = -1;          // split: the plane set that holds the current activation in its consumer's input form, or -1
+    bool f32_cur = true;      // split: buf[cur] holds the current activation
     auto prepend_act = [&](size_t i) -> int {     // the whole activation: it becomes buf[cur] = [history | new]
         if (s->H[i] == 0) return 0;
         note(C, s->H[i] + n);
@@ -564,6 +585,7 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
         const VocOp& op = v->ops[i];
         if (n != nc[i]) return -1;
         if (n == 0) break;                        // no sample of this push reaches further (a stream's very first columns)
+        if (!f32_cur && !(split && voc_split_capable(op))) return -1;   // only a split conv reads planes
         if (op.op == VOP_RVQ || op.op == VOP_EMBMEAN) {
             note(op.cout, n);
             if (!dry && voc_op_embed(v, op, s->d_codes, s->buf[cur ^ 1], (int)n, B)) return -1;
@@ -583,7 +605,86 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
             if (!dry && voc_launch_incr_attn(v->s, s->buf[cur], (int)pitch4(skip + n), skip, s->d_kv, (int)pitch4(Hk + n), Hk, s->buf[cur ^ 1],
                                              op.heads, op.head_dim, op.window, op.theta, s->d_meta + (1 + i) * mb, (int)n, B))
                 return -1;
-        } else if (voc_fused_unit(v, i, nops)) {
+        } else if (split && voc_split_capable(op)) {
+            const int H = s->H[i];
+            int in_set = planes;
+            if (H > 0) {
+                // [history | new] straight into the planes; as f32 too where it is the unit's residual
+                if (!f32_cur) return -1;
+                const bool keep = (op.flags & VF_RES_SAVE) != 0;
+                in_set = 0;
+                note(C, H + n);
+                if (!dry && voc_launch_incr_prepend_split(v->s, s->buf[cur], (int)pitch4(skip + n), skip, s->plane[0], s->plane[1],
+                                                  keep ? s->buf[cur ^ 1] : nullptr, (int)pitch4(H + n), C, op.alpha, op.inv_beta,
+                                                  (op.flags & VF_GELU) ? 1 : 0, s->d_hist + s->hoff[i], s->d_hist1 + s->hoff[i], s->d_par, H,
+                                                  (int)n, (long long)s->state_floats, s->d_meta, s->d_ovf, B))
+                    return -1;
+                (*launches)++;
+                if (keep) cur ^= 1;
+                skip = H;
+            } else if (in_set < 0) {
+                if (!f32_cur) return -1;
+                in_set = 0;
+                // (over the skip leading columns too: nothing reads their planes, but they can raise the entry's flag -- a redo
+                // that was not needed is exact all the same; include/qwen3tts_voc.h)
+                if (!dry && voc_launch_snake_split(v->s, s->buf[cur], op.alpha, op.inv_beta, s->plane[0], s->plane[1], C, (int)(skip + n),
+                                           (int)pitch4(skip + n), (op.flags & VF_GELU) ? 1 : 0, s->d_ovf, B, 1))
+                    return -1;
+                (*launches)++;
+            }
+            if (op.flags & VF_RES_SAVE) {
+                if (!f32_cur) return -1;     // (the producer keeps an f32 copy whenever its consumer saves a residual)
+                save_res();
+            }
+            const long long cols = skip + n;
+            SplitArgs sa = voc_split_args(op, cols);
+            long long n_next = n;
+            int skip_next = skip;
+            if (op.op == VOP_CONVT) {        // the exact branch's geometry, see below
+                n_next = nc[i + 1];
+                skip_next = 0;
+                sa.lt = skip * op.p0 + (int)extra[i];
+                sa.Lout = (int)n_next;
+                sa.Lc = (int)cols;
+                sa.ldy = (int)pitch4(sa.Lout);
+                Lf = convt_out(op, Lf);
+                if (n_next == 0) {
+                    n = 0;
+                    i++;
+                    break;
+                }
+            }
+            note(op.cout, sa.Lout);
+            // the consumer takes planes from this epilogue only where it reads these very columns: one that carries a history
+            // needs the f32 result for its own prepend
+            const VocOp* next = i + 1 < nops ? &v->ops[i + 1] : nullptr;
+            const bool want_planes = voc_split_emits_planes(op, next) && s->H[i + 1] == 0;
+            const bool want_f32 = !want_planes || (next->flags & VF_RES_SAVE);
+            if (op.flags & VF_RES_ADD) {
+                if (!have_res || res_ld != sa.ldy || res_skip != skip_next || op.op != VOP_CONV) {
+                    Q3_LOG("voc incremental: op %zu adds a residual that is not aligned with its output", i);
+                    return -1;
+                }
+                sa.res = res;
+            }
+            sa.xh = s->plane[2 * in_set];
+            sa.xl = s->plane[2 * in_set + 1];
+            sa.ovf = s->d_ovf;
+            sa.ovf_stride = 1;
+            if (want_f32) sa.y = s->buf[cur ^ 1];
+            if (want_planes) voc_split_out_planes(sa, *next, s->plane[2 * (in_set ^ 1)], s->plane[2 * (in_set ^ 1) + 1]);
+            if (want_planes) note(op.cout, cols);
+            if (!dry && launch_conv_split(v->s, sa, voc_split_taps(op), B)) return -1;
+            if (!dry) s->last_split++;
+            f32_cur = want_f32;
+            planes = want_planes ? (in_set ^ 1) : -1;
+            n = n_next;
+            skip = skip_next;
+            (*launches)++;
+            C = op.cout;
+            cur ^= 1;
+            continue;
+        } else if (!split && voc_fused_unit(v, i, nops)) {
             if (prepend_act(i)) return -1;
             if (!dry && launch_resunit(v->s, voc_resunit_args(op, v->ops[i + 1], s->buf[cur], s->buf[cur ^ 1], skip + n), op.cin, B)) return -1;
             i++;   // the 1x1 conv is done
@@ -629,9 +730,11 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
         (*launches)++;
         C = op.cout;
         cur ^= 1;
+        planes = -1;
     }
     if (i == nops && n != nc[nops]) return -1;
     if (i < nops && nc[nops] != 0) return -1;
+    if (!f32_cur && n > 0) return -1;
     if (out_buf) *out_buf = s->buf[cur];
     if (out_ld) *out_ld = (int)pitch4(skip + n);
     if (out_skip) *out_skip = skip;
@@ -709,11 +812,14 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
     std::vector<int64_t> hcodes;
     std::vector<int> meta((1 + nops) * mb);
     std::vector<long long> off(mb), before;
+    std::vector<int> par(mb);
     s->last_launches = 0;
     s->last_ms = 0.f;
+    s->last_split = 0;
+    s->last_redone = 0;
     if (!p.keys.empty()) Q3_HIP(hipEventRecord(v->e0, v->s), -1);
-    for (size_t g = 0; g < p.keys.size(); g++) {
-        const std::vector<int>& mem = p.members[g];
+    // one launch sequence over the entries `mem` of a group, on the split or the exact branch, complete on return
+    auto run_group = [&](const std::vector<long long>& key, const std::vector<int>& mem, bool split) -> int {
         const int B = (int)mem.size(), T = n_new[mem[0]];
         hcodes.resize((size_t)B * T * 16);
         std::fill(meta.begin(), meta.end(), 0);
@@ -724,19 +830,46 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
             meta[b] = k;
             for (size_t i = 0; i < nops; i++) meta[(1 + i) * mb + b] = (int)before[i];
             off[b] = offsets[e];
+            if (s->d_hist1) par[b] = s->parity[k];
         }
         Q3_HIP(hipMemcpyAsync(s->d_codes, hcodes.data(), sizeof(int64_t) * hcodes.size(), hipMemcpyHostToDevice, v->s), -1);
         Q3_HIP(hipMemcpyAsync(s->d_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, v->s), -1);
         Q3_HIP(hipMemcpyAsync(s->d_off, off.data(), sizeof(long long) * B, hipMemcpyHostToDevice, v->s), -1);
+        if (s->d_hist1) Q3_HIP(hipMemcpyAsync(s->d_par, par.data(), sizeof(int) * B, hipMemcpyHostToDevice, v->s), -1);
+        if (split) Q3_HIP(hipMemsetAsync(s->d_ovf, 0, sizeof(int) * B, v->s), -1);
         float* y = nullptr;
         int ld = 0, skip = 0;
-        if (incr_walk(s, p.keys[g], B, false, nullptr, nullptr, &s->last_launches, &y, &ld, &skip)) return -1;
-        const long long ns = p.keys[g][nops];
+        if (incr_walk(s, key, B, false, nullptr, nullptr, &s->last_launches, &y, &ld, &skip, split)) return -1;
+        const long long ns = key[nops];
         if (ns > 0) {
             if (voc_launch_incr_emit(v->s, y, ld, skip, (int)ns, s->d_off, want16 ? (void*)s->d_out16 : (void*)s->d_out, want16, B)) return -1;
             s->last_launches++;
         }
+        if (split) Q3_HIP(hipMemcpyAsync(s->h_ovf, s->d_ovf, sizeof(int) * B, hipMemcpyDeviceToHost, v->s), -1);
         Q3_HIP(hipStreamSynchronize(v->s), -1);   // the staging vectors are reused by the next group
+        return 0;
+    };
+    std::vector<int> redo;
+    for (size_t g = 0; g < p.keys.size(); g++) {
+        const std::vector<int>& mem = p.members[g];
+        if (run_group(p.keys[g], mem, s->split != 0)) return -1;
+        if (s->split) {
+            // a push is a transaction per entry: an entry whose planes left the fp16 range is not committed -- the flagged
+            // entries of the group run again, from their uncommitted history, on the exact branch, and their samples replace the
+            // split ones; the others' bits never depended on them (every kernel works per entry)
+            redo.clear();
+            for (size_t b = 0; b < mem.size(); b++)
+                if (s->h_ovf[b]) redo.push_back(mem[b]);
+            if (!redo.empty()) {
+                if (!s->warned_ovf)
+                    Q3_LOG("vocoder incremental: activation outside the fp16 range, decoding this entry's push with the exact-fp32 path");
+                s->warned_ovf = true;
+                if (run_group(p.keys[g], redo, false)) return -1;
+                s->last_redone += (int)redo.size();
+            }
+        }
+        if (s->d_hist1)
+            for (int e : mem) s->parity[streams[e]] ^= 1;   // commit: the written buffer is the stream's history now
     }
     if (!p.keys.empty()) {
         Q3_HIP(hipEventRecord(v->e1, v->s), -1);
@@ -756,8 +889,10 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
 void incr_destroy(VocIncr* s) {
     if (!s) return;
     for (void* p : {(void*)s->d_hist, (void*)s->buf[0], (void*)s->buf[1], (void*)s->buf[2], (void*)s->d_kv, (void*)s->d_codes,
-                    (void*)s->d_meta, (void*)s->d_off, (void*)s->d_out, (void*)s->d_out16})
+                    (void*)s->d_meta, (void*)s->d_off, (void*)s->d_out, (void*)s->d_out16, (void*)s->d_hist1, (void*)s->plane[0],
+                    (void*)s->plane[1], (void*)s->plane[2], (void*)s->plane[3], (void*)s->d_par, (void*)s->d_ovf})
         if (p) hipFree(p);
+    if (s->h_ovf) hipHostFree(s->h_ovf);
     delete s;
 }
 }  // namespace
@@ -789,6 +924,7 @@ void* voc_incr_create(void* vv, int max_streams) {
     s->max_streams = max_streams;
     s->n_frames.assign(max_streams, 0);
     s->finished.assign(max_streams, 0);
+    s->parity.assign(max_streams, 0);
     const size_t nops = v->ops.size();
     s->H.assign(nops, 0);
     s->hoff.assign(nops, 0);
@@ -827,6 +963,7 @@ void* voc_incr_create(void* vv, int max_streams) {
     }
     const size_t mb = (size_t)v->max_batch;
     const size_t buf_elems = need * mb + 1024, kv_elems = need_kv * mb + 1024;   // (+ slack: float4 groups past a row's last column)
+    s->buf_elems = buf_elems;
     s->out_cap = (size_t)max_streams * v->chunk * v->upsample;
     auto alloc = [&](void** p, size_t bytes, bool zero) {
         if (!ok) return;
@@ -856,6 +993,9 @@ int voc_incr_reset(void* ss, int stream) {
     voc_bind(s->v);
     if (s->state_floats)   // the stream's history is the zero padding again (ordered before the next push on the handle's stream)
         Q3_HIP(hipMemsetAsync(s->d_hist + (size_t)stream * s->state_floats, 0, sizeof(float) * s->state_floats, s->v->s), -1);
+    if (s->state_floats && s->d_hist1)   // (both buffers: an op a short first push does not reach reads the other one next time)
+        Q3_HIP(hipMemsetAsync(s->d_hist1 + (size_t)stream * s->state_floats, 0, sizeof(float) * s->state_floats, s->v->s), -1);
+    s->parity[stream] = 0;
     s->n_frames[stream] = 0;
     s->finished[stream] = 0;
     return 0;
@@ -884,5 +1024,66 @@ float voc_incr_last_ms(void* s) { return s ? ((VocIncr*)s)->last_ms : -1.f; }
 int voc_incr_last_launches(void* s) { return s ? ((VocIncr*)s)->last_launches : -1; }
 int64_t voc_incr_state_bytes(void* s) { return s ? (int64_t)(((VocIncr*)s)->state_floats * sizeof(float)) : -1; }
 int64_t voc_incr_device_bytes(void* s) { return s ? (int64_t)((VocIncr*)s)->device_bytes : -1; }
+
+int voc_incr_set_arithmetic(void* ss, int split) {
+    VocIncr* s = (VocIncr*)ss;
+    if (!s || (split != 0 && split != 1)) return -1;
+    for (int k = 0; k < s->max_streams; k++)
+        if (s->n_frames[k] > 0 && !s->finished[k]) {
+            Q3_LOG("voc_incr_set_arithmetic: stream %d is running (the arithmetic changes between utterances only)", k);
+            return -1;
+        }
+    if (split && !s->d_hist1) {
+        // the split walk's activations and planes must fit what voc_incr_create sized from the exact walk (the same ops over the
+        // same columns: a table where they do not is refused here, not overrun)
+        size_t need = 0, need_kv = 0;
+        std::vector<long long> key;
+        for (long long prev : {0LL, (long long)s->v->chunk}) {
+            int launches = 0;
+            incr_key(s->v, prev, prev + s->v->chunk, key);
+            if (incr_walk(s, key, s->v->max_batch, true, &need, &need_kv, &launches, nullptr, nullptr, nullptr, true) ||
+                need * (size_t)s->v->max_batch + 1024 > s->buf_elems) {
+                Q3_LOG("voc_incr_set_arithmetic: the split walk does not fit the object's work buffers");
+                return -1;
+            }
+        }
+        // the second history buffer, the plane sets and the per-entry flags.  Every stream is idle, and an idle stream's next
+        // utterance starts with voc_incr_reset (or is the first of a fresh object): both buffers zero, parity 0.
+        Voc* v = s->v;
+        voc_bind(v);
+        const size_t mb = (size_t)v->max_batch, hist = sizeof(float) * std::max<size_t>(1, s->state_floats * s->max_streams);
+        void* got[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const size_t bytes[7] = {hist, sizeof(_Float16) * s->buf_elems, sizeof(_Float16) * s->buf_elems, sizeof(_Float16) * s->buf_elems,
+                                 sizeof(_Float16) * s->buf_elems, sizeof(int) * mb, sizeof(int) * mb};
+        int* h = nullptr;
+        bool ok = hipHostMalloc((void**)&h, sizeof(int) * mb, 0) == hipSuccess;
+        for (int i = 0; i < 7 && ok; i++) ok = hipMalloc(&got[i], bytes[i]) == hipSuccess;
+        // the history a fresh stream continues from is zero in both buffers (a stream that ran in exact mode and finished is reset
+        // before its next utterance, which zeroes both)
+        ok = ok && hipMemcpyAsync(got[0], s->d_hist, hist, hipMemcpyDeviceToDevice, v->s) == hipSuccess &&
+             hipMemsetAsync(got[1], 0, bytes[1], v->s) == hipSuccess && hipMemsetAsync(got[2], 0, bytes[2], v->s) == hipSuccess &&
+             hipMemsetAsync(got[3], 0, bytes[3], v->s) == hipSuccess && hipMemsetAsync(got[4], 0, bytes[4], v->s) == hipSuccess &&
+             hipStreamSynchronize(v->s) == hipSuccess;
+        if (!ok) {
+            Q3_LOG("voc_incr_set_arithmetic: device allocation failed");
+            for (void* p : got)
+                if (p) hipFree(p);
+            if (h) hipHostFree(h);
+            return -1;
+        }
+        s->d_hist1 = (float*)got[0];
+        for (int i = 0; i < 4; i++) s->plane[i] = (_Float16*)got[1 + i];
+        s->d_par = (int*)got[5];
+        s->d_ovf = (int*)got[6];
+        s->h_ovf = h;
+        for (int i = 0; i < 7; i++) s->device_bytes += bytes[i];
+    }
+    s->split = split;
+    return s->split;
+}
+
+int voc_incr_arithmetic(void* s) { return s ? ((VocIncr*)s)->split : -1; }
+int voc_incr_last_split_launches(void* s) { return s ? ((VocIncr*)s)->last_split : -1; }
+int voc_incr_last_redone(void* s) { return s ? ((VocIncr*)s)->last_redone : -1; }
 
 }  // extern "C"

@@ -129,6 +129,10 @@ def load(path: str | None = None):
     _sig(lib, "voc_incr_samples", ctypes.c_int64, [c_void_p, ctypes.c_int64])
     _sig(lib, "voc_incr_state_bytes", ctypes.c_int64, [c_void_p])
     _sig(lib, "voc_incr_device_bytes", ctypes.c_int64, [c_void_p])
+    _sig(lib, "voc_incr_set_arithmetic", c_int, [c_void_p, c_int])
+    _sig(lib, "voc_incr_arithmetic", c_int, [c_void_p])
+    _sig(lib, "voc_incr_last_split_launches", c_int, [c_void_p])
+    _sig(lib, "voc_incr_last_redone", c_int, [c_void_p])
     # include/qwen3tts_enc.h
     _sig(lib, "enc_load", c_void_p, [c_char_p, c_int, c_int])
     _sig(lib, "enc_free", None, [c_void_p])

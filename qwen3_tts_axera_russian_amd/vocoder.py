@@ -32,7 +32,7 @@ class Vocoder:
         self.chunk_samples = self.lib.voc_chunk_samples(self.h)     # one decode's output (<= chunk_tokens * samples_per_token)
         self.samples_per_token = self.lib.voc_samples_per_token(self.h)
         self._streams = []
-        self._incr1 = None               # synthesize_incremental's one-stream object
+        self._incr1 = {}                 # synthesize_incremental's one-stream object per arithmetic
 
     def decode(self, codes):
         """codes [B][chunk_tokens][16] -> f32 [B][chunk_samples] (the reference's ONNX call, vocoder_server.py:67-71)"""
@@ -75,29 +75,31 @@ class Vocoder:
         self._streams.append(VocoderStream(self.lib, self.h, max_streams))
         return self._streams[-1]
 
-    def incremental(self, max_streams):
-        """-> an IncrementalStream of max_streams utterances on this handle (freed by its close() or by this handle's)"""
-        self._streams.append(IncrementalStream(self.lib, self.h, max_streams))
+    def incremental(self, max_streams, arithmetic="exact"):
+        """-> an IncrementalStream of max_streams utterances on this handle (freed by its close() or by this handle's);
+        arithmetic: "exact" (the default) or "split" (voc_incr_set_arithmetic)"""
+        self._streams.append(IncrementalStream(self.lib, self.h, max_streams, arithmetic))
         return self._streams[-1]
 
     def incremental_samples(self, n_frames):
         """S(n): the samples of a whole carry-state decode of n_frames frames (voc_incr_samples)"""
         return int(self.lib.voc_incr_samples(self.h, int(n_frames)))
 
-    def synthesize_incremental(self, codes, int16=False):
+    def synthesize_incremental(self, codes, int16=False, arithmetic="exact"):
         """codes [n][16] -> the carry-state decode of the whole utterance (voc_incr_*): one stream, pushed in chunk_tokens
         pieces.  One seamless decode of all n frames -- not synthesize()'s cross-faded chunk walk -- and bit for bit what
-        any other split of the frames across pushes gives."""
+        any other split of the frames across pushes gives (arithmetic="split": as long as no push is redone exactly)."""
         c = _cat([codes])
-        if self._incr1 is None:
-            self._incr1 = self.incremental(1)
-        self._incr1.reset(0)
-        parts = [self._incr1.push([0], [c[f:f + self.chunk_tokens]], [f + self.chunk_tokens >= len(c)], int16)[0].copy()
+        if arithmetic not in self._incr1:
+            self._incr1[arithmetic] = self.incremental(1, arithmetic)
+        st = self._incr1[arithmetic]
+        st.reset(0)
+        parts = [st.push([0], [c[f:f + self.chunk_tokens]], [f + self.chunk_tokens >= len(c)], int16)[0].copy()
                  for f in range(0, len(c), self.chunk_tokens)]
         return np.concatenate(parts + [np.zeros(0, np.int16 if int16 else np.float32)])
 
     def close(self):
-        self._incr1 = None
+        self._incr1 = {}
         for s in self._streams:          # every stream before the handle it runs on
             s.close()
         if self.h:
@@ -109,6 +111,9 @@ class Vocoder:
             self.close()
         except Exception:
             pass
+
+
+ARITHMETICS = ("exact", "split")     # voc_incr_set_arithmetic's 0 / 1
 
 
 class VocoderStream:
@@ -152,15 +157,29 @@ class IncrementalStream:
     """The carry-state incremental decode, for up to max_streams utterances at once (voc_incr_*): every push hands out the
     samples of its new frames; joined, a stream's samples are one whole-utterance decode whatever the split."""
 
-    def __init__(self, lib, voc, max_streams):
+    def __init__(self, lib, voc, max_streams, arithmetic="exact"):
         self.lib, self.h = lib, lib.voc_incr_create(voc, int(max_streams))
         if not self.h:
             raise RuntimeError("voc_incr_create failed (see the log)")
         self.last_launches, self.last_ms = 0, 0.0    # of the last push
+        self.last_split_launches, self.last_redone = 0, 0    # conv launches on the fp16 MFMA path, entries redone exactly
         self.state_bytes = int(lib.voc_incr_state_bytes(self.h))     # per stream, constant
+        if arithmetic != "exact":
+            self.set_arithmetic(arithmetic)
+
+    @property
+    def arithmetic(self):
+        return ARITHMETICS[int(self.lib.voc_incr_arithmetic(self.h))]
+
+    def set_arithmetic(self, arithmetic):
+        """"exact" or "split" (voc_incr_set_arithmetic): accepted only while every stream is idle"""
+        if arithmetic not in ARITHMETICS:
+            raise ValueError(f"arithmetic must be one of {ARITHMETICS}, got {arithmetic!r}")
+        if self.lib.voc_incr_set_arithmetic(self.h, ARITHMETICS.index(arithmetic)) < 0:
+            raise RuntimeError("voc_incr_set_arithmetic refused (a stream is running, or no device memory; see the log)")
 
     def device_bytes(self):
-        """device memory the object holds (fixed at creation)"""
+        """device memory the object holds (fixed at creation; grows once with the first switch to "split")"""
         return int(self.lib.voc_incr_device_bytes(self.h))
 
     def reset(self, k):
@@ -181,6 +200,8 @@ class IncrementalStream:
         fn = self.lib.voc_incr_push if int16 else self.lib.voc_incr_push_f32
         pcm = _packed(fn, args, len(st), cap, int16)
         self.last_launches = int(self.lib.voc_incr_last_launches(self.h))
+        self.last_split_launches = int(self.lib.voc_incr_last_split_launches(self.h))
+        self.last_redone = int(self.lib.voc_incr_last_redone(self.h))
         self.last_ms = float(self.lib.voc_incr_last_ms(self.h))
         return pcm
 

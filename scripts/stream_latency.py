@@ -11,14 +11,16 @@ ways in one process, alternating, `--repeats` times after one untimed pass of ea
 
   incremental  (--incremental) the stream leg with the carry-state decode (voc_incr_push) in place of the chunk walk: every
           check's new frames become samples at once -- what the batch server does for {"stream": true, "vocoder": "incremental"}.
-          Its joined PCM is checked against Vocoder.synthesize_incremental per utterance, bit for bit.
+          Its joined PCM is checked against Vocoder.synthesize_incremental per utterance, bit for bit.  --arithmetic picks its
+          convolutions: exact (the default; leg "incremental"), split (voc_incr_set_arithmetic; leg "incremental_split") or
+          both, side by side in the same process.
 
 Both exact fp32, int16 out.  Per utterance: time from the request's start to its first and to its last final sample (batch: the
 reply goes out once everything is done, so both are the request's end).  Fixed lengths (EOS off, --frames frames) and natural
 lengths (EOS on).  The joined streamed PCM of every utterance is checked against the batch reply, bit for bit.
 
     python scripts/stream_latency.py --out profiles/stream_latency.json
-    python scripts/stream_latency.py --incremental --out profiles/stream_latency_incremental.json
+    python scripts/stream_latency.py --incremental --arithmetic both --out profiles/stream_latency_incremental.json
 """
 from __future__ import annotations
 
@@ -48,7 +50,8 @@ def run_stream(eng, vs, pool, prefixes, n_text, frames, ignore_eos):
     U = len(prefixes)
     first, last = [None] * U, [None] * U
     pcm = [[] for _ in range(U)]
-    stats = {"pushes": 0, "decode_calls": 0, "chunks": 0, "launches": 0, "push_gpu_ms": 0.0, "push_wall_ms": 0.0, "loop_wait_ms": 0.0}
+    stats = {"pushes": 0, "decode_calls": 0, "chunks": 0, "launches": 0, "split_launches": 0, "redone": 0, "push_gpu_ms": 0.0,
+             "push_wall_ms": 0.0, "loop_wait_ms": 0.0}
     slot_utt, pushed = [None] * eng.max_batch, [0] * eng.max_batch
     fut = [None]
     t0 = time.perf_counter()
@@ -70,6 +73,8 @@ def run_stream(eng, vs, pool, prefixes, n_text, frames, ignore_eos):
         stats["decode_calls"] += getattr(vs, "last_decodes", 0)      # (the chunk walk's counters)
         stats["chunks"] += getattr(vs, "last_chunks", 0)
         stats["launches"] += getattr(vs, "last_launches", 0)         # (the incremental decode's)
+        stats["split_launches"] += getattr(vs, "last_split_launches", 0)
+        stats["redone"] += getattr(vs, "last_redone", 0)
         stats["push_gpu_ms"] += vs.last_ms
         stats["push_wall_ms"] += (time.perf_counter() - ts) * 1e3
 
@@ -127,6 +132,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--cache", default=os.environ.get("Q3_BENCH_CACHE", "/tmp/q3_bench_cache"))
     ap.add_argument("--incremental", action="store_true", help="add the carry-state incremental leg (voc_incr_push)")
+    ap.add_argument("--arithmetic", choices=("exact", "split", "both"), default="exact",
+                    help="--incremental: the convolutions of the incremental leg(s)")
     ap.add_argument("--out", default=None, help="write the JSON result here too")
     a = ap.parse_args()
     lib = hiplib.load()
@@ -141,7 +148,10 @@ def main():
     lib.voc_set_exact_fp32(1)
     voc = Vocoder(voc_path, 64, min(U, 32))
     vs = voc.stream(U)
-    vi = voc.incremental(U) if a.incremental else None
+    incr = {}        # leg name -> (IncrementalStream, arithmetic)
+    if a.incremental:
+        for arith in (("exact", "split") if a.arithmetic == "both" else (a.arithmetic,)):
+            incr["incremental" if arith == "exact" else "incremental_split"] = (voc.incremental(U, arith), arith)
     pool = ThreadPoolExecutor(max_workers=1)
     result = {"what": "first / last final sample per utterance of one request, streaming chunk walk vs generate-then-vocode",
               "utterances": U, "max_frames": a.frames, "repeats": a.repeats, "vocoder": "full table, exact fp32, int16 out",
@@ -149,13 +159,13 @@ def main():
     try:
         for leg, ignore_eos in (("fixed", True), ("natural", False)):
             runs = {"stream": [], "batch": []}
-            if a.incremental:
-                runs["incremental"] = []
+            for name in incr:
+                runs[name] = []
             for rep in range(a.repeats + 1):
                 for mode in runs:
                     if mode != "batch":
                         lib.voc_set_max_workgroups(-1)
-                        r = run_stream(eng, vs if mode == "stream" else vi, pool, prefixes, n_text, a.frames, ignore_eos)
+                        r = run_stream(eng, vs if mode == "stream" else incr[mode][0], pool, prefixes, n_text, a.frames, ignore_eos)
                     else:
                         lib.voc_set_max_workgroups(0)
                         r = run_batch(eng, voc, prefixes, n_text, a.frames, ignore_eos)
@@ -168,12 +178,12 @@ def main():
             frames_total = int(sum(len(c) for c in bc))
             out = {"frames_total": frames_total, "frames_min_max": [int(min(len(c) for c in bc)), int(max(len(c) for c in bc))],
                    "bit_identical": bool(identical)}
-            if a.incremental:
-                ic, ip = runs["incremental"][-1][0], runs["incremental"][-1][1]
+            for name, (_, arith) in incr.items():
+                ic, ip = runs[name][-1][0], runs[name][-1][1]
                 lib.voc_set_max_workgroups(0)
-                out["incremental_bit_identical_to_synthesize_incremental"] = bool(
+                out[f"{name}_bit_identical_to_synthesize_incremental"] = bool(
                     all(np.array_equal(x, y) for x, y in zip(ic, bc)) and
-                    all(np.array_equal(p, voc.synthesize_incremental(c, int16=True)) for c, p in zip(ic, ip)))
+                    all(np.array_equal(p, voc.synthesize_incremental(c, int16=True, arithmetic=arith)) for c, p in zip(ic, ip)))
             for mode, rs in runs.items():
                 walls = [r[4] for r in rs]
                 out[mode] = {
@@ -190,10 +200,13 @@ def main():
                                       "chunks_per_call": round(st["chunks"] / max(st["decode_calls"], 1), 2),
                                       "push_gpu_ms": round(st["push_gpu_ms"], 1), "push_wall_ms": round(st["push_wall_ms"], 1),
                                       "frame_loop_wait_for_push_ms": round(st["loop_wait_ms"], 1)})
-                elif mode == "incremental":
-                    out[mode].update({"pushes": st["pushes"], "launches": st["launches"],
+                elif mode in incr:
+                    out[mode].update({"arithmetic": incr[mode][1], "pushes": st["pushes"], "launches": st["launches"],
                                       "launches_per_push": round(st["launches"] / max(st["pushes"], 1), 1),
-                                      "push_gpu_ms": round(st["push_gpu_ms"], 1), "push_wall_ms": round(st["push_wall_ms"], 1),
+                                      "split_conv_launches": st["split_launches"], "entries_redone_exactly": st["redone"],
+                                      "push_gpu_ms": round(st["push_gpu_ms"], 1),
+                                      "push_gpu_ms_per_push": round(st["push_gpu_ms"] / max(st["pushes"], 1), 2),
+                                      "push_wall_ms": round(st["push_wall_ms"], 1),
                                       "frame_loop_wait_for_push_ms": round(st["loop_wait_ms"], 1)})
                 else:
                     out[mode].update({"chunks": st["chunks"], "decode_calls_min": -(-st["chunks"] // min(U, 32)),
