@@ -47,4 +47,8 @@ float enc_last_ms(void* h);
 #ifdef __cplusplus
 }
 #endif
+
+/* Streaming encode: clips of any length in constant memory, ids as the samples arrive */
+#include "qwen3tts_enc_stream.h"
+
 #endif /* QWEN3TTS_ENC_H */

@@ -1,0 +1,83 @@
+// q3_enc.h -- what the encoder's two translation units share: the loaded op table (q3_enc.hip builds it, q3_enc_stream.hip
+// walks it a push at a time), the quantiser's launcher, and the host arithmetic of the streaming encode (no device call: the
+// test library hands it to the CPU tests as it stands).
+#pragma once
+#include "q3_common.h"
+
+#include <vector>
+
+namespace q3 {
+
+enum { EOP_CONV_IN = 1, EOP_CONV = 2, EOP_CONV_S = 3, EOP_NORM = 4, EOP_ATTN = 5, EOP_RVQ = 6 };
+enum { EF_ELU = 1, EF_RES_SAVE = 2, EF_RES_ADD = 4, EF_TO_RES = 8, EF_GELU = 16, EF_REPLICATE = 32 };
+
+static inline long enc_pitch(long L) { return (L + 31) & ~31L; }
+
+constexpr int ENC_IN_MAXK = 16;
+
+struct EncOp {
+    int op = 0, cin = 0, cout = 0, k = 0, p0 = 0, flags = 0;   // p0: dilation (CONV) / stride (CONV_S)
+    float *w = nullptr, *bias = nullptr;                      // conv weights in conv_kernel's packed layout (CONV_IN: [cout][k])
+    int heads = 0, head_dim = 0, window = 0;
+    float eps = 0.f, theta = 10000.f;
+    int nq = 0, cb = 0, dim = 0, n_sem = 0;                    // RVQ
+    float *cbk = nullptr, *cbt = nullptr, *n2 = nullptr;
+};
+
+struct Enc {
+    int device = 0;
+    int max_batch = 1, max_samples = 0, sample_rate = 24000, hop = 1, nq = 0;
+    std::vector<EncOp> ops;
+    std::vector<void*> allocs;
+    hipStream_t s = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float* pcm = nullptr;           // [max_batch][pitch(max_samples)]
+    float* buf[4] = {nullptr, nullptr, nullptr, nullptr};   // ping-pong pair, residual, unfolded input
+    size_t buf_elems = 0;
+    int* d_lens = nullptr;          // [n_ops][max_batch] per-clip input lengths of every op
+    int64_t* d_codes = nullptr;     // [max_batch][max frames][nq]
+    size_t codes_cap = 0;
+    float last_ms = 0.f;
+};
+
+static inline void enc_bind(const Enc* e) {
+    int d = -1;
+    if (e && (hipGetDevice(&d) != hipSuccess || d != e->device)) hipSetDevice(e->device);
+}
+
+// the split residual VQ over n_frames frames, frame g = b * T + t read from z [B][2 * dim][ld] -> codes [n_frames][nq]
+int enc_launch_rvq(hipStream_t s, const float* z, int ld, int T, int n_frames, const EncOp& op, int64_t* codes);
+
+// ---- streaming encode: the column counts of every level from a stream's running total ----
+// Level l is the input of the l-th strided op (level 0: samples); cols[n_levels] are frames.  A strided op of stride s turns
+// the T columns it has been given into floor(T / s) outputs while the stream runs -- output u reads inputs below (u + 1) * s --
+// and into ceil(T / s) once the stream has finished (the leftover padded as a clip's end is).  Nested floors (and nested
+// ceilings) compose, so every level follows from the total alone.
+static inline void enc_stream_cols(const int* strides, int n_levels, long long total, bool finished, long long* cols) {
+    long long L = total;
+    for (int l = 0; l < n_levels; l++) {
+        cols[l] = L;
+        L = finished ? (L + strides[l] - 1) / strides[l] : L / strides[l];
+    }
+    cols[n_levels] = L;
+}
+
+// What one push does to a stream that had `before` samples: n_in[l] new columns at level l (n_in[n_levels]: frames handed
+// out), before_cols[l] the columns level l had taken, and carry[l] the columns strided op l holds when the push starts: its
+// k - s left-context columns plus the before_cols[l] % s not yet consumed by a whole stride.
+static inline void enc_stream_plan(const int* ks, const int* strides, int n_levels, long long before, long long n_new, bool finish,
+                                   long long* n_in, long long* before_cols, long long* carry) {
+    std::vector<long long> a(n_levels + 1);
+    enc_stream_cols(strides, n_levels, before, false, before_cols);
+    enc_stream_cols(strides, n_levels, before + n_new, finish, a.data());
+    for (int l = 0; l <= n_levels; l++) n_in[l] = a[l] - before_cols[l];
+    for (int l = 0; l < n_levels; l++) carry[l] = (ks[l] - strides[l]) + before_cols[l] % strides[l];
+}
+
+struct EncStream;
+// enc_stream_push with one more output (the test library's q3t_enc_stream_embeddings): emb_out, when given, receives the
+// pre-quantiser embedding columns of the push, [frames][channels] packed like the codes
+int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const float* pcm, const int32_t* n_new, const int32_t* finish,
+                         int64_t* codes_out, int64_t out_capacity_frames, int64_t* offsets, float* emb_out, int* emb_channels);
+
+}  // namespace q3

@@ -17,7 +17,7 @@
 // its own length, so the padding columns of a shorter clip never reach its kept outputs.  No variant rule looks at the
 // batch or the lengths (ConvArgs::Lrule, ConvArgs::elu, voc_launch_attn): clip b gives the same bits alone and in a batch.
 #include "../../include/qwen3tts_enc.h"
-#include "q3_common.h"
+#include "q3_enc.h"
 #include "q3_voc_ops.h"
 
 #include <algorithm>
@@ -26,16 +26,10 @@
 
 namespace q3 {
 
-enum { EOP_CONV_IN = 1, EOP_CONV = 2, EOP_CONV_S = 3, EOP_NORM = 4, EOP_ATTN = 5, EOP_RVQ = 6 };
-enum { EF_ELU = 1, EF_RES_SAVE = 2, EF_RES_ADD = 4, EF_TO_RES = 8, EF_GELU = 16, EF_REPLICATE = 32 };
-
-static inline long enc_pitch(long L) { return (L + 31) & ~31L; }
-
 // ---------------------------------------------------------------------------
 // First conv: x [B][ldx] (one channel) -> y [B][Cout][ldy], causal k taps (zeros left of column 0), + bias.
 // One thread per column holds its k inputs and walks the output channels (weights: wave-uniform loads).
 // ---------------------------------------------------------------------------
-constexpr int ENC_IN_MAXK = 16;
 __global__ void __launch_bounds__(256) enc_conv_in_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ y, int ldy,
                                                           int Cout, int K, int L) {
@@ -208,30 +202,19 @@ __global__ void __launch_bounds__(256) enc_rvq_kernel(const float* __restrict__ 
     }
 }
 
-struct EncOp {
-    int op = 0, cin = 0, cout = 0, k = 0, p0 = 0, flags = 0;   // p0: dilation (CONV) / stride (CONV_S)
-    float *w = nullptr, *bias = nullptr;                      // conv weights in conv_kernel's packed layout (CONV_IN: [cout][k])
-    int heads = 0, head_dim = 0, window = 0;
-    float eps = 0.f, theta = 10000.f;
-    int nq = 0, cb = 0, dim = 0, n_sem = 0;                    // RVQ
-    float *cbk = nullptr, *cbt = nullptr, *n2 = nullptr;
-};
-
-struct Enc {
-    int device = 0;
-    int max_batch = 1, max_samples = 0, sample_rate = 24000, hop = 1, nq = 0;
-    std::vector<EncOp> ops;
-    std::vector<void*> allocs;
-    hipStream_t s = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float* pcm = nullptr;           // [max_batch][pitch(max_samples)]
-    float* buf[4] = {nullptr, nullptr, nullptr, nullptr};   // ping-pong pair, residual, unfolded input
-    size_t buf_elems = 0;
-    int* d_lens = nullptr;          // [n_ops][max_batch] per-clip input lengths of every op
-    int64_t* d_codes = nullptr;     // [max_batch][max frames][nq]
-    size_t codes_cap = 0;
-    float last_ms = 0.f;
-};
+int enc_launch_rvq(hipStream_t s, const float* z, int ld, int T, int n_frames, const EncOp& op, int64_t* codes) {
+    const int nf = n_frames;
+    const int ft = nf >= 2048 ? 16 : 4;
+    const size_t lds = ((size_t)ft * op.dim + 4 * ft) * 4 + (size_t)5 * ft * 4;
+    if (ft == 16)
+        hipLaunchKernelGGL(enc_rvq_kernel<16>, dim3((unsigned)((nf + 15) / 16)), dim3(256), lds, s, z, ld, T, nf, op.cbk, op.cbt, op.n2,
+                           op.nq, op.cb, op.dim, op.n_sem, codes);
+    else
+        hipLaunchKernelGGL(enc_rvq_kernel<4>, dim3((unsigned)((nf + 3) / 4)), dim3(256), lds, s, z, ld, T, nf, op.cbk, op.cbt, op.n2,
+                           op.nq, op.cb, op.dim, op.n_sem, codes);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
 
 static float* enc_up(Enc* e, const float* h, size_t n) {
     float* d = nullptr;
@@ -324,16 +307,7 @@ static int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, floa
         } else if (op.op == EOP_ATTN) {
             if (voc_launch_attn(e->s, src, dst, op.heads, op.head_dim, (int)L, (int)ld, op.window, op.theta, B)) return -1;
         } else if (op.op == EOP_RVQ) {
-            const int nf = B * (int)L;
-            const int ft = nf >= 2048 ? 16 : 4;
-            const size_t lds = ((size_t)ft * op.dim + 4 * ft) * 4 + (size_t)5 * ft * 4;
-            if (ft == 16)
-                hipLaunchKernelGGL(enc_rvq_kernel<16>, dim3((unsigned)((nf + 15) / 16)), dim3(256), lds, e->s, src, (int)ld, (int)L, nf,
-                                   op.cbk, op.cbt, op.n2, op.nq, op.cb, op.dim, op.n_sem, e->d_codes);
-            else
-                hipLaunchKernelGGL(enc_rvq_kernel<4>, dim3((unsigned)((nf + 3) / 4)), dim3(256), lds, e->s, src, (int)ld, (int)L, nf,
-                                   op.cbk, op.cbt, op.n2, op.nq, op.cb, op.dim, op.n_sem, e->d_codes);
-            Q3_HIP(hipGetLastError(), -1);
+            if (enc_launch_rvq(e->s, src, (int)ld, (int)L, B * (int)L, op, e->d_codes)) return -1;
             *out = nullptr;
             *outC = op.nq;
             *outL = L;
@@ -352,11 +326,6 @@ static int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, floa
 }  // namespace q3
 
 using namespace q3;
-
-static inline void enc_bind(const Enc* e) {
-    int d = -1;
-    if (e && (hipGetDevice(&d) != hipSuccess || d != e->device)) hipSetDevice(e->device);
-}
 
 extern "C" {
 

@@ -1,6 +1,7 @@
 // q3_test_api.hip -- kernel-level entry points used only by tests/ and bench.py (host arrays in, host arrays
 // out).  Built into lib/libqwen3tts_test.so, which links against the product library; NOT part of
 // libqwen3tts.so / llama_wrapper.so.
+#include "q3_enc.h"
 #include "q3_model.h"
 #include "q3_voc_ops.h"
 #include <chrono>
@@ -657,4 +658,23 @@ extern "C" int q3t_cp_qkv_live(void* mm, int group, const int* toks, int R, int 
     }
     work_free(w);
     return rc;
+}
+
+// ---- streaming encode (enc_stream_*, csrc/q3_enc_stream.hip) ----
+// enc_stream_push that also hands back the pre-quantiser embedding columns of the push: emb [frames][*channels], packed like
+// the codes (emb must hold the push's frames x the encoder's hidden width).
+extern "C" int q3t_enc_stream_embeddings(void* s, int n, const int32_t* streams, const float* pcm, const int32_t* n_new,
+                                         const int32_t* finish, int64_t* codes_out, int64_t out_capacity_frames, int64_t* offsets,
+                                         float* emb, int* channels) {
+    if (!emb || !channels) return -1;
+    return enc_stream_push_impl((EncStream*)s, n, streams, pcm, n_new, finish, codes_out, out_capacity_frames, offsets, emb, channels);
+}
+// The host arithmetic of a push, no device call: a stream of `before` samples takes n_new more (and finishes) -> n_in
+// [n_levels + 1] new columns per level (the last: frames handed out), before_cols [n_levels + 1], carry [n_levels] columns
+// each strided op holds when the push starts.
+extern "C" int q3t_enc_stream_plan(const int* ks, const int* strides, int n_levels, long long before, long long n_new, int finish,
+                                   long long* n_in, long long* before_cols, long long* carry) {
+    if (!ks || !strides || n_levels < 1 || before < 0 || n_new < 0) return -1;
+    enc_stream_plan(ks, strides, n_levels, before, n_new, finish != 0, n_in, before_cols, carry);
+    return 0;
 }

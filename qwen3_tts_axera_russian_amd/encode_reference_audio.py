@@ -2,11 +2,13 @@
 scripts/encode_reference_audio.py, on the GPU encoder).
 
     python -m qwen3_tts_axera_russian_amd.encode_reference_audio --audio ref.wav --model enc.q3w --output_dir prompt/ \
-        [--ref_text "..."] [--max_tokens 256] [--decode_back ref_decoded.wav --vocoder voc.q3w]
+        [--ref_text "..."] [--max_tokens 256] [--decode_back ref_decoded.wav --vocoder voc.q3w] [--stream_seconds 1.0]
 
 Writes ref_codec_tokens.npy (int64 [min(T, max_tokens)][16], the semantic id first) to --output, or, with --output_dir,
 a prompt_dir holding ref_codec_tokens.npy and (with --ref_text) ref_text.txt.  --model is an encoder container
-(weights.convert_speech_tokenizer_encoder) or a speech_tokenizer/ directory, converted on the fly.
+(weights.convert_speech_tokenizer_encoder) or a speech_tokenizer/ directory, converted on the fly.  --stream_seconds S
+encodes the clip in pushes of S seconds through the streaming encode (Encoder.encode_streaming): device memory is that of
+one push, whatever the WAV's length.
 
 WAV loading follows the reference's load_wav: int16 / 32768, int32 / 2^31, any other dtype cast to float32 unscaled,
 channels averaged.  Audio at another rate than the encoder's is resampled on the host with scipy.signal.resample_poly;
@@ -91,9 +93,13 @@ def main(argv=None, encoder_factory=open_encoder):
     p.add_argument("--max_tokens", type=int, default=256)
     p.add_argument("--decode_back", default=None, help="also decode the saved ids to this WAV through the vocoder")
     p.add_argument("--vocoder", default=None, help="vocoder container for --decode_back")
+    p.add_argument("--stream_seconds", type=float, default=None,
+                   help="encode in pushes of this many seconds through the streaming encode (a WAV of any length)")
     a = p.parse_args(argv)
     if a.decode_back and not a.vocoder:
         p.error("--decode_back needs --vocoder")
+    if a.stream_seconds is not None and not a.stream_seconds > 0:
+        p.error("--stream_seconds must be > 0")
     if a.max_tokens < 1:
         p.error("--max_tokens must be >= 1")
     try:
@@ -106,12 +112,20 @@ def main(argv=None, encoder_factory=open_encoder):
         return 2
     print(f"Audio: {a.audio}\n  Duration: {x.size / sr:.2f}s, SR: {sr}")
     x = resample(x, sr, 24000)
-    enc = encoder_factory(a.model, max(int(x.size), 1))
+    if a.stream_seconds is None:
+        enc = encoder_factory(a.model, max(int(x.size), 1))
+    else:   # the handle's whole-clip buffers are not used: sized for one push
+        enc = encoder_factory(a.model, max(int(round(a.stream_seconds * 24000)), 1))
     if enc.sample_rate != 24000:
         x = resample(x, 24000, enc.sample_rate)
     t0 = time.time()
-    codes = enc.encode([x])[0]
-    print(f"Encode time: {time.time() - t0:.3f}s (GPU {enc.last_ms():.2f} ms)")
+    if a.stream_seconds is None:
+        codes = enc.encode([x])[0]
+        print(f"Encode time: {time.time() - t0:.3f}s (GPU {enc.last_ms():.2f} ms)")
+    else:
+        push = max(int(round(a.stream_seconds * enc.sample_rate)), 1)
+        codes = enc.encode_streaming(x, push)
+        print(f"Encode time: {time.time() - t0:.3f}s (streamed, {-(-x.size // push)} pushes of {push} samples)")
     n_tokens, n_groups = codes.shape
     print(f"Tokens: {n_tokens}, Groups: {n_groups}")
     keep = np.ascontiguousarray(codes[:min(n_tokens, a.max_tokens)], dtype=np.int64)

@@ -48,9 +48,87 @@ class Encoder:
         """GPU milliseconds of the last library call"""
         return float(self.lib.enc_last_ms(self.h))
 
+    def stream(self, max_streams=1, max_push_samples=24000):
+        """-> EncoderStream: max_streams clips of any length encoded as their samples arrive (enc_stream_*); close it before
+        this encoder."""
+        return EncoderStream(self, max_streams, max_push_samples)
+
+    def encode_streaming(self, pcm, push_samples=24000):
+        """One clip of any length (max_samples does not bound it) in pushes of push_samples samples -> int64 [frames, n_q]."""
+        pcm = np.ascontiguousarray(np.asarray(pcm, dtype=np.float32).reshape(-1))
+        push_samples = int(push_samples)
+        if push_samples <= 0:
+            raise ValueError("push_samples must be positive")
+        st = self.stream(1, push_samples)
+        try:
+            parts = []
+            for at in range(0, max(pcm.size, 1), push_samples):
+                last = at + push_samples >= pcm.size
+                parts.append(st.push([(0, pcm[at:at + push_samples], last)])[0])
+            return np.concatenate(parts, axis=0)
+        finally:
+            st.close()
+
     def close(self):
         if self.h:
             self.lib.enc_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EncoderStream:
+    """The carry-state streaming encode, for up to max_streams clips at once (enc_stream_*): after pushes totalling n samples a
+    stream has handed out floor(n / samples_per_frame) frames, and the finishing push brings that to frames(n).  Joined, a
+    stream's ids are the same bits whatever the split.  Device memory is fixed at creation, whatever the clips' lengths."""
+
+    def __init__(self, enc, max_streams, max_push_samples):
+        self.lib, self.enc = enc.lib, enc
+        self.max_streams, self.max_push_samples = int(max_streams), int(max_push_samples)
+        self.h = self.lib.enc_stream_create(enc.h, self.max_streams, self.max_push_samples)
+        if not self.h:
+            raise RuntimeError("enc_stream_create failed (no memory, or a table that cannot be streamed; see the log)")
+        self.n_q = enc.n_q
+        self.state_bytes = int(self.lib.enc_stream_state_bytes(self.h))    # per stream, constant
+        self.last_launches, self.last_ms = 0, 0.0                           # of the last push
+
+    def device_bytes(self):
+        """device memory the object holds (fixed at creation)"""
+        return int(self.lib.enc_stream_device_bytes(self.h))
+
+    def reset(self, k):
+        """stream k starts a new clip"""
+        if self.lib.enc_stream_reset(self.h, int(k)) != 0:
+            raise RuntimeError("enc_stream_reset failed")
+
+    def push(self, entries):
+        """entries: (stream, new samples (float32, 0..max_push_samples of them), finish) -> per entry the int64 [frames, n_q]
+        ids the push hands out (possibly 0 frames)."""
+        st = np.array([e[0] for e in entries], np.int32)
+        new = [np.ascontiguousarray(np.asarray(e[1], dtype=np.float32).reshape(-1)) for e in entries]
+        n_new = np.array([x.size for x in new], np.int32)
+        fin = np.array([int(bool(e[2])) for e in entries], np.int32)
+        pcm = np.concatenate(new + [np.zeros(1, np.float32)])
+        cap = int(self.lib.enc_stream_push_max_frames(self.h, len(st), hiplib.iptr(st), hiplib.iptr(n_new), hiplib.iptr(fin)))
+        if cap < 0:
+            raise RuntimeError("enc_stream_push: invalid push (see the log)")
+        codes = np.empty((max(cap, 1), self.n_q), np.int64)
+        off = np.zeros(len(st) + 1, np.int64)
+        rc = self.lib.enc_stream_push(self.h, len(st), hiplib.iptr(st), hiplib.fptr(pcm), hiplib.iptr(n_new), hiplib.iptr(fin),
+                                      codes.ctypes.data_as(hiplib.i64p), cap, off.ctypes.data_as(hiplib.i64p))
+        if rc != 0:
+            raise RuntimeError(f"enc_stream_push failed ({rc}); see the log")
+        self.last_launches = int(self.lib.enc_stream_last_launches(self.h))
+        self.last_ms = float(self.lib.enc_stream_last_ms(self.h))
+        return [codes[off[i]:off[i + 1]].copy() for i in range(len(st))]
+
+    def close(self):
+        if self.h:
+            self.lib.enc_stream_free(self.h)
             self.h = None
 
     def __del__(self):

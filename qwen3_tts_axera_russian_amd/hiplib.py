@@ -144,6 +144,16 @@ def load(path: str | None = None):
     _sig(lib, "enc_last_ms", c_float, [c_void_p])
     _sig(lib, "enc_debug_shape", c_int, [c_void_p, i32p, c_int, c_int, i32p, i32p])
     _sig(lib, "enc_debug_run", c_int, [c_void_p, f32p, i32p, c_int, c_int, f32p, i32p, i32p])
+    # include/qwen3tts_enc_stream.h
+    _sig(lib, "enc_stream_create", c_void_p, [c_void_p, c_int, c_int])
+    _sig(lib, "enc_stream_free", None, [c_void_p])
+    _sig(lib, "enc_stream_reset", c_int, [c_void_p, c_int])
+    _sig(lib, "enc_stream_push_max_frames", c_int, [c_void_p, c_int, i32p, i32p, i32p])
+    _sig(lib, "enc_stream_push", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, i64p_, ctypes.c_int64, i64p_])
+    _sig(lib, "enc_stream_last_ms", c_float, [c_void_p])
+    _sig(lib, "enc_stream_last_launches", c_int, [c_void_p])
+    _sig(lib, "enc_stream_state_bytes", ctypes.c_int64, [c_void_p])
+    _sig(lib, "enc_stream_device_bytes", ctypes.c_int64, [c_void_p])
     # include/qwen3tts_text.h
     _sig(lib, "tfe_load", c_void_p, [c_char_p, c_char_p, c_int])
     _sig(lib, "tfe_free", None, [c_void_p])
@@ -196,6 +206,9 @@ def load_test():
     _sig(lib, "q3t_cp_qkv_serves", c_int, [c_void_p, c_int])
     _sig(lib, "q3t_cp_qkv_tab", c_int, [c_void_p, c_int, i32p, c_int, f32p])
     _sig(lib, "q3t_cp_qkv_live", c_int, [c_void_p, c_int, i32p, c_int, c_int, f32p])
+    _sig(lib, "q3t_enc_stream_embeddings", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, i64p, ctypes.c_int64, i64p, f32p, i32p])
+    i64s = ctypes.POINTER(ctypes.c_longlong)
+    _sig(lib, "q3t_enc_stream_plan", c_int, [i32p, i32p, c_int, ctypes.c_longlong, ctypes.c_longlong, c_int, i64s, i64s, i64s])
     _test_lib = lib
     return lib
 
