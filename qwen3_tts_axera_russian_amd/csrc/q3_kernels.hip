@@ -1840,10 +1840,12 @@ __device__ int block_sample_topk(float* lg, int n, int top_k, float temperature,
             int pick = 0;
             if (found > 0 && !(selv[0] < INFINITY)) pick = seli[0];       // NaN / +inf on top: no softmax exists
             else if (found > 0) {
-                // the selection is in descending order: selv[0] is the maximum
+                // the selection is in descending order: selv[0] is the maximum (held in a register: the loop overwrites
+                // selv[0] with its weight, 1, in its first round)
+                const float top = selv[0];
                 float sum = 0.f;
                 for (int k = 0; k < found; k++) {
-                    selv[k] = expf((selv[k] - selv[0]) * inv_t);
+                    selv[k] = expf((selv[k] - top) * inv_t);
                     sum += selv[k];
                 }
                 int keep = found;
@@ -2295,6 +2297,10 @@ __global__ void __launch_bounds__(256) cp_argmax_kernel_slots(CpArgmaxArgs a) { 
 
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a) {
     if (a.R <= 0) return 0;
+    if (a.V % 4) {   // the arg-max reads each row as V / 4 float4: a tail would be dropped, and odd rows misaligned
+        Q3_LOG("cp_argmax: a vocabulary of %d is not a multiple of 4", a.V);
+        return -1;
+    }
     if (a.slots && a.V > SAMPLE_SORT_CAP) {
         Q3_LOG("cp_argmax: a vocabulary of %d is beyond the per-slot sampler (sort cap %d)", a.V, SAMPLE_SORT_CAP);
         return -1;

@@ -504,6 +504,171 @@ extern "C" int q3t_talker_sample(const float* logits, int V, const int* past, in
     return code;
 }
 
+// One launch_talker_sample over rows row0 .. row0+R-1 of a batch of R_total, every piece of state in and out on host
+// arrays: logits[R_total][V], past[R_total][32], n_past / n_text / done / n_frames / pos0 / pos [R_total],
+// codes[frame_cap][R_total][16], forced (same layout, or null), seed_ptr[R_total] (or null), slots = SlotParams[R_total]
+// (or null; non-null selects the per-slot kernel).  Returns the launcher's own refusal (-1), -2 for arguments this hook
+// cannot lay out, -1000 on a HIP error.
+extern "C" int q3t_talker_sample_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
+                                      const int* n_text, int* done, int* n_frames, const int* pos0, int* pos, int* codes,
+                                      int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos,
+                                      int max_frames, float rep_penalty, float temperature, int top_k, float top_p,
+                                      unsigned long long seed, const unsigned long long* seed_ptr, const void* slots) {
+    if (!logits || V <= 0 || R < 0 || row0 < 0 || row0 + R > R_total || frame_cap < 0 || eos < 0 || eos >= V) return -2;
+    for (int r = row0; r < row0 + R; r++)
+        if (n_frames[r] < 0 || n_past[r] < 0) return -2;
+    const size_t rt = (size_t)R_total, nc = (size_t)frame_cap * rt * 16;
+    DBuf dl, dpast, dn, dnt, ddone, dcodes, dnf, dpos0, dpos, dforced, dseed, dslots;
+    if (!dl.up(logits, rt * V * 4) || !dpast.up(past, rt * 32 * 4) || !dn.up(n_past, rt * 4) || !dnt.up(n_text, rt * 4) ||
+        !ddone.up(done, rt * 4) || !dcodes.up(codes, nc * 4) || !dnf.up(n_frames, rt * 4) || !dpos0.up(pos0, rt * 4) ||
+        !dpos.up(pos, rt * 4))
+        return -1000;
+    if (forced && !dforced.up(forced, nc * 4)) return -1000;
+    if (seed_ptr && !dseed.up(seed_ptr, rt * 8)) return -1000;
+    if (slots && !dslots.up(slots, rt * sizeof(SlotParams))) return -1000;
+    TalkerSampleArgs a;
+    a.logits = (const float*)dl.p;
+    a.V = V;
+    a.R = R;
+    a.row0 = row0;
+    a.R_total = R_total;
+    a.audio_vocab = audio_vocab;
+    a.eos = eos;
+    a.past = (int*)dpast.p;
+    a.n_past = (int*)dn.p;
+    a.n_text = (const int*)dnt.p;
+    a.done = (int*)ddone.p;
+    a.codes = (int*)dcodes.p;
+    a.n_frames = (int*)dnf.p;
+    a.frame_cap = frame_cap;
+    a.pos0 = (const int*)dpos0.p;
+    a.pos = (int*)dpos.p;
+    a.ignore_eos = ignore_eos;
+    a.max_frames = max_frames;
+    a.rep_penalty = rep_penalty;
+    a.temperature = temperature;
+    a.top_p = top_p;
+    a.top_k = top_k;
+    a.seed = seed;
+    a.seed_ptr = seed_ptr ? (const unsigned long long*)dseed.p : nullptr;
+    a.forced = forced ? (const int*)dforced.p : nullptr;
+    a.slots = slots ? (const SlotParams*)dslots.p : nullptr;
+    if (const int rc = launch_talker_sample(nullptr, a)) return rc;
+    Q3_HIP(hipDeviceSynchronize(), -1000);
+    Q3_HIP(hipMemcpy(past, dpast.p, rt * 32 * 4, hipMemcpyDeviceToHost), -1000);
+    Q3_HIP(hipMemcpy(n_past, dn.p, rt * 4, hipMemcpyDeviceToHost), -1000);
+    Q3_HIP(hipMemcpy(done, ddone.p, rt * 4, hipMemcpyDeviceToHost), -1000);
+    Q3_HIP(hipMemcpy(n_frames, dnf.p, rt * 4, hipMemcpyDeviceToHost), -1000);
+    Q3_HIP(hipMemcpy(pos, dpos.p, rt * 4, hipMemcpyDeviceToHost), -1000);
+    Q3_HIP(hipMemcpy(codes, dcodes.p, nc * 4, hipMemcpyDeviceToHost), -1000);
+    return 0;
+}
+
+// One launch_cp_argmax, state in and out on host arrays (layouts as in q3t_talker_sample_case).  epilogue 0: none;
+// 1: gather of next_table[V][H] (+ next_qkv[V][qkv_ld] -> qkv_out[R_total][qkv_ld] when non-null); 2: the feedback sum
+// over talker_emb[talker_vocab][H], cp_tables[n_groups][V][H] (one contiguous array) and pad[H] (or null).
+// h_out[R_total][H], ssq_out[R_total][H/16] and xh_out[R_total][H] (fp16 bits; with gamma[H], or both null) are row-major
+// in and out: the hook lays them out in fragment order on the device, so rows the launch leaves alone keep what the
+// caller put there.  Returns as q3t_talker_sample_case.
+extern "C" int q3t_cp_sample_case(const float* logits, int V, int R_total, int row0, int R, int group, int* codes,
+                                  const int* n_frames, int frame_cap, const int* forced, float temperature, int top_k,
+                                  unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
+                                  int epilogue, int H, const float* next_table, const float* next_qkv, int qkv_ld,
+                                  const float* gamma, const float* talker_emb, int talker_vocab, const float* cp_tables,
+                                  int n_groups, const float* pad, float* h_out, float* ssq_out, uint16_t* xh_out,
+                                  float* qkv_out) {
+    if (!logits || V <= 0 || R < 0 || row0 < 0 || row0 + R > R_total || frame_cap < 1 || group < 0 || group > 14 ||
+        epilogue < 0 || epilogue > 2)
+        return -2;
+    for (int r = row0; r < row0 + R; r++)
+        if (n_frames[r] < 0) return -2;
+    if (epilogue) {
+        if (H <= 0 || H % 32 || !h_out || !ssq_out || (xh_out != nullptr) != (gamma != nullptr)) return -2;
+        if (epilogue == 1 && (!next_table || (next_qkv && (!qkv_out || qkv_ld <= 0 || qkv_ld % 4)))) return -2;
+        if (epilogue == 2 && (!talker_emb || talker_vocab <= 0 || !cp_tables || n_groups <= group || n_groups > 15)) return -2;
+    }
+    const size_t rt = (size_t)R_total, nc = (size_t)frame_cap * rt * 16;
+    const int Rp = (R_total + 15) / 16 * 16;   // fragment order: blocks of 16 rows
+    DBuf dl, dcodes, dnf, dforced, dseed, dslots, dtab, dqkv, dgam, dtemb, dcpt, dcptp, dpad, dh, dssq, dxh, dqo;
+    if (!dl.up(logits, rt * V * 4) || !dcodes.up(codes, nc * 4) || !dnf.up(n_frames, rt * 4)) return -1000;
+    if (forced && !dforced.up(forced, nc * 4)) return -1000;
+    if (seed_ptr && !dseed.up(seed_ptr, rt * 8)) return -1000;
+    if (slots && !dslots.up(slots, rt * sizeof(SlotParams))) return -1000;
+    CpArgmaxArgs a;
+    a.logits = (const float*)dl.p;
+    a.V = V;
+    a.R = R;
+    a.H = H;
+    a.row0 = row0;
+    a.R_total = R_total;
+    a.group = group;
+    a.codes = (int*)dcodes.p;
+    a.n_frames = (const int*)dnf.p;
+    a.frame_cap = frame_cap;
+    a.temperature = temperature;
+    a.top_k = top_k;
+    a.seed = seed;
+    a.seed_ptr = seed_ptr ? (const unsigned long long*)dseed.p : nullptr;
+    a.forced = forced ? (const int*)dforced.p : nullptr;
+    a.slots = slots ? (const SlotParams*)dslots.p : nullptr;
+    std::vector<float> hh;
+    std::vector<uint16_t> hx;
+    if (epilogue) {
+        hh.assign((size_t)Rp * H, 0.f);
+        for (int r = 0; r < R_total; r++)
+            for (int k = 0; k < H; k++) hh[frag_idx_host(r, k, H)] = h_out[(size_t)r * H + k];
+        if (!dh.up(hh.data(), hh.size() * 4) || !dssq.up(ssq_out, rt * (H / 16) * 4)) return -1000;
+        a.h_out = (float*)dh.p;
+        a.ssq_out = (float*)dssq.p;
+        if (xh_out) {
+            hx.assign((size_t)Rp * H, 0);
+            for (int r = 0; r < R_total; r++)
+                for (int k = 0; k < H; k++) hx[frag_idx_host(r, k, H)] = xh_out[(size_t)r * H + k];
+            if (!dxh.up(hx.data(), hx.size() * 2) || !dgam.up(gamma, (size_t)H * 4)) return -1000;
+            a.xh_out = (half_t*)dxh.p;
+            a.gamma_next = (const float*)dgam.p;
+        }
+    }
+    if (epilogue == 1) {
+        if (!dtab.up(next_table, (size_t)V * H * 4)) return -1000;
+        a.next_table = (const float*)dtab.p;
+        if (next_qkv) {
+            if (!dqkv.up(next_qkv, (size_t)V * qkv_ld * 4) || !dqo.up(qkv_out, rt * qkv_ld * 4)) return -1000;
+            a.next_qkv = (const float*)dqkv.p;
+            a.qkv_out = (float*)dqo.p;
+            a.qkv_ld = qkv_ld;
+        }
+    } else if (epilogue == 2) {
+        const size_t tab = (size_t)V * H;
+        if (!dtemb.up(talker_emb, (size_t)talker_vocab * H * 4) || !dcpt.up(cp_tables, (size_t)n_groups * tab * 4)) return -1000;
+        std::vector<const float*> ptrs(n_groups);
+        for (int g = 0; g < n_groups; g++) ptrs[g] = (const float*)dcpt.p + (size_t)g * tab;
+        if (!dcptp.up(ptrs.data(), ptrs.size() * sizeof(const float*))) return -1000;
+        if (pad && !dpad.up(pad, (size_t)H * 4)) return -1000;
+        a.talker_emb = (const float*)dtemb.p;
+        a.talker_vocab = talker_vocab;
+        a.cp_tables = (const float* const*)dcptp.p;
+        a.n_groups = n_groups;
+        a.pad_embed = pad ? (const float*)dpad.p : nullptr;
+    }
+    if (const int rc = launch_cp_argmax(nullptr, a)) return rc;
+    Q3_HIP(hipDeviceSynchronize(), -1000);
+    Q3_HIP(hipMemcpy(codes, dcodes.p, nc * 4, hipMemcpyDeviceToHost), -1000);
+    if (epilogue) {
+        Q3_HIP(hipMemcpy(hh.data(), dh.p, hh.size() * 4, hipMemcpyDeviceToHost), -1000);
+        for (int r = 0; r < R_total; r++)
+            for (int k = 0; k < H; k++) h_out[(size_t)r * H + k] = hh[frag_idx_host(r, k, H)];
+        Q3_HIP(hipMemcpy(ssq_out, dssq.p, rt * (H / 16) * 4, hipMemcpyDeviceToHost), -1000);
+        if (xh_out) {
+            Q3_HIP(hipMemcpy(hx.data(), dxh.p, hx.size() * 2, hipMemcpyDeviceToHost), -1000);
+            for (int r = 0; r < R_total; r++)
+                for (int k = 0; k < H; k++) xh_out[(size_t)r * H + k] = hx[frag_idx_host(r, k, H)];
+        }
+        if (a.qkv_out) Q3_HIP(hipMemcpy(qkv_out, dqo.p, rt * qkv_ld * 4, hipMemcpyDeviceToHost), -1000);
+    }
+    return 0;
+}
+
 // ---- launch-boundary microbenchmark: a dependent chain of n small kernels, captured as a graph ----
 namespace {
 __global__ void chain_empty_kernel(float* buf) { (void)buf; }
