@@ -71,8 +71,9 @@ int q3e_start(void* e, int B, const float* prefix, const int32_t* n_rows, const 
               int ignore_eos, int max_frames);
 
 /* Generate up to n_frames more frames for the whole batch (returns early once every utterance
- * has finished; never steps past the max_frames given to q3e_start: 0 when none is left).  Returns the
- * number of frame steps executed, <0 on error. */
+ * has finished; never steps past the max_frames given to q3e_start: 0 when none is left; in a per-slot
+ * batch never past the text rows a live text slot has, see q3e_push_text).  Returns the number of frame
+ * steps executed, <0 on error. */
 int q3e_run(void* e, int n_frames);
 
 /* GPU time of the last q3e_run / q3e_start in milliseconds (HIP events on the engine's stream). */
@@ -132,13 +133,50 @@ typedef struct q3e_slot_params {
     int32_t cp_top_k;
     uint64_t seed;          /* the request's seed ... */
     int32_t utt;            /* ... and the utterance's index in its request: the draw stream is mix(seed, utt) */
-    int32_t reserved;       /* 0 */
+    int32_t reserved;       /* bit 0: a text slot (below); the other bits 0 */
 } q3e_slot_params;
 
 int q3e_open(void* e, int B, int ignore_eos);
 int q3e_admit(void* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
               const q3e_slot_params* params);
 int q3e_release(void* e, int n, const int32_t* slots);
+
+/* Text streamed into a running utterance, row by row (per-slot mode only).
+ *
+ * Layout (a recollection of the model's streaming mode, which the reference does not implement -- it pre-computes the
+ * pad row "for non-streaming feedback", tts_client.py:56; parity with the real model on real weights is NOT pinned, the
+ * arithmetic is: tests grade every frame against the CPU oracle fed the same rows): the prefix holds only the first text
+ * token (tfe_build_prefix_stream, 8 rows), and the feedback of frame f of the slot (f from its own start) adds, where
+ * tts_client.py:207-208 adds tts_pad, row f of the slot's text rows R = [T[1], .., T[n-1], E] (T = tfe_embed_text of the
+ * ids, E = tfe_tts_eos_embed) while f < n, and the pad row afterwards.
+ *
+ * q3e_text_reserve: call before q3e_open.  Allocates [max_batch][max_rows][hidden] f32 and the per-slot row counters
+ * (32 MiB at 32 x 256 x 1024); max_rows <= the max_frames of q3e_create (a row past the budget could never be
+ * consumed); 0 releases the reservation.  The pointers are part of the captured frame, so they are fixed here and
+ * admitting a text slot never recaptures; an engine that never calls this captures the frame it always did.  Refused
+ * while a text slot is live.
+ *
+ * A q3e_slot_params with bit 0 of `reserved` set admits a text slot: q3e_admit refuses it (<0, nothing changed) without
+ * a reservation; its n_text is ignored; prefix / n_rows are the streaming prefix, or any rows the caller likes.
+ *
+ * q3e_push_text: append n >= 0 rows ([n][hidden] f32) to the slot's text.  final != 0 ends the text.  Until then the
+ * slot's EOS logit is masked (as under ignore_eos) and its n_text is 0 (no boost, no forced EOS); the final push lifts
+ * the mask and sets n_text to n_text_total, so from the next sampled frame on the rules of
+ * llamacpp_talker_server.py:167-181 apply unchanged (a batch-wide ignore_eos still masks EOS for every slot).
+ * <0 with nothing written (the call can be retried): the slot is not a live text slot, a push after the final one,
+ * rows beyond the reservation, a non-finite value.
+ *
+ * A slot never runs ahead of its text: while a live slot's text is not final, q3e_run executes no step whose frame has
+ * no row yet -- it runs the steps every such slot has rows for and returns their number, which may be 0.  Row i is
+ * therefore always consumed at frame i: a slot's codes depend on its text and on nothing about arrival times.  A starved
+ * slot stalls the WHOLE batch (holding one row's logits, KV and counters inside the captured frame is deliberately not
+ * built): the host decides whether to wait, push, or release the slot.
+ *
+ * q3e_text_state: rows[b] = rows pushed to slot b (0: not a text slot), starved[b] = 1 when slot b is a live text slot
+ * the next step waits for.  Either pointer may be NULL.  0 ok / <0 error. */
+int q3e_text_reserve(void* e, int max_rows);
+int q3e_push_text(void* e, int slot, const float* rows, int n, int final, int n_text_total);
+int q3e_text_state(void* e, int32_t* rows /*[B]*/, int32_t* starved /*[B]*/);
 
 /* Talker hidden state of every utterance after the last executed step ([B][hidden]). */
 int q3e_get_hidden(void* e, float* out);

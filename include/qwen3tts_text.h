@@ -46,6 +46,16 @@ int tfe_build_prefix(void* h, const int32_t* text_token_ids, int n, const int32_
 /* The projected tts_pad row (tts_client.py:58-69 computes it once; q3e_set_pad_embed takes it). */
 int tfe_tts_pad_embed(void* h, float* out /*[hidden]*/);
 
+/* Text streamed into a running utterance (q3e_push_text, qwen3tts_engine.h).  The streaming prefix needs only the first
+ * text token: rows 0..6 of tfe_build_prefix (3 role rows, tts_pad + codec{nothink, think_bos, think_eos}, tts_bos +
+ * codec_pad), then first token + codec_bos = 8 rows; returns 8, <0 on error.  `special` as for tfe_build_prefix.  The
+ * rows that follow frame by frame are tfe_embed_text of tokens 1.. and, last, the projected tts_eos row.  This layout is
+ * a recollection of the model's streaming mode (the reference implements only the non-streaming one and names the gap,
+ * tts_client.py:56): same rows as the non-streaming prefix with the text moved out of it; parity with the model's own
+ * streaming mode on real weights is not pinned. */
+int tfe_build_prefix_stream(void* h, int32_t first_token_id, const int32_t* special, float* out /*[8][hidden]*/);
+int tfe_tts_eos_embed(void* h, float* out /*[hidden]*/);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,24 @@ row's f32 sums depend on the row count of the pass), every utterance is prefille
 tiles depend on the rows of the pass), and utterance u of a request with seed s draws from the stream mix(s, u), keyed by
 (stream, frame, group) and not by the slot (include/qwen3tts_engine.h).
 
+Streamed TEXT (`--concurrent` only; the request carries "text_stream": true, which needs "stream": true and exactly one
+utterance, else -2): the request's texts / token_ids hold only the first piece of the text (at least one token), and the
+client goes on sending the rest on the same connection, as records
+
+              i32 1, i32 n, n UTF-8 bytes (cut anywhere)      more text, tokenised by the server's incremental tokeniser
+              i32 2, i32 n, i32[n]                             more token ids
+              i32 0, i32 0                                     end of text
+
+while the audio records already come back.  The utterance runs in a text slot of the frame loop (include/qwen3tts_engine.h,
+q3e_push_text): its prefix holds the first token, every later token is projected (one token per call, so a row does not
+depend on how the text was cut) and added to the feedback of one frame, the tts_eos row follows the last token.  Before each
+check the engine thread reads, without blocking, what has arrived and pushes the rows.  A slot never runs ahead of its text,
+and a starved slot stalls the WHOLE batch: when a check runs no frame because a text slot waits for a row, the engine thread
+polls the starving requests' connections for at most --text_wait_ms (default 200); a client that stays connected but does not
+send its text in that time fails its own request (-2, its slot is released) -- the rule a client that stops reading already
+gets from --send_timeout.  The reply's codes and PCM depend on the text and not on how it was cut or when it arrived.  The
+text may not have more tokens than the request's max_tokens (a row per frame).
+
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
 vocoder then launches one persistent workgroup per compute unit (voc_set_max_workgroups(-1)), which leaves the frame loop's
@@ -79,7 +97,7 @@ class BatchSynthesisServer:
     def __init__(self, model_path, vocoder_path, socket_path="/tmp/qwen3_batch.sock", max_batch=32, n_ctx=512,
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
-                 cp_top_k=None, check_every=8, send_timeout=30.0):
+                 cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens = socket_path, max_batch, max_tokens
@@ -92,6 +110,7 @@ class BatchSynthesisServer:
         self.max_queue = int(max_queue) if max_queue else 16 * max_batch
         self.check_every = int(check_every)
         self.send_timeout = float(send_timeout)
+        self.text_wait_ms = float(text_wait_ms)
         self.sched = None
         # utterances one request may queue (the server is single-threaded: an unbounded request holds it indefinitely)
         self.max_request = int(max_request) if max_request else 8 * max_batch
@@ -313,11 +332,40 @@ class BatchSynthesisServer:
     def _prepare(self, msg):
         """--concurrent, accept side: a request -> its utterances in queue order as (request index, prefix, n_text,
         SlotParams); raises on anything malformed, before any of it is queued."""
-        ids = self._token_ids(msg)
         request_vocoder_arithmetic(msg)      # (checks "vocoder" too)
         base = request_slot_params(msg, self.defaults, self.max_tokens)
+        if msg.get("text_stream"):
+            return [self._prepare_text_stream(msg, base)]
+        ids = self._token_ids(msg)
         prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames)
         return [(i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i)) for i in order]
+
+    def _prepare_text_stream(self, msg, base):
+        """A "text_stream" request -> its one utterance as (0, streaming prefix, 0, SlotParams of a text slot, TextFeed)."""
+        from .frontend import text_stream_rows
+        if msg.get("stream") is not True:
+            raise ValueError('"text_stream" needs "stream": true')
+        by_ids = msg.get("token_ids") is not None
+        pieces = msg["token_ids"] if by_ids else msg.get("texts", [])
+        if not isinstance(pieces, list) or len(pieces) != 1:
+            raise ValueError('a "text_stream" request carries exactly one utterance')
+        encoder = None
+        if by_ids:
+            first = [int(x) for x in pieces[0]]
+        else:
+            if self.tokenizer is None:
+                raise RuntimeError("no tokenizer configured (--tokenizer DIR) and the request has no token_ids")
+            encoder = self.tokenizer.incremental()
+            first = encoder.feed(pieces[0])
+        if not first:
+            raise ValueError('the first piece of a "text_stream" request must give at least one token')
+        if 8 + base.max_frames > self.n_ctx:
+            raise ValueError("prefix + max_tokens exceed n_ctx")
+        tokeniser = self.tokenizer
+        feed = TextFeed(lambda ids, final=False: text_stream_rows(self.front, ids, final), encoder,
+                        None if tokeniser is None else tokeniser.incremental, first[1:], 1)
+        params = dataclasses.replace(base, utt=0, text_stream=True)
+        return (0, self.front.build_prefix_stream(first[0]), 0, params, feed)
 
     def _finish(self, conn, cs, t0, vocoder="walk", arithmetic="exact"):
         """Worker side of the pipelined mode: vocode, reply on the request's own connection, close it."""
@@ -360,6 +408,8 @@ class BatchSynthesisServer:
                     continue
                 t0 = time.time()
                 vocoder, arithmetic = request_vocoder(msg), request_vocoder_arithmetic(msg)
+                if msg.get("text_stream"):
+                    raise ValueError('"text_stream" needs a --concurrent server')
                 if msg.get("stream"):
                     # streamed reply: the worker writes every record and closes the connection
                     ids = self._token_ids(msg)
@@ -398,9 +448,10 @@ class BatchSynthesisServer:
         if self._vstream is None:
             self._vstream = self.voc.stream(self.max_batch)
         self._lib.voc_set_max_workgroups(-1)     # the vocoder runs beside the frame loop: one workgroup per CU
+        self.eng.reserve_text(self.max_tokens)   # before the scheduler opens the batch: a row per frame of every slot
         self.sched = ConcurrentScheduler(self.eng, self.max_batch, self.max_queue, self._prepare, self._finish, self._push,
                                          self._close_stream, self._send_error, check_every=self.check_every,
-                                         send_timeout=self.send_timeout)
+                                         send_timeout=self.send_timeout, text_wait_ms=self.text_wait_ms)
         self.sched.start()
         print(f"Batch synthesis server listening on {self.socket_path} (--concurrent: {self.max_batch} slots shared by every "
               f"request, up to {self.max_queue} queued utterances)")
@@ -446,6 +497,61 @@ class BatchSynthesisServer:
         self.eng.destroy()
 
 
+class TextFeed:
+    """The text of one "text_stream" request on its way into the frame loop: what the client has sent is read without
+    blocking (poll), turned into token ids (text through the incremental tokeniser) and projected; take() hands the rows that
+    are ready to the engine thread, which is the only caller.  project(ids, final) -> rows [n (+ 1: the tts_eos row)][hidden]."""
+
+    def __init__(self, project, encoder, new_encoder, first_ids, n_tokens):
+        self._project, self._encoder, self._new_encoder = project, encoder, new_encoder
+        self._by_text = encoder is not None
+        self._parser = P.TextRecordParser()
+        self._rows = [project(first_ids)] if len(first_ids) else []
+        self.n_tokens = int(n_tokens) + len(first_ids)     # text tokens so far (the final push's n_text)
+        self.ended = False                                  # the end-of-text record has arrived
+        self.final_pushed = False
+
+    def _ids(self, ids, final=False):
+        self.n_tokens += len(ids)
+        if len(ids) or final:
+            self._rows.append(self._project([int(t) for t in ids], final))
+
+    def records(self, data):
+        for kind, body in self._parser.feed(data):
+            if kind == P.TEXT_IDS:
+                if self._by_text:
+                    raise ValueError("token ids after text: the held-back tail of the text could not be placed")
+                self._ids(body)
+            elif kind == P.TEXT_BYTES:
+                if self._encoder is None:
+                    if self._new_encoder is None:
+                        raise RuntimeError("no tokenizer configured (--tokenizer DIR) for a text record")
+                    self._encoder = self._new_encoder()      # ids first, text from here on: a fresh piece of text
+                    self._by_text = True
+                self._ids(self._encoder.feed(body))
+            else:
+                self._ids(self._encoder.finish() if self._encoder is not None else [], final=True)
+                self.ended = True
+
+    def poll(self, conn):
+        """Reads what has arrived.  -> False once the client has closed its sending side before the end-of-text record."""
+        while not self.ended:
+            try:
+                data = conn.recv(65536, socket.MSG_DONTWAIT)
+            except (BlockingIOError, InterruptedError):
+                return True
+            if not data:
+                return False
+            self.records(data)
+        return True
+
+    def take(self):
+        """-> (rows [n][hidden] to push now, whether they end the text)."""
+        rows, self._rows = self._rows, []
+        final = self.ended and not self.final_pushed
+        return (np.concatenate(rows) if rows else None), final
+
+
 class _Request:
     """A request of --concurrent in flight: its connection and what has come back so far."""
 
@@ -456,6 +562,7 @@ class _Request:
         self.codes = [None] * self.n            # per request index
         self.state = {"failed": False, "n": self.n, "frames": 0}   # the push worker's view (BatchSynthesisServer._push)
         self.gone = False                       # the client went away or the request failed: its slots are released
+        self.feed = next((it[4] for it in items if len(it) > 4), None)   # TextFeed of a "text_stream" request
 
 
 class ConcurrentScheduler:
@@ -469,10 +576,16 @@ class ConcurrentScheduler:
     A client is gone once it has closed its connection (POLLHUP); a client that only shuts down its sending side after the
     request (shutdown(SHUT_WR)) still gets its reply.  Every write to a request's connection is bounded by send_timeout
     seconds (SO_SNDTIMEO): a client that stays connected but stops reading fails its own request -- the writer's error marks
-    it failed, the engine then releases its slots -- instead of holding the one worker, and with it every other request."""
+    it failed, the engine then releases its slots -- instead of holding the one worker, and with it every other request.
+
+    A "text_stream" request (an item with a fifth entry, its TextFeed) runs in a text slot: before every check the engine
+    thread reads what its client has sent and pushes the rows (eng.push_text); a check that runs no frame because such a slot
+    waits for its text (eng.text_state) polls the starving requests' connections for at most text_wait_ms, after which a
+    request that has still sent nothing fails (-2) and its slot is released -- the stall is the whole batch's, so it is
+    bounded the same way a stalled reader is."""
 
     def __init__(self, eng, max_batch, max_queue, prepare, reply, push, close_stream, send_error, check_every=8,
-                 send_timeout=30.0):
+                 send_timeout=30.0, text_wait_ms=200.0):
         from concurrent.futures import ThreadPoolExecutor
         self.eng, self.B, self.max_queue, self.check_every = eng, int(max_batch), int(max_queue), int(check_every)
         self._prepare, self._reply, self._push, self._close_stream, self._send_error = prepare, reply, push, close_stream, send_error
@@ -484,6 +597,8 @@ class ConcurrentScheduler:
         self.alive = True                       # False once the engine thread has stopped on an error
         self.frame_steps = 0                    # frame steps the engine has run
         self.send_timeout = float(send_timeout)
+        self.text_wait_ms = float(text_wait_ms)
+        self.starved_checks = 0                 # checks that ran no frame because a text slot waited for its text
 
     # ---- accept side ----
     def submit(self, conn, msg, t0=None):
@@ -547,6 +662,47 @@ class ConcurrentScheduler:
             req.gone = True
             self._pool.submit(req.conn.close)
 
+    def _fail(self, req, why):
+        """Engine side: a request that cannot go on gets -2 now; its slots are released at this check."""
+        if not req.gone:
+            print(f"Error: {why}")
+            req.state["failed"] = True
+            self._pool.submit(self._send_error, req.conn)
+            self._drop(req)
+
+    def _feed_text(self, owner):
+        """Engine side, before a check: read what the text-stream clients have sent and push the rows that are ready."""
+        for b, o in enumerate(owner):
+            req = o[0] if o is not None else None
+            if req is None or req.feed is None or req.gone or req.feed.final_pushed:
+                continue
+            try:
+                if not req.feed.poll(req.conn):
+                    raise ValueError("the client closed its sending side before the end of its text")
+                rows, final = req.feed.take()
+                if rows is not None or final:
+                    self.eng.push_text(b, rows if rows is not None else np.zeros((0, 1024), np.float32), final=final,
+                                       n_text=req.feed.n_tokens)
+                    req.feed.final_pushed = final
+            except Exception as e:     # a malformed record, an unknown token, more rows than frames: this request only
+                self._fail(req, f"text stream: {e}")
+
+    def _wait_for_text(self, owner):
+        """Engine side, after a check that ran no frame: if text slots starve, wait (at most text_wait_ms) until one of their
+        clients has sent something, and fail those that are still silent after it.  -> True if the check was a starved one."""
+        _, starved = self.eng.text_state()
+        waiting = {id(owner[b][0]): owner[b][0] for b in range(self.B) if starved[b] and owner[b] is not None and not owner[b][0].gone}
+        if not waiting:
+            return False
+        self.starved_checks += 1
+        p = select.poll()
+        for req in waiting.values():
+            p.register(req.conn.fileno(), select.POLLIN)
+        if not p.poll(self.text_wait_ms):
+            for req in waiting.values():
+                self._fail(req, f"text stream: no text for {self.text_wait_ms:.0f} ms while the frame loop waited for it")
+        return True
+
     def _engine_main(self):
         owner = [None] * self.B                 # (request, utt) of each slot
         try:
@@ -595,8 +751,12 @@ class ConcurrentScheduler:
                     pushed[b] = 0
                     if req.stream:
                         resets[id(req)].append(b)
+            text_live = any(o is not None and o[0].feed is not None for o in owner)
+            if text_live:
+                self._feed_text(owner)
             ran = eng.run(self.check_every)
             self.frame_steps += ran
+            waited = ran == 0 and text_live and self._wait_for_text(owner)
             done, per = eng.done()
             # clients that went away: their slots go idle now
             live = {id(o[0]): o[0] for o in owner if o is not None}
@@ -611,7 +771,7 @@ class ConcurrentScheduler:
             fin = [b for b in range(B) if owner[b] is not None and done[b]]
             streamed = [b for b in range(B) if owner[b] is not None and owner[b][0].stream]
             if not fin and not streamed:
-                if ran == 0 and not gone and not take:
+                if ran == 0 and not gone and not take and not waited:
                     raise RuntimeError("the engine ran no frame and no utterance ended")
                 continue
             codes, _ = eng.codes()
@@ -713,13 +873,16 @@ def request_slot_params(msg, defaults, max_tokens_cap):
 
 def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False, temperature=None,
                        top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None,
-                       vocoder_arithmetic=None) -> bytes:
+                       vocoder_arithmetic=None, text_stream=False) -> bytes:
     """The request of the batched protocol; the sampling keys (honoured by --concurrent), the vocoder mode ("walk" /
-    "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given."""
+    "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given.  text_stream: the
+    request carries only the first piece of its one utterance's text; the rest follows as text records."""
     import json
     msg = {"language": language}
     if stream:
         msg["stream"] = True
+    if text_stream:
+        msg["text_stream"] = True
     if token_ids is not None:
         msg["token_ids"] = [[int(t) for t in ids] for ids in token_ids]
     else:
@@ -817,6 +980,47 @@ def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="r
         s.close()
 
 
+def synthesize_text_stream(socket_path, pieces, language="russian", max_tokens=None, vocoder=None, vocoder_arithmetic=None,
+                           **sampling):
+    """Client side of a "text_stream" request (--concurrent servers): `pieces` is an iterable of the text's pieces as they
+    become available -- str / bytes (UTF-8, cut anywhere; the server tokenises) or sequences of token ids.  The first piece
+    goes out with the request (it must give at least one token), the others as text records from a sender thread that walks
+    the iterable, then the end-of-text record.  Yields the records of synthesize_batch_stream, utterance 0."""
+    it = iter(pieces)
+    first = next(it)
+    as_text = isinstance(first, (str, bytes, bytearray))
+    if isinstance(first, (bytes, bytearray)):
+        raise TypeError("the first piece goes into the JSON request: a str, or a sequence of token ids")
+    s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
+    s.connect(socket_path)
+    sender_error = []
+
+    def sender():
+        try:
+            for piece in it:
+                text = isinstance(piece, (str, bytes, bytearray))
+                s.sendall(P.pack_text_record(P.TEXT_BYTES if text else P.TEXT_IDS, piece))
+            s.sendall(P.pack_text_record(P.TEXT_END))
+        except Exception as e:      # noqa: BLE001 -- the reader sees the closed connection or the server's -2
+            sender_error.append(e)
+
+    th = threading.Thread(target=sender, daemon=True)
+    try:
+        s.sendall(pack_batch_request([first] if as_text else None, None if as_text else [list(first)], language, max_tokens,
+                                     stream=True, vocoder=vocoder, vocoder_arithmetic=vocoder_arithmetic, text_stream=True,
+                                     **sampling))
+        th.start()
+        while True:
+            rec = read_stream_record(s)
+            if rec[0] == "done":
+                return
+            yield rec
+    finally:
+        s.close()
+        if th.is_alive():
+            th.join(timeout=5)
+
+
 def synthesize_batch(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, **sampling):
     """Client side of the batched request.  sampling: the optional keys of pack_batch_request (vocoder and vocoder_arithmetic
     among them)."""
@@ -852,11 +1056,13 @@ def main():
     ap.add_argument("--check_every", type=int, default=8, help="--concurrent: frames between two admissions")
     ap.add_argument("--send_timeout", type=float, default=30.0,
                     help="--concurrent: seconds one write to a client may block before its request fails")
+    ap.add_argument("--text_wait_ms", type=float, default=200.0,
+                    help="--concurrent: milliseconds the frame loop waits for a text-stream client's text before its request fails")
     a = ap.parse_args()
     srv = BatchSynthesisServer(a.model, a.vocoder, a.socket, a.max_batch, a.n_ctx, a.max_tokens, a.temperature, a.top_k,
                                a.cp_temperature, a.tokenizer, a.seed, pipeline=a.pipeline, concurrent=a.concurrent,
                                max_queue=a.max_queue, top_p=a.top_p, cp_top_k=a.cp_top_k, check_every=a.check_every,
-                               send_timeout=a.send_timeout)
+                               send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms)
     try:
         srv.serve()
     finally:

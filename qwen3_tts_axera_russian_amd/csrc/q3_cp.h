@@ -14,6 +14,9 @@ struct CpFrameIO {
     half_t* fb_xh = nullptr;          // pre-scaled GEMM input of the talker's first layer ...
     const float* fb_gamma = nullptr;  // ... and that layer's input norm weight
     const float* pad_embed = nullptr;
+    const float* text_rows = nullptr;   // per-slot text rows standing where the pad stands (see CpArgmaxArgs); null = none
+    const int* text_avail = nullptr;
+    int text_cap = 0;
     // sampling of the 15 groups (code_predictor_server.py:87-92): temperature <= 1e-6 = arg-max
     float temperature = 0.f;
     int top_k = 50;

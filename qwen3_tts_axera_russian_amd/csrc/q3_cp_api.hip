@@ -144,6 +144,9 @@ int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const C
             x.talker_vocab = c.talker_vocab;
             x.cp_tables = m.d_cp_emb_ptrs;
             x.pad_embed = io.pad_embed;
+            x.text_rows = io.text_rows;
+            x.text_avail = io.text_avail;
+            x.text_cap = io.text_cap;
             x.n_groups = G;
             x.h_out = io.fb_h;
             x.ssq_out = io.fb_ssq;

@@ -62,7 +62,25 @@ struct Engine {
     SlotParams* d_slots = nullptr;          // [max_batch]
     std::vector<int> h_budget, h_age;       // h_age[b] < 0: the slot holds no utterance
     std::vector<char> h_live;               // admitted and neither released nor known to have ended
+    // text streamed into running utterances (q3e_text_reserve / q3e_push_text): row f of a text slot's rows is added to
+    // the feedback of its frame f where the pad stands.  The host writes rows and counters on s between the launches.
+    float* d_text = nullptr;                // [max_batch][text_cap][hidden]
+    int* d_tavail = nullptr;                // [max_batch] rows pushed (0: not a text slot)
+    int text_cap = 0;
+    std::vector<SlotParams> h_sp;           // the slots' device entries (the final push rewrites the flags)
+    std::vector<int> h_trows;               // rows pushed per slot
+    std::vector<char> h_text, h_tfinal;     // the slot holds a text utterance / its text has ended
+    int up_i[2] = {0, 0};                   // staging of one-word uploads (synchronised before reuse)
 };
+
+// steps a per-slot batch may take before a live text slot whose text has not ended would need a row it does not have
+int text_room(const Engine* e) {
+    int room = e->max_frames;
+    for (int b = 0; b < e->B; b++)
+        if (e->h_live[b] && e->h_text[b] && !e->h_tfinal[b] && e->h_age[b] < e->h_budget[b])
+            room = std::min(room, e->h_trows[b] - e->h_age[b]);
+    return room;
+}
 
 // splitmix64 finaliser of (seed + golden * k): the stream derivations of this file
 unsigned long long mix_seed(unsigned long long seed, unsigned long long k, unsigned long long golden) {
@@ -144,6 +162,11 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     io.fb_xh = e->wt.xh;
     io.fb_gamma = m.talker.L[0].in_ln;
     io.pad_embed = e->d_pad;
+    if (e->slot_mode && e->d_text) {
+        io.text_rows = e->d_text;
+        io.text_avail = e->d_tavail;
+        io.text_cap = e->text_cap;
+    }
     io.temperature = e->c_temp;
     io.top_k = e->c_top_k;
     io.seed = e->seed ^ 0x5851F42D4C957F2Dull;
@@ -234,7 +257,8 @@ void q3e_free(void* ee) {
     work_free(e->wt);
     work_free(e->wc);
     void* ps[] = {e->d_tiles, e->d_slot, e->d_pos,  e->d_iota,   e->d_past,    e->d_npast, e->d_ntext, e->d_done,
-                  e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots};
+                  e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots,
+                  e->d_text, e->d_tavail};
     for (void* p : ps)
         if (p) hipFree(p);
     if (e->h_done) hipHostFree(e->h_done);
@@ -552,6 +576,7 @@ int q3e_run(void* ee, int n_frames) {
         room = 0;
         for (int b = 0; b < e->B; b++)
             if (e->h_live[b]) room = std::max(room, e->h_budget[b] - e->h_age[b]);
+        room = std::min(room, text_room(e));   // a slot never runs ahead of its text: a starved slot stalls the batch
     }
     if (room <= 0) return 0;
     if (n_frames > room) n_frames = room;
@@ -738,6 +763,11 @@ int q3e_open(void* ee, int B, int ignore_eos) {
     e->h_budget.assign(B, 0);
     e->h_age.assign(B, -1);
     e->h_live.assign(B, 0);
+    e->h_sp.assign(B, SlotParams());
+    e->h_trows.assign(B, 0);
+    e->h_text.assign(B, 0);
+    e->h_tfinal.assign(B, 0);
+    if (e->d_tavail) Q3_HIP(hipMemsetAsync(e->d_tavail, 0, sizeof(int) * e->max_batch, e->s), -1);
     if (e->forced_on) {
         e->forced_on = false;
         for (auto& g : e->graph) g.reset();
@@ -798,12 +828,21 @@ int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const 
         sp[u].c_top_k = p.cp_top_k;
         sp[u].seed = mix_seed(p.seed, (unsigned long long)(uint32_t)p.utt + 1ull, 0x9E3779B97F4A7C15ull);   // mix(seed, utt)
         sp[u].no_row = 1;
+        if (p.reserved & 1) {
+            if (!e->d_text) {
+                Q3_LOG("q3e_admit: utterance %d is a text slot, but no text rows are reserved (q3e_text_reserve)", u);
+                return -1;
+            }
+            sp[u].flags = 3;   // a text slot; EOS masked until the final push
+        }
     }
+    static const int32_t zero = 0;
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     Q3_HIP(hipEventRecord(e->ev0, e->s), -1);
     for (int u = 0; u < n; u++) {
-        if (clear_slot(e, ids[u], n_rows + u, n_text + u)) return -1;
+        if (clear_slot(e, ids[u], n_rows + u, sp[u].flags ? &zero : n_text + u)) return -1;   // a text slot's n_text comes with its final push
         Q3_HIP(hipMemcpyAsync(e->d_slots + ids[u], &sp[u], sizeof(SlotParams), hipMemcpyHostToDevice, e->s), -1);
+        if (e->d_tavail) Q3_HIP(hipMemsetAsync(e->d_tavail + ids[u], 0, sizeof(int), e->s), -1);
     }
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     // one prefill per utterance: the ragged prefill's tiles follow the rows of its pass, so sharing a pass with another
@@ -822,6 +861,102 @@ int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const 
         e->h_budget[ids[u]] = sp[u].max_frames;
         e->h_age[ids[u]] = 0;
         e->h_live[ids[u]] = 1;
+        e->h_sp[ids[u]] = sp[u];
+        e->h_trows[ids[u]] = 0;
+        e->h_text[ids[u]] = sp[u].flags ? 1 : 0;
+        e->h_tfinal[ids[u]] = 0;
+    }
+    return 0;
+}
+
+int q3e_text_reserve(void* ee, int max_rows) {
+    Engine* e = (Engine*)ee;
+    if (!e || max_rows < 0 || max_rows > e->max_frames) {
+        if (e) Q3_LOG("q3e_text_reserve: %d rows are outside 0..max_frames=%d", max_rows, e->max_frames);
+        return -1;
+    }
+    if (e->slot_mode)
+        for (int b = 0; b < e->B; b++)
+            if (e->h_live[b] && e->h_text[b]) {
+                Q3_LOG("q3e_text_reserve: slot %d holds a live text utterance", b);
+                return -1;
+            }
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    if (max_rows == e->text_cap) return 0;
+    for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointers
+    if (e->d_text) hipFree(e->d_text);
+    if (e->d_tavail) hipFree(e->d_tavail);
+    e->d_text = nullptr;
+    e->d_tavail = nullptr;
+    e->text_cap = 0;
+    if (max_rows == 0) return 0;
+    const size_t n = (size_t)e->max_batch * max_rows * e->m->cfg.hidden;
+    if (hipMalloc((void**)&e->d_text, sizeof(float) * n) != hipSuccess ||
+        hipMalloc((void**)&e->d_tavail, sizeof(int) * e->max_batch) != hipSuccess) {
+        Q3_LOG("q3e_text_reserve: allocation of %zu bytes failed", sizeof(float) * n);
+        if (e->d_text) hipFree(e->d_text);
+        e->d_text = nullptr;
+        e->d_tavail = nullptr;
+        return -1;
+    }
+    Q3_HIP(hipMemsetAsync(e->d_text, 0, sizeof(float) * n, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_tavail, 0, sizeof(int) * e->max_batch, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    e->text_cap = max_rows;
+    return 0;
+}
+
+int q3e_push_text(void* ee, int slot, const float* rows, int n, int final, int n_text_total) {
+    Engine* e = (Engine*)ee;
+    if (!e || !e->slot_mode || !e->d_text || slot < 0 || slot >= e->B || n < 0 || (n > 0 && !rows)) return -1;
+    if (!e->h_text[slot] || !e->h_live[slot]) {
+        Q3_LOG("q3e_push_text: slot %d holds no live text utterance", slot);
+        return -1;
+    }
+    if (e->h_tfinal[slot]) {
+        Q3_LOG("q3e_push_text: the text of slot %d has ended", slot);
+        return -1;
+    }
+    if (e->h_trows[slot] + n > e->text_cap) {
+        Q3_LOG("q3e_push_text: slot %d: %d + %d rows exceed the reservation of %d", slot, e->h_trows[slot], n, e->text_cap);
+        return -1;
+    }
+    if (final && n_text_total < 0) return -1;
+    const int H = e->m->cfg.hidden;
+    for (size_t i = 0; i < (size_t)n * H; i++)
+        if (!std::isfinite(rows[i])) {
+            Q3_LOG("q3e_push_text: slot %d: row %d holds a non-finite value", slot, (int)(i / H));
+            return -1;
+        }
+    // the rows first, then the counter that makes them visible; q3e_run has synchronised, so no frame is in flight
+    if (n > 0)
+        Q3_HIP(hipMemcpyAsync(e->d_text + ((size_t)slot * e->text_cap + e->h_trows[slot]) * H, rows, sizeof(float) * (size_t)n * H,
+                              hipMemcpyHostToDevice, e->s), -1);
+    e->up_i[0] = e->h_trows[slot] + n;
+    Q3_HIP(hipMemcpyAsync(e->d_tavail + slot, &e->up_i[0], sizeof(int), hipMemcpyHostToDevice, e->s), -1);
+    SlotParams sp = e->h_sp[slot];
+    if (final) {   // the reference's EOS rules from the next sampled frame on: mask lifted, n_text known
+        sp.flags = 1;
+        e->up_i[1] = n_text_total;
+        Q3_HIP(hipMemcpyAsync(e->d_slots + slot, &sp, sizeof(SlotParams), hipMemcpyHostToDevice, e->s), -1);
+        Q3_HIP(hipMemcpyAsync(e->d_ntext + slot, &e->up_i[1], sizeof(int), hipMemcpyHostToDevice, e->s), -1);
+    }
+    Q3_HIP(hipStreamSynchronize(e->s), -1);   // the caller's rows (and the locals) are their own again on return
+    e->h_trows[slot] += n;
+    if (final) {
+        e->h_sp[slot] = sp;
+        e->h_tfinal[slot] = 1;
+    }
+    return 0;
+}
+
+int q3e_text_state(void* ee, int32_t* rows, int32_t* starved) {
+    Engine* e = (Engine*)ee;
+    if (!e || !e->slot_mode || e->B <= 0) return -1;
+    for (int b = 0; b < e->B; b++) {
+        const bool waits = e->h_live[b] && e->h_text[b] && !e->h_tfinal[b] && e->h_age[b] < e->h_budget[b];
+        if (rows) rows[b] = e->h_text[b] ? e->h_trows[b] : 0;
+        if (starved) starved[b] = waits && e->h_trows[b] <= e->h_age[b];
     }
     return 0;
 }

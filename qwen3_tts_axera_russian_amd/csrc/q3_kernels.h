@@ -127,7 +127,7 @@ struct SlotParams {
     int c_top_k = 0;
     unsigned long long seed = 0;   // the row's draw stream
     int no_row = 1;                // 1: the draw key is (seed, frame, group), without the row index
-    int pad_ = 0;
+    int flags = 0;                 // bit 0: a text slot (its feedback adds text_rows, see CpArgmaxArgs); bit 1: its EOS is masked
 };
 
 // Talker sampling (llamacpp_talker_server.py:163-206, greedy form).
@@ -196,6 +196,13 @@ struct CpArgmaxArgs {
     const unsigned long long* seed_ptr = nullptr;  // device array [rows] overriding `seed` (one stream per slot)
     const int* forced = nullptr;                   // teacher forcing (tests), see TalkerSampleArgs
     const SlotParams* slots = nullptr;             // per-slot mode: temperature, top-k, draw key of row r (see TalkerSampleArgs)
+    // (last, so that the fields above keep their kernarg offsets)
+    // per-slot mode, text streamed into the utterance (q3e_text_reserve; null: none): the row added last to the feedback
+    // of frame f of row r is text_rows[r][f] while f < text_avail[r] (<= text_cap), else pad_embed.  Both arrays are
+    // written by the host between launches, never by a kernel of the same launch.
+    const float* text_rows = nullptr;   // f32 [R_total][text_cap][H]
+    const int* text_avail = nullptr;    // [R_total]
+    int text_cap = 0;
 };
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a);
 

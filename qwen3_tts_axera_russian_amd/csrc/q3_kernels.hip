@@ -1974,12 +1974,14 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
     const bool was_done = uniform_load(a.done + r) != 0;
     float temperature = a.temperature, top_p = a.top_p;
     int top_k = a.top_k, max_frames = a.max_frames;
+    int slot_flags = 0;   // SLOTS only (bit 1: the row's EOS is masked -- a text slot before its final push)
     if constexpr (SLOTS) {
         const SlotParams sp = uniform_slot(a.slots, r);
         temperature = sp.t_temp;
         top_p = sp.t_top_p;
         top_k = sp.t_top_k;
         max_frames = sp.max_frames;
+        slot_flags = sp.flags;
     }
     if (threadIdx.x == 0) nwin = np < 30 ? np : 30;
     if (threadIdx.x < 30 && threadIdx.x < np) {
@@ -2012,7 +2014,7 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
         float l = nan_as_inf(a.logits[(size_t)r * a.V + v]);
         if (v >= a.audio_vocab && v != a.eos) l = -1e10f;
         if (v == a.eos) {
-            if (a.ignore_eos) l = -1e10f;
+            if (a.ignore_eos || (SLOTS && (slot_flags & 2))) l = -1e10f;
             else if (nt > 0 && progress > 0.8) l += boost;
         }
         bool rep = false;
@@ -2040,7 +2042,7 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
     }
     if (threadIdx.x == 0) {
         int code = bidx;
-        if (force_eos && !a.ignore_eos) code = a.eos;
+        if (force_eos && !a.ignore_eos && !(SLOTS && (slot_flags & 2))) code = a.eos;
         bool fin = was_done || code == a.eos || code >= a.audio_vocab || (max_frames > 0 && np >= max_frames);
         const int f = a.n_frames[r];
         // per-slot batches live as long as the server: an ended row's counter stops one past the codes array (frame_cap + 1,
@@ -2138,7 +2140,8 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     if constexpr (SLOTS)
         Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
                       "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
-                      "s"(a.talker_emb), "s"(a.slots), "s"(a.forced), "s"(a.next_qkv), "s"(a.qkv_out), "s"(a.qkv_ld));
+                      "s"(a.talker_emb), "s"(a.slots), "s"(a.forced), "s"(a.next_qkv), "s"(a.qkv_out), "s"(a.qkv_ld),
+                      "s"(a.text_rows), "s"(a.text_avail), "s"(a.text_cap));
     else
         Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
                       "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
@@ -2158,10 +2161,12 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     const int nf_r = uniform_load(a.n_frames + r);   // independent of the arg-max: a scalar load beside the logits' vector loads
     float temperature = a.temperature;
     int top_k = a.top_k;
+    int text_avail = 0;   // rows of streamed text the row has (feedback launch of an engine with a text reservation only)
     if constexpr (SLOTS) {
         const SlotParams sp = uniform_slot(a.slots, r);
         temperature = sp.c_temp;
         top_k = sp.c_top_k;
+        if (a.talker_emb && a.text_rows) text_avail = uniform_load(a.text_avail + r);
     }
     Q3_PH(0);
     {
@@ -2238,7 +2243,12 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     if (fz && fz[1 + a.group] >= 0) bidx = fz[1 + a.group];   // teacher forcing (tests): continue with the forced id
     Q3_PH(2);
     if (a.talker_emb) {
-        feedback_row(fc, r, a.talker_emb, a.talker_vocab, a.cp_tables, a.V, a.n_groups, a.pad_embed,
+        // text slot: row f of the slot's text stands where the pad stands (f from the slot's own start, before the clamps
+        // above; f < avail <= text_cap keeps the index inside the buffer, also for ended rows past frame_cap).  Uniform.
+        const float* last = a.pad_embed;
+        if constexpr (SLOTS)
+            if (nf_r >= 1 && nf_r - 1 < text_avail) last = a.text_rows + ((size_t)r * a.text_cap + (nf_r - 1)) * a.H;
+        feedback_row(fc, r, a.talker_emb, a.talker_vocab, a.cp_tables, a.V, a.n_groups, last,
                      a.h_out, a.ssq_out, a.H, a.group, bidx, fz, a.xh_out, a.gamma_next);
     } else if (a.next_table) {
         // a forced id beyond the vocabulary embeds as zeros (gather_embed_kernel's rule) and reads neither table; the

@@ -273,6 +273,24 @@ int tfe_build_prefix(void* hh, const int32_t* text_token_ids, int n, const int32
     return emit(t, ids, src, cod, out);
 }
 
+int tfe_build_prefix_stream(void* hh, int32_t first_token_id, const int32_t* special, float* out) {
+    TextFE* t = (TextFE*)hh;
+    if (!t || !out) return -1;
+    const int* sp = special ? special : t->special;
+    // rows 0..6 of tfe_build_prefix, then the first text token + codec_bos: the rest of the text follows frame by frame
+    // through the feedback (q3e_push_text).  Projected rows: 0-2 role tokens, 3 tts_pad, 4 tts_bos, 5 the first token.
+    std::vector<int> ids = {sp[0], sp[1], sp[2], sp[3], sp[4], first_token_id};
+    std::vector<int> src = {0, 1, 2, 3, 3, 3, 4, 5}, cod = {-1, -1, -1, sp[8], sp[9], sp[10], sp[6], sp[7]};
+    return emit(t, ids, src, cod, out);
+}
+
+int tfe_tts_eos_embed(void* hh, float* out) {
+    TextFE* t = (TextFE*)hh;
+    if (!t || !out) return -1;
+    const int32_t id = t->special[5];
+    return tfe_embed_text(t, &id, 1, out);
+}
+
 int tfe_tts_pad_embed(void* hh, float* out) {
     TextFE* t = (TextFE*)hh;
     if (!t || !out) return -1;

@@ -24,6 +24,7 @@ class SlotParams:
     cp_top_k: int = 50
     seed: int = 0
     utt: int = 0
+    text_stream: bool = False      # a text slot: its text arrives row by row (FrameEngine.push_text); n_text is ignored
 
     def check(self, max_frames):
         """Raises ValueError unless every field is in range for an engine of `max_frames` frames per utterance."""
@@ -206,11 +207,38 @@ class FrameEngine:
         nt = np.ascontiguousarray(np.asarray(n_text, np.int32))
         arr = (hiplib.SlotParamsC * len(params))(*[
             hiplib.SlotParamsC(int(p.max_frames), float(p.temperature), int(p.top_k), float(p.top_p), float(p.cp_temperature),
-                               int(p.cp_top_k), int(p.seed), int(p.utt), 0) for p in params])
+                               int(p.cp_top_k), int(p.seed), int(p.utt), 1 if p.text_stream else 0) for p in params])
         rc = self._lib.q3e_admit(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
                                  hiplib.iptr(nt), arr)
         if rc != 0:
             raise RuntimeError(f"q3e_admit failed: {rc}")
+
+    def reserve_text(self, max_rows):
+        """Room for `max_rows` streamed text rows per slot (q3e_text_reserve; before open(); 0 releases it)."""
+        if self._lib.q3e_text_reserve(self.h, int(max_rows)) != 0:
+            raise RuntimeError(f"q3e_text_reserve({max_rows}) failed")
+
+    def push_text(self, slot, rows, final=False, n_text=0):
+        """Append rows ([n, hidden] f32, n >= 0) to the text of the text slot `slot` (q3e_push_text).  final ends the text:
+        the slot's EOS mask is lifted and its text length becomes n_text.  Row i is consumed at the slot's frame i; run()
+        never steps a slot past its rows while its text is not final.  Raises ValueError when the engine refuses the
+        push (not a live text slot, after the final push, beyond the reservation, a non-finite value): nothing is written."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        rows = rows.reshape(-1, rows.shape[-1]) if rows.size else rows.reshape(0, 1024)
+        if rows.shape[1] != 1024:
+            raise ValueError(f"text rows are [n, 1024] (got {rows.shape})")
+        rc = self._lib.q3e_push_text(self.h, int(slot), hiplib.fptr(rows) if len(rows) else None, len(rows),
+                                     int(bool(final)), int(n_text))
+        if rc != 0:
+            raise ValueError(f"q3e_push_text refused the push to slot {slot}: {rc}")
+
+    def text_state(self):
+        """-> (rows pushed per slot, starved[B] bool: the live text slots the next step waits for)."""
+        rows = np.zeros(self.B, np.int32)
+        starved = np.zeros(self.B, np.int32)
+        if self._lib.q3e_text_state(self.h, hiplib.iptr(rows), hiplib.iptr(starved)) != 0:
+            raise RuntimeError("q3e_text_state failed")
+        return rows, starved.astype(bool)
 
     def release(self, slots):
         """Per-slot mode: end the utterances in `slots` now (q3e_release; cancellation)."""

@@ -41,6 +41,28 @@ class TextFrontEnd:
         out[8 + n] = self.tts_pad_embed + cod[c.codec_bos]
         return out
 
+    def build_prefix_stream(self, first_token_id):
+        """The 8-row prefix of a text-stream utterance (tfe_build_prefix_stream): rows 0..6 of build_prefix, then the first
+        text token + codec_bos.  The rest of the text follows frame by frame (text_stream_rows)."""
+        c, cod = self.cfg, self.codec
+        out = np.empty((8, cod.shape[1]), np.float32)
+        out[0:3] = self.embed_text([c.im_start, c.assistant, c.newline])
+        out[3:6] = self.tts_pad_embed + cod[[c.codec_nothink, c.codec_think_bos, c.codec_think_eos]]
+        out[6] = self.tts_bos_embed + cod[c.codec_pad]
+        out[7] = self.embed_text([int(first_token_id)])[0] + cod[c.codec_bos]
+        return out
+
+
+def text_stream_rows(fe, token_ids, final=False):
+    """Rows a text-stream utterance takes after its prefix, for a piece of its text: the projection of every id, one
+    token per call (so a row does not depend on how the text was cut into pieces), then the tts_eos row when the piece
+    ends the text.  For the whole text: text_stream_rows(fe, ids[1:], final=True) = [T[1], .., T[n-1], E]."""
+    rows = [fe.embed_text([int(t)])[0] for t in token_ids]
+    if final:
+        rows.append(np.asarray(fe.tts_eos_embed, np.float32))
+    hidden = len(fe.tts_eos_embed)
+    return np.stack(rows).astype(np.float32) if rows else np.zeros((0, hidden), np.float32)
+
 
 class DeviceTextFrontEnd:
     """The same two calls on the GPU (include/qwen3tts_text.h): fp16 text table resident in HBM, fc1 / SiLU / fc2 and
@@ -75,6 +97,13 @@ class DeviceTextFrontEnd:
                                        self._hl.iptr(self._special), self._hl.fptr(out))
         if n != len(ids) + 9:
             raise RuntimeError(f"tfe_build_prefix failed: {n}")
+        return out
+
+    def build_prefix_stream(self, first_token_id):
+        out = np.empty((8, self.hidden), np.float32)
+        n = self._lib.tfe_build_prefix_stream(self.h, int(first_token_id), self._hl.iptr(self._special), self._hl.fptr(out))
+        if n != 8:
+            raise RuntimeError(f"tfe_build_prefix_stream failed: {n}")
         return out
 
     def destroy(self):

@@ -28,7 +28,7 @@ class KernelSlotParamsC(ctypes.Structure):
     """q3::SlotParams (csrc/q3_kernels.h): the entry the sampling kernels read per row; test hooks only."""
     _fields_ = [("max_frames", ctypes.c_int32), ("t_temp", ctypes.c_float), ("t_top_k", ctypes.c_int32),
                 ("t_top_p", ctypes.c_float), ("c_temp", ctypes.c_float), ("c_top_k", ctypes.c_int32),
-                ("seed", ctypes.c_uint64), ("no_row", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+                ("seed", ctypes.c_uint64), ("no_row", ctypes.c_int32), ("pad_", ctypes.c_int32)]   # pad_ = SlotParams::flags
 
 
 def _sig(lib, name, restype, argtypes):
@@ -93,6 +93,9 @@ def load(path: str | None = None):
     _sig(lib, "q3e_open", c_int, [c_void_p, c_int, c_int])
     _sig(lib, "q3e_admit", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, ctypes.POINTER(SlotParamsC)])
     _sig(lib, "q3e_release", c_int, [c_void_p, c_int, i32p])
+    _sig(lib, "q3e_text_reserve", c_int, [c_void_p, c_int])
+    _sig(lib, "q3e_push_text", c_int, [c_void_p, c_int, f32p, c_int, c_int, c_int])
+    _sig(lib, "q3e_text_state", c_int, [c_void_p, i32p, i32p])
     _sig(lib, "q3e_get_hidden", c_int, [c_void_p, f32p])
     _sig(lib, "q3e_step_weight_bytes", ctypes.c_double, [c_void_p])
     # include/qwen3tts_voc.h
@@ -169,6 +172,8 @@ def load(path: str | None = None):
     _sig(lib, "tfe_embed_text", c_int, [c_void_p, i32p, c_int, f32p])
     _sig(lib, "tfe_build_prefix", c_int, [c_void_p, i32p, c_int, i32p, f32p])
     _sig(lib, "tfe_tts_pad_embed", c_int, [c_void_p, f32p])
+    _sig(lib, "tfe_build_prefix_stream", c_int, [c_void_p, ctypes.c_int32, i32p, f32p])
+    _sig(lib, "tfe_tts_eos_embed", c_int, [c_void_p, f32p])
     _sig(lib, "q3_device_count", c_int, [])
     _sig(lib, "q3_device_compute_units", c_int, [])
     _sig(lib, "q3_set_device", c_int, [c_int])

@@ -95,3 +95,57 @@ def read_voc_request(conn):
 def pack_voc_reply(audio_int16: np.ndarray) -> bytes:
     a = np.ascontiguousarray(audio_int16, dtype="<i2")
     return struct.pack("<i", a.shape[0]) + a.tobytes()
+
+
+# client -> batch server, after a request with "text_stream": true, on the same connection: the rest of the text as records
+# i32 kind, i32 n, payload -- kind 1: n UTF-8 bytes (cut anywhere), kind 2: n int32 token ids, kind 0 (n = 0): end of text
+TEXT_END, TEXT_BYTES, TEXT_IDS = 0, 1, 2
+
+
+def pack_text_record(kind: int, payload=b"") -> bytes:
+    if kind == TEXT_END:
+        return struct.pack("<ii", TEXT_END, 0)
+    if kind == TEXT_BYTES:
+        raw = payload.encode("utf-8") if isinstance(payload, str) else bytes(payload)
+        return struct.pack("<ii", TEXT_BYTES, len(raw)) + raw
+    if kind == TEXT_IDS:
+        ids = np.ascontiguousarray(payload, dtype="<i4").reshape(-1)
+        return struct.pack("<ii", TEXT_IDS, ids.shape[0]) + ids.tobytes()
+    raise ValueError(f"unknown text record kind {kind}")
+
+
+class TextRecordParser:
+    """Text records out of a byte stream that arrives in any pieces: feed(bytes) -> the records completed so far, as
+    (TEXT_BYTES, bytes) / (TEXT_IDS, int32 array) / (TEXT_END, None).  Raises ValueError on an unknown kind, a negative or
+    oversized count, and on anything after the end record."""
+
+    def __init__(self):
+        self._buf = bytearray()
+        self.ended = False
+
+    def feed(self, data: bytes) -> list:
+        self._buf += data
+        out = []
+        while len(self._buf) >= 8:
+            if self.ended:
+                raise ValueError("bytes after the end-of-text record")
+            kind, n = struct.unpack_from("<ii", self._buf, 0)
+            if kind not in (TEXT_END, TEXT_BYTES, TEXT_IDS) or n < 0 or (kind == TEXT_END and n != 0):
+                raise ValueError(f"bad text record (kind {kind}, count {n})")
+            size = n * (4 if kind == TEXT_IDS else 1)
+            if size > MAX_REQUEST_BYTES:
+                raise ValueError(f"text record of {size} bytes exceeds {MAX_REQUEST_BYTES}")
+            if len(self._buf) < 8 + size:
+                break
+            body = bytes(self._buf[8:8 + size])
+            del self._buf[:8 + size]
+            if kind == TEXT_END:
+                self.ended = True
+                out.append((TEXT_END, None))
+            elif kind == TEXT_BYTES:
+                out.append((TEXT_BYTES, body))
+            else:
+                out.append((TEXT_IDS, np.frombuffer(body, dtype="<i4").astype(np.int32)))
+        if self.ended and self._buf:
+            raise ValueError("bytes after the end-of-text record")
+        return out

@@ -9,6 +9,7 @@ to printable code points -> lowest-rank-first pair merges -> vocabulary lookup.
 """
 from __future__ import annotations
 
+import codecs
 import json
 import os
 import unicodedata
@@ -131,6 +132,11 @@ class ByteLevelBPE:
             self._encode_plain(text[pos:], ids)
         return ids
 
+    def incremental(self) -> "IncrementalEncoder":
+        """An encoder that takes the text piece by piece (str, or UTF-8 bytes cut anywhere): the ids of feed() ... finish()
+        joined are encode(whole text), however the text was cut."""
+        return IncrementalEncoder(self)
+
     def decode(self, ids) -> str:
         out = bytearray()
         for i in ids:
@@ -140,3 +146,112 @@ class ByteLevelBPE:
             else:
                 out += bytes(self.byte_unmap[c] for c in t)
         return out.decode("utf-8", errors="replace")
+
+
+def _nfc_safe_start(ch: str) -> bool:
+    """True when NFC never composes `ch` with what precedes it, so that NFC(a + ch + b) = NFC(a) + NFC(ch + b): a starter
+    (combining class 0) that is no mark and no Hangul vowel / trailing jamo (the characters whose NFC quick-check is not
+    "yes" are combining marks, spacing vowel signs and those jamo)."""
+    o = ord(ch)
+    return (unicodedata.combining(ch) == 0 and unicodedata.category(ch)[0] != "M"
+            and not (0x1161 <= o <= 0x1175 or 0x11A8 <= o <= 0x11C2))
+
+
+class IncrementalEncoder:
+    """ByteLevelBPE.incremental(): feed(piece) -> the ids that no continuation of the text can change; finish() -> the rest.
+
+    Three stages can still change the tail of what has arrived, and each holds its part back:
+      * UTF-8: an incomplete sequence at the end of a bytes piece waits for its remaining bytes;
+      * added tokens (split out of the RAW text, before normalisation): from the first position whose remainder is a prefix
+        of an added token, the text may become that token, so it stays raw; a match that starts before that position is final;
+      * NFC: the plain text is normalised up to the last character that cannot compose with what precedes it
+        (_nfc_safe_start); the rest stays raw;
+      * the pre-tokenisation regex, on the normalised text: it matches left to right without look-behind, and a match is
+        final once no alternative tried at its start could have run into the end of the text.  The match that touches the
+        end is held back (a word, a run of punctuation or of white space may go on; `\\s+(?!\\S)` and the other white-space
+        alternatives see the end as "no non-space follows"), and so is every match that starts within the last 3 characters
+        (the contractions `'ll`, `'re`, `'ve` fail at the end of "'l" and leave "'" to the punctuation alternative).
+    Pair merges work inside one pre-token, so a final pre-token has final ids."""
+
+    def __init__(self, bpe: ByteLevelBPE):
+        self.bpe = bpe
+        self._utf8 = codecs.getincrementaldecoder("utf-8")("strict")
+        self._raw = ""       # arrived, not normalised: the tail NFC or an added token may still change
+        self._norm = ""      # normalised text of the current plain segment, not yet tokenised
+        self._done = False
+        self._prefixes = {t[:i] for t in bpe.added for i in range(1, len(t) + 1)}
+        self._longest = max((len(t) for t in bpe.added), default=0)
+
+    def _text(self, piece) -> str:
+        return self._utf8.decode(bytes(piece)) if isinstance(piece, (bytes, bytearray, memoryview)) else piece
+
+    def _tokens(self, text: str, ids: list) -> None:
+        for piece in text:
+            mapped = "".join(self.bpe.byte_map[b] for b in piece.encode("utf-8"))
+            for sub in self.bpe._bpe(mapped):
+                tid = self.bpe.vocab.get(sub)
+                if tid is None:
+                    raise KeyError(f"token {sub!r} is not in the vocabulary (vocab.json / merges.txt mismatch)")
+                ids.append(tid)
+
+    def _nfc(self, text: str) -> str:
+        return unicodedata.normalize("NFC", text) if self.bpe.nfc else text
+
+    def _open_from(self, start: int) -> int:
+        """First position >= start of the raw text whose remainder is a prefix of an added token (len: none)."""
+        raw = self._raw
+        for p in range(max(start, len(raw) - self._longest), len(raw)):
+            if raw[p:] in self._prefixes:
+                return p
+        return len(raw)
+
+    def _drain(self, ids: list, end: bool) -> None:
+        bpe, pos = self.bpe, 0
+        while bpe.added_pat is not None:                 # added tokens whose match is final
+            m = bpe.added_pat.search(self._raw, pos)
+            if m is None or (not end and m.start() >= self._open_from(pos)):
+                break
+            self._tokens(bpe.pat.findall(self._norm + self._nfc(self._raw[pos:m.start()])), ids)   # a whole plain segment
+            self._norm = ""
+            ids.append(bpe.added[m.group(0)])
+            pos = m.end()
+        if end:
+            self._tokens(bpe.pat.findall(self._norm + self._nfc(self._raw[pos:])), ids)
+            self._norm = self._raw = ""
+            return
+        stop = self._open_from(pos) if bpe.added_pat is not None else len(self._raw)
+        cut = stop
+        if bpe.nfc and not (stop < len(self._raw) and _nfc_safe_start(self._raw[stop])):
+            cut = pos
+            for i in range(stop - 1, pos - 1, -1):
+                if _nfc_safe_start(self._raw[i]):
+                    cut = i
+                    break
+        self._norm += self._nfc(self._raw[pos:cut])
+        self._raw = self._raw[cut:]
+        keep = len(self._norm)                           # start of the held-back tail of the normalised text
+        final = []
+        for m in bpe.pat.finditer(self._norm):
+            if m.end() == len(self._norm) or m.start() >= len(self._norm) - 3:
+                keep = m.start()
+                break
+            final.append(m.group(0))
+        self._tokens(final, ids)
+        self._norm = self._norm[keep:]
+
+    def feed(self, piece) -> list:
+        if self._done:
+            raise ValueError("feed() after finish()")
+        ids: list = []
+        self._raw += self._text(piece)
+        self._drain(ids, end=False)
+        return ids
+
+    def finish(self) -> list:
+        if self._done:
+            return []
+        self._done = True
+        self._raw += self._utf8.decode(b"", final=True)   # raises on a sequence cut short
+        ids: list = []
+        self._drain(ids, end=True)
+        return ids

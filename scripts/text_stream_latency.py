@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Time to first audio when the text arrives token by token: a "text_stream" request against waiting for the whole text.
+
+One text of --tokens token ids becomes available at a fixed rate (--rate tokens/s, e.g. a language model writing it), the
+first token at t0.  Two clients of one in-process batch_server --concurrent (scripts/serve_load.py's packs: synthetic
+Qwen3-TTS-0.6B talker and code predictor, a 4096-entry text table, bench.py's whole vocoder; --tiny: the 2-layer packs of the
+tests), alternating, --repeats times after one untimed pass of each:
+
+  streamed  a "text_stream" request goes out at t0 with the first token; token i follows as a text record at t0 + i / rate,
+            then the end-of-text record (batch_server.synthesize_text_stream);
+  whole     the client waits until the last token exists (t0 + (tokens - 1) / rate) and sends an ordinary streamed request.
+
+Both greedy, streamed audio with --vocoder (default incremental: audio from the first check on).  Reported per leg: time from
+t0 to the first audio record and to the end of the reply (ms), frames; for the streamed leg also the checks that ran no frame
+because the slot waited for text (the frame loop is faster than the text, so it starves between tokens -- and with it every
+other slot of the batch: DESIGN.md section 11).
+
+    python scripts/text_stream_latency.py --out profiles/text_stream_latency.json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import threading
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+
+def tiny_packs(cache):
+    from qwen3_tts_axera_russian_amd import weights as W
+    os.makedirs(cache, exist_ok=True)
+    cfg = W.tiny_config(2, 2, text_vocab=512)
+    cfg.text_dim = 64
+    main, voc = os.path.join(cache, "tsl_tiny_t2c2.q3w"), os.path.join(cache, "tsl_voc_tiny.q3w")
+    if not os.path.exists(main):
+        W.write_synthetic(main, cfg, seed=1234, parts=("talker", "cp", "text"))
+    if not os.path.exists(voc):
+        W.write_pack(voc, {"voc_chunk": 64.0}, W.make_synthetic_voc(W.tiny_voc_config(), seed=7))
+    return main, voc, cfg
+
+
+def one(sock, ids, rate, max_tokens, vocoder, streamed):
+    from qwen3_tts_axera_russian_amd import batch_server as bs
+    t0 = time.perf_counter()
+
+    def pieces():
+        for i, t in enumerate(ids):
+            time.sleep(max(0.0, t0 + i / rate - time.perf_counter()))
+            yield [t]
+    if streamed:
+        recs = bs.synthesize_text_stream(sock, pieces(), max_tokens=max_tokens, vocoder=vocoder)
+    else:
+        time.sleep(max(0.0, t0 + (len(ids) - 1) / rate - time.perf_counter()))
+        recs = bs.synthesize_batch_stream(sock, token_ids=[ids], max_tokens=max_tokens, vocoder=vocoder)
+    first, frames, samples = None, 0, 0
+    for rec in recs:
+        if rec[0] == "audio":
+            first = first if first is not None else time.perf_counter()
+            samples += len(rec[2])
+        else:
+            frames = rec[2].shape[0]
+    return {"first_audio_ms": round(1e3 * (first - t0), 1), "done_ms": round(1e3 * (time.perf_counter() - t0), 1),
+            "frames": frames, "samples": samples}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rate", type=float, default=50.0, help="text tokens per second")
+    ap.add_argument("--tokens", type=int, default=40)
+    ap.add_argument("--max_tokens", type=int, default=120)
+    ap.add_argument("--vocoder", default="incremental", choices=["walk", "incremental"])
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--max_batch", type=int, default=32)
+    ap.add_argument("--text_wait_ms", type=float, default=200.0)
+    ap.add_argument("--tiny", action="store_true", help="the tests' 2-layer packs instead of the 0.6B architecture")
+    ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--cache", default=os.environ.get("Q3_BENCH_CACHE", "/tmp/q3_bench_cache"))
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from qwen3_tts_axera_russian_amd import batch_server as bs
+    if a.tiny:
+        main_pack, voc_pack, cfg = tiny_packs(a.cache)
+    else:
+        import serve_load
+        main_pack, voc_pack, cfg = serve_load.make_packs(a.cache, a.seed)
+    ids = np.random.default_rng(a.seed).integers(0, cfg.text_vocab - 8, a.tokens).tolist()
+    sock = os.path.join(a.cache, f"tsl_{os.getpid()}.sock")
+    srv = bs.BatchSynthesisServer(main_pack, voc_pack, sock, max_batch=a.max_batch, n_ctx=a.max_tokens + 64, max_tokens=a.max_tokens,
+                                  temperature=0.0, cp_temperature=0.0, install_signal_handlers=False, concurrent=True,
+                                  text_wait_ms=a.text_wait_ms)
+    th = threading.Thread(target=srv.serve, daemon=True)
+    th.start()
+    while not (os.path.exists(sock) and srv.sched is not None):
+        time.sleep(0.05)
+    legs = {"streamed": [], "whole": []}
+    try:
+        for rep in range(a.repeats + 1):
+            for leg in ("streamed", "whole"):
+                s0 = srv.sched.starved_checks
+                r = one(sock, ids, a.rate, a.max_tokens, a.vocoder, leg == "streamed")
+                if leg == "streamed":
+                    r["starved_checks"] = srv.sched.starved_checks - s0
+                if rep:
+                    legs[leg].append(r)
+                print(f"[text_stream_latency] {'warm-up' if not rep else rep} {leg}: {r}", file=sys.stderr, flush=True)
+    finally:
+        srv._running = False
+        th.join(timeout=60)
+        srv.close()
+    med = lambda leg, k: float(np.median([r[k] for r in legs[leg]]))
+    out = {"what": "time from the first text token to the first audio record: text streamed into the utterance vs the whole text first",
+           "packs": "tiny (2 + 2 layers)" if a.tiny else "synthetic Qwen3-TTS-0.6B architecture", "rate_tokens_per_s": a.rate,
+           "tokens": a.tokens, "text_ready_ms": round(1e3 * (a.tokens - 1) / a.rate, 1), "max_tokens": a.max_tokens,
+           "vocoder": a.vocoder, "max_batch": a.max_batch, "check_every": srv.check_every, "text_wait_ms": a.text_wait_ms,
+           "repeats": a.repeats, "runs": legs,
+           "median": {leg: {k: med(leg, k) for k in ("first_audio_ms", "done_ms", "frames")} for leg in legs},
+           "median_starved_checks": med("streamed", "starved_checks")}
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
