@@ -21,6 +21,19 @@ __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + e
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }   // ELU, alpha = 1
 
 static int g_voc_max_wgs = 0;  // 0 = one workgroup per tile; >0 caps the grid (persistent tile loop)
+// test hooks (voc_set_fill, voc_debug_last_variant at the end of this file; host side only)
+static int g_voc_fill = -1;    // < 0: the built-in workgroup target of the tile-height rules (512); >= 0 replaces it
+// the instantiation the last conv launch of this process took (a few plain stores per launch; named on request)
+enum { VV_NONE, VV_CONV, VV_OUT1, VV_RESUNIT, VV_SNAKE_SPLIT, VV_SPLIT };
+static struct {
+    int kind = VV_NONE, p[5] = {0, 0, 0, 0, 0};
+    bool after_pass = false;   // split conv: its planes came from snake_split_kernel right before it
+} g_voc_variant;
+static inline void voc_note_variant(int kind, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0) {
+    g_voc_variant.after_pass = kind == VV_SPLIT && g_voc_variant.kind == VV_SNAKE_SPLIT;
+    g_voc_variant.kind = kind;
+    g_voc_variant.p[0] = a, g_voc_variant.p[1] = b, g_voc_variant.p[2] = c, g_voc_variant.p[3] = d, g_voc_variant.p[4] = e;
+}
 constexpr int VKC = 8;     // input channels per LDS stage
 constexpr int VTN = 128;   // output columns per workgroup (4 waves x 32)
 // LDS row pitches of the staged operands.  An MFMA operand read is 64 lanes x 4 B: lanes 0-31 walk 32 consecutive floats of
@@ -344,6 +357,7 @@ static int launch_conv_t(hipStream_t s, const ConvArgs& a, int B) {
     c.n_tiles = c.tiles_l * c.tiles_m * (c.flat_B > 0 ? 1 : B);
     int grid = c.n_tiles;
     if (g_voc_max_wgs > 0 && grid > g_voc_max_wgs) grid = g_voc_max_wgs;
+    voc_note_variant(VV_CONV, MT, KT, KC, CT ? 1 : 0, ACT);
     hipLaunchKernelGGL((conv_kernel<MT, KT, KC, CT, ACT>), dim3(grid), dim3(256), lds, s, c);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
@@ -359,7 +373,8 @@ static int launch_conv_mt(hipStream_t s, const ConvArgs& a, int B) {
     // workgroup (1024 -> 512 over 2048 columns is 4 x 16 = 64 tiles of 128 rows) -- take shorter tiles until the grid
     // covers the chip
     // covers the chip twice (measured, 32 chunks: pre-transformer 5.8 -> 4.2 ms, the 4096 -> 1024 ConvNeXt conv 0.83 -> 0.62)
-    static const int fill = getenv("Q3_VOC_FILL") ? atoi(getenv("Q3_VOC_FILL")) : 512;
+    static const int fill_env = getenv("Q3_VOC_FILL") ? atoi(getenv("Q3_VOC_FILL")) : 512;
+    const int fill = g_voc_fill >= 0 ? g_voc_fill : fill_env;
     if (fill > 0) {
         const long cols = (KT == 1 && a.stride == 1) ? (long)a.ldx * B : (long)a.Lc;
         const long col_tiles = (cols + VTN - 1) / VTN * ((KT == 1 && a.stride == 1) ? 1 : B);
@@ -448,6 +463,7 @@ int voc_launch_conv(hipStream_t s, const ConvArgs& a, int B) {
         (size_t)B * c * a.ldx < ((size_t)1 << 31)) {
         ConvArgs k = a;
         k.Mp = 4;
+        voc_note_variant(VV_OUT1);
         hipLaunchKernelGGL(conv_out1_kernel, dim3((a.Lin + 2047) / 2048, B), dim3(256), 0, s, k);
         Q3_HIP(hipGetLastError(), -1);
         return 0;
@@ -639,6 +655,7 @@ static int launch_resunit_t(hipStream_t s, ResUnitArgs a, int B) {
     a.n_tiles = a.tiles_l * B;
     int grid = a.n_tiles;
     if (g_voc_max_wgs > 0 && grid > g_voc_max_wgs) grid = g_voc_max_wgs;
+    voc_note_variant(VV_RESUNIT, MT);
     hipLaunchKernelGGL((resunit_kernel<MT>), dim3(grid), dim3(256), lds, s, a);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
@@ -705,6 +722,7 @@ __global__ void __launch_bounds__(256) snake_split_kernel(const float* __restric
 
 int voc_launch_snake_split(hipStream_t s, const float* x, const float* alpha, const float* inv_beta, _Float16* xh, _Float16* xl, int C,
                            int L, int ld, int gelu, int* ovf, int B, int ovf_stride) {
+    voc_note_variant(VV_SNAKE_SPLIT);
     hipLaunchKernelGGL(snake_split_kernel, dim3((unsigned)((L + 255) / 256), C / 8, B), dim3(256), 0, s, x, alpha, inv_beta, xh, xl, C, L, ld,
                        gelu, ovf, ovf_stride);
     Q3_HIP(hipGetLastError(), -1);
@@ -897,6 +915,7 @@ static int launch_conv_split_t(hipStream_t s, const SplitArgs& a, int B) {
     if (c.my_fast) c.n_tiles = (c.tiles_l * B + 7) / 8 * 8 * c.tiles_m;
     int grid = c.n_tiles;
     if (g_voc_max_wgs > 0 && grid > g_voc_max_wgs) grid = g_voc_max_wgs;
+    voc_note_variant(VV_SPLIT, KT, KS, MW, NJ, c.my_fast);
     hipLaunchKernelGGL((conv_split_kernel<KT, KS, MW, NJ>), dim3(grid), dim3(256), lds, s, c);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
@@ -929,7 +948,7 @@ int launch_conv_split(hipStream_t s, const SplitArgs& a, int K, int B) {
     // give the chip enough workgroups: the input tile is read by Cout/96 workgroups instead of Cout/64
     const long tiles96 = (long)((a.Lc + 255) / 256) * (a.M / 96) * B;
     const bool fits96 = a.M % 96 == 0 && a.Mp % 96 == 0;
-    const bool use96 = fits96 && (a.Mp % 64 != 0 || tiles96 >= 512);
+    const bool use96 = fits96 && (a.Mp % 64 != 0 || tiles96 >= (g_voc_fill >= 0 ? g_voc_fill : 512));
     return use96 ? launch_conv_split_m<3>(s, a, K, B) : launch_conv_split_m<2>(s, a, K, B);
 }
 
@@ -1534,6 +1553,34 @@ extern "C" {
 int voc_set_narrow_k1(int on) {   // test hook: 128-column tiles for the 1-tap convs (default on)
     g_voc_narrow_k1 = on ? 1 : 0;
     return 0;
+}
+
+// test hook: the workgroup target below which launch_conv_mt takes shorter tiles and launch_conv_split 64-row ones (512, or
+// Q3_VOC_FILL for the exact path).  n >= 0 replaces it for the process (0: tile height follows divisibility alone), n < 0
+// restores the default.  -> the value set.
+int voc_set_fill(int n) {
+    g_voc_fill = n < 0 ? -1 : n;
+    return g_voc_fill;
+}
+
+// test hook: the instantiation the last conv launch took ("conv<4,1,16,ct0,act1>", "out1", "resunit<3>",
+// "split<7,1,3,1>/myfast", "snake_split", or "snake_split+split<...>" for a split conv that read the separate pass's planes;
+// "" before the first one)
+const char* voc_debug_last_variant() {
+    static char name[64];
+    const int* p = g_voc_variant.p;
+    switch (g_voc_variant.kind) {
+        case VV_CONV: snprintf(name, sizeof(name), "conv<%d,%d,%d,ct%d,act%d>", p[0], p[1], p[2], p[3], p[4]); break;
+        case VV_OUT1: snprintf(name, sizeof(name), "out1"); break;
+        case VV_RESUNIT: snprintf(name, sizeof(name), "resunit<%d>", p[0]); break;
+        case VV_SNAKE_SPLIT: snprintf(name, sizeof(name), "snake_split"); break;
+        case VV_SPLIT:
+            snprintf(name, sizeof(name), "%ssplit<%d,%d,%d,%d>%s", g_voc_variant.after_pass ? "snake_split+" : "", p[0], p[1], p[2], p[3],
+                     p[4] ? "/myfast" : "");
+            break;
+        default: name[0] = 0;
+    }
+    return name;
 }
 
 // Cap the number of workgroups every vocoder launch may occupy (0 = no cap).  Process-wide.
