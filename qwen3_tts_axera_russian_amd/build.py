@@ -42,7 +42,10 @@ def _newer(dst: str, srcs) -> bool:
 NO_SPILL = ("resunit_kernel", "linear_kernelILi1ELi1E", "linear_kernelILi1ELi2E", "linear_kernelILi2ELi1E",
             "linear_kernelILi2ELi2E", "attn_kernel", "attn_short_kernel", "cp_argmax_kernel", "talker_sample_kernel",
             "voc_attn_incr_kernel", "voc_incr_prepend_kernel", "voc_incr_emit_kernel", "voc_incr_prepend_split_kernel",
-            "enc_stream_conv_in_kernel", "enc_stream_unfold_kernel", "enc_stream_emit_kernel")
+            "enc_conv_in_kernel", "enc_stream_unfold_kernel", "enc_stream_emit_kernel",
+            # (the name the stream's first conv had before it became enc_conv_in_kernel's hist != nullptr case:
+            # tests/test_enc_stream_contract.py still asks for it, and a kernel that comes back under it is held too)
+            "enc_stream_conv_in_kernel")
 
 
 def kernel_resources(lib_path: str):

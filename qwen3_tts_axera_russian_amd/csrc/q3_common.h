@@ -92,6 +92,56 @@ inline float bf16_to_f32(uint16_t b) {
 float h2f(uint16_t h);
 uint16_t f2h_sat(float f);
 
+// ---------------------------------------------------------------------------
+// What the carry-state objects (VocIncr, EncStream) and the encoder handle share
+// ---------------------------------------------------------------------------
+// Owner of device allocations: it frees what it handed out, and `bytes` is the sum of the sizes asked for.
+struct DeviceAllocs {
+    std::vector<void*> ptrs;
+    size_t bytes = 0;
+    DeviceAllocs() = default;
+    DeviceAllocs(const DeviceAllocs&) = delete;
+    DeviceAllocs& operator=(const DeviceAllocs&) = delete;
+    ~DeviceAllocs() { release(); }
+    // *p = n bytes -> false on failure (what it got stays owned)
+    template <class T>
+    bool alloc(T** p, size_t n) {
+        if (hipMalloc((void**)p, n) != hipSuccess) return false;
+        ptrs.push_back(*p);
+        bytes += n;
+        return true;
+    }
+    // the same, zeroed on stream s: the stream is named at every call, and the caller waits for it before the first use
+    template <class T>
+    bool alloc_zeroed(T** p, size_t n, hipStream_t s) { return alloc(p, n) && hipMemsetAsync(*p, 0, n, s) == hipSuccess; }
+    void adopt(DeviceAllocs& o) {   // everything o owns becomes this one's
+        ptrs.insert(ptrs.end(), o.ptrs.begin(), o.ptrs.end());
+        bytes += o.bytes;
+        o.ptrs.clear();
+        o.bytes = 0;
+    }
+    void release() {
+        for (void* p : ptrs) hipFree(p);
+        ptrs.clear();
+        bytes = 0;
+    }
+};
+
+// The entries of a push that run as one launch sequence: those with equal keys, at most max_members to a group.
+struct PushGroups {
+    std::vector<std::vector<long long>> keys;   // per group
+    std::vector<std::vector<int>> members;      // per group: entry indices
+    void add(const std::vector<long long>& key, int entry, int max_members) {   // the first group with this key and room, else a new one
+        size_t g = 0;
+        while (g < keys.size() && (keys[g] != key || (int)members[g].size() >= max_members)) g++;
+        if (g == keys.size()) {
+            keys.push_back(key);
+            members.emplace_back();
+        }
+        members[g].push_back(entry);
+    }
+};
+
 struct ModelCfg {
     int hidden = 1024, head_dim = 128, n_heads = 16, n_kv = 8;
     int talker_layers = 28, talker_ffn = 3072, talker_vocab = 3072;

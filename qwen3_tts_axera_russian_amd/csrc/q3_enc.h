@@ -1,8 +1,10 @@
 // q3_enc.h -- what the encoder's two translation units share: the loaded op table (q3_enc.hip builds it, q3_enc_stream.hip
-// walks it a push at a time), the quantiser's launcher, and the host arithmetic of the streaming encode (no device call: the
+// walks it a push at a time), the op -> launch layer under both walks (enc_conv_args, and the launchers of the kernels that
+// q3_enc.hip defines: the first conv and the quantiser), and the host arithmetic of the streaming encode (no device call: the
 // test library hands it to the CPU tests as it stands).
 #pragma once
 #include "q3_common.h"
+#include "q3_voc_ops.h"
 
 #include <vector>
 
@@ -17,6 +19,7 @@ constexpr int ENC_IN_MAXK = 16;
 
 struct EncOp {
     int op = 0, cin = 0, cout = 0, k = 0, p0 = 0, flags = 0;   // p0: dilation (CONV) / stride (CONV_S)
+    int c_act = 0;                                            // channels of the activation after the op (a TO_RES shortcut keeps its input's)
     float *w = nullptr, *bias = nullptr;                      // conv weights in conv_kernel's packed layout (CONV_IN: [cout][k])
     int heads = 0, head_dim = 0, window = 0;
     float eps = 0.f, theta = 10000.f;
@@ -28,7 +31,7 @@ struct Enc {
     int device = 0;
     int max_batch = 1, max_samples = 0, sample_rate = 24000, hop = 1, nq = 0;
     std::vector<EncOp> ops;
-    std::vector<void*> allocs;
+    DeviceAllocs mem;
     hipStream_t s = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float* pcm = nullptr;           // [max_batch][pitch(max_samples)]
@@ -45,6 +48,39 @@ static inline void enc_bind(const Enc* e) {
     if (e && (hipGetDevice(&d) != hipSuccess || d != e->device)) hipSetDevice(e->device);
 }
 
+// the columns an op hands on from L: a strided conv pads a clip's end to whole strides, ceil(L / s)
+static inline long enc_cols_out(const EncOp& op, long L) { return op.op == EOP_CONV_S ? (L + op.p0 - 1) / op.p0 : L; }
+static inline long enc_cols_after(const std::vector<EncOp>& ops, size_t n_ops, long L) {
+    for (size_t i = 0; i < n_ops; i++) L = enc_cols_out(ops[i], L);
+    return L;
+}
+
+// A conv op over `cols` columns as voc_launch_conv takes it, all but x, y and res.  unfolded: a strided op as the 1-tap conv
+// over the [cin * k] rows of its unfold kernel.
+static inline ConvArgs enc_conv_args(const EncOp& op, long cols, bool unfolded) {
+    ConvArgs a;
+    a.Cin = unfolded ? op.cin * op.k : op.cin;
+    a.K = unfolded ? 1 : op.k;
+    a.dil = unfolded ? 1 : op.p0;
+    a.elu = (!unfolded && (op.flags & EF_ELU)) ? 1 : 0;   // (the unfold kernel has applied a strided op's ELU)
+    a.gelu = (!unfolded && (op.flags & EF_GELU)) ? 1 : 0;
+    a.wk = op.w;
+    a.bias = op.bias;
+    a.Cout = a.M = op.cout;
+    a.stride = 1;
+    a.Lin = a.Lout = a.Lc = (int)cols;
+    // Never the short-activation variants: the launcher's variant rule reads Lrule, so pinned it depends on nothing in the
+    // call -- not the columns, the batch or the split of a stream.  "Clip b gives the same bits alone, in a batch and in any
+    // split" rests on this line.
+    a.Lrule = 1 << 20;
+    a.ldx = a.ldy = (int)enc_pitch(cols);
+    return a;
+}
+
+// the first conv: x [B][ldx], n columns of the one input channel -> y [B][cout][ldy].  hist == nullptr: a whole clip (zeros left
+// of column 0); else entry b continues stream streams[b], whose last k - 1 samples are at hist + streams[b] * state_floats
+int enc_launch_conv_in(hipStream_t s, const float* x, int ldx, const EncOp& op, float* y, int ldy, int n, int B, float* hist,
+                       long long state_floats, const int* streams);
 // the split residual VQ over n_frames frames, frame g = b * T + t read from z [B][2 * dim][ld] -> codes [n_frames][nq]
 int enc_launch_rvq(hipStream_t s, const float* z, int ld, int T, int n_frames, const EncOp& op, int64_t* codes);
 

@@ -5,8 +5,10 @@
 // pitch ld = L rounded up to 32 floats, one row per clip and channel, L = the longest clip's columns at that stage.
 //
 // Shared with the vocoder (q3_voc_ops.h, defined in q3_voc_kernels.hip): the exact-fp32 MFMA conv (with ELU applied while the input is staged),
-// the channel norm and the sliding-window attention.  Own kernels:
-//   enc_conv_in_kernel   the first conv, ONE input channel (a dot product of k taps per output: no MFMA tile)
+// the channel norm and the sliding-window attention; q3_enc.h turns a conv op into the conv launcher's arguments (enc_conv_args)
+// for enc_run here and for the streaming walk (q3_enc_stream.hip).  Own kernels:
+//   enc_conv_in_kernel   the first conv, ONE input channel (a dot product of k taps per output: no MFMA tile), for a whole clip
+//                        and for a stream's push (the k - 1 carried samples left of column 0): enc_launch_conv_in
 //   enc_unfold_kernel    strided conv input -> [Cin * k][ceil(L / s)] columns (im2col), Mimi's padding per clip: zeros
 //                        (ELU'd, ELU(0) = 0) or replicate at both edges.  The strided conv is then a 1-tap conv.
 //   enc_rvq_kernel       split residual VQ encode: per frame, stage q scores ||e_j||^2 - 2 r.e_j for every entry j,
@@ -15,10 +17,9 @@
 // Ragged batches: every op's arithmetic for a column reads only that column and the columns left of it in its own clip
 // (causal convs, causal attention), or -- the strided ops -- the clip's own padding substituted for any column at or past
 // its own length, so the padding columns of a shorter clip never reach its kept outputs.  No variant rule looks at the
-// batch or the lengths (ConvArgs::Lrule, ConvArgs::elu, voc_launch_attn): clip b gives the same bits alone and in a batch.
+// batch or the lengths (enc_conv_args' pin, ConvArgs::elu, voc_launch_attn): clip b gives the same bits alone and in a batch.
 #include "../../include/qwen3tts_enc.h"
 #include "q3_enc.h"
-#include "q3_voc_ops.h"
 
 #include <algorithm>
 #include <cmath>
@@ -27,29 +28,47 @@
 namespace q3 {
 
 // ---------------------------------------------------------------------------
-// First conv: x [B][ldx] (one channel) -> y [B][Cout][ldy], causal k taps (zeros left of column 0), + bias.
-// One thread per column holds its k inputs and walks the output channels (weights: wave-uniform loads).
+// First conv: x [B][ldx] (one channel, n columns) -> y [B][Cout][ldy], causal k taps, + bias.  One thread per column holds its
+// k inputs and walks the output channels (weights: wave-uniform loads): bias first, then the taps in order.  Left of column 0
+// are zeros (hist == nullptr: a whole clip) or the last K - 1 samples of the entry's stream, which only workgroup 0 reads
+// (columns < K - 1) and, after a barrier, replaces with the last K - 1 of [history | new].
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) enc_conv_in_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
                                                           const float* __restrict__ bias, float* __restrict__ y, int ldy,
-                                                          int Cout, int K, int L) {
-    const int l = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
-    if (l >= L) return;
+                                                          int Cout, int K, int n, float* hist, long long state_floats,
+                                                          const int* __restrict__ streams) {
+    const int l = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, H = K - 1;
     const float* xb = x + (size_t)b * ldx;
-    float xv[ENC_IN_MAXK];
+    float* h = hist ? hist + (size_t)streams[b] * state_floats : nullptr;
+    float nw = 0.f;
+    const bool roll = h && blockIdx.x == 0 && (int)threadIdx.x < H;
+    if (roll) nw = ((int)threadIdx.x + n < H) ? h[threadIdx.x + n] : xb[(int)threadIdx.x + n - H];
+    if (l < n) {
+        float xv[ENC_IN_MAXK];
 #pragma unroll
-    for (int k = 0; k < ENC_IN_MAXK; k++) {
-        const int ls = l - (K - 1 - k);
-        xv[k] = (k < K && ls >= 0) ? xb[ls] : 0.f;
-    }
-    float* yb = y + (size_t)b * Cout * ldy + l;
-    for (int co = 0; co < Cout; co++) {
-        float acc = bias ? bias[co] : 0.f;
+        for (int k = 0; k < ENC_IN_MAXK; k++) {
+            const int ls = l - (K - 1 - k);
+            xv[k] = k < K ? (ls >= 0 ? xb[ls] : (h ? h[H + ls] : 0.f)) : 0.f;
+        }
+        float* yb = y + (size_t)b * Cout * ldy + l;
+        for (int co = 0; co < Cout; co++) {
+            float acc = bias ? bias[co] : 0.f;
 #pragma unroll
-        for (int k = 0; k < ENC_IN_MAXK; k++)
-            if (k < K) acc = fmaf(w[co * K + k], xv[k], acc);
-        yb[(size_t)co * ldy] = acc;
+            for (int k = 0; k < ENC_IN_MAXK; k++)
+                if (k < K) acc = fmaf(w[co * K + k], xv[k], acc);
+            yb[(size_t)co * ldy] = acc;
+        }
     }
+    __syncthreads();
+    if (roll) h[threadIdx.x] = nw;
+}
+
+int enc_launch_conv_in(hipStream_t s, const float* x, int ldx, const EncOp& op, float* y, int ldy, int n, int B, float* hist,
+                       long long state_floats, const int* streams) {
+    hipLaunchKernelGGL(enc_conv_in_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, s, x, ldx, op.w, op.bias, y, ldy, op.cout,
+                       op.k, n, hist, state_floats, streams);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -218,16 +237,14 @@ int enc_launch_rvq(hipStream_t s, const float* z, int ld, int T, int n_frames, c
 
 static float* enc_up(Enc* e, const float* h, size_t n) {
     float* d = nullptr;
-    if (hipMalloc((void**)&d, n * 4) != hipSuccess) return nullptr;
-    e->allocs.push_back(d);
-    if (hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    if (!e->mem.alloc(&d, n * 4) || hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
     return d;
 }
 
 static void enc_destroy(Enc* e) {
     if (!e) return;
     if (e->s) hipStreamSynchronize(e->s);
-    for (void* p : e->allocs) hipFree(p);
+    e->mem.release();
     if (e->e0) hipEventDestroy(e->e0);
     if (e->e1) hipEventDestroy(e->e1);
     if (e->s) hipStreamDestroy(e->s);
@@ -244,13 +261,13 @@ static int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, floa
     {
         std::vector<int> l2(lens);
         for (size_t i = 0; i < e->ops.size(); i++) {
-            for (int b = 0; b < B; b++) tab[i * e->max_batch + b] = l2[b];
-            if (e->ops[i].op == EOP_CONV_S)
-                for (int b = 0; b < B; b++) l2[b] = (l2[b] + e->ops[i].p0 - 1) / e->ops[i].p0;
+            for (int b = 0; b < B; b++) {
+                tab[i * e->max_batch + b] = l2[b];
+                l2[b] = (int)enc_cols_out(e->ops[i], l2[b]);
+            }
         }
         Q3_HIP(hipMemcpyAsync(e->d_lens, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, e->s), -1);
     }
-    int C = 1;
     float* P[2] = {e->buf[0], e->buf[1]};   // ping-pong pair
     float* res = e->buf[2];                 // the residual a later RES_ADD reads
     float* src = e->pcm;                    // the current activation
@@ -265,39 +282,19 @@ static int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, floa
         }
         float* dst = (op.flags & EF_TO_RES) ? res : other(src);
         if (op.op == EOP_CONV_IN) {
-            hipLaunchKernelGGL(enc_conv_in_kernel, dim3((unsigned)((L + 255) / 256), B), dim3(256), 0, e->s, src, (int)ld, op.w,
-                               op.bias, dst, (int)ld, op.cout, op.k, (int)L);
-            Q3_HIP(hipGetLastError(), -1);
+            if (enc_launch_conv_in(e->s, src, (int)ld, op, dst, (int)ld, (int)L, B, nullptr, 0, nullptr)) return -1;
         } else if (op.op == EOP_CONV || op.op == EOP_CONV_S) {
-            ConvArgs a;
-            long Lo = L;
-            a.x = src;
-            if (op.op == EOP_CONV_S) {
-                Lo = (L + op.p0 - 1) / op.p0;
+            const bool strided = op.op == EOP_CONV_S;
+            const long Lo = enc_cols_out(op, L);
+            if (strided) {
                 hipLaunchKernelGGL(enc_unfold_kernel, dim3((unsigned)((Lo + 255) / 256), op.cin * op.k, B), dim3(256), 0, e->s, src,
                                    (int)ld, op.cin, e->d_lens + i * e->max_batch, e->buf[3], (int)enc_pitch(Lo), (int)Lo, op.k,
                                    op.p0, (op.flags & EF_REPLICATE) ? 1 : 0, (op.flags & EF_ELU) ? 1 : 0);
                 Q3_HIP(hipGetLastError(), -1);
-                a.x = e->buf[3];
-                a.Cin = op.cin * op.k;
-                a.K = 1;
-                a.dil = 1;
-            } else {
-                a.Cin = op.cin;
-                a.K = op.k;
-                a.dil = op.p0;
-                a.elu = (op.flags & EF_ELU) ? 1 : 0;
-                a.gelu = (op.flags & EF_GELU) ? 1 : 0;
             }
+            ConvArgs a = enc_conv_args(op, Lo, strided);
+            a.x = strided ? e->buf[3] : src;
             a.y = dst;
-            a.wk = op.w;
-            a.bias = op.bias;
-            a.Cout = op.cout;
-            a.M = op.cout;
-            a.stride = 1;
-            a.Lin = a.Lout = a.Lc = (int)Lo;
-            a.Lrule = 1 << 20;   // never the short-activation variants: no rule depends on the lengths in this call
-            a.ldx = a.ldy = (int)enc_pitch(Lo);
             if (op.flags & EF_RES_ADD) a.res = res;
             if (voc_launch_conv(e->s, a, B)) return -1;
             L = Lo;
@@ -313,12 +310,10 @@ static int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, floa
             *outL = L;
             return 0;
         }
-        if (op.flags & EF_TO_RES) continue;   // a conv shortcut: the activation stays
-        C = op.cout;
-        src = dst;
+        if (!(op.flags & EF_TO_RES)) src = dst;   // (a conv shortcut: the activation stays)
     }
     *out = src;
-    *outC = C;
+    *outC = nrun ? e->ops[nrun - 1].c_act : 1;
     *outL = L;
     return 0;
 }
@@ -450,9 +445,8 @@ void* enc_load(const char* weights, int max_batch, int max_samples) {
             op.bias = b ? enc_up(e, b, op.cout) : nullptr;
             ok = op.w && (!b || op.bias);
             if (strided) {
-                const long Lo = (L + op.p0 - 1) / op.p0;
-                max_elems = std::max(max_elems, (size_t)cin_eff * enc_pitch(Lo));
-                L = Lo;
+                L = enc_cols_out(op, L);
+                max_elems = std::max(max_elems, (size_t)cin_eff * enc_pitch(L));
                 e->hop *= op.p0;
             }
             if (op.flags & EF_RES_SAVE) res_live = true;
@@ -521,6 +515,7 @@ void* enc_load(const char* weights, int max_batch, int max_samples) {
             break;
         }
         max_elems = std::max(max_elems, (size_t)std::max(op.cin, op.cout) * enc_pitch(L));
+        op.c_act = C;
         e->ops.push_back(op);
     }
     if (ok && !done) {
@@ -534,18 +529,11 @@ void* enc_load(const char* weights, int max_batch, int max_samples) {
     }
     if (ok) {
         e->buf_elems = (size_t)max_batch * max_elems;
-        for (int i = 0; i < 4 && ok; i++)   // (zeroed once: padding columns start finite)
-            ok = hipMalloc((void**)&e->buf[i], e->buf_elems * 4) == hipSuccess && hipMemset(e->buf[i], 0, e->buf_elems * 4) == hipSuccess;
-        for (int i = 0; i < 4 && ok; i++) e->allocs.push_back(e->buf[i]);
-        const size_t np = (size_t)max_batch * enc_pitch(max_samples);
-        ok = ok && hipMalloc((void**)&e->pcm, np * 4) == hipSuccess;
-        if (ok) e->allocs.push_back(e->pcm);
-        ok = ok && hipMalloc((void**)&e->d_lens, e->ops.size() * max_batch * sizeof(int)) == hipSuccess;
-        if (ok) e->allocs.push_back(e->d_lens);
+        for (int i = 0; i < 4 && ok; i++) ok = e->mem.alloc_zeroed(&e->buf[i], e->buf_elems * 4, e->s);   // (zeroed once: padding columns start finite)
         e->codes_cap = (size_t)max_batch * (size_t)((max_samples + e->hop - 1) / e->hop) * e->nq;
-        ok = ok && hipMalloc((void**)&e->d_codes, e->codes_cap * sizeof(int64_t)) == hipSuccess;
-        if (ok) e->allocs.push_back(e->d_codes);
-        ok = ok && hipDeviceSynchronize() == hipSuccess;
+        ok = ok && e->mem.alloc(&e->pcm, (size_t)max_batch * enc_pitch(max_samples) * 4) &&
+             e->mem.alloc(&e->d_lens, e->ops.size() * max_batch * sizeof(int)) && e->mem.alloc(&e->d_codes, e->codes_cap * sizeof(int64_t)) &&
+             hipDeviceSynchronize() == hipSuccess;
     }
     if (!ok) {
         Q3_LOG("enc_load failed");
@@ -563,10 +551,7 @@ float enc_last_ms(void* h) { return h ? ((Enc*)h)->last_ms : -1.f; }
 int enc_frames(void* h, int n) {
     Enc* e = (Enc*)h;
     if (!e || n <= 0) return -1;
-    long L = n;   // nested ceilings compose: ceil(ceil(n / a) / b) = ceil(n / (a b))
-    for (const EncOp& op : e->ops)
-        if (op.op == EOP_CONV_S) L = (L + op.p0 - 1) / op.p0;
-    return (int)L;
+    return (int)enc_cols_after(e->ops, e->ops.size(), n);   // nested ceilings compose: ceil(ceil(n / a) / b) = ceil(n / (a b))
 }
 
 // checks the arguments and uploads the clips (each row zero after its own length) -> 0 / <0
@@ -654,14 +639,8 @@ int enc_debug_shape(void* h, const int32_t* n_samples, int B, int n_ops, int* C,
     if (!e || !n_samples || B < 1 || B > e->max_batch || n_ops < 1 || n_ops >= (int)e->ops.size()) return -1;
     long Lc = 0;
     for (int b = 0; b < B; b++) Lc = std::max(Lc, (long)n_samples[b]);
-    int c = 1;
-    for (int i = 0; i < n_ops; i++) {
-        const EncOp& op = e->ops[i];
-        if (op.op == EOP_CONV_S) Lc = (Lc + op.p0 - 1) / op.p0;
-        if (!(op.op == EOP_CONV && (op.flags & EF_TO_RES))) c = op.cout;
-    }
-    *C = c;
-    *L = (int)Lc;
+    *C = e->ops[n_ops - 1].c_act;
+    *L = (int)enc_cols_after(e->ops, n_ops, Lc);
     return 0;
 }
 

@@ -4,9 +4,9 @@
 // work buffer, runs the op's ordinary kernel over it and drops the carried columns' outputs.
 //
 // Shared with the incremental vocoder (q3_voc_ops.h): the [history | new] assembly (voc_launch_incr_prepend), the attention
-// over a carried k|v window with absolute positions (voc_launch_incr_attn), and -- as in enc_run -- the exact-fp32 MFMA conv
-// pinned to Lrule = 1 << 20, the channel norm and enc_launch_rvq.  Own kernels:
-//   enc_stream_conv_in_kernel   the one-channel first conv reading its k - 1 carried samples
+// over a carried k|v window with absolute positions (voc_launch_incr_attn), and -- as in enc_run, through the same op -> launch
+// layer (q3_enc.h) -- the exact-fp32 MFMA conv under enc_conv_args' pin, the first conv reading its k - 1 carried samples
+// (enc_launch_conv_in), the channel norm and enc_launch_rvq.  Own kernels:
 //   enc_stream_unfold_kernel    strided conv input from [carry | new] -> [Cin * k][whole strides], rolling the left context and
 //                               the unconsumed tail back into the carry; the clip-end padding only in the finish push
 //   enc_stream_emit_kernel      columns of a group's activation -> rows of the push's packed [frame][channel] buffer
@@ -14,7 +14,6 @@
 // them), n are the new ones.  No rule looks at n, skip or B, so a column's bits are those of any other split.
 #include "../../include/qwen3tts_enc.h"
 #include "q3_enc.h"
-#include "q3_voc_ops.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,39 +22,6 @@ namespace q3 {
 
 constexpr int ENC_S_MAXCARRY = 32;    // columns a strided op carries (k - 1)
 constexpr int ENC_MAX_HIST = 256;     // columns voc_incr_prepend_kernel holds
-
-// x [B][ldx]: the entries' n new samples; hist: the stream's last K - 1 samples.  One thread per new column, as
-// enc_conv_in_kernel (the same fma chain: bias, then taps in order).  Only workgroup 0 reads the history (columns < K - 1),
-// and it writes the new one after a barrier.
-__global__ void __launch_bounds__(256) enc_stream_conv_in_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ w,
-                                                                 const float* __restrict__ bias, float* __restrict__ y, int ldy,
-                                                                 int Cout, int K, int n, float* hist, long long state_floats,
-                                                                 const int* __restrict__ streams) {
-    const int l = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, H = K - 1;
-    const float* xb = x + (size_t)b * ldx;
-    float* h = hist + (size_t)streams[b] * state_floats;
-    float nw = 0.f;
-    const bool roll = blockIdx.x == 0 && (int)threadIdx.x < H;
-    if (roll) nw = ((int)threadIdx.x + n < H) ? h[threadIdx.x + n] : xb[(int)threadIdx.x + n - H];
-    if (l < n) {
-        float xv[ENC_IN_MAXK];
-#pragma unroll
-        for (int k = 0; k < ENC_IN_MAXK; k++) {
-            const int ls = l - (K - 1 - k);
-            xv[k] = k < K ? (ls >= 0 ? xb[ls] : h[H + ls]) : 0.f;
-        }
-        float* yb = y + (size_t)b * Cout * ldy + l;
-        for (int co = 0; co < Cout; co++) {
-            float acc = bias ? bias[co] : 0.f;
-#pragma unroll
-            for (int k = 0; k < ENC_IN_MAXK; k++)
-                if (k < K) acc = fmaf(w[co * K + k], xv[k], acc);
-            yb[(size_t)co * ldy] = acc;
-        }
-    }
-    __syncthreads();
-    if (roll) h[threadIdx.x] = nw;
-}
 
 // Strided conv input with carry (MimiConv1d: k taps, stride s, k - s columns of left context).  The stream's carry row of
 // channel ci holds cnt = (k - s) + before % s columns: the left context of the next output and the columns no whole stride
@@ -122,7 +88,7 @@ struct EncStream {
     int64_t* d_codes = nullptr;           // [frames_cap][nq]
     size_t frames_cap = 0;
     int emb_op = -1, emb_C = 0;           // the op whose input is the embedding (the projection before the quantiser)
-    size_t device_bytes = 0;
+    DeviceAllocs mem;
     float last_ms = 0.f;
     int last_launches = 0;
 };
@@ -130,9 +96,8 @@ struct EncStream {
 namespace {
 
 struct Plan {
-    std::vector<long long> n_frames;                    // per entry
-    std::vector<std::vector<long long>> keys;           // per group: n_in[0 .. n_levels], then the finish flag
-    std::vector<std::vector<int>> members;              // per group: entry indices
+    std::vector<long long> n_frames;   // per entry
+    PushGroups groups;                 // keys: n_in[0 .. n_levels], then the finish flag
 };
 
 int make_plan(const EncStream* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish, Plan& p) {
@@ -142,8 +107,7 @@ int make_plan(const EncStream* s, int n, const int32_t* streams, const int32_t* 
     }
     const int nl = (int)s->lev_s.size();
     p.n_frames.assign(n, 0);
-    p.keys.clear();
-    p.members.clear();
+    p.groups = PushGroups();
     std::vector<char> seen(s->max_streams, 0);
     std::vector<long long> key(nl + 2), bc(nl + 1), carry(nl);
     for (int i = 0; i < n; i++) {
@@ -165,14 +129,7 @@ int make_plan(const EncStream* s, int n, const int32_t* streams, const int32_t* 
         enc_stream_plan(s->lev_k.data(), s->lev_s.data(), nl, s->total[k], n_new[i], fin, key.data(), bc.data(), carry.data());
         key[nl + 1] = fin;
         p.n_frames[i] = key[nl];
-        if (!std::any_of(key.begin(), key.begin() + nl + 1, [](long long v) { return v > 0; })) continue;   // nothing to run
-        size_t g = 0;
-        while (g < p.keys.size() && (p.keys[g] != key || (int)p.members[g].size() >= s->e->max_batch)) g++;
-        if (g == p.keys.size()) {
-            p.keys.push_back(key);
-            p.members.emplace_back();
-        }
-        p.members[g].push_back(i);
+        if (std::any_of(key.begin(), key.begin() + nl + 1, [](long long v) { return v > 0; })) p.groups.add(key, i, s->e->max_batch);
     }
     return 0;
 }
@@ -186,7 +143,7 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
     const bool fin = key[nl + 1] != 0;
     const int* d_streams = s->d_meta;
     const int* d_foff = s->d_meta + (1 + nops) * mb;
-    int cur = -1, res = -1, lvl = 0, skip = 0, C = 1, res_ld = 0, res_skip = 0;
+    int cur = -1, res = -1, lvl = 0, skip = 0, res_ld = 0, res_skip = 0;
     long long n = key[0];
     auto pick = [&](int x = -1) {
         for (int j = 0; j < 4; j++)
@@ -202,7 +159,7 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
                                                  (int)enc_pitch(s->H[i] + n), s->d_hist + s->hoff[i], nullptr, nullptr, s->H[i], (int)n,
                                                  (long long)s->state_floats, d_streams, B);
     };
-    auto emit = [&](float* out) -> int {
+    auto emit = [&](int C, float* out) -> int {
         (*launches)++;
         if (dry) return 0;
         hipLaunchKernelGGL(enc_stream_emit_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)n, B), dim3(256), 0, e->s, s->buf[cur], C,
@@ -212,7 +169,8 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
     };
     for (size_t i = 0; i < nops; i++) {
         const EncOp& op = e->ops[i];
-        if ((int)i == s->emb_op && want_emb && n > 0 && emit(s->d_emb)) return -1;
+        const int C = i ? e->ops[i - 1].c_act : 1;   // channels of the activation the op reads
+        if ((int)i == s->emb_op && want_emb && n > 0 && emit(C, s->d_emb)) return -1;
         if (op.op == EOP_CONV_S) {
             const long long n_out = key[lvl + 1];
             if (n > 0 || n_out > 0) {
@@ -229,23 +187,12 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
                 if (n_out > 0) {
                     const int d = pick(u);
                     if (d < 0 || !fits(op.cout, n_out)) return -1;
-                    ConvArgs a;
+                    ConvArgs a = enc_conv_args(op, n_out, true);
                     a.x = s->buf[u];
                     a.y = s->buf[d];
-                    a.Cin = op.cin * op.k;
-                    a.K = 1;
-                    a.dil = 1;
-                    a.wk = op.w;
-                    a.bias = op.bias;
-                    a.Cout = a.M = op.cout;
-                    a.stride = 1;
-                    a.Lin = a.Lout = a.Lc = (int)n_out;
-                    a.Lrule = 1 << 20;   // enc_run's pin: no rule depends on the columns of this call
-                    a.ldx = a.ldy = (int)enc_pitch(n_out);
                     (*launches)++;
                     if (!dry && voc_launch_conv(e->s, a, B)) return -1;
                     cur = d;
-                    C = op.cout;
                 }
             }
             n = n_out;
@@ -258,14 +205,10 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
             const int d = pick();
             if (!fits(op.cout, n)) return -1;
             (*launches)++;
-            if (!dry) {
-                hipLaunchKernelGGL(enc_stream_conv_in_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, e->s, s->d_pcm,
-                                   (int)enc_pitch(s->max_push), op.w, op.bias, s->buf[d], (int)enc_pitch(n), op.cout, op.k, (int)n,
-                                   s->d_hist + s->hoff[i], (long long)s->state_floats, d_streams);
-                Q3_HIP(hipGetLastError(), -1);
-            }
+            if (!dry && enc_launch_conv_in(e->s, s->d_pcm, (int)enc_pitch(s->max_push), op, s->buf[d], (int)enc_pitch(n), (int)n, B,
+                                           s->d_hist + s->hoff[i], (long long)s->state_floats, d_streams))
+                return -1;
             cur = d;
-            C = op.cout;
             skip = 0;
         } else if (op.op == EOP_CONV) {
             if (cur < 0) return -1;
@@ -280,7 +223,7 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
             const int ld = (int)enc_pitch(cols);
             if (op.flags & EF_RES_SAVE) res = cur, res_ld = ld, res_skip = skip;
             int tmp = -1;
-            ConvArgs a;
+            ConvArgs a = enc_conv_args(op, cols, false);
             if (op.flags & EF_RES_ADD) {
                 if (res < 0) return -1;
                 if (res_ld != ld || res_skip != skip) {
@@ -301,18 +244,6 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
             if (d < 0 || !fits(op.cout, cols)) return -1;
             a.x = s->buf[cur];
             a.y = s->buf[d];
-            a.Cin = op.cin;
-            a.K = op.k;
-            a.dil = op.p0;
-            a.elu = (op.flags & EF_ELU) ? 1 : 0;
-            a.gelu = (op.flags & EF_GELU) ? 1 : 0;
-            a.wk = op.w;
-            a.bias = op.bias;
-            a.Cout = a.M = op.cout;
-            a.stride = 1;
-            a.Lin = a.Lout = a.Lc = (int)cols;
-            a.Lrule = 1 << 20;
-            a.ldx = a.ldy = ld;
             (*launches)++;
             if (!dry && voc_launch_conv(e->s, a, B)) return -1;
             if (op.flags & EF_RES_ADD) res = -1;
@@ -322,7 +253,6 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
                 res_skip = skip;
             } else {
                 cur = d;
-                C = op.cout;
             }
         } else if (op.op == EOP_NORM) {
             if (cur < 0) return -1;
@@ -348,21 +278,12 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
                                              op.heads, op.head_dim, op.window, op.theta, before(i), (int)n, B))
                 return -1;
             cur = d;
-            C = HD;
         } else if (op.op == EOP_RVQ) {
             if (cur < 0 || C != 2 * op.dim) return -1;
-            if (emit(s->d_z)) return -1;   // the quantiser runs once over the frames of the whole push
+            if (emit(C, s->d_z)) return -1;   // the quantiser runs once over the frames of the whole push
         }
     }
     return 0;
-}
-
-void stream_destroy(EncStream* s) {
-    if (!s) return;
-    for (void* p : {(void*)s->d_hist, (void*)s->buf[0], (void*)s->buf[1], (void*)s->buf[2], (void*)s->buf[3], (void*)s->d_kv, (void*)s->d_pcm,
-                    (void*)s->d_meta, (void*)s->d_z, (void*)s->d_emb, (void*)s->d_codes})
-        if (p) hipFree(p);
-    delete s;
 }
 
 }  // namespace
@@ -395,8 +316,8 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
             return -1;
         }
     int dry_launches = 0;
-    for (size_t g = 0; g < p.keys.size(); g++)
-        if (walk(s, p.keys[g], (int)p.members[g].size(), true, emb_out != nullptr, &dry_launches)) {
+    for (size_t g = 0; g < p.groups.keys.size(); g++)
+        if (walk(s, p.groups.keys[g], (int)p.groups.members[g].size(), true, emb_out != nullptr, &dry_launches)) {
             Q3_LOG("enc_stream_push: a push does not fit the object's work buffers");
             return -1;
         }
@@ -408,13 +329,13 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
     const size_t nops = e->ops.size();
     const int nl = (int)s->lev_s.size(), mb = e->max_batch;
     const long ldp = enc_pitch(s->max_push);
-    std::vector<std::vector<int>> metas(p.keys.size());   // (alive until the stream has drained: the uploads are asynchronous)
+    std::vector<std::vector<int>> metas(p.groups.keys.size());   // (alive until the stream has drained: the uploads are asynchronous)
     std::vector<long long> key(nl + 2), bc(nl + 1), carry(nl);
     s->last_launches = 0;
     s->last_ms = 0.f;
-    if (!p.keys.empty()) Q3_HIP(hipEventRecord(e->e0, e->s), -1);
-    for (size_t g = 0; g < p.keys.size(); g++) {
-        const std::vector<int>& mem = p.members[g];
+    if (!p.groups.keys.empty()) Q3_HIP(hipEventRecord(e->e0, e->s), -1);
+    for (size_t g = 0; g < p.groups.keys.size(); g++) {
+        const std::vector<int>& mem = p.groups.members[g];
         const int B = (int)mem.size();
         std::vector<int>& meta = metas[g];
         meta.assign((2 + nops) * mb, 0);
@@ -429,7 +350,7 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
                 Q3_HIP(hipMemcpyAsync(s->d_pcm + (size_t)b * ldp, pcm + poff[en], sizeof(float) * (size_t)n_new[en], hipMemcpyHostToDevice, e->s), -1);
         }
         Q3_HIP(hipMemcpyAsync(s->d_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, e->s), -1);
-        if (walk(s, p.keys[g], B, false, emb_out != nullptr, &s->last_launches)) return -1;
+        if (walk(s, p.groups.keys[g], B, false, emb_out != nullptr, &s->last_launches)) return -1;
     }
     if (frames > 0) {
         const EncOp& q = e->ops.back();
@@ -439,9 +360,9 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
         if (emb_out)
             Q3_HIP(hipMemcpyAsync(emb_out, s->d_emb, sizeof(float) * (size_t)frames * s->emb_C, hipMemcpyDeviceToHost, e->s), -1);
     }
-    if (!p.keys.empty()) Q3_HIP(hipEventRecord(e->e1, e->s), -1);
+    if (!p.groups.keys.empty()) Q3_HIP(hipEventRecord(e->e1, e->s), -1);
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    if (!p.keys.empty()) hipEventElapsedTime(&s->last_ms, e->e0, e->e1);
+    if (!p.groups.keys.empty()) hipEventElapsedTime(&s->last_ms, e->e0, e->e1);
     for (int i = 0; i < n; i++) {
         s->total[streams[i]] += n_new[i];
         if (finish && finish[i]) s->finished[streams[i]] = 1;
@@ -460,7 +381,7 @@ void enc_stream_free(void* ss) {
     if (!s) return;
     enc_bind(s->e);
     hipStreamSynchronize(s->e->s);
-    stream_destroy(s);
+    delete s;   // (its allocations go with it: DeviceAllocs)
 }
 
 void* enc_stream_create(void* h, int max_streams, int max_push_samples) {
@@ -489,7 +410,6 @@ void* enc_stream_create(void* h, int max_streams, int max_push_samples) {
     // product of the strides above it; + 1: the column the finish push pads out) behind at most ENC_MAX_HIST carried ones.
     size_t need = 0, need_kv = 0;
     long long P = 1;
-    int C = 1;
     auto nmax = [&]() { return (long long)(max_push_samples + P - 1) / P + 1; };
     for (size_t i = 0; i < nops; i++) {
         const EncOp& op = e->ops[i];
@@ -524,14 +444,13 @@ void* enc_stream_create(void* h, int max_streams, int max_push_samples) {
         const long long cols = nmax() + ENC_MAX_HIST;
         if (op.op == EOP_ATTN) need_kv = std::max(need_kv, (size_t)chans * enc_pitch(s->H[i] + nmax()));
         if (op.op == EOP_RVQ) break;
-        need = std::max(need, (size_t)std::max(C, std::max(op.cin, op.cout)) * enc_pitch(cols));
+        need = std::max(need, (size_t)std::max(i ? e->ops[i - 1].c_act : 1, std::max(op.cin, op.cout)) * enc_pitch(cols));
         if (op.op == EOP_CONV_S) {
             s->lev_k.push_back(op.k);
             s->lev_s.push_back(op.p0);
             P *= op.p0;
             need = std::max(need, (size_t)op.cin * op.k * enc_pitch(nmax()));
         }
-        if (!(op.op == EOP_CONV && (op.flags & EF_TO_RES))) C = op.cout;
     }
     // the embedding is the input of the projection in front of the quantiser
     if (nops < 3 || e->ops[nops - 1].op != EOP_RVQ || e->ops[nops - 2].op != EOP_CONV || e->ops[nops - 2].k != 1)
@@ -548,25 +467,18 @@ void* enc_stream_create(void* h, int max_streams, int max_push_samples) {
     s->kv_elems = std::max<size_t>(1, need_kv * mb);
     s->frames_cap = (size_t)max_streams * ((size_t)max_push_samples / e->hop + 2);
     const EncOp& q = e->ops.back();
-    bool ok = true;
-    auto alloc = [&](void** p, size_t bytes, bool zero) {
-        if (!ok) return;
-        ok = hipMalloc(p, bytes) == hipSuccess && (!zero || hipMemsetAsync(*p, 0, bytes, e->s) == hipSuccess);
-        if (ok) s->device_bytes += bytes;
-    };
+    DeviceAllocs& m = s->mem;
     const size_t slack = 1024;   // (float4 groups past a row's last column)
-    alloc((void**)&s->d_hist, sizeof(float) * std::max<size_t>(1, s->state_floats * max_streams), true);
-    for (int i = 0; i < 4; i++) alloc((void**)&s->buf[i], sizeof(float) * (s->buf_elems + slack), true);   // (zeroed once: dropped columns start finite)
-    alloc((void**)&s->d_kv, sizeof(float) * (s->kv_elems + slack), true);
-    alloc((void**)&s->d_pcm, sizeof(float) * mb * enc_pitch(max_push_samples), true);
-    alloc((void**)&s->d_meta, sizeof(int) * (2 + nops) * mb, true);
-    alloc((void**)&s->d_z, sizeof(float) * s->frames_cap * 2 * q.dim, false);
-    alloc((void**)&s->d_emb, sizeof(float) * s->frames_cap * s->emb_C, false);
-    alloc((void**)&s->d_codes, sizeof(int64_t) * s->frames_cap * q.nq, false);
-    ok = ok && hipStreamSynchronize(e->s) == hipSuccess;
+    bool ok = m.alloc_zeroed(&s->d_hist, sizeof(float) * std::max<size_t>(1, s->state_floats * max_streams), e->s);
+    for (int i = 0; i < 4; i++) ok = ok && m.alloc_zeroed(&s->buf[i], sizeof(float) * (s->buf_elems + slack), e->s);   // (zeroed once: dropped columns start finite)
+    ok = ok && m.alloc_zeroed(&s->d_kv, sizeof(float) * (s->kv_elems + slack), e->s) &&
+         m.alloc_zeroed(&s->d_pcm, sizeof(float) * mb * enc_pitch(max_push_samples), e->s) &&
+         m.alloc_zeroed(&s->d_meta, sizeof(int) * (2 + nops) * mb, e->s) && m.alloc(&s->d_z, sizeof(float) * s->frames_cap * 2 * q.dim) &&
+         m.alloc(&s->d_emb, sizeof(float) * s->frames_cap * s->emb_C) && m.alloc(&s->d_codes, sizeof(int64_t) * s->frames_cap * q.nq) &&
+         hipStreamSynchronize(e->s) == hipSuccess;
     if (!ok) {
         Q3_LOG("enc_stream_create: device allocation failed");
-        stream_destroy(s);
+        delete s;
         return nullptr;
     }
     return s;
@@ -600,6 +512,6 @@ int enc_stream_push(void* s, int n, const int32_t* streams, const float* pcm, co
 float enc_stream_last_ms(void* s) { return s ? ((EncStream*)s)->last_ms : -1.f; }
 int enc_stream_last_launches(void* s) { return s ? ((EncStream*)s)->last_launches : -1; }
 int64_t enc_stream_state_bytes(void* s) { return s ? (int64_t)(((EncStream*)s)->state_floats * sizeof(float)) : -1; }
-int64_t enc_stream_device_bytes(void* s) { return s ? (int64_t)((EncStream*)s)->device_bytes : -1; }
+int64_t enc_stream_device_bytes(void* s) { return s ? (int64_t)((EncStream*)s)->mem.bytes : -1; }
 
 }  // extern "C"

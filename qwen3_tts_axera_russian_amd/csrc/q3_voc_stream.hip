@@ -472,7 +472,8 @@ struct VocIncr {
     long long* d_off = nullptr;           // [max_batch]: where each entry's samples start in the packed output
     float* d_out = nullptr;               // packed output of a push
     int16_t* d_out16 = nullptr;
-    size_t out_cap = 0, device_bytes = 0;
+    size_t out_cap = 0;
+    DeviceAllocs mem;                     // every device buffer of the object (h_ovf is pinned host memory: incr_destroy)
     float last_ms = 0.f;
     int last_launches = 0;
     // split-fp16 arithmetic (voc_incr_set_arithmetic), allocated by the first switch to it.  The history is then double-buffered:
@@ -742,17 +743,15 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
 }
 
 struct IncrPlan {
-    std::vector<long long> n_out;                       // per entry
-    std::vector<std::vector<long long>> keys;           // per group
-    std::vector<std::vector<int>> members;              // per group: entry indices
+    std::vector<long long> n_out;   // per entry
+    PushGroups groups;              // keys: incr_key
 };
 
 int incr_plan(const VocIncr* s, int n, const int32_t* streams, const int32_t* n_new, IncrPlan& p) {
     const Voc* v = s->v;
     if (n < 0 || (n > 0 && (!streams || !n_new))) return -1;
     p.n_out.assign(n, 0);
-    p.keys.clear();
-    p.members.clear();
+    p.groups = PushGroups();
     std::vector<char> seen(s->max_streams, 0);
     std::vector<long long> key;
     const size_t nops = v->ops.size();
@@ -774,13 +773,7 @@ int incr_plan(const VocIncr* s, int n, const int32_t* streams, const int32_t* n_
         }
         incr_key(v, s->n_frames[k], s->n_frames[k] + n_new[i], key);
         p.n_out[i] = key[nops];
-        size_t g = 0;
-        while (g < p.keys.size() && (p.keys[g] != key || (int)p.members[g].size() >= v->max_batch)) g++;
-        if (g == p.keys.size()) {
-            p.keys.push_back(key);
-            p.members.emplace_back();
-        }
-        p.members[g].push_back(i);
+        p.groups.add(key, i, v->max_batch);
     }
     return 0;
 }
@@ -817,7 +810,7 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
     s->last_ms = 0.f;
     s->last_split = 0;
     s->last_redone = 0;
-    if (!p.keys.empty()) Q3_HIP(hipEventRecord(v->e0, v->s), -1);
+    if (!p.groups.keys.empty()) Q3_HIP(hipEventRecord(v->e0, v->s), -1);
     // one launch sequence over the entries `mem` of a group, on the split or the exact branch, complete on return
     auto run_group = [&](const std::vector<long long>& key, const std::vector<int>& mem, bool split) -> int {
         const int B = (int)mem.size(), T = n_new[mem[0]];
@@ -850,9 +843,9 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
         return 0;
     };
     std::vector<int> redo;
-    for (size_t g = 0; g < p.keys.size(); g++) {
-        const std::vector<int>& mem = p.members[g];
-        if (run_group(p.keys[g], mem, s->split != 0)) return -1;
+    for (size_t g = 0; g < p.groups.keys.size(); g++) {
+        const std::vector<int>& mem = p.groups.members[g];
+        if (run_group(p.groups.keys[g], mem, s->split != 0)) return -1;
         if (s->split) {
             // a push is a transaction per entry: an entry whose planes left the fp16 range is not committed -- the flagged
             // entries of the group run again, from their uncommitted history, on the exact branch, and their samples replace the
@@ -864,14 +857,14 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
                 if (!s->warned_ovf)
                     Q3_LOG("vocoder incremental: activation outside the fp16 range, decoding this entry's push with the exact-fp32 path");
                 s->warned_ovf = true;
-                if (run_group(p.keys[g], redo, false)) return -1;
+                if (run_group(p.groups.keys[g], redo, false)) return -1;
                 s->last_redone += (int)redo.size();
             }
         }
         if (s->d_hist1)
             for (int e : mem) s->parity[streams[e]] ^= 1;   // commit: the written buffer is the stream's history now
     }
-    if (!p.keys.empty()) {
+    if (!p.groups.keys.empty()) {
         Q3_HIP(hipEventRecord(v->e1, v->s), -1);
         if (total > 0)
             if (voc_read_back(v, out, want16 ? (void*)s->d_out16 : (void*)s->d_out, (want16 ? sizeof(int16_t) : sizeof(float)) * (size_t)total))
@@ -888,12 +881,8 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
 
 void incr_destroy(VocIncr* s) {
     if (!s) return;
-    for (void* p : {(void*)s->d_hist, (void*)s->buf[0], (void*)s->buf[1], (void*)s->buf[2], (void*)s->d_kv, (void*)s->d_codes,
-                    (void*)s->d_meta, (void*)s->d_off, (void*)s->d_out, (void*)s->d_out16, (void*)s->d_hist1, (void*)s->plane[0],
-                    (void*)s->plane[1], (void*)s->plane[2], (void*)s->plane[3], (void*)s->d_par, (void*)s->d_ovf})
-        if (p) hipFree(p);
     if (s->h_ovf) hipHostFree(s->h_ovf);
-    delete s;
+    delete s;   // (its device allocations go with it: DeviceAllocs)
 }
 }  // namespace
 
@@ -965,20 +954,13 @@ void* voc_incr_create(void* vv, int max_streams) {
     const size_t buf_elems = need * mb + 1024, kv_elems = need_kv * mb + 1024;   // (+ slack: float4 groups past a row's last column)
     s->buf_elems = buf_elems;
     s->out_cap = (size_t)max_streams * v->chunk * v->upsample;
-    auto alloc = [&](void** p, size_t bytes, bool zero) {
-        if (!ok) return;
-        ok = hipMalloc(p, bytes) == hipSuccess && (!zero || hipMemsetAsync(*p, 0, bytes, v->s) == hipSuccess);
-        if (ok) s->device_bytes += bytes;
-    };
-    alloc((void**)&s->d_hist, sizeof(float) * std::max<size_t>(1, s->state_floats * max_streams), true);
-    for (int i = 0; i < 3; i++) alloc((void**)&s->buf[i], sizeof(float) * buf_elems, true);   // (zeroed once: dropped columns start finite)
-    alloc((void**)&s->d_kv, sizeof(float) * kv_elems, true);
-    alloc((void**)&s->d_codes, sizeof(int64_t) * 16 * v->chunk * mb, false);
-    alloc((void**)&s->d_meta, sizeof(int) * (1 + nops) * mb, false);
-    alloc((void**)&s->d_off, sizeof(long long) * mb, false);
-    alloc((void**)&s->d_out, sizeof(float) * s->out_cap, false);
-    alloc((void**)&s->d_out16, sizeof(int16_t) * s->out_cap, false);
-    ok = ok && hipStreamSynchronize(v->s) == hipSuccess;   // the zeroing above
+    DeviceAllocs& m = s->mem;
+    ok = m.alloc_zeroed(&s->d_hist, sizeof(float) * std::max<size_t>(1, s->state_floats * max_streams), v->s);
+    for (int i = 0; i < 3; i++) ok = ok && m.alloc_zeroed(&s->buf[i], sizeof(float) * buf_elems, v->s);   // (zeroed once: dropped columns start finite)
+    ok = ok && m.alloc_zeroed(&s->d_kv, sizeof(float) * kv_elems, v->s) && m.alloc(&s->d_codes, sizeof(int64_t) * 16 * v->chunk * mb) &&
+         m.alloc(&s->d_meta, sizeof(int) * (1 + nops) * mb) && m.alloc(&s->d_off, sizeof(long long) * mb) &&
+         m.alloc(&s->d_out, sizeof(float) * s->out_cap) && m.alloc(&s->d_out16, sizeof(int16_t) * s->out_cap) &&
+         hipStreamSynchronize(v->s) == hipSuccess;   // the zeroing above
     if (!ok) {
         Q3_LOG("voc_incr_create: device allocation failed");
         incr_destroy(s);
@@ -1023,7 +1005,7 @@ int voc_incr_push_f32(void* s, int n, const int32_t* streams, const int64_t* cod
 float voc_incr_last_ms(void* s) { return s ? ((VocIncr*)s)->last_ms : -1.f; }
 int voc_incr_last_launches(void* s) { return s ? ((VocIncr*)s)->last_launches : -1; }
 int64_t voc_incr_state_bytes(void* s) { return s ? (int64_t)(((VocIncr*)s)->state_floats * sizeof(float)) : -1; }
-int64_t voc_incr_device_bytes(void* s) { return s ? (int64_t)((VocIncr*)s)->device_bytes : -1; }
+int64_t voc_incr_device_bytes(void* s) { return s ? (int64_t)((VocIncr*)s)->mem.bytes : -1; }
 
 int voc_incr_set_arithmetic(void* ss, int split) {
     VocIncr* s = (VocIncr*)ss;
@@ -1052,31 +1034,27 @@ int voc_incr_set_arithmetic(void* ss, int split) {
         Voc* v = s->v;
         voc_bind(v);
         const size_t mb = (size_t)v->max_batch, hist = sizeof(float) * std::max<size_t>(1, s->state_floats * s->max_streams);
-        void* got[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        const size_t bytes[7] = {hist, sizeof(_Float16) * s->buf_elems, sizeof(_Float16) * s->buf_elems, sizeof(_Float16) * s->buf_elems,
-                                 sizeof(_Float16) * s->buf_elems, sizeof(int) * mb, sizeof(int) * mb};
-        int* h = nullptr;
-        bool ok = hipHostMalloc((void**)&h, sizeof(int) * mb, 0) == hipSuccess;
-        for (int i = 0; i < 7 && ok; i++) ok = hipMalloc(&got[i], bytes[i]) == hipSuccess;
+        DeviceAllocs got;   // all or nothing: the object adopts it once every buffer is there and filled
+        float* hist1 = nullptr;
+        _Float16* plane[4] = {nullptr, nullptr, nullptr, nullptr};
+        int *par = nullptr, *ovf = nullptr, *h = nullptr;
+        bool ok = hipHostMalloc((void**)&h, sizeof(int) * mb, 0) == hipSuccess && got.alloc(&hist1, hist);
+        for (int i = 0; i < 4; i++) ok = ok && got.alloc_zeroed(&plane[i], sizeof(_Float16) * s->buf_elems, v->s);
         // the history a fresh stream continues from is zero in both buffers (a stream that ran in exact mode and finished is reset
         // before its next utterance, which zeroes both)
-        ok = ok && hipMemcpyAsync(got[0], s->d_hist, hist, hipMemcpyDeviceToDevice, v->s) == hipSuccess &&
-             hipMemsetAsync(got[1], 0, bytes[1], v->s) == hipSuccess && hipMemsetAsync(got[2], 0, bytes[2], v->s) == hipSuccess &&
-             hipMemsetAsync(got[3], 0, bytes[3], v->s) == hipSuccess && hipMemsetAsync(got[4], 0, bytes[4], v->s) == hipSuccess &&
-             hipStreamSynchronize(v->s) == hipSuccess;
+        ok = ok && got.alloc(&par, sizeof(int) * mb) && got.alloc(&ovf, sizeof(int) * mb) &&
+             hipMemcpyAsync(hist1, s->d_hist, hist, hipMemcpyDeviceToDevice, v->s) == hipSuccess && hipStreamSynchronize(v->s) == hipSuccess;
         if (!ok) {
             Q3_LOG("voc_incr_set_arithmetic: device allocation failed");
-            for (void* p : got)
-                if (p) hipFree(p);
             if (h) hipHostFree(h);
-            return -1;
+            return -1;   // (`got` frees what it had)
         }
-        s->d_hist1 = (float*)got[0];
-        for (int i = 0; i < 4; i++) s->plane[i] = (_Float16*)got[1 + i];
-        s->d_par = (int*)got[5];
-        s->d_ovf = (int*)got[6];
+        s->mem.adopt(got);
+        s->d_hist1 = hist1;
+        std::copy(plane, plane + 4, s->plane);
+        s->d_par = par;
+        s->d_ovf = ovf;
         s->h_ovf = h;
-        for (int i = 0; i < 7; i++) s->device_bytes += bytes[i];
     }
     s->split = split;
     return s->split;

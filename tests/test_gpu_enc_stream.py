@@ -97,6 +97,8 @@ def splits(n, hop, kind, seed=0):
     """-> [(samples of the push, finish)]: how a clip of n samples reaches its stream"""
     if kind == "one":
         return [(n, True)]
+    if kind == "ones":
+        return [(1, False)] * n + [(0, True)]
     if kind == "hop":
         sizes = [hop] * (n // hop) + ([n % hop] if n % hop else [])
     elif kind == "edges":
@@ -248,6 +250,30 @@ def test_full_config_edge_lengths(lib, test_lib, full_synth):
         st.close()
         small.close()
         ref.close()
+
+
+@pytest.mark.parametrize("n_hops, rest", [(0, 1), (0, 5), (1, 3)], ids=["1", "5", "hop+3"])
+def test_tiny_clips_a_sample_at_a_time(lib, test_lib, tiny_synth, n_hops, rest):
+    """Clips of 1, 5 and hop + 3 samples (shorter than the first conv's 7 taps; one frame and a remainder) pushed a sample at a
+    time and finished by an empty push: left of its one new column the first conv of every push reads only the stream's carried
+    samples, zeros at the start.  Contracts 1-3: the bits of the whole clip in one push, the hand-out rule after every push
+    (run_streams), enc_encode's frames, embedding and ids."""
+    ec, t, path = tiny_synth
+    hop = W.enc_hop(ec)
+    n = n_hops * hop + rest
+    clip = C.seeded_clip(31, n)
+    enc = Encoder(path, max_batch=1, max_samples=hop + 3)
+    st = enc.stream(1, hop + 3)
+    try:
+        bytes0 = st.device_bytes()
+        ones = run_streams(test_lib, st, ec, {0: (clip, splits(n, hop, "ones"))})[0]
+        whole = run_streams(test_lib, st, ec, {0: (clip, splits(n, hop, "one"))})[0]
+        assert same_bits(ones, whole), f"{n} samples: pushing a sample at a time changes the bits"
+        against_one_shot(lib, enc, ec, t, clip, ones, f"tiny config {n}, a sample at a time")
+        assert st.device_bytes() == bytes0
+    finally:
+        st.close()
+        enc.close()
 
 
 def test_every_refused_push_leaves_the_streams_alone(lib, test_lib, tiny_synth):
