@@ -166,15 +166,32 @@ int q3e_release(void* e, int n, const int32_t* slots);
  * <0 with nothing written (the call can be retried): the slot is not a live text slot, a push after the final one,
  * rows beyond the reservation, a non-finite value.
  *
- * A slot never runs ahead of its text: while a live slot's text is not final, q3e_run executes no step whose frame has
- * no row yet -- it runs the steps every such slot has rows for and returns their number, which may be 0.  Row i is
- * therefore always consumed at frame i: a slot's codes depend on its text and on nothing about arrival times.  A starved
- * slot stalls the WHOLE batch (holding one row's logits, KV and counters inside the captured frame is deliberately not
- * built): the host decides whether to wait, push, or release the slot.
+ * A slot never runs ahead of its text: row i is always consumed at frame i, so a slot's codes depend on its text and on
+ * nothing about arrival times.  What a live text slot WITHOUT a row for its next frame (a starved slot) does to the
+ * others depends on the mode:
+ *   - default: it stalls the WHOLE batch.  q3e_run executes no step whose frame has no row yet -- it runs the steps every
+ *     such slot has rows for and returns their number, which may be 0; the host decides whether to wait, push, or
+ *     release the slot.
+ *   - q3e_text_hold(e, 1), called between q3e_text_reserve and q3e_open (<0 with nothing changed without a reservation
+ *     or while a per-slot batch is open; it changes arguments of the captured frame, so the next q3e_run captures
+ *     again): the starved slot is HELD inside the frame and the others step on.  The sampler leaves a held row's
+ *     counters, codes and logits alone, the code predictor continues with the ids the row's last frame records, and the
+ *     rest of the frame thereby recomputes the row's previous step onto itself: after the step the row's state is, bit
+ *     for bit, what it was before, and the other rows never depended on it.  q3e_run then executes min(n_frames, the
+ *     most steps a live slot can still use) steps: up to its rows for a text slot before its final push, up to its
+ *     budget for any other; 0 only when every live slot is held -- or when some live text slot has no frame yet and
+ *     no row (nothing of its own to repeat: such a slot still stalls the batch, so admit a text slot with its first
+ *     row at hand).  Slots then differ in the frames they have emitted by the steps they were held for; q3e_get_done,
+ *     q3e_get_codes and q3e_release keep their contracts with those per-slot counts.  A push lifts the hold from the
+ *     next step on (a final push with n = 0 as well: the slot goes on with pad rows), releasing a held slot ends it, and
+ *     a slot at its budget is never held, so it ends there.
  *
  * q3e_text_state: rows[b] = rows pushed to slot b (0: not a text slot), starved[b] = 1 when slot b is a live text slot
- * the next step waits for.  Either pointer may be NULL.  0 ok / <0 error. */
+ * the next step waits for (in either mode).  Either pointer may be NULL.  q3e_text_held: held_steps[b] = frame steps
+ * slot b's utterance was held for since its admission (0 without q3e_text_hold).  0 ok / <0 error. */
 int q3e_text_reserve(void* e, int max_rows);
+int q3e_text_hold(void* e, int on);
+int q3e_text_held(void* e, int64_t* held_steps /*[B]*/);
 int q3e_push_text(void* e, int slot, const float* rows, int n, int final, int n_text_total);
 int q3e_text_state(void* e, int32_t* rows /*[B]*/, int32_t* starved /*[B]*/);
 

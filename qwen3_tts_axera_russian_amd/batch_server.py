@@ -65,6 +65,13 @@ send its text in that time fails its own request (-2, its slot is released) -- t
 gets from --send_timeout.  The reply's codes and PCM depend on the text and not on how it was cut or when it arrived.  The
 text may not have more tokens than the request's max_tokens (a row per frame).
 
+`--text_hold` (with `--concurrent`): a starved text slot is HELD inside the frame (q3e_text_hold) and every other slot steps
+on, so a text client that pauses costs the other requests no time -- their replies did not depend on the traffic, now their
+timing does not either.  A held row still computes (it repeats its previous step onto itself), so held steps are frame-loop
+throughput the others do not get back.  A text-stream request is then admitted once its first row is there (a second token,
+or the end record), waiting in the queue like any queued request until then; a request whose slot has been held for
+--text_wait_ms with no byte from its client fails alone (-2, its slot is released), and the others see nothing of it.
+
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
 vocoder then launches one persistent workgroup per compute unit (voc_set_max_workgroups(-1)), which leaves the frame loop's
@@ -97,7 +104,7 @@ class BatchSynthesisServer:
     def __init__(self, model_path, vocoder_path, socket_path="/tmp/qwen3_batch.sock", max_batch=32, n_ctx=512,
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
-                 cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0):
+                 cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens = socket_path, max_batch, max_tokens
@@ -111,6 +118,9 @@ class BatchSynthesisServer:
         self.check_every = int(check_every)
         self.send_timeout = float(send_timeout)
         self.text_wait_ms = float(text_wait_ms)
+        if text_hold and not concurrent:
+            raise ValueError("--text_hold holds text slots of the shared frame loop: it needs --concurrent")
+        self.text_hold = bool(text_hold)
         self.sched = None
         # utterances one request may queue (the server is single-threaded: an unbounded request holds it indefinitely)
         self.max_request = int(max_request) if max_request else 8 * max_batch
@@ -449,9 +459,12 @@ class BatchSynthesisServer:
             self._vstream = self.voc.stream(self.max_batch)
         self._lib.voc_set_max_workgroups(-1)     # the vocoder runs beside the frame loop: one workgroup per CU
         self.eng.reserve_text(self.max_tokens)   # before the scheduler opens the batch: a row per frame of every slot
+        if self.text_hold:
+            self.eng.hold_text()                 # a text slot without a row is held inside the frame: the others step on
         self.sched = ConcurrentScheduler(self.eng, self.max_batch, self.max_queue, self._prepare, self._finish, self._push,
                                          self._close_stream, self._send_error, check_every=self.check_every,
-                                         send_timeout=self.send_timeout, text_wait_ms=self.text_wait_ms)
+                                         send_timeout=self.send_timeout, text_wait_ms=self.text_wait_ms,
+                                         text_hold=self.text_hold)
         self.sched.start()
         print(f"Batch synthesis server listening on {self.socket_path} (--concurrent: {self.max_batch} slots shared by every "
               f"request, up to {self.max_queue} queued utterances)")
@@ -507,6 +520,7 @@ class TextFeed:
         self._by_text = encoder is not None
         self._parser = P.TextRecordParser()
         self._rows = [project(first_ids)] if len(first_ids) else []
+        self.last_rx = time.monotonic()                     # when the client's last bytes arrived (the request itself at first)
         self.n_tokens = int(n_tokens) + len(first_ids)     # text tokens so far (the final push's n_text)
         self.ended = False                                  # the end-of-text record has arrived
         self.final_pushed = False
@@ -542,8 +556,13 @@ class TextFeed:
                 return True
             if not data:
                 return False
+            self.last_rx = time.monotonic()
             self.records(data)
         return True
+
+    def ready(self):
+        """Whether take() has something for the engine: at least one row, or the end of the text."""
+        return bool(self._rows) or (self.ended and not self.final_pushed)
 
     def take(self):
         """-> (rows [n][hidden] to push now, whether they end the text)."""
@@ -563,6 +582,7 @@ class _Request:
         self.state = {"failed": False, "n": self.n, "frames": 0}   # the push worker's view (BatchSynthesisServer._push)
         self.gone = False                       # the client went away or the request failed: its slots are released
         self.feed = next((it[4] for it in items if len(it) > 4), None)   # TextFeed of a "text_stream" request
+        self.starved_since = None               # text_hold: since when its slot has been held (None: it is not)
 
 
 class ConcurrentScheduler:
@@ -582,10 +602,17 @@ class ConcurrentScheduler:
     thread reads what its client has sent and pushes the rows (eng.push_text); a check that runs no frame because such a slot
     waits for its text (eng.text_state) polls the starving requests' connections for at most text_wait_ms, after which a
     request that has still sent nothing fails (-2) and its slot is released -- the stall is the whole batch's, so it is
-    bounded the same way a stalled reader is."""
+    bounded the same way a stalled reader is.
+
+    text_hold (the engine was told eng.hold_text() before this scheduler opens the batch): a text slot without a row is held
+    inside the frame and the other slots step on, so a slow text client costs nobody else time.  A text-stream request is then
+    admitted only once its feed has its first row (a slot without a frame cannot be held), waiting in the queue meanwhile
+    while later requests pass it; a request whose slot has been held for text_wait_ms with no byte received from its client
+    fails alone (-2, slot released); starved_checks counts only the checks that ran no frame (every live slot held), and
+    held_steps sums the frame steps requests were held for."""
 
     def __init__(self, eng, max_batch, max_queue, prepare, reply, push, close_stream, send_error, check_every=8,
-                 send_timeout=30.0, text_wait_ms=200.0):
+                 send_timeout=30.0, text_wait_ms=200.0, text_hold=False):
         from concurrent.futures import ThreadPoolExecutor
         self.eng, self.B, self.max_queue, self.check_every = eng, int(max_batch), int(max_queue), int(check_every)
         self._prepare, self._reply, self._push, self._close_stream, self._send_error = prepare, reply, push, close_stream, send_error
@@ -599,6 +626,8 @@ class ConcurrentScheduler:
         self.send_timeout = float(send_timeout)
         self.text_wait_ms = float(text_wait_ms)
         self.starved_checks = 0                 # checks that ran no frame because a text slot waited for its text
+        self.text_hold = bool(text_hold)
+        self.held_steps = 0                     # text_hold: frame steps text slots were held for, summed over requests
 
     # ---- accept side ----
     def submit(self, conn, msg, t0=None):
@@ -703,6 +732,52 @@ class ConcurrentScheduler:
                 self._fail(req, f"text stream: no text for {self.text_wait_ms:.0f} ms while the frame loop waited for it")
         return True
 
+    def _text_ready(self, req):
+        """Engine side, text_hold: whether a queued text-stream request has its first row (so that its slot never waits
+        without a frame).  A client that closed its sending side before any row fails here."""
+        try:
+            if not req.feed.poll(req.conn):
+                raise ValueError("the client closed its sending side before the end of its text")
+        except Exception as e:
+            self._fail(req, f"text stream: {e}")
+            return False
+        return req.feed.ready()
+
+    def _check_held(self, owner, ran, last_held):
+        """Engine side, text_hold, after every check: count the held steps, fail the requests whose slot has been held for
+        text_wait_ms without a byte from their client, and -- after a check that ran no frame because every live slot is
+        held -- wait a moment for one of them to send something.  -> True if the check was such a starved one."""
+        held = self.eng.held_steps()
+        for b in range(self.B):
+            if owner[b] is not None:
+                self.held_steps += int(held[b]) - last_held[b]
+                last_held[b] = int(held[b])
+        _, starved = self.eng.text_state()
+        now = time.monotonic()
+        waiting = {}
+        for b in range(self.B):
+            req = owner[b][0] if owner[b] is not None else None
+            if req is None or req.feed is None or req.gone:
+                continue
+            if not starved[b]:
+                req.starved_since = None
+                continue
+            if req.starved_since is None:
+                req.starved_since = now
+            idle_ms = (now - max(req.starved_since, req.feed.last_rx)) * 1e3
+            if idle_ms >= self.text_wait_ms:
+                self._fail(req, f"text stream: no text for {self.text_wait_ms:.0f} ms while its slot was held")
+            else:
+                waiting[id(req)] = (req, self.text_wait_ms - idle_ms)
+        if ran != 0 or not waiting:
+            return ran == 0 and bool(starved.any())
+        self.starved_checks += 1
+        p = select.poll()
+        for req, _ in waiting.values():
+            p.register(req.conn.fileno(), select.POLLIN)
+        p.poll(max(1.0, min([20.0] + [left for _, left in waiting.values()])))   # short: a new request must not wait for it
+        return True
+
     def _engine_main(self):
         owner = [None] * self.B                 # (request, utt) of each slot
         try:
@@ -723,6 +798,7 @@ class ConcurrentScheduler:
         eng, B = self.eng, self.B
         eng.open(B)
         pushed = [0] * B
+        last_held = [0] * B                    # text_hold: eng.held_steps() of each slot at the last check
         pending_pushes = []
         while True:
             with self._cv:
@@ -731,16 +807,28 @@ class ConcurrentScheduler:
                 if not self._running:
                     break
                 free = [b for b in range(B) if owner[b] is None]
-                take = []
+                take, later = [], []
                 while self._queue and len(take) < len(free):
                     req, it = self._queue.popleft()
-                    if not req.gone:
-                        take.append((req, it))
-            for req in {id(r): r for r, _ in take}.values():   # a client that left while its request waited
+                    if req.gone:
+                        continue
+                    if self.text_hold and req.feed is not None and not self._client_gone(req) and not self._text_ready(req):
+                        if not req.gone:
+                            later.append((req, it))   # no row yet: it keeps its place, those behind it pass
+                        continue
+                    take.append((req, it))
+                self._queue.extendleft(reversed(later))
+            for req in {id(r): r for r, _ in take + later}.values():   # a client that left while its request waited
                 if self._client_gone(req):
                     self._drop(req)
             take = [(r, it) for r, it in take if not r.gone]
             if not take and all(o is None for o in owner):
+                waiting = [r for r, _ in later if not r.gone]
+                if waiting:                    # only text requests without a row are queued: until one of them sends (or leaves)
+                    p = select.poll()
+                    for r in waiting:
+                        p.register(r.conn.fileno(), select.POLLIN)
+                    p.poll(20.0)               # (short: a request submitted meanwhile is looked at soon)
                 continue                       # what was queued has left and nothing is live: back to waiting
             resets = collections.defaultdict(list)
             if take:
@@ -749,6 +837,7 @@ class ConcurrentScheduler:
                 for b, (req, it) in zip(slots, take):
                     owner[b] = (req, it[0])
                     pushed[b] = 0
+                    last_held[b] = 0
                     if req.stream:
                         resets[id(req)].append(b)
             text_live = any(o is not None and o[0].feed is not None for o in owner)
@@ -756,7 +845,10 @@ class ConcurrentScheduler:
                 self._feed_text(owner)
             ran = eng.run(self.check_every)
             self.frame_steps += ran
-            waited = ran == 0 and text_live and self._wait_for_text(owner)
+            if self.text_hold:
+                waited = text_live and self._check_held(owner, ran, last_held)
+            else:
+                waited = ran == 0 and text_live and self._wait_for_text(owner)
             done, per = eng.done()
             # clients that went away: their slots go idle now
             live = {id(o[0]): o[0] for o in owner if o is not None}
@@ -1058,11 +1150,14 @@ def main():
                     help="--concurrent: seconds one write to a client may block before its request fails")
     ap.add_argument("--text_wait_ms", type=float, default=200.0,
                     help="--concurrent: milliseconds the frame loop waits for a text-stream client's text before its request fails")
+    ap.add_argument("--text_hold", action="store_true",
+                    help="--concurrent: a text-stream request without text for its next frame is held inside the frame while the "
+                         "other requests go on (default: the whole frame loop waits for it)")
     a = ap.parse_args()
     srv = BatchSynthesisServer(a.model, a.vocoder, a.socket, a.max_batch, a.n_ctx, a.max_tokens, a.temperature, a.top_k,
                                a.cp_temperature, a.tokenizer, a.seed, pipeline=a.pipeline, concurrent=a.concurrent,
                                max_queue=a.max_queue, top_p=a.top_p, cp_top_k=a.cp_top_k, check_every=a.check_every,
-                               send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms)
+                               send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms, text_hold=a.text_hold)
     try:
         srv.serve()
     finally:

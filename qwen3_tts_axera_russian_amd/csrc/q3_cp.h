@@ -17,6 +17,7 @@ struct CpFrameIO {
     const float* text_rows = nullptr;   // per-slot text rows standing where the pad stands (see CpArgmaxArgs); null = none
     const int* text_avail = nullptr;
     int text_cap = 0;
+    const int* held = nullptr;          // rows held in this step (see CpArgmaxArgs); null = none
     // sampling of the 15 groups (code_predictor_server.py:87-92): temperature <= 1e-6 = arg-max
     float temperature = 0.f;
     int top_k = 50;

@@ -128,6 +128,7 @@ int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const C
         x.seed_ptr = io.seed_ptr;
         x.forced = io.forced;
         x.slots = io.slots;
+        x.held = io.held;
         if (g + 1 < G) {
             x.next_table = m.cp_emb[g];  // group g+1 embeds token g with CP table g (:134)
             x.h_out = w.h;

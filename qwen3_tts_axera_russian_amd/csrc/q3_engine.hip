@@ -71,7 +71,19 @@ struct Engine {
     std::vector<int> h_trows;               // rows pushed per slot
     std::vector<char> h_text, h_tfinal;     // the slot holds a text utterance / its text has ended
     int up_i[2] = {0, 0};                   // staging of one-word uploads (synchronised before reuse)
+    // held text slots (q3e_text_hold): a live text slot without a row for its next frame is held inside the frame while
+    // the other rows step on; h_age then counts the steps a slot was NOT held for (= the frames it has emitted)
+    bool hold = false;
+    int* d_held = nullptr;                  // [max_batch] the sampler's per-step verdict, read by the frame's cp_argmax launches
+    std::vector<long long> h_held;          // steps each slot was held for since its admission
 };
+
+// the device's verdict for slot b at its next step (talker_sample_row<true>), from the host's copies: a live text slot
+// before its final push has not ended, and has emitted h_age frames
+bool slot_held(const Engine* e, int b) {
+    return e->hold && e->h_live[b] && e->h_text[b] && !e->h_tfinal[b] && e->h_age[b] >= 1 && e->h_age[b] >= e->h_trows[b] &&
+           e->h_age[b] < e->h_budget[b];
+}
 
 // steps a per-slot batch may take before a live text slot whose text has not ended would need a row it does not have
 int text_room(const Engine* e) {
@@ -152,6 +164,10 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     sa.seed_ptr = e->d_seed;
     sa.forced = e->forced_on ? e->d_forced : nullptr;
     sa.slots = e->slot_mode ? e->d_slots : nullptr;
+    if (e->slot_mode && e->d_text && e->hold) {
+        sa.text_avail = e->d_tavail;
+        sa.held = e->d_held;
+    }
     if (launch_talker_sample(st, sa)) return -1;
     CpFrameIO io;
     io.codes = e->d_codes;
@@ -166,6 +182,7 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
         io.text_rows = e->d_text;
         io.text_avail = e->d_tavail;
         io.text_cap = e->text_cap;
+        if (e->hold) io.held = e->d_held;
     }
     io.temperature = e->c_temp;
     io.top_k = e->c_top_k;
@@ -258,7 +275,7 @@ void q3e_free(void* ee) {
     work_free(e->wc);
     void* ps[] = {e->d_tiles, e->d_slot, e->d_pos,  e->d_iota,   e->d_past,    e->d_npast, e->d_ntext, e->d_done,
                   e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots,
-                  e->d_text, e->d_tavail};
+                  e->d_text, e->d_tavail, e->d_held};
     for (void* p : ps)
         if (p) hipFree(p);
     if (e->h_done) hipHostFree(e->h_done);
@@ -576,7 +593,21 @@ int q3e_run(void* ee, int n_frames) {
         room = 0;
         for (int b = 0; b < e->B; b++)
             if (e->h_live[b]) room = std::max(room, e->h_budget[b] - e->h_age[b]);
-        room = std::min(room, text_room(e));   // a slot never runs ahead of its text: a starved slot stalls the batch
+        if (!e->hold) {
+            room = std::min(room, text_room(e));   // a slot never runs ahead of its text: a starved slot stalls the batch
+        } else {
+            // held text slots: the steps the slot with the most progress ahead of it can take -- up to its rows (or its
+            // budget) for a text slot before its final push, the budget for any other.  0 when every live slot is held.
+            // A text slot that has no frame yet cannot be held (there is no step of its own to repeat): it stalls the batch.
+            room = 0;
+            for (int b = 0; b < e->B; b++) {
+                if (!e->h_live[b]) continue;
+                const bool waits = e->h_text[b] && !e->h_tfinal[b];
+                if (waits && e->h_age[b] == 0 && e->h_trows[b] == 0) return 0;
+                const int upto = waits ? std::min(e->h_trows[b], e->h_budget[b]) : e->h_budget[b];
+                room = std::max(room, upto - e->h_age[b]);
+            }
+        }
     }
     if (room <= 0) return 0;
     if (n_frames > room) n_frames = room;
@@ -640,8 +671,21 @@ int q3e_run(void* ee, int n_frames) {
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     hipEventElapsedTime(&e->last_run_ms, e->ev0, e->ev1);
     if (e->slot_mode) {
-        for (int b = 0; b < e->B; b++)
-            if (e->h_age[b] >= 0) e->h_age[b] = std::min(e->h_age[b] + done_frames, e->max_frames);
+        for (int b = 0; b < e->B; b++) {
+            if (e->h_age[b] < 0) continue;
+            if (!e->hold) {
+                e->h_age[b] = std::min(e->h_age[b] + done_frames, e->max_frames);
+                continue;
+            }
+            // step by step as the device decided (no row arrives during a run, so a slot that is held stays held)
+            for (int i = 0; i < done_frames; i++) {
+                if (slot_held(e, b)) {
+                    e->h_held[b] += done_frames - i;
+                    break;
+                }
+                e->h_age[b] = std::min(e->h_age[b] + 1, e->max_frames);
+            }
+        }
         return done_frames;
     }
     e->frames_run += done_frames;
@@ -767,6 +811,8 @@ int q3e_open(void* ee, int B, int ignore_eos) {
     e->h_trows.assign(B, 0);
     e->h_text.assign(B, 0);
     e->h_tfinal.assign(B, 0);
+    e->h_held.assign(B, 0);
+    if (e->d_held) Q3_HIP(hipMemsetAsync(e->d_held, 0, sizeof(int) * e->max_batch, e->s), -1);
     if (e->d_tavail) Q3_HIP(hipMemsetAsync(e->d_tavail, 0, sizeof(int) * e->max_batch, e->s), -1);
     if (e->forced_on) {
         e->forced_on = false;
@@ -865,6 +911,7 @@ int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const 
         e->h_trows[ids[u]] = 0;
         e->h_text[ids[u]] = sp[u].flags ? 1 : 0;
         e->h_tfinal[ids[u]] = 0;
+        e->h_held[ids[u]] = 0;
     }
     return 0;
 }
@@ -889,7 +936,10 @@ int q3e_text_reserve(void* ee, int max_rows) {
     e->d_text = nullptr;
     e->d_tavail = nullptr;
     e->text_cap = 0;
-    if (max_rows == 0) return 0;
+    if (max_rows == 0) {
+        e->hold = false;   // nothing left to hold a slot for
+        return 0;
+    }
     const size_t n = (size_t)e->max_batch * max_rows * e->m->cfg.hidden;
     if (hipMalloc((void**)&e->d_text, sizeof(float) * n) != hipSuccess ||
         hipMalloc((void**)&e->d_tavail, sizeof(int) * e->max_batch) != hipSuccess) {
@@ -958,6 +1008,36 @@ int q3e_text_state(void* ee, int32_t* rows, int32_t* starved) {
         if (rows) rows[b] = e->h_text[b] ? e->h_trows[b] : 0;
         if (starved) starved[b] = waits && e->h_trows[b] <= e->h_age[b];
     }
+    return 0;
+}
+
+int q3e_text_hold(void* ee, int on) {
+    Engine* e = (Engine*)ee;
+    if (!e) return -1;
+    if (!e->d_text) {
+        Q3_LOG("q3e_text_hold: no text rows are reserved (q3e_text_reserve)");
+        return -1;
+    }
+    if (e->slot_mode) {
+        Q3_LOG("q3e_text_hold: a per-slot batch is open (call between q3e_text_reserve and q3e_open)");
+        return -1;
+    }
+    const bool h = on != 0;
+    if (h == e->hold) return 0;
+    if (h && !e->d_held) {
+        Q3_HIP(hipMalloc((void**)&e->d_held, sizeof(int) * e->max_batch), -1);
+        Q3_HIP(hipMemsetAsync(e->d_held, 0, sizeof(int) * e->max_batch, e->s), -1);
+        Q3_HIP(hipStreamSynchronize(e->s), -1);
+    }
+    e->hold = h;
+    for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointers
+    return 0;
+}
+
+int q3e_text_held(void* ee, int64_t* held_steps) {
+    Engine* e = (Engine*)ee;
+    if (!e || !e->slot_mode || e->B <= 0 || !held_steps) return -1;
+    for (int b = 0; b < e->B; b++) held_steps[b] = e->h_held[b];
     return 0;
 }
 

@@ -161,6 +161,12 @@ struct TalkerSampleArgs {
     // per-slot mode (null: the scalar fields above): budget, temperature, top-k, top-p and draw key of row r come from
     // slots[r]; the dynamic LDS is then sized for the sort path whatever the row asks for
     const SlotParams* slots = nullptr;
+    // per-slot mode with held text slots (q3e_text_hold; both null: none).  A row is HELD in this step when its slot is a
+    // text slot whose text has not ended (flags 3), it has not ended, and 1 <= n_past < its budget while n_past >=
+    // text_avail[r]: its next frame has no text row yet.  The workgroup of a held row sets held[r] and returns before it
+    // reads a logit: no counter, code, ring entry or position of the row changes.  Every other row clears held[r].
+    const int* text_avail = nullptr;    // [R_total] rows pushed per slot (written by the host between launches)
+    int* held = nullptr;                // [R_total] 1: the row is held in this step (read by the frame's cp_argmax launches)
 };
 int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a);
 
@@ -203,6 +209,10 @@ struct CpArgmaxArgs {
     const float* text_rows = nullptr;   // f32 [R_total][text_cap][H]
     const int* text_avail = nullptr;    // [R_total]
     int text_cap = 0;
+    // per-slot mode with held text slots (null: none): held[r] != 0 (set by this step's talker_sample launch) makes the
+    // row continue with the id its current frame already records in this group's column, and store nothing: the gather,
+    // the q|k|v copy and the feedback sum then repeat what they produced when that frame was first computed.
+    const int* held = nullptr;          // [R_total]
 };
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a);
 

@@ -1982,6 +1982,14 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
         top_k = sp.t_top_k;
         max_frames = sp.max_frames;
         slot_flags = sp.flags;
+        if (a.text_avail) {
+            // held text slots (q3e_text_hold): the row's next frame has no text row yet.  Scalar values only, so the
+            // whole workgroup leaves together, before the first barrier and before it has read a logit.
+            const int avail = uniform_load(a.text_avail + r);
+            const bool held = (slot_flags & 3) == 3 && !was_done && np >= 1 && np >= avail && np < max_frames;
+            if (threadIdx.x == 0) a.held[r] = held ? 1 : 0;
+            if (held) return;
+        }
     }
     if (threadIdx.x == 0) nwin = np < 30 ? np : 30;
     if (threadIdx.x < 30 && threadIdx.x < np) {
@@ -2141,7 +2149,7 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
         Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
                       "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
                       "s"(a.talker_emb), "s"(a.slots), "s"(a.forced), "s"(a.next_qkv), "s"(a.qkv_out), "s"(a.qkv_ld),
-                      "s"(a.text_rows), "s"(a.text_avail), "s"(a.text_cap));
+                      "s"(a.text_rows), "s"(a.text_avail), "s"(a.text_cap), "s"(a.held));
     else
         Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
                       "s"(a.frame_cap), "s"(a.next_table), "s"(a.h_out), "s"(a.ssq_out), "s"(a.xh_out), "s"(a.gamma_next),
@@ -2162,7 +2170,9 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     float temperature = a.temperature;
     int top_k = a.top_k;
     int text_avail = 0;   // rows of streamed text the row has (feedback launch of an engine with a text reservation only)
+    int held = 0;         // the row is held in this step (an engine with q3e_text_hold only): see CpArgmaxArgs::held
     if constexpr (SLOTS) {
+        if (a.held) held = uniform_load(a.held + r);
         const SlotParams sp = uniform_slot(a.slots, r);
         temperature = sp.c_temp;
         top_k = sp.c_top_k;
@@ -2238,7 +2248,10 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     const bool keep = f < a.frame_cap;        // a frame beyond the codes array is not recorded
     if (!keep) f = a.frame_cap - 1;
     int* fc = a.codes + ((size_t)f * RT + r) * 16;
-    if (tid == 0 && keep) fc[1 + a.group] = bidx;
+    if (SLOTS && held) {   // (a held row has 1 <= n_frames <= frame_cap: its frame is recorded)
+        bidx = fc[1 + a.group];
+        if (bidx < 0 || bidx >= a.V) bidx = 0;
+    } else if (tid == 0 && keep) fc[1 + a.group] = bidx;
     const int* fz = (a.forced && keep) ? a.forced + ((size_t)f * RT + r) * 16 : nullptr;
     if (fz && fz[1 + a.group] >= 0) bidx = fz[1 + a.group];   // teacher forcing (tests): continue with the forced id
     Q3_PH(2);

@@ -218,6 +218,22 @@ class FrameEngine:
         if self._lib.q3e_text_reserve(self.h, int(max_rows)) != 0:
             raise RuntimeError(f"q3e_text_reserve({max_rows}) failed")
 
+    def hold_text(self, on=True):
+        """Hold a starved text slot inside the frame instead of stalling the batch (q3e_text_hold; after reserve_text(),
+        before open()).  run() then steps the other slots on while a live text slot has no row for its next frame, and
+        returns 0 only when every live slot is held (or a text slot without a frame has no row yet).  Raises ValueError
+        when the engine refuses (no reservation, or a per-slot batch is open): nothing changes."""
+        rc = self._lib.q3e_text_hold(self.h, int(bool(on)))
+        if rc != 0:
+            raise ValueError(f"q3e_text_hold refused: {rc}")
+
+    def held_steps(self):
+        """-> int64 [B]: frame steps each slot's utterance was held for since its admission (q3e_text_held)."""
+        held = np.zeros(self.B, np.int64)
+        if self._lib.q3e_text_held(self.h, held.ctypes.data_as(hiplib.i64p)) != 0:
+            raise RuntimeError("q3e_text_held failed")
+        return held
+
     def push_text(self, slot, rows, final=False, n_text=0):
         """Append rows ([n, hidden] f32, n >= 0) to the text of the text slot `slot` (q3e_push_text).  final ends the text:
         the slot's EOS mask is lifted and its text length becomes n_text.  Row i is consumed at the slot's frame i; run()

@@ -96,6 +96,8 @@ def load(path: str | None = None):
     _sig(lib, "q3e_text_reserve", c_int, [c_void_p, c_int])
     _sig(lib, "q3e_push_text", c_int, [c_void_p, c_int, f32p, c_int, c_int, c_int])
     _sig(lib, "q3e_text_state", c_int, [c_void_p, i32p, i32p])
+    _sig(lib, "q3e_text_hold", c_int, [c_void_p, c_int])
+    _sig(lib, "q3e_text_held", c_int, [c_void_p, i64p])
     _sig(lib, "q3e_get_hidden", c_int, [c_void_p, f32p])
     _sig(lib, "q3e_step_weight_bytes", ctypes.c_double, [c_void_p])
     # include/qwen3tts_voc.h

@@ -3,8 +3,9 @@
 
 bench.py's synthetic 0.6B-architecture weights and workload, EOS off, greedy.  One process measures one library
 (QWEN3TTS_LIB picks it), so two builds are compared by alternating processes in one session.  --reserve N calls
-q3e_text_reserve(N) first (the text-stream kernels then read one more per-row counter); libraries older than that call
-must run without it.  Prints one JSON line: the median and every run of --runs timed q3e_run(--frames) calls.
+q3e_text_reserve(N) first (the text-stream kernels then read one more per-row counter) and --hold, with it, q3e_text_hold
+(the sampler then reads that counter too and every arg-max launch a per-row flag; no slot is held: all are ordinary);
+libraries older than these calls must run without them.  Prints one JSON line: the median and every run of --runs timed q3e_run(--frames) calls.
 
     python scripts/slot_step_ms.py --batch 32 --runs 5
 """
@@ -27,6 +28,7 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--reserve", type=int, default=0)
+    ap.add_argument("--hold", action="store_true", help="with --reserve: q3e_text_hold(1) before the batch opens")
     ap.add_argument("--label", default="")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--cache", default=os.environ.get("Q3_BENCH_CACHE", "/tmp/q3_bench_cache"))
@@ -40,6 +42,8 @@ def main():
     eng.set_pad_embed(pad)
     if a.reserve:
         eng.reserve_text(a.reserve)
+    if a.hold:
+        eng.hold_text()
     eng.open(a.batch, ignore_eos=True)
     eng.admit(list(range(a.batch)), prefixes, n_text, [SlotParams(max_frames=budget)] * a.batch)
     assert eng.run(8) == 8                       # eager frame + capture
@@ -49,7 +53,7 @@ def main():
         assert eng.run(a.frames) == a.frames
         ms.append(eng.last_run_ms / a.frames)
     eng.destroy()
-    print(json.dumps({"label": a.label, "lib": os.environ.get("QWEN3TTS_LIB", "default"), "batch": a.batch, "reserve": a.reserve,
+    print(json.dumps({"label": a.label, "lib": os.environ.get("QWEN3TTS_LIB", "default"), "batch": a.batch, "reserve": a.reserve, "hold": bool(a.hold),
                       "ms_per_step_median": round(float(np.median(ms)), 4), "ms_per_step": [round(x, 4) for x in ms]}))
 
 

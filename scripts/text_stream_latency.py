@@ -16,6 +16,16 @@ because the slot waited for text (the frame loop is faster than the text, so it 
 other slot of the batch: DESIGN.md section 11).
 
     python scripts/text_stream_latency.py --out profiles/text_stream_latency.json
+
+--bystander: what a text client that PAUSES costs another request.  One ordinary streamed request (the bystander, --tokens
+token ids, whole text) starts together with one text-stream client whose tokens come at --rate but which stops for
+--pause_ms after every --pause_every tokens (a language model that stalls); one server without and one with --text_hold
+(batch_server; q3e_text_hold), --repeats times each after one untimed pass.  Reported per server: the bystander's time to
+its last audio record and the longest gap between two of its audio records, the text client's time to its first audio
+record, the frame steps text slots were held for and the checks that ran no frame.  Held steps are not free: a held row
+still computes, so the frame loop runs steps that emit nothing for it.
+
+    python scripts/text_stream_latency.py --bystander --out profiles/text_hold_bystander.json
 """
 from __future__ import annotations
 
@@ -70,6 +80,84 @@ def one(sock, ids, rate, max_tokens, vocoder, streamed):
             "frames": frames, "samples": samples}
 
 
+def bystander_pair(sock, ids, a):
+    """The bystander and the pausing text client, started together -> their figures."""
+    from qwen3_tts_axera_russian_amd import batch_server as bs
+    out = {}
+    t0 = time.perf_counter()
+
+    def pieces():
+        due = t0
+        for i, t in enumerate(ids):
+            if i:
+                due += 1.0 / a.rate + (a.pause_ms / 1e3 if i % a.pause_every == 0 else 0.0)
+            time.sleep(max(0.0, due - time.perf_counter()))
+            yield [t]
+
+    def text_client():
+        first = None
+        for rec in bs.synthesize_text_stream(sock, pieces(), max_tokens=a.max_tokens, vocoder=a.vocoder):
+            if rec[0] == "audio" and first is None:
+                first = time.perf_counter()
+        out["text_first_audio_ms"] = round(1e3 * (first - t0), 1)
+        out["text_done_ms"] = round(1e3 * (time.perf_counter() - t0), 1)
+
+    th = threading.Thread(target=text_client)
+    th.start()
+    stamps, frames = [], 0
+    for rec in bs.synthesize_batch_stream(sock, token_ids=[ids], max_tokens=a.max_tokens, vocoder=a.vocoder):
+        if rec[0] == "audio":
+            stamps.append(time.perf_counter())
+        else:
+            frames = rec[2].shape[0]
+    th.join()
+    gaps = np.diff(np.array([t0] + stamps))
+    out.update({"bystander_last_audio_ms": round(1e3 * (stamps[-1] - t0), 1), "bystander_longest_gap_ms": round(1e3 * float(gaps.max()), 1),
+                "bystander_frames": frames, "bystander_audio_records": len(stamps)})
+    return out
+
+
+def bystander(a, main_pack, voc_pack, cfg, ids):
+    from qwen3_tts_axera_russian_amd import batch_server as bs
+    legs = {}
+    for hold in (False, True):
+        name = "text_hold" if hold else "default"
+        sock = os.path.join(a.cache, f"tsl_{os.getpid()}_{int(hold)}.sock")
+        srv = bs.BatchSynthesisServer(main_pack, voc_pack, sock, max_batch=a.max_batch, n_ctx=a.max_tokens + 64, max_tokens=a.max_tokens,
+                                      temperature=0.0, cp_temperature=0.0, install_signal_handlers=False, concurrent=True,
+                                      text_wait_ms=max(a.text_wait_ms, 4.0 * a.pause_ms), text_hold=hold)
+        th = threading.Thread(target=srv.serve, daemon=True)
+        th.start()
+        while not (os.path.exists(sock) and srv.sched is not None):
+            time.sleep(0.05)
+        runs = []
+        try:
+            for rep in range(a.repeats + 1):
+                s0, h0, f0 = srv.sched.starved_checks, srv.sched.held_steps, srv.sched.frame_steps
+                r = bystander_pair(sock, ids, a)
+                r.update({"starved_checks": srv.sched.starved_checks - s0, "held_steps": srv.sched.held_steps - h0,
+                          "frame_steps": srv.sched.frame_steps - f0})
+                if rep:
+                    runs.append(r)
+                print(f"[text_stream_latency] bystander {name} {'warm-up' if not rep else rep}: {r}", file=sys.stderr, flush=True)
+        finally:
+            srv._running = False
+            th.join(timeout=60)
+            srv.close()
+        keys = [k for k in runs[0]]
+        legs[name] = {"runs": runs, "median": {k: float(np.median([r[k] for r in runs])) for k in keys}}
+    out = {"what": "an ordinary streamed request beside a text-stream client that pauses: without and with --text_hold",
+           "packs": "tiny (2 + 2 layers)" if a.tiny else "synthetic Qwen3-TTS-0.6B architecture", "rate_tokens_per_s": a.rate,
+           "tokens": a.tokens, "pause_ms": a.pause_ms, "pause_every": a.pause_every, "max_tokens": a.max_tokens, "vocoder": a.vocoder,
+           "max_batch": a.max_batch, "repeats": a.repeats, "legs": legs}
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rate", type=float, default=50.0, help="text tokens per second")
@@ -83,6 +171,9 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--cache", default=os.environ.get("Q3_BENCH_CACHE", "/tmp/q3_bench_cache"))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bystander", action="store_true", help="an ordinary request beside a pausing text client, without / with --text_hold")
+    ap.add_argument("--pause_ms", type=float, default=150.0, help="--bystander: the text client's pause")
+    ap.add_argument("--pause_every", type=int, default=8, help="--bystander: tokens between two pauses")
     a = ap.parse_args()
     from qwen3_tts_axera_russian_amd import batch_server as bs
     if a.tiny:
@@ -91,6 +182,8 @@ def main():
         import serve_load
         main_pack, voc_pack, cfg = serve_load.make_packs(a.cache, a.seed)
     ids = np.random.default_rng(a.seed).integers(0, cfg.text_vocab - 8, a.tokens).tolist()
+    if a.bystander:
+        return bystander(a, main_pack, voc_pack, cfg, ids)
     sock = os.path.join(a.cache, f"tsl_{os.getpid()}.sock")
     srv = bs.BatchSynthesisServer(main_pack, voc_pack, sock, max_batch=a.max_batch, n_ctx=a.max_tokens + 64, max_tokens=a.max_tokens,
                                   temperature=0.0, cp_temperature=0.0, install_signal_handlers=False, concurrent=True,
