@@ -141,6 +141,47 @@ int q3e_admit(void* e, int n, const int32_t* slots, const float* prefix, const i
               const q3e_slot_params* params);
 int q3e_release(void* e, int n, const int32_t* slots);
 
+/* Prefix cache of the per-slot admissions (the reference's KV prefix cache, llamacpp_talker_server.py:208-246: md5 of the
+ * prefix -> saved KV state + last hidden, a hit skips the prefill -- here for q3e_admit, on the device).
+ *
+ * q3e_admit prefills every utterance in a pass of its own, so the KV rows and the frame-0 state it leaves depend on the
+ * prefix rows and on nothing else: not the slot, not the neighbours, not B.  An entry holds a copy of them -- rows
+ * [0, n_rows) of K and V of every talker layer and KV head, and the last row's pre-norm residual with its sum-of-squares
+ * partials.  A hit copies the rows into the slot in ONE launch over all layers and runs the final norm a prefill runs on
+ * the saved residual, so the slot holds, bit for bit, what a prefill would have written: a reply with the cache is the
+ * reply without it.  Everything is ordered on the engine's one stream; the cache adds no stream, event or hardware queue.
+ *
+ * q3e_prefix_cache: reserve (n_entries > 0) or release (0) a device pool of prefix entries, each up to max_rows rows
+ * (clamped to the n_ctx of q3e_create).  Drops every entry; the counters of q3e_prefix_stats run on.  Not part of the
+ * captured frame: legal at any time between calls, never recaptures.  <0 = nothing changed (negative arguments, entries
+ * of 0 rows, no memory).  Pool size: n_entries * max_rows * (layers * 2 * n_kv * 128 * 2) bytes -- 114 688 B per row on
+ * the 28-layer model (n_kv 8), 7.3 MB for an entry of 64 rows -- plus (hidden + hidden / 16) * 4 bytes per entry.
+ * Entries survive q3e_open, q3e_set_chains and q3e_text_reserve (none changes what a prefill computes); q3e_free frees
+ * the pool.
+ *
+ * q3e_admit_keyed: q3e_admit with a 128-bit key per utterance (keys[2 * u], keys[2 * u + 1]; {0, 0} or keys == NULL:
+ * not cached, exactly q3e_admit).  Rows are always given.  Validation is q3e_admit's, before anything changes: a failed
+ * call leaves the slots and the cache as they were.  Utterances are processed in order (a key given twice in one call is
+ * a miss followed by a hit):
+ *   - hit (the key is present with the same n_rows): the rows are neither uploaded nor read; the slot's KV rows and
+ *     frame-0 state come from the entry;
+ *   - miss: prefill as q3e_admit, then store under the key, into a free entry or over the least recently used one (use =
+ *     hit or store).  A key present with another n_rows is a miss that replaces that entry.  Without a pool a keyed
+ *     utterance is a miss that stores nothing;
+ *   - n_rows > max_rows of the pool: a plain admission, counted as too long (neither hit nor miss).
+ * hit[u] (may be NULL) = 1 / 0.  Text slots (`reserved` bit 0) may be keyed like any other: the entry holds the prefix,
+ * not the pushed rows.  q3e_last_prefill_ms covers the call, as for q3e_admit.
+ *
+ * The key contract is the caller's: a key is a digest of EVERYTHING that determines the prefix rows (the token ids, the
+ * kind of prefix, the model if handles share keys); the engine never compares rows.  Only the per-slot mode uses the
+ * cache: q3e_start and q3e_refill prefill in shared passes whose sums are not a function of one prefix alone.
+ *
+ * q3e_prefix_stats: out[6] = hits, misses, stores, evictions, too long to cache, entries in use.  0 ok / <0 error. */
+int q3e_prefix_cache(void* e, int n_entries, int max_rows);
+int q3e_admit_keyed(void* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+                    const q3e_slot_params* params, const uint64_t* keys, int32_t* hit);
+int q3e_prefix_stats(void* e, int64_t* out /*[6]*/);
+
 /* Text streamed into a running utterance, row by row (per-slot mode only).
  *
  * Layout (a recollection of the model's streaming mode, which the reference does not implement -- it pre-computes the

@@ -45,7 +45,16 @@ and ignore them).  Determinism contract: a request's reply, codes and PCM, depen
 server's configuration -- not on what else is in flight nor on which slots it gets.  The loop always steps max_batch rows (a
 row's f32 sums depend on the row count of the pass), every utterance is prefilled in a pass of its own (the ragged prefill's
 tiles depend on the rows of the pass), and utterance u of a request with seed s draws from the stream mix(s, u), keyed by
-(stream, frame, group) and not by the slot (include/qwen3tts_engine.h).
+(stream, frame, group) and not by the slot (include/qwen3tts_engine.h).  With `--prefix_cache N` a reply is, bit for bit, the
+reply without it.
+
+`--prefix_cache N` (with `--concurrent`; N entries of up to `--prefix_cache_rows` prefix rows each, default 0 = off): the
+engine keeps the KV rows and the frame-0 state of admitted prefixes in a device pool (q3e_prefix_cache / q3e_admit_keyed), and
+an utterance whose prefix is there is admitted by one copy launch instead of a prefill: a repeated text, the k takes of a
+request that lists one text k times with a seed, and every text-stream request that begins with the same token (its 8-row
+streaming prefix depends on the first token alone).  The key is the server's own: the first 16 bytes of a SHA-256 over a kind
+tag (b"full" / b"stream") and the int32 token ids that determine the prefix rows (prefix_key); a client never supplies one.
+The prefix rows are still built on the accept thread; the wire protocol is unchanged.
 
 Streamed TEXT (`--concurrent` only; the request carries "text_stream": true, which needs "stream": true and exactly one
 utterance, else -2): the request's texts / token_ids hold only the first piece of the text (at least one token), and the
@@ -82,6 +91,7 @@ from __future__ import annotations
 import argparse
 import collections
 import dataclasses
+import hashlib
 import os
 import select
 import signal
@@ -100,11 +110,31 @@ from .vocoder import Vocoder
 from .weights import ModelConfig, read_pack
 
 
+def prefix_key(kind, token_ids):
+    """The prefix cache's key of an utterance: the first 16 bytes of a SHA-256 over the kind of prefix (b"full": the
+    dual-stream prefix of the whole text, b"stream": the streaming prefix) and the int32 token ids that determine its
+    rows -- for b"stream" the first token alone."""
+    ids = np.asarray(token_ids, dtype="<i4").reshape(-1)
+    return hashlib.sha256(bytes(kind) + b"\0" + ids.tobytes()).digest()[:16]
+
+
+class QueuedUtterance(tuple):
+    """An utterance as _prepare queues it -- the tuple (request index, prefix, n_text, SlotParams[, TextFeed]) the scheduler
+    has always taken -- with the prefix cache's key of its prefix beside it."""
+    prefix_key = None
+
+    def __new__(cls, fields, prefix_key=None):
+        self = super().__new__(cls, fields)
+        self.prefix_key = prefix_key
+        return self
+
+
 class BatchSynthesisServer:
     def __init__(self, model_path, vocoder_path, socket_path="/tmp/qwen3_batch.sock", max_batch=32, n_ctx=512,
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
-                 cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False):
+                 cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=0,
+                 prefix_cache_rows=64):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens = socket_path, max_batch, max_tokens
@@ -121,6 +151,11 @@ class BatchSynthesisServer:
         if text_hold and not concurrent:
             raise ValueError("--text_hold holds text slots of the shared frame loop: it needs --concurrent")
         self.text_hold = bool(text_hold)
+        if int(prefix_cache) < 0 or int(prefix_cache_rows) <= 0:
+            raise ValueError("--prefix_cache takes a number of entries >= 0, --prefix_cache_rows a number of rows >= 1")
+        if prefix_cache and not concurrent:
+            raise ValueError("--prefix_cache serves the per-slot admissions of the shared frame loop: it needs --concurrent")
+        self.prefix_cache, self.prefix_cache_rows = int(prefix_cache), int(prefix_cache_rows)
         self.sched = None
         # utterances one request may queue (the server is single-threaded: an unbounded request holds it indefinitely)
         self.max_request = int(max_request) if max_request else 8 * max_batch
@@ -262,7 +297,7 @@ class BatchSynthesisServer:
         try:
             if not state["failed"]:
                 conn.sendall(P.pack_sentinel(P.SENTINEL_DONE))
-                print(f"  {state['n']} utterances, {state['frames']} frames streamed in {time.time() - t0:.3f}s")
+                print(f"  {state['n']} utterances, {state['frames']} frames streamed in {time.time() - t0:.3f}s{self._prefix_note()}")
         except OSError:
             pass
         finally:
@@ -341,17 +376,19 @@ class BatchSynthesisServer:
 
     def _prepare(self, msg):
         """--concurrent, accept side: a request -> its utterances in queue order as (request index, prefix, n_text,
-        SlotParams); raises on anything malformed, before any of it is queued."""
+        SlotParams), each a QueuedUtterance with its prefix key; raises on anything malformed, before any of it is queued."""
         request_vocoder_arithmetic(msg)      # (checks "vocoder" too)
         base = request_slot_params(msg, self.defaults, self.max_tokens)
         if msg.get("text_stream"):
             return [self._prepare_text_stream(msg, base)]
         ids = self._token_ids(msg)
         prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames)
-        return [(i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i)) for i in order]
+        return [QueuedUtterance((i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i)),
+                                prefix_key(b"full", ids[i])) for i in order]
 
     def _prepare_text_stream(self, msg, base):
-        """A "text_stream" request -> its one utterance as (0, streaming prefix, 0, SlotParams of a text slot, TextFeed)."""
+        """A "text_stream" request -> its one utterance as (0, streaming prefix, 0, SlotParams of a text slot, TextFeed), a
+        QueuedUtterance whose prefix key covers the first token alone."""
         from .frontend import text_stream_rows
         if msg.get("stream") is not True:
             raise ValueError('"text_stream" needs "stream": true')
@@ -375,14 +412,20 @@ class BatchSynthesisServer:
         feed = TextFeed(lambda ids, final=False: text_stream_rows(self.front, ids, final), encoder,
                         None if tokeniser is None else tokeniser.incremental, first[1:], 1)
         params = dataclasses.replace(base, utt=0, text_stream=True)
-        return (0, self.front.build_prefix_stream(first[0]), 0, params, feed)
+        return QueuedUtterance((0, self.front.build_prefix_stream(first[0]), 0, params, feed), prefix_key(b"stream", first[:1]))
+
+    def _prefix_note(self):
+        """The prefix cache's counters so far, for the per-request line ("" without --prefix_cache)."""
+        if not self.prefix_cache or self.sched is None:
+            return ""
+        return f" (prefix cache: {self.sched.prefix_hits} hits, {self.sched.prefix_misses} misses so far)"
 
     def _finish(self, conn, cs, t0, vocoder="walk", arithmetic="exact"):
         """Worker side of the pipelined mode: vocode, reply on the request's own connection, close it."""
         try:
             res = self.vocode(cs, vocoder, arithmetic)
             conn.sendall(pack_batch_reply(res))
-            print(f"  {len(res)} utterances, {sum(len(c) for c, _ in res)} frames in {time.time() - t0:.3f}s")
+            print(f"  {len(res)} utterances, {sum(len(c) for c, _ in res)} frames in {time.time() - t0:.3f}s{self._prefix_note()}")
         except Exception as e:
             print(f"Error: {e}")
             try:
@@ -461,10 +504,12 @@ class BatchSynthesisServer:
         self.eng.reserve_text(self.max_tokens)   # before the scheduler opens the batch: a row per frame of every slot
         if self.text_hold:
             self.eng.hold_text()                 # a text slot without a row is held inside the frame: the others step on
+        if self.prefix_cache:
+            self.eng.prefix_cache(self.prefix_cache, self.prefix_cache_rows)
         self.sched = ConcurrentScheduler(self.eng, self.max_batch, self.max_queue, self._prepare, self._finish, self._push,
                                          self._close_stream, self._send_error, check_every=self.check_every,
                                          send_timeout=self.send_timeout, text_wait_ms=self.text_wait_ms,
-                                         text_hold=self.text_hold)
+                                         text_hold=self.text_hold, prefix_cache=bool(self.prefix_cache))
         self.sched.start()
         print(f"Batch synthesis server listening on {self.socket_path} (--concurrent: {self.max_batch} slots shared by every "
               f"request, up to {self.max_queue} queued utterances)")
@@ -609,10 +654,15 @@ class ConcurrentScheduler:
     admitted only once its feed has its first row (a slot without a frame cannot be held), waiting in the queue meanwhile
     while later requests pass it; a request whose slot has been held for text_wait_ms with no byte received from its client
     fails alone (-2, slot released); starved_checks counts only the checks that ran no frame (every live slot held), and
-    held_steps sums the frame steps requests were held for."""
+    held_steps sums the frame steps requests were held for.
+
+    prefix_cache (the engine was told eng.prefix_cache(n, rows) before this scheduler opens the batch): the keys of an
+    admission -- each item's `prefix_key` attribute (16 bytes; an item without one is admitted uncached) -- go to
+    eng.admit(..., keys=[...]) in slot order; prefix_hits / prefix_misses count the flags it returns.  Without it admit is
+    called as it always was, whatever the items carry."""
 
     def __init__(self, eng, max_batch, max_queue, prepare, reply, push, close_stream, send_error, check_every=8,
-                 send_timeout=30.0, text_wait_ms=200.0, text_hold=False):
+                 send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=False):
         from concurrent.futures import ThreadPoolExecutor
         self.eng, self.B, self.max_queue, self.check_every = eng, int(max_batch), int(max_queue), int(check_every)
         self._prepare, self._reply, self._push, self._close_stream, self._send_error = prepare, reply, push, close_stream, send_error
@@ -628,6 +678,8 @@ class ConcurrentScheduler:
         self.starved_checks = 0                 # checks that ran no frame because a text slot waited for its text
         self.text_hold = bool(text_hold)
         self.held_steps = 0                     # text_hold: frame steps text slots were held for, summed over requests
+        self.prefix_cache = bool(prefix_cache)
+        self.prefix_hits = self.prefix_misses = 0   # prefix_cache: admitted utterances that came from the cache / were prefilled
 
     # ---- accept side ----
     def submit(self, conn, msg, t0=None):
@@ -833,7 +885,13 @@ class ConcurrentScheduler:
             resets = collections.defaultdict(list)
             if take:
                 slots = free[:len(take)]
-                eng.admit(slots, [it[1] for _, it in take], [it[2] for _, it in take], [it[3] for _, it in take])
+                args = (slots, [it[1] for _, it in take], [it[2] for _, it in take], [it[3] for _, it in take])
+                if self.prefix_cache:
+                    hit = eng.admit(*args, keys=[getattr(it, "prefix_key", None) for _, it in take])
+                    self.prefix_hits += int(np.count_nonzero(hit))
+                    self.prefix_misses += len(take) - int(np.count_nonzero(hit))
+                else:
+                    eng.admit(*args)
                 for b, (req, it) in zip(slots, take):
                     owner[b] = (req, it[0])
                     pushed[b] = 0
@@ -1153,11 +1211,16 @@ def main():
     ap.add_argument("--text_hold", action="store_true",
                     help="--concurrent: a text-stream request without text for its next frame is held inside the frame while the "
                          "other requests go on (default: the whole frame loop waits for it)")
+    ap.add_argument("--prefix_cache", type=int, default=0,
+                    help="--concurrent: entries of the device prefix cache (0 = off): an utterance whose prefix is cached is "
+                         "admitted without a prefill, with the same reply")
+    ap.add_argument("--prefix_cache_rows", type=int, default=64, help="--prefix_cache: prefix rows an entry can hold")
     a = ap.parse_args()
     srv = BatchSynthesisServer(a.model, a.vocoder, a.socket, a.max_batch, a.n_ctx, a.max_tokens, a.temperature, a.top_k,
                                a.cp_temperature, a.tokenizer, a.seed, pipeline=a.pipeline, concurrent=a.concurrent,
                                max_queue=a.max_queue, top_p=a.top_p, cp_top_k=a.cp_top_k, check_every=a.check_every,
-                               send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms, text_hold=a.text_hold)
+                               send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms, text_hold=a.text_hold,
+                               prefix_cache=a.prefix_cache, prefix_cache_rows=a.prefix_cache_rows)
     try:
         srv.serve()
     finally:

@@ -76,6 +76,21 @@ struct Engine {
     bool hold = false;
     int* d_held = nullptr;                  // [max_batch] the sampler's per-step verdict, read by the frame's cp_argmax launches
     std::vector<long long> h_held;          // steps each slot was held for since its admission
+    // prefix cache of the per-slot admissions (q3e_prefix_cache / q3e_admit_keyed): a device pool of entries, each the KV
+    // rows of one prefix and the residual row its final norm reads; the host keeps the keys and the use order.  Nothing
+    // of it is an argument of the captured frame.
+    struct PfxEntry {
+        uint64_t k0 = 0, k1 = 0;
+        int n_rows = 0;                     // 0: free
+        unsigned long long use = 0;         // pfx_clock of the last hit or store
+    };
+    half_t* d_pfx = nullptr;                // [pfx_n][layers][2][n_kv][pfx_rows][128]
+    float* d_pfx_state = nullptr;           // [pfx_n][hidden + hidden / 16]
+    int pfx_n = 0, pfx_rows = 0;
+    std::vector<PfxEntry> pfx;
+    unsigned long long pfx_clock = 0;
+    long long pfx_stat[5] = {0, 0, 0, 0, 0};   // hits, misses, stores, evictions, too long
+    size_t pfx_entry_elems() const { return (size_t)kv_t.n_layers * 2 * kv_t.n_kv * pfx_rows * 128; }
 };
 
 // the device's verdict for slot b at its next step (talker_sample_row<true>), from the host's copies: a live text slot
@@ -275,7 +290,7 @@ void q3e_free(void* ee) {
     work_free(e->wc);
     void* ps[] = {e->d_tiles, e->d_slot, e->d_pos,  e->d_iota,   e->d_past,    e->d_npast, e->d_ntext, e->d_done,
                   e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots,
-                  e->d_text, e->d_tavail, e->d_held};
+                  e->d_text, e->d_tavail, e->d_held, e->d_pfx, e->d_pfx_state};
     for (void* p : ps)
         if (p) hipFree(p);
     if (e->h_done) hipHostFree(e->h_done);
@@ -417,6 +432,33 @@ int q3e_set_pad_embed(void* ee, const float* pad) {
     return 0;
 }
 
+// Final norm after a prefill: the rows d_lastrow[row0 .. row0 + R) of the residual stream into rows row0.. of the post-norm
+// buffers and of the code predictor's position-0 input (prefill_ids; a prefix-cache hit launches it for its one row)
+static int prefill_final_norm(Engine* e, int row0, int R, int B_total) {
+    const Model& m = *e->m;
+    const int H = m.cfg.hidden;
+    FinalNormArgs f;
+    f.h = e->wt.h;
+    f.ssq = e->wt.ssq;
+    f.ssq_parts = H / 16;
+    f.gamma = m.talker.final_norm;
+    f.eps = m.cfg.eps;
+    f.R = R;
+    f.row0 = row0;   // output rows (fragment-ordered buffers are indexed, not offset)
+    f.H = H;
+    f.row_map = e->d_lastrow;
+    f.out_f32 = e->wt.hidden_f32;
+    f.out_f16 = e->wt.hidden_f16;
+    f.out_copy = e->wc.h;
+    f.out_copy_ssq = e->wc.ssq;
+    f.out_copy_xh = e->wc.xh;
+    f.out_copy_gamma = m.cp.L[0].in_ln;
+    // the first frame's code predictor pass reads its position-0 rows where cp_frame expects them (the same
+    // place for one chain and for parallel chains)
+    f.out_copy_row_off = cp_seed_row0(e->wc, B_total, 0, B_total);
+    return launch_final_norm(e->s, f);
+}
+
 // Ragged prefill of n utterances into the KV slots / output rows ids[0..n) (prefix rows concatenated in that order):
 // utterances are packed into passes of at most prefill_rows rows; every row carries its own (slot, position).  The
 // hidden of each utterance's last row lands in row ids[u] of the post-norm buffers, one group at a time.
@@ -467,28 +509,8 @@ static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, co
         rm.n_tiles = (int)(tiles.size() / 4);
         if (run_stack(e->s, m, m.talker, e->wt, e->kv_t, rows, rm, 1024)) return -1;
         // final norm of the last rows of this group into rows ids[u0..u1) of the post-norm buffers
-        for (int u = u0; u < u1; u += contiguous ? (u1 - u0) : 1) {
-            FinalNormArgs f;
-            f.h = e->wt.h;
-            f.ssq = e->wt.ssq;
-            f.ssq_parts = H / 16;
-            f.gamma = m.talker.final_norm;
-            f.eps = m.cfg.eps;
-            f.R = contiguous ? u1 - u0 : 1;
-            f.row0 = ids[u];   // output rows (fragment-ordered buffers are indexed, not offset)
-            f.H = H;
-            f.row_map = e->d_lastrow;
-            f.out_f32 = e->wt.hidden_f32;
-            f.out_f16 = e->wt.hidden_f16;
-            f.out_copy = e->wc.h;
-            f.out_copy_ssq = e->wc.ssq;
-            f.out_copy_xh = e->wc.xh;
-            f.out_copy_gamma = m.cp.L[0].in_ln;
-            // the first frame's code predictor pass reads its position-0 rows where cp_frame expects them (the same
-            // place for one chain and for parallel chains)
-            f.out_copy_row_off = cp_seed_row0(e->wc, B_total, 0, B_total);
-            if (launch_final_norm(e->s, f)) return -1;
-        }
+        for (int u = u0; u < u1; u += contiguous ? (u1 - u0) : 1)
+            if (prefill_final_norm(e, ids[u], contiguous ? u1 - u0 : 1, B_total)) return -1;
         Q3_HIP(hipStreamSynchronize(e->s), -1);  // host staging vectors are reused by the next group
         row_off += rows;
         u0 = u1;
@@ -837,9 +859,34 @@ int q3e_open(void* ee, int B, int ignore_eos) {
     return 0;
 }
 
-int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
-              const q3e_slot_params* params) {
-    Engine* e = (Engine*)ee;
+// one utterance's prefix state between its slot and pool entry i (launch_prefix_move); h_row: the row of the talker's
+// residual stream the state sits in
+static int prefix_move(Engine* e, int i, int slot, int n_rows, int h_row, int restore) {
+    PrefixMoveArgs a;
+    a.kc = e->kv_t.k;
+    a.vc = e->kv_t.v;
+    a.layer_stride = e->kv_t.layer_stride();
+    a.n_layers = e->kv_t.n_layers;
+    a.n_kv = e->kv_t.n_kv;
+    a.n_ctx = e->kv_t.n_ctx;
+    a.slot = slot;
+    a.n_rows = n_rows;
+    a.entry = e->d_pfx + (size_t)i * e->pfx_entry_elems();
+    a.max_rows = e->pfx_rows;
+    const int H = e->m->cfg.hidden;
+    a.state = e->d_pfx_state + (size_t)i * (H + H / 16);
+    a.h = e->wt.h;
+    a.ssq = e->wt.ssq;
+    a.h_row = h_row;
+    a.H = H;
+    a.restore = restore;
+    if (i < 0 || i >= e->pfx_n || slot >= e->kv_t.n_slots || h_row >= e->wt.max_rows) return -1;
+    return launch_prefix_move(e->s, a);
+}
+
+// q3e_admit (keys == NULL) and q3e_admit_keyed
+static int admit_slots(Engine* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+                       const q3e_slot_params* params, const uint64_t* keys, int32_t* hit) {
     if (!e || !e->slot_mode || n <= 0 || n > e->B || !slots || !prefix || !n_rows || !n_text || !params) {
         if (e && !e->slot_mode) Q3_LOG("q3e_admit: the batch was not opened with q3e_open");
         return -1;
@@ -895,9 +942,50 @@ int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const 
     // request's utterance would change this one's sums
     const int H = e->m->cfg.hidden;
     size_t row_off = 0;
-    for (int u = 0; u < n; u++) {
+    std::vector<int32_t> hits(n, 0);
+    for (int u = 0; u < n; row_off += n_rows[u], u++) {
+        const uint64_t k0 = keys ? keys[2 * u] : 0, k1 = keys ? keys[2 * u + 1] : 0;
+        const bool keyed = k0 != 0 || k1 != 0;
+        int at = -1;   // the entry that holds the key
+        if (keyed && e->pfx_n > 0 && n_rows[u] <= e->pfx_rows)
+            for (int i = 0; i < e->pfx_n && at < 0; i++)
+                if (e->pfx[i].n_rows && e->pfx[i].k0 == k0 && e->pfx[i].k1 == k1) at = i;
+        if (at >= 0 && e->pfx[at].n_rows == n_rows[u]) {
+            // hit: the KV rows, and the last row's residual where a prefill of one utterance leaves it for the same final
+            // norm launch (the residual stream is scratch between two frame steps, as it is for a prefill)
+            if (prefix_move(e, at, ids[u], n_rows[u], 0, 1)) return -1;
+            Q3_HIP(hipMemsetAsync(e->d_lastrow + ids[u], 0, sizeof(int), e->s), -1);
+            if (prefill_final_norm(e, ids[u], 1, e->B)) return -1;
+            e->pfx[at].use = ++e->pfx_clock;
+            e->pfx_stat[0]++;
+            hits[u] = 1;
+            continue;
+        }
         if (prefill_ids(e, 1, &ids[u], prefix + row_off * H, n_rows + u, e->B)) return -1;
-        row_off += n_rows[u];
+        if (!keyed) continue;
+        if (e->pfx_n > 0 && n_rows[u] > e->pfx_rows) {
+            e->pfx_stat[4]++;
+            continue;
+        }
+        e->pfx_stat[1]++;
+        if (e->pfx_n <= 0) continue;
+        if (at < 0) {   // a free entry, else the least recently used one
+            for (int i = 0; i < e->pfx_n; i++) {
+                if (!e->pfx[i].n_rows) {
+                    at = i;
+                    break;
+                }
+                if (at < 0 || e->pfx[i].use < e->pfx[at].use) at = i;
+            }
+            if (e->pfx[at].n_rows) e->pfx_stat[3]++;
+        }
+        e->pfx[at].n_rows = 0;   // (an entry whose store fails holds nothing)
+        if (prefix_move(e, at, ids[u], n_rows[u], n_rows[u] - 1, 0)) return -1;
+        e->pfx[at].k0 = k0;
+        e->pfx[at].k1 = k1;
+        e->pfx[at].n_rows = n_rows[u];
+        e->pfx[at].use = ++e->pfx_clock;
+        e->pfx_stat[2]++;
     }
     if (head_all_rows(e)) return -1;
     Q3_HIP(hipEventRecord(e->ev1, e->s), -1);
@@ -913,6 +1001,57 @@ int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const 
         e->h_tfinal[ids[u]] = 0;
         e->h_held[ids[u]] = 0;
     }
+    if (hit) memcpy(hit, hits.data(), sizeof(int32_t) * n);
+    return 0;
+}
+
+int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+              const q3e_slot_params* params) {
+    return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, nullptr, nullptr);
+}
+
+int q3e_admit_keyed(void* ee, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+                    const q3e_slot_params* params, const uint64_t* keys, int32_t* hit) {
+    return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, keys, hit);
+}
+
+int q3e_prefix_cache(void* ee, int n_entries, int max_rows) {
+    Engine* e = (Engine*)ee;
+    if (!e || n_entries < 0 || max_rows < 0 || (n_entries > 0 && max_rows == 0)) {
+        if (e) Q3_LOG("q3e_prefix_cache: %d entries of %d rows", n_entries, max_rows);
+        return -1;
+    }
+    if (max_rows > e->n_ctx) max_rows = e->n_ctx;   // a longer prefix fits no slot
+    if (n_entries == 0) max_rows = 0;
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    half_t* pool = nullptr;
+    float* state = nullptr;
+    if (n_entries > 0) {
+        const int H = e->m->cfg.hidden;
+        const size_t elems = (size_t)e->kv_t.n_layers * 2 * e->kv_t.n_kv * max_rows * 128;
+        if (hipMalloc((void**)&pool, sizeof(half_t) * elems * n_entries) != hipSuccess ||
+            hipMalloc((void**)&state, sizeof(float) * (size_t)(H + H / 16) * n_entries) != hipSuccess) {
+            Q3_LOG("q3e_prefix_cache: allocation of %zu bytes failed", sizeof(half_t) * elems * n_entries);
+            if (pool) hipFree(pool);
+            return -1;   // the pool that was there stays
+        }
+    }
+    if (e->d_pfx) hipFree(e->d_pfx);
+    if (e->d_pfx_state) hipFree(e->d_pfx_state);
+    e->d_pfx = pool;
+    e->d_pfx_state = state;
+    e->pfx_n = n_entries;
+    e->pfx_rows = max_rows;
+    e->pfx.assign(n_entries, Engine::PfxEntry());
+    return 0;
+}
+
+int q3e_prefix_stats(void* ee, int64_t* out) {
+    Engine* e = (Engine*)ee;
+    if (!e || !out) return -1;
+    for (int i = 0; i < 5; i++) out[i] = e->pfx_stat[i];
+    out[5] = 0;
+    for (const auto& p : e->pfx) out[5] += p.n_rows ? 1 : 0;
     return 0;
 }
 

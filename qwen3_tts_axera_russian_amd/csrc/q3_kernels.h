@@ -115,6 +115,27 @@ int launch_gather_embed(hipStream_t s, const float* table, int V, int H, const i
                         const int* n_frames, int frame_cap, int col, float* h, float* ssq, int R, int row0 = 0,
                         int R_total = 0, const int* forced = nullptr, half_t* xh = nullptr, const float* gamma = nullptr);
 
+// Prefix state of one utterance between its talker KV slot and a prefix-cache entry (q3e_admit_keyed), either way, in one
+// launch over every layer: rows [0, n_rows) of K and V of every KV head -- one contiguous run of n_rows * 256 bytes per
+// (layer, K|V, head) on both sides, moved 16 bytes per lane -- and the last prefix row's pre-norm residual with its
+// sum-of-squares partials (what the final norm after a prefill reads), between row h_row of the fragment-ordered h / ssq
+// and the entry's row-major state.
+struct PrefixMoveArgs {
+    half_t* kc = nullptr;       // talker cache: [layer][slot][n_kv][n_ctx][128]
+    half_t* vc = nullptr;
+    size_t layer_stride = 0;    // elements between two layers of kc / vc
+    int n_layers = 0, n_kv = 0, n_ctx = 0;
+    int slot = 0, n_rows = 0;   // n_rows <= min(n_ctx, max_rows)
+    half_t* entry = nullptr;    // [layer][2][n_kv][max_rows][128]
+    int max_rows = 0;
+    float* state = nullptr;     // [H + H/16]: residual row, then its ssq partials
+    float* h = nullptr;         // Work::h / Work::ssq of the talker
+    float* ssq = nullptr;
+    int h_row = 0, H = 0;
+    int restore = 0;            // 0: slot -> entry, 1: entry -> slot
+};
+int launch_prefix_move(hipStream_t s, const PrefixMoveArgs& a);
+
 // Per-slot parameters of the frame loop (q3e_open / q3e_admit): one entry per row of the batch.  When a sampling kernel
 // gets a non-null `slots` array it reads the row's entry instead of its scalar fields (frame budget, temperature, top-k,
 // top-p, draw seed); one workgroup handles one row, so every branch these values pick stays uniform in the workgroup.

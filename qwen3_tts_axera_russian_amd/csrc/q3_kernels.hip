@@ -1074,6 +1074,49 @@ int launch_final_norm(hipStream_t s, const FinalNormArgs& a) {
 }
 
 // ---------------------------------------------------------------------------
+// prefix cache: an utterance's prefix state between its KV slot and a pool entry
+// ---------------------------------------------------------------------------
+// grid (x, n_layers * 2 * n_kv): workgroups (., y) move run y = (layer, K|V, head), 16 bytes per lane, grid-stride over
+// the run; those of run 0 also move the residual row and its ssq partials.
+__global__ void __launch_bounds__(256) prefix_move_kernel(PrefixMoveArgs a) {
+    const int run = blockIdx.y;
+    const int head = run % a.n_kv, kv = (run / a.n_kv) & 1, layer = run / (2 * a.n_kv);
+    uint4* cache = (uint4*)((kv ? a.vc : a.kc) + (size_t)layer * a.layer_stride + ((size_t)a.slot * a.n_kv + head) * a.n_ctx * 128);
+    uint4* ent = (uint4*)(a.entry + (size_t)run * a.max_rows * 128);
+    const uint4* src = a.restore ? ent : cache;
+    uint4* dst = a.restore ? cache : ent;
+    const int n16 = a.n_rows * 16;   // 16-byte groups of the run
+    const int i0 = blockIdx.x * blockDim.x + threadIdx.x, step = gridDim.x * blockDim.x;
+    for (int i = i0; i < n16; i += step) dst[i] = src[i];
+    if (run != 0) return;
+    for (int k4 = i0; k4 < a.H / 4; k4 += step) {
+        float4* ph = (float4*)(a.h + frag_idx(a.h_row, k4 * 4, a.H));
+        float4* pe = (float4*)(a.state + k4 * 4);
+        if (a.restore) *ph = *pe;
+        else *pe = *ph;
+    }
+    const int parts = a.H / 16;
+    for (int p = i0; p < parts; p += step) {
+        float* ps = a.ssq + (size_t)a.h_row * parts + p;
+        float* pe = a.state + a.H + p;
+        if (a.restore) *ps = *pe;
+        else *pe = *ps;
+    }
+}
+int launch_prefix_move(hipStream_t s, const PrefixMoveArgs& a) {
+    if (!a.kc || !a.vc || !a.entry || !a.state || !a.h || !a.ssq || a.n_layers <= 0 || a.n_kv <= 0 || a.slot < 0 || a.n_rows <= 0 ||
+        a.n_rows > a.n_ctx || a.n_rows > a.max_rows || a.h_row < 0 || a.H <= 0 || a.H % 32) {
+        Q3_LOG("launch_prefix_move: bad arguments (%d rows, entry of %d, n_ctx %d)", a.n_rows, a.max_rows, a.n_ctx);
+        return -1;
+    }
+    int gx = (a.n_rows * 16 + 255) / 256;   // 256 lanes x 16 B = 16 rows of a run per workgroup
+    if (gx > 8) gx = 8;
+    hipLaunchKernelGGL(prefix_move_kernel, dim3(gx, a.n_layers * 2 * a.n_kv), dim3(256), 0, s, a);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // embedding gather with ssq partials
 // ---------------------------------------------------------------------------
 __global__ void gather_embed_kernel(const float* __restrict__ table, int V, int H, const int* __restrict__ tok,

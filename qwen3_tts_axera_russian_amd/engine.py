@@ -4,6 +4,7 @@ Stands where the reference's client closes the loop over sockets (dual_npu/tts_c
 the per-frame work (talker step, 15-group code predictor, feedback sum) stays on the GPU."""
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass
 
@@ -196,8 +197,24 @@ class FrameEngine:
             raise RuntimeError("q3e_open failed")
         self.B = B
 
-    def admit(self, slots, prefixes, n_text, params):
-        """Per-slot mode: put new utterances into `slots` (q3e_admit), each with its SlotParams (checked here first)."""
+    def prefix_cache(self, n_entries, max_rows=64):
+        """Reserve a device pool of `n_entries` prefix entries of up to `max_rows` rows each for admit(keys=...)
+        (q3e_prefix_cache; 0 entries releases it).  Drops every entry.  Raises ValueError when the engine refuses."""
+        if self._lib.q3e_prefix_cache(self.h, int(n_entries), int(max_rows)) != 0:
+            raise ValueError(f"q3e_prefix_cache({n_entries}, {max_rows}) refused")
+
+    def prefix_stats(self):
+        """-> dict: hits, misses, stores, evictions, too_long, in_use of the prefix cache (q3e_prefix_stats)."""
+        out = np.zeros(6, np.int64)
+        if self._lib.q3e_prefix_stats(self.h, out.ctypes.data_as(hiplib.i64p)) != 0:
+            raise RuntimeError("q3e_prefix_stats failed")
+        return dict(zip(("hits", "misses", "stores", "evictions", "too_long", "in_use"), (int(v) for v in out)))
+
+    def admit(self, slots, prefixes, n_text, params, keys=None):
+        """Per-slot mode: put new utterances into `slots` (q3e_admit), each with its SlotParams (checked here first).
+        keys (q3e_admit_keyed): one 16-byte key per utterance, or None for an utterance that is not cached -- a digest of
+        everything that determines its prefix rows; an utterance whose key the prefix cache holds takes its KV rows and
+        frame-0 state from there instead of a prefill, bit for bit the same.  -> None, or with keys the hit flags (bool [n])."""
         slots = np.ascontiguousarray(np.asarray(slots, np.int32))
         assert len(slots) == len(prefixes) == len(n_text) == len(params) and len(slots) > 0
         for p in params:
@@ -208,10 +225,26 @@ class FrameEngine:
         arr = (hiplib.SlotParamsC * len(params))(*[
             hiplib.SlotParamsC(int(p.max_frames), float(p.temperature), int(p.top_k), float(p.top_p), float(p.cp_temperature),
                                int(p.cp_top_k), int(p.seed), int(p.utt), 1 if p.text_stream else 0) for p in params])
-        rc = self._lib.q3e_admit(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
-                                 hiplib.iptr(nt), arr)
+        if keys is None:
+            rc = self._lib.q3e_admit(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
+                                     hiplib.iptr(nt), arr)
+            if rc != 0:
+                raise RuntimeError(f"q3e_admit failed: {rc}")
+            return None
+        assert len(keys) == len(slots)
+        kk = np.zeros((len(slots), 2), np.uint64)
+        for u, k in enumerate(keys):
+            if k is None:
+                continue
+            if not isinstance(k, (bytes, bytearray)) or len(k) != 16:
+                raise ValueError(f"a prefix key is 16 bytes or None (got {k!r})")
+            kk[u] = np.frombuffer(bytes(k), "<u8")
+        hit = np.zeros(len(slots), np.int32)
+        rc = self._lib.q3e_admit_keyed(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
+                                       hiplib.iptr(nt), arr, kk.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), hiplib.iptr(hit))
         if rc != 0:
-            raise RuntimeError(f"q3e_admit failed: {rc}")
+            raise RuntimeError(f"q3e_admit_keyed failed: {rc}")
+        return hit.astype(bool)
 
     def reserve_text(self, max_rows):
         """Room for `max_rows` streamed text rows per slot (q3e_text_reserve; before open(); 0 releases it)."""
