@@ -98,16 +98,116 @@ __device__ __forceinline__ int uniform_load(const int* p) {
     return *(const __attribute__((address_space(4))) int*)p;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+// ---- cross-lane exchange: the value of lane (l ^ MASK) inside aligned groups of WIDTH lanes ----
+// __shfl_xor becomes a ds_bpermute_b32 on gfx950: an LDS instruction, queued behind whatever else the CU's LDS pipe is
+// serving (beside the vocoder's persistent workgroups: their ds_reads), its result behind an s_waitcnt lgkmcnt.  The same
+// xor butterfly exists in the register file: DPP modifiers inside a row of 16 lanes (the compiler folds the move into the
+// add), v_permlane16_swap / v_permlane32_swap across rows.  The exchange is the same, so every reduction built on it
+// keeps its tree and its bits.
+//
+// CONTRACT: every lane of the exchange group (the WIDTH aligned lanes) is active at the call.  A DPP read of an inactive
+// lane returns 0 (bound_ctrl), a permlane swap leaves inactive lanes unswapped -- neither is what ds_bpermute returns.
+// Uniform-per-group divergence is fine (attn_kernel's `if (t < T)` per 16-lane group with WIDTH 16); a site whose mask
+// is not uniform per group keeps __shfl_xor, with a comment saying why (none today; attn_kernel's merge of a wave's
+// groups keeps it for another reason, written there).
+// -DQ3_XLANE_SHFL (through Q3_EXTRA_HIPCC_FLAGS) expands the helpers to __shfl_xor again: the A/B build, not a runtime knob.
+template <int MASK, int WIDTH>
+__device__ __forceinline__ int xlane_shfl(int v) {
+    return __shfl_xor(v, MASK, WIDTH);
+}
+template <int CTRL>
+__device__ __forceinline__ int dpp_mov(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true);
+}
+template <int MASK, int WIDTH>
+__device__ __forceinline__ int xlane_xor(int v) {
+    static_assert(WIDTH == 4 || WIDTH == 16 || WIDTH == 64, "exchange groups are quads, rows or the wave");
+    static_assert(MASK > 0 && MASK < WIDTH && (MASK & (MASK - 1)) == 0, "one xor bit inside the group");
+#ifdef Q3_XLANE_SHFL
+    return xlane_shfl<MASK, WIDTH>(v);
+#else
+    if constexpr (MASK == 1) {
+        return dpp_mov<0xB1>(v);                       // quad_perm:[1,0,3,2]
+    } else if constexpr (MASK == 2) {
+        return dpp_mov<0x4E>(v);                       // quad_perm:[2,3,0,1]
+    } else if constexpr (MASK == 4) {
+        return dpp_mov<0x1B>(dpp_mov<0x141>(v));       // row_half_mirror (xor 7), then quad_perm:[3,2,1,0] (xor 3)
+    } else if constexpr (MASK == 8) {
+        return dpp_mov<0x128>(v);                      // row_ror:8
+    } else if constexpr (MASK == 16) {
+        // swap(vdst, src): odd rows of vdst <-> even rows of src.  With both = v: [0] holds the even rows' values in
+        // every row pair, [1] the odd rows' -- a lane takes the one that is not its own.
+        const auto r = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
+        return (int)((__lane_id() & 16) ? r[0] : r[1]);
+    } else {
+        // the same with the wave's halves: [0] = lanes 0-31's values in both halves, [1] = lanes 32-63's
+        const auto r = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
+        return (int)((__lane_id() & 32) ? r[0] : r[1]);
+    }
+#endif
+}
+template <int MASK, int WIDTH>
+__device__ __forceinline__ float xlane_xor(float v) {
+    return __int_as_float(xlane_xor<MASK, WIDTH>(__float_as_int(v)));
+}
+template <int MASK, int WIDTH>
+__device__ __forceinline__ float xlane_shfl(float v) {
+    return __int_as_float(xlane_shfl<MASK, WIDTH>(__float_as_int(v)));
+}
+// The butterflies of the call sites, stage order spelled by the name: down = WIDTH/2, ..., 2, 1; up = 1, 2, ..., WIDTH/2.
+// XL: the exchange (xlane_xor in the kernels; the test hook also instantiates them on xlane_shfl).
+struct XlDpp {
+    template <int MASK, int WIDTH, typename T>
+    static __device__ __forceinline__ T x(T v) { return xlane_xor<MASK, WIDTH>(v); }
+};
+struct XlShfl {
+    template <int MASK, int WIDTH, typename T>
+    static __device__ __forceinline__ T x(T v) { return xlane_shfl<MASK, WIDTH>(v); }
+};
+template <int WIDTH, int MASK = WIDTH / 2, typename XL = XlDpp>
+__device__ __forceinline__ float group_sum_down(float v) {
+    v += XL::template x<MASK, WIDTH>(v);
+    if constexpr (MASK > 1) v = group_sum_down<WIDTH, MASK / 2, XL>(v);
     return v;
 }
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+// two sums side by side, stage by stage (the attention kernels' pair of scores)
+template <int WIDTH, int MASK = WIDTH / 2, typename XL = XlDpp>
+__device__ __forceinline__ void group_sum_down2(float& a, float& b) {
+    a += XL::template x<MASK, WIDTH>(a);
+    b += XL::template x<MASK, WIDTH>(b);
+    if constexpr (MASK > 1) group_sum_down2<WIDTH, MASK / 2, XL>(a, b);
+}
+template <int WIDTH, int MASK = 1, typename XL = XlDpp>
+__device__ __forceinline__ float group_sum_up(float v) {
+    v += XL::template x<MASK, WIDTH>(v);
+    if constexpr (MASK * 2 < WIDTH) v = group_sum_up<WIDTH, MASK * 2, XL>(v);
     return v;
 }
+template <int WIDTH, int MASK = WIDTH / 2, typename XL = XlDpp>
+__device__ __forceinline__ float group_max_down(float v) {
+    v = fmaxf(v, XL::template x<MASK, WIDTH>(v));
+    if constexpr (MASK > 1) v = group_max_down<WIDTH, MASK / 2, XL>(v);
+    return v;
+}
+template <int WIDTH, int MASK = 1, typename XL = XlDpp>
+__device__ __forceinline__ float group_max_up(float v) {
+    v = fmaxf(v, XL::template x<MASK, WIDTH>(v));
+    if constexpr (MASK * 2 < WIDTH) v = group_max_up<WIDTH, MASK * 2, XL>(v);
+    return v;
+}
+// (value, index) arg-max exchange, lowest index wins ties
+template <int WIDTH, int MASK = WIDTH / 2, typename XL = XlDpp>
+__device__ __forceinline__ void group_argmax_down(float& v, int& idx) {
+    const float ov = XL::template x<MASK, WIDTH>(v);
+    const int oi = XL::template x<MASK, WIDTH>(idx);
+    if (ov > v || (ov == v && oi < idx)) {
+        v = ov;
+        idx = oi;
+    }
+    if constexpr (MASK > 1) group_argmax_down<WIDTH, MASK / 2, XL>(v, idx);
+}
+__device__ __forceinline__ float wave_sum(float v) { return group_sum_down<64>(v); }
+__device__ __forceinline__ float wave_max(float v) { return group_max_down<64>(v); }
 __device__ __forceinline__ half_t sat_half(float x) {
     return (half_t)fminf(fmaxf(x, -65504.f), 65504.f);
 }
@@ -286,10 +386,7 @@ __global__ void __launch_bounds__(NW * 64)
         for (int i = 0; i < SQI; i++) {
             const int g4 = tid + i * NTH;
             float s = (sq[i].x + sq[i].y) + (sq[i].z + sq[i].w);
-            s += __shfl_xor(s, 8, 16);
-            s += __shfl_xor(s, 4, 16);
-            s += __shfl_xor(s, 2, 16);
-            s += __shfl_xor(s, 1, 16);
+            s = group_sum_down<16>(s);
             if (g4 < MR * 16 && (g4 & 15) == 0) inv_s[g4 / 16] = (1.0f / sqrtf(s / (float)K + a.eps)) * NORM_POST;
         }
     }
@@ -344,11 +441,7 @@ __global__ void __launch_bounds__(NW * 64)
                     const float hn = ok ? hold[i] + v : 0.f;
                     if (ok) Q3_OUT_STORE(hn, &a.h_out[frag_idx(m, ng, a.N)]);
                     if (ok && a.xh_out) Q3_OUT_STORE(pre_scaled(hn, gnext[i]), &a.xh_out[frag_idx(m, ng, a.N)]);
-                    float s = hn * hn;
-                    s += __shfl_xor(s, 8, 16);
-                    s += __shfl_xor(s, 4, 16);
-                    s += __shfl_xor(s, 2, 16);
-                    s += __shfl_xor(s, 1, 16);
+                    const float s = group_sum_down<16>(hn * hn);
                     if (ok && (n & 15) == 0) Q3_OUT_STORE(s, &a.ssq_out[(size_t)m * (a.N / 16) + (ng >> 4)]);
                 }
             }
@@ -460,11 +553,7 @@ __device__ __forceinline__ void gemm_epilogue(const LinArgs& a, f4 (&acc)[BM / 3
                         const float hn = ok ? a.h_out[hi] + v : 0.f;
                         if (ok) a.h_out[hi] = hn;
                         if (ok && a.xh_out) a.xh_out[hi] = pre_scaled(hn, a.gamma[ng]);
-                        float s2 = hn * hn;
-                        s2 += __shfl_xor(s2, 8, 16);
-                        s2 += __shfl_xor(s2, 4, 16);
-                        s2 += __shfl_xor(s2, 2, 16);
-                        s2 += __shfl_xor(s2, 1, 16);
+                        const float s2 = group_sum_down<16>(hn * hn);
                         if (ok && c == 0) a.ssq_out[(size_t)m * (a.N / 16) + (ng >> 4)] = s2;
                     }
                 }
@@ -877,11 +966,7 @@ __global__ void __launch_bounds__(NW * 64)
         const float hn = ok ? hold + v : 0.f;
         if (ok) Q3_OUT_STORE(hn, &p_h[frag_idx(m, ng, N)]);
         if (ok && p_xh_out) Q3_OUT_STORE(pre_scaled(hn, gnext), &p_xh_out[frag_idx(m, ng, N)]);
-        float s = hn * hn;
-        s += __shfl_xor(s, 8, 16);
-        s += __shfl_xor(s, 4, 16);
-        s += __shfl_xor(s, 2, 16);
-        s += __shfl_xor(s, 1, 16);
+        const float s = group_sum_down<16>(hn * hn);
         if (ok && n == 0) Q3_OUT_STORE(s, &p_ssq_out[(size_t)m * (N / 16) + tile0]);
     }
 }
@@ -1006,8 +1091,7 @@ __device__ __forceinline__ void store_row_ssq(float* h, float* ssq, int r, int H
         p[3] = pre_scaled(v.w, g.w);
     }
     float s = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-    s += __shfl_xor(s, 1, 4);
-    s += __shfl_xor(s, 2, 4);
+    s = group_sum_up<4>(s);   // every caller's k4 loop runs whole quads (H is a multiple of 16)
     if ((k4 & 3) == 0) ssq[(size_t)r * (H / 16) + (k4 >> 2)] = s;
 }
 
@@ -1276,6 +1360,12 @@ __global__ void __launch_bounds__(1024) attn_kernel(AttnArgs a) {
 #pragma unroll
     for (int j = 0; j < 8; j++) a0[j] = a1[j] = 0.f;
 
+    // NOT restructured on purpose (e.g. the prefetched keys' scores hoisted out of their branches, so that their
+    // reductions overlap): the compiler contracts `d += q * k` differently from call site to call site of this lambda --
+    // in the ISA some sites compute the first two terms as v_fma_mix_f32 and the rest as v_pk_mul_f32 + v_add_f32, the
+    // others all eight unfused, and which site does what differs per instantiation -- so moving the dot products changes
+    // the low bits of some scores, and with them codec ids downstream.  Whoever restructures this pins the arithmetic
+    // first (`#pragma clang fp contract(off)` in the dot product), as a change of its own that moves the bits knowingly.
     auto step = [&](const h8& kk, const h8& vv) {
         float d0 = 0.f, d1 = 0.f;
 #pragma unroll
@@ -1284,11 +1374,8 @@ __global__ void __launch_bounds__(1024) attn_kernel(AttnArgs a) {
             d0 += q0[j] * kf;
             d1 += q1[j] * kf;
         }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            d0 += __shfl_xor(d0, o, 16);
-            d1 += __shfl_xor(d1, o, 16);
-        }
+        // inside `if (t < T)`, which is uniform per 16-lane group: the whole exchange group is active (xlane_xor's contract)
+        group_sum_down2<16>(d0, d1);
         const float n0 = fmaxf(m0, d0), n1 = fmaxf(m1, d1);
         const float c0 = __expf(m0 - n0), c1 = __expf(m1 - n1);   // exp(-inf) = 0 on the first row
         const float p0 = __expf(d0 - n0), p1 = __expf(d1 - n1);
@@ -1325,7 +1412,11 @@ __global__ void __launch_bounds__(1024) attn_kernel(AttnArgs a) {
     }
     asm volatile("" ::"v"(a0[0]), "v"(l0));
     Q3_PH(2);  // cached rows + the new token processed
-    // merge the 4 groups of a wave (lanes xor 16, 32), then the waves through LDS
+    // merge the 4 groups of a wave (lanes xor 16, 32), then the waves through LDS.
+    // These two stages stay on __shfl_xor although every lane is active: 20 independent exchanges per stage overlap in
+    // the LDS queue (two round trips on the critical path, not forty), and with them on permlane swaps the compiler
+    // fuses the first terms of one more of step()'s dot products into v_fma_mix_f32 in the APRE = 8 instantiations
+    // (16 instead of 12 in the ISA) -- other low bits in some scores, other codec ids downstream.  See the note at step().
 #pragma unroll
     for (int o = 16; o <= 32; o <<= 1) {
         const float om0 = __shfl_xor(m0, o, 64), om1 = __shfl_xor(m1, o, 64);
@@ -1481,11 +1572,7 @@ __global__ void __launch_bounds__(256)
             d0 += (qs[0][l16 * 8 + j] * a.scale) * kf;
             d1 += (qs[1][l16 * 8 + j] * a.scale) * kf;
         }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            d0 += __shfl_xor(d0, o, 16);
-            d1 += __shfl_xor(d1, o, 16);
-        }
+        group_sum_down2<16>(d0, d1);
         if (l16 == 0) {
             sc[0][grp] = d0;
             sc[1][grp] = d1;
@@ -1641,11 +1728,7 @@ __global__ void __launch_bounds__(256) attn_tile_mfma_kernel(AttnArgs a) {
                 float v = sh[qb][r] + sl[qb][r] * ILO;
                 if (!(i < nrows && key <= pos0 + i)) v = -INFINITY;          // causal mask, rows beyond the tile
                 sc[qb][r] = v;
-                float x = v;
-                x = fmaxf(x, __shfl_xor(x, 1, 16));
-                x = fmaxf(x, __shfl_xor(x, 2, 16));
-                x = fmaxf(x, __shfl_xor(x, 4, 16));
-                x = fmaxf(x, __shfl_xor(x, 8, 16));
+                const float x = group_max_up<16>(v);
                 mx[qb][r] = x;
                 if (c == 0) red[w * 32 + 16 * qb + i] = x;
             }
@@ -1663,11 +1746,7 @@ __global__ void __launch_bounds__(256) attn_tile_mfma_kernel(AttnArgs a) {
                 const half_t hi = (half_t)p;
                 ph[qr * VP + 16 * w + c] = hi;
                 pl[qr * VP + 16 * w + c] = (half_t)((p - (float)hi) * LO);
-                float ssum = p;
-                ssum += __shfl_xor(ssum, 1, 16);
-                ssum += __shfl_xor(ssum, 2, 16);
-                ssum += __shfl_xor(ssum, 4, 16);
-                ssum += __shfl_xor(ssum, 8, 16);
+                const float ssum = group_sum_up<16>(p);
                 if (c == 0) red2[w * 32 + qr] = ssum;
                 mrow[qb][r] = mn;
             }
@@ -1789,15 +1868,7 @@ int launch_attn(hipStream_t s, const AttnArgs& a, int mode) {
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ void block_argmax(float& v, int& idx, float* sv, int* si) {
     // lowest index wins ties
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(idx, o, 64);
-        if (ov > v || (ov == v && oi < idx)) {
-            v = ov;
-            idx = oi;
-        }
-    }
+    group_argmax_down<64>(v, idx);
     const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         sv[w] = v;
@@ -2244,15 +2315,7 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
                 bidx = v4 * 4 + j;
             }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bidx, o, 64);
-        if (ov > best || (ov == best && oi < bidx)) {
-            best = ov;
-            bidx = oi;
-        }
-    }
+    group_argmax_down<64>(best, bidx);
     if ((tid & 63) == 0) {
         sv[tid >> 6] = best;
         si[tid >> 6] = bidx;
@@ -2397,6 +2460,49 @@ int launch_feedback(hipStream_t s, const int* codes16, int R, const float* talke
     if (R <= 0) return 0;
     hipLaunchKernelGGL(feedback_kernel, dim3(R), dim3(256), 0, s, codes16, talker_emb, talker_vocab, cp_tables,
                        cp_vocab, n_groups, pad_embed, h_out, ssq_out, H, xh_out, gamma);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// test hook of the cross-lane helpers (q3t_xlane_case): one kernel applies a butterfly built on xlane_xor and the same
+// butterfly built on __shfl_xor to the same registers.  op 0: sum, 1: max, 2: the (value, index) arg-max exchange of
+// block_argmax (index = the element's position in `in`); stages WIDTH/2 .. 1.  n is a multiple of 64 (whole waves, the
+// helpers' contract); out_* hold n words, for op 2 another n with the winning indices behind them.
+// ---------------------------------------------------------------------------
+template <int OP, int WIDTH>
+__global__ void __launch_bounds__(256) xlane_case_kernel(const float* __restrict__ in, int n, float* __restrict__ out_new,
+                                                         float* __restrict__ out_shfl) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // grid * block == n
+    const float v = in[i];
+    if (OP == 0) {
+        out_new[i] = group_sum_down<WIDTH, WIDTH / 2, XlDpp>(v);
+        out_shfl[i] = group_sum_down<WIDTH, WIDTH / 2, XlShfl>(v);
+    } else if (OP == 1) {
+        out_new[i] = group_max_down<WIDTH, WIDTH / 2, XlDpp>(v);
+        out_shfl[i] = group_max_down<WIDTH, WIDTH / 2, XlShfl>(v);
+    } else {
+        float va = v, vb = v;
+        int ia = i, ib = i;
+        group_argmax_down<WIDTH, WIDTH / 2, XlDpp>(va, ia);
+        group_argmax_down<WIDTH, WIDTH / 2, XlShfl>(vb, ib);
+        out_new[i] = va;
+        out_new[n + i] = __int_as_float(ia);
+        out_shfl[i] = vb;
+        out_shfl[n + i] = __int_as_float(ib);
+    }
+}
+int launch_xlane_case(hipStream_t s, int op, int width, int n, const float* in, float* out_new, float* out_shfl) {
+    if (op < 0 || op > 2 || (width != 4 && width != 16 && width != 64) || n <= 0 || n % 64) return -2;
+    const int threads = n % 256 ? 64 : 256;
+    const dim3 grid(n / threads), block(threads);
+#define Q3_XLANE(OP_, W_)                                                                                   \
+    if (op == OP_ && width == W_)                                                                           \
+        hipLaunchKernelGGL((xlane_case_kernel<OP_, W_>), grid, block, 0, s, in, n, out_new, out_shfl);
+    Q3_XLANE(0, 4) Q3_XLANE(0, 16) Q3_XLANE(0, 64)
+    Q3_XLANE(1, 4) Q3_XLANE(1, 16) Q3_XLANE(1, 64)
+    Q3_XLANE(2, 4) Q3_XLANE(2, 16) Q3_XLANE(2, 64)
+#undef Q3_XLANE
     Q3_HIP(hipGetLastError(), -1);
     return 0;
 }

@@ -16,6 +16,7 @@ int set_linear_split_rows(int on);
 int set_linear_narrow8(int on);
 int set_linear_wide_tiles(int on);
 int set_attn_short(int on);
+int launch_xlane_case(hipStream_t s, int op, int width, int n, const float* in, float* out_new, float* out_shfl);
 int set_gemm_min_rows(int n);
 int set_gemm_glds(int on);
 int reset_linear_knobs();
@@ -414,6 +415,22 @@ int q3t_voc_attn(int kernel, const float* x, float* y, int B, int H, int D, int 
         for (int l = L; l < ld; l++)
             if (hy[r * ld + l] != GUARD) return -3;
     }
+    return 0;
+}
+
+// The cross-lane helpers of q3_kernels.hip (xlane_xor) against __shfl_xor, both applied to the same registers by one
+// kernel.  op 0: sum, 1: max, 2: the (value, index) arg-max exchange of block_argmax; width 4, 16 or 64 lanes; n values
+// (a multiple of 64).  out_new / out_shfl: n words each, for op 2 another n int32 words (the winning indices) behind them.
+int q3t_xlane_case(int op, int width, int n, const float* in, float* out_new, float* out_shfl) {
+    if (!in || !out_new || !out_shfl || n <= 0 || n % 64) return -2;
+    const size_t words = (size_t)n * (op == 2 ? 2 : 1);
+    DBuf din, da, db;
+    if (!din.up(in, (size_t)n * 4) || !da.alloc(words * 4) || !db.alloc(words * 4)) return -1;
+    const int rc = launch_xlane_case(nullptr, op, width, n, (const float*)din.p, (float*)da.p, (float*)db.p);
+    if (rc) return rc;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    Q3_HIP(hipMemcpy(out_new, da.p, words * 4, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(out_shfl, db.p, words * 4, hipMemcpyDeviceToHost), -1);
     return 0;
 }
 

@@ -216,6 +216,7 @@ def load_test():
     _sig(lib, "q3t_attn", c_int, [c_int, c_int, c_int, f32p, f32p, f32p, c_float, f32p, f32p, c_int, i32p, i32p, c_int,
                                   c_int, c_int, c_int, u16p, u16p, c_int, c_int, i32p, c_int, c_int, c_int, c_int, u16p])
     _sig(lib, "q3t_voc_attn", c_int, [c_int, f32p, f32p, c_int, c_int, c_int, c_int, c_int, c_float])
+    _sig(lib, "q3t_xlane_case", c_int, [c_int, c_int, c_int, f32p, f32p, f32p])
     _sig(lib, "q3t_set_linear_split_rows", c_int, [c_int])
     _sig(lib, "q3t_set_linear_narrow8", c_int, [c_int])
     _sig(lib, "q3t_set_linear_wide_tiles", c_int, [c_int])
