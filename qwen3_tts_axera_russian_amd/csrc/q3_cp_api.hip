@@ -270,15 +270,7 @@ int cp_predict_batch(void* hh, const float* hidden, const int32_t* code_0, int n
     } else if (!h->graph.e || h->graph_rows != R) {
         if (body()) return -1;  // eager once (kernel attributes), result is valid
         Q3_HIP(hipStreamSynchronize(h->s), -1);
-        h->graph.reset();
-        Q3_HIP(hipStreamBeginCapture(h->s, hipStreamCaptureModeThreadLocal), -1);
-        int rc = body();
-        hipError_t e = hipStreamEndCapture(h->s, &h->graph.g);
-        if (rc || e != hipSuccess) {
-            Q3_LOG("cp_predict: graph capture failed");
-            return -1;
-        }
-        Q3_HIP(hipGraphInstantiate(&h->graph.e, h->graph.g, nullptr, nullptr, 0), -1);
+        if (h->graph.capture(h->s, hipStreamCaptureModeThreadLocal, "cp_predict", body)) return -1;
         h->graph_rows = R;
     } else {
         Q3_HIP(hipGraphLaunch(h->graph.e, h->s), -1);

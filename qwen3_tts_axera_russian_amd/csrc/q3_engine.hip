@@ -6,6 +6,7 @@
 // same graph serves every frame.
 #include "../../include/qwen3tts_engine.h"
 #include "q3_cp.h"
+#include "q3_engine_host.h"
 
 #include <algorithm>
 #include <chrono>
@@ -55,59 +56,31 @@ struct Engine {
     hipStream_t cs[8] = {nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[8] = {nullptr};
     // per-slot mode (q3e_open / q3e_admit / q3e_release): every row reads its own budget, sampling settings and draw
-    // stream from d_slots; the host keeps each slot's budget and the frame steps run since its admission (capped at
-    // max_frames: no host counter grows with the server's life)
+    // stream from d_slots; the host's view of every slot -- budget, frames emitted, text rows, steps held -- and every rule
+    // over it is the book (q3_engine_host.h)
     bool slot_mode = false;
     int graph_slots = -1;
     SlotParams* d_slots = nullptr;          // [max_batch]
-    std::vector<int> h_budget, h_age;       // h_age[b] < 0: the slot holds no utterance
-    std::vector<char> h_live;               // admitted and neither released nor known to have ended
+    SlotBook book;
     // text streamed into running utterances (q3e_text_reserve / q3e_push_text): row f of a text slot's rows is added to
     // the feedback of its frame f where the pad stands.  The host writes rows and counters on s between the launches.
     float* d_text = nullptr;                // [max_batch][text_cap][hidden]
     int* d_tavail = nullptr;                // [max_batch] rows pushed (0: not a text slot)
     int text_cap = 0;
     std::vector<SlotParams> h_sp;           // the slots' device entries (the final push rewrites the flags)
-    std::vector<int> h_trows;               // rows pushed per slot
-    std::vector<char> h_text, h_tfinal;     // the slot holds a text utterance / its text has ended
     int up_i[2] = {0, 0};                   // staging of one-word uploads (synchronised before reuse)
     // held text slots (q3e_text_hold): a live text slot without a row for its next frame is held inside the frame while
-    // the other rows step on; h_age then counts the steps a slot was NOT held for (= the frames it has emitted)
+    // the other rows step on
     bool hold = false;
     int* d_held = nullptr;                  // [max_batch] the sampler's per-step verdict, read by the frame's cp_argmax launches
-    std::vector<long long> h_held;          // steps each slot was held for since its admission
     // prefix cache of the per-slot admissions (q3e_prefix_cache / q3e_admit_keyed): a device pool of entries, each the KV
-    // rows of one prefix and the residual row its final norm reads; the host keeps the keys and the use order.  Nothing
-    // of it is an argument of the captured frame.
-    struct PfxEntry {
-        uint64_t k0 = 0, k1 = 0;
-        int n_rows = 0;                     // 0: free
-        unsigned long long use = 0;         // pfx_clock of the last hit or store
-    };
-    half_t* d_pfx = nullptr;                // [pfx_n][layers][2][n_kv][pfx_rows][128]
-    float* d_pfx_state = nullptr;           // [pfx_n][hidden + hidden / 16]
-    int pfx_n = 0, pfx_rows = 0;
-    std::vector<PfxEntry> pfx;
-    unsigned long long pfx_clock = 0;
-    long long pfx_stat[5] = {0, 0, 0, 0, 0};   // hits, misses, stores, evictions, too long
-    size_t pfx_entry_elems() const { return (size_t)kv_t.n_layers * 2 * kv_t.n_kv * pfx_rows * 128; }
+    // rows of one prefix and the residual row its final norm reads; the index keeps the keys and the use order
+    // (q3_engine_host.h).  Nothing of it is an argument of the captured frame.
+    half_t* d_pfx = nullptr;                // [pfx.size()][layers][2][n_kv][pfx.max_rows()][128]
+    float* d_pfx_state = nullptr;           // [pfx.size()][hidden + hidden / 16]
+    PrefixIndex pfx;
+    size_t pfx_entry_elems() const { return (size_t)kv_t.n_layers * 2 * kv_t.n_kv * pfx.max_rows() * 128; }
 };
-
-// the device's verdict for slot b at its next step (talker_sample_row<true>), from the host's copies: a live text slot
-// before its final push has not ended, and has emitted h_age frames
-bool slot_held(const Engine* e, int b) {
-    return e->hold && e->h_live[b] && e->h_text[b] && !e->h_tfinal[b] && e->h_age[b] >= 1 && e->h_age[b] >= e->h_trows[b] &&
-           e->h_age[b] < e->h_budget[b];
-}
-
-// steps a per-slot batch may take before a live text slot whose text has not ended would need a row it does not have
-int text_room(const Engine* e) {
-    int room = e->max_frames;
-    for (int b = 0; b < e->B; b++)
-        if (e->h_live[b] && e->h_text[b] && !e->h_tfinal[b] && e->h_age[b] < e->h_budget[b])
-            room = std::min(room, e->h_trows[b] - e->h_age[b]);
-    return room;
-}
 
 // splitmix64 finaliser of (seed + golden * k): the stream derivations of this file
 unsigned long long mix_seed(unsigned long long seed, unsigned long long k, unsigned long long golden) {
@@ -117,8 +90,10 @@ unsigned long long mix_seed(unsigned long long seed, unsigned long long k, unsig
     return z ^ (z >> 31);
 }
 
-int talker_tail(Engine* e, hipStream_t st, int row0, int R) {
-    // final norm (+ CP seed copy) and codec head for rows row0..row0+R-1
+// The talker's final norm into rows row0..row0+R-1 of the post-norm buffers, with the copy that seeds the code predictor's
+// position 0 (copy_row_off: where cp_frame expects those rows).  row_map (device, indexed by the output row; null: the
+// row itself) names the source rows of the residual stream -- the utterances' last rows after a prefill.
+int talker_final_norm(Engine* e, hipStream_t st, int row0, int R, const int* row_map, int copy_row_off) {
     const Model& m = *e->m;
     const int H = m.cfg.hidden;
     FinalNormArgs f;
@@ -128,20 +103,26 @@ int talker_tail(Engine* e, hipStream_t st, int row0, int R) {
     f.gamma = m.talker.final_norm;
     f.eps = m.cfg.eps;
     f.R = R;
-    f.row0 = row0;
+    f.row0 = row0;   // output rows (fragment-ordered buffers are indexed, not offset)
     f.H = H;
+    f.row_map = row_map;
     f.out_f32 = e->wt.hidden_f32;
     f.out_f16 = e->wt.hidden_f16;
     f.out_copy = e->wc.h;
     f.out_copy_ssq = e->wc.ssq;
     f.out_copy_xh = e->wc.xh;
     f.out_copy_gamma = m.cp.L[0].in_ln;
-    f.out_copy_row_off = cp_seed_row0(e->wc, R, row0, e->B);   // where cp_frame expects its position-0 rows
-    if (launch_final_norm(st, f)) return -1;
+    f.out_copy_row_off = copy_row_off;
+    return launch_final_norm(st, f);
+}
+
+// codec head over rows row0..row0+R-1 of the post-norm hidden
+int codec_head(Engine* e, hipStream_t st, int row0, int R) {
+    const Model& m = *e->m;
     LinArgs a;
     a.wp = m.talker_head.wp;
     a.N = m.cfg.talker_vocab;
-    a.K = H;
+    a.K = m.cfg.hidden;
     a.M = row0 + R;
     a.m_begin = row0;
     a.nt = 1;
@@ -149,6 +130,10 @@ int talker_tail(Engine* e, hipStream_t st, int row0, int R) {
     a.y = e->wt.logits;
     a.ldy = m.cfg.talker_vocab;
     return launch_linear(st, a, PRO_F16, EPI_STORE);
+}
+
+int talker_tail(Engine* e, hipStream_t st, int row0, int R) {
+    return talker_final_norm(e, st, row0, R, nullptr, cp_seed_row0(e->wc, R, row0, e->B)) || codec_head(e, st, row0, R) ? -1 : 0;
 }
 
 int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
@@ -272,6 +257,18 @@ int join_chains(Engine* e) {   // the main stream continues after every chain st
         Q3_HIP(hipEventRecord(e->ev_join[c], e->cs[c]), -1);
         Q3_HIP(hipStreamWaitEvent(e->s, e->ev_join[c], 0), -1);
     }
+    return 0;
+}
+
+// body() (-> 0 ok: the launches of a prefill, up to the codec head) between the events behind q3e_last_prefill_ms; the
+// stream is synchronised on return
+template <class F>
+int timed_prefill(Engine* e, F&& body) {
+    Q3_HIP(hipEventRecord(e->ev0, e->s), -1);
+    if (body()) return -1;
+    Q3_HIP(hipEventRecord(e->ev1, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    hipEventElapsedTime(&e->last_prefill_ms, e->ev0, e->ev1);
     return 0;
 }
 
@@ -435,28 +432,9 @@ int q3e_set_pad_embed(void* ee, const float* pad) {
 // Final norm after a prefill: the rows d_lastrow[row0 .. row0 + R) of the residual stream into rows row0.. of the post-norm
 // buffers and of the code predictor's position-0 input (prefill_ids; a prefix-cache hit launches it for its one row)
 static int prefill_final_norm(Engine* e, int row0, int R, int B_total) {
-    const Model& m = *e->m;
-    const int H = m.cfg.hidden;
-    FinalNormArgs f;
-    f.h = e->wt.h;
-    f.ssq = e->wt.ssq;
-    f.ssq_parts = H / 16;
-    f.gamma = m.talker.final_norm;
-    f.eps = m.cfg.eps;
-    f.R = R;
-    f.row0 = row0;   // output rows (fragment-ordered buffers are indexed, not offset)
-    f.H = H;
-    f.row_map = e->d_lastrow;
-    f.out_f32 = e->wt.hidden_f32;
-    f.out_f16 = e->wt.hidden_f16;
-    f.out_copy = e->wc.h;
-    f.out_copy_ssq = e->wc.ssq;
-    f.out_copy_xh = e->wc.xh;
-    f.out_copy_gamma = m.cp.L[0].in_ln;
     // the first frame's code predictor pass reads its position-0 rows where cp_frame expects them (the same
     // place for one chain and for parallel chains)
-    f.out_copy_row_off = cp_seed_row0(e->wc, B_total, 0, B_total);
-    return launch_final_norm(e->s, f);
+    return talker_final_norm(e, e->s, row0, R, e->d_lastrow, cp_seed_row0(e->wc, B_total, 0, B_total));
 }
 
 // Ragged prefill of n utterances into the KV slots / output rows ids[0..n) (prefix rows concatenated in that order):
@@ -518,91 +496,85 @@ static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, co
     return 0;
 }
 
-// A slot back to "just started" (q3e_refill, q3e_admit): counters, the emitted-token ring, the slot's column of the codes
-// array, its text length and positions (n_rows / n_text: host values that must live until the stream is synchronised)
-static int clear_slot(Engine* e, int b, const int32_t* n_rows, const int32_t* n_text) {
-    Q3_HIP(hipMemsetAsync(e->d_npast + b, 0, sizeof(int), e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_done + b, 0, sizeof(int), e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_nframes + b, 0, sizeof(int), e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_past + 32 * b, 0, sizeof(int) * 32, e->s), -1);
-    Q3_HIP(hipMemset2DAsync(e->d_codes + 16 * (size_t)b, sizeof(int) * 16 * (size_t)e->B, 0xff, sizeof(int) * 16, e->max_frames, e->s), -1);
-    Q3_HIP(hipMemcpyAsync(e->d_ntext + b, n_text, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
-    Q3_HIP(hipMemcpyAsync(e->d_pos0 + b, n_rows, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
-    Q3_HIP(hipMemcpyAsync(e->d_posdec + b, n_rows, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
+// Rows b0..b0+n-1 of every per-slot device array back to a start state, asynchronously on e->s:
+//   fresh  "just started": counters 0, an empty emitted-token ring, positions n_rows[0..n), text lengths n_text[0..n) (null:
+//          0 -- a text slot's comes with its final push); host arrays that must live until the stream is synchronised
+//   idle   ended (done) with the frame counter at the end of the codes array, so nothing is recorded, at position 0
+// and either way the rows' columns of the codes array to -1 and no text row pushed, no hold.
+enum class RowStart { fresh, idle };
+static int reset_rows(Engine* e, int b0, int n, RowStart how, const int32_t* n_rows = nullptr, const int32_t* n_text = nullptr) {
+    const bool idle = how == RowStart::idle;
+    const size_t bytes = sizeof(int) * n;
+    Q3_HIP(hipMemsetAsync(e->d_npast + b0, 0, bytes, e->s), -1);
+    Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->d_done + b0), idle ? 1 : 0, n, e->s), -1);
+    Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->d_nframes + b0), idle ? e->max_frames : 0, n, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_past + 32 * b0, 0, 32 * bytes, e->s), -1);
+    if (n == e->B)
+        Q3_HIP(hipMemsetAsync(e->d_codes, 0xff, sizeof(int) * 16 * (size_t)e->B * e->max_frames, e->s), -1);
+    else
+        Q3_HIP(hipMemset2DAsync(e->d_codes + 16 * (size_t)b0, sizeof(int) * 16 * (size_t)e->B, 0xff, 16 * bytes, e->max_frames, e->s), -1);
+    if (idle || !n_text) Q3_HIP(hipMemsetAsync(e->d_ntext + b0, 0, bytes, e->s), -1);
+    else Q3_HIP(hipMemcpyAsync(e->d_ntext + b0, n_text, bytes, hipMemcpyHostToDevice, e->s), -1);
+    if (idle) {
+        Q3_HIP(hipMemsetAsync(e->d_pos0 + b0, 0, bytes, e->s), -1);
+        Q3_HIP(hipMemsetAsync(e->d_posdec + b0, 0, bytes, e->s), -1);
+        Q3_HIP(hipMemsetAsync(e->d_lastrow + b0, 0, bytes, e->s), -1);
+    } else {
+        Q3_HIP(hipMemcpyAsync(e->d_pos0 + b0, n_rows, bytes, hipMemcpyHostToDevice, e->s), -1);
+        Q3_HIP(hipMemcpyAsync(e->d_posdec + b0, n_rows, bytes, hipMemcpyHostToDevice, e->s), -1);
+    }
+    if (e->d_tavail) Q3_HIP(hipMemsetAsync(e->d_tavail + b0, 0, bytes, e->s), -1);
+    if (e->d_held) Q3_HIP(hipMemsetAsync(e->d_held + b0, 0, bytes, e->s), -1);
     return 0;
 }
 
 // codec head over rows 0..B-1 of the post-norm hidden (rows of running utterances give the logits they already have)
-static int head_all_rows(Engine* e) {
-    const Model& m = *e->m;
-    LinArgs a;
-    a.wp = m.talker_head.wp;
-    a.N = m.cfg.talker_vocab;
-    a.K = m.cfg.hidden;
-    a.M = e->B;
-    a.nt = 1;
-    a.x16 = e->wt.hidden_f16;
-    a.y = e->wt.logits;
-    a.ldy = m.cfg.talker_vocab;
-    return launch_linear(e->s, a, PRO_F16, EPI_STORE);
+static int head_all_rows(Engine* e) { return codec_head(e, e->s, 0, e->B); }
+
+// n_rows prefix rows and `frames` frames of utterance u fit a prefill pass and the context
+static bool check_fit(const Engine* e, const char* who, int u, int n_rows, int frames) {
+    if (n_rows > 0 && n_rows <= e->prefill_rows && n_rows + frames <= e->n_ctx) return true;
+    Q3_LOG("%s: utterance %d: %d prefix rows + %d frames do not fit n_ctx=%d", who, u, n_rows, frames, e->n_ctx);
+    return false;
+}
+
+// slots[u] is one of the batch's B and none of slots[0..u) (called for u = 0, 1, ..: a list is checked in its order,
+// between the other checks of each utterance)
+static bool check_slot_list(const char* who, int u, const int32_t* slots, int B) {
+    if (slots[u] >= 0 && slots[u] < B && std::find(slots, slots + u, slots[u]) == slots + u) return true;
+    Q3_LOG("%s: slot %d is out of range or listed twice (batch of %d)", who, slots[u], B);
+    return false;
 }
 
 int q3e_start(void* ee, int B, const float* prefix, const int32_t* n_rows, const int32_t* n_text, int ignore_eos,
               int max_frames) {
     Engine* e = (Engine*)ee;
     if (!e || !prefix || !n_rows || !n_text || B <= 0 || B > e->max_batch) return -1;
-    const Model& m = *e->m;
-    const int H = m.cfg.hidden;
     if (max_frames <= 0 || max_frames > e->max_frames) max_frames = e->max_frames;
-    std::vector<int> pos0(B);
-    std::vector<unsigned long long> seeds;   // (host staging of this call's uploads: alive until the stream is synchronised)
-    for (int b = 0; b < B; b++) {
-        if (n_rows[b] <= 0 || n_rows[b] > e->prefill_rows || n_rows[b] + max_frames > e->n_ctx) {
-            Q3_LOG("q3e_start: utterance %d: %d prefix rows + %d frames do not fit n_ctx=%d", b, n_rows[b], max_frames,
-                   e->n_ctx);
-            return -1;
-        }
-        pos0[b] = n_rows[b];
-    }
+    for (int b = 0; b < B; b++)
+        if (!check_fit(e, "q3e_start", b, n_rows[b], max_frames)) return -1;
     e->B = B;
     e->ignore_eos = ignore_eos ? 1 : 0;
     e->cap_frames = max_frames;
     e->frames_run = 0;
     e->frames_hi = 0;
     e->slot_mode = false;
-    Q3_HIP(hipMemsetAsync(e->d_npast, 0, sizeof(int) * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_done, 0, sizeof(int) * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_nframes, 0, sizeof(int) * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_past, 0, sizeof(int) * 32 * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_codes, 0xff, sizeof(int) * 16 * (size_t)B * e->max_frames, e->s), -1);
-    {   // a fresh draw stream per request (the reference's generators advance from their seed across requests)
-        unsigned long long z = e->seed + 0x9E3779B97F4A7C15ull * e->n_requests++;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        e->req_seed = e->n_requests == 1 ? e->seed : (z ^ (z >> 31));
-        e->n_refills = 0;
-        seeds.assign(B, e->req_seed);   // (the row index separates the slots' draws)
-        Q3_HIP(hipMemcpyAsync(e->d_seed, seeds.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice, e->s), -1);
-    }
+    if (reset_rows(e, 0, B, RowStart::fresh, n_rows, n_text)) return -1;
+    // a fresh draw stream per request (the reference's generators advance from their seed across requests); the row
+    // index separates the slots' draws
+    const unsigned long long k = e->n_requests++;
+    e->req_seed = k == 0 ? e->seed : mix_seed(e->seed, k, 0x9E3779B97F4A7C15ull);
+    e->n_refills = 0;
+    const std::vector<unsigned long long> seeds(B, e->req_seed);   // (alive until the stream is synchronised)
+    Q3_HIP(hipMemcpyAsync(e->d_seed, seeds.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice, e->s), -1);
     if (e->forced_on) {   // forcing belongs to the batch it was set for
         e->forced_on = false;
         for (auto& g : e->graph) g.reset();
     }
-    Q3_HIP(hipMemcpyAsync(e->d_ntext, n_text, sizeof(int) * B, hipMemcpyHostToDevice, e->s), -1);
-    Q3_HIP(hipMemcpyAsync(e->d_pos0, pos0.data(), sizeof(int) * B, hipMemcpyHostToDevice, e->s), -1);
-    Q3_HIP(hipMemcpyAsync(e->d_posdec, pos0.data(), sizeof(int) * B, hipMemcpyHostToDevice, e->s), -1);
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    Q3_HIP(hipEventRecord(e->ev0, e->s), -1);
-    {
-        std::vector<int> ids(B);
-        for (int b = 0; b < B; b++) ids[b] = b;
-        if (prefill_ids(e, B, ids.data(), prefix, n_rows, B)) return -1;
-    }
-    if (head_all_rows(e)) return -1;
-    Q3_HIP(hipEventRecord(e->ev1, e->s), -1);
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
-    hipEventElapsedTime(&e->last_prefill_ms, e->ev0, e->ev1);
-    return 0;
+    std::vector<int> ids(B);
+    for (int b = 0; b < B; b++) ids[b] = b;
+    return timed_prefill(e, [&] { return prefill_ids(e, B, ids.data(), prefix, n_rows, B) || head_all_rows(e); });
 }
 
 int q3e_run(void* ee, int n_frames) {
@@ -611,26 +583,7 @@ int q3e_run(void* ee, int n_frames) {
     // never step past the frames the batch was started for (nor past the codes array): a further step would
     // have no frame to record into
     int room = (e->cap_frames < e->max_frames ? e->cap_frames : e->max_frames) - e->frames_run;
-    if (e->slot_mode) {   // the live slot with the most budget left
-        room = 0;
-        for (int b = 0; b < e->B; b++)
-            if (e->h_live[b]) room = std::max(room, e->h_budget[b] - e->h_age[b]);
-        if (!e->hold) {
-            room = std::min(room, text_room(e));   // a slot never runs ahead of its text: a starved slot stalls the batch
-        } else {
-            // held text slots: the steps the slot with the most progress ahead of it can take -- up to its rows (or its
-            // budget) for a text slot before its final push, the budget for any other.  0 when every live slot is held.
-            // A text slot that has no frame yet cannot be held (there is no step of its own to repeat): it stalls the batch.
-            room = 0;
-            for (int b = 0; b < e->B; b++) {
-                if (!e->h_live[b]) continue;
-                const bool waits = e->h_text[b] && !e->h_tfinal[b];
-                if (waits && e->h_age[b] == 0 && e->h_trows[b] == 0) return 0;
-                const int upto = waits ? std::min(e->h_trows[b], e->h_budget[b]) : e->h_budget[b];
-                room = std::max(room, upto - e->h_age[b]);
-            }
-        }
-    }
+    if (e->slot_mode) room = e->book.room(e->hold, e->max_frames);
     if (room <= 0) return 0;
     if (n_frames > room) n_frames = room;
     int done_frames = 0;
@@ -653,15 +606,9 @@ int q3e_run(void* ee, int n_frames) {
         for (int c = 0; c < nc; c++) {
             int row0, R;
             chain_rows(e, c, row0, R);
-            e->graph[c].reset();
-            Q3_HIP(hipStreamBeginCapture(chain_stream(e, c), hipStreamCaptureModeRelaxed), -1);
-            int rc = frame_chain(e, chain_stream(e, c), row0, R);
-            hipError_t er = hipStreamEndCapture(chain_stream(e, c), &e->graph[c].g);
-            if (rc || er != hipSuccess) {
-                Q3_LOG("q3e_run: graph capture failed");
+            hipStream_t st = chain_stream(e, c);
+            if (e->graph[c].capture(st, hipStreamCaptureModeRelaxed, "q3e_run", [&] { return frame_chain(e, st, row0, R); }))
                 return -1;
-            }
-            Q3_HIP(hipGraphInstantiate(&e->graph[c].e, e->graph[c].g, nullptr, nullptr, 0), -1);
         }
         e->graph_B = e->B;
         e->graph_ignore = e->ignore_eos;
@@ -693,21 +640,7 @@ int q3e_run(void* ee, int n_frames) {
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     hipEventElapsedTime(&e->last_run_ms, e->ev0, e->ev1);
     if (e->slot_mode) {
-        for (int b = 0; b < e->B; b++) {
-            if (e->h_age[b] < 0) continue;
-            if (!e->hold) {
-                e->h_age[b] = std::min(e->h_age[b] + done_frames, e->max_frames);
-                continue;
-            }
-            // step by step as the device decided (no row arrives during a run, so a slot that is held stays held)
-            for (int i = 0; i < done_frames; i++) {
-                if (slot_held(e, b)) {
-                    e->h_held[b] += done_frames - i;
-                    break;
-                }
-                e->h_age[b] = std::min(e->h_age[b] + 1, e->max_frames);
-            }
-        }
+        e->book.advance(done_frames, e->hold, e->max_frames);
         return done_frames;
     }
     e->frames_run += done_frames;
@@ -723,12 +656,7 @@ int q3e_get_codes(void* ee, int32_t* out, int max_out_frames, int32_t* n_frames_
     Engine* e = (Engine*)ee;
     if (!e || !out || e->B <= 0) return -1;
     int nf = e->frames_hi < e->max_frames ? e->frames_hi : e->max_frames;
-    if (e->slot_mode) {   // up to the frames of the slot admitted first
-        int hi = 0;
-        for (int b = 0; b < e->B; b++)
-            hi = std::max(hi, e->h_age[b]);
-        nf = std::min(hi, e->max_frames);
-    }
+    if (e->slot_mode) nf = std::min(e->book.frames_hi(), e->max_frames);   // up to the frames of the slot admitted first
     if (nf > max_out_frames) nf = max_out_frames;
     // through the pinned staging on the engine's own stream: a pageable destination would go through the runtime's staging
     int* h_np = e->h_read;
@@ -752,11 +680,10 @@ int q3e_get_done(void* ee, int32_t* done, int32_t* frames) {
     std::vector<int> np(e->h_read, e->h_read + e->B);
     // the device raises done[b] on the step AFTER the budget's last frame, a step q3e_run never takes: an utterance
     // that has emitted its whole budget has ended
-    for (int b = 0; b < e->B; b++)
-        if (np[b] >= (e->slot_mode ? e->h_budget[b] : e->cap_frames)) done[b] = 1;
-    if (e->slot_mode)
-        for (int b = 0; b < e->B; b++)
-            if (done[b]) e->h_live[b] = 0;
+    for (int b = 0; b < e->B; b++) {
+        if (np[b] >= (e->slot_mode ? e->book[b].budget : e->cap_frames)) done[b] = 1;
+        if (e->slot_mode && done[b]) e->book.mark_ended(b);
+    }
     if (frames) memcpy(frames, np.data(), sizeof(int) * e->B);
     return 0;
 }
@@ -772,39 +699,22 @@ int q3e_refill(void* ee, int n, const int32_t* slots, const float* prefix, const
         Q3_LOG("q3e_refill: a per-slot batch (q3e_open) takes new utterances with q3e_admit");
         return -1;
     }
-    std::vector<int> ids(slots, slots + n), seen(e->B, 0);
-    for (int u = 0; u < n; u++) {
-        const int b = ids[u];
-        if (b < 0 || b >= e->B || seen[b]++) {
-            Q3_LOG("q3e_refill: slot %d is out of range or listed twice (batch of %d)", b, e->B);
-            return -1;
-        }
-        if (n_rows[u] <= 0 || n_rows[u] > e->prefill_rows || n_rows[u] + e->cap_frames > e->n_ctx) {
-            Q3_LOG("q3e_refill: utterance %d: %d prefix rows + %d frames do not fit n_ctx=%d", u, n_rows[u], e->cap_frames, e->n_ctx);
-            return -1;
-        }
-    }
+    for (int u = 0; u < n; u++)
+        if (!check_slot_list("q3e_refill", u, slots, e->B) || !check_fit(e, "q3e_refill", u, n_rows[u], e->cap_frames)) return -1;
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    Q3_HIP(hipEventRecord(e->ev0, e->s), -1);
-    // per-slot state back to "just started": counters, the emitted-token ring, the slot's column of the codes array
-    for (int u = 0; u < n; u++) {
-        const int b = ids[u];
-        if (clear_slot(e, b, n_rows + u, n_text + u)) return -1;
-        // a fresh draw stream for the new occupant: the counters (frame, group) restart with the slot, so keeping the
-        // request's seed would replay the previous occupant's uniforms
-        unsigned long long z = e->req_seed + 0xD1B54A32D192ED03ull * ++e->n_refills;
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
-        Q3_HIP(hipMemcpyAsync(e->d_seed + b, &z, sizeof(z), hipMemcpyHostToDevice, e->s), -1);   // (synchronised below: z is a local)
+    std::vector<unsigned long long> seeds(n);   // (alive until timed_prefill has synchronised the stream)
+    const int rc = timed_prefill(e, [&]() -> int {
+        for (int u = 0; u < n; u++) {
+            if (reset_rows(e, slots[u], 1, RowStart::fresh, n_rows + u, n_text + u)) return -1;
+            // a fresh draw stream for the new occupant: the counters (frame, group) restart with the slot, so keeping the
+            // request's seed would replay the previous occupant's uniforms
+            seeds[u] = mix_seed(e->req_seed, ++e->n_refills, 0xD1B54A32D192ED03ull);
+            Q3_HIP(hipMemcpyAsync(e->d_seed + slots[u], &seeds[u], sizeof(seeds[u]), hipMemcpyHostToDevice, e->s), -1);
+        }
         Q3_HIP(hipStreamSynchronize(e->s), -1);
-    }
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
-    if (prefill_ids(e, n, ids.data(), prefix, n_rows, e->B)) return -1;
-    if (head_all_rows(e)) return -1;
-    Q3_HIP(hipEventRecord(e->ev1, e->s), -1);
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
-    hipEventElapsedTime(&e->last_prefill_ms, e->ev0, e->ev1);
+        return prefill_ids(e, n, slots, prefix, n_rows, e->B) || head_all_rows(e);
+    });
+    if (rc) return -1;
     e->frames_run = 0;   // the new utterances have their whole frame budget; running ones stop at theirs on the device
     return 0;
 }
@@ -826,16 +736,8 @@ int q3e_open(void* ee, int B, int ignore_eos) {
     e->frames_run = 0;
     e->frames_hi = 0;
     e->slot_mode = true;
-    e->h_budget.assign(B, 0);
-    e->h_age.assign(B, -1);
-    e->h_live.assign(B, 0);
+    e->book.open(B);
     e->h_sp.assign(B, SlotParams());
-    e->h_trows.assign(B, 0);
-    e->h_text.assign(B, 0);
-    e->h_tfinal.assign(B, 0);
-    e->h_held.assign(B, 0);
-    if (e->d_held) Q3_HIP(hipMemsetAsync(e->d_held, 0, sizeof(int) * e->max_batch, e->s), -1);
-    if (e->d_tavail) Q3_HIP(hipMemsetAsync(e->d_tavail, 0, sizeof(int) * e->max_batch, e->s), -1);
     if (e->forced_on) {
         e->forced_on = false;
         for (auto& g : e->graph) g.reset();
@@ -843,15 +745,7 @@ int q3e_open(void* ee, int B, int ignore_eos) {
     // idle rows step through the graph with everything else: they have ended (done), their frame counter sits at the end of
     // the codes array (nothing is recorded), and they run at position 0 of zeroed caches and activations (finite values;
     // rows are independent, so what an idle row computes never reaches another row)
-    Q3_HIP(hipMemsetAsync(e->d_npast, 0, sizeof(int) * B, e->s), -1);
-    Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_done, 1, B, e->s), -1);
-    Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)e->d_nframes, e->max_frames, B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_past, 0, sizeof(int) * 32 * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_ntext, 0, sizeof(int) * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_pos0, 0, sizeof(int) * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_posdec, 0, sizeof(int) * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_lastrow, 0, sizeof(int) * B, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_codes, 0xff, sizeof(int) * 16 * (size_t)B * e->max_frames, e->s), -1);
+    if (reset_rows(e, 0, B, RowStart::idle)) return -1;
     Q3_HIP(hipMemsetAsync(e->d_slots, 0, sizeof(SlotParams) * e->max_batch, e->s), -1);
     if (kv_zero(e->s, e->kv_t) || kv_zero(e->s, e->kv_c)) return -1;
     if (work_zero(e->s, e->wt, c, c.talker_ffn, c.talker_vocab) || work_zero(e->s, e->wc, c, c.cp_ffn, c.cp_vocab)) return -1;
@@ -872,7 +766,7 @@ static int prefix_move(Engine* e, int i, int slot, int n_rows, int h_row, int re
     a.slot = slot;
     a.n_rows = n_rows;
     a.entry = e->d_pfx + (size_t)i * e->pfx_entry_elems();
-    a.max_rows = e->pfx_rows;
+    a.max_rows = e->pfx.max_rows();
     const int H = e->m->cfg.hidden;
     a.state = e->d_pfx_state + (size_t)i * (H + H / 16);
     a.h = e->wt.h;
@@ -880,7 +774,7 @@ static int prefix_move(Engine* e, int i, int slot, int n_rows, int h_row, int re
     a.h_row = h_row;
     a.H = H;
     a.restore = restore;
-    if (i < 0 || i >= e->pfx_n || slot >= e->kv_t.n_slots || h_row >= e->wt.max_rows) return -1;
+    if (i < 0 || i >= e->pfx.size() || slot >= e->kv_t.n_slots || h_row >= e->wt.max_rows) return -1;
     return launch_prefix_move(e->s, a);
 }
 
@@ -891,23 +785,15 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
         if (e && !e->slot_mode) Q3_LOG("q3e_admit: the batch was not opened with q3e_open");
         return -1;
     }
-    std::vector<int> ids(slots, slots + n), seen(e->B, 0);
     std::vector<SlotParams> sp(n);
     for (int u = 0; u < n; u++) {
-        const int b = ids[u];
         const q3e_slot_params& p = params[u];
-        if (b < 0 || b >= e->B || seen[b]++) {
-            Q3_LOG("q3e_admit: slot %d is out of range or listed twice (batch of %d)", b, e->B);
-            return -1;
-        }
+        if (!check_slot_list("q3e_admit", u, slots, e->B)) return -1;
         if (p.max_frames <= 0 || p.max_frames > e->max_frames) {
             Q3_LOG("q3e_admit: utterance %d: a budget of %d frames is outside 1..%d", u, p.max_frames, e->max_frames);
             return -1;
         }
-        if (n_rows[u] <= 0 || n_rows[u] > e->prefill_rows || n_rows[u] + p.max_frames > e->n_ctx) {
-            Q3_LOG("q3e_admit: utterance %d: %d prefix rows + %d frames do not fit n_ctx=%d", u, n_rows[u], p.max_frames, e->n_ctx);
-            return -1;
-        }
+        if (!check_fit(e, "q3e_admit", u, n_rows[u], p.max_frames)) return -1;
         if (!(std::isfinite(p.temperature) && p.temperature >= 0.f) || !(std::isfinite(p.cp_temperature) && p.cp_temperature >= 0.f) ||
             !(p.top_p > 0.f && p.top_p <= 1.f)) {
             Q3_LOG("q3e_admit: utterance %d: temperatures must be finite and >= 0, top_p in (0, 1]", u);
@@ -929,77 +815,44 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
             sp[u].flags = 3;   // a text slot; EOS masked until the final push
         }
     }
-    static const int32_t zero = 0;
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    Q3_HIP(hipEventRecord(e->ev0, e->s), -1);
-    for (int u = 0; u < n; u++) {
-        if (clear_slot(e, ids[u], n_rows + u, sp[u].flags ? &zero : n_text + u)) return -1;   // a text slot's n_text comes with its final push
-        Q3_HIP(hipMemcpyAsync(e->d_slots + ids[u], &sp[u], sizeof(SlotParams), hipMemcpyHostToDevice, e->s), -1);
-        if (e->d_tavail) Q3_HIP(hipMemsetAsync(e->d_tavail + ids[u], 0, sizeof(int), e->s), -1);
-    }
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
-    // one prefill per utterance: the ragged prefill's tiles follow the rows of its pass, so sharing a pass with another
-    // request's utterance would change this one's sums
-    const int H = e->m->cfg.hidden;
-    size_t row_off = 0;
     std::vector<int32_t> hits(n, 0);
-    for (int u = 0; u < n; row_off += n_rows[u], u++) {
-        const uint64_t k0 = keys ? keys[2 * u] : 0, k1 = keys ? keys[2 * u + 1] : 0;
-        const bool keyed = k0 != 0 || k1 != 0;
-        int at = -1;   // the entry that holds the key
-        if (keyed && e->pfx_n > 0 && n_rows[u] <= e->pfx_rows)
-            for (int i = 0; i < e->pfx_n && at < 0; i++)
-                if (e->pfx[i].n_rows && e->pfx[i].k0 == k0 && e->pfx[i].k1 == k1) at = i;
-        if (at >= 0 && e->pfx[at].n_rows == n_rows[u]) {
-            // hit: the KV rows, and the last row's residual where a prefill of one utterance leaves it for the same final
-            // norm launch (the residual stream is scratch between two frame steps, as it is for a prefill)
-            if (prefix_move(e, at, ids[u], n_rows[u], 0, 1)) return -1;
-            Q3_HIP(hipMemsetAsync(e->d_lastrow + ids[u], 0, sizeof(int), e->s), -1);
-            if (prefill_final_norm(e, ids[u], 1, e->B)) return -1;
-            e->pfx[at].use = ++e->pfx_clock;
-            e->pfx_stat[0]++;
-            hits[u] = 1;
-            continue;
+    const int rc = timed_prefill(e, [&]() -> int {
+        for (int u = 0; u < n; u++) {   // (a text slot's n_text comes with its final push)
+            if (reset_rows(e, slots[u], 1, RowStart::fresh, n_rows + u, sp[u].flags ? nullptr : n_text + u)) return -1;
+            Q3_HIP(hipMemcpyAsync(e->d_slots + slots[u], &sp[u], sizeof(SlotParams), hipMemcpyHostToDevice, e->s), -1);
         }
-        if (prefill_ids(e, 1, &ids[u], prefix + row_off * H, n_rows + u, e->B)) return -1;
-        if (!keyed) continue;
-        if (e->pfx_n > 0 && n_rows[u] > e->pfx_rows) {
-            e->pfx_stat[4]++;
-            continue;
-        }
-        e->pfx_stat[1]++;
-        if (e->pfx_n <= 0) continue;
-        if (at < 0) {   // a free entry, else the least recently used one
-            for (int i = 0; i < e->pfx_n; i++) {
-                if (!e->pfx[i].n_rows) {
-                    at = i;
-                    break;
-                }
-                if (at < 0 || e->pfx[i].use < e->pfx[at].use) at = i;
+        Q3_HIP(hipStreamSynchronize(e->s), -1);
+        // one prefill per utterance: the ragged prefill's tiles follow the rows of its pass, so sharing a pass with another
+        // request's utterance would change this one's sums
+        const int H = e->m->cfg.hidden;
+        size_t row_off = 0;
+        for (int u = 0; u < n; row_off += n_rows[u], u++) {
+            const int b = slots[u];
+            const uint64_t k0 = keys ? keys[2 * u] : 0, k1 = keys ? keys[2 * u + 1] : 0;
+            const PrefixIndex::Lookup l = e->pfx.lookup(k0, k1, n_rows[u]);
+            if (l.what == PrefixIndex::HIT) {
+                // the KV rows, and the last row's residual where a prefill of one utterance leaves it for the same final
+                // norm launch (the residual stream is scratch between two frame steps, as it is for a prefill)
+                if (prefix_move(e, l.entry, b, n_rows[u], 0, 1)) return -1;
+                Q3_HIP(hipMemsetAsync(e->d_lastrow + b, 0, sizeof(int), e->s), -1);
+                if (prefill_final_norm(e, b, 1, e->B)) return -1;
+                e->pfx.hit(l);
+                hits[u] = 1;
+                continue;
             }
-            if (e->pfx[at].n_rows) e->pfx_stat[3]++;
+            if (prefill_ids(e, 1, &b, prefix + row_off * H, n_rows + u, e->B)) return -1;
+            const int at = e->pfx.miss(l);   // keyed, and it fits the pool: the entry to keep it in
+            if (at < 0) continue;
+            if (prefix_move(e, at, b, n_rows[u], n_rows[u] - 1, 0)) return -1;
+            e->pfx.store(at, k0, k1, n_rows[u]);
         }
-        e->pfx[at].n_rows = 0;   // (an entry whose store fails holds nothing)
-        if (prefix_move(e, at, ids[u], n_rows[u], n_rows[u] - 1, 0)) return -1;
-        e->pfx[at].k0 = k0;
-        e->pfx[at].k1 = k1;
-        e->pfx[at].n_rows = n_rows[u];
-        e->pfx[at].use = ++e->pfx_clock;
-        e->pfx_stat[2]++;
-    }
-    if (head_all_rows(e)) return -1;
-    Q3_HIP(hipEventRecord(e->ev1, e->s), -1);
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
-    hipEventElapsedTime(&e->last_prefill_ms, e->ev0, e->ev1);
+        return head_all_rows(e);
+    });
+    if (rc) return -1;
     for (int u = 0; u < n; u++) {
-        e->h_budget[ids[u]] = sp[u].max_frames;
-        e->h_age[ids[u]] = 0;
-        e->h_live[ids[u]] = 1;
-        e->h_sp[ids[u]] = sp[u];
-        e->h_trows[ids[u]] = 0;
-        e->h_text[ids[u]] = sp[u].flags ? 1 : 0;
-        e->h_tfinal[ids[u]] = 0;
-        e->h_held[ids[u]] = 0;
+        e->book.admit(slots[u], sp[u].max_frames, sp[u].flags != 0);
+        e->h_sp[slots[u]] = sp[u];
     }
     if (hit) memcpy(hit, hits.data(), sizeof(int32_t) * n);
     return 0;
@@ -1040,18 +893,16 @@ int q3e_prefix_cache(void* ee, int n_entries, int max_rows) {
     if (e->d_pfx_state) hipFree(e->d_pfx_state);
     e->d_pfx = pool;
     e->d_pfx_state = state;
-    e->pfx_n = n_entries;
-    e->pfx_rows = max_rows;
-    e->pfx.assign(n_entries, Engine::PfxEntry());
+    e->pfx.resize(n_entries, max_rows);
     return 0;
 }
 
 int q3e_prefix_stats(void* ee, int64_t* out) {
     Engine* e = (Engine*)ee;
     if (!e || !out) return -1;
-    for (int i = 0; i < 5; i++) out[i] = e->pfx_stat[i];
-    out[5] = 0;
-    for (const auto& p : e->pfx) out[5] += p.n_rows ? 1 : 0;
+    const PrefixIndex& p = e->pfx;
+    const int64_t stats[6] = {p.hits, p.misses, p.stores, p.evictions, p.too_long, p.used()};
+    memcpy(out, stats, sizeof(stats));
     return 0;
 }
 
@@ -1061,12 +912,11 @@ int q3e_text_reserve(void* ee, int max_rows) {
         if (e) Q3_LOG("q3e_text_reserve: %d rows are outside 0..max_frames=%d", max_rows, e->max_frames);
         return -1;
     }
-    if (e->slot_mode)
-        for (int b = 0; b < e->B; b++)
-            if (e->h_live[b] && e->h_text[b]) {
-                Q3_LOG("q3e_text_reserve: slot %d holds a live text utterance", b);
-                return -1;
-            }
+    const int busy = e->slot_mode ? e->book.first_live_text() : -1;
+    if (busy >= 0) {
+        Q3_LOG("q3e_text_reserve: slot %d holds a live text utterance", busy);
+        return -1;
+    }
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     if (max_rows == e->text_cap) return 0;
     for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointers
@@ -1098,16 +948,17 @@ int q3e_text_reserve(void* ee, int max_rows) {
 int q3e_push_text(void* ee, int slot, const float* rows, int n, int final, int n_text_total) {
     Engine* e = (Engine*)ee;
     if (!e || !e->slot_mode || !e->d_text || slot < 0 || slot >= e->B || n < 0 || (n > 0 && !rows)) return -1;
-    if (!e->h_text[slot] || !e->h_live[slot]) {
+    const int have = e->book[slot].text_rows;
+    if (!e->book.live_text(slot)) {
         Q3_LOG("q3e_push_text: slot %d holds no live text utterance", slot);
         return -1;
     }
-    if (e->h_tfinal[slot]) {
+    if (e->book[slot].text_final) {
         Q3_LOG("q3e_push_text: the text of slot %d has ended", slot);
         return -1;
     }
-    if (e->h_trows[slot] + n > e->text_cap) {
-        Q3_LOG("q3e_push_text: slot %d: %d + %d rows exceed the reservation of %d", slot, e->h_trows[slot], n, e->text_cap);
+    if (have + n > e->text_cap) {
+        Q3_LOG("q3e_push_text: slot %d: %d + %d rows exceed the reservation of %d", slot, have, n, e->text_cap);
         return -1;
     }
     if (final && n_text_total < 0) return -1;
@@ -1119,9 +970,9 @@ int q3e_push_text(void* ee, int slot, const float* rows, int n, int final, int n
         }
     // the rows first, then the counter that makes them visible; q3e_run has synchronised, so no frame is in flight
     if (n > 0)
-        Q3_HIP(hipMemcpyAsync(e->d_text + ((size_t)slot * e->text_cap + e->h_trows[slot]) * H, rows, sizeof(float) * (size_t)n * H,
+        Q3_HIP(hipMemcpyAsync(e->d_text + ((size_t)slot * e->text_cap + have) * H, rows, sizeof(float) * (size_t)n * H,
                               hipMemcpyHostToDevice, e->s), -1);
-    e->up_i[0] = e->h_trows[slot] + n;
+    e->up_i[0] = have + n;
     Q3_HIP(hipMemcpyAsync(e->d_tavail + slot, &e->up_i[0], sizeof(int), hipMemcpyHostToDevice, e->s), -1);
     SlotParams sp = e->h_sp[slot];
     if (final) {   // the reference's EOS rules from the next sampled frame on: mask lifted, n_text known
@@ -1131,11 +982,8 @@ int q3e_push_text(void* ee, int slot, const float* rows, int n, int final, int n
         Q3_HIP(hipMemcpyAsync(e->d_ntext + slot, &e->up_i[1], sizeof(int), hipMemcpyHostToDevice, e->s), -1);
     }
     Q3_HIP(hipStreamSynchronize(e->s), -1);   // the caller's rows (and the locals) are their own again on return
-    e->h_trows[slot] += n;
-    if (final) {
-        e->h_sp[slot] = sp;
-        e->h_tfinal[slot] = 1;
-    }
+    e->book.push(slot, n, final != 0);
+    if (final) e->h_sp[slot] = sp;
     return 0;
 }
 
@@ -1143,9 +991,8 @@ int q3e_text_state(void* ee, int32_t* rows, int32_t* starved) {
     Engine* e = (Engine*)ee;
     if (!e || !e->slot_mode || e->B <= 0) return -1;
     for (int b = 0; b < e->B; b++) {
-        const bool waits = e->h_live[b] && e->h_text[b] && !e->h_tfinal[b] && e->h_age[b] < e->h_budget[b];
-        if (rows) rows[b] = e->h_text[b] ? e->h_trows[b] : 0;
-        if (starved) starved[b] = waits && e->h_trows[b] <= e->h_age[b];
+        if (rows) rows[b] = e->book[b].text_rows;   // (only a text slot is pushed rows)
+        if (starved) starved[b] = e->book.starved(b);
     }
     return 0;
 }
@@ -1176,7 +1023,7 @@ int q3e_text_hold(void* ee, int on) {
 int q3e_text_held(void* ee, int64_t* held_steps) {
     Engine* e = (Engine*)ee;
     if (!e || !e->slot_mode || e->B <= 0 || !held_steps) return -1;
-    for (int b = 0; b < e->B; b++) held_steps[b] = e->h_held[b];
+    for (int b = 0; b < e->B; b++) held_steps[b] = e->book[b].held;
     return 0;
 }
 
@@ -1190,7 +1037,7 @@ int q3e_release(void* ee, int n, const int32_t* slots) {
         }
     for (int u = 0; u < n; u++) {
         Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->d_done + slots[u]), 1, 1, e->s), -1);
-        e->h_live[slots[u]] = 0;
+        e->book.release(slots[u]);
     }
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     return 0;

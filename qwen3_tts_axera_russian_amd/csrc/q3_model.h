@@ -122,6 +122,17 @@ struct GraphExec {
     hipGraph_t g = nullptr;
     hipGraphExec_t e = nullptr;
     void reset();
+    // Capture what body() (-> 0 ok) launches on s and instantiate it, in place of whatever was held; `who` names the caller
+    // in the log.  The caller has run the body eagerly once before (the kernels' attributes are set outside a capture).
+    template <class F>
+    int capture(hipStream_t s, hipStreamCaptureMode mode, const char* who, F&& body) {
+        reset();
+        Q3_HIP(hipStreamBeginCapture(s, mode), -1);
+        return end_capture(s, body(), who);
+    }
+
+private:
+    int end_capture(hipStream_t s, int body_rc, const char* who);
 };
 
 }  // namespace q3

@@ -506,4 +506,14 @@ void GraphExec::reset() {
     g = nullptr;
 }
 
+int GraphExec::end_capture(hipStream_t s, int body_rc, const char* who) {
+    const hipError_t er = hipStreamEndCapture(s, &g);
+    if (body_rc || er != hipSuccess) {
+        Q3_LOG("%s: graph capture failed", who);
+        return -1;
+    }
+    Q3_HIP(hipGraphInstantiate(&e, g, nullptr, nullptr, 0), -1);
+    return 0;
+}
+
 }  // namespace q3

@@ -179,17 +179,10 @@ int wrapper_decode_embd_slot(void* ctx, int slot, const float* embd, int n_token
         rm.pos = c->d_pos;
         if (!c->g1.e || c->g1_rows != 1) {
             // eager once (sets kernel attributes), then capture
-            if (forward_rows(c, 1, rm) || final_hidden(c, 0, 1)) return -1;
+            auto step = [&]() -> int { return forward_rows(c, 1, rm) || final_hidden(c, 0, 1); };
+            if (step()) return -1;
             Q3_HIP(hipStreamSynchronize(c->s), -1);
-            c->g1.reset();
-            Q3_HIP(hipStreamBeginCapture(c->s, hipStreamCaptureModeThreadLocal), -1);
-            int rc = forward_rows(c, 1, rm) || final_hidden(c, 0, 1);
-            hipError_t e = hipStreamEndCapture(c->s, &c->g1.g);
-            if (rc || e != hipSuccess) {
-                Q3_LOG("wrapper_decode_embd: graph capture failed");
-                return -1;
-            }
-            Q3_HIP(hipGraphInstantiate(&c->g1.e, c->g1.g, nullptr, nullptr, 0), -1);
+            if (c->g1.capture(c->s, hipStreamCaptureModeThreadLocal, "wrapper_decode_embd", step)) return -1;
             c->g1_rows = 1;
             // the eager pass above already produced this step's result
         } else {
