@@ -83,6 +83,16 @@ int enc_launch_conv_in(hipStream_t s, const float* x, int ldx, const EncOp& op, 
                        long long state_floats, const int* streams);
 // the split residual VQ over n_frames frames, frame g = b * T + t read from z [B][2 * dim][ld] -> codes [n_frames][nq]
 int enc_launch_rvq(hipStream_t s, const float* z, int ld, int T, int n_frames, const EncOp& op, int64_t* codes);
+// frames per workgroup of that launch: enc_rvq_kernel<16> from 2048 frames, enc_rvq_kernel<4> below.  A frame's ids do not
+// depend on the width (per frame, one fma chain over d in order).
+static inline int enc_rvq_tile(int n_frames) { return n_frames >= 2048 ? 16 : 4; }
+// the quantiser geometry enc_load admits (its input is the 2 * dim rows semantic | acoustic)
+static inline bool enc_rvq_geometry(int nq, int cb, int dim, int n_sem) {
+    return nq >= 1 && nq <= 32 && cb >= 1 && dim >= 4 && dim % 4 == 0 && dim <= 1024 && n_sem >= 1 && n_sem <= nq;
+}
+// the quantiser's device tables from the host codebook [nq][cb][dim] (finite; op.nq, op.cb and op.dim set): op.cbk the codebook,
+// op.cbt its transpose [nq][dim][cb], op.n2 [nq][cb] = (float) of the double sum of squares.  -> false: an allocation or a copy failed
+bool enc_rvq_tables(DeviceAllocs& mem, const float* codebook, EncOp& op);
 
 // ---- streaming encode: the column counts of every level from a stream's running total ----
 // Level l is the input of the l-th strided op (level 0: samples); cols[n_levels] are frames.  A strided op of stride s turns

@@ -223,8 +223,10 @@ __global__ void __launch_bounds__(256) enc_rvq_kernel(const float* __restrict__ 
 
 int enc_launch_rvq(hipStream_t s, const float* z, int ld, int T, int n_frames, const EncOp& op, int64_t* codes) {
     const int nf = n_frames;
-    const int ft = nf >= 2048 ? 16 : 4;
+    const int ft = enc_rvq_tile(nf);
     const size_t lds = ((size_t)ft * op.dim + 4 * ft) * 4 + (size_t)5 * ft * 4;
+    // (at most 66 112 B, 16 frames of the loader's largest dim 1024, of the CU's 160 KiB: the runtime launches it as it is,
+    // tests/test_gpu_enc_rvq.py runs that shape)
     if (ft == 16)
         hipLaunchKernelGGL(enc_rvq_kernel<16>, dim3((unsigned)((nf + 15) / 16)), dim3(256), lds, s, z, ld, T, nf, op.cbk, op.cbt, op.n2,
                            op.nq, op.cb, op.dim, op.n_sem, codes);
@@ -235,10 +237,30 @@ int enc_launch_rvq(hipStream_t s, const float* z, int ld, int T, int n_frames, c
     return 0;
 }
 
-static float* enc_up(Enc* e, const float* h, size_t n) {
+static float* enc_up(DeviceAllocs& mem, const float* h, size_t n) {
     float* d = nullptr;
-    if (!e->mem.alloc(&d, n * 4) || hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    if (!mem.alloc(&d, n * 4) || hipMemcpy(d, h, n * 4, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
     return d;
+}
+static float* enc_up(Enc* e, const float* h, size_t n) { return enc_up(e->mem, h, n); }
+
+bool enc_rvq_tables(DeviceAllocs& mem, const float* cbk, EncOp& op) {
+    const size_t ne = (size_t)op.nq * op.cb * op.dim;
+    std::vector<float> t(ne), n2((size_t)op.nq * op.cb);
+    for (int q = 0; q < op.nq; q++)
+        for (int j = 0; j < op.cb; j++) {
+            double s = 0.0;
+            for (int d = 0; d < op.dim; d++) {
+                const float v = cbk[((size_t)q * op.cb + j) * op.dim + d];
+                t[((size_t)q * op.dim + d) * op.cb + j] = v;
+                s += (double)v * v;
+            }
+            n2[(size_t)q * op.cb + j] = (float)s;
+        }
+    op.cbk = enc_up(mem, cbk, ne);
+    op.cbt = enc_up(mem, t.data(), ne);
+    op.n2 = enc_up(mem, n2.data(), n2.size());
+    return op.cbk && op.cbt && op.n2;
 }
 
 static void enc_destroy(Enc* e) {
@@ -482,8 +504,7 @@ void* enc_load(const char* weights, int max_batch, int max_samples) {
             op.cb = r[3];
             op.dim = r[4];
             op.n_sem = r[6];
-            if (op.cin != C || op.cin != 2 * op.dim || op.nq < 1 || op.nq > 32 || op.cb < 1 || op.dim < 4 || op.dim % 4 ||
-                op.dim > 1024 || op.n_sem < 1 || op.n_sem > op.nq) {
+            if (op.cin != C || op.cin != 2 * op.dim || !enc_rvq_geometry(op.nq, op.cb, op.dim, op.n_sem)) {
                 fail("quantiser geometry (input = semantic | acoustic projections, dim % 4 == 0, 1 <= n_sem <= nq <= 32)");
                 break;
             }
@@ -493,21 +514,7 @@ void* enc_load(const char* weights, int max_batch, int max_samples) {
             for (size_t x = 0; x < ne && ok; x++)
                 if (!std::isfinite(cbk[x])) fail("non-finite codebook entry");
             if (!ok) break;
-            std::vector<float> t(ne), n2((size_t)op.nq * op.cb);
-            for (int q = 0; q < op.nq; q++)
-                for (int j = 0; j < op.cb; j++) {
-                    double s = 0.0;
-                    for (int d = 0; d < op.dim; d++) {
-                        const float v = cbk[((size_t)q * op.cb + j) * op.dim + d];
-                        t[((size_t)q * op.dim + d) * op.cb + j] = v;
-                        s += (double)v * v;
-                    }
-                    n2[(size_t)q * op.cb + j] = (float)s;
-                }
-            op.cbk = enc_up(e, cbk, ne);
-            op.cbt = enc_up(e, t.data(), ne);
-            op.n2 = enc_up(e, n2.data(), n2.size());
-            ok = op.cbk && op.cbt && op.n2;
+            ok = enc_rvq_tables(e->mem, cbk, op);
             e->nq = op.nq;
             done = true;
         } else {

@@ -860,3 +860,99 @@ extern "C" int q3t_enc_stream_plan(const int* ks, const int* strides, int n_leve
     enc_stream_plan(ks, strides, n_levels, before, n_new, finish != 0, n_in, before_cols, carry);
     return 0;
 }
+
+// ---- the encoder's own kernels (csrc/q3_enc.hip), one launch each ----
+extern "C" int q3t_enc_rvq_tile(int n_frames) { return enc_rvq_tile(n_frames); }
+
+// One enc_launch_rvq over the tables enc_load builds (enc_rvq_tables) from codebook [nq][cb][dim].  stream == 0, the clip
+// layout of enc_run: z [B][2 * dim][T] in, on the device rows of pitch enc_pitch(T) whose pad columns hold NaN, frame
+// g = b * T + t.  stream != 0, the layout of an EncStream push: z [B][2 * dim] (B frames), ld = T = 1.  -> codes [B * T][nq].
+// -2: a geometry enc_load refuses (or a non-finite codebook), before anything launches; -3: the launch wrote outside
+// codes [0, B * T * nq) (the device buffer is one 16-frame tile longer and filled with a sentinel); -1: a HIP error.
+extern "C" int q3t_enc_rvq_case(const float* codebook, int nq, int cb, int dim, int n_sem, int stream, int B, int T, const float* z,
+                                int64_t* codes) {
+    constexpr int64_t GUARD = 0x5a5a5a5a5a5a5a5aLL;
+    if (!codebook || !z || !codes || !enc_rvq_geometry(nq, cb, dim, n_sem)) return -2;
+    if (B < 1 || T < 1 || (stream && T != 1) || (long long)B * T > (1 << 24)) return -2;
+    const size_t ne = (size_t)nq * cb * dim;
+    for (size_t i = 0; i < ne; i++)
+        if (!std::isfinite(codebook[i])) return -2;
+    const int n_frames = B * T, ld = stream ? 1 : (int)enc_pitch(T);
+    const size_t rows = (size_t)B * 2 * dim;
+    std::vector<float> hz(rows * ld, std::nanf(""));
+    for (size_t r = 0; r < rows; r++) memcpy(hz.data() + r * ld, z + r * T, (size_t)T * 4);
+    std::vector<int64_t> hc((size_t)(n_frames + 16) * nq, GUARD);
+    DeviceAllocs mem;
+    EncOp op;
+    op.op = EOP_RVQ;
+    op.cin = 2 * dim;
+    op.nq = nq;
+    op.cb = cb;
+    op.dim = dim;
+    op.n_sem = n_sem;
+    if (!enc_rvq_tables(mem, codebook, op)) return -1;
+    DBuf dz, dc;
+    if (!dz.up(hz.data(), hz.size() * 4) || !dc.up(hc.data(), hc.size() * 8)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (enc_launch_rvq(nullptr, (const float*)dz.p, ld, T, n_frames, op, (int64_t*)dc.p)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    Q3_HIP(hipMemcpy(hc.data(), dc.p, hc.size() * 8, hipMemcpyDeviceToHost), -1);
+    memcpy(codes, hc.data(), (size_t)n_frames * nq * 8);
+    for (size_t i = (size_t)n_frames * nq; i < hc.size(); i++)
+        if (hc[i] != GUARD) return -3;
+    return 0;
+}
+
+// One enc_launch_conv_in: x [B][n] (device rows of pitch enc_pitch(n), NaN in the pad), w [cout][k], bias [cout] or null
+// -> y [B][cout][n].  hist == null: whole clips.  Else entry b continues stream streams[b] (distinct, < max_streams) of
+// hist [max_streams][k - 1], which comes back as the call left it.  -2: arguments the encoder never passes; -3: a pad column
+// of y or a word behind the history block was written; -1: a HIP error.
+extern "C" int q3t_enc_conv_in_case(const float* x, int B, int n, const float* w, const float* bias, int cout, int k, float* hist,
+                                    int max_streams, const int* streams, float* y) {
+    constexpr uint32_t GUARD = 0x7fc5a5a5u;   // a NaN pattern the kernel never produces
+    if (!x || !w || !y || B < 1 || n < 1 || cout < 1 || k < 1 || k > ENC_IN_MAXK) return -2;
+    if ((hist != nullptr) != (streams != nullptr)) return -2;
+    const int H = k - 1;
+    if (hist) {
+        if (max_streams < B) return -2;
+        std::vector<char> seen((size_t)max_streams, 0);
+        for (int b = 0; b < B; b++)
+            if (streams[b] < 0 || streams[b] >= max_streams || seen[(size_t)streams[b]]++) return -2;
+    }
+    const int ld = (int)enc_pitch(n);
+    std::vector<float> hx((size_t)B * ld, std::nanf(""));
+    for (int b = 0; b < B; b++) memcpy(hx.data() + (size_t)b * ld, x + (size_t)b * n, (size_t)n * 4);
+    const size_t ny = (size_t)B * cout;
+    std::vector<uint32_t> hy(ny * ld, GUARD);
+    const size_t nh = hist ? (size_t)max_streams * H : 0;
+    std::vector<uint32_t> hh(nh + 32, GUARD);
+    if (nh) memcpy(hh.data(), hist, nh * 4);
+    DBuf dx, dw, db, dy, dh, ds;
+    if (!dx.up(hx.data(), hx.size() * 4) || !dw.up(w, (size_t)cout * k * 4) || !dy.up(hy.data(), hy.size() * 4) ||
+        !dh.up(hh.data(), hh.size() * 4))
+        return -1;
+    if (bias && !db.up(bias, (size_t)cout * 4)) return -1;
+    if (hist && !ds.up(streams, (size_t)B * 4)) return -1;
+    EncOp op;
+    op.op = EOP_CONV_IN;
+    op.cin = 1;
+    op.cout = cout;
+    op.k = k;
+    op.w = (float*)dw.p;
+    op.bias = bias ? (float*)db.p : nullptr;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (enc_launch_conv_in(nullptr, (const float*)dx.p, ld, op, (float*)dy.p, ld, n, B, hist ? (float*)dh.p : nullptr, H,
+                           hist ? (const int*)ds.p : nullptr))
+        return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    Q3_HIP(hipMemcpy(hy.data(), dy.p, hy.size() * 4, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(hh.data(), dh.p, hh.size() * 4, hipMemcpyDeviceToHost), -1);
+    int outside = 0;
+    for (size_t r = 0; r < ny; r++) {
+        memcpy(y + r * n, hy.data() + r * ld, (size_t)n * 4);
+        for (int l = n; l < ld; l++) outside += hy[r * ld + l] != GUARD;
+    }
+    if (nh) memcpy(hist, hh.data(), nh * 4);
+    for (size_t i = nh; i < hh.size(); i++) outside += hh[i] != GUARD;
+    return outside ? -3 : 0;
+}

@@ -235,6 +235,9 @@ def load_test():
     _sig(lib, "q3t_enc_stream_embeddings", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, i64p, ctypes.c_int64, i64p, f32p, i32p])
     i64s = ctypes.POINTER(ctypes.c_longlong)
     _sig(lib, "q3t_enc_stream_plan", c_int, [i32p, i32p, c_int, ctypes.c_longlong, ctypes.c_longlong, c_int, i64s, i64s, i64s])
+    _sig(lib, "q3t_enc_rvq_tile", c_int, [c_int])
+    _sig(lib, "q3t_enc_rvq_case", c_int, [f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, f32p, i64p])
+    _sig(lib, "q3t_enc_conv_in_case", c_int, [f32p, c_int, c_int, f32p, f32p, c_int, c_int, f32p, c_int, i32p, f32p])
     _test_lib = lib
     return lib
 

@@ -42,7 +42,8 @@ def test_test_hooks_are_not_in_the_product_library(lib):
     assert not [n for n in prod if "handoff" in n or "bench_chain" in n]
     hooks = exported(TEST_LIB_PATH)
     for n in ("q3t_linear", "q3t_linear_case", "q3t_last_linear_variant", "q3t_reset_linear_knobs", "q3t_talker_sample",
-              "q3t_talker_sample_case", "q3t_cp_sample_case", "q3t_bench_linear", "q3t_inspect_weights", "q3t_attn", "q3t_voc_attn"):
+              "q3t_talker_sample_case", "q3t_cp_sample_case", "q3t_bench_linear", "q3t_inspect_weights", "q3t_attn", "q3t_voc_attn",
+              "q3t_enc_rvq_tile", "q3t_enc_rvq_case", "q3t_enc_conv_in_case"):
         assert n in hooks
     assert {"q3_device_count", "q3_set_device"} <= prod
 

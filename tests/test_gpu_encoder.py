@@ -5,7 +5,9 @@ Golden cases (tests/golden/mimi_encode_golden.npz, transformers' MimiModel.encod
 near as the float64 nearest entry within a relative 1e-5 -- distances evaluated in float64 from the GPU's own embedding,
 the residual formed from the GPU's own earlier ids -- and the ids that differ from the fixture are counted (0 at these
 sizes).  Then: the default config on synthetic weights against tests/enc_ref.py, ragged batches bit for bit against
-clips alone, every error path, the frame count, the round trip through the vocoder, the exported symbols."""
+clips alone, every error path, the frame count, the round trip through the vocoder, the exported symbols.  Last, the
+headline invariant across the quantiser's two tile widths (enc_rvq_tile): a clip alone, in a batch and streamed, id for id."""
+import dataclasses
 import json
 import os
 import re
@@ -303,3 +305,54 @@ def test_cli_prompt_dir_decodes(lib, full_synth, tmp_path):
     assert (d / "ref_text.txt").read_text() == "тест"
     sr, back = wavfile.read(str(out))
     assert sr == 24000 and back.dtype == np.int16 and (codes.shape[0] - 1) * 1920 < back.size <= codes.shape[0] * 1920
+
+
+# ---- clip b gives the same ids alone, in a batch and in any split -- across the quantiser's two kernels ----
+@pytest.fixture(scope="module")
+def short_stride_synth(tmp_path_factory):
+    """the tiny table with short strides, 8 samples per frame: thousands of frames from a few thousand samples"""
+    ec = dataclasses.replace(W.tiny_enc_config(), ratios=(2, 2))
+    assert W.enc_hop(ec) == 8
+    path = str(tmp_path_factory.mktemp("encq") / "enc_tiny_hop8.q3w")
+    W.write_synthetic_enc(path, ec, seed=5)
+    return ec, path
+
+
+def test_batch_and_alone_across_the_tile_widths(lib, test_lib, short_stride_synth):
+    """8 ragged clips of about 300 frames: each alone is quantised by the 4-frame kernel, the batch (B * longest = 2488
+    frames) by the 16-frame one.  encode(batch)[b] == encode([clip b])[0], id for id."""
+    ec, path = short_stride_synth
+    lengths = [2400, 2393, 2401, 2312, 2488, 2250, 2399, 2456]
+    frames = [W.enc_frames(ec, n) for n in lengths]
+    assert all(test_lib.q3t_enc_rvq_tile(f) == 4 for f in frames)
+    assert test_lib.q3t_enc_rvq_tile(len(lengths) * max(frames)) == 16
+    enc = Encoder(path, max_batch=len(lengths), max_samples=max(lengths))
+    try:
+        clips = [C.seeded_clip(21, n) for n in lengths]
+        batch = enc.encode(clips)
+        for b, c in enumerate(clips):
+            alone = enc.encode([c])[0]
+            assert alone.shape == (frames[b], 16)
+            assert np.array_equal(batch[b], alone), f"clip {b}: {int((batch[b] != alone).sum())} ids differ inside the batch"
+        assert len({tuple(r) for r in np.concatenate(batch).tolist()}) > 500      # not degenerate
+    finally:
+        enc.close()
+
+
+def test_long_clip_and_its_stream_across_the_tile_widths(lib, test_lib, short_stride_synth):
+    """One clip of 2100 frames at once (the 16-frame kernel) against the same clip through EncoderStream in pushes of 500
+    frames (the 4-frame kernel), id for id."""
+    ec, path = short_stride_synth
+    n, push = 16795, 4000
+    assert W.enc_frames(ec, n) == 2100 and test_lib.q3t_enc_rvq_tile(2100) == 16
+    assert test_lib.q3t_enc_rvq_tile(W.enc_frames(ec, push)) == 4
+    enc = Encoder(path, max_batch=1, max_samples=n)
+    try:
+        clip = C.seeded_clip(22, n)
+        whole = enc.encode([clip])[0]
+        streamed = enc.encode_streaming(clip, push_samples=push)
+        assert whole.shape == streamed.shape == (2100, 16)
+        diff = np.argwhere(whole != streamed)
+        assert diff.size == 0, f"{len(diff)} ids differ between the clip at once and its stream, first (frame, group) {diff[0].tolist()}"
+    finally:
+        enc.close()
