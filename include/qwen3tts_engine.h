@@ -182,6 +182,42 @@ int q3e_admit_keyed(void* e, int n, const int32_t* slots, const float* prefix, c
                     const q3e_slot_params* params, const uint64_t* keys, int32_t* hit);
 int q3e_prefix_stats(void* e, int64_t* out /*[6]*/);
 
+/* Codec prompts of the per-slot admissions: an utterance that continues given audio (the ids qwen3tts_enc.h makes of a
+ * reference clip).  Not present in the reference.  What text the prefix holds beside the prompt is the caller's choice;
+ * parity with the real model's prompted mode on real weights is NOT pinned, the arithmetic is: tests grade every frame
+ * against the CPU oracle fed the same rows and the same history.
+ *
+ * q3e_admit_prompted: q3e_admit_keyed where utterance u may carry T = prompt_frames[u] frames of 16 codec ids
+ * (prompt_codes: [sum T][16], in the order of the utterances) that count as frames it has ALREADY emitted:
+ *   - rows: prompt frame i is talker row n_rows + i, = codec_embedding[P[i][0]] + sum over g = 0..14 of
+ *     cp_table[g][P[i][1 + g]] + tts_pad (what q3e_set_pad_embed last set), added in that order in f32: the feedback sum
+ *     of tts_client.py:199-208, built on the device by the frame loop's own code.  The utterance's pass prefills n_rows + T
+ *     rows, and the slot's KV rows and frame-0 state are, bit for bit, what q3e_admit leaves when given the n_rows + T rows
+ *     [prefix ; rows(P)] as a plain prefix;
+ *   - sampler state: the emitted-token ring holds P[i][0] for the last min(T, 32) frames and the utterance has T frames
+ *     behind it: the repetition window (the last 30), the EOS-boost progress (T + frames generated) / (3 * n_text) and the
+ *     forced EOS above 2.0 of llamacpp_talker_server.py:163-206 all see the prompt;
+ *   - generated frames: the codes array, q3e_get_done, q3e_get_codes and the budget count GENERATED frames only: row 0 of
+ *     the slot's column is its first generated frame, `max_frames` of q3e_slot_params is the number of generated frames,
+ *     and the draw key stays (stream, generated frame index, group), so the seed contract above holds unchanged;
+ *   - positions: the first frame step runs at position n_rows + T.
+ * Validation is q3e_admit's, before anything changes, with n_rows + T where it has n_rows (the rows one prefill pass
+ * takes, and n_rows + T + max_frames <= n_ctx), and: T >= 0, column 0 of every prompt frame in 0..2047 (an audio id),
+ * columns 1..15 inside the code predictor's vocabulary, no prompt on a text slot (`reserved` bit 0).  A failed call leaves
+ * the slots and the cache as they were.  prompt_frames == NULL, or T = 0 for an utterance: exactly q3e_admit_keyed.
+ *
+ * Prefix cache: an entry of a prompted utterance holds its n_rows + T rows and the last prompt row's residual state, and
+ * n_rows + T is the length the index compares (and compares with the pool's max_rows: a longer utterance is a plain
+ * admission, counted as too long).  On a hit the prefix rows are not read; the prompt codes always are, the ring is
+ * rebuilt from them.  The key contract stays the caller's: the digest must cover the prompt.
+ *
+ * The prompt costs one launch per prompted utterance on the engine's stream, outside the captured frame, which does not
+ * change: no recapture, no new stream, event or hardware queue.  0 ok / <0 error. */
+int q3e_admit_prompted(void* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+                       const q3e_slot_params* params, const uint64_t* keys, int32_t* hit,
+                       const int32_t* prompt_codes /* [sum T][16], utterance order */,
+                       const int32_t* prompt_frames /* [n], 0 = none */);
+
 /* Text streamed into a running utterance, row by row (per-slot mode only).
  *
  * Layout (a recollection of the model's streaming mode, which the reference does not implement -- it pre-computes the

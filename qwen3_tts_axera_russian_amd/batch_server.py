@@ -81,6 +81,20 @@ throughput the others do not get back.  A text-stream request is then admitted o
 or the end record), waiting in the queue like any queued request until then; a request whose slot has been held for
 --text_wait_ms with no byte from its client fails alone (-2, its slot is released), and the others see nothing of it.
 
+Codec prompts (`--concurrent` only): a request may carry "prompt_codes" -- one [T][16] list of codec ids shared by its
+utterances, or a list of one such list per utterance -- and every utterance then CONTINUES that audio: the frames count as
+frames it has already emitted (include/qwen3tts_engine.h, q3e_admit_prompted), and the reply holds the generated frames
+and their audio only.  "prompt_token_ids" / "prompt_text" (optional) is the text spoken in the prompt: it is put in front
+of each utterance's text ids, and the EOS heuristics count both.  `--voice NAME=DIR` (repeatable; DIR as
+encode_reference_audio --output_dir writes it: ref_codec_tokens.npy and, if there, ref_text.txt) names such a pair, and a
+request's "voice": "NAME" stands for the same two keys.  With "vocoder": "incremental" the prompt's frames are pushed into
+the utterance's stream first and their voc_incr_samples(T) samples dropped, so the audio continues the prompt seamlessly;
+the chunk walk (the default) decodes the generated frames on their own.  A prompt in any other mode, together with
+"text_stream", an unknown voice, malformed codes, or one that does not fit n_ctx is answered with -2 for that request alone,
+before any of it is queued.  Prompt text in front of the target text is a recollection of the model's in-context mode:
+parity with real weights is not pinned.  With `--prefix_cache` the key of a prompted utterance is of the kind b"prompt" and
+digests the ids and the prompt's codes.
+
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
 vocoder then launches one persistent workgroup per compute unit (voc_set_max_workgroups(-1)), which leaves the frame loop's
@@ -110,22 +124,28 @@ from .vocoder import Vocoder
 from .weights import ModelConfig, read_pack
 
 
-def prefix_key(kind, token_ids):
+def prefix_key(kind, token_ids, prompt_codes=None):
     """The prefix cache's key of an utterance: the first 16 bytes of a SHA-256 over the kind of prefix (b"full": the
-    dual-stream prefix of the whole text, b"stream": the streaming prefix) and the int32 token ids that determine its
-    rows -- for b"stream" the first token alone."""
+    dual-stream prefix of the whole text, b"stream": the streaming prefix, b"prompt": the dual-stream prefix followed by
+    the rows of a codec prompt) and the int32 token ids that determine its rows -- for b"stream" the first token alone,
+    for b"prompt" the ids (the prompt's text first), their number, and the prompt's [T][16] codes."""
     ids = np.asarray(token_ids, dtype="<i4").reshape(-1)
-    return hashlib.sha256(bytes(kind) + b"\0" + ids.tobytes()).digest()[:16]
+    if prompt_codes is None:
+        return hashlib.sha256(bytes(kind) + b"\0" + ids.tobytes()).digest()[:16]
+    codes = np.asarray(prompt_codes, dtype="<i4").reshape(-1, 16)
+    return hashlib.sha256(bytes(kind) + b"\0" + struct.pack("<i", len(ids)) + ids.tobytes() + codes.tobytes()).digest()[:16]
 
 
 class QueuedUtterance(tuple):
     """An utterance as _prepare queues it -- the tuple (request index, prefix, n_text, SlotParams[, TextFeed]) the scheduler
-    has always taken -- with the prefix cache's key of its prefix beside it."""
+    has always taken -- with the prefix cache's key of its prefix, and its codec prompt ([T][16] int32, or None), beside it."""
     prefix_key = None
+    prompt = None
 
-    def __new__(cls, fields, prefix_key=None):
+    def __new__(cls, fields, prefix_key=None, prompt=None):
         self = super().__new__(cls, fields)
         self.prefix_key = prefix_key
+        self.prompt = prompt
         return self
 
 
@@ -134,7 +154,7 @@ class BatchSynthesisServer:
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
                  cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=0,
-                 prefix_cache_rows=64):
+                 prefix_cache_rows=64, voices=None):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens = socket_path, max_batch, max_tokens
@@ -156,6 +176,9 @@ class BatchSynthesisServer:
         if prefix_cache and not concurrent:
             raise ValueError("--prefix_cache serves the per-slot admissions of the shared frame loop: it needs --concurrent")
         self.prefix_cache, self.prefix_cache_rows = int(prefix_cache), int(prefix_cache_rows)
+        if voices and not concurrent:
+            raise ValueError("--voice names codec prompts of the shared frame loop's admissions: it needs --concurrent")
+        self.voices = {name: load_voice(d) for name, d in dict(voices or {}).items()}   # name -> (codes [T][16], text or None)
         self.sched = None
         # utterances one request may queue (the server is single-threaded: an unbounded request holds it indefinitely)
         self.max_request = int(max_request) if max_request else 8 * max_batch
@@ -232,12 +255,23 @@ class BatchSynthesisServer:
             per_utt = [codes[:int(per[b]), b, :] for b in range(B)]
         return [np.ascontiguousarray(c, dtype=np.int32) for c in per_utt]
 
-    def vocode(self, cs, vocoder="walk", arithmetic="exact"):
+    def vocode(self, cs, vocoder="walk", arithmetic="exact", prompts=None):
         """The vocoder of a request: every utterance's chunk walk in ONE batched call -> list of (codes, pcm int16).
         vocoder="incremental": the carry-state decode per utterance, in the request's arithmetic -- the bits a streamed reply in
-        that mode carries."""
+        that mode carries.  prompts (one [T][16] array or None per utterance): the incremental decode runs over the prompt's
+        frames and the utterance's, and the prompt's voc_incr_samples(T) samples are dropped; the chunk walk decodes the
+        generated frames on their own."""
         if vocoder == "incremental":
-            return [(c, self.voc.synthesize_incremental(c, int16=True, arithmetic=arithmetic)) for c in cs]
+            out = []
+            for u, c in enumerate(cs):
+                pr = prompts[u] if prompts is not None else None
+                if pr is None or not len(pr):
+                    out.append((c, self.voc.synthesize_incremental(c, int16=True, arithmetic=arithmetic)))
+                    continue
+                both = np.concatenate([np.asarray(pr, np.int32).reshape(-1, 16), np.asarray(c, np.int32).reshape(-1, 16)])
+                pcm = self.voc.synthesize_incremental(both, int16=True, arithmetic=arithmetic)
+                out.append((c, pcm[self.voc.incremental_samples(len(pr)):]))
+            return out
         return list(zip(cs, self.voc.synthesize_batch(cs)))
 
     def synthesize(self, token_ids, max_tokens=None, vocoder="walk", arithmetic="exact"):
@@ -255,9 +289,18 @@ class BatchSynthesisServer:
         if arithmetic not in self._istreams:
             self._istreams[arithmetic] = self.voc.incremental(self.max_batch, arithmetic)
         istream = self._istreams[arithmetic]
+        ch = self.voc.chunk_tokens
+        drop = state.setdefault("drop", {})    # samples of a slot's prompt that are still to be dropped from what it hands out
         for b in resets:
             istream.reset(b)
-        ch, parts, j = self.voc.chunk_tokens, [[] for _ in entries], 0
+            drop.pop(b, None)
+            pr = state.get("prompts", {}).pop(b, None)
+            if pr is not None and len(pr):
+                # the prompt's frames first, in pieces of at most chunk_tokens frames; none of their samples goes out
+                drop[b] = self.voc.incremental_samples(len(pr))
+                for f in range(0, len(pr), ch):
+                    drop[b] -= len(istream.push([b], [pr[f:f + ch]], [False])[0])
+        parts, j = [[] for _ in entries], 0
         while entries and (j == 0 or any(len(e[2]) > j * ch for e in entries)):
             sel = [k for k, e in enumerate(entries) if j == 0 or len(e[2]) > j * ch]
             pcm = istream.push([entries[k][0] for k in sel], [entries[k][2][j * ch:(j + 1) * ch] for k in sel],
@@ -265,7 +308,13 @@ class BatchSynthesisServer:
             for k, a in zip(sel, pcm):
                 parts[k].append(a.copy())
             j += 1
-        return [np.concatenate(p) for p in parts]
+        out = [np.concatenate(p) for p in parts]
+        for k, e in enumerate(entries):
+            left = drop.get(e[0], 0)
+            if left > 0:
+                drop[e[0]] = left - min(left, len(out[k]))
+                out[k] = out[k][left:]
+        return out
 
     def _push(self, conn, state, resets, entries):
         """Worker side of a streamed request: start the refilled slots' streams, push every live slot's new frames to the
@@ -380,11 +429,54 @@ class BatchSynthesisServer:
         request_vocoder_arithmetic(msg)      # (checks "vocoder" too)
         base = request_slot_params(msg, self.defaults, self.max_tokens)
         if msg.get("text_stream"):
+            if request_has_prompt(msg):
+                raise ValueError('a codec prompt does not combine with "text_stream"')
             return [self._prepare_text_stream(msg, base)]
         ids = self._token_ids(msg)
+        if not request_has_prompt(msg):
+            prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames)
+            return [QueuedUtterance((i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i)),
+                                    prefix_key(b"full", ids[i])) for i in order]
+        # a codec prompt: its text (if any) in front of every utterance's, its frames behind every prefix
+        prompts, head = self._request_prompts(msg, len(ids))
+        ids = [head + u for u in ids]
         prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames)
+        for i in order:
+            rows = prefixes[i].shape[0] + len(prompts[i])
+            if rows + max_tokens > self.n_ctx or rows > max(self.max_batch, 2048):
+                raise ValueError("prefix + codec prompt + max_tokens exceed n_ctx (or the rows of one prefill pass)")
         return [QueuedUtterance((i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i)),
-                                prefix_key(b"full", ids[i])) for i in order]
+                                prefix_key(b"prompt", ids[i], prompts[i]) if len(prompts[i]) else prefix_key(b"full", ids[i]),
+                                prompts[i] if len(prompts[i]) else None) for i in order]
+
+    def _request_prompts(self, msg, n_utts):
+        """A request's codec prompt -> (one [T][16] int32 array per utterance, the prompt text's token ids): from
+        "prompt_codes" and "prompt_token_ids" / "prompt_text", or from the "voice" that names them; raises ValueError on
+        anything malformed."""
+        if msg.get("text_stream"):
+            raise ValueError('a codec prompt does not combine with "text_stream"')
+        codes, text, head = msg.get("prompt_codes"), msg.get("prompt_text"), msg.get("prompt_token_ids")
+        if msg.get("voice") is not None:
+            if codes is not None or text is not None or head is not None:
+                raise ValueError('"voice" stands for "prompt_codes" and the prompt text: give one or the other')
+            name = msg["voice"]
+            if not isinstance(name, str) or name not in self.voices:
+                raise ValueError(f"unknown voice {name!r}")
+            codes, text = self.voices[name]
+        if codes is None:
+            raise ValueError('a prompt text needs "prompt_codes" (or a "voice")')
+        if head is not None and text is not None:
+            raise ValueError('"prompt_token_ids" and "prompt_text" are the same thing: give one')
+        if head is not None:
+            if not isinstance(head, list) or any(isinstance(t, bool) or not isinstance(t, int) for t in head):
+                raise ValueError('"prompt_token_ids" is a list of integers')
+        elif text is not None:
+            if not isinstance(text, str):
+                raise ValueError('"prompt_text" is a string')
+            if self.tokenizer is None:
+                raise RuntimeError("no tokenizer configured (--tokenizer DIR) for the prompt's text")
+            head = self.tokenizer.encode(text, add_special_tokens=False)
+        return request_prompt_codes(codes, n_utts, self.cfg.cp_vocab), [int(t) for t in (head or [])]
 
     def _prepare_text_stream(self, msg, base):
         """A "text_stream" request -> its one utterance as (0, streaming prefix, 0, SlotParams of a text slot, TextFeed), a
@@ -420,10 +512,10 @@ class BatchSynthesisServer:
             return ""
         return f" (prefix cache: {self.sched.prefix_hits} hits, {self.sched.prefix_misses} misses so far)"
 
-    def _finish(self, conn, cs, t0, vocoder="walk", arithmetic="exact"):
+    def _finish(self, conn, cs, t0, vocoder="walk", arithmetic="exact", prompts=None):
         """Worker side of the pipelined mode: vocode, reply on the request's own connection, close it."""
         try:
-            res = self.vocode(cs, vocoder, arithmetic)
+            res = self.vocode(cs, vocoder, arithmetic, prompts)
             conn.sendall(pack_batch_reply(res))
             print(f"  {len(res)} utterances, {sum(len(c) for c, _ in res)} frames in {time.time() - t0:.3f}s{self._prefix_note()}")
         except Exception as e:
@@ -463,6 +555,8 @@ class BatchSynthesisServer:
                 vocoder, arithmetic = request_vocoder(msg), request_vocoder_arithmetic(msg)
                 if msg.get("text_stream"):
                     raise ValueError('"text_stream" needs a --concurrent server')
+                if request_has_prompt(msg):
+                    raise ValueError("a codec prompt needs a --concurrent server")
                 if msg.get("stream"):
                     # streamed reply: the worker writes every record and closes the connection
                     ids = self._token_ids(msg)
@@ -627,6 +721,11 @@ class _Request:
         self.state = {"failed": False, "n": self.n, "frames": 0}   # the push worker's view (BatchSynthesisServer._push)
         self.gone = False                       # the client went away or the request failed: its slots are released
         self.feed = next((it[4] for it in items if len(it) > 4), None)   # TextFeed of a "text_stream" request
+        self.prompts = None                     # codec prompts per request index (None: the request has none)
+        if any(getattr(it, "prompt", None) is not None for it in items):
+            self.prompts = [None] * self.n
+            for it in items:
+                self.prompts[it[0]] = getattr(it, "prompt", None)
         self.starved_since = None               # text_hold: since when its slot has been held (None: it is not)
 
 
@@ -659,7 +758,12 @@ class ConcurrentScheduler:
     prefix_cache (the engine was told eng.prefix_cache(n, rows) before this scheduler opens the batch): the keys of an
     admission -- each item's `prefix_key` attribute (16 bytes; an item without one is admitted uncached) -- go to
     eng.admit(..., keys=[...]) in slot order; prefix_hits / prefix_misses count the flags it returns.  Without it admit is
-    called as it always was, whatever the items carry."""
+    called as it always was, whatever the items carry.
+
+    Codec prompts: an item's `prompt` attribute ([T][16] int32; absent or None: no prompt) goes to eng.admit(...,
+    prompts=[...]) in slot order -- only when an utterance of the admission has one, so an engine without the argument
+    serves everything else.  A streamed request's push worker finds the prompt of a slot it resets in state["prompts"][slot];
+    an unstreamed request whose vocoder is not the chunk walk gets them as reply's sixth argument."""
 
     def __init__(self, eng, max_batch, max_queue, prepare, reply, push, close_stream, send_error, check_every=8,
                  send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=False):
@@ -886,18 +990,22 @@ class ConcurrentScheduler:
             if take:
                 slots = free[:len(take)]
                 args = (slots, [it[1] for _, it in take], [it[2] for _, it in take], [it[3] for _, it in take])
+                prompts = [getattr(it, "prompt", None) for _, it in take]
+                kw = {"prompts": prompts} if any(p is not None for p in prompts) else {}
                 if self.prefix_cache:
-                    hit = eng.admit(*args, keys=[getattr(it, "prefix_key", None) for _, it in take])
+                    hit = eng.admit(*args, keys=[getattr(it, "prefix_key", None) for _, it in take], **kw)
                     self.prefix_hits += int(np.count_nonzero(hit))
                     self.prefix_misses += len(take) - int(np.count_nonzero(hit))
                 else:
-                    eng.admit(*args)
-                for b, (req, it) in zip(slots, take):
+                    eng.admit(*args, **kw)
+                for b, (req, it), prompt in zip(slots, take, prompts):
                     owner[b] = (req, it[0])
                     pushed[b] = 0
                     last_held[b] = 0
                     if req.stream:
                         resets[id(req)].append(b)
+                        if prompt is not None and req.state.get("vocoder") == "incremental":
+                            req.state.setdefault("prompts", {})[b] = prompt   # (taken by the push that resets slot b)
             text_live = any(o is not None and o[0].feed is not None for o in owner)
             if text_live:
                 self._feed_text(owner)
@@ -952,8 +1060,11 @@ class ConcurrentScheduler:
                         self._pool.submit(self._close_stream, req.conn, req.state, req.t0)
                     elif req.state["vocoder"] == "walk":
                         self._pool.submit(self._reply, req.conn, req.codes, req.t0)
-                    else:      # (reply's documented form is (conn, codes, t0); another vocoder adds its mode and arithmetic)
+                    elif req.prompts is None:   # (reply's documented form is (conn, codes, t0); another vocoder adds its mode and arithmetic)
                         self._pool.submit(self._reply, req.conn, req.codes, req.t0, req.state["vocoder"], req.state["vocoder_arithmetic"])
+                    else:
+                        self._pool.submit(self._reply, req.conn, req.codes, req.t0, req.state["vocoder"], req.state["vocoder_arithmetic"],
+                                          req.prompts)
         # shutting down: whatever is still in flight or queued gets -2
         with self._cv:
             rest = {id(r): r for r, _ in self._queue}
@@ -995,6 +1106,55 @@ def request_vocoder_arithmetic(msg):
     return a
 
 
+PROMPT_KEYS = ("prompt_codes", "prompt_token_ids", "prompt_text", "voice")
+
+
+def request_has_prompt(msg):
+    """Whether a request carries a codec prompt, or any key that belongs to one."""
+    return any(msg.get(k) is not None for k in PROMPT_KEYS)
+
+
+def request_prompt_codes(codes, n_utts, cp_vocab=2048):
+    """A request's "prompt_codes" -> one [T][16] int32 array per utterance: one [T][16] list shared by the utterances, or a
+    list of n_utts such lists.  Column 0 holds audio ids (0..2047), the others ids of the code predictor's vocabulary;
+    raises ValueError on any other shape, type or value."""
+    def one(c):
+        if isinstance(c, np.ndarray):
+            c = c.tolist()
+        if not isinstance(c, list) or any(not isinstance(f, list) or len(f) != 16 for f in c):
+            raise ValueError("a codec prompt is a list of frames of 16 ids")
+        if any(isinstance(t, bool) or not isinstance(t, int) for f in c for t in f):
+            raise ValueError("codec prompt ids are integers")
+        a = np.asarray(c, np.int64).reshape(-1, 16)
+        if len(a) and (a.min() < 0 or a[:, 0].max() >= 2048 or a[:, 1:].max() >= cp_vocab):
+            raise ValueError(f"codec prompt ids lie in 0..2047 (column 0) and 0..{cp_vocab - 1} (the others)")
+        return a.astype(np.int32)
+    if isinstance(codes, np.ndarray):
+        codes = codes.tolist()
+    if not isinstance(codes, list):
+        raise ValueError('"prompt_codes" is a list')
+    shared = all(isinstance(f, list) and len(f) == 16 and not any(isinstance(t, list) for t in f) for f in codes)
+    if shared:                          # [T][16] (or an empty prompt)
+        a = one(codes)
+        return [a] * n_utts
+    if len(codes) != n_utts:
+        raise ValueError(f'"prompt_codes" holds {len(codes)} prompts for {n_utts} utterances')
+    return [one(c) for c in codes]
+
+
+def load_voice(prompt_dir):
+    """A directory as encode_reference_audio --output_dir writes it -> (codes as "prompt_codes" takes them, the text of
+    ref_text.txt or None)."""
+    codes = np.load(os.path.join(prompt_dir, "ref_codec_tokens.npy"))
+    if codes.ndim != 2 or codes.shape[1] != 16 or not np.issubdtype(codes.dtype, np.integer):
+        raise ValueError(f"{prompt_dir}: ref_codec_tokens.npy is not an integer array [T][16]")
+    text = None
+    if os.path.exists(os.path.join(prompt_dir, "ref_text.txt")):
+        with open(os.path.join(prompt_dir, "ref_text.txt")) as f:
+            text = f.read()
+    return codes.astype(np.int64).tolist(), text
+
+
 _PARAM_KEYS = ("temperature", "top_k", "top_p", "cp_temperature", "cp_top_k", "seed")   # request keys = SlotParams fields
 
 
@@ -1023,10 +1183,12 @@ def request_slot_params(msg, defaults, max_tokens_cap):
 
 def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False, temperature=None,
                        top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None,
-                       vocoder_arithmetic=None, text_stream=False) -> bytes:
+                       vocoder_arithmetic=None, text_stream=False, prompt_codes=None, prompt_token_ids=None, prompt_text=None,
+                       voice=None) -> bytes:
     """The request of the batched protocol; the sampling keys (honoured by --concurrent), the vocoder mode ("walk" /
     "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given.  text_stream: the
-    request carries only the first piece of its one utterance's text; the rest follows as text records."""
+    request carries only the first piece of its one utterance's text; the rest follows as text records.  prompt_codes ([T][16], or
+    one such per utterance), prompt_token_ids / prompt_text, voice: the codec prompt the utterances continue (--concurrent)."""
     import json
     msg = {"language": language}
     if stream:
@@ -1039,8 +1201,15 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
         msg["texts"] = list(texts)
     if max_tokens:
         msg["max_tokens"] = int(max_tokens)
+    if prompt_codes is not None:
+        prompt_codes = np.asarray(prompt_codes).tolist() if not isinstance(prompt_codes, list) else \
+            [np.asarray(c).tolist() if isinstance(c, np.ndarray) else c for c in prompt_codes]
+    if prompt_token_ids is not None:
+        prompt_token_ids = [int(t) for t in prompt_token_ids]
     for key, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("cp_temperature", cp_temperature),
-                   ("cp_top_k", cp_top_k), ("seed", seed), ("vocoder", vocoder), ("vocoder_arithmetic", vocoder_arithmetic)):
+                   ("cp_top_k", cp_top_k), ("seed", seed), ("vocoder", vocoder), ("vocoder_arithmetic", vocoder_arithmetic),
+                   ("prompt_codes", prompt_codes), ("prompt_token_ids", prompt_token_ids), ("prompt_text", prompt_text),
+                   ("voice", voice)):
         if v is not None:
             msg[key] = v
     raw = json.dumps(msg).encode()
@@ -1215,12 +1384,18 @@ def main():
                     help="--concurrent: entries of the device prefix cache (0 = off): an utterance whose prefix is cached is "
                          "admitted without a prefill, with the same reply")
     ap.add_argument("--prefix_cache_rows", type=int, default=64, help="--prefix_cache: prefix rows an entry can hold")
+    ap.add_argument("--voice", action="append", default=[], metavar="NAME=DIR",
+                    help="--concurrent: a codec prompt requests may name with \"voice\": \"NAME\"; DIR as "
+                         "encode_reference_audio --output_dir writes it (repeatable)")
     a = ap.parse_args()
+    if any("=" not in v or not v.split("=", 1)[0] for v in a.voice):
+        ap.error("--voice takes NAME=DIR")
     srv = BatchSynthesisServer(a.model, a.vocoder, a.socket, a.max_batch, a.n_ctx, a.max_tokens, a.temperature, a.top_k,
                                a.cp_temperature, a.tokenizer, a.seed, pipeline=a.pipeline, concurrent=a.concurrent,
                                max_queue=a.max_queue, top_p=a.top_p, cp_top_k=a.cp_top_k, check_every=a.check_every,
                                send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms, text_hold=a.text_hold,
-                               prefix_cache=a.prefix_cache, prefix_cache_rows=a.prefix_cache_rows)
+                               prefix_cache=a.prefix_cache, prefix_cache_rows=a.prefix_cache_rows,
+                               voices=dict(v.split("=", 1) for v in a.voice))
     try:
         srv.serve()
     finally:

@@ -26,6 +26,7 @@ struct Engine {
     // device state
     int *d_slot = nullptr, *d_pos = nullptr;       // prefill row maps [prefill_rows]
     int* d_tiles = nullptr;                        // prefill attention tiles, int[4] each (<= prefill_rows of them)
+    int* d_prompt = nullptr;                       // codec prompt of the utterance being admitted, [prefill_rows][16] (q3e_admit_prompted)
     int *d_iota = nullptr;                         // [max_batch]
     int *d_past = nullptr, *d_npast = nullptr, *d_ntext = nullptr, *d_done = nullptr, *d_nframes = nullptr;
     int *d_pos0 = nullptr, *d_posdec = nullptr, *d_lastrow = nullptr;
@@ -287,7 +288,7 @@ void q3e_free(void* ee) {
     work_free(e->wc);
     void* ps[] = {e->d_tiles, e->d_slot, e->d_pos,  e->d_iota,   e->d_past,    e->d_npast, e->d_ntext, e->d_done,
                   e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots,
-                  e->d_text, e->d_tavail, e->d_held, e->d_pfx, e->d_pfx_state};
+                  e->d_text, e->d_tavail, e->d_held, e->d_pfx, e->d_pfx_state, e->d_prompt};
     for (void* p : ps)
         if (p) hipFree(p);
     if (e->h_done) hipHostFree(e->h_done);
@@ -346,7 +347,7 @@ void* q3e_create(const char* weights, int max_batch, int n_ctx, int max_frames) 
     ok = ok && work_alloc(e->wc, c, 2 * ((max_batch + 15) / 16 * 16), c.cp_ffn, c.cp_vocab, e->s) == 0;   // two rows per utterance in the CP's first pass
     auto ialloc = [&](int** p, size_t n) { return hipMalloc((void**)p, sizeof(int) * n) == hipSuccess; };
     ok = ok && ialloc(&e->d_slot, e->prefill_rows) && ialloc(&e->d_pos, e->prefill_rows);
-    ok = ok && ialloc(&e->d_tiles, (size_t)4 * e->prefill_rows);
+    ok = ok && ialloc(&e->d_tiles, (size_t)4 * e->prefill_rows) && ialloc(&e->d_prompt, (size_t)16 * e->prefill_rows);
     ok = ok && ialloc(&e->d_iota, max_batch) && ialloc(&e->d_past, (size_t)max_batch * 32);
     ok = ok && ialloc(&e->d_npast, max_batch) && ialloc(&e->d_ntext, max_batch) && ialloc(&e->d_done, max_batch);
     ok = ok && ialloc(&e->d_nframes, max_batch) && ialloc(&e->d_pos0, max_batch) && ialloc(&e->d_posdec, max_batch);
@@ -437,10 +438,41 @@ static int prefill_final_norm(Engine* e, int row0, int R, int B_total) {
     return talker_final_norm(e, e->s, row0, R, e->d_lastrow, cp_seed_row0(e->wc, B_total, 0, B_total));
 }
 
+// The codec prompt in d_prompt (T frames) into slot `slot`: its sampler state, and with `rows` its T talker rows into rows
+// row0.. of the talker's residual stream, as launch_ssq_rows leaves uploaded rows (launch_prompt_rows)
+static int prompt_launch(Engine* e, int slot, int T, int row0, bool rows) {
+    const Model& m = *e->m;
+    PromptRowsArgs a;
+    a.codes = e->d_prompt;
+    a.T = T;
+    a.past = e->d_past + 32 * (size_t)slot;
+    a.n_past = e->d_npast + slot;
+    a.talker_emb = m.talker_emb;
+    a.talker_vocab = m.cfg.talker_vocab;
+    a.cp_tables = m.d_cp_emb_ptrs;
+    a.cp_vocab = m.cfg.cp_vocab;
+    a.n_groups = m.cfg.cp_groups;
+    a.pad_embed = e->d_pad;
+    if (rows) {
+        a.h = e->wt.h;
+        a.ssq = e->wt.ssq;
+        a.xh = e->wt.xh;
+        a.gamma = m.talker.L[0].in_ln;
+        a.row0 = row0;
+        a.max_rows = e->prefill_rows;
+        a.H = m.cfg.hidden;
+    }
+    if (slot < 0 || slot >= e->max_batch || T > e->prefill_rows) return -1;
+    return launch_prompt_rows(e->s, a);
+}
+
 // Ragged prefill of n utterances into the KV slots / output rows ids[0..n) (prefix rows concatenated in that order):
 // utterances are packed into passes of at most prefill_rows rows; every row carries its own (slot, position).  The
 // hidden of each utterance's last row lands in row ids[u] of the post-norm buffers, one group at a time.
-static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, const int32_t* n_rows, int B_total) {
+// n_prompt > 0 (n == 1 only): the last n_prompt of the utterance's n_rows[0] rows are not in `prefix`; they are built on
+// the device from the codec prompt in d_prompt, which also seeds the slot's sampler state.
+static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, const int32_t* n_rows, int B_total, int n_prompt = 0) {
+    if (n_prompt && (n != 1 || n_prompt >= n_rows[0])) return -1;
     const Model& m = *e->m;
     const int H = m.cfg.hidden;
     size_t row_off = 0;
@@ -468,7 +500,8 @@ static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, co
             }
             last[u] = r - 1;
         }
-        Q3_HIP(hipMemcpyAsync(e->wt.rows_in, prefix + row_off * H, sizeof(float) * (size_t)rows * H, hipMemcpyHostToDevice, e->s), -1);
+        const int up_rows = rows - n_prompt;   // rows that come from the host
+        Q3_HIP(hipMemcpyAsync(e->wt.rows_in, prefix + row_off * H, sizeof(float) * (size_t)up_rows * H, hipMemcpyHostToDevice, e->s), -1);
         Q3_HIP(hipMemcpyAsync(e->d_slot, slot.data(), sizeof(int) * rows, hipMemcpyHostToDevice, e->s), -1);
         Q3_HIP(hipMemcpyAsync(e->d_pos, pos.data(), sizeof(int) * rows, hipMemcpyHostToDevice, e->s), -1);
         Q3_HIP(hipMemcpyAsync(e->d_tiles, tiles.data(), sizeof(int) * tiles.size(), hipMemcpyHostToDevice, e->s), -1);
@@ -478,7 +511,8 @@ static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, co
             for (int u = u0; u < u1; u++)
                 Q3_HIP(hipMemcpyAsync(e->d_lastrow + ids[u], last.data() + u, sizeof(int), hipMemcpyHostToDevice, e->s), -1);
         }
-        if (launch_ssq_rows(e->s, e->wt.rows_in, e->wt.h, e->wt.ssq, rows, H, e->wt.xh, m.talker.L[0].in_ln)) return -1;
+        if (launch_ssq_rows(e->s, e->wt.rows_in, e->wt.h, e->wt.ssq, up_rows, H, e->wt.xh, m.talker.L[0].in_ln)) return -1;
+        if (n_prompt && prompt_launch(e, ids[u0], n_prompt, up_rows, true)) return -1;
         RowMap rm;
         rm.slot = e->d_slot;
         rm.pos = e->d_pos;
@@ -666,7 +700,8 @@ int q3e_get_codes(void* ee, int32_t* out, int max_out_frames, int32_t* n_frames_
     if (n_frames_per_utt) Q3_HIP(hipMemcpyAsync(h_np, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     if (n_codes) memcpy(out, h_codes, sizeof(int) * n_codes);
-    if (n_frames_per_utt) memcpy(n_frames_per_utt, h_np, sizeof(int) * e->B);
+    if (n_frames_per_utt)   // (a prompted slot's n_past began at its prompt's length)
+        for (int b = 0; b < e->B; b++) n_frames_per_utt[b] = e->slot_mode ? e->book.generated(b, h_np[b]) : h_np[b];
     return nf;
 }
 
@@ -678,6 +713,8 @@ int q3e_get_done(void* ee, int32_t* done, int32_t* frames) {
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     memcpy(done, e->h_done, sizeof(int) * e->B);
     std::vector<int> np(e->h_read, e->h_read + e->B);
+    if (e->slot_mode)   // frames generated: a prompted slot's n_past began at its prompt's length
+        for (int b = 0; b < e->B; b++) np[b] = e->book.generated(b, np[b]);
     // the device raises done[b] on the step AFTER the budget's last frame, a step q3e_run never takes: an utterance
     // that has emitted its whole budget has ended
     for (int b = 0; b < e->B; b++) {
@@ -778,28 +815,47 @@ static int prefix_move(Engine* e, int i, int slot, int n_rows, int h_row, int re
     return launch_prefix_move(e->s, a);
 }
 
-// q3e_admit (keys == NULL) and q3e_admit_keyed
+// q3e_admit (keys == NULL), q3e_admit_keyed (prompt_frames == NULL) and q3e_admit_prompted
 static int admit_slots(Engine* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
-                       const q3e_slot_params* params, const uint64_t* keys, int32_t* hit) {
+                       const q3e_slot_params* params, const uint64_t* keys, int32_t* hit, const int32_t* prompt_codes,
+                       const int32_t* prompt_frames) {
     if (!e || !e->slot_mode || n <= 0 || n > e->B || !slots || !prefix || !n_rows || !n_text || !params) {
         if (e && !e->slot_mode) Q3_LOG("q3e_admit: the batch was not opened with q3e_open");
         return -1;
     }
     std::vector<SlotParams> sp(n);
+    std::vector<int32_t> n_prompt(n, 0), n_tot(n);   // prompt frames, and the rows the utterance's pass prefills
+    size_t n_codes = 0;
     for (int u = 0; u < n; u++) {
         const q3e_slot_params& p = params[u];
+        if (prompt_frames) n_prompt[u] = prompt_frames[u];
+        if (n_prompt[u] < 0 || n_prompt[u] > e->prefill_rows || n_rows[u] <= 0 || (n_prompt[u] > 0 && !prompt_codes)) {
+            Q3_LOG("q3e_admit: utterance %d: %d prefix rows, %d prompt frames", u, n_rows[u], n_prompt[u]);
+            return -1;
+        }
+        n_tot[u] = n_rows[u] + n_prompt[u];
         if (!check_slot_list("q3e_admit", u, slots, e->B)) return -1;
         if (p.max_frames <= 0 || p.max_frames > e->max_frames) {
             Q3_LOG("q3e_admit: utterance %d: a budget of %d frames is outside 1..%d", u, p.max_frames, e->max_frames);
             return -1;
         }
-        if (!check_fit(e, "q3e_admit", u, n_rows[u], p.max_frames)) return -1;
+        if (!check_fit(e, "q3e_admit", u, n_tot[u], p.max_frames)) return -1;
+        for (size_t i = n_codes * 16; i < (n_codes + n_prompt[u]) * 16; i++) {
+            // (column 0 is an audio id of the talker, the sampler's audio_vocab; the others index the code predictor's tables)
+            const int32_t id = prompt_codes[i], vocab = e->m->cfg.cp_vocab;
+            if (id < 0 || id >= vocab) {
+                Q3_LOG("q3e_admit: utterance %d: prompt frame %zu holds id %d in column %zu (vocabulary %d)", u, i / 16 - n_codes,
+                       id, i % 16, vocab);
+                return -1;
+            }
+        }
+        n_codes += n_prompt[u];
         if (!(std::isfinite(p.temperature) && p.temperature >= 0.f) || !(std::isfinite(p.cp_temperature) && p.cp_temperature >= 0.f) ||
             !(p.top_p > 0.f && p.top_p <= 1.f)) {
             Q3_LOG("q3e_admit: utterance %d: temperatures must be finite and >= 0, top_p in (0, 1]", u);
             return -1;
         }
-        sp[u].max_frames = p.max_frames;
+        sp[u].max_frames = n_prompt[u] + p.max_frames;   // the device counts the prompt's frames with the emitted ones (n_past)
         sp[u].t_temp = p.temperature;
         sp[u].t_top_k = p.top_k;
         sp[u].t_top_p = p.top_p;
@@ -810,6 +866,10 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
         if (p.reserved & 1) {
             if (!e->d_text) {
                 Q3_LOG("q3e_admit: utterance %d is a text slot, but no text rows are reserved (q3e_text_reserve)", u);
+                return -1;
+            }
+            if (n_prompt[u]) {
+                Q3_LOG("q3e_admit: utterance %d: a text slot takes no codec prompt", u);
                 return -1;
             }
             sp[u].flags = 3;   // a text slot; EOS masked until the final push
@@ -826,32 +886,38 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
         // one prefill per utterance: the ragged prefill's tiles follow the rows of its pass, so sharing a pass with another
         // request's utterance would change this one's sums
         const int H = e->m->cfg.hidden;
-        size_t row_off = 0;
-        for (int u = 0; u < n; row_off += n_rows[u], u++) {
+        size_t row_off = 0, code_off = 0;
+        for (int u = 0; u < n; row_off += n_rows[u], code_off += n_prompt[u], u++) {
             const int b = slots[u];
             const uint64_t k0 = keys ? keys[2 * u] : 0, k1 = keys ? keys[2 * u + 1] : 0;
-            const PrefixIndex::Lookup l = e->pfx.lookup(k0, k1, n_rows[u]);
+            // a codec prompt's frames are rows of the utterance like the prefix's: one pass prefills them all, and an entry
+            // of the cache holds them all.  The codes are read on a hit too: the ring is rebuilt from them.
+            if (n_prompt[u])
+                Q3_HIP(hipMemcpyAsync(e->d_prompt, prompt_codes + code_off * 16, sizeof(int32_t) * 16 * (size_t)n_prompt[u],
+                                      hipMemcpyHostToDevice, e->s), -1);
+            const PrefixIndex::Lookup l = e->pfx.lookup(k0, k1, n_tot[u]);
             if (l.what == PrefixIndex::HIT) {
+                if (n_prompt[u] && prompt_launch(e, b, n_prompt[u], 0, false)) return -1;
                 // the KV rows, and the last row's residual where a prefill of one utterance leaves it for the same final
                 // norm launch (the residual stream is scratch between two frame steps, as it is for a prefill)
-                if (prefix_move(e, l.entry, b, n_rows[u], 0, 1)) return -1;
+                if (prefix_move(e, l.entry, b, n_tot[u], 0, 1)) return -1;
                 Q3_HIP(hipMemsetAsync(e->d_lastrow + b, 0, sizeof(int), e->s), -1);
                 if (prefill_final_norm(e, b, 1, e->B)) return -1;
                 e->pfx.hit(l);
                 hits[u] = 1;
                 continue;
             }
-            if (prefill_ids(e, 1, &b, prefix + row_off * H, n_rows + u, e->B)) return -1;
+            if (prefill_ids(e, 1, &b, prefix + row_off * H, &n_tot[u], e->B, n_prompt[u])) return -1;
             const int at = e->pfx.miss(l);   // keyed, and it fits the pool: the entry to keep it in
             if (at < 0) continue;
-            if (prefix_move(e, at, b, n_rows[u], n_rows[u] - 1, 0)) return -1;
-            e->pfx.store(at, k0, k1, n_rows[u]);
+            if (prefix_move(e, at, b, n_tot[u], n_tot[u] - 1, 0)) return -1;
+            e->pfx.store(at, k0, k1, n_tot[u]);
         }
         return head_all_rows(e);
     });
     if (rc) return -1;
     for (int u = 0; u < n; u++) {
-        e->book.admit(slots[u], sp[u].max_frames, sp[u].flags != 0);
+        e->book.admit(slots[u], params[u].max_frames, sp[u].flags != 0, n_prompt[u]);
         e->h_sp[slots[u]] = sp[u];
     }
     if (hit) memcpy(hit, hits.data(), sizeof(int32_t) * n);
@@ -860,12 +926,18 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
 
 int q3e_admit(void* ee, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
               const q3e_slot_params* params) {
-    return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, nullptr, nullptr);
+    return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, nullptr, nullptr, nullptr, nullptr);
 }
 
 int q3e_admit_keyed(void* ee, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
                     const q3e_slot_params* params, const uint64_t* keys, int32_t* hit) {
-    return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, keys, hit);
+    return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, keys, hit, nullptr, nullptr);
+}
+
+int q3e_admit_prompted(void* ee, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+                       const q3e_slot_params* params, const uint64_t* keys, int32_t* hit, const int32_t* prompt_codes,
+                       const int32_t* prompt_frames) {
+    return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, keys, hit, prompt_codes, prompt_frames);
 }
 
 int q3e_prefix_cache(void* ee, int n_entries, int max_rows) {

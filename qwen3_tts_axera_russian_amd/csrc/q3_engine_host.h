@@ -19,6 +19,8 @@ struct Slot {
     bool live = false;     // admitted and neither released nor known to have ended
     bool text = false;     // a text slot ...
     bool text_final = false;   // ... whose text has ended
+    int prompt = 0;        // codec-prompt frames it was admitted with (q3e_admit_prompted): the device's n_past counts them,
+                           // budget and age do not
 };
 
 class SlotBook {
@@ -27,7 +29,9 @@ public:
     int size() const { return (int)s_.size(); }
     const Slot& operator[](int b) const { return s_[b]; }
 
-    void admit(int b, int budget, bool is_text) { s_[b] = Slot{budget, 0, 0, 0, true, is_text, false}; }
+    void admit(int b, int budget, bool is_text, int prompt = 0) { s_[b] = Slot{budget, 0, 0, 0, true, is_text, false, prompt}; }
+    // frames slot b has generated, from the device's n_past (which starts at the prompt's length)
+    int generated(int b, int n_past) const { return n_past - s_[b].prompt; }
     void release(int b) { s_[b].live = false; }
     void mark_ended(int b) { s_[b].live = false; }   // q3e_get_done saw its EOS or its whole budget
     void push(int b, int n, bool final) {

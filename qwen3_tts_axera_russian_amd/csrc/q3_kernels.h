@@ -242,6 +242,32 @@ int launch_feedback(hipStream_t s, const int* codes16, int R, const float* talke
                     const float* const* cp_tables, int cp_vocab, int n_groups, const float* pad_embed,
                     float* h_out, float* ssq_out, int H, half_t* xh_out = nullptr, const float* gamma = nullptr);
 
+// Codec prompt of one admitted utterance (q3e_admit_prompted): T frames of 16 ids the utterance counts as already emitted.
+// One launch, one workgroup per prompt frame i:
+//   - with h != null, the frame's talker row -- the feedback sum of tts_client.py:199-208 (feedback_row, the frame loop's
+//     own) -- goes to row row0 + i of the fragment-ordered h / ssq / xh, with the sum-of-squares partials and the pre-scaled
+//     fp16 copy launch_ssq_rows gives a row of these values: the prefill reads it where it reads an uploaded row;
+//   - the sampler's state of the slot: column 0 of the last min(T, 32) frames into the emitted-token ring at i & 31, and
+//     n_past = T.
+// The caller has checked the ids (column 0 < talker_vocab, the others < cp_vocab, none negative) and row0 + T <= max_rows.
+struct PromptRowsArgs {
+    const int* codes = nullptr;   // device [T][16]
+    int T = 0;
+    int* past = nullptr;          // the slot's ring [32]
+    int* n_past = nullptr;        // the slot's counter
+    const float* talker_emb = nullptr;
+    int talker_vocab = 0;
+    const float* const* cp_tables = nullptr;   // device array [n_groups]
+    int cp_vocab = 0, n_groups = 15;
+    const float* pad_embed = nullptr;
+    float* h = nullptr;           // null: the rows are not built (a prefix-cache hit holds what a prefill makes of them)
+    float* ssq = nullptr;
+    half_t* xh = nullptr;
+    const float* gamma = nullptr; // input norm weight of the layer that consumes xh
+    int row0 = 0, max_rows = 0, H = 0;
+};
+int launch_prompt_rows(hipStream_t s, const PromptRowsArgs& a);
+
 // diagnostic timeline build: node numbering of the launches that follow (no-op otherwise)
 int tl_next_node();
 

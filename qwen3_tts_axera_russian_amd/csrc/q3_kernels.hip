@@ -2464,6 +2464,31 @@ int launch_feedback(hipStream_t s, const int* codes16, int R, const float* talke
     return 0;
 }
 
+// codec prompt (PromptRowsArgs): workgroup i owns prompt frame i.  The ring and the counter are written with plain vector
+// stores by lane 0; every workgroup writes other words, and the frame's sampler reads them in a later launch.
+__global__ void __launch_bounds__(256) prompt_rows_kernel(PromptRowsArgs a) {
+    const int i = blockIdx.x;
+    const int* codes = a.codes + (size_t)i * 16;
+    if (threadIdx.x == 0) {
+        if (i >= a.T - 32) a.past[i & 31] = codes[0];
+        if (i == a.T - 1) a.n_past[0] = a.T;
+    }
+    if (a.h)
+        feedback_row(codes, a.row0 + i, a.talker_emb, a.talker_vocab, a.cp_tables, a.cp_vocab, a.n_groups, a.pad_embed,
+                     a.h, a.ssq, a.H, -1, 0, nullptr, a.xh, a.gamma);
+}
+int launch_prompt_rows(hipStream_t s, const PromptRowsArgs& a) {
+    if (a.T <= 0) return 0;
+    if (!a.codes || !a.past || !a.n_past || !a.talker_emb || !a.cp_tables || a.n_groups <= 0 || a.n_groups > 15 ||
+        (a.h && (!a.ssq || a.row0 < 0 || a.row0 + a.T > a.max_rows || a.H <= 0 || a.H % 16))) {
+        Q3_LOG("launch_prompt_rows: bad arguments (%d frames at row %d of %d)", a.T, a.row0, a.max_rows);
+        return -1;
+    }
+    hipLaunchKernelGGL(prompt_rows_kernel, dim3(a.T), dim3(256), 0, s, a);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+
 // ---------------------------------------------------------------------------
 // test hook of the cross-lane helpers (q3t_xlane_case): one kernel applies a butterfly built on xlane_xor and the same
 // butterfly built on __shfl_xor to the same registers.  op 0: sum, 1: max, 2: the (value, index) arg-max exchange of

@@ -210,11 +210,15 @@ class FrameEngine:
             raise RuntimeError("q3e_prefix_stats failed")
         return dict(zip(("hits", "misses", "stores", "evictions", "too_long", "in_use"), (int(v) for v in out)))
 
-    def admit(self, slots, prefixes, n_text, params, keys=None):
+    def admit(self, slots, prefixes, n_text, params, keys=None, prompts=None):
         """Per-slot mode: put new utterances into `slots` (q3e_admit), each with its SlotParams (checked here first).
         keys (q3e_admit_keyed): one 16-byte key per utterance, or None for an utterance that is not cached -- a digest of
         everything that determines its prefix rows; an utterance whose key the prefix cache holds takes its KV rows and
-        frame-0 state from there instead of a prefill, bit for bit the same.  -> None, or with keys the hit flags (bool [n])."""
+        frame-0 state from there instead of a prefill, bit for bit the same.
+        prompts (q3e_admit_prompted): one [T][16] int array of codec ids per utterance, or None for an utterance without
+        one -- frames the utterance counts as already emitted: they are prefilled behind its prefix, the sampler's history
+        starts with them, and codes() / done() / max_frames count the generated frames only.  A key must digest the prompt.
+        -> None, or with keys the hit flags (bool [n])."""
         slots = np.ascontiguousarray(np.asarray(slots, np.int32))
         assert len(slots) == len(prefixes) == len(n_text) == len(params) and len(slots) > 0
         for p in params:
@@ -225,26 +229,47 @@ class FrameEngine:
         arr = (hiplib.SlotParamsC * len(params))(*[
             hiplib.SlotParamsC(int(p.max_frames), float(p.temperature), int(p.top_k), float(p.top_p), float(p.cp_temperature),
                                int(p.cp_top_k), int(p.seed), int(p.utt), 1 if p.text_stream else 0) for p in params])
-        if keys is None:
+        if keys is None and prompts is None:
             rc = self._lib.q3e_admit(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
                                      hiplib.iptr(nt), arr)
             if rc != 0:
                 raise RuntimeError(f"q3e_admit failed: {rc}")
             return None
-        assert len(keys) == len(slots)
-        kk = np.zeros((len(slots), 2), np.uint64)
-        for u, k in enumerate(keys):
-            if k is None:
-                continue
-            if not isinstance(k, (bytes, bytearray)) or len(k) != 16:
-                raise ValueError(f"a prefix key is 16 bytes or None (got {k!r})")
-            kk[u] = np.frombuffer(bytes(k), "<u8")
-        hit = np.zeros(len(slots), np.int32)
-        rc = self._lib.q3e_admit_keyed(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
-                                       hiplib.iptr(nt), arr, kk.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), hiplib.iptr(hit))
+        kk = hit = None
+        if keys is not None:
+            assert len(keys) == len(slots)
+            kk = np.zeros((len(slots), 2), np.uint64)
+            for u, k in enumerate(keys):
+                if k is None:
+                    continue
+                if not isinstance(k, (bytes, bytearray)) or len(k) != 16:
+                    raise ValueError(f"a prefix key is 16 bytes or None (got {k!r})")
+                kk[u] = np.frombuffer(bytes(k), "<u8")
+            hit = np.zeros(len(slots), np.int32)
+        kptr = kk.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if kk is not None else None
+        hptr = hiplib.iptr(hit) if hit is not None else None
+        if prompts is None:
+            rc = self._lib.q3e_admit_keyed(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
+                                           hiplib.iptr(nt), arr, kptr, hptr)
+            if rc != 0:
+                raise RuntimeError(f"q3e_admit_keyed failed: {rc}")
+            return hit.astype(bool)
+        assert len(prompts) == len(slots)
+        pcs = []
+        for pr in prompts:
+            pr = np.zeros((0, 16), np.int32) if pr is None else np.asarray(pr)
+            if pr.ndim != 2 or pr.shape[1] != 16 or not np.issubdtype(pr.dtype, np.integer):
+                raise ValueError(f"a codec prompt is an integer array [T][16] or None (got shape {pr.shape}, {pr.dtype})")
+            if pr.size and (pr.min() < -(1 << 31) or pr.max() >= 1 << 31):
+                raise ValueError("codec prompt ids must fit in an i32")
+            pcs.append(pr.astype(np.int32))
+        frames = np.array([len(pr) for pr in pcs], np.int32)
+        pcat = np.ascontiguousarray(np.concatenate(pcs, axis=0)) if frames.sum() else np.zeros((1, 16), np.int32)
+        rc = self._lib.q3e_admit_prompted(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
+                                          hiplib.iptr(nt), arr, kptr, hptr, hiplib.iptr(pcat), hiplib.iptr(frames))
         if rc != 0:
-            raise RuntimeError(f"q3e_admit_keyed failed: {rc}")
-        return hit.astype(bool)
+            raise RuntimeError(f"q3e_admit_prompted failed: {rc}")
+        return None if hit is None else hit.astype(bool)
 
     def reserve_text(self, max_rows):
         """Room for `max_rows` streamed text rows per slot (q3e_text_reserve; before open(); 0 releases it)."""

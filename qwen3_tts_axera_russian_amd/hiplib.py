@@ -97,6 +97,8 @@ def load(path: str | None = None):
     _sig(lib, "q3e_admit_keyed", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, ctypes.POINTER(SlotParamsC),
                                          ctypes.POINTER(ctypes.c_uint64), i32p])
     _sig(lib, "q3e_prefix_stats", c_int, [c_void_p, i64p])
+    _sig(lib, "q3e_admit_prompted", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, ctypes.POINTER(SlotParamsC),
+                                            ctypes.POINTER(ctypes.c_uint64), i32p, i32p, i32p])
     _sig(lib, "q3e_text_reserve", c_int, [c_void_p, c_int])
     _sig(lib, "q3e_push_text", c_int, [c_void_p, c_int, f32p, c_int, c_int, c_int])
     _sig(lib, "q3e_text_state", c_int, [c_void_p, i32p, i32p])
