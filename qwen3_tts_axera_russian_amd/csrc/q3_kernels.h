@@ -225,8 +225,11 @@ struct CpArgmaxArgs {
     const SlotParams* slots = nullptr;             // per-slot mode: temperature, top-k, draw key of row r (see TalkerSampleArgs)
     // (last, so that the fields above keep their kernarg offsets)
     // per-slot mode, text streamed into the utterance (q3e_text_reserve; null: none): the row added last to the feedback
-    // of frame f of row r is text_rows[r][f] while f < text_avail[r] (<= text_cap), else pad_embed.  Both arrays are
-    // written by the host between launches, never by a kernel of the same launch.
+    // of frame f of row r is text_rows[r][f] while f < text_avail[r] (<= text_cap), else pad_embed; f = n_frames[r] - 1 as the
+    // slot counts it, NOT clamped to frame_cap (a row that ended past the codes array still adds its own frame's text row),
+    // and a row without a frame yet (n_frames = 0) adds pad_embed.  Whether the slot is a text slot (flags) plays no part:
+    // the host keeps text_avail 0 for the others.  Both arrays are written by the host between launches, never by a kernel
+    // of the same launch.
     const float* text_rows = nullptr;   // f32 [R_total][text_cap][H]
     const int* text_avail = nullptr;    // [R_total]
     int text_cap = 0;

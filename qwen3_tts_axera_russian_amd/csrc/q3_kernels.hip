@@ -2198,6 +2198,12 @@ static size_t sample_lds_bytes_slots(int n) { return (size_t)sample_sort_len(n) 
 
 int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a) {
     if (a.R <= 0) return 0;
+    // held text slots are a per-slot feature: the kernel writes held[r] wherever text_avail is given
+    if ((a.text_avail && !a.held) || ((a.text_avail || a.held) && !a.slots)) {
+        Q3_LOG("talker_sample: text_avail / held need each other and per-slot mode (text_avail %p, held %p, slots %p)",
+               (const void*)a.text_avail, (const void*)a.held, (const void*)a.slots);
+        return -1;
+    }
     if (a.slots && a.V > SAMPLE_SORT_CAP) {
         Q3_LOG("talker_sample: a vocabulary of %d is beyond the per-slot sampler (sort cap %d)", a.V, SAMPLE_SORT_CAP);
         return -1;
@@ -2428,6 +2434,13 @@ int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a) {
     if (a.R <= 0) return 0;
     if (a.V % 4) {   // the arg-max reads each row as V / 4 float4: a tail would be dropped, and odd rows misaligned
         Q3_LOG("cp_argmax: a vocabulary of %d is not a multiple of 4", a.V);
+        return -1;
+    }
+    // text rows and held rows are read in per-slot mode only; text_rows is indexed with text_avail and text_cap
+    if (((a.text_rows || a.text_avail || a.held) && !a.slots) || (a.text_rows && (!a.text_avail || a.text_cap <= 0))) {
+        Q3_LOG("cp_argmax: text_rows / text_avail / held need per-slot mode, text_rows needs text_avail and text_cap > 0 "
+               "(text_rows %p, text_avail %p, text_cap %d, held %p, slots %p)", (const void*)a.text_rows,
+               (const void*)a.text_avail, a.text_cap, (const void*)a.held, (const void*)a.slots);
         return -1;
     }
     if (a.slots && a.V > SAMPLE_SORT_CAP) {

@@ -526,16 +526,18 @@ extern "C" int q3t_talker_sample(const float* logits, int V, const int* past, in
 // codes[frame_cap][R_total][16], forced (same layout, or null), seed_ptr[R_total] (or null), slots = SlotParams[R_total]
 // (or null; non-null selects the per-slot kernel).  Returns the launcher's own refusal (-1), -2 for arguments this hook
 // cannot lay out, -1000 on a HIP error.
-extern "C" int q3t_talker_sample_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
-                                      const int* n_text, int* done, int* n_frames, const int* pos0, int* pos, int* codes,
-                                      int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos,
-                                      int max_frames, float rep_penalty, float temperature, int top_k, float top_p,
-                                      unsigned long long seed, const unsigned long long* seed_ptr, const void* slots) {
+static int talker_sample_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
+                              const int* n_text, int* done, int* n_frames, const int* pos0, int* pos, int* codes,
+                              int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos, int max_frames,
+                              float rep_penalty, float temperature, int top_k, float top_p, unsigned long long seed,
+                              const unsigned long long* seed_ptr, const void* slots, const int* text_avail, int* held) {
     if (!logits || V <= 0 || R < 0 || row0 < 0 || row0 + R > R_total || frame_cap < 0 || eos < 0 || eos >= V) return -2;
     for (int r = row0; r < row0 + R; r++)
         if (n_frames[r] < 0 || n_past[r] < 0) return -2;
     const size_t rt = (size_t)R_total, nc = (size_t)frame_cap * rt * 16;
-    DBuf dl, dpast, dn, dnt, ddone, dcodes, dnf, dpos0, dpos, dforced, dseed, dslots;
+    DBuf dl, dpast, dn, dnt, ddone, dcodes, dnf, dpos0, dpos, dforced, dseed, dslots, dtav, dheld;
+    if (text_avail && !dtav.up(text_avail, rt * 4)) return -1000;
+    if (held && !dheld.up(held, rt * 4)) return -1000;
     if (!dl.up(logits, rt * V * 4) || !dpast.up(past, rt * 32 * 4) || !dn.up(n_past, rt * 4) || !dnt.up(n_text, rt * 4) ||
         !ddone.up(done, rt * 4) || !dcodes.up(codes, nc * 4) || !dnf.up(n_frames, rt * 4) || !dpos0.up(pos0, rt * 4) ||
         !dpos.up(pos, rt * 4))
@@ -570,6 +572,8 @@ extern "C" int q3t_talker_sample_case(const float* logits, int V, int R_total, i
     a.seed_ptr = seed_ptr ? (const unsigned long long*)dseed.p : nullptr;
     a.forced = forced ? (const int*)dforced.p : nullptr;
     a.slots = slots ? (const SlotParams*)dslots.p : nullptr;
+    a.text_avail = text_avail ? (const int*)dtav.p : nullptr;
+    a.held = held ? (int*)dheld.p : nullptr;
     if (const int rc = launch_talker_sample(nullptr, a)) return rc;
     Q3_HIP(hipDeviceSynchronize(), -1000);
     Q3_HIP(hipMemcpy(past, dpast.p, rt * 32 * 4, hipMemcpyDeviceToHost), -1000);
@@ -578,7 +582,29 @@ extern "C" int q3t_talker_sample_case(const float* logits, int V, int R_total, i
     Q3_HIP(hipMemcpy(n_frames, dnf.p, rt * 4, hipMemcpyDeviceToHost), -1000);
     Q3_HIP(hipMemcpy(pos, dpos.p, rt * 4, hipMemcpyDeviceToHost), -1000);
     Q3_HIP(hipMemcpy(codes, dcodes.p, nc * 4, hipMemcpyDeviceToHost), -1000);
+    if (held) Q3_HIP(hipMemcpy(held, dheld.p, rt * 4, hipMemcpyDeviceToHost), -1000);
     return 0;
+}
+extern "C" int q3t_talker_sample_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
+                                      const int* n_text, int* done, int* n_frames, const int* pos0, int* pos, int* codes,
+                                      int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos,
+                                      int max_frames, float rep_penalty, float temperature, int top_k, float top_p,
+                                      unsigned long long seed, const unsigned long long* seed_ptr, const void* slots) {
+    return talker_sample_case(logits, V, R_total, row0, R, past, n_past, n_text, done, n_frames, pos0, pos, codes, frame_cap,
+                              forced, audio_vocab, eos, ignore_eos, max_frames, rep_penalty, temperature, top_k, top_p, seed,
+                              seed_ptr, slots, nullptr, nullptr);
+}
+// q3t_talker_sample_case with held text slots (TalkerSampleArgs::text_avail / held): text_avail[R_total] in, held[R_total]
+// in and out, whole -- rows outside the launch come back as they went in.  Either may be null (the launcher's refusals).
+extern "C" int q3t_talker_sample_text_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
+                                           const int* n_text, int* done, int* n_frames, const int* pos0, int* pos, int* codes,
+                                           int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos,
+                                           int max_frames, float rep_penalty, float temperature, int top_k, float top_p,
+                                           unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
+                                           const int* text_avail, int* held) {
+    return talker_sample_case(logits, V, R_total, row0, R, past, n_past, n_text, done, n_frames, pos0, pos, codes, frame_cap,
+                              forced, audio_vocab, eos, ignore_eos, max_frames, rep_penalty, temperature, top_k, top_p, seed,
+                              seed_ptr, slots, text_avail, held);
 }
 
 // One launch_cp_argmax, state in and out on host arrays (layouts as in q3t_talker_sample_case).  epilogue 0: none;
@@ -587,13 +613,13 @@ extern "C" int q3t_talker_sample_case(const float* logits, int V, int R_total, i
 // h_out[R_total][H], ssq_out[R_total][H/16] and xh_out[R_total][H] (fp16 bits; with gamma[H], or both null) are row-major
 // in and out: the hook lays them out in fragment order on the device, so rows the launch leaves alone keep what the
 // caller put there.  Returns as q3t_talker_sample_case.
-extern "C" int q3t_cp_sample_case(const float* logits, int V, int R_total, int row0, int R, int group, int* codes,
-                                  const int* n_frames, int frame_cap, const int* forced, float temperature, int top_k,
-                                  unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
-                                  int epilogue, int H, const float* next_table, const float* next_qkv, int qkv_ld,
-                                  const float* gamma, const float* talker_emb, int talker_vocab, const float* cp_tables,
-                                  int n_groups, const float* pad, float* h_out, float* ssq_out, uint16_t* xh_out,
-                                  float* qkv_out) {
+static int cp_sample_case(const float* logits, int V, int R_total, int row0, int R, int group, int* codes,
+                          const int* n_frames, int frame_cap, const int* forced, float temperature, int top_k,
+                          unsigned long long seed, const unsigned long long* seed_ptr, const void* slots, int epilogue, int H,
+                          const float* next_table, const float* next_qkv, int qkv_ld, const float* gamma,
+                          const float* talker_emb, int talker_vocab, const float* cp_tables, int n_groups, const float* pad,
+                          float* h_out, float* ssq_out, uint16_t* xh_out, float* qkv_out, const float* text_rows,
+                          const int* text_avail, int text_cap, const int* held) {
     if (!logits || V <= 0 || R < 0 || row0 < 0 || row0 + R > R_total || frame_cap < 1 || group < 0 || group > 14 ||
         epilogue < 0 || epilogue > 2)
         return -2;
@@ -604,9 +630,17 @@ extern "C" int q3t_cp_sample_case(const float* logits, int V, int R_total, int r
         if (epilogue == 1 && (!next_table || (next_qkv && (!qkv_out || qkv_ld <= 0 || qkv_ld % 4)))) return -2;
         if (epilogue == 2 && (!talker_emb || talker_vocab <= 0 || !cp_tables || n_groups <= group || n_groups > 15)) return -2;
     }
+    // a text row is read at [r][n_frames - 1] while n_frames - 1 < text_avail[r]: inside [R_total][text_cap][H] only while
+    // text_avail <= text_cap
+    if (text_rows && text_avail && text_cap > 0)
+        for (int r = row0; r < row0 + R; r++)
+            if (text_avail[r] < 0 || text_avail[r] > text_cap) return -2;
     const size_t rt = (size_t)R_total, nc = (size_t)frame_cap * rt * 16;
     const int Rp = (R_total + 15) / 16 * 16;   // fragment order: blocks of 16 rows
-    DBuf dl, dcodes, dnf, dforced, dseed, dslots, dtab, dqkv, dgam, dtemb, dcpt, dcptp, dpad, dh, dssq, dxh, dqo;
+    DBuf dl, dcodes, dnf, dforced, dseed, dslots, dtab, dqkv, dgam, dtemb, dcpt, dcptp, dpad, dh, dssq, dxh, dqo, dtrows, dtav, dheld;
+    if (text_rows && !dtrows.up(text_rows, rt * (size_t)(text_cap > 0 ? text_cap : 1) * (H > 0 ? H : 1) * 4)) return -1000;
+    if (text_avail && !dtav.up(text_avail, rt * 4)) return -1000;
+    if (held && !dheld.up(held, rt * 4)) return -1000;
     if (!dl.up(logits, rt * V * 4) || !dcodes.up(codes, nc * 4) || !dnf.up(n_frames, rt * 4)) return -1000;
     if (forced && !dforced.up(forced, nc * 4)) return -1000;
     if (seed_ptr && !dseed.up(seed_ptr, rt * 8)) return -1000;
@@ -628,6 +662,10 @@ extern "C" int q3t_cp_sample_case(const float* logits, int V, int R_total, int r
     a.seed_ptr = seed_ptr ? (const unsigned long long*)dseed.p : nullptr;
     a.forced = forced ? (const int*)dforced.p : nullptr;
     a.slots = slots ? (const SlotParams*)dslots.p : nullptr;
+    a.text_rows = text_rows ? (const float*)dtrows.p : nullptr;
+    a.text_avail = text_avail ? (const int*)dtav.p : nullptr;
+    a.text_cap = text_cap;
+    a.held = held ? (const int*)dheld.p : nullptr;
     std::vector<float> hh;
     std::vector<uint16_t> hx;
     if (epilogue) {
@@ -684,6 +722,31 @@ extern "C" int q3t_cp_sample_case(const float* logits, int V, int R_total, int r
         if (a.qkv_out) Q3_HIP(hipMemcpy(qkv_out, dqo.p, rt * qkv_ld * 4, hipMemcpyDeviceToHost), -1000);
     }
     return 0;
+}
+extern "C" int q3t_cp_sample_case(const float* logits, int V, int R_total, int row0, int R, int group, int* codes,
+                                  const int* n_frames, int frame_cap, const int* forced, float temperature, int top_k,
+                                  unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
+                                  int epilogue, int H, const float* next_table, const float* next_qkv, int qkv_ld,
+                                  const float* gamma, const float* talker_emb, int talker_vocab, const float* cp_tables,
+                                  int n_groups, const float* pad, float* h_out, float* ssq_out, uint16_t* xh_out,
+                                  float* qkv_out) {
+    return cp_sample_case(logits, V, R_total, row0, R, group, codes, n_frames, frame_cap, forced, temperature, top_k, seed,
+                          seed_ptr, slots, epilogue, H, next_table, next_qkv, qkv_ld, gamma, talker_emb, talker_vocab, cp_tables,
+                          n_groups, pad, h_out, ssq_out, xh_out, qkv_out, nullptr, nullptr, 0, nullptr);
+}
+// q3t_cp_sample_case with streamed text and held rows (CpArgmaxArgs): text_rows[R_total][max(text_cap, 1)][H],
+// text_avail[R_total] (<= text_cap on the rows of the launch, else -2), held[R_total]; each may be null.
+extern "C" int q3t_cp_sample_text_case(const float* logits, int V, int R_total, int row0, int R, int group, int* codes,
+                                       const int* n_frames, int frame_cap, const int* forced, float temperature, int top_k,
+                                       unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
+                                       int epilogue, int H, const float* next_table, const float* next_qkv, int qkv_ld,
+                                       const float* gamma, const float* talker_emb, int talker_vocab, const float* cp_tables,
+                                       int n_groups, const float* pad, float* h_out, float* ssq_out, uint16_t* xh_out,
+                                       float* qkv_out, const float* text_rows, const int* text_avail, int text_cap,
+                                       const int* held) {
+    return cp_sample_case(logits, V, R_total, row0, R, group, codes, n_frames, frame_cap, forced, temperature, top_k, seed,
+                          seed_ptr, slots, epilogue, H, next_table, next_qkv, qkv_ld, gamma, talker_emb, talker_vocab, cp_tables,
+                          n_groups, pad, h_out, ssq_out, xh_out, qkv_out, text_rows, text_avail, text_cap, held);
 }
 
 // ---- launch-boundary microbenchmark: a dependent chain of n small kernels, captured as a graph ----
@@ -955,4 +1018,333 @@ extern "C" int q3t_enc_conv_in_case(const float* x, int B, int n, const float* w
     if (nh) memcpy(hist, hh.data(), nh * 4);
     for (size_t i = nh; i < hh.size(); i++) outside += hh[i] != GUARD;
     return outside ? -3 : 0;
+}
+
+// ---- the frame loop's row kernels, one launch each (tests/test_gpu_row_kernels.py) ----------------------------------
+namespace {
+constexpr uint32_t ROW_GUARD32 = 0x7fc5a5a5u;   // the NaN patterns of q3t_linear_case
+constexpr uint16_t ROW_GUARD16 = 0x7d5au;
+
+// What a producer of residual rows writes -- h (f32, fragment order or row-major), ssq partials [row][H/16], xh (fp16,
+// fragment order) -- each over its 16-row-padded extent and filled with guards before the launch.
+struct RowOut {
+    int Rp = 0, H = 0, parts = 0;
+    bool frag = true;
+    std::vector<uint32_t> h, s;
+    std::vector<uint16_t> x;
+    DBuf dh, ds, dx;
+    bool init(int rows, int H_, bool with_h, bool with_s, bool with_x, bool frag_ = true) {
+        Rp = (rows + 15) / 16 * 16;
+        H = H_;
+        parts = H / 16;
+        frag = frag_;
+        if (with_h) h.assign((size_t)Rp * H, ROW_GUARD32);
+        if (with_s) s.assign((size_t)Rp * parts, ROW_GUARD32);
+        if (with_x) x.assign((size_t)Rp * H, ROW_GUARD16);
+        return (!with_h || dh.up(h.data(), h.size() * 4)) && (!with_s || ds.up(s.data(), s.size() * 4)) &&
+               (!with_x || dx.up(x.data(), x.size() * 2));
+    }
+    float* ph() { return h.empty() ? nullptr : (float*)dh.p; }
+    float* ps() { return s.empty() ? nullptr : (float*)ds.p; }
+    half_t* px() { return x.empty() ? nullptr : (half_t*)dx.p; }
+    size_t at(int r, int k) const { return frag ? frag_idx_host(r, k, H) : (size_t)r * H + k; }
+    // Rows own(r) go to the host arrays (row-major, rows of the caller's own count); -> the number of words of every other
+    // row that no longer hold their guard, or -1 on a HIP error.
+    template <class F>
+    int collect(F own, float* h_out, float* ssq_out, uint16_t* xh_out) {
+        if (!h.empty() && hipMemcpy(h.data(), dh.p, h.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (!s.empty() && hipMemcpy(s.data(), ds.p, s.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        if (!x.empty() && hipMemcpy(x.data(), dx.p, x.size() * 2, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        int outside = 0;
+        for (int r = 0; r < Rp; r++) {
+            const bool mine = own(r);
+            for (int k = 0; k < H; k++) {
+                const size_t i = at(r, k);
+                if (mine) {
+                    if (!h.empty()) memcpy(&h_out[(size_t)r * H + k], &h[i], 4);
+                    if (!x.empty()) xh_out[(size_t)r * H + k] = x[frag_idx_host(r, k, H)];
+                } else {
+                    if (!h.empty() && h[i] != ROW_GUARD32) outside++;
+                    if (!x.empty() && x[frag_idx_host(r, k, H)] != ROW_GUARD16) outside++;
+                }
+            }
+            if (!s.empty())
+                for (int p = 0; p < parts; p++) {
+                    const uint32_t v = s[(size_t)r * parts + p];
+                    if (mine) memcpy(&ssq_out[(size_t)r * parts + p], &v, 4);
+                    else if (v != ROW_GUARD32) outside++;
+                }
+        }
+        return outside;
+    }
+};
+
+// cp_tables[n_tab][cp_vocab][H] (one contiguous host array) -> the device array of 16 table pointers the kernels index
+// with the group (entries beyond n_tab repeat the last table, so that no group index leaves the array)
+bool upload_tables(const float* cp_tables, int n_tab, int cp_vocab, int H, DBuf& dtab, DBuf& dptrs) {
+    const size_t tab = (size_t)cp_vocab * H;
+    if (!dtab.up(cp_tables, (size_t)n_tab * tab * 4)) return false;
+    const float* ptrs[16];
+    for (int g = 0; g < 16; g++) ptrs[g] = (const float*)dtab.p + (size_t)(g < n_tab ? g : n_tab - 1) * tab;
+    return dptrs.up(ptrs, sizeof(ptrs));
+}
+}  // namespace
+
+// One launch_final_norm over output rows row0 .. row0+R-1 of `rows`-row buffers.  h[rows][H] and ssq[rows][parts] are
+// row-major on the host (h is laid out in fragment order here; padding rows hold finite poison); the source row of output
+// row r is row_map[r] (row_map[rows], indexed by the output row) or, with row_map null, r + src_off.  want_f32 / want_f16 /
+// want_copy say which outputs the launch produces: out_f32[rows][H], out_f16[rows][H] (fp16 bits), and out_copy[rows][H]
+// with out_copy_ssq[rows][H/16] and -- with out_copy_gamma[H] -- out_copy_xh[rows][H], whose row r + out_copy_row_off is
+// the copy of output row r.  Every output is a guard pattern over its 16-row-padded extent before the launch; the rows the
+// launch owns come back (row-major), the others stay as the caller passed them.  -3: anything outside those rows changed;
+// -2: arguments no caller passes (a source or copy row outside the buffers, parts != H / 16, a wanted output without its
+// array, out_copy_xh without out_copy_gamma or the reverse); -1: the launcher's refusal or a HIP error.
+extern "C" int q3t_final_norm_case(const float* h, const float* ssq, int rows, int H, int parts, const float* gamma, float eps,
+                                   int R, int row0, const int* row_map, int src_off, int want_f32, int want_f16, int want_copy,
+                                   int out_copy_row_off, const float* out_copy_gamma, float* out_f32, uint16_t* out_f16,
+                                   float* out_copy, float* out_copy_ssq, uint16_t* out_copy_xh) {
+    if (!h || !ssq || !gamma || rows <= 0 || H <= 0 || H % 32 || parts != H / 16 || R <= 0 || row0 < 0 || row0 + R > rows) return -2;
+    if ((want_f32 && !out_f32) || (want_f16 && !out_f16) || (want_copy && (!out_copy || !out_copy_ssq))) return -2;
+    if ((out_copy_xh != nullptr) != (out_copy_gamma != nullptr) || (out_copy_xh && !want_copy)) return -2;
+    if (want_copy && (row0 + out_copy_row_off < 0 || row0 + R + out_copy_row_off > rows)) return -2;
+    for (int r = row0; r < row0 + R; r++) {
+        const int src = row_map ? row_map[r] : r + src_off;
+        if (src < 0 || src >= rows) return -2;
+    }
+    const int Rp = (rows + 15) / 16 * 16;
+    std::vector<float> hp((size_t)Rp * H, 3.0e4f), sp((size_t)Rp * parts, 1.0e9f);
+    for (int r = 0; r < rows; r++) {
+        for (int k = 0; k < H; k++) hp[frag_idx_host(r, k, H)] = h[(size_t)r * H + k];
+        memcpy(&sp[(size_t)r * parts], &ssq[(size_t)r * parts], (size_t)parts * 4);
+    }
+    DBuf dh, ds, dg, dmap, dcg;
+    if (!dh.up(hp.data(), hp.size() * 4) || !ds.up(sp.data(), sp.size() * 4) || !dg.up(gamma, (size_t)H * 4)) return -1;
+    if (row_map && !dmap.up(row_map, (size_t)rows * 4)) return -1;
+    if (out_copy_gamma && !dcg.up(out_copy_gamma, (size_t)H * 4)) return -1;
+    RowOut o32, o16, oc;
+    if (!o32.init(rows, H, want_f32, false, false, false) || !o16.init(rows, H, false, false, want_f16) ||
+        !oc.init(rows, H, want_copy, want_copy, want_copy && out_copy_xh))
+        return -1;
+    FinalNormArgs a;
+    a.h = (const float*)dh.p;
+    a.ssq = (const float*)ds.p;
+    a.ssq_parts = parts;
+    a.gamma = (const float*)dg.p;
+    a.eps = eps;
+    a.R = R;
+    a.H = H;
+    a.row0 = row0;
+    a.row_map = row_map ? (const int*)dmap.p : nullptr;
+    a.src_off = src_off;
+    a.out_f32 = o32.ph();
+    a.out_f16 = o16.px();
+    a.out_copy = oc.ph();
+    a.out_copy_ssq = oc.ps();
+    a.out_copy_row_off = out_copy_row_off;
+    a.out_copy_xh = oc.px();
+    a.out_copy_gamma = out_copy_gamma ? (const float*)dcg.p : nullptr;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (launch_final_norm(nullptr, a)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    auto own = [&](int r) { return r >= row0 && r < row0 + R; };
+    auto own_copy = [&](int r) { return r >= row0 + out_copy_row_off && r < row0 + R + out_copy_row_off; };
+    const int c32 = o32.collect(own, out_f32, nullptr, nullptr), c16 = o16.collect(own, nullptr, nullptr, out_f16);
+    const int cc = oc.collect(own_copy, out_copy, out_copy_ssq, out_copy_xh);
+    if (c32 < 0 || c16 < 0 || cc < 0) return -1;
+    return (c32 || c16 || cc) ? -3 : 0;
+}
+
+// One launch_gather_embed over rows row0 .. row0+R-1 of R_total.  n_frames null: the `tok` form, tok[R_total * tok_stride]
+// (row r reads tok[r * tok_stride]).  n_frames[R_total] given: the `codes` form, tok = codes[frame_cap][R_total][16], column
+// col of the row's current frame, forced (same layout) or null.  h[R_total][H], ssq[R_total][H/16] and, with gamma[H],
+// xh[R_total][H] come back row-major for the rows of the launch; guards and return codes as q3t_final_norm_case.
+extern "C" int q3t_gather_embed_case(const float* table, int V, int H, const int* tok, int tok_stride, const int* n_frames,
+                                     int frame_cap, int col, const int* forced, int R, int row0, int R_total,
+                                     const float* gamma, float* h, float* ssq, uint16_t* xh) {
+    if (!table || V <= 0 || H <= 0 || H % 32 || !tok || R <= 0 || row0 < 0 || row0 + R > R_total || !h || !ssq) return -2;
+    if ((xh != nullptr) != (gamma != nullptr)) return -2;
+    if (n_frames ? (frame_cap < 1 || col < 0 || col > 15) : (tok_stride < 1 || forced)) return -2;
+    const size_t nt = n_frames ? (size_t)frame_cap * R_total * 16 : (size_t)R_total * tok_stride;
+    DBuf dt, dtok, dnf, dfz, dg;
+    if (!dt.up(table, (size_t)V * H * 4) || !dtok.up(tok, nt * 4)) return -1;
+    if (n_frames && !dnf.up(n_frames, (size_t)R_total * 4)) return -1;
+    if (forced && !dfz.up(forced, nt * 4)) return -1;
+    if (gamma && !dg.up(gamma, (size_t)H * 4)) return -1;
+    RowOut o;
+    if (!o.init(R_total, H, true, true, xh != nullptr)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (launch_gather_embed(nullptr, (const float*)dt.p, V, H, (const int*)dtok.p, tok_stride, n_frames ? (const int*)dnf.p : nullptr,
+                            frame_cap, col, o.ph(), o.ps(), R, row0, R_total, forced ? (const int*)dfz.p : nullptr, o.px(),
+                            gamma ? (const float*)dg.p : nullptr))
+        return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    const int c = o.collect([&](int r) { return r >= row0 && r < row0 + R; }, h, ssq, xh);
+    return c < 0 ? -1 : c ? -3 : 0;
+}
+
+// One launch_feedback over R rows: codes16[R][16], talker_emb[talker_vocab][H], cp_tables[n_groups][cp_vocab][H] (one
+// contiguous array), pad[H] or null.  h[R][H], ssq[R][H/16] and, with gamma[H], xh[R][H] come back; guards (the rows that pad
+// R to 16) and return codes as q3t_final_norm_case.
+extern "C" int q3t_feedback_case(const int* codes16, int R, const float* talker_emb, int talker_vocab, const float* cp_tables,
+                                 int cp_vocab, int n_groups, const float* pad, int H, const float* gamma, float* h, float* ssq,
+                                 uint16_t* xh) {
+    if (!codes16 || R <= 0 || !talker_emb || talker_vocab <= 0 || !cp_tables || cp_vocab <= 0 || n_groups < 1 || n_groups > 15 ||
+        H <= 0 || H % 32 || !h || !ssq || (xh != nullptr) != (gamma != nullptr))
+        return -2;
+    DBuf dc, de, dtab, dptrs, dpad, dg;
+    if (!dc.up(codes16, (size_t)R * 16 * 4) || !de.up(talker_emb, (size_t)talker_vocab * H * 4) ||
+        !upload_tables(cp_tables, n_groups, cp_vocab, H, dtab, dptrs))
+        return -1;
+    if (pad && !dpad.up(pad, (size_t)H * 4)) return -1;
+    if (gamma && !dg.up(gamma, (size_t)H * 4)) return -1;
+    RowOut o;
+    if (!o.init(R, H, true, true, xh != nullptr)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (launch_feedback(nullptr, (const int*)dc.p, R, (const float*)de.p, talker_vocab, (const float* const*)dptrs.p, cp_vocab,
+                        n_groups, pad ? (const float*)dpad.p : nullptr, o.ph(), o.ps(), H, o.px(), gamma ? (const float*)dg.p : nullptr))
+        return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    const int c = o.collect([&](int r) { return r < R; }, h, ssq, xh);
+    return c < 0 ? -1 : c ? -3 : 0;
+}
+
+// One launch_prompt_rows: codes[T][16]; the slot's ring past[32] and counter n_past[1] in and out; tables as in
+// q3t_feedback_case (n_tab of them on the device; n_groups is what the launch is told).  Rows row0 .. row0+T-1 of buffers of
+// buf_rows rows (>= row0 + T; the launch is told max_rows): with_h != 0 builds them into h[buf_rows][H], ssq and -- with
+// gamma -- xh, which come back for those rows; with_h == 0 passes h = null (only the ring and the counter may change).
+// null_table: 1 passes talker_emb = null, 2 cp_tables = null (the launcher's refusals).  A refusal (-1) still brings the ring
+// and the counter back and checks every guard.  Guards and the other return codes as q3t_final_norm_case.
+extern "C" int q3t_prompt_rows_case(const int* codes, int T, int* past, int* n_past, const float* talker_emb, int talker_vocab,
+                                    const float* cp_tables, int n_tab, int cp_vocab, int n_groups, const float* pad, int H,
+                                    int row0, int max_rows, int buf_rows, int with_h, const float* gamma, float* h, float* ssq,
+                                    uint16_t* xh, int null_table) {
+    if (!codes || T <= 0 || !past || !n_past || !talker_emb || talker_vocab <= 0 || !cp_tables || n_tab < 1 || n_tab > 15 ||
+        cp_vocab <= 0 || H <= 0 || H % 32 || row0 < 0 || buf_rows < row0 + T)
+        return -2;
+    if (with_h ? (!h || !ssq || (xh != nullptr) != (gamma != nullptr)) : (xh || gamma)) return -2;
+    // ids as the caller of launch_prompt_rows has checked them
+    for (int i = 0; i < T; i++)
+        for (int g = 0; g < 16; g++)
+            if (codes[i * 16 + g] < 0 || codes[i * 16 + g] >= (g ? cp_vocab : talker_vocab)) return -2;
+    std::vector<int> cpad((size_t)T * 16 + 16, 0);   // (one frame of slack behind the ids)
+    memcpy(cpad.data(), codes, (size_t)T * 16 * 4);
+    DBuf dc, dpast, dn, de, dtab, dptrs, dpad, dg;
+    if (!dc.up(cpad.data(), cpad.size() * 4) || !dpast.up(past, 32 * 4) || !dn.up(n_past, 4) ||
+        !de.up(talker_emb, (size_t)talker_vocab * H * 4) || !upload_tables(cp_tables, n_tab, cp_vocab, H, dtab, dptrs))
+        return -1;
+    if (pad && !dpad.up(pad, (size_t)H * 4)) return -1;
+    if (gamma && !dg.up(gamma, (size_t)H * 4)) return -1;
+    RowOut o;
+    if (!o.init(buf_rows, H, true, true, xh != nullptr)) return -1;
+    PromptRowsArgs a;
+    a.codes = (const int*)dc.p;
+    a.T = T;
+    a.past = (int*)dpast.p;
+    a.n_past = (int*)dn.p;
+    a.talker_emb = null_table == 1 ? nullptr : (const float*)de.p;
+    a.talker_vocab = talker_vocab;
+    a.cp_tables = null_table == 2 ? nullptr : (const float* const*)dptrs.p;
+    a.cp_vocab = cp_vocab;
+    a.n_groups = n_groups;
+    a.pad_embed = pad ? (const float*)dpad.p : nullptr;
+    if (with_h) {
+        a.h = o.ph();
+        a.ssq = o.ps();
+        a.xh = o.px();
+        a.gamma = gamma ? (const float*)dg.p : nullptr;
+    }
+    a.row0 = row0;
+    a.max_rows = max_rows;
+    a.H = H;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    const int rc = launch_prompt_rows(nullptr, a);
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    Q3_HIP(hipMemcpy(past, dpast.p, 32 * 4, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(n_past, dn.p, 4, hipMemcpyDeviceToHost), -1);
+    const bool built = with_h && rc == 0;
+    const int c = o.collect([&](int r) { return built && r >= row0 && r < row0 + T; }, h, ssq, xh);
+    return c < 0 ? -1 : c ? -3 : rc;
+}
+
+// One launch_prefix_move on host arrays, everything in and out whole: caches kc / vc [n_layers][n_slots][n_kv][n_ctx][128]
+// (fp16 bits), pool[n_entries][n_layers][2][n_kv][max_rows][128], states[n_entries][H + H/16], h[h_rows][H] (row-major here,
+// fragment order on the device) and ssq[h_rows][H/16].  launch = {n_layers, n_kv, n_ctx, max_rows, H, slot, n_rows, h_row,
+// restore, null} is what the launch is told (null: bit i nulls kc, vc, entry, state, h, ssq): a set the launcher accepts must
+// lie inside the buffers (-2 otherwise); one it refuses (-1) still brings everything back.  -3: the guard rows behind kc, vc,
+// the pool or h changed.
+extern "C" int q3t_prefix_move_case(uint16_t* kc, uint16_t* vc, int n_layers, int n_slots, int n_kv, int n_ctx, uint16_t* pool,
+                                    int n_entries, int max_rows, float* states, float* h, float* ssq, int h_rows, int H, int entry,
+                                    const int* launch) {
+    if (!kc || !vc || !pool || !states || !h || !ssq || !launch || n_layers <= 0 || n_slots <= 0 || n_kv <= 0 || n_ctx <= 0 ||
+        n_entries <= 0 || max_rows <= 0 || h_rows <= 0 || H <= 0 || H % 32 || entry < 0 || entry >= n_entries)
+        return -2;
+    const int l_layers = launch[0], l_kv = launch[1], l_ctx = launch[2], l_max = launch[3], l_H = launch[4], slot = launch[5],
+              n_rows = launch[6], h_row = launch[7], restore = launch[8], nul = launch[9];
+    const bool refused = nul || l_layers <= 0 || l_kv <= 0 || slot < 0 || n_rows <= 0 || n_rows > l_ctx || n_rows > l_max || h_row < 0 ||
+                         l_H <= 0 || l_H % 32;
+    if (!refused && (l_layers > n_layers || l_kv != n_kv || l_ctx != n_ctx || l_max != max_rows || l_H != H || slot >= n_slots ||
+                     h_row >= h_rows))
+        return -2;
+    constexpr size_t TAIL = 16 * 128;   // guard rows behind every fp16 buffer
+    const size_t layer = (size_t)n_slots * n_kv * n_ctx * 128, nc = (size_t)n_layers * layer;
+    const size_t ent = (size_t)n_layers * 2 * n_kv * max_rows * 128, np = (size_t)n_entries * ent;
+    const int parts = H / 16, Rp = (h_rows + 15) / 16 * 16;
+    std::vector<uint16_t> hk(nc + TAIL, ROW_GUARD16), hv(nc + TAIL, ROW_GUARD16), hpool(np + TAIL, ROW_GUARD16);
+    memcpy(hk.data(), kc, nc * 2);
+    memcpy(hv.data(), vc, nc * 2);
+    memcpy(hpool.data(), pool, np * 2);
+    std::vector<uint32_t> hh((size_t)Rp * H, ROW_GUARD32), hs((size_t)Rp * parts, ROW_GUARD32);
+    for (int r = 0; r < h_rows; r++) {
+        for (int k = 0; k < H; k++) memcpy(&hh[frag_idx_host(r, k, H)], &h[(size_t)r * H + k], 4);
+        memcpy(&hs[(size_t)r * parts], &ssq[(size_t)r * parts], (size_t)parts * 4);
+    }
+    const size_t nst = (size_t)n_entries * (H + parts);
+    DBuf dk, dv, dp, dst, dh, ds;
+    if (!dk.up(hk.data(), hk.size() * 2) || !dv.up(hv.data(), hv.size() * 2) || !dp.up(hpool.data(), hpool.size() * 2) ||
+        !dst.up(states, nst * 4) || !dh.up(hh.data(), hh.size() * 4) || !ds.up(hs.data(), hs.size() * 4))
+        return -1;
+    PrefixMoveArgs a;
+    a.kc = (nul & 1) ? nullptr : (half_t*)dk.p;
+    a.vc = (nul & 2) ? nullptr : (half_t*)dv.p;
+    a.layer_stride = layer;
+    a.n_layers = l_layers;
+    a.n_kv = l_kv;
+    a.n_ctx = l_ctx;
+    a.slot = slot;
+    a.n_rows = n_rows;
+    a.entry = (nul & 4) ? nullptr : (half_t*)dp.p + (size_t)entry * ent;
+    a.max_rows = l_max;
+    a.state = (nul & 8) ? nullptr : (float*)dst.p + (size_t)entry * (H + parts);
+    a.h = (nul & 16) ? nullptr : (float*)dh.p;
+    a.ssq = (nul & 32) ? nullptr : (float*)ds.p;
+    a.h_row = h_row;
+    a.H = l_H;
+    a.restore = restore;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    const int rc = launch_prefix_move(nullptr, a);
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    Q3_HIP(hipMemcpy(hk.data(), dk.p, hk.size() * 2, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(hv.data(), dv.p, hv.size() * 2, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(hpool.data(), dp.p, hpool.size() * 2, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(states, dst.p, nst * 4, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(hh.data(), dh.p, hh.size() * 4, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(hs.data(), ds.p, hs.size() * 4, hipMemcpyDeviceToHost), -1);
+    memcpy(kc, hk.data(), nc * 2);
+    memcpy(vc, hv.data(), nc * 2);
+    memcpy(pool, hpool.data(), np * 2);
+    int outside = 0;
+    for (size_t i = 0; i < TAIL; i++) outside += (hk[nc + i] != ROW_GUARD16) + (hv[nc + i] != ROW_GUARD16) + (hpool[np + i] != ROW_GUARD16);
+    for (int r = 0; r < Rp; r++) {
+        for (int k = 0; k < H; k++) {
+            const uint32_t v = hh[frag_idx_host(r, k, H)];
+            if (r < h_rows) memcpy(&h[(size_t)r * H + k], &v, 4);
+            else outside += v != ROW_GUARD32;
+        }
+        for (int p = 0; p < parts; p++) {
+            const uint32_t v = hs[(size_t)r * parts + p];
+            if (r < h_rows) memcpy(&ssq[(size_t)r * parts + p], &v, 4);
+            else outside += v != ROW_GUARD32;
+        }
+    }
+    return outside ? -3 : rc;
 }

@@ -28,7 +28,7 @@ class KernelSlotParamsC(ctypes.Structure):
     """q3::SlotParams (csrc/q3_kernels.h): the entry the sampling kernels read per row; test hooks only."""
     _fields_ = [("max_frames", ctypes.c_int32), ("t_temp", ctypes.c_float), ("t_top_k", ctypes.c_int32),
                 ("t_top_p", ctypes.c_float), ("c_temp", ctypes.c_float), ("c_top_k", ctypes.c_int32),
-                ("seed", ctypes.c_uint64), ("no_row", ctypes.c_int32), ("pad_", ctypes.c_int32)]   # pad_ = SlotParams::flags
+                ("seed", ctypes.c_uint64), ("no_row", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
 def _sig(lib, name, restype, argtypes):
@@ -215,6 +215,21 @@ def load_test():
     _sig(lib, "q3t_cp_sample_case", c_int, [f32p, c_int, c_int, c_int, c_int, c_int, i32p, i32p, c_int, i32p, c_float, c_int,
                                             u64, u64p, c_void_p, c_int, c_int, f32p, f32p, c_int, f32p, f32p, c_int, f32p,
                                             c_int, f32p, f32p, f32p, ctypes.POINTER(ctypes.c_uint16), f32p])
+    talker_case = [f32p, c_int, c_int, c_int, c_int, i32p, i32p, i32p, i32p, i32p, i32p, i32p, i32p, c_int, i32p, c_int, c_int,
+                   c_int, c_int, c_float, c_float, c_int, c_float, u64, u64p, c_void_p]
+    cp_case = [f32p, c_int, c_int, c_int, c_int, c_int, i32p, i32p, c_int, i32p, c_float, c_int, u64, u64p, c_void_p, c_int,
+               c_int, f32p, f32p, c_int, f32p, f32p, c_int, f32p, c_int, f32p, f32p, f32p, u16p, f32p]
+    _sig(lib, "q3t_talker_sample_text_case", c_int, talker_case + [i32p, i32p])
+    _sig(lib, "q3t_cp_sample_text_case", c_int, cp_case + [f32p, i32p, c_int, i32p])
+    _sig(lib, "q3t_final_norm_case", c_int, [f32p, f32p, c_int, c_int, c_int, f32p, c_float, c_int, c_int, i32p, c_int, c_int,
+                                             c_int, c_int, c_int, f32p, f32p, u16p, f32p, f32p, u16p])
+    _sig(lib, "q3t_gather_embed_case", c_int, [f32p, c_int, c_int, i32p, c_int, i32p, c_int, c_int, i32p, c_int, c_int, c_int,
+                                               f32p, f32p, f32p, u16p])
+    _sig(lib, "q3t_feedback_case", c_int, [i32p, c_int, f32p, c_int, f32p, c_int, c_int, f32p, c_int, f32p, f32p, f32p, u16p])
+    _sig(lib, "q3t_prompt_rows_case", c_int, [i32p, c_int, i32p, i32p, f32p, c_int, f32p, c_int, c_int, c_int, f32p, c_int,
+                                              c_int, c_int, c_int, c_int, f32p, f32p, f32p, u16p, c_int])
+    _sig(lib, "q3t_prefix_move_case", c_int, [u16p, u16p, c_int, c_int, c_int, c_int, u16p, c_int, c_int, f32p, f32p, f32p,
+                                              c_int, c_int, c_int, i32p])
     _sig(lib, "q3t_attn", c_int, [c_int, c_int, c_int, f32p, f32p, f32p, c_float, f32p, f32p, c_int, i32p, i32p, c_int,
                                   c_int, c_int, c_int, u16p, u16p, c_int, c_int, i32p, c_int, c_int, c_int, c_int, u16p])
     _sig(lib, "q3t_voc_attn", c_int, [c_int, f32p, f32p, c_int, c_int, c_int, c_int, c_int, c_float])

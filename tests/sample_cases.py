@@ -73,9 +73,9 @@ def make_logits(family, rng, V, n_live, top_k, temperature, eos_finite=0):
     return l
 
 
-def slot(max_frames=0, t_temp=0.0, t_top_k=0, t_top_p=1.0, c_temp=0.0, c_top_k=0, seed=0, no_row=1):
+def slot(max_frames=0, t_temp=0.0, t_top_k=0, t_top_p=1.0, c_temp=0.0, c_top_k=0, seed=0, no_row=1, flags=0):
     return dict(max_frames=max_frames, t_temp=t_temp, t_top_k=t_top_k, t_top_p=t_top_p, c_temp=c_temp, c_top_k=c_top_k,
-                seed=seed, no_row=no_row)
+                seed=seed, no_row=no_row, flags=flags)
 
 
 def talker_state(rng, RT, V, audio_vocab, frame_cap=FRAME_CAP, sentinel=True):
@@ -182,7 +182,7 @@ def ambiguous_share(cases, sets_of):
         for i, fam in enumerate(c["families"]):
             r = c["cfg"]["row0"] + i
             p = SR._row_params(c["cfg"], r, "st" in c)
-            if SR.is_greedy(p["temperature"]):
+            if SR.is_greedy(p["temperature"]) or r not in sets:      # (a held row makes no draw)
                 continue
             a, n = out.get(fam, (0, 0))
             out[fam] = (a + (len(sets[r]) > 1), n + 1)
@@ -193,3 +193,134 @@ def share_report(name, shares):
     txt = ", ".join(f"{f} {a}/{n}" for f, (a, n) in shares.items())
     print(f"ambiguous share {name}: {txt}")
     return txt
+
+
+# ---- text slots: hold rule, EOS mask, held rows in the code predictor, text rows in the feedback ---------------------
+# One case per row, TEXT_R rows per launch between untouched rows; a list longer than a launch is cut into launches
+# (the last one filled up from the start of the list).  Even rows are greedy, odd rows stochastic.
+TEXT_RT, TEXT_ROW0, TEXT_R = 21, 3, 16
+TEXT_TALKER_VOCABS = (64, 2152)
+TEXT_CP_VOCABS = (64, 2048)
+HOLD_AVAIL, HOLD_BUDGET = 5, 12
+HOLD_N_PAST = (0, 1, HOLD_AVAIL - 1, HOLD_AVAIL, HOLD_AVAIL + 1, HOLD_BUDGET - 1, HOLD_BUDGET)
+TEXT_CAP = 6
+TEXT_AVAILS = (0, 1, 3, 6)
+HELD_SENTINEL = -7
+
+
+def hold_grid():
+    """(n_past, flags, done) of the hold rule's hand grid: every edge of 1 <= n_past, text_avail <= n_past < budget."""
+    return [(n, fl, done) for n in HOLD_N_PAST for fl in (0, 1, 2, 3) for done in (0, 1)]
+
+
+def _launches(specs, R=TEXT_R):
+    specs = list(specs)
+    specs += specs[:(-len(specs)) % R]
+    return [specs[i:i + R] for i in range(0, len(specs), R)]
+
+
+def _text_slots(rng, flags_of, talker):
+    """SlotParams of a launch: row TEXT_ROW0 + i greedy for even i, stochastic for odd i."""
+    slots = []
+    for r in range(TEXT_RT):
+        i = r - TEXT_ROW0
+        T = 0.8 if i % 2 else 0.0
+        slots.append(slot(max_frames=HOLD_BUDGET, t_temp=T if talker else 0.7, t_top_k=5, t_top_p=0.9, c_temp=0.7 if talker else T,
+                          c_top_k=5, seed=int(rng.integers(0, 2 ** 63)), no_row=r % 2, flags=flags_of(i) if 0 <= i < TEXT_R else 3))
+    return slots
+
+
+def _talker_text_case(V, tag, li, rows, text_avail):
+    """rows: TEXT_R tuples (n_past, flags, done, n_text).  EOS is on top of every row of the launch, far above the
+    rest: a row that decides ends, unless its EOS is masked."""
+    audio_vocab, eos = TALKER_VOCABS[V]
+    rng = rng_for(tag, V, li)
+    st = talker_state(rng, TEXT_RT, V, audio_vocab)
+    st["n_text"][:] = 0
+    st["held"] = np.full(TEXT_RT, HELD_SENTINEL, np.int32)
+    logits = (SPREAD * 0.8 * rng.standard_normal((TEXT_RT, V))).astype(np.float32)
+    for i, (n_past, _, done, n_text) in enumerate(rows):
+        r = TEXT_ROW0 + i
+        st["n_past"][r], st["done"][r], st["n_text"][r] = n_past, done, n_text
+        logits[r, eos] = 200.0
+    cfg = dict(V=V, audio_vocab=audio_vocab, eos=eos, rep_penalty=1.2, frame_cap=FRAME_CAP, row0=TEXT_ROW0, R=TEXT_R,
+               R_total=TEXT_RT, slots=_text_slots(rng, lambda i: rows[i][1], True), text_avail=text_avail)
+    return dict(logits=logits, st=st, cfg=cfg, families=[tag] * TEXT_R)
+
+
+def hold_grid_cases(V):
+    """The hand grid of tests/test_sample_reference.py on the device: text_avail = HOLD_AVAIL and a budget of HOLD_BUDGET
+    on every row."""
+    # (the grid's held cells all fall on even, greedy rows: the rows that fill the last launch repeat them on both kinds)
+    grid = hold_grid() + [(n, 3, 0) for n in (5, 5, 6, 6, 11, 11, 4, 12)]
+    return [_talker_text_case(V, "hold", li, [(n, fl, done, 0) for n, fl, done in rows], np.full(TEXT_RT, HOLD_AVAIL, np.int32))
+            for li, rows in enumerate(_launches(grid))]
+
+
+def eos_mask_cases(V):
+    """flags 0 .. 3 with hold off (text_avail null), EOS on top; half of the rows beyond progress 2 (forced EOS: n_past
+    31 of n_text 5), half far below (n_past 3)."""
+    rows = [((31, 3)[(i // 4) % 2], i % 4, 0, 5) for i in range(TEXT_R)]
+    case = _talker_text_case(V, "eos_mask", 0, rows, None)
+    for s in case["cfg"]["slots"]:
+        s["max_frames"] = 0
+    for i in range(TEXT_R):                      # greedy and stochastic rows of every (flags, forced) pair
+        case["cfg"]["slots"][TEXT_ROW0 + i]["t_temp"] = 0.8 if i >= 8 else 0.0
+    return [case]
+
+
+def _cp_text_case(V, tag, li, frame_cap=FRAME_CAP, group=4):
+    rng = rng_for(tag, V, li)
+    cfg = dict(V=V, frame_cap=frame_cap, row0=TEXT_ROW0, R=TEXT_R, R_total=TEXT_RT, group=group,
+               slots=_text_slots(rng, lambda i: (1, 0, 3, 2)[i % 4], False))
+    logits = (SPREAD * 0.8 * rng.standard_normal((TEXT_RT, V))).astype(np.float32)
+    codes = rng.integers(0, 64, (frame_cap, TEXT_RT, 16)).astype(np.int32)      # ids of every vocabulary in use
+    return rng, dict(logits=logits, cfg=cfg, families=[tag] * TEXT_R, codes=codes,
+                     n_frames=rng.integers(1, frame_cap + 1, TEXT_RT).astype(np.int32))
+
+
+def cp_held_cases(V):
+    """Even rows of the launch held, in pairs greedy / stochastic; the id the frame records in this group's column is in
+    range, -1, beyond the vocabulary, or in range under a teacher-forced id.  A held row's logits put another id on
+    top, far above the rest: a fresh decision would differ from the recorded id."""
+    rng, case = _cp_text_case(V, "cp_held", 0)
+    cfg, g = case["cfg"], case["cfg"]["group"]
+    held = np.ones(TEXT_RT, np.int32)
+    forced = np.full((FRAME_CAP, TEXT_RT, 16), -1, np.int32)
+    for i in range(TEXT_R):
+        r = TEXT_ROW0 + i
+        held[r] = int(i % 4 < 2)                 # held rows 0, 1 (greedy, stochastic), free rows 2, 3, ...
+        nf = case["n_frames"][r] = 1 + (i * 3) % FRAME_CAP
+        rec = (int(rng.integers(0, V)), -1, V + 5, int(rng.integers(0, V)))[(i // 4) % 4]
+        case["codes"][nf - 1, r, 1 + g] = rec
+        if (i // 4) % 4 == 3:
+            forced[nf - 1, r, 1 + g] = 9
+            forced[nf - 1, r, 1 + (g + 1) % 15] = 2
+        if held[r]:
+            case["logits"][r, ((rec if 0 <= rec < V else 0) + 7) % V] = 200.0
+    cfg.update(held=held, forced=forced)
+    return [case]
+
+
+def text_row_cases(V):
+    """The feedback launch (group 14) of text slots: (text_avail, n_frames) over TEXT_AVAILS x {0, 1, avail, avail + 1,
+    frame_cap, frame_cap + 1}; flags 0 rows with text_avail > 0 among them.  A last launch has frame_cap = 2 below
+    text_avail = 6: rows that ended past the codes array still add the text row of their own frame."""
+    specs = [(av, nf, FRAME_CAP) for av in TEXT_AVAILS for nf in (0, 1, av, av + 1, FRAME_CAP, FRAME_CAP + 1)]
+    cases = []
+    for li, rows in enumerate(_launches(specs) + [[(TEXT_CAP, nf, 2) for nf in (1, 2, 3, 4, 5, 6, 7, 8)] * 2]):
+        rng, case = _cp_text_case(V, "text_rows", li, frame_cap=rows[0][2], group=14)
+        ta = np.zeros(TEXT_RT, np.int32)
+        for i, (av, nf, _) in enumerate(rows):
+            ta[TEXT_ROW0 + i], case["n_frames"][TEXT_ROW0 + i] = av, nf
+        case["cfg"].update(text_avail=ta, text_cap=TEXT_CAP)
+        cases.append(case)
+    return cases
+
+
+def text_talker_cases(V):
+    return hold_grid_cases(V) + eos_mask_cases(V)
+
+
+def text_cp_cases(V):
+    return cp_held_cases(V) + text_row_cases(V)

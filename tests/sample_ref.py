@@ -157,15 +157,48 @@ def _row_params(cfg, r, talker):
 
 
 # ---- talker: decision + state transition -------------------------------------------------------------------------
+def slot_flags(cfg, r) -> int:
+    """SlotParams::flags of row r (per-slot mode only): bit 0 a text slot, bit 1 its EOS is masked."""
+    slots = cfg.get("slots")
+    return int(slots[r].get("flags", 0)) if slots is not None else 0
+
+
+def talker_held(st, cfg, r) -> bool:
+    """TalkerSampleArgs (csrc/q3_kernels.h): with text_avail given, in per-slot mode, a row is held in this step when
+    its slot is a text slot whose text has not ended (flags 3), the row has not ended, and 1 <= n_past < its budget
+    while n_past >= text_avail[r]."""
+    ta = cfg.get("text_avail")
+    if ta is None or cfg.get("slots") is None:
+        return False
+    n_past = int(st["n_past"][r])
+    return (slot_flags(cfg, r) & 3) == 3 and not st["done"][r] and 1 <= n_past < cfg["slots"][r]["max_frames"] and \
+        n_past >= int(ta[r])
+
+
+def talker_held_after(st, cfg):
+    """held[] after the launch: 1 on a held row, 0 on every other row of the launch, rows outside it as they were;
+    without text_avail nothing is written."""
+    held = np.array(st["held"], copy=True)
+    if cfg.get("text_avail") is not None:
+        for r in range(cfg["row0"], cfg["row0"] + cfg["R"]):
+            held[r] = int(talker_held(st, cfg, r))
+    return held
+
+
 def talker_sets(logits, st, cfg):
     """-> {row: (set of acceptable decisions, processed logits)} for rows row0 .. row0 + R - 1.  A decision is the id
-    after the forced-EOS rule (progress > 2 and not ignore_eos: EOS whatever was drawn)."""
+    after the forced-EOS rule (progress > 2 and not ignore_eos: EOS whatever was drawn).  A slot whose EOS is masked
+    (flags & 2) is a row under ignore_eos: EOS at -1e10, no boost, no forced EOS.  A held row (talker_held) decides
+    nothing and has no entry."""
     out = {}
     for r in range(cfg["row0"], cfg["row0"] + cfg["R"]):
+        if talker_held(st, cfg, r):
+            continue
         p = _row_params(cfg, r, True)
+        ign = bool(cfg.get("ignore_eos", False)) or bool(slot_flags(cfg, r) & 2)
         l, forced = process_talker(logits[r], st["past"][r], int(st["n_past"][r]), int(st["n_text"][r]),
-                                   cfg["audio_vocab"], cfg["eos"], cfg.get("ignore_eos", False), cfg.get("rep_penalty", 1.2))
-        if forced and not cfg.get("ignore_eos", False):
+                                   cfg["audio_vocab"], cfg["eos"], ign, cfg.get("rep_penalty", 1.2))
+        if forced and not ign:
             s = {cfg["eos"]}
         else:
             u = uniform01(p["seed"], p["row_key"], int(st["n_frames"][r]), 0)
@@ -216,10 +249,19 @@ def cp_frame(n_frames_r, frame_cap):
     return (f, True) if f < frame_cap else (frame_cap - 1, False)
 
 
+def cp_held(cfg, r) -> bool:
+    """CpArgmaxArgs::held: per-slot mode, held[r] != 0."""
+    held = cfg.get("held")
+    return held is not None and cfg.get("slots") is not None and int(held[r]) != 0
+
+
 def cp_sets(logits, n_frames, cfg):
-    """-> {row: set of acceptable decisions}.  No top-p; the draw key's group is 1 + group, its frame n_frames[r]."""
+    """-> {row: set of acceptable decisions}.  No top-p; the draw key's group is 1 + group, its frame n_frames[r].
+    A held row decides nothing and has no entry."""
     out = {}
     for r in range(cfg["row0"], cfg["row0"] + cfg["R"]):
+        if cp_held(cfg, r):
+            continue
         p = _row_params(cfg, r, False)
         u = uniform01(p["seed"], p["row_key"], int(n_frames[r]), 1 + cfg["group"])
         out[r] = pick_set(logits[r], p["temperature"], p["top_k"], 0.0, u)
@@ -228,11 +270,18 @@ def cp_sets(logits, n_frames, cfg):
 
 def cp_apply_row(codes, n_frames, cfg, r, code):
     """Records the decision in column group + 1 (in place) and returns the id the stream continues with: the forced
-    one when teacher forcing names one for a recorded frame."""
+    one when teacher forcing names one for a recorded frame.  A held row (cp_held; `code` is ignored) stores nothing
+    and continues with the id its frame records in that column, 0 when that is no id of the vocabulary; teacher
+    forcing overrides afterwards as for any row."""
     f, keep = cp_frame(n_frames[r], cfg["frame_cap"])
     used = code
-    if keep:
+    if cp_held(cfg, r):
+        used = int(codes[f, r, 1 + cfg["group"]])
+        if not 0 <= used < cfg["V"]:
+            used = 0
+    elif keep:
         codes[f, r, 1 + cfg["group"]] = code
+    if keep:
         forced = cfg.get("forced")
         if forced is not None and forced[f, r, 1 + cfg["group"]] >= 0:
             used = int(forced[f, r, 1 + cfg["group"]])
@@ -258,6 +307,16 @@ def feedback_row(codes16, talker_emb, cp_tables, pad):
     if pad is not None:
         buf += pad
     return buf
+
+
+def feedback_last(pad, text_rows, text_avail, n_frames_r):
+    """The last addend of the feedback sum of a row whose frame counter is n_frames_r (CpArgmaxArgs::text_rows): row
+    n_frames_r - 1 of the slot's text_rows [text_cap][H] while that is a frame (>= 0) below text_avail, else pad (which
+    may be None: nothing is added).  The frame is counted from the slot's start and is not clamped to frame_cap."""
+    f = int(n_frames_r) - 1
+    if text_rows is not None and 0 <= f < int(text_avail):
+        return text_rows[f]
+    return pad
 
 
 def cp_feedback_codes(codes, n_frames, cfg, r, used):

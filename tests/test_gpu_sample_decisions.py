@@ -9,7 +9,13 @@ rows outside the launch included.
 
 Ambiguous shares (computed from the reference alone, so the same on every machine; worst family over all vocabularies
 and both modes): talker 3 of 75 (4.0 %), code predictor 1 of 47 (2.1 %); most families 0 -- printed per family by
-tests/test_sample_reference.py::test_ambiguity_cap and by the decision tests here."""
+tests/test_sample_reference.py::test_ambiguity_cap and by the decision tests here.
+
+Text slots (q3t_talker_sample_text_case / q3t_cp_sample_text_case, 16 rows per launch at row 3 of 21, greedy and stochastic
+rows side by side): the hold rule over its hand grid, the EOS mask of flags & 2, held rows of the code predictor under every
+epilogue, and the text row the feedback adds last.  None of their stochastic rows is ambiguous (talker 0 of 58 + 0 of 16,
+code predictor 0 of 8 + 0 of 48 over both vocabularies; held rows make no draw and are not counted) --
+tests/test_sample_reference.py::test_ambiguity_cap_text_cases."""
 import ctypes
 
 import numpy as np
@@ -32,6 +38,7 @@ def _slots_array(slots):
     for a, s in zip(arr, slots):
         a.max_frames, a.t_temp, a.t_top_k, a.t_top_p = s["max_frames"], s["t_temp"], s["t_top_k"], s["t_top_p"]
         a.c_temp, a.c_top_k, a.seed, a.no_row = s["c_temp"], s["c_top_k"], s["seed"], s["no_row"]
+        a.flags = s.get("flags", 0)
     return arr, ctypes.cast(arr, ctypes.c_void_p)
 
 
@@ -40,7 +47,8 @@ def _opt(a, ptr):
 
 
 def run_talker(lib, logits, st, cfg):
-    """-> (return code, state after the launch); `st` itself stays as it is."""
+    """-> (return code, state after the launch); `st` itself stays as it is.  A state with `held` (and cfg["text_avail"],
+    which may be None) goes through q3t_talker_sample_text_case."""
     out = SR.copy_state(st)
     RT = logits.shape[0]
     assert cfg.get("R_total", RT) == RT
@@ -48,13 +56,17 @@ def run_talker(lib, logits, st, cfg):
     forced = cfg.get("forced")
     seed_ptr = cfg.get("seed_ptr")
     keep, slots = _slots_array(cfg.get("slots"))
-    rc = lib.q3t_talker_sample_case(
+    text = "held" in st or cfg.get("text_avail") is not None
+    ta = cfg.get("text_avail")
+    ta = None if ta is None else np.ascontiguousarray(ta, np.int32)
+    extra = (_opt(ta, hiplib.iptr), _opt(out.get("held"), hiplib.iptr)) if text else ()
+    rc = (lib.q3t_talker_sample_text_case if text else lib.q3t_talker_sample_case)(
         hiplib.fptr(logits), logits.shape[1], RT, cfg["row0"], cfg["R"], hiplib.iptr(out["past"]), hiplib.iptr(out["n_past"]),
         hiplib.iptr(out["n_text"]), hiplib.iptr(out["done"]), hiplib.iptr(out["n_frames"]), hiplib.iptr(out["pos0"]),
         hiplib.iptr(out["pos"]), hiplib.iptr(out["codes"]), cfg["frame_cap"], _opt(forced, hiplib.iptr),
         cfg["audio_vocab"], cfg["eos"], int(cfg.get("ignore_eos", False)), cfg.get("max_frames", 0),
         cfg.get("rep_penalty", 1.2), cfg.get("temperature", 0.0), cfg.get("top_k", 50), cfg.get("top_p", 0.95),
-        cfg.get("seed", 0), None if seed_ptr is None else seed_ptr.ctypes.data_as(U64P), slots)
+        cfg.get("seed", 0), None if seed_ptr is None else seed_ptr.ctypes.data_as(U64P), slots, *extra)
     return rc, out
 
 
@@ -62,12 +74,17 @@ ROW_KEYS = ("past", "n_past", "done", "n_frames", "pos")
 
 
 def check_talker(lib, case, counts=None):
-    """One launch: the decision of every row is in its acceptable set and the whole state equals the reference's."""
+    """One launch: the decision of every row is in its acceptable set and the whole state equals the reference's.  A
+    held row has no decision: it is missing from the sets, so the reference's state keeps its input bit for bit in
+    past, n_past, done, n_frames, pos and codes, and the comparison of the whole state below demands the same of the
+    device; held[] is compared over every row of the batch."""
     logits, st, cfg = case["logits"], case["st"], case["cfg"]
     rc, dev = run_talker(lib, logits, st, cfg)
     assert rc == 0, f"launch refused: {rc}"
     sets = SR.talker_sets(logits, st, cfg)
     exp = SR.copy_state(st)
+    if "held" in st:
+        exp["held"] = SR.talker_held_after(st, cfg)
     for r, (picks, _) in sets.items():
         ok = False
         for code in sorted(picks):
@@ -97,7 +114,8 @@ def check_talker(lib, case, counts=None):
 
 def run_cp(lib, logits, codes, n_frames, cfg, epi=None):
     """epi: None, or dict(kind=1, H, next_table, next_qkv=None, gamma=None) / dict(kind=2, H, talker_emb, cp_tables [G][V][H],
-    pad, gamma=None).  -> (rc, codes, outputs dict); outputs start as sentinels so untouched rows show."""
+    pad, gamma=None, text_rows [RT][text_cap][H] = None).  cfg["held"] / cfg["text_avail"] + cfg["text_cap"] / text_rows send
+    the launch through q3t_cp_sample_text_case.  -> (rc, codes, outputs dict); outputs start as sentinels so untouched rows show."""
     RT, V = logits.shape
     logits = np.ascontiguousarray(logits, np.float32)
     codes = np.array(codes, np.int32, copy=True)
@@ -121,14 +139,20 @@ def run_cp(lib, logits, codes, n_frames, cfg, epi=None):
                 out["qkv"] = np.full((RT, qkv_ld), 777.0, np.float32)
         else:
             temb, cpt, pad = epi["talker_emb"], np.ascontiguousarray(epi["cp_tables"], np.float32), epi.get("pad")
-    rc = lib.q3t_cp_sample_case(
+    trows = epi.get("text_rows") if epi else None
+    ta, held = cfg.get("text_avail"), cfg.get("held")
+    text = trows is not None or ta is not None or held is not None
+    ta = None if ta is None else np.ascontiguousarray(ta, np.int32)
+    held = None if held is None else np.ascontiguousarray(held, np.int32)
+    extra = (_opt(trows, hiplib.fptr), _opt(ta, hiplib.iptr), cfg.get("text_cap", 0), _opt(held, hiplib.iptr)) if text else ()
+    rc = (lib.q3t_cp_sample_text_case if text else lib.q3t_cp_sample_case)(
         hiplib.fptr(logits), V, RT, cfg["row0"], cfg["R"], cfg["group"], hiplib.iptr(codes), hiplib.iptr(n_frames),
         cfg["frame_cap"], _opt(forced, hiplib.iptr), cfg.get("temperature", 0.0), cfg.get("top_k", 50), cfg.get("seed", 0),
         None if seed_ptr is None else seed_ptr.ctypes.data_as(U64P), slots, kind, H, _opt(tab, hiplib.fptr),
         _opt(qkv, hiplib.fptr), qkv_ld, _opt(gamma, hiplib.fptr), _opt(temb, hiplib.fptr), 0 if temb is None else temb.shape[0],
         _opt(cpt, hiplib.fptr), 0 if cpt is None else cpt.shape[0], _opt(pad, hiplib.fptr), _opt(out.get("h"), hiplib.fptr),
         _opt(out.get("ssq"), hiplib.fptr), None if "xh" not in out else out["xh"].ctypes.data_as(U16P),
-        _opt(out.get("qkv"), hiplib.fptr))
+        _opt(out.get("qkv"), hiplib.fptr), *extra)
     return rc, codes, out
 
 
@@ -142,6 +166,9 @@ def check_cp(lib, case, epi=None, counts=None):
     rows = range(cfg["row0"], cfg["row0"] + cfg["R"])
     used = {}
     for r in rows:
+        if SR.cp_held(cfg, r):   # no decision: the row continues with the id its frame records, and stores nothing
+            used[r] = SR.cp_apply_row(exp, n_frames, cfg, r, None)
+            continue
         picks = sets[r]
         f, keep = SR.cp_frame(n_frames[r], cfg["frame_cap"])
         got = int(dcodes[f, r, 1 + g]) if keep else None
@@ -185,7 +212,10 @@ def _epi_row(epi, codes_after, n_frames, cfg, r, used):
     if epi["kind"] == 1:
         return SR.gather_row(epi["next_table"], used)
     ids = SR.cp_feedback_codes(codes_after, n_frames, cfg, r, used)
-    return SR.feedback_row(ids, epi["talker_emb"], list(epi["cp_tables"]), epi.get("pad"))
+    last = epi.get("pad")
+    if epi.get("text_rows") is not None and cfg.get("slots") is not None:
+        last = SR.feedback_last(last, epi["text_rows"][r], cfg["text_avail"][r], n_frames[r])
+    return SR.feedback_row(ids, epi["talker_emb"], list(epi["cp_tables"]), last)
 
 
 def _epi_matches(out, epi, codes, n_frames, cfg, r, code):
@@ -482,6 +512,160 @@ def test_cp_feedback_epilogue(test_lib, H):
                    pad=rng.standard_normal(H).astype(np.float32) if pad_on else None,
                    gamma=(1.0 + 0.3 * rng.standard_normal(H)).astype(np.float32) if pad_on else None)
         check_cp(test_lib, case, epi)
+
+
+# ---- text slots: hold rule, EOS mask, held rows of the code predictor, text rows in the feedback ------------------------
+def _launch_rows(case):
+    return range(case["cfg"]["row0"], case["cfg"]["row0"] + case["cfg"]["R"])
+
+
+@pytest.mark.parametrize("V", SC.TEXT_TALKER_VOCABS)
+def test_talker_hold_grid(test_lib, V):
+    """Every cell of the hold rule's hand grid (tests/test_sample_reference.py::test_hold_rule_hand_grid), 16 per launch
+    of talker_sample_kernel_slots with text_avail and held.  EOS is on top of every row: a held row that decided
+    anything would end.  A held row keeps its state bit for bit and held[] equals the reference on all 21 rows
+    (check_talker); greedy and stochastic rows alternate."""
+    counts = [0, 0]
+    held_rows = free_flag3 = 0
+    for case in SC.hold_grid_cases(V):
+        st, cfg = case["st"], case["cfg"]
+        dev = check_talker(test_lib, case, counts)
+        for r in _launch_rows(case):
+            if SR.talker_held(st, cfg, r):
+                held_rows += 1
+                assert dev["held"][r] == 1 and dev["done"][r] == 0 and dev["n_frames"][r] == st["n_frames"][r]
+            else:
+                assert dev["held"][r] == 0
+                free_flag3 += cfg["slots"][r]["flags"] == 3
+        outside = [r for r in range(cfg["R_total"]) if r not in _launch_rows(case)]
+        assert (dev["held"][outside] == SC.HELD_SENTINEL).all()
+    assert held_rows == 9 and free_flag3 >= 9
+    _report("talker hold grid", counts)
+
+
+@pytest.mark.parametrize("V", SC.TEXT_TALKER_VOCABS)
+def test_talker_eos_mask(test_lib, V):
+    """flags 2 and 3 with hold off: EOS on top, with and without forced EOS (progress > 2) -- the row continues with the
+    best audio id; flags 0 and 1 end.  held[] (given, with text_avail null) stays untouched."""
+    counts = [0, 0]
+    av, eos = SC.TALKER_VOCABS[V]
+    for case in SC.eos_mask_cases(V):
+        st, cfg, logits = case["st"], case["cfg"], case["logits"]
+        assert cfg["text_avail"] is None
+        dev = check_talker(test_lib, case, counts)
+        sets = SR.talker_sets(logits, st, cfg)
+        kinds = set()
+        for r in _launch_rows(case):
+            fl, f = cfg["slots"][r]["flags"], int(st["n_frames"][r])
+            forced = st["n_past"][r] / (3 * st["n_text"][r]) > 2
+            assert int(np.argmax(logits[r])) == eos
+            if fl & 2:
+                code = int(dev["codes"][f, r, 0])
+                assert dev["done"][r] == 0 and 0 <= code < av and code in sets[r][0]
+                if SR.is_greedy(cfg["slots"][r]["t_temp"]):
+                    assert code == SR.first_argmax(sets[r][1][:av])
+            else:
+                assert dev["done"][r] == 1 and dev["codes"][f, r, 0] == -1
+            kinds.add((fl, bool(forced), SR.is_greedy(cfg["slots"][r]["t_temp"])))
+        assert len(kinds) == 16
+        assert (dev["held"] == SC.HELD_SENTINEL).all()
+    _report("talker EOS mask", counts)
+
+
+def _text_epilogue(name, V, H, rng):
+    gamma = (1.0 + 0.3 * rng.standard_normal(H)).astype(np.float32)
+    if name == "none":
+        return None
+    if name.startswith("gather"):
+        epi = dict(kind=1, H=H, next_table=rng.standard_normal((V, H), dtype=np.float32), gamma=gamma)
+        if name == "gather_qkv":
+            epi["next_qkv"] = rng.standard_normal((V, 192), dtype=np.float32)
+        return epi
+    return dict(kind=2, H=H, talker_emb=rng.standard_normal((100, H), dtype=np.float32),
+                cp_tables=rng.standard_normal((15, V, H), dtype=np.float32), pad=rng.standard_normal(H, dtype=np.float32), gamma=gamma)
+
+
+@pytest.mark.parametrize("epilogue", ["none", "gather", "gather_qkv", "feedback"])
+@pytest.mark.parametrize("V", SC.TEXT_CP_VOCABS)
+def test_cp_held_rows(test_lib, V, epilogue):
+    """A held row of cp_argmax_kernel_slots leaves codes untouched and continues with the id its frame records (0 for -1 and
+    for an id beyond the vocabulary; the teacher-forced id where one is given), whatever its logits say: h_out bit-equal,
+    ssq_out / xh_out / qkv_out as check_cp grades them, built from that id.  Free rows of the same launch decide as ever."""
+    H = 1024 if V == 64 else 96
+    counts = [0, 0]
+    for case in SC.cp_held_cases(V):
+        cfg, g = case["cfg"], case["cfg"]["group"]
+        epi = _text_epilogue(epilogue, V, H, SC.rng_for("held epi", V, epilogue))
+        dcodes, _ = check_cp(test_lib, case, epi, counts)
+        recorded = set()
+        for r in _launch_rows(case):
+            f = int(case["n_frames"][r]) - 1
+            if cfg["held"][r]:
+                rec = int(case["codes"][f, r, 1 + g])
+                recorded.add("in" if 0 <= rec < V else rec)
+                assert dcodes[f, r, 1 + g] == rec
+                assert SR.first_argmax(case["logits"][r]) != (rec if 0 <= rec < V else 0), "a fresh decision must differ"
+            else:
+                assert dcodes[f, r, 1 + g] in SR.cp_sets(case["logits"], case["n_frames"], cfg)[r]
+        assert recorded == {"in", -1, V + 5}
+    _report("cp held rows", counts)
+
+
+@pytest.mark.parametrize("H", [96, 1024])
+@pytest.mark.parametrize("V", SC.TEXT_CP_VOCABS)
+def test_cp_feedback_text_rows(test_lib, V, H):
+    """The feedback sum's last addend: text_rows[r][n_frames - 1] while n_frames - 1 < text_avail[r], pad otherwise (also on
+    flags-0 rows, as CpArgmaxArgs documents; also where the codes' frame is clamped to frame_cap - 1).  Every text row
+    and the pad are distinct random rows; h_out is bit-equal to sample_ref.feedback_row."""
+    rng = SC.rng_for("text rows", V, H)
+    epi = _text_epilogue("feedback", V, H, rng)
+    epi["text_rows"] = rng.standard_normal((SC.TEXT_RT, SC.TEXT_CAP, H), dtype=np.float32)
+    counts = [0, 0]
+    seen = set()
+    for case in SC.text_row_cases(V):
+        cfg = case["cfg"]
+        check_cp(test_lib, case, epi, counts)
+        for r in _launch_rows(case):
+            last = SR.feedback_last(None, epi["text_rows"][r], cfg["text_avail"][r], case["n_frames"][r])
+            seen.add((last is not None, cfg["slots"][r]["flags"] & 1, int(case["n_frames"][r]) - 1 >= cfg["frame_cap"]))
+    assert seen == {(t, f, c) for t in (False, True) for f in (0, 1) for c in (False, True)}
+    _report("cp text rows", counts)
+
+
+def test_sampler_launchers_refuse_inconsistent_text_arguments(test_lib):
+    """text_avail without held, either of them without per-slot mode (talker); text_rows / text_avail / held without
+    per-slot mode, text_rows without text_avail or with text_cap = 0 (code predictor): -1, and nothing changes."""
+    V = 64
+    case = SC.hold_grid_cases(V)[0]
+    st, cfg = case["st"], case["cfg"]
+    no_held = {k: v for k, v in st.items() if k != "held"}
+    scalar = dict(cfg, slots=None, temperature=0.0)
+    for state, c in ((no_held, cfg), (st, scalar), (no_held, scalar), (st, dict(scalar, text_avail=None))):
+        rc, dev = run_talker(test_lib, case["logits"], state, c)
+        assert rc == -1
+        for k in state:
+            np.testing.assert_array_equal(dev[k], state[k], err_msg=k)
+    rc, _ = run_talker(test_lib, case["logits"], st, cfg)        # the consistent set is served
+    assert rc == 0
+    case = SC.text_row_cases(V)[0]
+    cfg = case["cfg"]
+    H = 96
+    epi = _text_epilogue("feedback", V, H, SC.rng_for("refusals"))
+    epi["text_rows"] = np.zeros((SC.TEXT_RT, SC.TEXT_CAP, H), np.float32)
+    held = np.zeros(SC.TEXT_RT, np.int32)
+    scalar = dict(cfg, slots=None, temperature=0.0)
+    no_text = dict(epi, text_rows=None)
+    bad = [(scalar, epi), (scalar, no_text), (dict(scalar, text_avail=None, text_cap=0, held=held), no_text),
+           (dict(cfg, text_avail=None), epi), (dict(cfg, text_cap=0), epi), (dict(cfg, text_cap=-1), epi)]
+    for c, e in bad:
+        rc, got, out = run_cp(test_lib, case["logits"], case["codes"], case["n_frames"], c, e)
+        assert rc == -1
+        np.testing.assert_array_equal(got, case["codes"])
+        assert (out["h"] == 777.0).all() and (out["ssq"] == 777.0).all()
+    rc, _, _ = run_cp(test_lib, case["logits"], case["codes"], case["n_frames"], cfg, epi)
+    assert rc == 0
+    rc, _, _ = run_cp(test_lib, case["logits"], case["codes"], case["n_frames"], dict(cfg, held=held), no_text)
+    assert rc == 0
 
 
 # ---- what the launcher refuses ----------------------------------------------------------------------------------------

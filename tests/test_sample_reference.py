@@ -259,3 +259,136 @@ def test_ambiguity_cap(slots_mode):
                 assert a <= 0.05 * n, f"{kernel} V={V} {fam}: {a} of {n} ambiguous"
                 worst[kernel] = max(worst.get(kernel, 0.0), a / n)
     print("worst share per kernel:", {k: f"{100 * v:.1f} %" for k, v in worst.items()})
+
+
+# ---- text slots: hold rule, EOS mask, held rows of the code predictor, the feedback's last addend ----------------------
+def _hold_state(n_past, done):
+    return dict(past=np.arange(32, dtype=np.int32)[None].copy(), n_past=np.array([n_past], np.int32), n_text=np.zeros(1, np.int32),
+                done=np.array([done], np.int32), n_frames=np.array([1], np.int32), pos0=np.array([9], np.int32),
+                pos=np.array([-7], np.int32), codes=np.full((2, 1, 16), -7, np.int32), held=np.array([-7], np.int32))
+
+
+def test_hold_rule_hand_grid():
+    """text_avail 5, budget 12: held exactly for a live flags-3 row with n_past in 5 .. 11 (n_past >= 1 decides alone
+    where text_avail is 0)."""
+    assert SC.HOLD_N_PAST == (0, 1, 4, 5, 6, 11, 12) and len(SC.hold_grid()) == 56
+    seen = 0
+    for n_past, flags, done in SC.hold_grid():
+        st = _hold_state(n_past, done)
+        cfg = dict(audio_vocab=48, eos=50, frame_cap=2, row0=0, R=1, slots=[SC.slot(max_frames=12, flags=flags)],
+                   text_avail=np.array([5], np.int32))
+        want = flags == 3 and not done and n_past in (5, 6, 11)
+        assert SR.talker_held(st, cfg, 0) == want, (n_past, flags, done)
+        assert SR.talker_held_after(st, cfg).tolist() == [int(want)]
+        assert (0 in SR.talker_sets(np.zeros((1, 64), np.float32), st, cfg)) == (not want)
+        seen += want
+    assert seen == 3
+    st = _hold_state(0, 0)
+    flags3 = [SC.slot(max_frames=12, flags=3)]
+    for avail, n_past, want in ((0, 0, False), (0, 1, True), (1, 1, True), (2, 1, False), (12, 11, False), (11, 11, True), (0, 12, False)):
+        st["n_past"][0] = n_past
+        assert SR.talker_held(st, dict(slots=flags3, text_avail=[avail]), 0) == want, (avail, n_past)
+    # hold is per-slot mode with text_avail: without either nothing is held and held[] is not written
+    st["n_past"][0] = 6
+    assert not SR.talker_held(st, dict(slots=flags3), 0) and not SR.talker_held(st, dict(text_avail=[5]), 0)
+    assert SR.talker_held_after(st, dict(slots=flags3, row0=0, R=1)).tolist() == [-7]
+    # rows outside the launch keep what they had
+    st3 = dict(n_past=np.array([6, 6, 6]), done=np.zeros(3, np.int32), held=np.array([-7, -7, -7], np.int32))
+    cfg3 = dict(slots=[SC.slot(max_frames=12, flags=f) for f in (3, 3, 1)], text_avail=[5, 5, 5], row0=1, R=2)
+    assert SR.talker_held_after(st3, cfg3).tolist() == [-7, 1, 0]
+
+
+def test_eos_mask_hand_cases():
+    """flags & 2: the EOS logit is -1e10 (still penalised when EOS repeats) and neither boost nor forced EOS applies;
+    flags 0 and 1 are the plain row."""
+    V, av, eos = 64, 48, 50
+    l = np.full(V, -5.0, np.float32)
+    l[eos], l[7] = 9.0, 1.0
+    for flags in (0, 1, 2, 3):
+        for n_past, n_text in ((31, 5), (3, 5), (3, 0)):
+            st = _hold_state(n_past, 0)
+            st["n_text"][0] = n_text
+            st["past"][0, :] = 40                      # (an id that is on top of nothing)
+            cfg = dict(audio_vocab=av, eos=eos, frame_cap=2, row0=0, R=1, slots=[SC.slot(flags=flags)])
+            picks, proc = SR.talker_sets(l[None], st, cfg)[0]
+            if flags & 2:
+                assert picks == {7} and proc[eos] == np.float32(-1e10)
+            else:
+                assert picks == {eos}
+                boost = min((n_past / (3 * n_text) - 0.8) / 0.7, 1.0) * 15.0 if n_text and n_past / (3 * n_text) > 0.8 else 0.0
+                assert proc[eos] == np.float32(9.0) + np.float32(boost)
+    st = _hold_state(3, 0)
+    st["past"][0, :3] = eos                            # EOS repeats: -1e10 * 1.2
+    _, proc = SR.talker_sets(l[None], st, dict(audio_vocab=av, eos=eos, row0=0, R=1, slots=[SC.slot(flags=2)]))[0]
+    assert proc[eos] == np.float32(-1e10) * np.float32(1.2)
+    # scalar mode has no flags
+    assert SR.slot_flags(dict(), 0) == 0
+
+
+def test_cp_held_hand_cases():
+    V = 64
+    forced = np.full((2, 1, 16), -1, np.int32)
+    base = dict(V=V, frame_cap=2, group=2, slots=[SC.slot()], row0=0, R=1)
+    for rec, want in ((17, 17), (-1, 0), (V, 0), (V + 5, 0), (0, 0), (V - 1, V - 1)):
+        codes = np.full((2, 1, 16), -7, np.int32)
+        codes[1, 0, 3] = rec
+        before = codes.copy()
+        cfg = dict(base, held=np.array([1], np.int32))
+        assert SR.cp_held(cfg, 0) and SR.cp_sets(np.zeros((1, V), np.float32), [2], cfg) == {}
+        assert SR.cp_apply_row(codes, [2], cfg, 0, 33) == want and (codes == before).all()
+        assert SR.cp_feedback_codes(codes, [2], cfg, 0, want)[3] == want
+        # teacher forcing overrides afterwards; the other groups' forced ids still replace the recorded ones
+        forced[1, 0, 3], forced[1, 0, 5] = 21, 22
+        assert SR.cp_apply_row(codes, [2], dict(cfg, forced=forced), 0, 33) == 21 and (codes == before).all()
+        assert SR.cp_feedback_codes(codes, [2], dict(cfg, forced=forced), 0, 21)[3:6] == [21, -7, 22]
+        forced[:] = -1
+        # beyond the codes array the last frame is read and nothing is forced
+        forced[1, 0, 3] = 21
+        assert SR.cp_apply_row(codes, [4], dict(cfg, forced=forced), 0, 33) == want
+        forced[:] = -1
+        # held = 0, or scalar mode: the row decides and records
+        for c2 in (dict(base, held=np.array([0], np.int32)), dict(base, held=np.array([1], np.int32), slots=None)):
+            c = before.copy()
+            assert not SR.cp_held(c2, 0) and SR.cp_apply_row(c, [2], c2, 0, 33) == 33 and c[1, 0, 3] == 33
+
+
+def test_feedback_last_hand_cases():
+    cap, H = 8, 4
+    pad = np.full(H, -1.0, np.float32)
+    text = np.arange(6 * H, dtype=np.float32).reshape(6, H)
+    for avail in (0, 1, 3, 6):
+        for nf in (0, 1, avail, avail + 1, cap, cap + 1):
+            got = SR.feedback_last(pad, text, avail, nf)
+            if 1 <= nf <= avail:
+                assert got is not pad and (got == text[nf - 1]).all(), (avail, nf)
+            else:
+                assert got is pad, (avail, nf)
+    assert SR.feedback_last(pad, None, 3, 1) is pad and SR.feedback_last(None, text, 3, 4) is None
+    # the frame is the slot's own, not the clamped frame of the codes array: frame_cap 2, n_frames 4 -> text row 3
+    assert (SR.feedback_last(pad, text, 6, 4) == text[3]).all() and SR.cp_frame(4, 2) == (1, False)
+    tabs = [np.zeros((2, H), np.float32)] * 15
+    row = SR.feedback_row([0] * 16, np.ones((1, H), np.float32), tabs, SR.feedback_last(pad, text, 6, 2))
+    np.testing.assert_array_equal(row, np.float32(1.0) + text[1])
+
+
+def test_ambiguity_cap_text_cases():
+    """The stochastic rows of the text-slot cases (tests/test_gpu_sample_decisions.py): at most 5 % ambiguous per family;
+    held rows make no draw and do not count."""
+    total = {}
+    for kernel, vocabs in (("talker", SC.TEXT_TALKER_VOCABS), ("cp", SC.TEXT_CP_VOCABS)):
+        for V in vocabs:
+            if kernel == "talker":
+                cases = SC.text_talker_cases(V)
+                shares = SC.ambiguous_share(cases, lambda c: {r: s for r, (s, _) in SR.talker_sets(c["logits"], c["st"], c["cfg"]).items()})
+                held = sum(SR.talker_held(c["st"], c["cfg"], r) for c in cases for r in range(SC.TEXT_ROW0, SC.TEXT_ROW0 + SC.TEXT_R))
+                assert held == 3 + 6              # the grid's three held cells + those that fill the last launch
+            else:
+                cases = SC.text_cp_cases(V)
+                shares = SC.ambiguous_share(cases, lambda c: SR.cp_sets(c["logits"], c["n_frames"], c["cfg"]))
+            SC.share_report(f"{kernel} V={V} text slots", shares)
+            for fam, (a, n) in shares.items():
+                assert n >= 4 and a <= 0.05 * n, f"{kernel} V={V} {fam}: {a} of {n} ambiguous"
+                ta, tn = total.get((kernel, fam), (0, 0))
+                total[kernel, fam] = (ta + a, tn + n)
+    assert set(f for _, f in total) == {"hold", "eos_mask", "cp_held", "text_rows"}
+    print("text-slot cases:", {f"{k} {f}": f"{a}/{n}" for (k, f), (a, n) in total.items()})
