@@ -44,8 +44,8 @@ def voc_reference(tensors: dict, codes: np.ndarray, n_ops: int = -1, dtype=np.fl
                 nq, cbs = int(row[1]), int(row[2])
                 tab = t(p + "embedding")
                 valid = ((codes_t >= 0) & (codes_t < cbs)).to(tab.dtype)
-                idx = codes_t.clamp(0, cbs - 1) + torch.arange(nq)[None, None, :] * cbs
-                y = (tab[idx[..., :nq]] * valid[..., :nq, None]).mean(2)            # [B,T,dim]
+                idx = codes_t[..., :nq].clamp(0, cbs - 1) + torch.arange(nq)[None, None, :] * cbs   # (the first nq of a frame's 16 ids)
+                y = (tab[idx] * valid[..., :nq, None]).mean(2)                      # [B,T,dim]
                 x = y.transpose(1, 2).contiguous()
             elif op in (W.VOP_CONV, W.VOP_CONVT):
                 k, p0, flags = int(row[3]), int(row[4]), int(row[5])
@@ -71,7 +71,7 @@ def voc_reference(tensors: dict, codes: np.ndarray, n_ops: int = -1, dtype=np.fl
                 k, flags = int(row[3]), int(row[5])
                 if flags & W.VF_RES_SAVE:
                     res = x
-                x = F.conv1d(F.pad(x, (k - 1, 0)), t(p + "weight"), t(p + "bias"), groups=x.shape[1])
+                x = F.conv1d(F.pad(x, (k - 1, 0)), t(p + "weight"), t(p + "bias") if (p + "bias") in tensors else None, groups=x.shape[1])
             elif op == W.VOP_NORM:     # over channels, per column: 0 RMSNorm, 1 LayerNorm
                 kind, eps, flags = int(row[3]), int(row[4]) * 1e-9, int(row[5])
                 if flags & W.VF_RES_SAVE:

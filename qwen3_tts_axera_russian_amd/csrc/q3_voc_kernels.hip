@@ -23,8 +23,9 @@ __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x);
 static int g_voc_max_wgs = 0;  // 0 = one workgroup per tile; >0 caps the grid (persistent tile loop)
 // test hooks (voc_set_fill, voc_debug_last_variant at the end of this file; host side only)
 static int g_voc_fill = -1;    // < 0: the built-in workgroup target of the tile-height rules (512); >= 0 replaces it
-// the instantiation the last conv launch of this process took (a few plain stores per launch; named on request)
-enum { VV_NONE, VV_CONV, VV_OUT1, VV_RESUNIT, VV_SNAKE_SPLIT, VV_SPLIT };
+// the instantiation the last conv (or full-chunk attention) launch of this process took (a few plain stores per launch; named on
+// request)
+enum { VV_NONE, VV_CONV, VV_OUT1, VV_RESUNIT, VV_SNAKE_SPLIT, VV_SPLIT, VV_ATTN_TILE, VV_ATTN };
 static struct {
     int kind = VV_NONE, p[5] = {0, 0, 0, 0, 0};
     bool after_pass = false;   // split conv: its planes came from snake_split_kernel right before it
@@ -1163,6 +1164,7 @@ int voc_launch_attn_tile(hipStream_t s, const float* x, float* y, int H, int D, 
         Q3_HIP(hipFuncSetAttribute((const void*)voc_attn_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024), -1);
         attr = true;
     }
+    voc_note_variant(VV_ATTN_TILE);
     hipLaunchKernelGGL(voc_attn_tile_kernel, dim3(H, B), dim3(256), lds, s, x, y, H, D, L, ld, window, theta);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
@@ -1173,6 +1175,7 @@ int voc_launch_attn(hipStream_t s, const float* x, float* y, int H, int D, int L
         Q3_LOG("voc attention: head_dim %d is not built (even, <= 128)", D);
         return -1;
     }
+    voc_note_variant(VV_ATTN);
     hipLaunchKernelGGL(voc_attn_kernel, dim3((unsigned)L, H, B), dim3(64), 0, s, x, y, H, D, L, ld, window, theta);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
@@ -1565,7 +1568,7 @@ int voc_set_fill(int n) {
 
 // test hook: the instantiation the last conv launch took ("conv<4,1,16,ct0,act1>", "out1", "resunit<3>",
 // "split<7,1,3,1>/myfast", "snake_split", or "snake_split+split<...>" for a split conv that read the separate pass's planes;
-// "" before the first one)
+// "attn_tile" / "attn" after a full-chunk attention launch; "" before the first one)
 const char* voc_debug_last_variant() {
     static char name[64];
     const int* p = g_voc_variant.p;
@@ -1574,6 +1577,8 @@ const char* voc_debug_last_variant() {
         case VV_OUT1: snprintf(name, sizeof(name), "out1"); break;
         case VV_RESUNIT: snprintf(name, sizeof(name), "resunit<%d>", p[0]); break;
         case VV_SNAKE_SPLIT: snprintf(name, sizeof(name), "snake_split"); break;
+        case VV_ATTN_TILE: snprintf(name, sizeof(name), "attn_tile"); break;
+        case VV_ATTN: snprintf(name, sizeof(name), "attn"); break;
         case VV_SPLIT:
             snprintf(name, sizeof(name), "%ssplit<%d,%d,%d,%d>%s", g_voc_variant.after_pass ? "snake_split+" : "", p[0], p[1], p[2], p[3],
                      p[4] ? "/myfast" : "");

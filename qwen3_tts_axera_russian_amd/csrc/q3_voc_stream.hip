@@ -539,10 +539,12 @@ void incr_key(const Voc* v, long long prev, long long now, std::vector<long long
 // (my_fast) launch_conv_split picks from Lc and B -- so nothing needs pinning to the full-chunk length here.  An activation is buf[cur],
 // [B][C][pitch4(skip + n)]: `skip` leading columns are the outputs of history columns (dropped: nothing reads them), n are the
 // new ones.  dry: no launch, *need / *need_kv take the largest work buffer / k|v buffer (floats per entry) the sequence asks for.
+// stop: the walk ends after the first `stop` ops (voc_run's n_ops; the test hook voc_debug_incr_push): the op it ends on hands
+// over f32 as the table's last op does, the histories of the ops behind it are not touched.
 int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, size_t* need, size_t* need_kv, int* launches,
-              float** out_buf, int* out_ld, int* out_skip, bool split = false) {
+              float** out_buf, int* out_ld, int* out_skip, bool split = false, size_t stop = (size_t)-1) {
     Voc* v = s->v;
-    const size_t nops = v->ops.size();
+    const size_t nops = v->ops.size(), nend = std::min(stop, nops);
     const long long* nc = key.data();
     const long long* extra = key.data() + nops + 1;
     int cur = 0, skip = 0, C = 0;
@@ -582,7 +584,7 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
         res_skip = skip;
     };
     size_t i = 0;
-    for (; i < nops; i++) {
+    for (; i < nend; i++) {
         const VocOp& op = v->ops[i];
         if (n != nc[i]) return -1;
         if (n == 0) break;                        // no sample of this push reaches further (a stream's very first columns)
@@ -658,7 +660,7 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
             note(op.cout, sa.Lout);
             // the consumer takes planes from this epilogue only where it reads these very columns: one that carries a history
             // needs the f32 result for its own prepend
-            const VocOp* next = i + 1 < nops ? &v->ops[i + 1] : nullptr;
+            const VocOp* next = i + 1 < nend ? &v->ops[i + 1] : nullptr;
             const bool want_planes = voc_split_emits_planes(op, next) && s->H[i + 1] == 0;
             const bool want_f32 = !want_planes || (next->flags & VF_RES_SAVE);
             if (op.flags & VF_RES_ADD) {
@@ -685,7 +687,7 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
             C = op.cout;
             cur ^= 1;
             continue;
-        } else if (!split && voc_fused_unit(v, i, nops)) {
+        } else if (!split && voc_fused_unit(v, i, nend)) {
             if (prepend_act(i)) return -1;
             if (!dry && launch_resunit(v->s, voc_resunit_args(op, v->ops[i + 1], s->buf[cur], s->buf[cur ^ 1], skip + n), op.cin, B)) return -1;
             i++;   // the 1x1 conv is done
@@ -734,7 +736,7 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
         planes = -1;
     }
     if (i == nops && n != nc[nops]) return -1;
-    if (i < nops && nc[nops] != 0) return -1;
+    if (i < nend && nc[nops] != 0) return -1;
     if (!f32_cur && n > 0) return -1;
     if (out_buf) *out_buf = s->buf[cur];
     if (out_ld) *out_ld = (int)pitch4(skip + n);
@@ -778,13 +780,24 @@ int incr_plan(const VocIncr* s, int n, const int32_t* streams, const int32_t* n_
     return 0;
 }
 
+// n_stop >= 0 (voc_debug_incr_push): the walk ends after the first n_stop ops and `out` (f32) takes, per entry, the new columns
+// of that activation, [C][cols] packed at offsets[e] (floats), straight from the work buffer; *out_C = C.
 int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
-              bool want16, void* out, int64_t cap, int64_t* offsets) {
+              bool want16, void* out, int64_t cap, int64_t* offsets, int n_stop = -1, int32_t* out_C = nullptr) {
     if (!s || !offsets) return -1;
     Voc* v = s->v;
     voc_bind(v);
     IncrPlan p;
     if (incr_plan(s, n, streams, n_new, p)) return -1;
+    const bool debug = n_stop >= 0;
+    const size_t stop = debug ? std::min((size_t)n_stop, v->ops.size()) : v->ops.size();
+    const int stop_C = stop > 0 ? v->ops[stop - 1].cout : 0;
+    if (debug) {
+        if (want16 || stop == 0) return -1;
+        for (size_t g = 0; g < p.groups.keys.size(); g++)
+            for (int e : p.groups.members[g]) p.n_out[e] = p.groups.keys[g][stop] * stop_C;
+        if (out_C) *out_C = stop_C;
+    }
     long long total = 0;
     size_t frames = 0;
     std::vector<size_t> coff(n, 0);
@@ -795,7 +808,7 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
         frames += (size_t)n_new[i];
     }
     offsets[n] = total;
-    if (total > cap || (total > 0 && !out) || (frames > 0 && !codes) || (size_t)total > s->out_cap) {
+    if (total > cap || (total > 0 && !out) || (frames > 0 && !codes) || (!debug && (size_t)total > s->out_cap)) {
         Q3_LOG("voc_incr_push: %lld samples do not fit the caller's buffer of %lld (or no codes given)", total, (long long)cap);
         return -1;
     }
@@ -832,8 +845,14 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
         if (split) Q3_HIP(hipMemsetAsync(s->d_ovf, 0, sizeof(int) * B, v->s), -1);
         float* y = nullptr;
         int ld = 0, skip = 0;
-        if (incr_walk(s, key, B, false, nullptr, nullptr, &s->last_launches, &y, &ld, &skip, split)) return -1;
-        const long long ns = key[nops];
+        if (incr_walk(s, key, B, false, nullptr, nullptr, &s->last_launches, &y, &ld, &skip, split, stop)) return -1;
+        const long long ns = debug ? 0 : key[nops];
+        if (debug && key[stop] > 0) {   // rows of key[stop] new columns behind the `skip` dropped ones -> the caller's packed block
+            const size_t row = sizeof(float) * (size_t)key[stop];
+            for (int b = 0; b < B; b++)
+                Q3_HIP(hipMemcpy2DAsync((float*)out + offsets[mem[b]], row, y + (size_t)b * stop_C * ld + skip, sizeof(float) * (size_t)ld, row,
+                                        (size_t)stop_C, hipMemcpyDeviceToHost, v->s), -1);
+        }
         if (ns > 0) {
             if (voc_launch_incr_emit(v->s, y, ld, skip, (int)ns, s->d_off, want16 ? (void*)s->d_out16 : (void*)s->d_out, want16, B)) return -1;
             s->last_launches++;
@@ -866,7 +885,7 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
     }
     if (!p.groups.keys.empty()) {
         Q3_HIP(hipEventRecord(v->e1, v->s), -1);
-        if (total > 0)
+        if (total > 0 && !debug)
             if (voc_read_back(v, out, want16 ? (void*)s->d_out16 : (void*)s->d_out, (want16 ? sizeof(int16_t) : sizeof(float)) * (size_t)total))
                 return -1;
         Q3_HIP(hipStreamSynchronize(v->s), -1);
@@ -1000,6 +1019,16 @@ int voc_incr_push(void* s, int n, const int32_t* streams, const int64_t* codes, 
 int voc_incr_push_f32(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, const int32_t* finish,
                       float* out, int64_t out_capacity, int64_t* offsets) {
     return incr_push((VocIncr*)s, n, streams, codes, n_new, finish, false, out, out_capacity, offsets);
+}
+
+// test hook (like voc_debug_run, not in the header): a push whose walk ends after the first n_ops ops.  out takes, per entry, the
+// new columns of that activation, [C][cols] f32 packed at offsets[e] (offsets[n] = the total, in floats); *C its channels.  The
+// histories of the ops that ran move on exactly as in a real push, later ops' are not touched: a stream driven through this hook
+// is reset (voc_incr_reset) before it is driven through voc_incr_push*.
+int voc_debug_incr_push(void* s, int n, const int32_t* streams, const int64_t* codes, const int32_t* n_new, int n_ops, float* out,
+                        int64_t out_capacity, int64_t* offsets, int32_t* C) {
+    if (n_ops <= 0) return -1;
+    return incr_push((VocIncr*)s, n, streams, codes, n_new, nullptr, false, out, out_capacity, offsets, n_ops, C);
 }
 
 float voc_incr_last_ms(void* s) { return s ? ((VocIncr*)s)->last_ms : -1.f; }

@@ -14,7 +14,6 @@ assert it, voc_set_fill() moves the tile-height rule's workgroup target so that 
   E  an input above 65 504 on the split path: voc_decode returns the exact path's bits
   F  the ELU instantiations through the smallest encoder table the loader takes
 and a last test: the union of the instantiations reached equals voc_conv_ref.REACHABLE."""
-import ctypes
 import json
 import os
 import subprocess
@@ -28,6 +27,7 @@ from qwen3_tts_axera_russian_amd import hiplib
 from qwen3_tts_axera_russian_amd import weights as W
 from tests import voc_conv_ref as R
 from tests.enc_ref import enc_reference
+from tests.voc_gpu_common import grade as _grade, hooks as _hooks, reset as _reset, run as _run, variant as _variant
 
 pytestmark = pytest.mark.gpu
 
@@ -38,29 +38,10 @@ WORST = {}       # (family, arithmetic) -> (error / bound, case)
 PAIRS = [(n, d) for n, c in R.CASES.items() for d in c["data"]]
 
 
-def _hooks(lib):
-    lib.voc_debug_run.restype = ctypes.c_int
-    lib.voc_debug_run.argtypes = [ctypes.c_void_p, hiplib.i64p, ctypes.c_int, ctypes.c_int, hiplib.f32p, hiplib.i32p, hiplib.i32p]
-    lib.voc_debug_last_variant.restype = ctypes.c_char_p
-    lib.voc_debug_last_variant.argtypes = []
-    for n in ("voc_set_fill", "voc_set_narrow_k1"):
-        getattr(lib, n).restype = ctypes.c_int
-        getattr(lib, n).argtypes = [ctypes.c_int]
-    return lib
-
-
 @pytest.fixture(scope="module")
 def lib(gpu_lib):
     yield _hooks(gpu_lib)
     _reset(gpu_lib)
-
-
-def _reset(lib):
-    lib.voc_set_exact_fp32(0)
-    lib.voc_set_fused_units(1)
-    lib.voc_set_narrow_k1(1)
-    lib.voc_set_fill(-1)
-    lib.voc_set_max_workgroups(0)
 
 
 def _knobs(lib, c, arith):
@@ -69,10 +50,6 @@ def _knobs(lib, c, arith):
     lib.voc_set_narrow_k1(c["narrow"])
     lib.voc_set_fill(-1 if c["fill"] is None else c["fill"])
     lib.voc_set_max_workgroups(0)
-
-
-def _variant(lib):
-    return lib.voc_debug_last_variant().decode()
 
 
 def _note(variant, case):
@@ -87,25 +64,6 @@ def _worst(variant, arith, ratio, case):
     fam = variant.split("+")[-1].split("<")[0]
     if ratio > WORST.get((fam, arith), (-1.0, ""))[0]:
         WORST[(fam, arith)] = (ratio, case)
-
-
-def _run(lib, h, codes, n_ops, shape):
-    """the activation after n_ops ops for codes [B][T][16] -> [B][C][L] (shape: what the reference says it is)"""
-    codes = np.ascontiguousarray(codes, np.int64)
-    B = codes.shape[0]
-    out = np.full((B,) + tuple(shape[1:]), np.nan, np.float32)
-    C, L = np.zeros(1, np.int32), np.zeros(1, np.int32)
-    assert lib.voc_debug_run(h, codes.ctypes.data_as(hiplib.i64p), B, n_ops, hiplib.fptr(out), hiplib.iptr(C), hiplib.iptr(L)) == 0
-    assert (int(C[0]), int(L[0])) == tuple(shape[1:])
-    return out
-
-
-def _grade(y, ref, bound):
-    """-> the largest error / bound (0 / 0 counts as 0); asserts the bound element by element"""
-    err = np.abs(y.astype(np.float64) - ref)
-    assert np.all(np.isfinite(y))
-    ratio = float(np.max(np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err > 0, np.inf, 0.0))))
-    return ratio
 
 
 def _check_table(lib, path, c, t, n_ops, codes, data, name, arithmetics=("exact", "split"), want_override=None):

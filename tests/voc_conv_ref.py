@@ -118,6 +118,34 @@ def _front(tensors, codes, dtype):
     return np.ascontiguousarray(x.transpose(0, 2, 1)).astype(dtype)
 
 
+def conv_int(tensors, i, row, x, res):
+    """one VOP_CONV / VOP_CONVT row of an integer case on x (int64) -> (y, the sum of magnitudes each output accumulates)"""
+    p = f"voc.op{i}."
+    flags = int(row[5])
+    if flags & W.VF_SNAKE:
+        assert np.all(np.asarray(tensors[p + "alpha"]) == NO_SNAKE[0]) and np.all(np.asarray(tensors[p + "beta"]) == NO_SNAKE[1])
+    h = x
+    if flags & W.VF_GELU:
+        assert np.all((h == 0) | (np.abs(h) >= 16))
+        h = np.maximum(h, 0)
+    w = np.asarray(tensors[p + "weight"])
+    assert np.all(w == np.round(w))
+    w = w.astype(np.int64)
+    y = _conv_like(row, h, w)
+    mag = _conv_like(row, np.abs(h), np.abs(w))
+    if (p + "bias") in tensors:
+        b = np.asarray(tensors[p + "bias"])
+        assert np.all(b == np.round(b))
+        y = y + b.astype(np.int64)[None, :, None]
+        mag = mag + np.abs(b.astype(np.int64))[None, :, None]
+    if flags & W.VF_RES_ADD:
+        y = y + res
+        mag = mag + np.abs(res)
+    if flags & W.VF_CLAMP:
+        y = np.clip(y, -1, 1)
+    return y, mag
+
+
 def reference_int(tensors, codes, n_ops):
     """int64 evaluation of an integer case: identity Snake (NO_SNAKE), GELU only on inputs that are 0 or |v| >= 16 (where
     exact GELU is ReLU to the last bit of f32 and of float64's 0.5 x (1 + erf): erf(16 / sqrt 2) = 1 - 6e-58).
@@ -126,35 +154,57 @@ def reference_int(tensors, codes, n_ops):
     x = _front(tensors, codes, np.int64)
     res, peak = None, 0
     for i in range(1, n_ops):
-        row, p = prog[i], f"voc.op{i}."
+        row = prog[i]
         assert int(row[0]) in (W.VOP_CONV, W.VOP_CONVT)
-        flags = int(row[5])
-        if flags & W.VF_RES_SAVE:
+        if int(row[5]) & W.VF_RES_SAVE:
             res = x
-        if flags & W.VF_SNAKE:
-            assert np.all(np.asarray(tensors[p + "alpha"]) == NO_SNAKE[0]) and np.all(np.asarray(tensors[p + "beta"]) == NO_SNAKE[1])
-        h = x
-        if flags & W.VF_GELU:
-            assert np.all((h == 0) | (np.abs(h) >= 16))
-            h = np.maximum(h, 0)
-        w = np.asarray(tensors[p + "weight"])
-        assert np.all(w == np.round(w))
-        w = w.astype(np.int64)
-        y = _conv_like(row, h, w)
-        mag = _conv_like(row, np.abs(h), np.abs(w))
-        if (p + "bias") in tensors:
-            b = np.asarray(tensors[p + "bias"])
-            assert np.all(b == np.round(b))
-            y = y + b.astype(np.int64)[None, :, None]
-            mag = mag + np.abs(b.astype(np.int64))[None, :, None]
-        if flags & W.VF_RES_ADD:
-            y = y + res
-            mag = mag + np.abs(res)
-        if flags & W.VF_CLAMP:
-            y = np.clip(y, -1, 1)
+        x, mag = conv_int(tensors, i, row, x, res)
         peak = max(peak, int(mag.max()))
-        x = y
     return x, peak
+
+
+def conv_f64(tensors, i, row, x, ex, res, eres, arith):
+    """one VOP_CONV / VOP_CONVT row in float64 on x, whose device value is off by at most ex -> (y, the bound of the device's
+    error on y: the module docstring's, arith "exact" / "split"; None: as "exact", the Snake range not asserted)"""
+    p = f"voc.op{i}."
+    flags = int(row[5])
+    h, dh = x, ex
+    if flags & W.VF_SNAKE:
+        al, be = np.asarray(tensors[p + "alpha"], np.float64), np.asarray(tensors[p + "beta"], np.float64)
+        a = np.exp(al)[None, :, None]
+        ib = 1.0 / (np.exp(be)[None, :, None] + 1e-9)
+        h = snake64(x, al, be)
+        arg = np.abs(a * x) + a * ex
+        live = ib > 2.0 ** -100          # (an inv_beta that is 0 in f32 takes the sine out of the result)
+        assert arith is None or float((arg * live).max()) <= 16.0 * (1 + 2.0 ** -20), "Snake argument beyond the probed range"
+        dh = (1.0 + a * ib) * ex + ib * (SIN2_ERR + 3 * U * arg + 3 * U) * live + U * np.abs(h)
+    if flags & W.VF_GELU:
+        g = gelu64(h)
+        dh = GELU_LIP * dh + GELU_ERR * np.maximum(1.0, np.abs(h) / 8.0)
+        h = g
+    w = np.asarray(tensors[p + "weight"], np.float64)
+    y = _conv_like(row, h, w)
+    habs = np.abs(h) + dh
+    Sw = _conv_like(row, habs, np.abs(w))
+    S = Sw.copy()
+    e = _conv_like(row, dh, np.abs(w))
+    if (p + "bias") in tensors:
+        b = np.asarray(tensors[p + "bias"], np.float64)[None, :, None]
+        y = y + b
+        S = S + np.abs(b)
+    if flags & W.VF_RES_ADD:
+        y = y + res
+        S = S + np.abs(res) + eres
+        e = e + eres
+    taps = int(row[3]) if int(row[0]) == W.VOP_CONV else int(row[3]) // int(row[4])
+    n = int(row[1]) * taps
+    e = e + (2 * n + 4) * U * S
+    if arith == "split" and int(row[1]) % 16 == 0:
+        ones_h, ones_w = np.ones_like(habs), np.ones_like(w)
+        e = e + 3 * 2.0 ** -22 * Sw + 2.0 ** -36 * (_conv_like(row, ones_h, np.abs(w)) + _conv_like(row, habs, ones_w))
+    if flags & W.VF_CLAMP:
+        y = np.clip(y, -1.0, 1.0)
+    return y, e
 
 
 def reference_f64(tensors, codes, n_ops, arith=None):
@@ -165,48 +215,11 @@ def reference_f64(tensors, codes, n_ops, arith=None):
     ex = np.zeros_like(x)
     res = eres = None
     for i in range(1, n_ops):
-        row, p = prog[i], f"voc.op{i}."
+        row = prog[i]
         assert int(row[0]) in (W.VOP_CONV, W.VOP_CONVT)
-        flags = int(row[5])
-        if flags & W.VF_RES_SAVE:
+        if int(row[5]) & W.VF_RES_SAVE:
             res, eres = x, ex
-        h, dh = x, ex
-        if flags & W.VF_SNAKE:
-            al, be = np.asarray(tensors[p + "alpha"], np.float64), np.asarray(tensors[p + "beta"], np.float64)
-            a = np.exp(al)[None, :, None]
-            ib = 1.0 / (np.exp(be)[None, :, None] + 1e-9)
-            h = snake64(x, al, be)
-            arg = np.abs(a * x) + a * ex
-            live = ib > 2.0 ** -100          # (an inv_beta that is 0 in f32 takes the sine out of the result)
-            assert arith is None or float((arg * live).max()) <= 16.0 * (1 + 2.0 ** -20), "Snake argument beyond the probed range"
-            dh = (1.0 + a * ib) * ex + ib * (SIN2_ERR + 3 * U * arg + 3 * U) * live + U * np.abs(h)
-        if flags & W.VF_GELU:
-            g = gelu64(h)
-            dh = GELU_LIP * dh + GELU_ERR * np.maximum(1.0, np.abs(h) / 8.0)
-            h = g
-        w = np.asarray(tensors[p + "weight"], np.float64)
-        y = _conv_like(row, h, w)
-        habs = np.abs(h) + dh
-        Sw = _conv_like(row, habs, np.abs(w))
-        S = Sw.copy()
-        e = _conv_like(row, dh, np.abs(w))
-        if (p + "bias") in tensors:
-            b = np.asarray(tensors[p + "bias"], np.float64)[None, :, None]
-            y = y + b
-            S = S + np.abs(b)
-        if flags & W.VF_RES_ADD:
-            y = y + res
-            S = S + np.abs(res) + eres
-            e = e + eres
-        taps = int(row[3]) if int(row[0]) == W.VOP_CONV else int(row[3]) // int(row[4])
-        n = int(row[1]) * taps
-        e = e + (2 * n + 4) * U * S
-        if arith == "split" and int(row[1]) % 16 == 0:
-            ones_h, ones_w = np.ones_like(habs), np.ones_like(w)
-            e = e + 3 * 2.0 ** -22 * Sw + 2.0 ** -36 * (_conv_like(row, ones_h, np.abs(w)) + _conv_like(row, habs, ones_w))
-        if flags & W.VF_CLAMP:
-            y = np.clip(y, -1.0, 1.0)
-        x, ex = y, e
+        x, ex = conv_f64(tensors, i, row, x, ex, res, eres, arith)
     return (x, ex) if arith else x
 
 
