@@ -133,7 +133,8 @@ typedef struct q3e_slot_params {
     int32_t cp_top_k;
     uint64_t seed;          /* the request's seed ... */
     int32_t utt;            /* ... and the utterance's index in its request: the draw stream is mix(seed, utt) */
-    int32_t reserved;       /* bit 0: a text slot (below); the other bits 0 */
+    int32_t reserved;       /* bit 0: a text slot (below); bit 1, valid only with bit 0: a text slot that may continue a codec
+                             * prompt (q3e_admit_prompted); the other bits 0 */
 } q3e_slot_params;
 
 int q3e_open(void* e, int B, int ignore_eos);
@@ -203,8 +204,22 @@ int q3e_prefix_stats(void* e, int64_t* out /*[6]*/);
  *   - positions: the first frame step runs at position n_rows + T.
  * Validation is q3e_admit's, before anything changes, with n_rows + T where it has n_rows (the rows one prefill pass
  * takes, and n_rows + T + max_frames <= n_ctx), and: T >= 0, column 0 of every prompt frame in 0..2047 (an audio id),
- * columns 1..15 inside the code predictor's vocabulary, no prompt on a text slot (`reserved` bit 0).  A failed call leaves
- * the slots and the cache as they were.  prompt_frames == NULL, or T = 0 for an utterance: exactly q3e_admit_keyed.
+ * columns 1..15 inside the code predictor's vocabulary, no prompt on a text slot that did not ask for one (`reserved`
+ * == 1; == 3 below).  A failed call leaves the slots and the cache as they were.  prompt_frames == NULL, or T = 0 for an
+ * utterance: exactly q3e_admit_keyed.
+ *
+ * Text slots that continue a prompt (streamed text in a cloned voice): `reserved` == 3 (bits 0 and 1) admits a text slot
+ * WITH its T prompt frames; == 2 is refused, == 3 without q3e_text_reserve is refused like any text slot, == 3 with T = 0
+ * is exactly == 1.  Rows, KV, frame-0 state, ring, positions, validation and the cache are those of an ordinary prompted
+ * slot (the prompt's rows add tts_pad), and the slot's text is counted by the GENERATED frame: pushed row i is row i of
+ * the slot's reservation and stands where tts_pad would in the feedback of generated frame i -- the frame row i of the
+ * slot's column of the codes array holds -- so the reservation keeps its size (rows <= max_frames) and q3e_push_text,
+ * q3e_text_state, q3e_text_held, q3e_get_done, q3e_get_codes and q3e_release keep their contracts.  Starved, stalled and
+ * held (q3e_text_hold) are judged with g = the frames generated: held when g >= 1 and g >= the rows pushed, a stall of
+ * the batch at g == 0 without a row.  EOS is masked until the final push; from then on n_text = n_text_total and the
+ * rules see T + g emitted frames, as for an ordinary prompted slot.  The layout (a streaming prefix, then the prompt, then
+ * text rows riding on the generated frames) is, like both of its halves, a recollection: parity on real weights is NOT
+ * pinned, the arithmetic is.
  *
  * Prefix cache: an entry of a prompted utterance holds its n_rows + T rows and the last prompt row's residual state, and
  * n_rows + T is the length the index compares (and compares with the pool's max_rows: a longer utterance is a plain

@@ -90,10 +90,24 @@ encode_reference_audio --output_dir writes it: ref_codec_tokens.npy and, if ther
 request's "voice": "NAME" stands for the same two keys.  With "vocoder": "incremental" the prompt's frames are pushed into
 the utterance's stream first and their voc_incr_samples(T) samples dropped, so the audio continues the prompt seamlessly;
 the chunk walk (the default) decodes the generated frames on their own.  A prompt in any other mode, together with
-"text_stream", an unknown voice, malformed codes, or one that does not fit n_ctx is answered with -2 for that request alone,
+"text_stream" (without `--text_voice`, below), an unknown voice, malformed codes, or one that does not fit n_ctx is answered with -2 for that request alone,
 before any of it is queued.  Prompt text in front of the target text is a recollection of the model's in-context mode:
 parity with real weights is not pinned.  With `--prefix_cache` the key of a prompted utterance is of the kind b"prompt" and
 digests the ids and the prompt's codes.
+
+`--text_voice` (with `--concurrent`): a "text_stream" request may carry a codec prompt -- "voice", or "prompt_codes" with an
+optional "prompt_token_ids" / "prompt_text" -- and its audio then continues the prompt while its text still arrives: streamed
+text in a cloned voice.  The checks are the codec prompt's, and 8 + the prompt text's tokens + T + max_tokens must fit n_ctx.
+The utterance runs in a text slot that continues a prompt (q3e_slot_params.reserved == 3): its prefix is rows 0..6 of the
+streaming prefix, one `text + codec_pad` row per token of the prompt's text, then the first token + codec_bos
+(build_prefix_stream(first, head)); the prompt's T frames follow as they do for any prompted utterance; and row i of the
+streamed text rides on GENERATED frame i.  Its text length for the EOS heuristics counts the prompt's text, as the unstreamed
+prompted request of the same texts does, and its prefix key is prefix_key(b"stream", prompt text ids + first token, codes).
+The vocoder follows the streamed reply of a prompted request: "incremental" warms the utterance's stream up with the prompt's
+frames and drops their samples, the chunk walk decodes the generated frames alone.  `--text_hold`, `--text_wait_ms` and
+`--prefix_cache` work as they do for any text-stream request; the wire protocol has no new record.  Like both of its halves
+the layout is a recollection of the model's in-context mode: parity with real weights is not pinned.  Without the flag such a
+request is answered -2, as before.
 
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
@@ -154,7 +168,7 @@ class BatchSynthesisServer:
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
                  cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=0,
-                 prefix_cache_rows=64, voices=None):
+                 prefix_cache_rows=64, voices=None, text_voice=False):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens = socket_path, max_batch, max_tokens
@@ -179,6 +193,9 @@ class BatchSynthesisServer:
         if voices and not concurrent:
             raise ValueError("--voice names codec prompts of the shared frame loop's admissions: it needs --concurrent")
         self.voices = {name: load_voice(d) for name, d in dict(voices or {}).items()}   # name -> (codes [T][16], text or None)
+        if text_voice and not concurrent:
+            raise ValueError("--text_voice lets text slots of the shared frame loop continue a codec prompt: it needs --concurrent")
+        self.text_voice = bool(text_voice)
         self.sched = None
         # utterances one request may queue (the server is single-threaded: an unbounded request holds it indefinitely)
         self.max_request = int(max_request) if max_request else 8 * max_batch
@@ -429,7 +446,7 @@ class BatchSynthesisServer:
         request_vocoder_arithmetic(msg)      # (checks "vocoder" too)
         base = request_slot_params(msg, self.defaults, self.max_tokens)
         if msg.get("text_stream"):
-            if request_has_prompt(msg):
+            if request_has_prompt(msg) and not getattr(self, "text_voice", False):
                 raise ValueError('a codec prompt does not combine with "text_stream"')
             return [self._prepare_text_stream(msg, base)]
         ids = self._token_ids(msg)
@@ -453,7 +470,7 @@ class BatchSynthesisServer:
         """A request's codec prompt -> (one [T][16] int32 array per utterance, the prompt text's token ids): from
         "prompt_codes" and "prompt_token_ids" / "prompt_text", or from the "voice" that names them; raises ValueError on
         anything malformed."""
-        if msg.get("text_stream"):
+        if msg.get("text_stream") and not getattr(self, "text_voice", False):
             raise ValueError('a codec prompt does not combine with "text_stream"')
         codes, text, head = msg.get("prompt_codes"), msg.get("prompt_text"), msg.get("prompt_token_ids")
         if msg.get("voice") is not None:
@@ -480,7 +497,10 @@ class BatchSynthesisServer:
 
     def _prepare_text_stream(self, msg, base):
         """A "text_stream" request -> its one utterance as (0, streaming prefix, 0, SlotParams of a text slot, TextFeed), a
-        QueuedUtterance whose prefix key covers the first token alone."""
+        QueuedUtterance whose prefix key covers the first token alone.  With a codec prompt (--text_voice): the prefix holds
+        the prompt's text in front of the first token (build_prefix_stream(first, head)), the utterance carries the prompt,
+        its SlotParams ask for text after a prompt, its text length counts the prompt's text, and the key covers the prompt's
+        text, the first token and the prompt's codes."""
         from .frontend import text_stream_rows
         if msg.get("stream") is not True:
             raise ValueError('"text_stream" needs "stream": true')
@@ -498,13 +518,24 @@ class BatchSynthesisServer:
             first = encoder.feed(pieces[0])
         if not first:
             raise ValueError('the first piece of a "text_stream" request must give at least one token')
+        prompt, head = None, []
+        if request_has_prompt(msg):
+            prompts, head = self._request_prompts(msg, 1)
+            prompt = prompts[0]
+            rows = 8 + len(head) + len(prompt)
+            if rows + base.max_frames > self.n_ctx or rows > max(self.max_batch, 2048):
+                raise ValueError("prefix + codec prompt + max_tokens exceed n_ctx (or the rows of one prefill pass)")
         if 8 + base.max_frames > self.n_ctx:
             raise ValueError("prefix + max_tokens exceed n_ctx")
         tokeniser = self.tokenizer
         feed = TextFeed(lambda ids, final=False: text_stream_rows(self.front, ids, final), encoder,
-                        None if tokeniser is None else tokeniser.incremental, first[1:], 1)
-        params = dataclasses.replace(base, utt=0, text_stream=True)
-        return QueuedUtterance((0, self.front.build_prefix_stream(first[0]), 0, params, feed), prefix_key(b"stream", first[:1]))
+                        None if tokeniser is None else tokeniser.incremental, first[1:], 1 + len(head))
+        if prompt is None:
+            params = dataclasses.replace(base, utt=0, text_stream=True)
+            return QueuedUtterance((0, self.front.build_prefix_stream(first[0]), 0, params, feed), prefix_key(b"stream", first[:1]))
+        params = dataclasses.replace(base, utt=0, text_stream=True, text_after_prompt=True)
+        return QueuedUtterance((0, self.front.build_prefix_stream(first[0], head), 0, params, feed),
+                               prefix_key(b"stream", head + first[:1], prompt), prompt if len(prompt) else None)
 
     def _prefix_note(self):
         """The prefix cache's counters so far, for the per-request line ("" without --prefix_cache)."""
@@ -1300,11 +1331,12 @@ def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="r
 
 
 def synthesize_text_stream(socket_path, pieces, language="russian", max_tokens=None, vocoder=None, vocoder_arithmetic=None,
-                           **sampling):
+                           voice=None, prompt_codes=None, prompt_token_ids=None, prompt_text=None, **sampling):
     """Client side of a "text_stream" request (--concurrent servers): `pieces` is an iterable of the text's pieces as they
     become available -- str / bytes (UTF-8, cut anywhere; the server tokenises) or sequences of token ids.  The first piece
     goes out with the request (it must give at least one token), the others as text records from a sender thread that walks
-    the iterable, then the end-of-text record.  Yields the records of synthesize_batch_stream, utterance 0."""
+    the iterable, then the end-of-text record.  Yields the records of synthesize_batch_stream, utterance 0.  voice, or
+    prompt_codes with prompt_token_ids / prompt_text: the codec prompt the utterance continues (--text_voice servers)."""
     it = iter(pieces)
     first = next(it)
     as_text = isinstance(first, (str, bytes, bytearray))
@@ -1327,7 +1359,8 @@ def synthesize_text_stream(socket_path, pieces, language="russian", max_tokens=N
     try:
         s.sendall(pack_batch_request([first] if as_text else None, None if as_text else [list(first)], language, max_tokens,
                                      stream=True, vocoder=vocoder, vocoder_arithmetic=vocoder_arithmetic, text_stream=True,
-                                     **sampling))
+                                     prompt_codes=prompt_codes, prompt_token_ids=prompt_token_ids, prompt_text=prompt_text,
+                                     voice=voice, **sampling))
         th.start()
         while True:
             rec = read_stream_record(s)
@@ -1387,6 +1420,9 @@ def main():
     ap.add_argument("--voice", action="append", default=[], metavar="NAME=DIR",
                     help="--concurrent: a codec prompt requests may name with \"voice\": \"NAME\"; DIR as "
                          "encode_reference_audio --output_dir writes it (repeatable)")
+    ap.add_argument("--text_voice", action="store_true",
+                    help="--concurrent: a text-stream request may carry a codec prompt (\"voice\" / \"prompt_codes\"): streamed "
+                         "text in the prompt's voice")
     a = ap.parse_args()
     if any("=" not in v or not v.split("=", 1)[0] for v in a.voice):
         ap.error("--voice takes NAME=DIR")
@@ -1395,7 +1431,7 @@ def main():
                                max_queue=a.max_queue, top_p=a.top_p, cp_top_k=a.cp_top_k, check_every=a.check_every,
                                send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms, text_hold=a.text_hold,
                                prefix_cache=a.prefix_cache, prefix_cache_rows=a.prefix_cache_rows,
-                               voices=dict(v.split("=", 1) for v in a.voice))
+                               voices=dict(v.split("=", 1) for v in a.voice), text_voice=a.text_voice)
     try:
         srv.serve()
     finally:

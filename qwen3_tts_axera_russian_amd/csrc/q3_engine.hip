@@ -863,16 +863,22 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
         sp[u].c_top_k = p.cp_top_k;
         sp[u].seed = mix_seed(p.seed, (unsigned long long)(uint32_t)p.utt + 1ull, 0x9E3779B97F4A7C15ull);   // mix(seed, utt)
         sp[u].no_row = 1;
+        if ((p.reserved & 2) && !(p.reserved & 1)) {
+            Q3_LOG("q3e_admit: utterance %d: bit 1 of reserved (text after a codec prompt) needs bit 0 (a text slot)", u);
+            return -1;
+        }
         if (p.reserved & 1) {
             if (!e->d_text) {
                 Q3_LOG("q3e_admit: utterance %d is a text slot, but no text rows are reserved (q3e_text_reserve)", u);
                 return -1;
             }
-            if (n_prompt[u]) {
+            if (n_prompt[u] && !(p.reserved & 2)) {
                 Q3_LOG("q3e_admit: utterance %d: a text slot takes no codec prompt", u);
                 return -1;
             }
             sp[u].flags = 3;   // a text slot; EOS masked until the final push
+            // its rows are counted from the first generated frame: the sampler's hold test takes the prompt off n_past
+            sp[u].prompt = n_prompt[u];
         }
     }
     Q3_HIP(hipStreamSynchronize(e->s), -1);

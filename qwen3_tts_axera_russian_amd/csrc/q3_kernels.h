@@ -149,6 +149,8 @@ struct SlotParams {
     unsigned long long seed = 0;   // the row's draw stream
     int no_row = 1;                // 1: the draw key is (seed, frame, group), without the row index
     int flags = 0;                 // bit 0: a text slot (its feedback adds text_rows, see CpArgmaxArgs); bit 1: its EOS is masked
+    int prompt = 0;                // codec-prompt frames n_past started at (q3e_admit_prompted): a text slot's hold test counts
+                                   // the frames it generated, n_past - prompt (n_frames and the text rows already do)
 };
 
 // Talker sampling (llamacpp_talker_server.py:163-206, greedy form).
@@ -183,8 +185,9 @@ struct TalkerSampleArgs {
     // slots[r]; the dynamic LDS is then sized for the sort path whatever the row asks for
     const SlotParams* slots = nullptr;
     // per-slot mode with held text slots (q3e_text_hold; both null: none).  A row is HELD in this step when its slot is a
-    // text slot whose text has not ended (flags 3), it has not ended, and 1 <= n_past < its budget while n_past >=
-    // text_avail[r]: its next frame has no text row yet.  The workgroup of a held row sets held[r] and returns before it
+    // text slot whose text has not ended (flags 3), it has not ended, n_past < its budget, and with g = n_past -
+    // slots[r].prompt, the frames it generated, g >= 1 and g >= text_avail[r]: its next frame has no text row yet, and it
+    // has a frame of its own to repeat.  The workgroup of a held row sets held[r] and returns before it
     // reads a logit: no counter, code, ring entry or position of the row changes.  Every other row clears held[r].
     const int* text_avail = nullptr;    // [R_total] rows pushed per slot (written by the host between launches)
     int* held = nullptr;                // [R_total] 1: the row is held in this step (read by the frame's cp_argmax launches)

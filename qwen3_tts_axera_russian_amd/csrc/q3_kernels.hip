@@ -2098,9 +2098,11 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
         slot_flags = sp.flags;
         if (a.text_avail) {
             // held text slots (q3e_text_hold): the row's next frame has no text row yet.  Scalar values only, so the
-            // whole workgroup leaves together, before the first barrier and before it has read a logit.
+            // whole workgroup leaves together, before the first barrier and before it has read a logit.  Rows are counted
+            // by the frames the slot generated: a codec prompt's frames (sp.prompt of n_past) need no row.
             const int avail = uniform_load(a.text_avail + r);
-            const bool held = (slot_flags & 3) == 3 && !was_done && np >= 1 && np >= avail && np < max_frames;
+            const int gen = np - sp.prompt;
+            const bool held = (slot_flags & 3) == 3 && !was_done && gen >= 1 && gen >= avail && np < max_frames;
             if (threadIdx.x == 0) a.held[r] = held ? 1 : 0;
             if (held) return;
         }

@@ -26,6 +26,8 @@ class SlotParams:
     seed: int = 0
     utt: int = 0
     text_stream: bool = False      # a text slot: its text arrives row by row (FrameEngine.push_text); n_text is ignored
+    text_after_prompt: bool = False    # a text slot that may continue a codec prompt (admit(prompts=...)): its text rows
+                                       # are counted from its first generated frame; needs text_stream
 
     def check(self, max_frames):
         """Raises ValueError unless every field is in range for an engine of `max_frames` frames per utterance."""
@@ -46,6 +48,8 @@ class SlotParams:
             raise ValueError(f"utt must be in 0..2**31-1 (got {self.utt})")
         if not (-(1 << 31) <= self.top_k < 1 << 31 and -(1 << 31) <= self.cp_top_k < 1 << 31):
             raise ValueError("top_k / cp_top_k must fit in an i32")
+        if self.text_after_prompt and not self.text_stream:
+            raise ValueError("text_after_prompt needs text_stream (a codec prompt under streamed text is a text slot's)")
 
 
 class FrameEngine:
@@ -218,6 +222,7 @@ class FrameEngine:
         prompts (q3e_admit_prompted): one [T][16] int array of codec ids per utterance, or None for an utterance without
         one -- frames the utterance counts as already emitted: they are prefilled behind its prefix, the sampler's history
         starts with them, and codes() / done() / max_frames count the generated frames only.  A key must digest the prompt.
+        A text slot takes a prompt only with SlotParams.text_after_prompt; its pushed row i then rides on generated frame i.
         -> None, or with keys the hit flags (bool [n])."""
         slots = np.ascontiguousarray(np.asarray(slots, np.int32))
         assert len(slots) == len(prefixes) == len(n_text) == len(params) and len(slots) > 0
@@ -228,7 +233,8 @@ class FrameEngine:
         nt = np.ascontiguousarray(np.asarray(n_text, np.int32))
         arr = (hiplib.SlotParamsC * len(params))(*[
             hiplib.SlotParamsC(int(p.max_frames), float(p.temperature), int(p.top_k), float(p.top_p), float(p.cp_temperature),
-                               int(p.cp_top_k), int(p.seed), int(p.utt), 1 if p.text_stream else 0) for p in params])
+                               int(p.cp_top_k), int(p.seed), int(p.utt),
+                               (1 if p.text_stream else 0) | (2 if p.text_after_prompt else 0)) for p in params])
         if keys is None and prompts is None:
             rc = self._lib.q3e_admit(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
                                      hiplib.iptr(nt), arr)

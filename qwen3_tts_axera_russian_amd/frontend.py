@@ -41,15 +41,22 @@ class TextFrontEnd:
         out[8 + n] = self.tts_pad_embed + cod[c.codec_bos]
         return out
 
-    def build_prefix_stream(self, first_token_id):
+    def build_prefix_stream(self, first_token_id, head=()):
         """The 8-row prefix of a text-stream utterance (tfe_build_prefix_stream): rows 0..6 of build_prefix, then the first
-        text token + codec_bos.  The rest of the text follows frame by frame (text_stream_rows)."""
+        text token + codec_bos.  The rest of the text follows frame by frame (text_stream_rows).
+        head (token ids; a text-stream utterance that continues a codec prompt: the text the prompt speaks): one
+        `text + codec_pad` row per head token stands between row 6 and the last row, as rows 7.. of build_prefix(head)
+        do -- 8 + len(head) rows.  Like the other streamed layouts this is a recollection of the model's in-context mode:
+        parity on real weights is not pinned, the arithmetic is.  Without head: today's 8 rows, bit for bit."""
         c, cod = self.cfg, self.codec
-        out = np.empty((8, cod.shape[1]), np.float32)
+        n = len(head)
+        out = np.empty((8 + n, cod.shape[1]), np.float32)
         out[0:3] = self.embed_text([c.im_start, c.assistant, c.newline])
         out[3:6] = self.tts_pad_embed + cod[[c.codec_nothink, c.codec_think_bos, c.codec_think_eos]]
         out[6] = self.tts_bos_embed + cod[c.codec_pad]
-        out[7] = self.embed_text([int(first_token_id)])[0] + cod[c.codec_bos]
+        if n:
+            out[7:7 + n] = self.embed_text(head) + cod[c.codec_pad]
+        out[7 + n] = self.embed_text([int(first_token_id)])[0] + cod[c.codec_bos]
         return out
 
 
@@ -99,12 +106,16 @@ class DeviceTextFrontEnd:
             raise RuntimeError(f"tfe_build_prefix failed: {n}")
         return out
 
-    def build_prefix_stream(self, first_token_id):
+    def build_prefix_stream(self, first_token_id, head=()):
+        """TextFrontEnd.build_prefix_stream: with head, rows 0..6+len(head) of tfe_build_prefix(head), then the last row of
+        tfe_build_prefix_stream(first_token_id)."""
         out = np.empty((8, self.hidden), np.float32)
         n = self._lib.tfe_build_prefix_stream(self.h, int(first_token_id), self._hl.iptr(self._special), self._hl.fptr(out))
         if n != 8:
             raise RuntimeError(f"tfe_build_prefix_stream failed: {n}")
-        return out
+        if len(head) == 0:
+            return out
+        return np.concatenate([self.build_prefix(head)[:7 + len(head)], out[7:]], axis=0)
 
     def destroy(self):
         if self.h:

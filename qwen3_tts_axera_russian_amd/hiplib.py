@@ -28,7 +28,8 @@ class KernelSlotParamsC(ctypes.Structure):
     """q3::SlotParams (csrc/q3_kernels.h): the entry the sampling kernels read per row; test hooks only."""
     _fields_ = [("max_frames", ctypes.c_int32), ("t_temp", ctypes.c_float), ("t_top_k", ctypes.c_int32),
                 ("t_top_p", ctypes.c_float), ("c_temp", ctypes.c_float), ("c_top_k", ctypes.c_int32),
-                ("seed", ctypes.c_uint64), ("no_row", ctypes.c_int32), ("flags", ctypes.c_int32)]
+                ("seed", ctypes.c_uint64), ("no_row", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("prompt", ctypes.c_int32)]
 
 
 def _sig(lib, name, restype, argtypes):

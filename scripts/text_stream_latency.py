@@ -26,6 +26,19 @@ record, the frame steps text slots were held for and the checks that ran no fram
 still computes, so the frame loop runs steps that emit nothing for it.
 
     python scripts/text_stream_latency.py --bystander --out profiles/text_hold_bystander.json
+
+--voice DIR (as encode_reference_audio --output_dir writes it) or --prompt_frames T (T synthetic prompt frames): streamed
+text in a cloned voice.  One server with --text_voice, three clients alternating, --repeats times after one untimed pass:
+
+  voiced_streamed  the streamed leg above, carrying the codec prompt (a text slot that continues a prompt);
+  streamed         the same text stream without a voice;
+  voiced_whole     the whole leg above, carrying the codec prompt (an ordinary prompted request once the text is complete).
+
+Reported per leg: time from t0 to the first audio record and to the end of the reply, frames.  No target: the table states
+what was measured.  --frame_step FILE (JSON lines of scripts/slot_step_ms.py, labelled "parent" and "change", one line per
+process) adds the frame-step comparison to the .md written beside --out.
+
+    python scripts/text_stream_latency.py --prompt_frames 75 --out profiles/text_voice_latency.json
 """
 from __future__ import annotations
 
@@ -56,7 +69,7 @@ def tiny_packs(cache):
     return main, voc, cfg
 
 
-def one(sock, ids, rate, max_tokens, vocoder, streamed):
+def one(sock, ids, rate, max_tokens, vocoder, streamed, **prompt):
     from qwen3_tts_axera_russian_amd import batch_server as bs
     t0 = time.perf_counter()
 
@@ -65,10 +78,10 @@ def one(sock, ids, rate, max_tokens, vocoder, streamed):
             time.sleep(max(0.0, t0 + i / rate - time.perf_counter()))
             yield [t]
     if streamed:
-        recs = bs.synthesize_text_stream(sock, pieces(), max_tokens=max_tokens, vocoder=vocoder)
+        recs = bs.synthesize_text_stream(sock, pieces(), max_tokens=max_tokens, vocoder=vocoder, **prompt)
     else:
         time.sleep(max(0.0, t0 + (len(ids) - 1) / rate - time.perf_counter()))
-        recs = bs.synthesize_batch_stream(sock, token_ids=[ids], max_tokens=max_tokens, vocoder=vocoder)
+        recs = bs.synthesize_batch_stream(sock, token_ids=[ids], max_tokens=max_tokens, vocoder=vocoder, **prompt)
     first, frames, samples = None, 0, 0
     for rec in recs:
         if rec[0] == "audio":
@@ -158,6 +171,104 @@ def bystander(a, main_pack, voc_pack, cfg, ids):
             f.write("\n")
 
 
+def frame_step_table(path):
+    """JSON lines of scripts/slot_step_ms.py (one per process, labelled "parent" / "change") -> (summary dict, .md lines)."""
+    rows = [json.loads(ln) for ln in open(path) if ln.strip().startswith("{")]
+    by = {}
+    for r in rows:
+        by.setdefault(r["label"], []).append(r["ms_per_step_median"])
+    out = {k: {"processes": len(v), "ms_per_step_median_of_medians": round(float(np.median(v)), 4), "min": min(v), "max": max(v),
+               "medians": v} for k, v in by.items()}
+    md = ["## Frame step of an engine with a text reservation", "",
+          "`scripts/slot_step_ms.py --batch %d --reserve %d%s`: q3e_last_run_ms per step, every slot an ordinary utterance (no text "
+          "slot live), one process per figure, the two libraries alternating in one session; with q3e_text_hold, and without it "
+          "(no hold)." %
+          (rows[0]["batch"], rows[0]["reserve"], " [--hold]"), "",
+          "| library | processes | median of medians (ms/step) | min | max |", "|---|---|---|---|---|"]
+    for k, v in out.items():
+        md.append("| %s | %d | %.4f | %.4f | %.4f |" % (k, v["processes"], v["ms_per_step_median_of_medians"], v["min"], v["max"]))
+    for suffix in sorted({k[len("parent"):] for k in by if k.startswith("parent")}):   # ("", " (no hold)", ..)
+        if "change" + suffix not in by:
+            continue
+        par, chg = out["parent" + suffix], out["change" + suffix]
+        spread = par["max"] - par["min"]
+        diff = chg["ms_per_step_median_of_medians"] - par["ms_per_step_median_of_medians"]
+        chg["parent_spread_ms"], chg["minus_parent_ms"] = round(spread, 4), round(diff, 4)
+        md += ["", "parent%s: its own spread over its processes (max - min) is %.4f ms; the change's median differs from the parent's "
+               "by %+.4f ms: %s." % (suffix, spread, diff, "inside that spread" if abs(diff) <= spread else
+                                     "OUTSIDE that spread -- the sampler reads two more words of the row's SlotParams entry")]
+    return out, md
+
+
+def voiced(a, main_pack, voc_pack, cfg, ids):
+    """--voice / --prompt_frames: first audio of a voiced text stream, of the same stream unvoiced, and of the voiced request
+    with the whole text up front."""
+    from qwen3_tts_axera_russian_amd import batch_server as bs
+    head = []
+    if a.voice:
+        codes, text = bs.load_voice(a.voice)
+        codes = np.asarray(codes, np.int32)
+        if text:
+            print("[text_stream_latency] the voice's text is not used (no tokenizer here): the prompt has no text", file=sys.stderr)
+    else:
+        codes = np.random.default_rng(a.seed + 1).integers(0, 2048, size=(a.prompt_frames, 16)).astype(np.int32)
+    T = len(codes)
+    sock = os.path.join(a.cache, f"tsl_{os.getpid()}_v.sock")
+    srv = bs.BatchSynthesisServer(main_pack, voc_pack, sock, max_batch=a.max_batch, n_ctx=a.max_tokens + 64 + T, max_tokens=a.max_tokens,
+                                  temperature=0.0, cp_temperature=0.0, install_signal_handlers=False, concurrent=True,
+                                  text_wait_ms=a.text_wait_ms, text_voice=True)
+    th = threading.Thread(target=srv.serve, daemon=True)
+    th.start()
+    while not (os.path.exists(sock) and srv.sched is not None):
+        time.sleep(0.05)
+    prompt = dict(prompt_codes=codes, prompt_token_ids=head or None)
+    plan = {"voiced_streamed": (True, prompt), "streamed": (True, {}), "voiced_whole": (False, prompt)}
+    legs = {k: [] for k in plan}
+    try:
+        for rep in range(a.repeats + 1):
+            for leg, (streamed, kw) in plan.items():
+                r = one(sock, ids, a.rate, a.max_tokens, a.vocoder, streamed, **kw)
+                if rep:
+                    legs[leg].append(r)
+                print(f"[text_stream_latency] {'warm-up' if not rep else rep} {leg}: {r}", file=sys.stderr, flush=True)
+    finally:
+        srv._running = False
+        th.join(timeout=60)
+        srv.close()
+    med = lambda leg, k: float(np.median([r[k] for r in legs[leg]]))
+    out = {"what": "time from the first text token to the first audio record: a text stream in a cloned voice, the same stream "
+                   "without a voice, and the voiced request once the whole text exists",
+           "packs": "tiny (2 + 2 layers)" if a.tiny else "synthetic Qwen3-TTS-0.6B architecture", "rate_tokens_per_s": a.rate,
+           "tokens": a.tokens, "text_ready_ms": round(1e3 * (a.tokens - 1) / a.rate, 1), "prompt_frames": T,
+           "prompt": a.voice or "synthetic", "max_tokens": a.max_tokens, "vocoder": a.vocoder, "max_batch": a.max_batch,
+           "check_every": srv.check_every, "repeats": a.repeats, "runs": legs,
+           "median": {leg: {k: med(leg, k) for k in ("first_audio_ms", "done_ms", "frames")} for leg in legs}}
+    md = ["# Streamed text in a cloned voice: time to first audio", "",
+          "`scripts/text_stream_latency.py %s`, one run on one MI355X: %s packs, %d text tokens at %g tokens/s (the whole text exists "
+          "after %.0f ms), a codec prompt of %d frames (%s), vocoder %s, %d slots, %d timed repeats after one untimed pass.  Medians; "
+          "no target is set." % (" ".join(sys.argv[1:]), out["packs"], a.tokens, a.rate, out["text_ready_ms"], T, out["prompt"], a.vocoder,
+                                 a.max_batch, a.repeats), "",
+          "| leg | first audio (ms) | reply done (ms) | frames |", "|---|---|---|---|"]
+    for leg in plan:
+        m = out["median"][leg]
+        md.append("| %s | %.1f | %.1f | %d |" % (leg, m["first_audio_ms"], m["done_ms"], m["frames"]))
+    md += ["", "voiced_streamed: a \"text_stream\" request with the prompt (--text_voice); streamed: the same without a prompt; "
+           "voiced_whole: an ordinary streamed request with the prompt, sent once the last token exists.  The synthetic weights say "
+           "nothing about how the audio sounds; the layout is a recollection of the model's in-context mode (DESIGN.md section 11)."
+           "  The voiced legs prefill the prompt's frames behind the prefix and, with the incremental vocoder, push them through the utterance's stream before the first generated frame (their samples are dropped): that work is what separates their first audio from the unvoiced stream's.  The legs end at different frame counts because the EOS rules count the prompt's frames and, for voiced_whole, see the text length from the first frame."]
+    if a.frame_step:
+        out["frame_step"], more = frame_step_table(a.frame_step)
+        md += [""] + more
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        with open(os.path.splitext(a.out)[0] + ".md", "w") as f:
+            f.write("\n".join(md) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rate", type=float, default=50.0, help="text tokens per second")
@@ -174,6 +285,10 @@ def main():
     ap.add_argument("--bystander", action="store_true", help="an ordinary request beside a pausing text client, without / with --text_hold")
     ap.add_argument("--pause_ms", type=float, default=150.0, help="--bystander: the text client's pause")
     ap.add_argument("--pause_every", type=int, default=8, help="--bystander: tokens between two pauses")
+    ap.add_argument("--voice", default=None, metavar="DIR", help="a codec prompt as encode_reference_audio --output_dir writes it")
+    ap.add_argument("--prompt_frames", type=int, default=0, help="instead of --voice: this many synthetic prompt frames")
+    ap.add_argument("--frame_step", default=None, metavar="FILE",
+                    help="--voice / --prompt_frames: JSON lines of scripts/slot_step_ms.py (labels parent / change) for the .md")
     a = ap.parse_args()
     from qwen3_tts_axera_russian_amd import batch_server as bs
     if a.tiny:
@@ -184,6 +299,8 @@ def main():
     ids = np.random.default_rng(a.seed).integers(0, cfg.text_vocab - 8, a.tokens).tolist()
     if a.bystander:
         return bystander(a, main_pack, voc_pack, cfg, ids)
+    if a.voice or a.prompt_frames > 0:
+        return voiced(a, main_pack, voc_pack, cfg, ids)
     sock = os.path.join(a.cache, f"tsl_{os.getpid()}.sock")
     srv = bs.BatchSynthesisServer(main_pack, voc_pack, sock, max_batch=a.max_batch, n_ctx=a.max_tokens + 64, max_tokens=a.max_tokens,
                                   temperature=0.0, cp_temperature=0.0, install_signal_handlers=False, concurrent=True,
