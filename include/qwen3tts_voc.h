@@ -184,6 +184,40 @@ int voc_incr_arithmetic(void* s);
 int voc_incr_last_split_launches(void* s);
 int voc_incr_last_redone(void* s);
 
+/* Snapshots of a stream's carried state.  A stream's samples depend on its frames and on nothing else, so the state it carries
+ * after frames P is a function of P and the arithmetic alone: it can be computed once, saved, and copied into any stream that is
+ * to continue P (a voice's codec prompt in front of many utterances).  The pool belongs to the vocoder HANDLE: every incremental
+ * object on a handle lays a stream's state out the same way, so a slot saved by one object serves the others.
+ *  - voc_incr_snapshots(voc, n_slots): n_slots > 0 reserves a device pool of n_slots x voc_incr_state_bytes() (5 193 984 B per slot
+ *    at the default table), 0 releases it; either way every snapshot is dropped.  -> n_slots; <0 with nothing changed on a
+ *    negative n_slots or no memory.  Legal at any time between calls.  voc_free frees the pool, voc_incr_free does not touch it.
+ *  - voc_incr_save(s, stream, slot): the stream's committed history (under double buffering the buffer its parity selects) goes
+ *    into the slot, with the frames the stream has taken and the arithmetic of s, replacing what the slot held.  Any unfinished
+ *    stream can be saved, a fresh one too (0 frames: restoring it is voc_incr_reset).  <0 with nothing changed: a bad stream or
+ *    slot, a finished stream, no pool.  Runs on the handle's stream: no further stream, event or hardware queue.
+ *  - voc_incr_restore(s, n, streams, slots): stream streams[i] becomes a running, unfinished stream whose history and frame count
+ *    are those of slots[i]; the utterance it held is dropped, as by a reset.  A slot may be named several times (one voice into many
+ *    streams), a stream at most once.  All n entries are copied by ONE kernel launch; a double-buffered object gets both of its
+ *    history buffers written, since an op that a push does not reach reads the other buffer next time (voc_incr_reset clears both
+ *    for the same reason).  Every entry is checked before anything changes -- <0 with every stream as it was: a bad index, a
+ *    stream named twice, an empty slot, a slot saved under the other arithmetic, no pool.
+ *  - voc_incr_snapshot_frames(voc, slot): the frames the slot holds; -1: an empty slot or a bad argument.
+ *  - voc_incr_last_restore_ms(s): GPU milliseconds of the last voc_incr_restore (HIP events on the handle's stream).
+ *  - Contract: let stream a take frames P (T of them, in any pushes); save it; restore the slot into stream b of any object on the
+ *    same handle that runs the same arithmetic; push frames U into b in any split, beside any neighbours.  b's samples, joined, are
+ *    bit for bit samples [S(T), S(T + |U|)) of ONE uninterrupted stream fed [P ; U] -- always in exact mode, in split mode as long
+ *    as no push on either side is redone on the exact path (voc_incr_set_arithmetic's rule).  After pushes totalling m frames b has
+ *    handed out exactly S(T + m) - S(T) samples.  Nothing else about b is special: its launches are grouped by its frame count (with
+ *    T >= 1 it is a running stream, not a first push), the 2^31 frame limit counts T, voc_incr_set_arithmetic sees it as running.
+ *  - Snapshots survive voc_incr_set_arithmetic and voc_incr_free and stay tagged with the arithmetic they were saved under.
+ *    voc_set_fused_units changes the last bit of exact-mode results: a snapshot taken under one setting and continued under the
+ *    other is the caller's affair (the library does not tag it). */
+int voc_incr_snapshots(void* voc, int n_slots);
+int voc_incr_save(void* s, int stream, int slot);
+int voc_incr_restore(void* s, int n, const int32_t* streams, const int32_t* slots);
+int64_t voc_incr_snapshot_frames(void* voc, int slot);
+float voc_incr_last_restore_ms(void* s);
+
 /* Arithmetic of the convolutions.  Default (0): split precision -- every f32 operand (weights once at load,
  * activations in the producing kernel's epilogue) is carried as two fp16 terms (22 mantissa bits) and each
  * product costs three fp16 MFMAs with f32 accumulation.  1: the exact-f32 MFMA (v_mfma_f32_32x32x2_f32)

@@ -109,6 +109,17 @@ frames and drops their samples, the chunk walk decodes the generated frames alon
 the layout is a recollection of the model's in-context mode: parity with real weights is not pinned.  Without the flag such a
 request is answered -2, as before.
 
+`--voice_warm N` (with `--concurrent`; default 0 = off): the incremental vocoder's warm-up per codec prompt is cached.  The
+state a stream carries after the prompt's T frames is a function of the frames and the arithmetic alone, so the server keeps it
+in N snapshot slots of its vocoder handle (voc_incr_snapshots; voice_warm.VoiceWarmCache is the LRU over them, keyed by a digest
+of the prompt's ids and T and by the arithmetic -- a named voice and the same codes sent inline share an entry).  A miss warms
+the stream up as before and saves it; a hit pushes no prompt frame: all hits of one check go into one voc_incr_restore, and an
+unstreamed reply starts from the slot (synthesize_incremental(start_slot=)).  Several slots admitted together with the same new
+voice: the first is the miss, the rest hit.  Every reply -- codes and PCM, streamed and not, both arithmetics as long as no
+push is redone exactly -- is bit for bit the reply without the flag; requests without a prompt, or not "incremental", touch
+nothing.  The counters voice_warm_hits / voice_warm_misses / voice_warm_evictions are on the server object, hits and misses in the
+per-request line.  Only the vocoder worker touches the cache.
+
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
 vocoder then launches one persistent workgroup per compute unit (voc_set_max_workgroups(-1)), which leaves the frame loop's
@@ -135,6 +146,7 @@ from . import protocol as P
 from .engine import FrameEngine, SlotParams
 from .frontend import TextFrontEnd
 from .vocoder import Vocoder
+from .voice_warm import VoiceWarmCache
 from .weights import ModelConfig, read_pack
 
 
@@ -168,7 +180,7 @@ class BatchSynthesisServer:
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
                  cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=0,
-                 prefix_cache_rows=64, voices=None, text_voice=False):
+                 prefix_cache_rows=64, voices=None, text_voice=False, voice_warm=0):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens = socket_path, max_batch, max_tokens
@@ -196,6 +208,10 @@ class BatchSynthesisServer:
         if text_voice and not concurrent:
             raise ValueError("--text_voice lets text slots of the shared frame loop continue a codec prompt: it needs --concurrent")
         self.text_voice = bool(text_voice)
+        if int(voice_warm) < 0:
+            raise ValueError("--voice_warm takes a number of snapshot slots >= 0")
+        if voice_warm and not concurrent:
+            raise ValueError("--voice_warm caches the vocoder warm-up of the shared frame loop's codec prompts: it needs --concurrent")
         self.sched = None
         # utterances one request may queue (the server is single-threaded: an unbounded request holds it indefinitely)
         self.max_request = int(max_request) if max_request else 8 * max_batch
@@ -214,6 +230,10 @@ class BatchSynthesisServer:
         self.n_ctx = n_ctx
         self._lib = hiplib.load()
         self.voc = Vocoder(vocoder_path, 64, min(max_batch, 32))
+        # --voice_warm N: N snapshot slots on the vocoder handle, and the LRU over them (the vocoder worker's, like the handle)
+        self._voice_warm = VoiceWarmCache(int(voice_warm))
+        if self._voice_warm.n_slots:
+            self.voc.snapshots(self._voice_warm.n_slots)
         self.pipeline = bool(pipeline)
         self._pool = None
         self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
@@ -285,6 +305,13 @@ class BatchSynthesisServer:
                 if pr is None or not len(pr):
                     out.append((c, self.voc.synthesize_incremental(c, int16=True, arithmetic=arithmetic)))
                     continue
+                if self._voice_warm.n_slots:
+                    # the prompt's state from the voice's snapshot (decoded and saved first on a miss), then the utterance alone
+                    slot = self._voice_warm.slot_of(self.voc.incremental_one(arithmetic), arithmetic,
+                                                    np.asarray(pr, np.int32).reshape(-1, 16), self.voc.chunk_tokens,
+                                                    self.voc.incremental_samples)
+                    out.append((c, self.voc.synthesize_incremental(c, int16=True, arithmetic=arithmetic, start_slot=slot)))
+                    continue
                 both = np.concatenate([np.asarray(pr, np.int32).reshape(-1, 16), np.asarray(c, np.int32).reshape(-1, 16)])
                 pcm = self.voc.synthesize_incremental(both, int16=True, arithmetic=arithmetic)
                 out.append((c, pcm[self.voc.incremental_samples(len(pr)):]))
@@ -309,14 +336,11 @@ class BatchSynthesisServer:
         ch = self.voc.chunk_tokens
         drop = state.setdefault("drop", {})    # samples of a slot's prompt that are still to be dropped from what it hands out
         for b in resets:
-            istream.reset(b)
             drop.pop(b, None)
-            pr = state.get("prompts", {}).pop(b, None)
-            if pr is not None and len(pr):
-                # the prompt's frames first, in pieces of at most chunk_tokens frames; none of their samples goes out
-                drop[b] = self.voc.incremental_samples(len(pr))
-                for f in range(0, len(pr), ch):
-                    drop[b] -= len(istream.push([b], [pr[f:f + ch]], [False])[0])
+        # a slot that continues a prompt: the prompt's frames first, in pieces of at most chunk_tokens frames, none of their
+        # samples going out -- or, with --voice_warm, the state those pushes leave, copied from the voice's snapshot
+        prompts = {b: state.get("prompts", {}).pop(b, None) for b in resets}
+        drop.update(self._voice_warm.start(istream, arithmetic, resets, prompts, ch, self.voc.incremental_samples))
         parts, j = [[] for _ in entries], 0
         while entries and (j == 0 or any(len(e[2]) > j * ch for e in entries)):
             sel = [k for k, e in enumerate(entries) if j == 0 or len(e[2]) > j * ch]
@@ -538,10 +562,15 @@ class BatchSynthesisServer:
                                prefix_key(b"stream", head + first[:1], prompt), prompt if len(prompt) else None)
 
     def _prefix_note(self):
-        """The prefix cache's counters so far, for the per-request line ("" without --prefix_cache)."""
-        if not self.prefix_cache or self.sched is None:
-            return ""
-        return f" (prefix cache: {self.sched.prefix_hits} hits, {self.sched.prefix_misses} misses so far)"
+        """The prefix cache's and the voice warm-ups' counters so far, for the per-request line ("" without the flags)."""
+        note = ""
+        if self.prefix_cache and self.sched is not None:
+            note = f" (prefix cache: {self.sched.prefix_hits} hits, {self.sched.prefix_misses} misses so far)"
+        return note + self._voice_warm.note()
+
+    voice_warm_hits = property(lambda self: self._voice_warm.hits)
+    voice_warm_misses = property(lambda self: self._voice_warm.misses)
+    voice_warm_evictions = property(lambda self: self._voice_warm.evictions)
 
     def _finish(self, conn, cs, t0, vocoder="walk", arithmetic="exact", prompts=None):
         """Worker side of the pipelined mode: vocode, reply on the request's own connection, close it."""
@@ -1420,6 +1449,9 @@ def main():
     ap.add_argument("--voice", action="append", default=[], metavar="NAME=DIR",
                     help="--concurrent: a codec prompt requests may name with \"voice\": \"NAME\"; DIR as "
                          "encode_reference_audio --output_dir writes it (repeatable)")
+    ap.add_argument("--voice_warm", type=int, default=0,
+                    help="with --concurrent: cache the incremental vocoder's warm-up per codec prompt in N snapshot slots of the "
+                         "vocoder (a known voice then costs one copy launch instead of decoding its prompt; default 0 = off)")
     ap.add_argument("--text_voice", action="store_true",
                     help="--concurrent: a text-stream request may carry a codec prompt (\"voice\" / \"prompt_codes\"): streamed "
                          "text in the prompt's voice")
@@ -1431,7 +1463,8 @@ def main():
                                max_queue=a.max_queue, top_p=a.top_p, cp_top_k=a.cp_top_k, check_every=a.check_every,
                                send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms, text_hold=a.text_hold,
                                prefix_cache=a.prefix_cache, prefix_cache_rows=a.prefix_cache_rows,
-                               voices=dict(v.split("=", 1) for v in a.voice), text_voice=a.text_voice)
+                               voices=dict(v.split("=", 1) for v in a.voice), text_voice=a.text_voice,
+                               voice_warm=a.voice_warm)
     try:
         srv.serve()
     finally:

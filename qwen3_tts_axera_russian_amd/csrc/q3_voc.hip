@@ -77,6 +77,8 @@ static void voc_destroy(Voc* v) {
     if (v->d_wave16) hipFree(v->d_wave16);
     if (v->d_place) hipFree(v->d_place);
     if (v->d_ovf) hipFree(v->d_ovf);
+    if (v->d_snap) hipFree(v->d_snap);
+    if (v->d_snap_tab) hipFree(v->d_snap_tab);
     if (v->h_stage) hipHostFree(v->h_stage);
     if (v->h_ovf) hipHostFree(v->h_ovf);
     if (v->e0) hipEventDestroy(v->e0);

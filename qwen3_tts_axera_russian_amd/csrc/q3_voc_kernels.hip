@@ -1547,6 +1547,53 @@ int voc_launch_incr_emit(hipStream_t s, const float* y, int ld, int skip, int n,
     return 0;
 }
 
+// Snapshots of a stream's carried state (voc_incr_restore): entry blockIdx.y copies `floats` floats from its slot into its
+// stream's history -- into both history buffers where the object is double-buffered (dst1 != null), so that an op the next push
+// does not reach finds the same columns whichever buffer it reads.  16 bytes per lane over the whole float4 groups, grid-strided;
+// the floats behind the last whole group go one per lane (workgroup 0 of the entry).  A stream's state starts at stream *
+// floats: with 4 | floats (the default table) every entry is 16-byte aligned; an entry that is not takes the scalar loop whole.
+__global__ void __launch_bounds__(256) voc_incr_restore_kernel(const SnapCopy* __restrict__ tab, long long floats) {
+    const SnapCopy e = tab[blockIdx.y];
+    const long long first = (long long)blockIdx.x * 256 + threadIdx.x, step = (long long)gridDim.x * 256;
+    if ((((uintptr_t)e.src | (uintptr_t)e.dst0 | (uintptr_t)e.dst1) & 15) != 0) {
+        for (long long i = first; i < floats; i += step) {
+            const float x = e.src[i];
+            e.dst0[i] = x;
+            if (e.dst1) e.dst1[i] = x;
+        }
+        return;
+    }
+    const long long nvec = floats / 4;
+    const float4* __restrict__ s4 = (const float4*)e.src;
+    float4* d0 = (float4*)e.dst0;
+    float4* d1 = (float4*)e.dst1;
+    for (long long i = first; i < nvec; i += step) {
+        const float4 x = s4[i];
+        d0[i] = x;
+        if (d1) d1[i] = x;
+    }
+    const long long t = nvec * 4 + threadIdx.x;
+    if (blockIdx.x == 0 && t < floats) {
+        const float x = e.src[t];
+        e.dst0[t] = x;
+        if (e.dst1) e.dst1[t] = x;
+    }
+}
+
+// The grid follows the bytes: one workgroup per 256 float4 groups of an entry, capped so that the n entries together stay
+// near 2048 workgroups (8 per compute unit); the kernel strides over the rest.
+int voc_launch_incr_restore(hipStream_t s, const SnapCopy* tab, long long floats, int n) {
+    if (n <= 0) return 0;
+    if (n > 65535) {   // (gridDim.y; an object of that many streams does not fit a device)
+        Q3_LOG("voc_incr_restore: %d entries in one call", n);
+        return -1;
+    }
+    const long long want = std::max(1LL, (floats / 4 + 255) / 256), cap = std::max(1, 2048 / n);
+    hipLaunchKernelGGL(voc_incr_restore_kernel, dim3((unsigned)std::min(want, cap), (unsigned)n), dim3(256), 0, s, tab, floats);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+
 }  // namespace q3
 
 using namespace q3;

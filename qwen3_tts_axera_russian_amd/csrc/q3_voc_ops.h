@@ -136,4 +136,13 @@ int voc_launch_incr_attn(hipStream_t s, const float* x, int x_ld, int skip, cons
                          int window, float theta, const int* pos0, int n, int B);
 int voc_launch_incr_emit(hipStream_t s, const float* y, int ld, int skip, int n, const long long* out_off, void* out, bool want16, int B);
 
+// snapshot restore: n entries of a device table, each `floats` floats from a slot into a stream's history (dst1: the second
+// history buffer of a double-buffered object, or null), in one launch
+struct SnapCopy {
+    const float* src;
+    float* dst0;
+    float* dst1;
+};
+int voc_launch_incr_restore(hipStream_t s, const SnapCopy* tab, long long floats, int n);
+
 }  // namespace q3

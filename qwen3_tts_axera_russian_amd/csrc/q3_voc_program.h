@@ -62,6 +62,14 @@ struct Voc {
     char* h_stage = nullptr;
     size_t h_stage_bytes = 0;
     int* h_ovf = nullptr;
+    // snapshots of incremental streams' carried state (voc_incr_snapshots): the pool is the handle's, since every VocIncr on it
+    // lays a stream's state out the same way (H and hoff come from the op table)
+    float* d_snap = nullptr;               // [snap slots][snap_pitch]
+    size_t snap_pitch = 0;                 // floats between slots: the state, rounded up to 4 (slots start 16-byte aligned)
+    std::vector<long long> snap_frames;    // per slot: frames the saved stream had taken, -1 = empty
+    std::vector<char> snap_split;          // per slot: the arithmetic it was saved under
+    SnapCopy* d_snap_tab = nullptr;        // voc_incr_restore's entries (grown on demand, with the pool)
+    size_t snap_tab_cap = 0;
 };
 
 // A handle's buffers, stream and events live on the device it was loaded on.  The HIP current device is a per-THREAD setting that

@@ -488,6 +488,7 @@ struct VocIncr {
     std::vector<char> parity;             // per stream
     bool warned_ovf = false;
     int last_split = 0, last_redone = 0;
+    float last_restore_ms = 0.f;          // voc_incr_restore
 };
 
 int incr_hist_cols(const VocOp& op) {
@@ -500,6 +501,12 @@ int incr_hist_cols(const VocOp& op) {
     }
 }
 int incr_hist_chans(const VocOp& op) { return op.op == VOP_ATTN ? 2 * op.heads * op.head_dim : op.cin; }
+// floats of one stream's carried state: the same for every object on a handle (voc_incr_create lays it out op by op)
+size_t incr_state_floats(const Voc* v) {
+    size_t f = 0;
+    for (const VocOp& op : v->ops) f += (size_t)incr_hist_cols(op) * incr_hist_chans(op);
+    return f;
+}
 
 // in[i]: columns op i has consumed once its stream has taken n frames; in[n_ops]: samples handed out = S(n).  A transposed
 // conv whose right trim is k - s (voc_incr_create's rule) turns L columns into L * s - lt: the convt_out chain, 0 where the
@@ -1092,5 +1099,95 @@ int voc_incr_set_arithmetic(void* ss, int split) {
 int voc_incr_arithmetic(void* s) { return s ? ((VocIncr*)s)->split : -1; }
 int voc_incr_last_split_launches(void* s) { return s ? ((VocIncr*)s)->last_split : -1; }
 int voc_incr_last_redone(void* s) { return s ? ((VocIncr*)s)->last_redone : -1; }
+
+// ---- snapshots of a stream's carried state (the pool is the handle's: q3_voc_program.h) ----
+int voc_incr_snapshots(void* vv, int n_slots) {
+    Voc* v = (Voc*)vv;
+    if (!v || n_slots < 0) return -1;
+    voc_bind(v);
+    float* pool = nullptr;
+    const size_t pitch = (incr_state_floats(v) + 3) / 4 * 4;
+    if (n_slots > 0 && hipMalloc((void**)&pool, sizeof(float) * std::max<size_t>(4, pitch * (size_t)n_slots)) != hipSuccess) {
+        Q3_LOG("voc_incr_snapshots: no device memory for %d slots of %zu bytes", n_slots, sizeof(float) * pitch);
+        return -1;
+    }
+    hipStreamSynchronize(v->s);   // (a save or restore of the old pool is complete before it goes)
+    if (v->d_snap) hipFree(v->d_snap);
+    v->d_snap = pool;
+    v->snap_pitch = pitch;
+    v->snap_frames.assign(n_slots, -1);
+    v->snap_split.assign(n_slots, 0);
+    return n_slots;
+}
+
+int64_t voc_incr_snapshot_frames(void* vv, int slot) {
+    const Voc* v = (const Voc*)vv;
+    if (!v || slot < 0 || slot >= (int)v->snap_frames.size()) return -1;
+    return v->snap_frames[slot];
+}
+
+int voc_incr_save(void* ss, int stream, int slot) {
+    VocIncr* s = (VocIncr*)ss;
+    if (!s || stream < 0 || stream >= s->max_streams || s->finished[stream]) return -1;
+    Voc* v = s->v;
+    if (!v->d_snap || slot < 0 || slot >= (int)v->snap_frames.size()) return -1;
+    voc_bind(v);
+    // the committed history: in a double-buffered object the buffer the stream's parity selects
+    const float* hist = (s->d_hist1 && s->parity[stream] ? s->d_hist1 : s->d_hist) + (size_t)stream * s->state_floats;
+    if (s->state_floats)
+        Q3_HIP(hipMemcpyAsync(v->d_snap + (size_t)slot * v->snap_pitch, hist, sizeof(float) * s->state_floats, hipMemcpyDeviceToDevice, v->s), -1);
+    v->snap_frames[slot] = s->n_frames[stream];
+    v->snap_split[slot] = (char)s->split;
+    return 0;
+}
+
+int voc_incr_restore(void* ss, int n, const int32_t* streams, const int32_t* slots) {
+    VocIncr* s = (VocIncr*)ss;
+    if (!s || n < 0 || (n > 0 && (!streams || !slots))) return -1;
+    Voc* v = s->v;
+    if (!v->d_snap) {
+        Q3_LOG("voc_incr_restore: the handle has no snapshot pool (voc_incr_snapshots)");
+        return -1;
+    }
+    // every entry is checked before any stream changes
+    std::vector<char> seen(s->max_streams, 0);
+    for (int i = 0; i < n; i++) {
+        const int k = streams[i], z = slots[i];
+        if (k < 0 || k >= s->max_streams || seen[k] || z < 0 || z >= (int)v->snap_frames.size() || v->snap_frames[z] < 0) {
+            Q3_LOG("voc_incr_restore: entry %d: bad stream %d (or named twice) or bad or empty slot %d", i, k, z);
+            return -1;
+        }
+        if (v->snap_split[z] != (char)s->split) {
+            Q3_LOG("voc_incr_restore: slot %d was saved under the %s arithmetic, the object runs the %s one", z,
+                   v->snap_split[z] ? "split" : "exact", s->split ? "split" : "exact");
+            return -1;
+        }
+        seen[k] = 1;
+    }
+    s->last_restore_ms = 0.f;
+    if (n == 0) return 0;
+    voc_bind(v);
+    if (grow(&v->d_snap_tab, &v->snap_tab_cap, (size_t)std::max(n, s->max_streams))) return -1;
+    std::vector<SnapCopy> tab(n);
+    for (int i = 0; i < n; i++) {
+        const size_t ho = (size_t)streams[i] * s->state_floats;
+        tab[i] = {v->d_snap + (size_t)slots[i] * v->snap_pitch, s->d_hist + ho, s->d_hist1 ? s->d_hist1 + ho : nullptr};
+    }
+    Q3_HIP(hipMemcpyAsync(v->d_snap_tab, tab.data(), sizeof(SnapCopy) * n, hipMemcpyHostToDevice, v->s), -1);
+    Q3_HIP(hipEventRecord(v->e0, v->s), -1);
+    if (s->state_floats && voc_launch_incr_restore(v->s, v->d_snap_tab, (long long)s->state_floats, n)) return -1;
+    Q3_HIP(hipEventRecord(v->e1, v->s), -1);
+    Q3_HIP(hipStreamSynchronize(v->s), -1);   // (the table's staging vector; the events)
+    hipEventElapsedTime(&s->last_restore_ms, v->e0, v->e1);
+    for (int i = 0; i < n; i++) {
+        const int k = streams[i];
+        s->parity[k] = 0;   // both buffers hold the slot's columns
+        s->n_frames[k] = v->snap_frames[slots[i]];
+        s->finished[k] = 0;
+    }
+    return 0;
+}
+
+float voc_incr_last_restore_ms(void* s) { return s ? ((VocIncr*)s)->last_restore_ms : -1.f; }
 
 }  // extern "C"

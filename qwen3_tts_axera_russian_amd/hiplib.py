@@ -152,6 +152,11 @@ def load(path: str | None = None):
     _sig(lib, "voc_incr_arithmetic", c_int, [c_void_p])
     _sig(lib, "voc_incr_last_split_launches", c_int, [c_void_p])
     _sig(lib, "voc_incr_last_redone", c_int, [c_void_p])
+    _sig(lib, "voc_incr_snapshots", c_int, [c_void_p, c_int])
+    _sig(lib, "voc_incr_save", c_int, [c_void_p, c_int, c_int])
+    _sig(lib, "voc_incr_restore", c_int, [c_void_p, c_int, i32p, i32p])
+    _sig(lib, "voc_incr_snapshot_frames", ctypes.c_int64, [c_void_p, c_int])
+    _sig(lib, "voc_incr_last_restore_ms", c_float, [c_void_p])
     # include/qwen3tts_enc.h
     _sig(lib, "enc_load", c_void_p, [c_char_p, c_int, c_int])
     _sig(lib, "enc_free", None, [c_void_p])

@@ -85,15 +85,34 @@ class Vocoder:
         """S(n): the samples of a whole carry-state decode of n_frames frames (voc_incr_samples)"""
         return int(self.lib.voc_incr_samples(self.h, int(n_frames)))
 
-    def synthesize_incremental(self, codes, int16=False, arithmetic="exact"):
-        """codes [n][16] -> the carry-state decode of the whole utterance (voc_incr_*): one stream, pushed in chunk_tokens
-        pieces.  One seamless decode of all n frames -- not synthesize()'s cross-faded chunk walk -- and bit for bit what
-        any other split of the frames across pushes gives (arithmetic="split": as long as no push is redone exactly)."""
-        c = _cat([codes])
+    def snapshots(self, n_slots):
+        """Reserve n_slots snapshot slots of one stream's carried state on this handle (0: release them); every snapshot
+        held so far is dropped (voc_incr_snapshots)."""
+        if self.lib.voc_incr_snapshots(self.h, int(n_slots)) < 0:
+            raise RuntimeError("voc_incr_snapshots failed (a negative count, or no device memory; see the log)")
+
+    def snapshot_frames(self, slot):
+        """the frames the stream saved in `slot` had taken; -1: an empty slot (voc_incr_snapshot_frames)"""
+        return int(self.lib.voc_incr_snapshot_frames(self.h, int(slot)))
+
+    def incremental_one(self, arithmetic="exact"):
+        """-> synthesize_incremental's one-stream object for `arithmetic` (created on first use)"""
         if arithmetic not in self._incr1:
             self._incr1[arithmetic] = self.incremental(1, arithmetic)
-        st = self._incr1[arithmetic]
-        st.reset(0)
+        return self._incr1[arithmetic]
+
+    def synthesize_incremental(self, codes, int16=False, arithmetic="exact", start_slot=None):
+        """codes [n][16] -> the carry-state decode of the whole utterance (voc_incr_*): one stream, pushed in chunk_tokens
+        pieces.  One seamless decode of all n frames -- not synthesize()'s cross-faded chunk walk -- and bit for bit what
+        any other split of the frames across pushes gives (arithmetic="split": as long as no push is redone exactly).
+        start_slot: the stream starts from that snapshot (IncrementalStream.save) instead of from silence, and the result
+        holds the samples of `codes` alone: what a decode of [the snapshot's frames ; codes] yields behind the snapshot's."""
+        c = _cat([codes])
+        st = self.incremental_one(arithmetic)
+        if start_slot is None:
+            st.reset(0)
+        else:
+            st.restore([0], [start_slot])
         parts = [st.push([0], [c[f:f + self.chunk_tokens]], [f + self.chunk_tokens >= len(c)], int16)[0].copy()
                  for f in range(0, len(c), self.chunk_tokens)]
         return np.concatenate(parts + [np.zeros(0, np.int16 if int16 else np.float32)])
@@ -162,6 +181,7 @@ class IncrementalStream:
         if not self.h:
             raise RuntimeError("voc_incr_create failed (see the log)")
         self.last_launches, self.last_ms = 0, 0.0    # of the last push
+        self.last_restore_ms = 0.0                   # GPU milliseconds of the last restore
         self.last_split_launches, self.last_redone = 0, 0    # conv launches on the fp16 MFMA path, entries redone exactly
         self.state_bytes = int(lib.voc_incr_state_bytes(self.h))     # per stream, constant
         if arithmetic != "exact":
@@ -204,6 +224,20 @@ class IncrementalStream:
         self.last_redone = int(self.lib.voc_incr_last_redone(self.h))
         self.last_ms = float(self.lib.voc_incr_last_ms(self.h))
         return pcm
+
+    def save(self, k, slot):
+        """the carried state of the unfinished stream k -> snapshot slot `slot` of the handle (voc_incr_save)"""
+        if self.lib.voc_incr_save(self.h, int(k), int(slot)) != 0:
+            raise RuntimeError("voc_incr_save failed (a bad or finished stream, a bad slot, or no pool: Vocoder.snapshots)")
+
+    def restore(self, streams, slots):
+        """streams[i] continues the stream saved in slots[i], all in one launch (voc_incr_restore); a slot may repeat, a
+        stream may not.  Nothing changes when any entry is refused."""
+        st, sl = np.array(streams, np.int32), np.array(slots, np.int32)
+        if len(st) != len(sl) or self.lib.voc_incr_restore(self.h, len(st), hiplib.iptr(st), hiplib.iptr(sl)) != 0:
+            raise RuntimeError("voc_incr_restore refused (a bad or repeated stream, an empty slot, or one saved under the "
+                               "other arithmetic; see the log)")
+        self.last_restore_ms = float(self.lib.voc_incr_last_restore_ms(self.h))
 
     def close(self):
         if self.h:

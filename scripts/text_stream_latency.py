@@ -39,6 +39,14 @@ what was measured.  --frame_step FILE (JSON lines of scripts/slot_step_ms.py, la
 process) adds the frame-step comparison to the .md written beside --out.
 
     python scripts/text_stream_latency.py --prompt_frames 75 --out profiles/text_voice_latency.json
+
+--voice_warm N (with --prompt_frames T): the vocoder's warm-up per voice, cached (batch_server --voice_warm).  The voiced legs
+run against a server without the flag and then against one with it, in the same process: "off", "on/miss" (new random prompt
+codes every request) and "on/hit" (the prompt of the untimed pass).  Then, on the server's vocoder shape and one stream, the
+warm-up pushes of a prompt of --restore_frames frames (summed voc_incr_last_ms) beside voc_incr_last_restore_ms of the restore
+that replaces them.  No target: the tables state what was measured.
+
+    python scripts/text_stream_latency.py --prompt_frames 75 --voice_warm 4 --repeats 5 --out profiles/voice_warm.json
 """
 from __future__ import annotations
 
@@ -269,6 +277,121 @@ def voiced(a, main_pack, voc_pack, cfg, ids):
             f.write("\n".join(md) + "\n")
 
 
+def restore_table(a, voc_pack):
+    """One stream on the server's vocoder shape: per prompt length T the warm-up pushes (chunk_tokens pieces, summed
+    voc_incr_last_ms and launches) beside the one restore launch that replaces them (voc_incr_last_restore_ms)."""
+    from qwen3_tts_axera_russian_amd.vocoder import Vocoder
+    voc = Vocoder(voc_pack, 64, min(a.max_batch, 32))
+    voc.snapshots(1)
+    rows = []
+    try:
+        st = voc.incremental(1, "exact")
+        rng = np.random.default_rng(a.seed + 2)
+        for T in a.restore_frames:
+            codes = rng.integers(0, 2048, size=(T, 16)).astype(np.int64)
+            push_ms, restore_ms, launches = [], [], 0
+            for rep in range(a.repeats + 1):
+                st.reset(0)
+                ms, launches = 0.0, 0
+                for f in range(0, T, voc.chunk_tokens):
+                    st.push([0], [codes[f:f + voc.chunk_tokens]], [False])
+                    ms += st.last_ms
+                    launches += st.last_launches
+                st.save(0, 0)
+                st.restore([0], [0])
+                if rep:
+                    push_ms.append(ms)
+                    restore_ms.append(st.last_restore_ms)
+            rows.append({"prompt_frames": T, "pushes": -(-T // voc.chunk_tokens), "push_launches": launches,
+                         "push_ms": [round(x, 4) for x in push_ms], "restore_ms": [round(x, 4) for x in restore_ms],
+                         "push_ms_median": round(float(np.median(push_ms)), 4), "restore_ms_median": round(float(np.median(restore_ms)), 4)})
+            print(f"[text_stream_latency] restore table: {rows[-1]}", file=sys.stderr, flush=True)
+        state = st.state_bytes
+    finally:
+        voc.close()
+    return {"state_bytes": state, "rows": rows}
+
+
+def voice_warm(a, main_pack, voc_pack, cfg, ids):
+    """--voice_warm N with --prompt_frames T: the voiced legs against one server without the flag and one with it, in one
+    session.  With the flag, "miss" requests carry a prompt the server has not seen (new random codes every time), "hit" requests
+    the prompt of the untimed pass."""
+    from qwen3_tts_axera_russian_amd import batch_server as bs
+    T = a.prompt_frames
+    rng = np.random.default_rng(a.seed + 1)
+    fresh = lambda: rng.integers(0, 2048, size=(T, 16)).astype(np.int32)
+    known = fresh()
+    plan = {"voiced_streamed": True, "voiced_whole": False}
+    legs = {}
+    for flag in (0, a.voice_warm):
+        sock = os.path.join(a.cache, f"tsl_{os.getpid()}_w{flag}.sock")
+        srv = bs.BatchSynthesisServer(main_pack, voc_pack, sock, max_batch=a.max_batch, n_ctx=a.max_tokens + 64 + T, max_tokens=a.max_tokens,
+                                      temperature=0.0, cp_temperature=0.0, install_signal_handlers=False, concurrent=True,
+                                      text_wait_ms=a.text_wait_ms, text_voice=True, voice_warm=flag)
+        th = threading.Thread(target=srv.serve, daemon=True)
+        th.start()
+        while not (os.path.exists(sock) and srv.sched is not None):
+            time.sleep(0.05)
+        cases = {"off": lambda: known} if not flag else {"on/miss": fresh, "on/hit": lambda: known}
+        try:
+            for rep in range(a.repeats + 1):
+                for case, codes in cases.items():
+                    for leg, streamed in plan.items():
+                        h0, m0 = srv.voice_warm_hits, srv.voice_warm_misses
+                        r = one(sock, ids, a.rate, a.max_tokens, a.vocoder, streamed, prompt_codes=codes())
+                        r["hits"], r["misses"] = srv.voice_warm_hits - h0, srv.voice_warm_misses - m0
+                        if rep:
+                            legs.setdefault(f"{leg} {case}", []).append(r)
+                        print(f"[text_stream_latency] {'warm-up' if not rep else rep} {leg} {case}: {r}", file=sys.stderr, flush=True)
+        finally:
+            srv._running = False
+            th.join(timeout=60)
+            srv.close()
+    for name, runs in legs.items():      # the legs are what they are called
+        want = {"off": (0, 0), "on/miss": (0, 1), "on/hit": (1, 0)}[name.split(" ")[1]]
+        assert all((r["hits"], r["misses"]) == want for r in runs), (name, runs)
+    med = lambda leg, k: float(np.median([r[k] for r in legs[leg]]))
+    table = restore_table(a, voc_pack)
+    out = {"what": "time from the first text token to the first audio record of a request that continues a codec prompt, with the "
+                   "incremental vocoder: --voice_warm off, on with an unknown prompt (miss), on with a known one (hit); and one "
+                   "stream's warm-up pushes beside the restore launch that replaces them",
+           "packs": "tiny (2 + 2 layers)" if a.tiny else "synthetic Qwen3-TTS-0.6B architecture", "rate_tokens_per_s": a.rate,
+           "tokens": a.tokens, "text_ready_ms": round(1e3 * (a.tokens - 1) / a.rate, 1), "prompt_frames": T, "max_tokens": a.max_tokens,
+           "vocoder": a.vocoder, "max_batch": a.max_batch, "voice_warm": a.voice_warm, "repeats": a.repeats, "runs": legs,
+           "median": {leg: {k: med(leg, k) for k in ("first_audio_ms", "done_ms", "frames")} for leg in legs}, "restore": table}
+    md = ["# Voice warm-up cache: time to first audio, and the restore launch", "",
+          "`scripts/text_stream_latency.py %s`, one run on one MI355X: %s packs, %d text tokens at %g tokens/s (the whole text exists "
+          "after %.0f ms), a synthetic codec prompt of %d frames, vocoder %s, %d slots, %d timed repeats after one untimed pass, the "
+          "server without the flag first and the one with `--voice_warm %d` after it in the same process.  Medians; no target is set."
+          % (" ".join(sys.argv[1:]), out["packs"], a.tokens, a.rate, out["text_ready_ms"], T, a.vocoder, a.max_batch, a.repeats,
+             a.voice_warm), "",
+          "| leg | --voice_warm | first audio (ms) | reply done (ms) | frames |", "|---|---|---|---|---|"]
+    for name in legs:
+        m = out["median"][name]
+        md.append("| %s | %s | %.1f | %.1f | %d |" % (*name.split(" "), m["first_audio_ms"], m["done_ms"], m["frames"]))
+    md += ["", "voiced_streamed: a \"text_stream\" request with the prompt (--text_voice), first audio from the first token; "
+           "voiced_whole: an ordinary streamed request with the prompt, sent once the last token exists (first audio counts from the "
+           "first token all the same).  off: the parent's code path.  on/miss: a prompt the server has not seen (new random codes "
+           "every request): the warm-up pushes as before, then a save.  on/hit: the prompt of the untimed pass: no prompt push, one "
+           "restore launch.  The prefix cache is off in all of them, so every request still prefills its prompt's rows.", "",
+           "## One stream: the warm-up pushes and the restore that replaces them", "",
+           "The server's vocoder shape (chunk_tokens 64), exact arithmetic, one stream, state %d B; per prompt length the summed "
+           "voc_incr_last_ms of the pushes and voc_incr_last_restore_ms of the restore, medians of %d repeats after one untimed pass "
+           "(GPU time between HIP events on the vocoder's stream; the host's share of a push -- staging, one synchronisation per "
+           "launch group -- is not in it)." % (table["state_bytes"], a.repeats), "",
+           "| prompt frames | pushes | launches | pushes (ms) | restore (ms) |", "|---|---|---|---|---|"]
+    for r in table["rows"]:
+        md.append("| %d | %d | %d | %.3f | %.4f |" % (r["prompt_frames"], r["pushes"], r["push_launches"], r["push_ms_median"], r["restore_ms_median"]))
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+            f.write("\n")
+        with open(os.path.splitext(a.out)[0] + ".md", "w") as f:
+            f.write("\n".join(md) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rate", type=float, default=50.0, help="text tokens per second")
@@ -289,7 +412,14 @@ def main():
     ap.add_argument("--prompt_frames", type=int, default=0, help="instead of --voice: this many synthetic prompt frames")
     ap.add_argument("--frame_step", default=None, metavar="FILE",
                     help="--voice / --prompt_frames: JSON lines of scripts/slot_step_ms.py (labels parent / change) for the .md")
+    ap.add_argument("--voice_warm", type=int, default=0,
+                    help="--prompt_frames: the voiced legs against a server without the flag and one with --voice_warm N, and the "
+                         "restore table")
+    ap.add_argument("--restore_frames", type=int, nargs="*", default=[25, 75, 125, 375],
+                    help="--voice_warm: prompt lengths of the restore table (profiles/codec_prompt.md's)")
     a = ap.parse_args()
+    if a.voice_warm and (a.voice or a.prompt_frames <= 0 or a.vocoder != "incremental"):
+        ap.error("--voice_warm measures synthetic prompts with the incremental vocoder: give --prompt_frames T")
     from qwen3_tts_axera_russian_amd import batch_server as bs
     if a.tiny:
         main_pack, voc_pack, cfg = tiny_packs(a.cache)
@@ -299,6 +429,8 @@ def main():
     ids = np.random.default_rng(a.seed).integers(0, cfg.text_vocab - 8, a.tokens).tolist()
     if a.bystander:
         return bystander(a, main_pack, voc_pack, cfg, ids)
+    if a.voice_warm:
+        return voice_warm(a, main_pack, voc_pack, cfg, ids)
     if a.voice or a.prompt_frames > 0:
         return voiced(a, main_pack, voc_pack, cfg, ids)
     sock = os.path.join(a.cache, f"tsl_{os.getpid()}.sock")
