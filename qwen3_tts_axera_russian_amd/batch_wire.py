@@ -1,0 +1,201 @@
+"""The batched protocol of batch_server and its clients (standard library, numpy and protocol only: no engine, no GPU).
+
+Extension of the reference's wire protocol, same conventions (little-endian, u32 length + UTF-8 JSON):
+
+    request   u32 len + JSON {"texts": [...], "language": "...", "max_tokens": N}   or {"token_ids": [[...], ...]}
+    reply     i32 n_utterances (or -2 on error), then per utterance:
+              i32 n_frames, i32[n_frames*16] codes, i32 n_samples, i16[n_samples] PCM (24 kHz)
+
+Streamed reply (the request carries "stream": true): the same synthesis, handed out while the frame loop runs, as records on
+the same connection (in the order they are ready; `utt` indexes the request's utterances):
+
+              i32 1, i32 utt, i32 n, i16[n]                  PCM of utterance utt: the next n samples
+              i32 2, i32 utt, i32 n_frames, i32[n_frames*16]  utterance utt has ended: all its codes
+              i32 -1                                          the request is done   (i32 -2: error, as above)
+
+Streamed TEXT (`--concurrent` only; the request carries "text_stream": true, which needs "stream": true and exactly one
+utterance, else -2): the request's texts / token_ids hold only the first piece of the text (at least one token), and the
+client goes on sending the rest on the same connection, as records
+
+              i32 1, i32 n, n UTF-8 bytes (cut anywhere)      more text, tokenised by the server's incremental tokeniser
+              i32 2, i32 n, i32[n]                             more token ids
+              i32 0, i32 0                                     end of text
+
+while the audio records already come back.  The request's other keys: batch_request.
+"""
+from __future__ import annotations
+
+import json
+import socket
+import struct
+import threading
+
+import numpy as np
+
+from . import protocol as P
+
+REC_AUDIO, REC_END = 1, 2     # the records of a streamed reply
+
+
+def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False, temperature=None,
+                       top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None,
+                       vocoder_arithmetic=None, text_stream=False, prompt_codes=None, prompt_token_ids=None, prompt_text=None,
+                       voice=None) -> bytes:
+    """The request of the batched protocol; the sampling keys (honoured by --concurrent), the vocoder mode ("walk" /
+    "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given.  text_stream: the
+    request carries only the first piece of its one utterance's text; the rest follows as text records.  prompt_codes ([T][16], or
+    one such per utterance), prompt_token_ids / prompt_text, voice: the codec prompt the utterances continue (--concurrent)."""
+    msg = {"language": language}
+    if stream:
+        msg["stream"] = True
+    if text_stream:
+        msg["text_stream"] = True
+    if token_ids is not None:
+        msg["token_ids"] = [[int(t) for t in ids] for ids in token_ids]
+    else:
+        msg["texts"] = list(texts)
+    if max_tokens:
+        msg["max_tokens"] = int(max_tokens)
+    if prompt_codes is not None:
+        prompt_codes = np.asarray(prompt_codes).tolist() if not isinstance(prompt_codes, list) else \
+            [np.asarray(c).tolist() if isinstance(c, np.ndarray) else c for c in prompt_codes]
+    if prompt_token_ids is not None:
+        prompt_token_ids = [int(t) for t in prompt_token_ids]
+    for key, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("cp_temperature", cp_temperature),
+                   ("cp_top_k", cp_top_k), ("seed", seed), ("vocoder", vocoder), ("vocoder_arithmetic", vocoder_arithmetic),
+                   ("prompt_codes", prompt_codes), ("prompt_token_ids", prompt_token_ids), ("prompt_text", prompt_text),
+                   ("voice", voice)):
+        if v is not None:
+            msg[key] = v
+    raw = json.dumps(msg).encode()
+    return struct.pack("<I", len(raw)) + raw
+
+
+def pack_batch_reply(results) -> bytes:
+    parts = [struct.pack("<i", len(results))]
+    for codes, pcm in results:
+        c = np.ascontiguousarray(codes, dtype="<i4").reshape(-1, 16)
+        a = np.ascontiguousarray(pcm, dtype="<i2")
+        parts += [struct.pack("<i", c.shape[0]), c.tobytes(), struct.pack("<i", a.shape[0]), a.tobytes()]
+    return b"".join(parts)
+
+
+def read_batch_reply(conn):
+    """-> list of (codes [n][16] int32, pcm int16); raises on the error sentinel / a short read."""
+    head = P.recv_exact(conn, 4)
+    if len(head) < 4:
+        raise RuntimeError("connection closed")
+    (n,) = struct.unpack("<i", head)
+    if n < 0:
+        raise RuntimeError(f"server error ({n})")
+    out = []
+    for _ in range(n):
+        (nf,) = struct.unpack("<i", P.recv_exact(conn, 4))
+        codes = np.frombuffer(P.recv_exact(conn, nf * 16 * 4), dtype="<i4").reshape(nf, 16)
+        (ns,) = struct.unpack("<i", P.recv_exact(conn, 4))
+        pcm = np.frombuffer(P.recv_exact(conn, ns * 2), dtype="<i2")
+        out.append((codes, pcm))
+    return out
+
+
+def pack_stream_audio(utt, pcm) -> bytes:
+    a = np.ascontiguousarray(pcm, dtype="<i2").reshape(-1)
+    return struct.pack("<iii", REC_AUDIO, int(utt), a.shape[0]) + a.tobytes()
+
+
+def pack_stream_end(utt, codes) -> bytes:
+    c = np.ascontiguousarray(codes, dtype="<i4").reshape(-1, 16)
+    return struct.pack("<iii", REC_END, int(utt), c.shape[0]) + c.tobytes()
+
+
+def read_stream_record(conn):
+    """One record of a streamed reply -> ("audio", utt, pcm int16) / ("end", utt, codes [n][16] int32) / ("done",); raises on
+    the error sentinel, an unknown record or a short read."""
+    def exact(n):
+        b = P.recv_exact(conn, n)
+        if len(b) < n:
+            raise RuntimeError("connection closed inside a streamed reply")
+        return b
+    (kind,) = struct.unpack("<i", exact(4))
+    if kind == P.SENTINEL_DONE:
+        return ("done",)
+    if kind == P.SENTINEL_ERROR:
+        raise RuntimeError(f"server error ({kind})")
+    if kind not in (REC_AUDIO, REC_END):
+        raise RuntimeError(f"unknown record {kind} in a streamed reply")
+    utt, n = struct.unpack("<ii", exact(8))
+    if n < 0:
+        raise RuntimeError(f"record of {n} entries")
+    if kind == REC_AUDIO:
+        return ("audio", utt, np.frombuffer(exact(n * 2), dtype="<i2"))
+    return ("end", utt, np.frombuffer(exact(n * 16 * 4), dtype="<i4").reshape(n, 16))
+
+
+def _stream_records(s):
+    """The records of a streamed reply on `s` until the request is done."""
+    while True:
+        rec = read_stream_record(s)
+        if rec[0] == "done":
+            return
+        yield rec
+
+
+def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, vocoder=None,
+                            vocoder_arithmetic=None, **sampling):
+    """Client side of the streamed request: yields its records as they arrive -- ("audio", utt, pcm) and ("end", utt, codes)
+    -- until the request is done; raises on the error sentinel.  vocoder="incremental": the carry-state decode (audio from the
+    first check on) instead of the chunk walk, vocoder_arithmetic="split": on its split-fp16 convolutions.  sampling: the optional
+    keys of pack_batch_request."""
+    with socket.socket(socket.AF_UNIX, socket.SOCK_STREAM) as s:
+        s.connect(socket_path)
+        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True, vocoder=vocoder,
+                                     vocoder_arithmetic=vocoder_arithmetic, **sampling))
+        yield from _stream_records(s)
+
+
+def synthesize_text_stream(socket_path, pieces, language="russian", max_tokens=None, vocoder=None, vocoder_arithmetic=None,
+                           voice=None, prompt_codes=None, prompt_token_ids=None, prompt_text=None, **sampling):
+    """Client side of a "text_stream" request (--concurrent servers): `pieces` is an iterable of the text's pieces as they
+    become available -- str / bytes (UTF-8, cut anywhere; the server tokenises) or sequences of token ids.  The first piece
+    goes out with the request (it must give at least one token), the others as text records from a sender thread that walks
+    the iterable, then the end-of-text record.  Yields the records of synthesize_batch_stream, utterance 0.  voice, or
+    prompt_codes with prompt_token_ids / prompt_text: the codec prompt the utterance continues (--text_voice servers)."""
+    it = iter(pieces)
+    first = next(it)
+    as_text = isinstance(first, (str, bytes, bytearray))
+    if isinstance(first, (bytes, bytearray)):
+        raise TypeError("the first piece goes into the JSON request: a str, or a sequence of token ids")
+    s = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
+    s.connect(socket_path)
+    sender_error = []
+
+    def sender():
+        try:
+            for piece in it:
+                text = isinstance(piece, (str, bytes, bytearray))
+                s.sendall(P.pack_text_record(P.TEXT_BYTES if text else P.TEXT_IDS, piece))
+            s.sendall(P.pack_text_record(P.TEXT_END))
+        except Exception as e:      # noqa: BLE001 -- the reader sees the closed connection or the server's -2
+            sender_error.append(e)
+
+    th = threading.Thread(target=sender, daemon=True)
+    try:
+        s.sendall(pack_batch_request([first] if as_text else None, None if as_text else [list(first)], language, max_tokens,
+                                     stream=True, vocoder=vocoder, vocoder_arithmetic=vocoder_arithmetic, text_stream=True,
+                                     prompt_codes=prompt_codes, prompt_token_ids=prompt_token_ids, prompt_text=prompt_text,
+                                     voice=voice, **sampling))
+        th.start()
+        yield from _stream_records(s)
+    finally:
+        s.close()
+        if th.is_alive():
+            th.join(timeout=5)
+
+
+def synthesize_batch(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, **sampling):
+    """Client side of the batched request.  sampling: the optional keys of pack_batch_request (vocoder and vocoder_arithmetic
+    among them)."""
+    with socket.socket(socket.AF_UNIX, socket.SOCK_STREAM) as s:
+        s.connect(socket_path)
+        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, **sampling))
+        return read_batch_reply(s)

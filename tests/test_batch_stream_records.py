@@ -66,3 +66,36 @@ def test_error_and_unknown_records_raise():
                 bs.read_stream_record(r)
         finally:
             r.close()
+
+
+def test_new_entries_cuts_each_slots_new_frames():
+    """new_entries over two successive checks of three slots: slot 0 grows in both, slot 1 grows once and then finishes with
+    no new frame, slot 2 never has a frame and is not finished."""
+    codes = (np.arange(5 * 3 * 16, dtype=np.int64).reshape(5, 3, 16) * 7) % 2048       # [frames][B=3][16]
+    slots, pushed = [(0, 4), (1, 9), (2, 5)], [0, 0, 0]
+    first = bs.new_entries(codes, [2, 3, 0], slots, pushed, finished=[])
+    assert [(e.slot, e.utt, e.finished) for e in first] == [(0, 4, False), (1, 9, False)]      # nothing new, not finished: no entry
+    np.testing.assert_array_equal(first[0].frames, codes[0:2, 0, :])
+    np.testing.assert_array_equal(first[1].frames, codes[0:3, 1, :])
+    assert first[0].codes is None and first[1].codes is None and pushed == [2, 3, 0]
+    second = bs.new_entries(codes, [5, 3, 0], slots, pushed, finished={1})
+    assert [(e.slot, e.utt, e.finished) for e in second] == [(0, 4, False), (1, 9, True)]
+    np.testing.assert_array_equal(second[0].frames, codes[2:5, 0, :])                    # exactly codes[pushed:n]
+    assert second[0].frames.flags["C_CONTIGUOUS"] and second[0].codes is None
+    slot, utt, frames, finished, whole = second[1]                                       # (a push unpacks five values)
+    assert frames.shape == (0, 16) and finished                                          # finished with no new frame: empty slice
+    assert whole.dtype == np.int32 and whole.shape == (3, 16) and whole.flags["C_CONTIGUOUS"]
+    np.testing.assert_array_equal(whole, codes[0:3, 1, :])
+    assert pushed == [5, 3, 0]
+
+
+def test_the_wire_module_imports_no_engine_vocoder_or_loader():
+    import os
+    import subprocess
+    import sys
+    pkg = "qwen3_tts_axera_russian_amd"
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (f"import sys, {pkg}.batch_wire; "
+            f"print([m for m in ('hiplib', 'engine', 'vocoder') if '{pkg}.' + m in sys.modules])")
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, check=True, cwd=root)
+    assert out.stdout.strip() == "[]"

@@ -59,25 +59,25 @@ def test_prepare_queues_the_prompt_beside_the_tuple():
     srv = _server()
     ids = [[5, 6, 7], [9], [5, 6, 7]]
     items = srv._prepare(_msg(token_ids=ids, seed=3, prompt_codes=PROMPT, prompt_token_ids=[11, 12]))
-    assert [len(it) for it in items] == [4, 4, 4]                                  # the tuple keeps its shape
+    assert [it.feed for it in items] == [None, None, None]                         # no text feed: the plain utterance
     for it in items:
-        full = [11, 12] + ids[it[0]]
-        np.testing.assert_array_equal(it[1], srv.front.build_prefix(full))         # the prompt's text in front
-        assert it[2] == len(full)                                                  # n_text counts both
-        assert it[3].utt == it[0] and it[3].max_frames == CAP and it[3].seed == 3
+        full = [11, 12] + ids[it.utt]
+        np.testing.assert_array_equal(it.prefix, srv.front.build_prefix(full))         # the prompt's text in front
+        assert it.n_text == len(full)                                                  # n_text counts both
+        assert it.params.utt == it.utt and it.params.max_frames == CAP and it.params.seed == 3
         assert it.prompt.dtype == np.int32 and it.prompt.shape == (7, 16)
         np.testing.assert_array_equal(it.prompt, PROMPT)
         assert it.prefix_key == bs.prefix_key(b"prompt", full, PROMPT)
     # one prompt per utterance; an empty one is no prompt, and its key is the plain one
     items = srv._prepare(_msg(token_ids=ids, prompt_codes=[PROMPT.tolist(), [], OTHER.tolist()]))
-    by_utt = {it[0]: it for it in items}
+    by_utt = {it.utt: it for it in items}
     np.testing.assert_array_equal(by_utt[0].prompt, PROMPT)
     np.testing.assert_array_equal(by_utt[2].prompt, OTHER)
     assert by_utt[1].prompt is None and by_utt[1].prefix_key == bs.prefix_key(b"full", ids[1])
     assert by_utt[0].prefix_key != by_utt[2].prefix_key
     # without the keys nothing changes
     plain = srv._prepare(_msg(token_ids=ids, seed=3))
-    assert all(it.prompt is None and it.prefix_key == bs.prefix_key(b"full", ids[it[0]]) for it in plain)
+    assert all(it.prompt is None and it.prefix_key == bs.prefix_key(b"full", ids[it.utt]) for it in plain)
 
 
 def test_a_voice_stands_for_its_codes_and_text(tmp_path):
@@ -89,9 +89,9 @@ def test_a_voice_stands_for_its_codes_and_text(tmp_path):
     by_voice = srv._prepare(_msg(token_ids=ids, voice="anna"))
     inline = srv._prepare(_msg(token_ids=ids, prompt_codes=PROMPT))
     for a, b in zip(by_voice, inline):
-        np.testing.assert_array_equal(a[1], b[1])
+        np.testing.assert_array_equal(a.prefix, b.prefix)
         np.testing.assert_array_equal(a.prompt, b.prompt)
-        assert a[:1] + a[2:] == b[:1] + b[2:] and a.prefix_key == b.prefix_key
+        assert (a.utt, a.n_text, a.params, a.feed) == (b.utt, b.n_text, b.params, b.feed) and a.prefix_key == b.prefix_key
     (d / "ref_text.txt").write_text("spoken in the clip")
     codes, text = bs.load_voice(str(d))
     assert text == "spoken in the clip" and codes == PROMPT.tolist()
@@ -107,8 +107,8 @@ def test_a_voice_stands_for_its_codes_and_text(tmp_path):
     by_voice = srv._prepare(_msg(token_ids=ids, voice="anna"))
     inline = srv._prepare(_msg(token_ids=ids, prompt_codes=PROMPT, prompt_token_ids=[6, 2, 3, 4]))
     for a, b in zip(by_voice, inline):
-        np.testing.assert_array_equal(a[1], b[1])
-        assert a[2] == b[2] == 4 + len(ids[a[0]]) and a.prefix_key == b.prefix_key
+        np.testing.assert_array_equal(a.prefix, b.prefix)
+        assert a.n_text == b.n_text == 4 + len(ids[a.utt]) and a.prefix_key == b.prefix_key
 
 
 BAD = [
@@ -150,7 +150,7 @@ def test_the_longest_prompt_that_fits_is_queued():
     srv = _server()
     T = 96 - 12 - CAP                                    # n_ctx 96, 9 + 3 prefix rows, max_tokens CAP
     (it,) = srv._prepare(_msg(token_ids=[[5, 6, 7]], prompt_codes=np.zeros((T, 16), np.int32)))
-    assert it[1].shape[0] == 12 and it.prompt.shape == (T, 16)
+    assert it.prefix.shape[0] == 12 and it.prompt.shape == (T, 16)
 
 
 class PromptFakeEngine(FakeEngine):
@@ -172,8 +172,8 @@ def tagged_prepare(msg):
     base = bs.request_slot_params(msg, DEFAULTS, CAP)
     ids = msg["token_ids"]
     prompts = bs.request_prompt_codes(msg["prompt_codes"], len(ids)) if msg.get("prompt_codes") is not None else [None] * len(ids)
-    return [bs.QueuedUtterance((i, np.full((2, 4), t[0], np.float32), len(t), dataclasses.replace(base, utt=i)), None,
-                               prompts[i] if prompts[i] is not None and len(prompts[i]) else None) for i, t in enumerate(ids)]
+    return [bs.Utterance(i, np.full((2, 4), t[0], np.float32), len(t), dataclasses.replace(base, utt=i), prompt=prompts[i])
+            for i, t in enumerate(ids)]
 
 
 def make(eng, prepare, max_batch=2):

@@ -82,10 +82,10 @@ def fake_prepare(msg):
         raise ValueError("a request needs at least one utterance")
     base = bs.request_slot_params(msg, DEFAULTS, CAP)
     import dataclasses
-    return [(i, np.full((2, 4), t[0], np.float32), len(t), dataclasses.replace(base, utt=i)) for i, t in enumerate(ids)]
+    return [bs.Utterance(i, np.full((2, 4), t[0], np.float32), len(t), dataclasses.replace(base, utt=i)) for i, t in enumerate(ids)]
 
 
-def fake_reply(conn, cs, t0):
+def fake_reply(conn, cs, t0, state):
     try:
         conn.sendall(bs.pack_batch_reply([(c, c[:, 0].astype(np.int16)) for c in cs]))
     finally:
@@ -103,12 +103,12 @@ def fake_push(conn, state, resets, entries):
         if out:
             conn.sendall(b"".join(out))
     except OSError:
-        state["failed"] = True
+        state.failed = True
 
 
 def fake_close_stream(conn, state, t0):
     try:
-        if not state["failed"]:
+        if not state.failed:
             conn.sendall(P.pack_sentinel(P.SENTINEL_DONE))
     except OSError:
         pass
@@ -345,12 +345,12 @@ def test_a_client_that_stops_reading_fails_alone():
     """A streamed client that stays connected but never reads: the write to it times out, its request fails and its slot is
     released; the other request is answered meanwhile."""
     def big_push(conn, state, resets, entries):
-        if state["failed"]:
+        if state.failed:
             return
         try:
             conn.sendall(b"\0" * (8 << 20))                     # far more than the socket buffer
         except OSError:
-            state["failed"] = True
+            state.failed = True
 
     eng = FakeEngine(step_s=0.002)
     sched = bs.ConcurrentScheduler(eng, 2, 64, fake_prepare, fake_reply, big_push, fake_close_stream, send_error,

@@ -319,10 +319,10 @@ def test_server_text_hold_costs_the_other_request_nothing_and_changes_no_reply(g
         sched = srv.sched
         inner = sched._check_held
 
-        def spy(owner, ran, last_held):                      # a starved check while an ordinary request holds a slot?
+        def spy(ran):                                        # a starved check while an ordinary request holds a slot?
             before = sched.starved_checks
-            out = inner(owner, ran, last_held)
-            if sched.starved_checks > before and any(o is not None and o[0].feed is None for o in owner):
+            out = inner(ran)
+            if sched.starved_checks > before and any(o is not None and o[0].feed is None for o in sched._owner):
                 beside.append(ran)
             return out
         sched._check_held = spy

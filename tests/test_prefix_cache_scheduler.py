@@ -1,6 +1,7 @@
 """batch_server --concurrent --prefix_cache without a GPU: the keys the server derives (prefix_key, _prepare,
 _prepare_text_stream) and how ConcurrentScheduler hands them to the engine, against a stand-in engine in the style of
 tests/test_concurrent_scheduler.py.  CPU only."""
+import dataclasses
 import json
 
 import numpy as np
@@ -36,7 +37,7 @@ class KeyedFakeEngine(FakeEngine):
 
 def keyed_prepare(msg):
     """fake_prepare with the server's keys: the tag (first token id) rides in the prefix, the key covers all ids."""
-    return [bs.QueuedUtterance(it, bs.prefix_key(b"full", msg["token_ids"][it[0]])) for it in fake_prepare(msg)]
+    return [dataclasses.replace(it, prefix_key=bs.prefix_key(b"full", msg["token_ids"][it.utt])) for it in fake_prepare(msg)]
 
 
 def make(eng, prepare, prefix_cache, max_batch=2):
@@ -58,11 +59,11 @@ def test_prepare_attaches_the_key_of_each_utterance():
     srv = _bare_server()
     ids = [[5, 6, 7], [9], [5, 6, 7]]
     items = srv._prepare(json.loads(bs.pack_batch_request(token_ids=ids, seed=3)[4:].decode()))
-    assert [len(it) for it in items] == [4, 4, 4]                                  # the tuples the scheduler always took
-    assert [it.prefix_key for it in items] == [bs.prefix_key(b"full", ids[it[0]]) for it in items]
-    by_utt = {it[0]: it for it in items}
+    assert [it.feed for it in items] == [None, None, None]                         # the plain utterances the scheduler always took
+    assert [it.prefix_key for it in items] == [bs.prefix_key(b"full", ids[it.utt]) for it in items]
+    by_utt = {it.utt: it for it in items}
     assert by_utt[0].prefix_key == by_utt[2].prefix_key != by_utt[1].prefix_key   # two takes of one text share the prefill
-    assert (by_utt[0][3].utt, by_utt[2][3].utt) == (0, 2)                          # ... and keep their own draw streams
+    assert (by_utt[0].params.utt, by_utt[2].params.utt) == (0, 2)                          # ... and keep their own draw streams
     # a client cannot supply a key
     forged = dict(json.loads(bs.pack_batch_request(token_ids=ids)[4:].decode()), prefix_key="00" * 16, keys=["00" * 16] * 3)
     assert [it.prefix_key for it in srv._prepare(forged)] == [it.prefix_key for it in items]
@@ -73,7 +74,7 @@ def test_a_text_stream_key_depends_on_the_first_token_alone():
 
     def key(first_piece):
         (item,) = srv._prepare(json.loads(bs.pack_batch_request(token_ids=[first_piece], stream=True, text_stream=True)[4:].decode()))
-        assert len(item) == 5 and item[3].text_stream
+        assert item.feed is not None and item.params.text_stream
         return item.prefix_key
 
     assert key([5, 6, 7]) == key([5]) == key([5, 9, 9, 9]) == bs.prefix_key(b"stream", [5])
@@ -110,7 +111,7 @@ def test_keys_reach_admit_in_slot_order_and_the_counters_add_up():
 
 def test_an_item_without_a_key_is_admitted_uncached():
     eng = KeyedFakeEngine()
-    sched = make(eng, fake_prepare, prefix_cache=True)                              # plain tuples: no prefix_key attribute
+    sched = make(eng, fake_prepare, prefix_cache=True)                              # plain utterances: no prefix key
     cli = submit(sched, token_ids=[[21, 1], [21, 1]])
     sched.start()
     try:

@@ -88,7 +88,7 @@ def text_prepare(msg):
     first = msg["token_ids"][0]
     base = bs.request_slot_params(msg, DEFAULTS, CAP)
     feed = bs.TextFeed(project, None, None, first[1:], 1)
-    return [(0, np.full((8, 4), first[0], np.float32), 0, dataclasses.replace(base, utt=0, text_stream=True), feed)]
+    return [bs.Utterance(0, np.full((8, 4), first[0], np.float32), 0, dataclasses.replace(base, utt=0, text_stream=True), feed)]
 
 
 def make(eng, prepare=text_prepare, text_wait_ms=2000.0, max_batch=2, check_every=2):
@@ -214,6 +214,7 @@ def _bare_server(tokenizer=None):
     srv = object.__new__(bs.BatchSynthesisServer)
     srv.front, srv.tokenizer, srv.cfg = front, tokenizer, cfg
     srv.max_tokens, srv.max_batch, srv.max_request, srv.n_ctx, srv.defaults = CAP, 2, 16, 96, DEFAULTS
+    srv.text_voice = False
     return srv
 
 
@@ -241,7 +242,8 @@ def test_a_malformed_text_stream_request_gets_minus_two(bad):
 
 def test_a_well_formed_request_is_prepared_with_the_streaming_prefix():
     srv = _bare_server()
-    (utt, prefix, n_text, params, feed), = srv._prepare(json.loads(bs.pack_batch_request(**GOOD)[4:].decode()))
+    (it,) = srv._prepare(json.loads(bs.pack_batch_request(**GOOD)[4:].decode()))
+    utt, prefix, n_text, params, feed = it.utt, it.prefix, it.n_text, it.params, it.feed
     assert utt == 0 and n_text == 0 and params.text_stream and params.utt == 0
     np.testing.assert_array_equal(prefix, srv.front.build_prefix_stream(5))
     rows, final = feed.take()

@@ -46,20 +46,21 @@ def test_prepare_queues_one_prompted_text_slot():
     items = srv._prepare(_msg(**GOOD))
     assert len(items) == 1
     (it,) = items
-    assert len(it) == 5 and it[0] == 0 and it[2] == 0
-    np.testing.assert_array_equal(it[1], srv.front.build_prefix_stream(5, HEAD))       # the prefix of 8 + len(head) rows
-    assert it[1].shape[0] == 8 + len(HEAD)
-    assert it[3].text_stream and it[3].text_after_prompt and it[3].utt == 0 and it[3].seed == 3 and it[3].max_frames == CAP
-    it[3].check(CAP)
+    assert it.feed is not None and it.utt == 0 and it.n_text == 0
+    np.testing.assert_array_equal(it.prefix, srv.front.build_prefix_stream(5, HEAD))       # the prefix of 8 + len(head) rows
+    assert it.prefix.shape[0] == 8 + len(HEAD)
+    assert it.params.text_stream and it.params.text_after_prompt and it.params.utt == 0 and it.params.seed == 3
+    assert it.params.max_frames == CAP
+    it.params.check(CAP)
     assert it.prompt.dtype == np.int32
     np.testing.assert_array_equal(it.prompt, PROMPT)
     assert it.prefix_key == bs.prefix_key(b"stream", HEAD + [5], PROMPT)
-    feed = it[4]
+    feed = it.feed
     assert isinstance(feed, bs.TextFeed) and feed.n_tokens == len(HEAD) + 3            # what the unstreamed request passes
     unstreamed = _server()._prepare(_msg(token_ids=[[5, 6, 7]], prompt_codes=PROMPT, prompt_token_ids=HEAD))
-    assert unstreamed[0][2] == feed.n_tokens
+    assert unstreamed[0].n_text == feed.n_tokens
     rows, final = feed.take()
-    assert rows.shape == (2, it[1].shape[1]) and not final                             # tokens 6 and 7 ride on frames 0 and 1
+    assert rows.shape == (2, it.prefix.shape[1]) and not final                             # tokens 6 and 7 ride on frames 0 and 1
     feed.records(P.pack_text_record(P.TEXT_IDS, [8]) + P.pack_text_record(P.TEXT_END))
     rows, final = feed.take()
     assert rows.shape[0] == 2 and final and feed.n_tokens == len(HEAD) + 4
@@ -68,15 +69,15 @@ def test_prepare_queues_one_prompted_text_slot():
                                  bs.prefix_key(b"stream", HEAD[:-1] + [5], PROMPT), bs.prefix_key(b"stream", HEAD + [5], PROMPT[:-1]))
     # without a prompt text the prefix is the 8 rows of any text stream, the key still covers the codes
     (it,) = srv._prepare(_msg(**{k: v for k, v in GOOD.items() if k != "prompt_token_ids"}))
-    np.testing.assert_array_equal(it[1], srv.front.build_prefix_stream(5))
-    assert it.prefix_key == bs.prefix_key(b"stream", [5], PROMPT) and it[4].n_tokens == 3 and it[3].text_after_prompt
+    np.testing.assert_array_equal(it.prefix, srv.front.build_prefix_stream(5))
+    assert it.prefix_key == bs.prefix_key(b"stream", [5], PROMPT) and it.feed.n_tokens == 3 and it.params.text_after_prompt
     # an empty prompt is no prompt (the engine takes the bit without frames)
     (it,) = srv._prepare(_msg(**dict(GOOD, prompt_codes=[])))
-    assert it.prompt is None and it[3].text_after_prompt and it[1].shape[0] == 8 + len(HEAD)
+    assert it.prompt is None and it.params.text_after_prompt and it.prefix.shape[0] == 8 + len(HEAD)
     # a request without any prompt key is the text-stream request it always was
     (it,) = srv._prepare(_msg(token_ids=[[5, 6, 7]], stream=True, text_stream=True))
-    assert it.prompt is None and not it[3].text_after_prompt and it.prefix_key == bs.prefix_key(b"stream", [5])
-    np.testing.assert_array_equal(it[1], srv.front.build_prefix_stream(5))
+    assert it.prompt is None and not it.params.text_after_prompt and it.prefix_key == bs.prefix_key(b"stream", [5])
+    np.testing.assert_array_equal(it.prefix, srv.front.build_prefix_stream(5))
 
 
 def test_a_voice_stands_for_its_codes(tmp_path):
@@ -86,16 +87,16 @@ def test_a_voice_stands_for_its_codes(tmp_path):
     srv = _server(voices={"anna": bs.load_voice(str(d))})
     (a,) = srv._prepare(_msg(token_ids=[[5, 6]], stream=True, text_stream=True, voice="anna"))
     (b,) = srv._prepare(_msg(token_ids=[[5, 6]], stream=True, text_stream=True, prompt_codes=PROMPT))
-    np.testing.assert_array_equal(a[1], b[1])
+    np.testing.assert_array_equal(a.prefix, b.prefix)
     np.testing.assert_array_equal(a.prompt, b.prompt)
-    assert a.prefix_key == b.prefix_key and a[3] == b[3]
+    assert a.prefix_key == b.prefix_key and a.params == b.params
 
 
 def test_the_longest_prompt_that_fits_is_queued():
     srv = _server()
     T = N_CTX - 8 - len(HEAD) - CAP
     (it,) = srv._prepare(_msg(**dict(GOOD, prompt_codes=np.zeros((T, 16), np.int32))))
-    assert it.prompt.shape == (T, 16) and it[1].shape[0] == 8 + len(HEAD)
+    assert it.prompt.shape == (T, 16) and it.prefix.shape[0] == 8 + len(HEAD)
 
 
 BAD = [

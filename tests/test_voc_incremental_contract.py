@@ -104,7 +104,7 @@ def test_scheduler_refuses_a_bad_key_and_passes_a_good_one():
 
     def prepare(msg):
         bs.request_vocoder(msg)
-        return [(0, None, 1, None)]
+        return [bs.Utterance(0, None, 1, None)]
     errors = []
     sched = bs.ConcurrentScheduler(None, 2, 8, prepare, None, None, None, lambda conn: errors.append(conn))
     a, b = socket.socketpair()
@@ -113,7 +113,7 @@ def test_scheduler_refuses_a_bad_key_and_passes_a_good_one():
         c, d = socket.socketpair()
         assert sched.submit(c, {"vocoder": "incremental", "stream": True}) is True
         req, _ = sched._queue[0]
-        assert req.state["vocoder"] == "incremental" and req.stream
+        assert req.state.vocoder == "incremental" and req.stream
         c.close()
         d.close()
     finally:

@@ -44,7 +44,7 @@ def test_scheduler_answers_minus_two_and_carries_the_arithmetic():
 
     def prepare(msg):
         bs.request_vocoder_arithmetic(msg)
-        return [(0, None, 1, None)]
+        return [bs.Utterance(0, None, 1, None)]
     sched = bs.ConcurrentScheduler(None, 2, 8, prepare, None, None, None, bs.BatchSynthesisServer._send_error)
     try:
         for msg in ({"vocoder": "incremental", "vocoder_arithmetic": "half"}, {"vocoder_arithmetic": "split"},
@@ -58,7 +58,7 @@ def test_scheduler_answers_minus_two_and_carries_the_arithmetic():
             c, d = socket.socketpair()
             assert sched.submit(c, msg) is True
             req, _ = sched._queue[-1]
-            assert req.state["vocoder_arithmetic"] == want and req.state["vocoder"] == msg.get("vocoder", "walk")
+            assert req.state.arithmetic == want and req.state.vocoder == msg.get("vocoder", "walk")
             c.close()
             d.close()
     finally:
