@@ -28,7 +28,8 @@ extern "C" {
 
 /* weights: Q3TTSW1 container (or the HF snapshot's model.safetensors) holding text.embedding, text.fc{1,2}.{weight,bias}
  * and talker.codec_embedding; embeddings_dir: the reference's own embeddings/ directory instead (may be NULL).
- * max_tokens: longest text accepted by one call.  NULL on failure (message on stderr). */
+ * max_tokens: longest text accepted by one call.  The text dim and the projection's mid width must be 2048 or 3072, the hidden
+ * size a multiple of 128.  NULL on failure (message on stderr). */
 void* tfe_load(const char* weights, const char* embeddings_dir, int max_tokens);
 void tfe_free(void* h);
 int tfe_hidden_size(void* h);      /* 1024 */
@@ -40,7 +41,8 @@ int tfe_embed_text(void* h, const int32_t* token_ids, int n, float* out);
 /* _build_prefix: n text token ids (n >= 0) -> out[(n + 9)][hidden]; returns the number of rows, <0 on error.
  * `special` = the 12 ids {im_start, assistant, newline, tts_pad, tts_bos, tts_eos, codec_pad, codec_bos,
  * codec_nothink, codec_think_bos, codec_think_eos, 0} (llamacpp_talker_server.py:44-55,132); NULL = the
- * container's meta / the 0.6B defaults. */
+ * container's meta / the 0.6B defaults.  A text id outside the text table, or a codec id that is neither -1 (no codec
+ * row added) nor inside the codec table, is an error; the handle stays usable. */
 int tfe_build_prefix(void* h, const int32_t* text_token_ids, int n, const int32_t* special, float* out);
 
 /* The projected tts_pad row (tts_client.py:58-69 computes it once; q3e_set_pad_embed takes it). */

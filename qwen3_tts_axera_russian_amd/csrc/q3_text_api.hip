@@ -157,12 +157,22 @@ int project(TextFE* t, int R) {
     return 0;
 }
 
-int emit(TextFE* t, const std::vector<int>& ids, const std::vector<int>& src, const std::vector<int>& cod, float* out) {
-    const int R = (int)ids.size(), J = (int)src.size();
-    if (R > t->max_rows || J > t->max_rows) return -1;
+bool ids_in_table(const TextFE* t, const std::vector<int>& ids) {
     for (int id : ids)
         if (id < 0 || id >= t->V) {
             Q3_LOG("text front-end: token id %d outside the table of %d rows", id, t->V);
+            return false;
+        }
+    return true;
+}
+
+int emit(TextFE* t, const std::vector<int>& ids, const std::vector<int>& src, const std::vector<int>& cod, float* out) {
+    const int R = (int)ids.size(), J = (int)src.size();
+    if (R > t->max_rows || J > t->max_rows) return -1;
+    if (!ids_in_table(t, ids)) return -1;
+    for (int c : cod)   // (prefix_rows_kernel would drop the codec add of such a row and the call would still report success)
+        if (c != -1 && (c < 0 || c >= t->codec_vocab)) {
+            Q3_LOG("text front-end: codec id %d outside the codec table of %d rows", c, t->codec_vocab);
             return -1;
         }
     Q3_HIP(hipMemcpyAsync(t->d_ids, ids.data(), sizeof(int) * R, hipMemcpyHostToDevice, t->s), -1);
@@ -212,8 +222,11 @@ void* tfe_load(const char* weights, const char* embeddings_dir, int max_tokens) 
     t->codec_vocab = (int)ce->shape[0];
     const int mid = (int)w1->shape[0];
     if (te->ndim != 2 || (int)w1->shape[1] != t->TD || (int)w2->shape[1] != mid || (int)ce->shape[1] != t->H ||
-        (t->TD != 1024 && t->TD != 2048 && t->TD != 3072) || (mid != 1024 && mid != 2048 && mid != 3072) || t->H % 128 || mid % 128) {
-        Q3_LOG("tfe_load: unsupported geometry table [%d][%d] -> %d -> %d (the GEMM kernels take K in {1024, 2048, 3072}, N %% 128 == 0)",
+        (t->TD != 2048 && t->TD != 3072) || (mid != 2048 && mid != 3072) || t->H % 128 || mid % 128) {
+        // K = 1024 is not taken: launch_linear has no fp16-input / residual-epilogue instantiation for it, so every call of
+        // fewer than 65 projected rows (tfe_tts_pad_embed among them) would fail after a load that succeeded
+        Q3_LOG("tfe_load: unsupported geometry table [%d][%d] -> %d -> %d (the projection's kernels take K in {2048, 3072}, N %% 128 == 0; "
+               "below 65 rows there is no K = 1024 kernel with fp16 input and a residual epilogue)",
                t->V, t->TD, mid, t->H);
         delete t;
         return nullptr;
@@ -228,7 +241,8 @@ void* tfe_load(const char* weights, const char* embeddings_dir, int max_tokens) 
     ok = ok && (t->b1 = upload_f32(t, c1)) && (t->b2 = upload_f32(t, c2)) && (t->codec = upload_f32(t, ce));
     ok = ok && (t->x16 = (half_t*)dal(t, Rp * t->TD * 2)) && (t->a16 = (half_t*)dal(t, Rp * mid * 2));
     ok = ok && (t->h1 = (float*)dal(t, Rp * mid * 4)) && (t->h2 = (float*)dal(t, Rp * t->H * 4));
-    ok = ok && (t->ssq = (float*)dal(t, Rp * (mid / 16) * 4)) && (t->out = (float*)dal(t, Rp * t->H * 4));
+    // both projections store one sum-of-squares partial per 16 output columns: rows x max(mid, H) / 16 floats
+    ok = ok && (t->ssq = (float*)dal(t, Rp * ((mid > t->H ? mid : t->H) / 16) * 4)) && (t->out = (float*)dal(t, Rp * t->H * 4));
     ok = ok && (t->d_ids = (int*)dal(t, Rp * 4)) && (t->d_src = (int*)dal(t, Rp * 4)) && (t->d_cod = (int*)dal(t, Rp * 4));
     ok = ok && hipStreamSynchronize(t->s) == hipSuccess;   // the zeroing of dal()
     if (!ok) {
@@ -296,6 +310,34 @@ int tfe_tts_pad_embed(void* hh, float* out) {
     if (!t || !out) return -1;
     const int32_t id = t->special[3];
     return tfe_embed_text(t, &id, 1, out);
+}
+
+// Test hook (not in include/qwen3tts_text.h, like enc_debug_run / voc_debug_run): the projection of n ids, stage by stage.
+// Copies back the device buffers as they are, in fragment order, ceil(n / 16) * 16 rows each: x16 [rows][text dim] fp16,
+// h1 [rows][mid] f32, a16 [rows][mid] fp16, h2 [rows][hidden] f32.  dims (optional) = {text dim, mid, hidden, max_rows}.
+// Returns the number of rows copied, -1 on a refusal.
+int tfe_debug_stages(void* hh, const int32_t* token_ids, int n, uint16_t* x16, float* h1, uint16_t* a16, float* h2, int32_t* dims) {
+    TextFE* t = (TextFE*)hh;
+    if (!t) return -1;
+    if (dims) {
+        dims[0] = t->TD;
+        dims[1] = t->fc1.N;
+        dims[2] = t->H;
+        dims[3] = t->max_rows;
+    }
+    if (!token_ids || n <= 0) return dims ? 0 : -1;
+    if (!x16 || !h1 || !a16 || !h2 || n > t->max_rows) return -1;
+    std::vector<int> ids(token_ids, token_ids + n);
+    if (!ids_in_table(t, ids)) return -1;
+    Q3_HIP(hipMemcpyAsync(t->d_ids, ids.data(), sizeof(int) * n, hipMemcpyHostToDevice, t->s), -1);
+    if (project(t, n)) return -1;
+    const size_t Rp = ((size_t)n + 15) / 16 * 16, mid = (size_t)t->fc1.N;
+    Q3_HIP(hipMemcpyAsync(x16, t->x16, Rp * t->TD * 2, hipMemcpyDeviceToHost, t->s), -1);
+    Q3_HIP(hipMemcpyAsync(h1, t->h1, Rp * mid * 4, hipMemcpyDeviceToHost, t->s), -1);
+    Q3_HIP(hipMemcpyAsync(a16, t->a16, Rp * mid * 2, hipMemcpyDeviceToHost, t->s), -1);
+    Q3_HIP(hipMemcpyAsync(h2, t->h2, Rp * t->H * 4, hipMemcpyDeviceToHost, t->s), -1);
+    Q3_HIP(hipStreamSynchronize(t->s), -1);
+    return (int)Rp;
 }
 
 }  // extern "C"

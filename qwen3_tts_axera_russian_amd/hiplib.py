@@ -188,6 +188,8 @@ def load(path: str | None = None):
     _sig(lib, "tfe_tts_pad_embed", c_int, [c_void_p, f32p])
     _sig(lib, "tfe_build_prefix_stream", c_int, [c_void_p, ctypes.c_int32, i32p, f32p])
     _sig(lib, "tfe_tts_eos_embed", c_int, [c_void_p, f32p])
+    # test hook of csrc/q3_text_api.hip (not in the header): ids, n -> x16, h1, a16, h2 in fragment order, dims[4]
+    _sig(lib, "tfe_debug_stages", c_int, [c_void_p, i32p, c_int, u16p, f32p, u16p, f32p, i32p])
     _sig(lib, "q3_device_count", c_int, [])
     _sig(lib, "q3_device_compute_units", c_int, [])
     _sig(lib, "q3_set_device", c_int, [c_int])
