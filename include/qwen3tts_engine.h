@@ -233,6 +233,59 @@ int q3e_admit_prompted(void* e, int n, const int32_t* slots, const float* prefix
                        const int32_t* prompt_codes /* [sum T][16], utterance order */,
                        const int32_t* prompt_frames /* [n], 0 = none */);
 
+/* Sampler rules per slot (per-slot mode only).  Contract: every rule of the talker sampler that is a constant of
+ * llamacpp_talker_server.py:163-206 -- the repetition penalty 1.2 over the last 30 ids, the adaptive EOS boost of up to 15
+ * from 0.8 of the expected length, the forced EOS above 2.0 of it, no minimum length -- and the code predictor's missing
+ * nucleus cut become values of the slot.  The defaults ARE those constants (the penalty the same f32 1.2f, the others exact
+ * in f32): a slot with default rules, an admission without rules and an engine without a reservation give the same codes,
+ * bit for bit.
+ *   rep_penalty  finite, >= 1.  A penalised logit l becomes l / p when l > 0, else l * p (the reference's operations); 1
+ *                changes nothing, exactly.
+ *   rep_window   1..30: the ids penalised are the last min(emitted, w) of the utterance, a codec prompt's frames included.
+ *                0: EVERY id the utterance has emitted, prompt frames included -- the semantics of transformers'
+ *                RepetitionPenaltyLogitsProcessor over the emitted ids.  The engine keeps a set of emitted ids per slot
+ *                (one bit per audio id) for it; ids outside the audio vocabulary have no bit and are never emitted.
+ *   eos_boost    finite, >= 0: the boost is (float)(b * (double)eos_boost), b = min((progress - 0.8) / 0.7, 1) in double
+ *                as in the reference (0.8 and 0.7 stay constants); 0 adds nothing.
+ *   eos_force    finite, >= 0: EOS replaces the decision when progress > eos_force; 0 never forces.
+ *   min_frames   >= 0: until the utterance has GENERATED this many frames its EOS logit is -1e10 (as under ignore_eos):
+ *                no boost, and a forced EOS is not applied.  The budget still ends the utterance.
+ *   cp_top_p     (0, 1]: nucleus cut of the code predictor's stochastic draws, by the talker's rule (the smallest prefix
+ *                of the descending order whose mass reaches it); 1 = none; arg-max ignores it.
+ *   reserved     0.
+ * progress = (prompt frames + frames generated) / (3 * n_text) as before; a text slot's EOS mask and min_frames both put
+ * EOS at -1e10 and compose.
+ *
+ * q3e_default_rules: the defaults above into *out.
+ *
+ * q3e_rules_reserve(e, 1): call before q3e_open.  Allocates the rules entry and the emitted-id set of max_batch slots (24 +
+ * 256 bytes per slot at an audio vocabulary of 2048) and makes their pointers arguments of the captured frame, so the next
+ * q3e_run captures again and admitting a ruled utterance never does; 0 releases them.  <0 with nothing changed while a
+ * per-slot batch is open.  An engine that never calls it captures the frame it always did and launches the kernels it
+ * always did.
+ *
+ * q3e_admit_ruled: q3e_admit_prompted with a rules block per utterance.  rules == NULL, or a block equal to the defaults,
+ * is exactly q3e_admit_prompted; non-NULL rules without a reservation are refused.  Validation (the ranges above,
+ * non-finite values, reserved != 0, min_frames < 0) comes with q3e_admit's, before anything changes: a failed call leaves
+ * the slots, the cache and the emitted-id sets as they were.  Under a reservation every admission starts its slot with an
+ * empty set (then the prompt's ids) and default rules unless it brings its own: a recycled slot inherits nothing.  Rules do
+ * not enter what a prefill computes: the prefix cache and its key contract are untouched.  q3e_start / q3e_refill /
+ * q3e_set_sampling keep the constants.  0 ok / <0 error. */
+typedef struct q3e_slot_rules {
+    float rep_penalty;   /* >= 1, 1 = none            (reference: 1.2) */
+    int32_t rep_window;  /* 1..30 last ids, 0 = whole utterance (30)   */
+    float eos_boost;     /* >= 0, ceiling of the adaptive boost (15)   */
+    float eos_force;     /* progress above which EOS is forced, 0 = never (2) */
+    int32_t min_frames;  /* GENERATED frames before EOS may be chosen (0) */
+    float cp_top_p;      /* (0, 1], 1 = none (1) */
+    int32_t reserved[2]; /* 0 */
+} q3e_slot_rules;
+void q3e_default_rules(q3e_slot_rules* out);
+int q3e_rules_reserve(void* e, int on);
+int q3e_admit_ruled(void* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+                    const q3e_slot_params* params, const uint64_t* keys, int32_t* hit, const int32_t* prompt_codes,
+                    const int32_t* prompt_frames, const q3e_slot_rules* rules /* [n], or NULL */);
+
 /* Text streamed into a running utterance, row by row (per-slot mode only).
  *
  * Layout (a recollection of the model's streaming mode, which the reference does not implement -- it pre-computes the

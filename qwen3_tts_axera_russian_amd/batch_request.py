@@ -24,6 +24,14 @@ the chunk walk (the default) decodes the generated frames on their own.  A promp
 answered with -2 for that request alone, before any of it is queued.  Prompt text in front of the target text is a
 recollection of the model's in-context mode: parity with real weights is not pinned.  With `--prefix_cache` the key of a
 prompted utterance is of the kind b"prompt" and digests the ids and the prompt's codes.
+
+Sampler rules (`--concurrent --sampler_rules`): a request may carry "repetition_penalty" (>= 1), "repetition_window" (1..30
+last ids, 0 = every id the utterance has emitted), "eos_boost" (>= 0), "eos_force" (>= 0, 0 = never), "min_tokens" (frames
+generated before EOS may be chosen) and "cp_top_p" ((0, 1]) -- q3e_slot_rules, include/qwen3tts_engine.h -- and "sampler":
+"reference" (the defaults: the reference's constants, what a request without any of these keys gets) or "upstream"
+(SAMPLER_PRESETS: a recollection of the upstream model's generation settings, NOT pinned against its shipped config);
+explicit keys override the preset.  Every utterance of the request runs under the same rules.  Without the flag a request
+that carries any of these keys, and with it a wrong type or a value out of range, is answered -2 for that request alone.
 """
 from __future__ import annotations
 
@@ -38,6 +46,13 @@ VOCODER_MODES = ("walk", "incremental")
 VOCODER_ARITHMETICS = ("exact", "split")
 PROMPT_KEYS = ("prompt_codes", "prompt_token_ids", "prompt_text", "voice")
 _PARAM_KEYS = ("temperature", "top_k", "top_p", "cp_temperature", "cp_top_k", "seed")   # request keys = SlotParams fields
+# request key -> SlotRules field
+_RULE_KEYS = {"repetition_penalty": "rep_penalty", "repetition_window": "rep_window", "eos_boost": "eos_boost",
+              "eos_force": "eos_force", "min_tokens": "min_frames", "cp_top_p": "cp_top_p"}
+RULE_KEYS = tuple(_RULE_KEYS) + ("sampler",)
+# "upstream": a mild penalty over the whole emitted history, a minimum length, no length-based EOS heuristics -- as far as
+# this repository recollects the upstream model's generation settings; not pinned
+SAMPLER_PRESETS = {"reference": {}, "upstream": dict(rep_penalty=1.05, rep_window=0, eos_boost=0.0, eos_force=0.0, min_frames=2)}
 
 
 def prefix_key(kind, token_ids, prompt_codes=None):
@@ -62,6 +77,7 @@ class Utterance:
     feed: object = None             # TextFeed of a "text_stream" request
     prefix_key: bytes = None        # the prefix cache's key of its prefix (None: admitted uncached)
     prompt: np.ndarray = None       # its codec prompt [T][16] int32 (None: it has none; an empty one counts as none)
+    rules: object = None            # engine.SlotRules of a request with sampler rules (None: the defaults)
 
     def __post_init__(self):
         if self.prompt is not None and not len(self.prompt):
@@ -133,6 +149,46 @@ def load_voice(prompt_dir):
         with open(os.path.join(prompt_dir, "ref_text.txt")) as f:
             text = f.read()
     return codes.astype(np.int64).tolist(), text
+
+
+def request_has_rules(msg):
+    """Whether a request carries a sampler-rules key."""
+    return any(msg.get(k) is not None for k in RULE_KEYS)
+
+
+def request_slot_rules(msg, enabled):
+    """A request's sampler-rules keys -> engine.SlotRules, or None for a request without any of them.  The "sampler" preset
+    first, explicit keys over it.  Raises ValueError on such a key when the server runs without --sampler_rules (`enabled`
+    false), on an unknown preset, a wrong type or a value out of range."""
+    from .engine import SlotRules
+    if not request_has_rules(msg):
+        return None
+    if not enabled:
+        raise ValueError("sampler rules need a --concurrent --sampler_rules server")
+    kw = {}
+    preset = msg.get("sampler")
+    if preset is not None:
+        if not isinstance(preset, str) or preset not in SAMPLER_PRESETS:
+            raise ValueError(f"sampler must be one of {tuple(SAMPLER_PRESETS)} (got {preset!r})")
+        kw.update(SAMPLER_PRESETS[preset])
+    for key, field in _RULE_KEYS.items():
+        v = msg.get(key)
+        if v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{key} must be a number (got {v!r})")
+        if field in ("rep_window", "min_frames"):
+            if not (isinstance(v, int) or float(v).is_integer()):
+                raise ValueError(f"{key} must be an integer (got {v!r})")
+            kw[field] = int(v)
+        else:
+            try:
+                kw[field] = float(v)
+            except OverflowError:       # (a JSON integer beyond the doubles)
+                raise ValueError(f"{key} is out of range (got {v!r})") from None
+    rules = SlotRules(**kw)
+    rules.check()
+    return rules
 
 
 def request_slot_params(msg, defaults, max_tokens_cap):

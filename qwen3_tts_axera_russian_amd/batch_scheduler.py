@@ -422,6 +422,8 @@ class ConcurrentScheduler:
         slots = free[:len(take)]
         args = (slots, [it.prefix for _, it in take], [it.n_text for _, it in take], [it.params for _, it in take])
         kw = {"prompts": [it.prompt for _, it in take]} if any(it.prompt is not None for _, it in take) else {}
+        if any(it.rules is not None for _, it in take):     # (a server with --sampler_rules: eng.rules() was called)
+            kw["rules"] = [it.rules for _, it in take]
         if self.prefix_cache:
             hit = self.eng.admit(*args, keys=[it.prefix_key for _, it in take], **kw)
             self.prefix_hits += int(np.count_nonzero(hit))

@@ -34,6 +34,14 @@ prompted request of the same texts does, and its prefix key is prefix_key(b"stre
 The vocoder follows the streamed reply of a prompted request.  `--text_hold`, `--text_wait_ms` and `--prefix_cache` work as
 they do for any text-stream request; the wire protocol has no new record.  Without the flag such a request is answered -2.
 
+`--sampler_rules` (with `--concurrent`): the engine reserves a sampler-rules entry and an emitted-id set per slot
+(q3e_rules_reserve, before the scheduler opens the batch), and a request may then set the rules its utterances are sampled
+under -- "repetition_penalty", "repetition_window", "eos_boost", "eos_force", "min_tokens", "cp_top_p", or a "sampler" preset
+(batch_request says which values, and that "upstream" is a recollection) -- through q3e_admit_ruled.  A request without these
+keys, or with the default values spelled out, gets the reply it gets without the flag, bit for bit; the per-request output
+names a rule set that is not the default.  Without the flag a request that carries any of the keys is answered -2; the wire
+protocol has no new record.
+
 `--voice_warm N` (with `--concurrent`; default 0 = off): the incremental vocoder's warm-up per codec prompt is cached in N
 snapshot slots of the vocoder handle (voice_warm.VoiceWarmCache, which says how).  A hit pushes no prompt frame: all hits of one
 check go into one voc_incr_restore, and an unstreamed reply starts from the slot (synthesize_incremental(start_slot=)).  Several slots admitted together with the same new
@@ -62,7 +70,7 @@ import numpy as np
 from . import hiplib
 from . import protocol as P
 from .batch_request import (PROMPT_KEYS, VOCODER_ARITHMETICS, VOCODER_MODES, Utterance, load_voice, prefix_key,  # noqa: F401
-                            request_has_prompt, request_prompt_codes, request_slot_params, request_vocoder,
+                            request_has_prompt, request_prompt_codes, request_slot_params, request_slot_rules, request_vocoder,
                             request_vocoder_arithmetic)
 from .batch_scheduler import ConcurrentScheduler, PushEntry, ReplyState, TextFeed, new_entries  # noqa: F401
 from .batch_wire import (REC_AUDIO, REC_END, pack_batch_reply, pack_batch_request, pack_stream_audio,  # noqa: F401
@@ -76,11 +84,13 @@ from .weights import ModelConfig, read_pack
 
 
 class BatchSynthesisServer:
+    sampler_rules = False      # --sampler_rules: requests may carry sampler rules (set by __init__)
+
     def __init__(self, model_path, vocoder_path, socket_path="/tmp/qwen3_batch.sock", max_batch=32, n_ctx=512,
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
                  cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=0,
-                 prefix_cache_rows=64, voices=None, text_voice=False, voice_warm=0):
+                 prefix_cache_rows=64, voices=None, text_voice=False, voice_warm=0, sampler_rules=False):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens, self.n_ctx = socket_path, max_batch, max_tokens, n_ctx
@@ -100,11 +110,13 @@ class BatchSynthesisServer:
                 (prefix_cache and alone, "--prefix_cache serves the per-slot admissions of the shared frame loop: it needs --concurrent"),
                 (voices and alone, "--voice names codec prompts of the shared frame loop's admissions: it needs --concurrent"),
                 (text_voice and alone, "--text_voice lets text slots of the shared frame loop continue a codec prompt: it needs --concurrent"),
+                (sampler_rules and alone, "--sampler_rules sets the sampler rules of the shared frame loop's slots: it needs --concurrent"),
                 (int(voice_warm) < 0, "--voice_warm takes a number of snapshot slots >= 0"),
                 (voice_warm and alone, "--voice_warm caches the vocoder warm-up of the shared frame loop's codec prompts: it needs --concurrent")):
             if bad:
                 raise ValueError(message)
         self.text_hold, self.text_voice = bool(text_hold), bool(text_voice)
+        self.sampler_rules = bool(sampler_rules)
         self.prefix_cache, self.prefix_cache_rows = int(prefix_cache), int(prefix_cache_rows)
         self.voices = {name: load_voice(d) for name, d in dict(voices or {}).items()}   # name -> (codes [T][16], text or None)
         self.sched = None
@@ -339,11 +351,14 @@ class BatchSynthesisServer:
         prompt, if it has one); raises on anything malformed, before any of it is queued."""
         request_vocoder_arithmetic(msg)      # (checks "vocoder" too)
         base = request_slot_params(msg, self.defaults, self.max_tokens)
+        rules = request_slot_rules(msg, self.sampler_rules)
+        if rules is not None and not rules.is_default():
+            print(f"  sampler rules: {rules}")
         prompted = request_has_prompt(msg)
         if msg.get("text_stream"):
             if prompted:
                 self._check_text_voice(msg)
-            return [self._prepare_text_stream(msg, base)]
+            return [dataclasses.replace(self._prepare_text_stream(msg, base), rules=rules)]
         ids = self._token_ids(msg)
         prompts = [None] * len(ids)
         if prompted:     # a codec prompt: its text (if any) in front of every utterance's, its frames behind every prefix
@@ -356,7 +371,7 @@ class BatchSynthesisServer:
                 raise ValueError("prefix + codec prompt + max_tokens exceed n_ctx (or the rows of one prefill pass)")
         return [Utterance(i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i),
                           prefix_key=prefix_key(b"prompt", ids[i], prompts[i]) if prompted and len(prompts[i]) else
-                          prefix_key(b"full", ids[i]), prompt=prompts[i]) for i in order]
+                          prefix_key(b"full", ids[i]), prompt=prompts[i], rules=rules) for i in order]
 
     def _check_text_voice(self, msg):
         if msg.get("text_stream") and not self.text_voice:
@@ -476,6 +491,7 @@ class BatchSynthesisServer:
                     raise ValueError('"text_stream" needs a --concurrent server')
                 if request_has_prompt(msg):
                     raise ValueError("a codec prompt needs a --concurrent server")
+                request_slot_rules(msg, False)
                 if msg.get("stream"):
                     # streamed reply: the worker writes every record and closes the connection
                     ids = self._token_ids(msg)
@@ -515,6 +531,8 @@ class BatchSynthesisServer:
             self.eng.hold_text()                 # a text slot without a row is held inside the frame: the others step on
         if self.prefix_cache:
             self.eng.prefix_cache(self.prefix_cache, self.prefix_cache_rows)
+        if self.sampler_rules:
+            self.eng.rules()                     # the rules entry and the emitted-id set of every slot: arguments of the frame
         self.sched = ConcurrentScheduler(self.eng, self.max_batch, self.max_queue, self._prepare, self._finish, self._push,
                                          self._close_stream, self._send_error, check_every=self.check_every,
                                          send_timeout=self.send_timeout, text_wait_ms=self.text_wait_ms,
@@ -595,6 +613,9 @@ def main():
                     help="--concurrent: entries of the device prefix cache (0 = off): an utterance whose prefix is cached is "
                          "admitted without a prefill, with the same reply")
     ap.add_argument("--prefix_cache_rows", type=int, default=64, help="--prefix_cache: prefix rows an entry can hold")
+    ap.add_argument("--sampler_rules", action="store_true",
+                    help="--concurrent: requests may set their sampler rules (repetition_penalty, repetition_window, eos_boost, "
+                         "eos_force, min_tokens, cp_top_p, sampler: reference / upstream)")
     ap.add_argument("--voice", action="append", default=[], metavar="NAME=DIR",
                     help="--concurrent: a codec prompt requests may name with \"voice\": \"NAME\"; DIR as "
                          "encode_reference_audio --output_dir writes it (repeatable)")
@@ -613,7 +634,7 @@ def main():
                                send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms, text_hold=a.text_hold,
                                prefix_cache=a.prefix_cache, prefix_cache_rows=a.prefix_cache_rows,
                                voices=dict(v.split("=", 1) for v in a.voice), text_voice=a.text_voice,
-                               voice_warm=a.voice_warm)
+                               voice_warm=a.voice_warm, sampler_rules=a.sampler_rules)
     try:
         srv.serve()
     finally:

@@ -40,11 +40,14 @@ REC_AUDIO, REC_END = 1, 2     # the records of a streamed reply
 def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False, temperature=None,
                        top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None,
                        vocoder_arithmetic=None, text_stream=False, prompt_codes=None, prompt_token_ids=None, prompt_text=None,
-                       voice=None) -> bytes:
+                       voice=None, sampler=None, repetition_penalty=None, repetition_window=None, eos_boost=None, eos_force=None,
+                       min_tokens=None, cp_top_p=None) -> bytes:
     """The request of the batched protocol; the sampling keys (honoured by --concurrent), the vocoder mode ("walk" /
     "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given.  text_stream: the
     request carries only the first piece of its one utterance's text; the rest follows as text records.  prompt_codes ([T][16], or
-    one such per utterance), prompt_token_ids / prompt_text, voice: the codec prompt the utterances continue (--concurrent)."""
+    one such per utterance), prompt_token_ids / prompt_text, voice: the codec prompt the utterances continue (--concurrent).
+    sampler ("reference" / "upstream"), repetition_penalty, repetition_window, eos_boost, eos_force, min_tokens, cp_top_p: the
+    request's sampler rules (--concurrent --sampler_rules; batch_request)"""
     msg = {"language": language}
     if stream:
         msg["stream"] = True
@@ -64,7 +67,9 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
     for key, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("cp_temperature", cp_temperature),
                    ("cp_top_k", cp_top_k), ("seed", seed), ("vocoder", vocoder), ("vocoder_arithmetic", vocoder_arithmetic),
                    ("prompt_codes", prompt_codes), ("prompt_token_ids", prompt_token_ids), ("prompt_text", prompt_text),
-                   ("voice", voice)):
+                   ("voice", voice), ("sampler", sampler), ("repetition_penalty", repetition_penalty),
+                   ("repetition_window", repetition_window), ("eos_boost", eos_boost), ("eos_force", eos_force),
+                   ("min_tokens", min_tokens), ("cp_top_p", cp_top_p)):
         if v is not None:
             msg[key] = v
     raw = json.dumps(msg).encode()

@@ -25,6 +25,7 @@ struct CpFrameIO {
     const unsigned long long* seed_ptr = nullptr;  // device array [rows] overriding `seed`: one draw stream per slot (engine: per request and per refill)
     const int* forced = nullptr;                   // teacher forcing (tests): see TalkerSampleArgs
     const SlotParams* slots = nullptr;             // per-slot mode (engine): overrides temperature / top_k / seed per row
+    const SlotRules* rules = nullptr;              // per-slot sampler rules (see CpArgmaxArgs); null = none
 };
 
 // Runs positions 0..n_groups, writes columns 1..n_groups of each row's frame.  Rows row0..row0+R-1 of a batch of

@@ -129,6 +129,7 @@ int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const C
         x.forced = io.forced;
         x.slots = io.slots;
         x.held = io.held;
+        x.rules = io.rules;
         if (g + 1 < G) {
             x.next_table = m.cp_emb[g];  // group g+1 embeds token g with CP table g (:134)
             x.h_out = w.h;

@@ -74,6 +74,13 @@ struct Engine {
     // the other rows step on
     bool hold = false;
     int* d_held = nullptr;                  // [max_batch] the sampler's per-step verdict, read by the frame's cp_argmax launches
+    // per-slot sampler rules (q3e_rules_reserve / q3e_admit_ruled): the rules entry and the set of emitted ids of every
+    // slot; both null without a reservation, and then no argument of the frame
+    SlotRules* d_rules = nullptr;           // [max_batch]
+    unsigned* d_seen = nullptr;             // [max_batch][seen_words]
+    int seen_words = 0;                     // (cp_vocab + 31) / 32: one bit per audio id
+    std::vector<SlotRules> h_rules_default; // [max_batch] defaults, the source of reset_rows' uploads (outlives the stream's copies)
+    int graph_rules = -1;
     // prefix cache of the per-slot admissions (q3e_prefix_cache / q3e_admit_keyed): a device pool of entries, each the KV
     // rows of one prefix and the residual row its final norm reads; the index keeps the keys and the use order
     // (q3_engine_host.h).  Nothing of it is an argument of the captured frame.
@@ -169,6 +176,10 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
         sa.text_avail = e->d_tavail;
         sa.held = e->d_held;
     }
+    if (e->slot_mode && e->d_rules) {
+        sa.rules = e->d_rules;
+        sa.seen = e->d_seen;
+    }
     if (launch_talker_sample(st, sa)) return -1;
     CpFrameIO io;
     io.codes = e->d_codes;
@@ -191,6 +202,7 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     io.seed_ptr = e->d_seed;   // (the group index separates the talker's and the code predictor's draws)
     io.forced = e->forced_on ? e->d_forced : nullptr;
     io.slots = e->slot_mode ? e->d_slots : nullptr;
+    io.rules = e->slot_mode ? e->d_rules : nullptr;
     if (cp_frame(st, m, e->wc, e->kv_c, R, io, row0, e->B)) return -1;
     RowMap rm;
     rm.slot_base = 0;        // row r of the batch owns KV slot r (no table: one dependent load less in front of every attention)
@@ -288,7 +300,7 @@ void q3e_free(void* ee) {
     work_free(e->wc);
     void* ps[] = {e->d_tiles, e->d_slot, e->d_pos,  e->d_iota,   e->d_past,    e->d_npast, e->d_ntext, e->d_done,
                   e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots,
-                  e->d_text, e->d_tavail, e->d_held, e->d_pfx, e->d_pfx_state, e->d_prompt};
+                  e->d_text, e->d_tavail, e->d_held, e->d_pfx, e->d_pfx_state, e->d_prompt, e->d_rules, e->d_seen};
     for (void* p : ps)
         if (p) hipFree(p);
     if (e->h_done) hipHostFree(e->h_done);
@@ -453,6 +465,10 @@ static int prompt_launch(Engine* e, int slot, int T, int row0, bool rows) {
     a.cp_vocab = m.cfg.cp_vocab;
     a.n_groups = m.cfg.cp_groups;
     a.pad_embed = e->d_pad;
+    if (e->d_seen) {   // (reset_rows has cleared the slot's set)
+        a.seen = e->d_seen + (size_t)(slot < 0 ? 0 : slot) * e->seen_words;
+        a.seen_vocab = m.cfg.cp_vocab;   // (the sampler's audio_vocab, frame_chain)
+    }
     if (rows) {
         a.h = e->wt.h;
         a.ssq = e->wt.ssq;
@@ -534,7 +550,8 @@ static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, co
 //   fresh  "just started": counters 0, an empty emitted-token ring, positions n_rows[0..n), text lengths n_text[0..n) (null:
 //          0 -- a text slot's comes with its final push); host arrays that must live until the stream is synchronised
 //   idle   ended (done) with the frame counter at the end of the codes array, so nothing is recorded, at position 0
-// and either way the rows' columns of the codes array to -1 and no text row pushed, no hold.
+// and either way the rows' columns of the codes array to -1 and no text row pushed, no hold; under q3e_rules_reserve an empty
+// seen-set and default rules: a recycled slot inherits neither the previous utterance's history nor its rules.
 enum class RowStart { fresh, idle };
 static int reset_rows(Engine* e, int b0, int n, RowStart how, const int32_t* n_rows = nullptr, const int32_t* n_text = nullptr) {
     const bool idle = how == RowStart::idle;
@@ -559,6 +576,10 @@ static int reset_rows(Engine* e, int b0, int n, RowStart how, const int32_t* n_r
     }
     if (e->d_tavail) Q3_HIP(hipMemsetAsync(e->d_tavail + b0, 0, bytes, e->s), -1);
     if (e->d_held) Q3_HIP(hipMemsetAsync(e->d_held + b0, 0, bytes, e->s), -1);
+    if (e->d_rules) {
+        Q3_HIP(hipMemsetAsync(e->d_seen + (size_t)b0 * e->seen_words, 0, sizeof(unsigned) * (size_t)n * e->seen_words, e->s), -1);
+        Q3_HIP(hipMemcpyAsync(e->d_rules + b0, e->h_rules_default.data(), sizeof(SlotRules) * n, hipMemcpyHostToDevice, e->s), -1);
+    }
     return 0;
 }
 
@@ -628,7 +649,7 @@ int q3e_run(void* ee, int n_frames) {
     static const bool no_graph = getenv("Q3_NO_GRAPH") && atoi(getenv("Q3_NO_GRAPH")) != 0;
     const bool need_capture = !e->graph[0].e || e->graph_B != e->B || e->graph_ignore != e->ignore_eos ||
                               e->graph_cap != e->cap_frames || e->graph_chains != nc ||
-                              e->graph_slots != (int)e->slot_mode;
+                              e->graph_slots != (int)e->slot_mode || e->graph_rules != (int)(e->d_rules != nullptr);
     if (no_graph) {
         for (; done_frames < n_frames; done_frames++)
             if (frame_eager(e)) return -1;
@@ -649,6 +670,7 @@ int q3e_run(void* ee, int n_frames) {
         e->graph_cap = e->cap_frames;
         e->graph_chains = nc;
         e->graph_slots = (int)e->slot_mode;
+        e->graph_rules = (int)(e->d_rules != nullptr);
     }
     const int check_every = 16;
     const auto th0 = std::chrono::steady_clock::now();
@@ -815,15 +837,32 @@ static int prefix_move(Engine* e, int i, int slot, int n_rows, int h_row, int re
     return launch_prefix_move(e->s, a);
 }
 
-// q3e_admit (keys == NULL), q3e_admit_keyed (prompt_frames == NULL) and q3e_admit_prompted
+// what is wrong with a rules block (q3e_admit_ruled's ranges), or null
+static const char* rules_error(const q3e_slot_rules& r) {
+    if (!(std::isfinite(r.rep_penalty) && r.rep_penalty >= 1.f)) return "rep_penalty must be finite and >= 1";
+    if (r.rep_window < 0 || r.rep_window > 30) return "rep_window must be 0..30";
+    if (!(std::isfinite(r.eos_boost) && r.eos_boost >= 0.f)) return "eos_boost must be finite and >= 0";
+    if (!(std::isfinite(r.eos_force) && r.eos_force >= 0.f)) return "eos_force must be finite and >= 0";
+    if (r.min_frames < 0) return "min_frames must be >= 0";
+    if (!(r.cp_top_p > 0.f && r.cp_top_p <= 1.f)) return "cp_top_p must be in (0, 1]";
+    if (r.reserved[0] || r.reserved[1]) return "reserved must be 0";
+    return nullptr;
+}
+
+// q3e_admit (keys == NULL), q3e_admit_keyed (prompt_frames == NULL), q3e_admit_prompted (rules == NULL) and q3e_admit_ruled
 static int admit_slots(Engine* e, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
                        const q3e_slot_params* params, const uint64_t* keys, int32_t* hit, const int32_t* prompt_codes,
-                       const int32_t* prompt_frames) {
+                       const int32_t* prompt_frames, const q3e_slot_rules* rules = nullptr) {
     if (!e || !e->slot_mode || n <= 0 || n > e->B || !slots || !prefix || !n_rows || !n_text || !params) {
         if (e && !e->slot_mode) Q3_LOG("q3e_admit: the batch was not opened with q3e_open");
         return -1;
     }
+    if (rules && !e->d_rules) {
+        Q3_LOG("q3e_admit_ruled: no sampler rules are reserved (q3e_rules_reserve)");
+        return -1;
+    }
     std::vector<SlotParams> sp(n);
+    std::vector<SlotRules> kr(rules ? n : 0);        // the rules entries as the kernels read them
     std::vector<int32_t> n_prompt(n, 0), n_tot(n);   // prompt frames, and the rows the utterance's pass prefills
     size_t n_codes = 0;
     for (int u = 0; u < n; u++) {
@@ -854,6 +893,20 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
             !(p.top_p > 0.f && p.top_p <= 1.f)) {
             Q3_LOG("q3e_admit: utterance %d: temperatures must be finite and >= 0, top_p in (0, 1]", u);
             return -1;
+        }
+        if (rules) {
+            const q3e_slot_rules& q = rules[u];
+            if (const char* why = rules_error(q)) {
+                Q3_LOG("q3e_admit_ruled: utterance %d: %s", u, why);
+                return -1;
+            }
+            kr[u].rep_penalty = q.rep_penalty;
+            kr[u].rep_window = q.rep_window;
+            kr[u].eos_boost = q.eos_boost;
+            kr[u].eos_force = q.eos_force;
+            // counted as the device counts: the prompt's frames are in n_past (saturating: the sum never wraps)
+            kr[u].min_past = q.min_frames > INT32_MAX - n_prompt[u] ? INT32_MAX : n_prompt[u] + q.min_frames;
+            kr[u].cp_top_p = q.cp_top_p;
         }
         sp[u].max_frames = n_prompt[u] + p.max_frames;   // the device counts the prompt's frames with the emitted ones (n_past)
         sp[u].t_temp = p.temperature;
@@ -887,6 +940,8 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
         for (int u = 0; u < n; u++) {   // (a text slot's n_text comes with its final push)
             if (reset_rows(e, slots[u], 1, RowStart::fresh, n_rows + u, sp[u].flags ? nullptr : n_text + u)) return -1;
             Q3_HIP(hipMemcpyAsync(e->d_slots + slots[u], &sp[u], sizeof(SlotParams), hipMemcpyHostToDevice, e->s), -1);
+            // (reset_rows has written the defaults)
+            if (rules) Q3_HIP(hipMemcpyAsync(e->d_rules + slots[u], &kr[u], sizeof(SlotRules), hipMemcpyHostToDevice, e->s), -1);
         }
         Q3_HIP(hipStreamSynchronize(e->s), -1);
         // one prefill per utterance: the ragged prefill's tiles follow the rows of its pass, so sharing a pass with another
@@ -944,6 +999,56 @@ int q3e_admit_prompted(void* ee, int n, const int32_t* slots, const float* prefi
                        const q3e_slot_params* params, const uint64_t* keys, int32_t* hit, const int32_t* prompt_codes,
                        const int32_t* prompt_frames) {
     return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, keys, hit, prompt_codes, prompt_frames);
+}
+
+int q3e_admit_ruled(void* ee, int n, const int32_t* slots, const float* prefix, const int32_t* n_rows, const int32_t* n_text,
+                    const q3e_slot_params* params, const uint64_t* keys, int32_t* hit, const int32_t* prompt_codes,
+                    const int32_t* prompt_frames, const q3e_slot_rules* rules) {
+    return admit_slots((Engine*)ee, n, slots, prefix, n_rows, n_text, params, keys, hit, prompt_codes, prompt_frames, rules);
+}
+
+void q3e_default_rules(q3e_slot_rules* out) {
+    if (!out) return;
+    const SlotRules d;   // the constants of llamacpp_talker_server.py:163-206
+    out->rep_penalty = d.rep_penalty;
+    out->rep_window = d.rep_window;
+    out->eos_boost = d.eos_boost;
+    out->eos_force = d.eos_force;
+    out->min_frames = 0;
+    out->cp_top_p = d.cp_top_p;
+    out->reserved[0] = out->reserved[1] = 0;
+}
+
+int q3e_rules_reserve(void* ee, int on) {
+    Engine* e = (Engine*)ee;
+    if (!e) return -1;
+    if (e->slot_mode) {
+        Q3_LOG("q3e_rules_reserve: a per-slot batch is open (call before q3e_open)");
+        return -1;
+    }
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    if ((on != 0) == (e->d_rules != nullptr)) return 0;
+    for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointers
+    if (e->d_rules) hipFree(e->d_rules);
+    if (e->d_seen) hipFree(e->d_seen);
+    e->d_rules = nullptr;
+    e->d_seen = nullptr;
+    if (!on) return 0;
+    e->seen_words = (e->m->cfg.cp_vocab + 31) / 32;
+    e->h_rules_default.assign(e->max_batch, SlotRules());
+    const size_t seen_bytes = sizeof(unsigned) * (size_t)e->max_batch * e->seen_words;
+    if (hipMalloc((void**)&e->d_rules, sizeof(SlotRules) * e->max_batch) != hipSuccess ||
+        hipMalloc((void**)&e->d_seen, seen_bytes) != hipSuccess) {
+        Q3_LOG("q3e_rules_reserve: allocation failed");
+        if (e->d_rules) hipFree(e->d_rules);
+        e->d_rules = nullptr;
+        e->d_seen = nullptr;
+        return -1;
+    }
+    Q3_HIP(hipMemcpyAsync(e->d_rules, e->h_rules_default.data(), sizeof(SlotRules) * e->max_batch, hipMemcpyHostToDevice, e->s), -1);
+    Q3_HIP(hipMemsetAsync(e->d_seen, 0, seen_bytes, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    return 0;
 }
 
 int q3e_prefix_cache(void* ee, int n_entries, int max_rows) {

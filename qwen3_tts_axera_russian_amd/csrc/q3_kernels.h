@@ -153,6 +153,20 @@ struct SlotParams {
                                    // the frames it generated, n_past - prompt (n_frames and the text rows already do)
 };
 
+// Per-slot sampler rules (q3e_rules_reserve / q3e_admit_ruled): one entry per row of the batch, in an array of its own
+// beside SlotParams.  A sampling kernel given a non-null `rules` array reads the row's entry where it otherwise uses the
+// constants of llamacpp_talker_server.py:163-206; the defaults below ARE those constants (the penalty the same f32, the
+// others exact in f32), so a row with default rules gives the bits of a launch without the array.  Written by the host
+// between launches only.
+struct SlotRules {
+    float rep_penalty = 1.2f;      // talker: finite, >= 1; replaces TalkerSampleArgs::rep_penalty for the row (1: none, exact)
+    int rep_window = 30;           // 1..30: the last min(n_past, w) ids of the ring; 0: every id in the row's seen-set
+    float eos_boost = 15.f;        // ceiling of the adaptive EOS boost, finite, >= 0 (0: nothing is added)
+    float eos_force = 2.f;         // EOS is forced when progress > this; 0: never
+    int min_past = 0;              // while n_past < min_past the EOS logit is -1e10f (as under ignore_eos) and no EOS is forced
+    float cp_top_p = 1.f;          // code predictor: nucleus cut of the stochastic path, (0, 1]; 1: none
+};
+
 // Talker sampling (llamacpp_talker_server.py:163-206, greedy form).
 struct TalkerSampleArgs {
     int tl_node = -1;  // diagnostic timeline build only: graph node index
@@ -191,6 +205,14 @@ struct TalkerSampleArgs {
     // reads a logit: no counter, code, ring entry or position of the row changes.  Every other row clears held[r].
     const int* text_avail = nullptr;    // [R_total] rows pushed per slot (written by the host between launches)
     int* held = nullptr;                // [R_total] 1: the row is held in this step (read by the frame's cp_argmax launches)
+    // per-slot mode with sampler rules (q3e_rules_reserve; both null: the constants, and the kernel of a launch without
+    // them).  rules[r] replaces rep_penalty, the window of 30, the boost of 15, the forced EOS above 2.0 and "no minimum"
+    // for row r (SlotRules).  seen[r] is the row's set of emitted ids, one bit per audio id in (audio_vocab + 31) / 32
+    // words: whenever it is given, the launch sets the bit of the id the stream continues with where it writes the ring
+    // (ids outside [0, audio_vocab) have no bit), for every row whatever its window; a held row, an ended row and a row
+    // outside the launch write nothing.  rep_window == 0 reads it, and so needs it.
+    const SlotRules* rules = nullptr;   // [R_total]
+    unsigned* seen = nullptr;           // [R_total][(audio_vocab + 31) / 32]
 };
 int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a);
 
@@ -240,6 +262,9 @@ struct CpArgmaxArgs {
     // row continue with the id its current frame already records in this group's column, and store nothing: the gather,
     // the q|k|v copy and the feedback sum then repeat what they produced when that frame was first computed.
     const int* held = nullptr;          // [R_total]
+    // per-slot mode with sampler rules (null: none): rules[r].cp_top_p is the nucleus cut of row r's stochastic draw
+    // (block_sample_topk's top_p; without rules there is none).  The arg-max path ignores it.
+    const SlotRules* rules = nullptr;   // [R_total]
 };
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a);
 
@@ -254,13 +279,16 @@ int launch_feedback(hipStream_t s, const int* codes16, int R, const float* talke
 //     own) -- goes to row row0 + i of the fragment-ordered h / ssq / xh, with the sum-of-squares partials and the pre-scaled
 //     fp16 copy launch_ssq_rows gives a row of these values: the prefill reads it where it reads an uploaded row;
 //   - the sampler's state of the slot: column 0 of the last min(T, 32) frames into the emitted-token ring at i & 31, and
-//     n_past = T.
+//     n_past = T; with seen != null, the bit of column 0 of EVERY frame into the slot's seen-set (TalkerSampleArgs::seen;
+//     the caller has cleared it): the workgroups share words, so each sets its bit with a vector atomic OR.
 // The caller has checked the ids (column 0 < talker_vocab, the others < cp_vocab, none negative) and row0 + T <= max_rows.
 struct PromptRowsArgs {
     const int* codes = nullptr;   // device [T][16]
     int T = 0;
     int* past = nullptr;          // the slot's ring [32]
     int* n_past = nullptr;        // the slot's counter
+    unsigned* seen = nullptr;     // the slot's seen-set [(seen_vocab + 31) / 32], or null
+    int seen_vocab = 0;           // the sampler's audio_vocab: ids outside [0, seen_vocab) have no bit
     const float* talker_emb = nullptr;
     int talker_vocab = 0;
     const float* const* cp_tables = nullptr;   // device array [n_groups]

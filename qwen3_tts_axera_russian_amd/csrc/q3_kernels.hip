@@ -2073,8 +2073,23 @@ __device__ __forceinline__ SlotParams uniform_slot(const SlotParams* p, int r) {
     return sp;
 }
 
+// The row's entry of the per-slot rules array (q3e_admit_ruled writes it before the launch): scalar loads, as uniform_slot
+__device__ __forceinline__ SlotRules uniform_rules(const SlotRules* p, int r) {
+    static_assert(sizeof(SlotRules) % 4 == 0, "SlotRules is read as words");
+    constexpr int NW = (int)(sizeof(SlotRules) / 4);
+    const __attribute__((address_space(4))) int* q = (const __attribute__((address_space(4))) int*)(p + r);
+    int w[NW];
+#pragma unroll
+    for (int i = 0; i < NW; i++) w[i] = q[i];
+    SlotRules ru;
+    __builtin_memcpy(&ru, w, sizeof(ru));
+    return ru;
+}
+
 // SLOTS: per-slot mode -- budget, temperature, top-k, top-p and draw key of the row come from a.slots[r]
-template <bool SLOTS>
+// RULES (with SLOTS): a.rules[r] / a.seen[r] where given (TalkerSampleArgs); a kernel of its own, so that a launch without
+// them runs the code it always did
+template <bool SLOTS, bool RULES = false>
 __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
     Q3_TL(42);
     __shared__ float sv[16];
@@ -2107,9 +2122,28 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
             if (held) return;
         }
     }
-    if (threadIdx.x == 0) nwin = np < 30 ? np : 30;
-    if (threadIdx.x < 30 && threadIdx.x < np) {
-        // last 30 emitted tokens (ring of 32)
+    // the rules of the row: the launch's constants, or the row's entry of a.rules (all uniform)
+    float rep_penalty = a.rep_penalty;
+    int rep_window = 30;
+    double eos_boost = 15.0, eos_force = 2.0;
+    bool add_boost = true, may_force = true, eos_early = false;   // eos_early: n_past < min_past, EOS cannot be chosen yet
+    const unsigned* seen_row = nullptr;   // rep_window 0: the repetition test reads the row's seen-set, not the ring
+    if constexpr (RULES) {
+        if (a.rules) {
+            const SlotRules ru = uniform_rules(a.rules, r);
+            rep_penalty = ru.rep_penalty;
+            rep_window = ru.rep_window < 0 ? 0 : ru.rep_window > 30 ? 30 : ru.rep_window;   // (win holds 32)
+            eos_boost = (double)ru.eos_boost;
+            eos_force = (double)ru.eos_force;
+            add_boost = ru.eos_boost != 0.f;
+            may_force = ru.eos_force != 0.f;
+            eos_early = np < ru.min_past;
+            if (rep_window == 0) seen_row = a.seen + (size_t)r * ((a.audio_vocab + 31) / 32);
+        }
+    }
+    if (threadIdx.x == 0) nwin = np < rep_window ? np : rep_window;
+    if (threadIdx.x < rep_window && threadIdx.x < np) {
+        // last 30 (rep_window) emitted tokens (ring of 32)
         win[threadIdx.x] = a.past[r * 32 + ((np - 1 - threadIdx.x) & 31)];
     }
     __syncthreads();
@@ -2123,10 +2157,11 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
         if (progress > 0.8) {
             double b = (progress - 0.8) / 0.7;
             if (b > 1.0) b = 1.0;
-            boost = (float)(b * 15.0);
+            boost = (float)(b * eos_boost);
         }
-        if (progress > 2.0) force_eos = true;
+        if (may_force && progress > eos_force) force_eos = true;
     }
+    const bool eos_masked = a.ignore_eos || (SLOTS && (slot_flags & 2)) || (RULES && eos_early);
     float best = -INFINITY;
     int bidx = 0x7fffffff;
     const int nw_ = nwin;
@@ -2138,12 +2173,14 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
         float l = nan_as_inf(a.logits[(size_t)r * a.V + v]);
         if (v >= a.audio_vocab && v != a.eos) l = -1e10f;
         if (v == a.eos) {
-            if (a.ignore_eos || (SLOTS && (slot_flags & 2))) l = -1e10f;
-            else if (nt > 0 && progress > 0.8) l += boost;
+            if (eos_masked) l = -1e10f;
+            else if (nt > 0 && progress > 0.8 && add_boost) l += boost;
         }
         bool rep = false;
         for (int i = 0; i < nw_; i++) rep |= (win[i] == v);
-        if (rep) l = l > 0.f ? __fdiv_rn(l, a.rep_penalty) : l * a.rep_penalty;
+        if constexpr (RULES)   // (written by earlier launches of this kernel: a vector load, not a scalar one)
+            if (seen_row && v < a.audio_vocab) rep = (seen_row[v >> 5] >> (v & 31)) & 1u;
+        if (rep) l = l > 0.f ? __fdiv_rn(l, rep_penalty) : l * rep_penalty;
         if (stochastic) slg[v] = l;
         if (l > best || (l == best && v < bidx)) {
             best = l;
@@ -2166,7 +2203,7 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
     }
     if (threadIdx.x == 0) {
         int code = bidx;
-        if (force_eos && !a.ignore_eos && !(SLOTS && (slot_flags & 2))) code = a.eos;
+        if (force_eos && !eos_masked) code = a.eos;
         bool fin = was_done || code == a.eos || code >= a.audio_vocab || (max_frames > 0 && np >= max_frames);
         const int f = a.n_frames[r];
         // per-slot batches live as long as the server: an ended row's counter stops one past the codes array (frame_cap + 1,
@@ -2186,6 +2223,10 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
         } else {
             fc[0] = code;
             a.past[r * 32 + (np & 31)] = used;
+            if constexpr (RULES)   // one workgroup owns the row: a plain read-modify-write (every read of the loop above is
+                                   // behind the barriers of the winner's reduction)
+                if (a.seen && used >= 0 && used < a.audio_vocab)
+                    a.seen[(size_t)r * ((a.audio_vocab + 31) / 32) + (used >> 5)] |= 1u << (used & 31);
             a.n_past[r] = np + 1;
             a.pos[r] = a.pos0[r] + np;
         }
@@ -2193,6 +2234,7 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
 }
 __global__ void talker_sample_kernel(TalkerSampleArgs a) { talker_sample_row<false>(a); }
 __global__ void talker_sample_kernel_slots(TalkerSampleArgs a) { talker_sample_row<true>(a); }
+__global__ void talker_sample_kernel_rules(TalkerSampleArgs a) { talker_sample_row<true, true>(a); }
 
 // per-slot mode: any row may take the sort path, so its LDS is reserved whatever the rows ask for (admitting a request
 // never changes the captured launch)
@@ -2204,6 +2246,12 @@ int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a) {
     if ((a.text_avail && !a.held) || ((a.text_avail || a.held) && !a.slots)) {
         Q3_LOG("talker_sample: text_avail / held need each other and per-slot mode (text_avail %p, held %p, slots %p)",
                (const void*)a.text_avail, (const void*)a.held, (const void*)a.slots);
+        return -1;
+    }
+    // sampler rules are a per-slot feature too; a window of 0 reads the seen-set, so rules come with one
+    if ((a.rules || a.seen) && (!a.slots || (a.rules && !a.seen) || a.audio_vocab <= 0)) {
+        Q3_LOG("talker_sample: rules need seen, and both per-slot mode (rules %p, seen %p, slots %p)", (const void*)a.rules,
+               (const void*)a.seen, (const void*)a.slots);
         return -1;
     }
     if (a.slots && a.V > SAMPLE_SORT_CAP) {
@@ -2218,7 +2266,8 @@ int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a) {
     const size_t lds = a.slots ? sample_lds_bytes_slots(a.V) : sample_lds_bytes(a.V, a.top_k, a.temperature);
     TalkerSampleArgs a2 = a;
     a2.tl_node = tl_next_node();
-    if (a.slots) hipLaunchKernelGGL(talker_sample_kernel_slots, dim3(a.R), dim3(256), lds, s, a2);
+    if (a.rules || a.seen) hipLaunchKernelGGL(talker_sample_kernel_rules, dim3(a.R), dim3(256), lds, s, a2);
+    else if (a.slots) hipLaunchKernelGGL(talker_sample_kernel_slots, dim3(a.R), dim3(256), lds, s, a2);
     else hipLaunchKernelGGL(talker_sample_kernel, dim3(a.R), dim3(256), lds, s, a2);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
@@ -2265,7 +2314,8 @@ __device__ __forceinline__ void feedback_row(const int* codes, int r, const floa
 
 // One workgroup per row: the 2048 logits arrive as two float4 per thread (one round trip), one barrier
 // picks the winner, then the next embedding row is gathered (second round trip).
-template <bool SLOTS>
+// RULES (with SLOTS): a.rules[r].cp_top_p cuts the stochastic draw; a kernel of its own, as for the talker
+template <bool SLOTS, bool RULES = false>
 __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     if constexpr (SLOTS)
         Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
@@ -2354,7 +2404,9 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
         } else {
             u = uniform01(a.seed_ptr ? a.seed_ptr[r] : a.seed, (unsigned)r, (unsigned)nf_r, 1u + (unsigned)a.group);
         }
-        bidx = block_sample_topk(slg, a.V, top_k, temperature, 0.f, u, sv2, si2, selv, seli);
+        float top_p = 0.f;   // no nucleus cut (code_predictor_server.py has none)
+        if constexpr (RULES) top_p = uniform_rules(a.rules, r).cp_top_p;
+        bidx = block_sample_topk(slg, a.V, top_k, temperature, top_p, u, sv2, si2, selv, seli);
     }
     if (bidx < 0 || bidx >= a.V) bidx = 0;   // every logit -inf: numpy's argmax answers 0; never gather with an invalid winner
     int f = nf_r - 1;
@@ -2431,6 +2483,7 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
 }
 __global__ void __launch_bounds__(256) cp_argmax_kernel(CpArgmaxArgs a) { cp_argmax_row<false>(a); }
 __global__ void __launch_bounds__(256) cp_argmax_kernel_slots(CpArgmaxArgs a) { cp_argmax_row<true>(a); }
+__global__ void __launch_bounds__(256) cp_argmax_kernel_rules(CpArgmaxArgs a) { cp_argmax_row<true, true>(a); }
 
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a) {
     if (a.R <= 0) return 0;
@@ -2445,6 +2498,10 @@ int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a) {
                (const void*)a.text_avail, a.text_cap, (const void*)a.held, (const void*)a.slots);
         return -1;
     }
+    if (a.rules && !a.slots) {
+        Q3_LOG("cp_argmax: rules need per-slot mode (rules %p, slots %p)", (const void*)a.rules, (const void*)a.slots);
+        return -1;
+    }
     if (a.slots && a.V > SAMPLE_SORT_CAP) {
         Q3_LOG("cp_argmax: a vocabulary of %d is beyond the per-slot sampler (sort cap %d)", a.V, SAMPLE_SORT_CAP);
         return -1;
@@ -2457,7 +2514,8 @@ int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a) {
     const size_t lds = a.slots ? sample_lds_bytes_slots(a.V) : sample_lds_bytes(a.V, a.top_k, a.temperature);
     CpArgmaxArgs a2 = a;
     a2.tl_node = tl_next_node();
-    if (a.slots) hipLaunchKernelGGL(cp_argmax_kernel_slots, dim3(a.R), dim3(256), lds, s, a2);
+    if (a.rules) hipLaunchKernelGGL(cp_argmax_kernel_rules, dim3(a.R), dim3(256), lds, s, a2);
+    else if (a.slots) hipLaunchKernelGGL(cp_argmax_kernel_slots, dim3(a.R), dim3(256), lds, s, a2);
     else hipLaunchKernelGGL(cp_argmax_kernel, dim3(a.R), dim3(256), lds, s, a2);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
@@ -2487,6 +2545,8 @@ __global__ void __launch_bounds__(256) prompt_rows_kernel(PromptRowsArgs a) {
     if (threadIdx.x == 0) {
         if (i >= a.T - 32) a.past[i & 31] = codes[0];
         if (i == a.T - 1) a.n_past[0] = a.T;
+        // the seen-set takes every frame; workgroups share its words: a vector atomic on global memory
+        if (a.seen && codes[0] >= 0 && codes[0] < a.seen_vocab) atomicOr(a.seen + (codes[0] >> 5), 1u << (codes[0] & 31));
     }
     if (a.h)
         feedback_row(codes, a.row0 + i, a.talker_emb, a.talker_vocab, a.cp_tables, a.cp_vocab, a.n_groups, a.pad_embed,
@@ -2495,7 +2555,7 @@ __global__ void __launch_bounds__(256) prompt_rows_kernel(PromptRowsArgs a) {
 int launch_prompt_rows(hipStream_t s, const PromptRowsArgs& a) {
     if (a.T <= 0) return 0;
     if (!a.codes || !a.past || !a.n_past || !a.talker_emb || !a.cp_tables || a.n_groups <= 0 || a.n_groups > 15 ||
-        (a.h && (!a.ssq || a.row0 < 0 || a.row0 + a.T > a.max_rows || a.H <= 0 || a.H % 16))) {
+        (a.seen && a.seen_vocab <= 0) || (a.h && (!a.ssq || a.row0 < 0 || a.row0 + a.T > a.max_rows || a.H <= 0 || a.H % 16))) {
         Q3_LOG("launch_prompt_rows: bad arguments (%d frames at row %d of %d)", a.T, a.row0, a.max_rows);
         return -1;
     }

@@ -530,12 +530,17 @@ static int talker_sample_case(const float* logits, int V, int R_total, int row0,
                               const int* n_text, int* done, int* n_frames, const int* pos0, int* pos, int* codes,
                               int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos, int max_frames,
                               float rep_penalty, float temperature, int top_k, float top_p, unsigned long long seed,
-                              const unsigned long long* seed_ptr, const void* slots, const int* text_avail, int* held) {
+                              const unsigned long long* seed_ptr, const void* slots, const int* text_avail, int* held,
+                              const void* rules = nullptr, unsigned* seen = nullptr) {
     if (!logits || V <= 0 || R < 0 || row0 < 0 || row0 + R > R_total || frame_cap < 0 || eos < 0 || eos >= V) return -2;
+    if (seen && audio_vocab <= 0) return -2;
+    const size_t seen_words = seen ? (size_t)R_total * ((audio_vocab + 31) / 32) : 0;
     for (int r = row0; r < row0 + R; r++)
         if (n_frames[r] < 0 || n_past[r] < 0) return -2;
     const size_t rt = (size_t)R_total, nc = (size_t)frame_cap * rt * 16;
-    DBuf dl, dpast, dn, dnt, ddone, dcodes, dnf, dpos0, dpos, dforced, dseed, dslots, dtav, dheld;
+    DBuf dl, dpast, dn, dnt, ddone, dcodes, dnf, dpos0, dpos, dforced, dseed, dslots, dtav, dheld, drules, dseen;
+    if (rules && !drules.up(rules, rt * sizeof(SlotRules))) return -1000;
+    if (seen && !dseen.up(seen, seen_words * 4)) return -1000;
     if (text_avail && !dtav.up(text_avail, rt * 4)) return -1000;
     if (held && !dheld.up(held, rt * 4)) return -1000;
     if (!dl.up(logits, rt * V * 4) || !dpast.up(past, rt * 32 * 4) || !dn.up(n_past, rt * 4) || !dnt.up(n_text, rt * 4) ||
@@ -574,6 +579,8 @@ static int talker_sample_case(const float* logits, int V, int R_total, int row0,
     a.slots = slots ? (const SlotParams*)dslots.p : nullptr;
     a.text_avail = text_avail ? (const int*)dtav.p : nullptr;
     a.held = held ? (int*)dheld.p : nullptr;
+    a.rules = rules ? (const SlotRules*)drules.p : nullptr;
+    a.seen = seen ? (unsigned*)dseen.p : nullptr;
     if (const int rc = launch_talker_sample(nullptr, a)) return rc;
     Q3_HIP(hipDeviceSynchronize(), -1000);
     Q3_HIP(hipMemcpy(past, dpast.p, rt * 32 * 4, hipMemcpyDeviceToHost), -1000);
@@ -583,6 +590,7 @@ static int talker_sample_case(const float* logits, int V, int R_total, int row0,
     Q3_HIP(hipMemcpy(pos, dpos.p, rt * 4, hipMemcpyDeviceToHost), -1000);
     Q3_HIP(hipMemcpy(codes, dcodes.p, nc * 4, hipMemcpyDeviceToHost), -1000);
     if (held) Q3_HIP(hipMemcpy(held, dheld.p, rt * 4, hipMemcpyDeviceToHost), -1000);
+    if (seen) Q3_HIP(hipMemcpy(seen, dseen.p, seen_words * 4, hipMemcpyDeviceToHost), -1000);
     return 0;
 }
 extern "C" int q3t_talker_sample_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
@@ -606,6 +614,18 @@ extern "C" int q3t_talker_sample_text_case(const float* logits, int V, int R_tot
                               forced, audio_vocab, eos, ignore_eos, max_frames, rep_penalty, temperature, top_k, top_p, seed,
                               seed_ptr, slots, text_avail, held);
 }
+// q3t_talker_sample_text_case with sampler rules (TalkerSampleArgs::rules / seen): rules = SlotRules[R_total] in,
+// seen[R_total][(audio_vocab + 31) / 32] in and out, whole.  Either may be null (the launcher's refusals).
+extern "C" int q3t_talker_sample_rules_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
+                                            const int* n_text, int* done, int* n_frames, const int* pos0, int* pos, int* codes,
+                                            int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos,
+                                            int max_frames, float rep_penalty, float temperature, int top_k, float top_p,
+                                            unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
+                                            const int* text_avail, int* held, const void* rules, unsigned* seen) {
+    return talker_sample_case(logits, V, R_total, row0, R, past, n_past, n_text, done, n_frames, pos0, pos, codes, frame_cap,
+                              forced, audio_vocab, eos, ignore_eos, max_frames, rep_penalty, temperature, top_k, top_p, seed,
+                              seed_ptr, slots, text_avail, held, rules, seen);
+}
 
 // One launch_cp_argmax, state in and out on host arrays (layouts as in q3t_talker_sample_case).  epilogue 0: none;
 // 1: gather of next_table[V][H] (+ next_qkv[V][qkv_ld] -> qkv_out[R_total][qkv_ld] when non-null); 2: the feedback sum
@@ -619,7 +639,7 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
                           const float* next_table, const float* next_qkv, int qkv_ld, const float* gamma,
                           const float* talker_emb, int talker_vocab, const float* cp_tables, int n_groups, const float* pad,
                           float* h_out, float* ssq_out, uint16_t* xh_out, float* qkv_out, const float* text_rows,
-                          const int* text_avail, int text_cap, const int* held) {
+                          const int* text_avail, int text_cap, const int* held, const void* rules = nullptr) {
     if (!logits || V <= 0 || R < 0 || row0 < 0 || row0 + R > R_total || frame_cap < 1 || group < 0 || group > 14 ||
         epilogue < 0 || epilogue > 2)
         return -2;
@@ -637,7 +657,8 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
             if (text_avail[r] < 0 || text_avail[r] > text_cap) return -2;
     const size_t rt = (size_t)R_total, nc = (size_t)frame_cap * rt * 16;
     const int Rp = (R_total + 15) / 16 * 16;   // fragment order: blocks of 16 rows
-    DBuf dl, dcodes, dnf, dforced, dseed, dslots, dtab, dqkv, dgam, dtemb, dcpt, dcptp, dpad, dh, dssq, dxh, dqo, dtrows, dtav, dheld;
+    DBuf dl, dcodes, dnf, dforced, dseed, dslots, dtab, dqkv, dgam, dtemb, dcpt, dcptp, dpad, dh, dssq, dxh, dqo, dtrows, dtav, dheld, drules;
+    if (rules && !drules.up(rules, rt * sizeof(SlotRules))) return -1000;
     if (text_rows && !dtrows.up(text_rows, rt * (size_t)(text_cap > 0 ? text_cap : 1) * (H > 0 ? H : 1) * 4)) return -1000;
     if (text_avail && !dtav.up(text_avail, rt * 4)) return -1000;
     if (held && !dheld.up(held, rt * 4)) return -1000;
@@ -666,6 +687,7 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
     a.text_avail = text_avail ? (const int*)dtav.p : nullptr;
     a.text_cap = text_cap;
     a.held = held ? (const int*)dheld.p : nullptr;
+    a.rules = rules ? (const SlotRules*)drules.p : nullptr;
     std::vector<float> hh;
     std::vector<uint16_t> hx;
     if (epilogue) {
@@ -747,6 +769,19 @@ extern "C" int q3t_cp_sample_text_case(const float* logits, int V, int R_total, 
     return cp_sample_case(logits, V, R_total, row0, R, group, codes, n_frames, frame_cap, forced, temperature, top_k, seed,
                           seed_ptr, slots, epilogue, H, next_table, next_qkv, qkv_ld, gamma, talker_emb, talker_vocab, cp_tables,
                           n_groups, pad, h_out, ssq_out, xh_out, qkv_out, text_rows, text_avail, text_cap, held);
+}
+// q3t_cp_sample_text_case with sampler rules (CpArgmaxArgs::rules): rules = SlotRules[R_total], or null.
+extern "C" int q3t_cp_sample_rules_case(const float* logits, int V, int R_total, int row0, int R, int group, int* codes,
+                                        const int* n_frames, int frame_cap, const int* forced, float temperature, int top_k,
+                                        unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
+                                        int epilogue, int H, const float* next_table, const float* next_qkv, int qkv_ld,
+                                        const float* gamma, const float* talker_emb, int talker_vocab, const float* cp_tables,
+                                        int n_groups, const float* pad, float* h_out, float* ssq_out, uint16_t* xh_out,
+                                        float* qkv_out, const float* text_rows, const int* text_avail, int text_cap,
+                                        const int* held, const void* rules) {
+    return cp_sample_case(logits, V, R_total, row0, R, group, codes, n_frames, frame_cap, forced, temperature, top_k, seed,
+                          seed_ptr, slots, epilogue, H, next_table, next_qkv, qkv_ld, gamma, talker_emb, talker_vocab, cp_tables,
+                          n_groups, pad, h_out, ssq_out, xh_out, qkv_out, text_rows, text_avail, text_cap, held, rules);
 }
 
 // ---- launch-boundary microbenchmark: a dependent chain of n small kernels, captured as a graph ----
@@ -1214,10 +1249,10 @@ extern "C" int q3t_feedback_case(const int* codes16, int R, const float* talker_
 // gamma -- xh, which come back for those rows; with_h == 0 passes h = null (only the ring and the counter may change).
 // null_table: 1 passes talker_emb = null, 2 cp_tables = null (the launcher's refusals).  A refusal (-1) still brings the ring
 // and the counter back and checks every guard.  Guards and the other return codes as q3t_final_norm_case.
-extern "C" int q3t_prompt_rows_case(const int* codes, int T, int* past, int* n_past, const float* talker_emb, int talker_vocab,
-                                    const float* cp_tables, int n_tab, int cp_vocab, int n_groups, const float* pad, int H,
-                                    int row0, int max_rows, int buf_rows, int with_h, const float* gamma, float* h, float* ssq,
-                                    uint16_t* xh, int null_table) {
+static int prompt_rows_case(const int* codes, int T, int* past, int* n_past, const float* talker_emb, int talker_vocab,
+                            const float* cp_tables, int n_tab, int cp_vocab, int n_groups, const float* pad, int H,
+                            int row0, int max_rows, int buf_rows, int with_h, const float* gamma, float* h, float* ssq,
+                            uint16_t* xh, int null_table, unsigned* seen, int seen_vocab) {
     if (!codes || T <= 0 || !past || !n_past || !talker_emb || talker_vocab <= 0 || !cp_tables || n_tab < 1 || n_tab > 15 ||
         cp_vocab <= 0 || H <= 0 || H % 32 || row0 < 0 || buf_rows < row0 + T)
         return -2;
@@ -1228,7 +1263,9 @@ extern "C" int q3t_prompt_rows_case(const int* codes, int T, int* past, int* n_p
             if (codes[i * 16 + g] < 0 || codes[i * 16 + g] >= (g ? cp_vocab : talker_vocab)) return -2;
     std::vector<int> cpad((size_t)T * 16 + 16, 0);   // (one frame of slack behind the ids)
     memcpy(cpad.data(), codes, (size_t)T * 16 * 4);
-    DBuf dc, dpast, dn, de, dtab, dptrs, dpad, dg;
+    DBuf dc, dpast, dn, de, dtab, dptrs, dpad, dg, dseen;
+    const size_t seen_words = seen_vocab > 0 ? ((size_t)seen_vocab + 31) / 32 : 0;
+    if (seen && (seen_vocab <= 0 || !dseen.up(seen, seen_words * 4))) return seen_vocab <= 0 ? -2 : -1;
     if (!dc.up(cpad.data(), cpad.size() * 4) || !dpast.up(past, 32 * 4) || !dn.up(n_past, 4) ||
         !de.up(talker_emb, (size_t)talker_vocab * H * 4) || !upload_tables(cp_tables, n_tab, cp_vocab, H, dtab, dptrs))
         return -1;
@@ -1256,14 +1293,33 @@ extern "C" int q3t_prompt_rows_case(const int* codes, int T, int* past, int* n_p
     a.row0 = row0;
     a.max_rows = max_rows;
     a.H = H;
+    a.seen = seen ? (unsigned*)dseen.p : nullptr;
+    a.seen_vocab = seen ? seen_vocab : 0;
     Q3_HIP(hipDeviceSynchronize(), -1);
     const int rc = launch_prompt_rows(nullptr, a);
     Q3_HIP(hipDeviceSynchronize(), -1);
+    if (seen) Q3_HIP(hipMemcpy(seen, dseen.p, seen_words * 4, hipMemcpyDeviceToHost), -1);
     Q3_HIP(hipMemcpy(past, dpast.p, 32 * 4, hipMemcpyDeviceToHost), -1);
     Q3_HIP(hipMemcpy(n_past, dn.p, 4, hipMemcpyDeviceToHost), -1);
     const bool built = with_h && rc == 0;
     const int c = o.collect([&](int r) { return built && r >= row0 && r < row0 + T; }, h, ssq, xh);
     return c < 0 ? -1 : c ? -3 : rc;
+}
+extern "C" int q3t_prompt_rows_case(const int* codes, int T, int* past, int* n_past, const float* talker_emb, int talker_vocab,
+                                    const float* cp_tables, int n_tab, int cp_vocab, int n_groups, const float* pad, int H,
+                                    int row0, int max_rows, int buf_rows, int with_h, const float* gamma, float* h, float* ssq,
+                                    uint16_t* xh, int null_table) {
+    return prompt_rows_case(codes, T, past, n_past, talker_emb, talker_vocab, cp_tables, n_tab, cp_vocab, n_groups, pad, H, row0,
+                            max_rows, buf_rows, with_h, gamma, h, ssq, xh, null_table, nullptr, 0);
+}
+// q3t_prompt_rows_case with the slot's seen-set (PromptRowsArgs::seen / seen_vocab): seen[(seen_vocab + 31) / 32] in and out.
+extern "C" int q3t_prompt_rows_seen_case(const int* codes, int T, int* past, int* n_past, const float* talker_emb,
+                                         int talker_vocab, const float* cp_tables, int n_tab, int cp_vocab, int n_groups,
+                                         const float* pad, int H, int row0, int max_rows, int buf_rows, int with_h,
+                                         const float* gamma, float* h, float* ssq, uint16_t* xh, int null_table, unsigned* seen,
+                                         int seen_vocab) {
+    return prompt_rows_case(codes, T, past, n_past, talker_emb, talker_vocab, cp_tables, n_tab, cp_vocab, n_groups, pad, H, row0,
+                            max_rows, buf_rows, with_h, gamma, h, ssq, xh, null_table, seen, seen_vocab);
 }
 
 // One launch_prefix_move on host arrays, everything in and out whole: caches kc / vc [n_layers][n_slots][n_kv][n_ctx][128]

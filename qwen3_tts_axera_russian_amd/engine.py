@@ -52,6 +52,52 @@ class SlotParams:
             raise ValueError("text_after_prompt needs text_stream (a codec prompt under streamed text is a text slot's)")
 
 
+@dataclass(frozen=True)
+class SlotRules:
+    """One utterance's sampler rules in a per-slot batch (FrameEngine.rules / admit(rules=...); q3e_slot_rules).  The
+    defaults are the reference's constants (llamacpp_talker_server.py:163-206): a default SlotRules changes nothing."""
+    rep_penalty: float = 1.2       # >= 1; 1 = none
+    rep_window: int = 30           # 1..30 last ids; 0 = every id the utterance has emitted
+    eos_boost: float = 15.0        # >= 0: ceiling of the adaptive EOS boost
+    eos_force: float = 2.0         # progress above which EOS is forced; 0 = never
+    min_frames: int = 0            # generated frames before EOS may be chosen
+    cp_top_p: float = 1.0          # (0, 1]: the code predictor's nucleus cut; 1 = none
+
+    def check(self):
+        """Raises ValueError unless every field is in the range q3e_admit_ruled accepts."""
+        def f32(v):
+            # the value as the engine sees it: a float rounds to f32 on its way into q3e_slot_rules (1e39 is inf there,
+            # 1e-50 is 0); None for anything that is not a finite number
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v):
+                return None
+            with np.errstate(over="ignore"):
+                v = float(np.float32(v))
+            return v if math.isfinite(v) else None
+        if not (f32(self.rep_penalty) is not None and f32(self.rep_penalty) >= 1):
+            raise ValueError(f"rep_penalty must be finite (as an f32) and >= 1 (got {self.rep_penalty!r})")
+        for name in ("eos_boost", "eos_force"):
+            v = getattr(self, name)
+            if not (f32(v) is not None and f32(v) >= 0):
+                raise ValueError(f"{name} must be finite (as an f32) and >= 0 (got {v!r})")
+        if not (f32(self.cp_top_p) is not None and 0 < f32(self.cp_top_p) <= 1):
+            raise ValueError(f"cp_top_p must be in (0, 1] as an f32 (got {self.cp_top_p!r})")
+        for name in ("rep_window", "min_frames"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer (got {v!r})")
+        if not 0 <= self.rep_window <= 30:
+            raise ValueError(f"rep_window must be in 0..30 (got {self.rep_window})")
+        if not 0 <= self.min_frames < 1 << 31:
+            raise ValueError(f"min_frames must be in 0..2**31-1 (got {self.min_frames})")
+
+    def is_default(self):
+        return self == SlotRules()
+
+    def to_c(self):
+        return hiplib.SlotRulesC(float(self.rep_penalty), int(self.rep_window), float(self.eos_boost), float(self.eos_force),
+                                 int(self.min_frames), float(self.cp_top_p), (ctypes.c_int32 * 2)(0, 0))
+
+
 class FrameEngine:
     def __init__(self, weights_path, max_batch=32, n_ctx=512, max_frames=256):
         self._lib = hiplib.load()
@@ -214,7 +260,14 @@ class FrameEngine:
             raise RuntimeError("q3e_prefix_stats failed")
         return dict(zip(("hits", "misses", "stores", "evictions", "too_long", "in_use"), (int(v) for v in out)))
 
-    def admit(self, slots, prefixes, n_text, params, keys=None, prompts=None):
+    def rules(self, on=True):
+        """Reserve (or release) the per-slot sampler rules and emitted-id sets (q3e_rules_reserve; before open()): admit()
+        then takes rules=.  Raises ValueError when the engine refuses (a per-slot batch is open): nothing changes."""
+        rc = self._lib.q3e_rules_reserve(self.h, int(bool(on)))
+        if rc != 0:
+            raise ValueError(f"q3e_rules_reserve refused: {rc}")
+
+    def admit(self, slots, prefixes, n_text, params, keys=None, prompts=None, rules=None):
         """Per-slot mode: put new utterances into `slots` (q3e_admit), each with its SlotParams (checked here first).
         keys (q3e_admit_keyed): one 16-byte key per utterance, or None for an utterance that is not cached -- a digest of
         everything that determines its prefix rows; an utterance whose key the prefix cache holds takes its KV rows and
@@ -223,6 +276,7 @@ class FrameEngine:
         one -- frames the utterance counts as already emitted: they are prefilled behind its prefix, the sampler's history
         starts with them, and codes() / done() / max_frames count the generated frames only.  A key must digest the prompt.
         A text slot takes a prompt only with SlotParams.text_after_prompt; its pushed row i then rides on generated frame i.
+        rules (q3e_admit_ruled; after rules()): one SlotRules per utterance, or None for the defaults (checked here first).
         -> None, or with keys the hit flags (bool [n])."""
         slots = np.ascontiguousarray(np.asarray(slots, np.int32))
         assert len(slots) == len(prefixes) == len(n_text) == len(params) and len(slots) > 0
@@ -235,7 +289,14 @@ class FrameEngine:
             hiplib.SlotParamsC(int(p.max_frames), float(p.temperature), int(p.top_k), float(p.top_p), float(p.cp_temperature),
                                int(p.cp_top_k), int(p.seed), int(p.utt),
                                (1 if p.text_stream else 0) | (2 if p.text_after_prompt else 0)) for p in params])
-        if keys is None and prompts is None:
+        rarr = None
+        if rules is not None:
+            assert len(rules) == len(slots)
+            rules = [SlotRules() if r is None else r for r in rules]
+            for r in rules:
+                r.check()
+            rarr = (hiplib.SlotRulesC * len(rules))(*[r.to_c() for r in rules])
+        if keys is None and prompts is None and rarr is None:
             rc = self._lib.q3e_admit(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
                                      hiplib.iptr(nt), arr)
             if rc != 0:
@@ -254,12 +315,14 @@ class FrameEngine:
             hit = np.zeros(len(slots), np.int32)
         kptr = kk.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if kk is not None else None
         hptr = hiplib.iptr(hit) if hit is not None else None
-        if prompts is None:
+        if prompts is None and rarr is None:
             rc = self._lib.q3e_admit_keyed(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
                                            hiplib.iptr(nt), arr, kptr, hptr)
             if rc != 0:
                 raise RuntimeError(f"q3e_admit_keyed failed: {rc}")
             return hit.astype(bool)
+        if prompts is None:
+            prompts = [None] * len(slots)
         assert len(prompts) == len(slots)
         pcs = []
         for pr in prompts:
@@ -271,6 +334,12 @@ class FrameEngine:
             pcs.append(pr.astype(np.int32))
         frames = np.array([len(pr) for pr in pcs], np.int32)
         pcat = np.ascontiguousarray(np.concatenate(pcs, axis=0)) if frames.sum() else np.zeros((1, 16), np.int32)
+        if rarr is not None:
+            rc = self._lib.q3e_admit_ruled(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
+                                           hiplib.iptr(nt), arr, kptr, hptr, hiplib.iptr(pcat), hiplib.iptr(frames), rarr)
+            if rc != 0:
+                raise RuntimeError(f"q3e_admit_ruled failed: {rc}")
+            return None if hit is None else hit.astype(bool)
         rc = self._lib.q3e_admit_prompted(self.h, len(slots), hiplib.iptr(slots), hiplib.fptr(cat), hiplib.iptr(n_rows),
                                           hiplib.iptr(nt), arr, kptr, hptr, hiplib.iptr(pcat), hiplib.iptr(frames))
         if rc != 0:

@@ -32,6 +32,19 @@ class KernelSlotParamsC(ctypes.Structure):
                 ("prompt", ctypes.c_int32)]
 
 
+class SlotRulesC(ctypes.Structure):
+    """q3e_slot_rules (include/qwen3tts_engine.h)."""
+    _fields_ = [("rep_penalty", ctypes.c_float), ("rep_window", ctypes.c_int32), ("eos_boost", ctypes.c_float),
+                ("eos_force", ctypes.c_float), ("min_frames", ctypes.c_int32), ("cp_top_p", ctypes.c_float),
+                ("reserved", ctypes.c_int32 * 2)]
+
+
+class KernelSlotRulesC(ctypes.Structure):
+    """q3::SlotRules (csrc/q3_kernels.h): the entry the sampling kernels read per row; test hooks only."""
+    _fields_ = [("rep_penalty", ctypes.c_float), ("rep_window", ctypes.c_int32), ("eos_boost", ctypes.c_float),
+                ("eos_force", ctypes.c_float), ("min_past", ctypes.c_int32), ("cp_top_p", ctypes.c_float)]
+
+
 def _sig(lib, name, restype, argtypes):
     fn = getattr(lib, name)
     fn.restype, fn.argtypes = restype, argtypes
@@ -100,6 +113,10 @@ def load(path: str | None = None):
     _sig(lib, "q3e_prefix_stats", c_int, [c_void_p, i64p])
     _sig(lib, "q3e_admit_prompted", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, ctypes.POINTER(SlotParamsC),
                                             ctypes.POINTER(ctypes.c_uint64), i32p, i32p, i32p])
+    _sig(lib, "q3e_default_rules", None, [ctypes.POINTER(SlotRulesC)])
+    _sig(lib, "q3e_rules_reserve", c_int, [c_void_p, c_int])
+    _sig(lib, "q3e_admit_ruled", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p, ctypes.POINTER(SlotParamsC),
+                                         ctypes.POINTER(ctypes.c_uint64), i32p, i32p, i32p, ctypes.POINTER(SlotRulesC)])
     _sig(lib, "q3e_text_reserve", c_int, [c_void_p, c_int])
     _sig(lib, "q3e_push_text", c_int, [c_void_p, c_int, f32p, c_int, c_int, c_int])
     _sig(lib, "q3e_text_state", c_int, [c_void_p, i32p, i32p])
@@ -229,6 +246,11 @@ def load_test():
                c_int, f32p, f32p, c_int, f32p, f32p, c_int, f32p, c_int, f32p, f32p, f32p, u16p, f32p]
     _sig(lib, "q3t_talker_sample_text_case", c_int, talker_case + [i32p, i32p])
     _sig(lib, "q3t_cp_sample_text_case", c_int, cp_case + [f32p, i32p, c_int, i32p])
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    _sig(lib, "q3t_talker_sample_rules_case", c_int, talker_case + [i32p, i32p, c_void_p, u32p])
+    _sig(lib, "q3t_cp_sample_rules_case", c_int, cp_case + [f32p, i32p, c_int, i32p, c_void_p])
+    _sig(lib, "q3t_prompt_rows_seen_case", c_int, [i32p, c_int, i32p, i32p, f32p, c_int, f32p, c_int, c_int, c_int, f32p, c_int,
+                                                   c_int, c_int, c_int, c_int, f32p, f32p, f32p, u16p, c_int, u32p, c_int])
     _sig(lib, "q3t_final_norm_case", c_int, [f32p, f32p, c_int, c_int, c_int, f32p, c_float, c_int, c_int, i32p, c_int, c_int,
                                              c_int, c_int, c_int, f32p, f32p, u16p, f32p, f32p, u16p])
     _sig(lib, "q3t_gather_embed_case", c_int, [f32p, c_int, c_int, i32p, c_int, i32p, c_int, c_int, i32p, c_int, c_int, c_int,
