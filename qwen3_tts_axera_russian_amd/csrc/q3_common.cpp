@@ -1,6 +1,7 @@
 // q3_common.cpp -- container reader and host fp16 helpers.
 #include "q3_common.h"
 #include <cstdlib>
+#include <exception>
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -54,27 +55,38 @@ bool Pack::open(const char* path) {
         return false;
     }
     map = (uint8_t*)m;
-    const FileHeader* h = (const FileHeader*)map;
+    if (!open_bytes(map, map_size, path)) {
+        close();
+        return false;
+    }
+    return true;
+}
+
+// The container's three tables, parsed from n bytes at p (the records are packed: no alignment is assumed).
+bool Pack::open_bytes(const uint8_t* p, size_t n, const char* what) try {
+    if (n < sizeof(FileHeader)) {
+        Q3_LOG("%s: too small for a Q3TTSW1 container", what);
+        return false;
+    }
+    const FileHeader* h = (const FileHeader*)p;
     if (memcmp(h->magic, "Q3TTSW1\0", 8) != 0 || h->version != 1) {
-        Q3_LOG("%s: bad magic/version (not a Q3TTSW1 v1 container)", path);
-        close();
+        Q3_LOG("%s: bad magic/version (not a Q3TTSW1 v1 container)", what);
         return false;
     }
-    size_t need = sizeof(FileHeader) + (size_t)h->n_meta * sizeof(MetaRec) +
-                  (size_t)h->n_tensors * sizeof(TensorRec);
-    if (need > map_size) {
-        Q3_LOG("%s: truncated tables", path);
-        close();
+    // 32-bit counts times 56 / 152 bytes: the sum stays far below 2^64
+    const uint64_t need = sizeof(FileHeader) + (uint64_t)h->n_meta * sizeof(MetaRec) + (uint64_t)h->n_tensors * sizeof(TensorRec);
+    if (need > n) {
+        Q3_LOG("%s: truncated tables", what);
         return false;
     }
-    const MetaRec* mr = (const MetaRec*)(map + sizeof(FileHeader));
+    const MetaRec* mr = (const MetaRec*)(p + sizeof(FileHeader));
     for (uint32_t i = 0; i < h->n_meta; i++) {
         char key[49];
         memcpy(key, mr[i].key, 48);
         key[48] = 0;
         meta[key] = mr[i].value;
     }
-    const TensorRec* tr = (const TensorRec*)(map + sizeof(FileHeader) + (size_t)h->n_meta * sizeof(MetaRec));
+    const TensorRec* tr = (const TensorRec*)(p + sizeof(FileHeader) + (size_t)h->n_meta * sizeof(MetaRec));
     for (uint32_t i = 0; i < h->n_tensors; i++) {
         char name[97];
         memcpy(name, tr[i].name, 96);
@@ -84,23 +96,26 @@ bool Pack::open(const char* path) {
         t.dtype = tr[i].dtype;
         t.ndim = tr[i].ndim;
         if (t.ndim > 4 || t.dtype > 3) {
-            Q3_LOG("%s: tensor %s has bad ndim/dtype", path, name);
-            close();
+            Q3_LOG("%s: tensor %s has bad ndim/dtype", what, name);
             return false;
         }
         for (int d = 0; d < 4; d++) t.shape[d] = tr[i].shape[d];
         t.offset = tr[i].offset;
         t.nbytes = tr[i].nbytes;
         static const uint64_t esz[4] = {4, 2, 4, 8};
-        if (t.offset + t.nbytes > map_size || t.nbytes != t.numel() * esz[t.dtype]) {
-            Q3_LOG("%s: tensor %s out of bounds / size mismatch", path, name);
-            close();
+        uint64_t ne, want;
+        if (t.offset > n || t.nbytes > n - t.offset || !t.numel_checked(&ne) || __builtin_mul_overflow(ne, esz[t.dtype], &want) ||
+            t.nbytes != want) {
+            Q3_LOG("%s: tensor %s out of bounds / size mismatch", what, name);
             return false;
         }
-        t.data = map + t.offset;
+        t.data = p + t.offset;
         tensors[t.name] = t;
     }
     return true;
+} catch (const std::exception& e) {
+    Q3_LOG("%s: %s", what, e.what());
+    return false;
 }
 
 void Pack::close() {

@@ -46,6 +46,19 @@ struct PackTensor {
         for (uint32_t i = 0; i < ndim; i++) n *= shape[i];
         return n;
     }
+    // The same for a shape that has not been validated yet (a file's): false when the product does not fit 64 bits.
+    bool numel_checked(uint64_t* out) const {
+        uint64_t n = 1;
+        for (uint32_t i = 0; i < ndim; i++)
+            if (shape[i] == 0) {
+                *out = 0;
+                return true;
+            }
+        for (uint32_t i = 0; i < ndim; i++)
+            if (__builtin_mul_overflow(n, shape[i], &n)) return false;
+        *out = n;
+        return true;
+    }
 };
 
 struct Pack {
@@ -62,7 +75,13 @@ struct Pack {
     bool add_npy(const char* path, const std::string& name);
     bool add_npz(const char* path, std::string (*rename)(const std::string&));
     bool add_safetensors(const char* path, std::string (*rename)(const std::string&));
+    // The parsers proper: everything above maps its file and calls one of these on the mapping.  They read nothing outside
+    // [p, p + n), refuse (false, with a Q3_LOG line) what does not fit there, and let no exception out.  Tensors point into
+    // [p, p + n) or into `owned`, so the bytes must outlive the Pack's use.
     bool add_npy_bytes(const uint8_t* p, size_t n, const std::string& name, const char* what);
+    bool add_npz_bytes(const uint8_t* p, size_t n, const char* what, std::string (*rename)(const std::string&));
+    bool add_safetensors_bytes(const uint8_t* p, size_t n, const char* what, std::string (*rename)(const std::string&));
+    bool open_bytes(const uint8_t* p, size_t n, const char* what);   // a Q3TTSW1 container
     const uint8_t* map_file(const char* path, size_t* size);
     std::vector<std::pair<uint8_t*, size_t>> extra_maps;   // files mapped by the add_* readers
     std::vector<std::vector<uint8_t>> owned;                // inflated / converted arrays

@@ -13,6 +13,8 @@
 //   embeddings/*.npy             codec_embedding.npy, codec_head.npy (scripts/extract_embeddings.py:62-72)
 #include "q3_common.h"
 
+#include <exception>
+
 #include <dirent.h>
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -87,9 +89,16 @@ size_t npy_header(const uint8_t* p, size_t n, PackTensor& t, std::string& err) {
         return 0;
     }
     size_t f = value_after("fortran_order");
-    if (f != std::string::npos && h.compare(h.find_first_not_of(' ', f), 4, "True") == 0) {
-        err = ".npy fortran_order=True is not supported";
-        return 0;
+    if (f != std::string::npos) {   // the key may be absent; its value may not
+        f = h.find_first_not_of(' ', f);   // npos when the header ends after the colon
+        if (f != std::string::npos && h.compare(f, 4, "True") == 0) {
+            err = ".npy fortran_order=True is not supported";
+            return 0;
+        }
+        if (f == std::string::npos || h.compare(f, 5, "False") != 0) {
+            err = ".npy header: fortran_order has no value";
+            return 0;
+        }
     }
     size_t s = value_after("shape");
     size_t lp = s == std::string::npos ? s : h.find('(', s);
@@ -105,7 +114,10 @@ size_t npy_header(const uint8_t* p, size_t n, PackTensor& t, std::string& err) {
         uint64_t v = 0;
         bool any = false;
         while (i < rp && h[i] >= '0' && h[i] <= '9') {
-            v = v * 10 + (uint64_t)(h[i] - '0');
+            if (__builtin_mul_overflow(v, (uint64_t)10, &v) || __builtin_add_overflow(v, (uint64_t)(h[i] - '0'), &v)) {
+                err = ".npy shape: a dimension does not fit 64 bits";
+                return 0;
+            }
             i++;
             any = true;
         }
@@ -160,15 +172,23 @@ struct JParser {
         uint64_t v = 0;
         bool any = false;
         while (p < e && *p >= '0' && *p <= '9') {
-            v = v * 10 + (uint64_t)(*p++ - '0');
+            if (__builtin_mul_overflow(v, (uint64_t)10, &v) || __builtin_add_overflow(v, (uint64_t)(*p - '0'), &v)) {
+                ok = false;   // a shape or an offset that does not fit 64 bits
+                return 0;
+            }
+            p++;
             any = true;
         }
         if (!any) ok = false;
         return v;
     }
-    void skip_value() {   // any JSON value (used for __metadata__)
+    // Any JSON value (used for __metadata__ and unknown keys of a tensor).  It recurses per nesting level, so the depth is
+    // limited: the format's __metadata__ is a flat string -> string map (depth 1) and a tensor's entry has depth 2, while
+    // a header of nothing but '[' would otherwise use one stack frame per byte.  Every turn of the loop consumes input.
+    static constexpr int kMaxDepth = 32;
+    void skip_value(int depth = 0) {
         ws();
-        if (p >= e) {
+        if (p >= e || depth > kMaxDepth) {
             ok = false;
             return;
         }
@@ -177,17 +197,20 @@ struct JParser {
         } else if (*p == '{' || *p == '[') {
             const char open = *p, close = open == '{' ? '}' : ']';
             p++;
-            while (ok && !eat(close)) {
+            if (eat(close)) return;
+            while (ok) {
                 if (open == '{') {
                     str();
                     if (!eat(':')) ok = false;
                 }
-                skip_value();
-                eat(',');
-                if (p >= e) ok = false;
+                if (ok) skip_value(depth + 1);
+                if (!ok || eat(close)) return;
+                if (!eat(',')) ok = false;
             }
-        } else {
-            while (p < e && *p != ',' && *p != '}' && *p != ']') p++;
+        } else {   // a number, true, false, null: at least one character
+            const char* s = p;
+            while (p < e && *p != ',' && *p != '}' && *p != ']' && *p != ' ' && *p != '\n' && *p != '\t' && *p != '\r') p++;
+            if (p == s) ok = false;
         }
     }
     bool tensor(JTensor& t) {
@@ -309,22 +332,26 @@ const uint8_t* Pack::map_file(const char* path, size_t* size) {
     return (const uint8_t*)m;
 }
 
-bool Pack::add_npy_bytes(const uint8_t* p, size_t n, const std::string& name, const char* what) {
+bool Pack::add_npy_bytes(const uint8_t* p, size_t n, const std::string& name, const char* what) try {
     PackTensor t;
     std::string err;
-    const size_t off = npy_header(p, n, t, err);
+    const size_t off = npy_header(p, n, t, err);   // <= n
     if (!off) {
         Q3_LOG("%s: %s", what, err.c_str());
         return false;
     }
     t.name = name;
-    const uint64_t ne = t.numel();
+    uint64_t ne;
+    if (!t.numel_checked(&ne)) {
+        Q3_LOG("%s: the shape's element count does not fit 64 bits", what);
+        return false;
+    }
     if (t.dtype == 100) {   // f8 -> f4, as the reference's reader does
-        if (off + ne * 8 > n) {
+        if (ne > (n - off) / 8) {
             Q3_LOG("%s: truncated data", what);
             return false;
         }
-        owned.emplace_back(ne * 4);
+        owned.emplace_back((size_t)ne * 4);
         float* dst = (float*)owned.back().data();
         for (uint64_t i = 0; i < ne; i++) {
             double v;
@@ -336,8 +363,7 @@ bool Pack::add_npy_bytes(const uint8_t* p, size_t n, const std::string& name, co
         t.nbytes = ne * 4;
     } else {
         static const uint64_t esz[4] = {4, 2, 4, 8};
-        t.nbytes = ne * esz[t.dtype];
-        if (off + t.nbytes > n) {
+        if (__builtin_mul_overflow(ne, esz[t.dtype], &t.nbytes) || t.nbytes > n - off) {
             Q3_LOG("%s: truncated data", what);
             return false;
         }
@@ -345,6 +371,9 @@ bool Pack::add_npy_bytes(const uint8_t* p, size_t n, const std::string& name, co
     }
     tensors[name] = t;
     return true;
+} catch (const std::exception& e) {
+    Q3_LOG("%s: %s", what, e.what());
+    return false;
 }
 
 bool Pack::add_npy(const char* path, const std::string& name) {
@@ -357,20 +386,30 @@ bool Pack::add_npy(const char* path, const std::string& name) {
     return add_npy_bytes(p, n, name, path);
 }
 
-// Zip: end-of-central-directory record -> central directory -> local headers.  Sizes come from the
-// central directory (numpy writes zip64 extras into the local headers with force_zip64=True).
 bool Pack::add_npz(const char* path, std::string (*rename)(const std::string&)) {
     size_t n = 0;
     const uint8_t* p = map_file(path, &n);
-    if (!p || n < 22) {
+    if (!p) {
         Q3_LOG("cannot open %s as a zip archive", path);
         return false;
     }
+    return add_npz_bytes(p, n, path, rename);
+}
+
+// Zip: end-of-central-directory record -> central directory -> local headers.  Sizes come from the
+// central directory (numpy writes zip64 extras into the local headers with force_zip64=True).
+// Every offset and length in the archive is the file's word: `have(o, k)` is asked before bytes [o, o + k) are read.
+bool Pack::add_npz_bytes(const uint8_t* p, size_t n, const char* path, std::string (*rename)(const std::string&)) try {
+    if (n < 22) {
+        Q3_LOG("cannot open %s as a zip archive", path);
+        return false;
+    }
+    auto have = [&](uint64_t o, uint64_t k) { return o <= n && k <= n - o; };
     auto u16 = [&](size_t o) { return (uint32_t)p[o] | ((uint32_t)p[o + 1] << 8); };
     auto u32 = [&](size_t o) { return u16(o) | (u16(o + 2) << 16); };
     auto u64 = [&](size_t o) { return (uint64_t)u32(o) | ((uint64_t)u32(o + 4) << 32); };
     size_t eocd = std::string::npos;
-    for (size_t i = n - 22;; i--) {
+    for (size_t i = n - 22;; i--) {   // [i, i + 22) is inside the file
         if (u32(i) == 0x06054b50u) {
             eocd = i;
             break;
@@ -384,42 +423,53 @@ bool Pack::add_npz(const char* path, std::string (*rename)(const std::string&)) 
     uint64_t n_ent = u16(eocd + 10), cd_off = u32(eocd + 16);
     if ((n_ent == 0xffff || cd_off == 0xffffffffu) && eocd >= 20 && u32(eocd - 20) == 0x07064b50u) {
         const uint64_t z64 = u64(eocd - 20 + 8);   // zip64 EOCD locator -> zip64 EOCD record
-        if (z64 + 56 <= n && u32(z64) == 0x06064b50u) {
-            n_ent = u64(z64 + 32);
-            cd_off = u64(z64 + 48);
+        if (!have(z64, 56) || u32(z64) != 0x06064b50u) {
+            Q3_LOG("%s: the zip64 locator points at no zip64 end-of-central-directory record", path);
+            return false;
         }
+        n_ent = u64(z64 + 32);
+        cd_off = u64(z64 + 48);
     }
-    size_t c = cd_off;
+    uint64_t c = cd_off;
     int added = 0;
-    for (uint64_t e = 0; e < n_ent; e++) {
-        if (c + 46 > n || u32(c) != 0x02014b50u) {
+    for (uint64_t e = 0; e < n_ent; e++) {   // every entry takes >= 46 bytes of the file: this ends
+        if (!have(c, 46) || u32(c) != 0x02014b50u) {
             Q3_LOG("%s: corrupt zip central directory", path);
             return false;
         }
         const uint32_t method = u16(c + 10), nlen = u16(c + 28), xlen = u16(c + 30), clen = u16(c + 32);
         uint64_t csize = u32(c + 20), usize = u32(c + 24), lho = u32(c + 42);
+        if (!have(c + 46, (uint64_t)nlen + xlen + clen)) {
+            Q3_LOG("%s: a central directory entry runs past the end of the archive", path);
+            return false;
+        }
         const std::string member((const char*)p + c + 46, nlen);
         // zip64 extended information (header id 1): only the fields that overflowed, in this order
-        for (size_t x = c + 46 + nlen; x + 4 <= c + 46 + nlen + xlen;) {
+        const uint64_t xend = c + 46 + nlen + xlen;
+        for (uint64_t x = c + 46 + nlen; x + 4 <= xend;) {
             const uint32_t id = u16(x), sz = u16(x + 2);
+            if (sz > xend - (x + 4)) {
+                Q3_LOG("%s: corrupt extra field of %s", path, member.c_str());
+                return false;
+            }
             if (id == 1) {
-                size_t q = x + 4;
+                uint64_t q = x + 4;
                 if (usize == 0xffffffffu && q + 8 <= x + 4 + sz) { usize = u64(q); q += 8; }
                 if (csize == 0xffffffffu && q + 8 <= x + 4 + sz) { csize = u64(q); q += 8; }
                 if (lho == 0xffffffffu && q + 8 <= x + 4 + sz) { lho = u64(q); q += 8; }
             }
             x += 4 + sz;
         }
-        c += 46 + nlen + xlen + clen;
+        c = xend + clen;
         if (!ends_with(member, ".npy")) continue;
         const std::string name = rename(member.substr(0, member.size() - 4));
         if (name.empty()) continue;
-        if (lho + 30 > n || u32(lho) != 0x04034b50u) {
+        if (!have(lho, 30) || u32(lho) != 0x04034b50u) {
             Q3_LOG("%s: corrupt local header of %s", path, member.c_str());
             return false;
         }
-        const size_t data = lho + 30 + u16(lho + 26) + u16(lho + 28);
-        if (data + csize > n) {
+        const uint64_t data = lho + 30 + u16(lho + 26) + u16(lho + 28);   // lho <= n: no wrap
+        if (!have(data, csize)) {
             Q3_LOG("%s: member %s runs past the end of the archive", path, member.c_str());
             return false;
         }
@@ -427,6 +477,13 @@ bool Pack::add_npz(const char* path, std::string (*rename)(const std::string&)) 
         if (method == 0) {
             if (!add_npy_bytes(p + data, (size_t)csize, name, what.c_str())) return false;
         } else if (method == 8) {
+            // Deflate's densest code is a 258-byte match in 2 bits: it cannot make more than 1032 bytes from one (zlib's
+            // own figure).  Anything above is a damaged directory, and is refused before it is allocated.
+            if (usize / 1032 > csize) {
+                Q3_LOG("%s: claims %llu bytes from %llu deflated ones", what.c_str(), (unsigned long long)usize,
+                       (unsigned long long)csize);
+                return false;
+            }
             owned.emplace_back((size_t)usize);
             std::vector<uint8_t>& buf = owned.back();
             z_stream zs;
@@ -458,12 +515,23 @@ bool Pack::add_npz(const char* path, std::string (*rename)(const std::string&)) 
         added++;
     }
     return added > 0;
+} catch (const std::exception& e) {
+    Q3_LOG("%s: %s", path, e.what());
+    return false;
 }
 
 bool Pack::add_safetensors(const char* path, std::string (*rename)(const std::string&)) {
     size_t n = 0;
     const uint8_t* p = map_file(path, &n);
-    if (!p || n < 8) {
+    if (!p) {
+        Q3_LOG("cannot open %s", path);
+        return false;
+    }
+    return add_safetensors_bytes(p, n, path, rename);
+}
+
+bool Pack::add_safetensors_bytes(const uint8_t* p, size_t n, const char* path, std::string (*rename)(const std::string&)) try {
+    if (n < 8) {
         Q3_LOG("cannot open %s", path);
         return false;
     }
@@ -522,7 +590,8 @@ bool Pack::add_safetensors(const char* path, std::string (*rename)(const std::st
                 t.ndim = (uint32_t)jt.shape.size();
                 for (size_t d = 0; d < jt.shape.size(); d++) t.shape[d] = jt.shape[d];
                 t.nbytes = jt.end - jt.begin;
-                if (t.nbytes != t.numel() * (t.dtype == F32 ? 4 : 2)) {
+                uint64_t ne, want;
+                if (!t.numel_checked(&ne) || __builtin_mul_overflow(ne, (uint64_t)(t.dtype == F32 ? 4 : 2), &want) || t.nbytes != want) {
                     Q3_LOG("%s: tensor %s: size does not match its shape", path, key.c_str());
                     return false;
                 }
@@ -538,6 +607,9 @@ bool Pack::add_safetensors(const char* path, std::string (*rename)(const std::st
         return false;
     }
     return added > 0;
+} catch (const std::exception& e) {
+    Q3_LOG("%s: %s", path, e.what());
+    return false;
 }
 
 // A Q3TTSW1 container, or the reference's deployed files: `path` may be a container file, a

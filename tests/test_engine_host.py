@@ -24,7 +24,9 @@ MAX_FRAMES = 16     # the engine's max_frames in the scripts (budgets are <= 12)
 def driver(tmp_path_factory):
     assert shutil.which("g++"), "the host rules are tested with g++"
     exe = str(tmp_path_factory.mktemp("engine_host") / "engine_host_driver")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", os.path.join(ROOT, "tests", "engine_host_driver.cpp"), "-o", exe])
+    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-std=c++17",
+                           "-static-libasan", "-static-libubsan",     # (runs whatever else a process is made to preload)
+                           os.path.join(ROOT, "tests", "engine_host_driver.cpp"), "-o", exe])
     return exe
 
 

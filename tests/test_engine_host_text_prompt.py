@@ -26,7 +26,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def pdriver(tmp_path_factory):
     assert shutil.which("g++"), "the host rules are tested with g++"
     exe = str(tmp_path_factory.mktemp("engine_host_tp") / "engine_host_text_prompt_driver")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", os.path.join(ROOT, "tests", "engine_host_text_prompt_driver.cpp"),
+    subprocess.check_call(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-std=c++17",
+                           "-static-libasan", "-static-libubsan",     # (runs whatever else a process is made to preload)
+                           os.path.join(ROOT, "tests", "engine_host_text_prompt_driver.cpp"),
                            "-o", exe])
     return exe
 
