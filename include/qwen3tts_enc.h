@@ -41,7 +41,8 @@ int enc_frames(void* h, int n_samples);   /* frames a clip of n_samples gives (<
 int enc_encode(void* h, const float* pcm, const int32_t* n_samples, int B, int64_t* codes_out, int max_frames,
                int32_t* n_frames);
 
-/* GPU milliseconds of the last enc_encode (HIP events on the handle's stream: upload to codes) */
+/* GPU milliseconds of the last enc_encode / enc_encode_pcm (HIP events on the handle's stream: upload -- the front-end
+ * included -- to codes) */
 float enc_last_ms(void* h);
 
 #ifdef __cplusplus
@@ -50,5 +51,7 @@ float enc_last_ms(void* h);
 
 /* Streaming encode: clips of any length in constant memory, ids as the samples arrive */
 #include "qwen3tts_enc_stream.h"
+/* PCM front-end: s16 / f32 PCM of any channel count at the client's rate, decoded, downmixed and resampled on the device */
+#include "qwen3tts_enc_pcm.h"
 
 #endif /* QWEN3TTS_ENC_H */

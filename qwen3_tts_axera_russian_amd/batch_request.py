@@ -32,19 +32,39 @@ generated before EOS may be chosen) and "cp_top_p" ((0, 1]) -- q3e_slot_rules, i
 (SAMPLER_PRESETS: a recollection of the upstream model's generation settings, NOT pinned against its shipped config);
 explicit keys override the preset.  Every utterance of the request runs under the same rules.  Without the flag a request
 that carries any of these keys, and with it a wrong type or a value out of range, is answered -2 for that request alone.
+
+Audio prompts (`--concurrent --encoder ENC.q3w`): instead of "prompt_codes" a request may carry "prompt_audio": {"format":
+"s16" | "f32", "rate": R, "channels": C, "frames": n, "max_frames": K (optional)} -- or a list of such objects, one per
+utterance -- and the clips' raw little-endian interleaved bytes (n * C * itemsize per descriptor, in order) right behind the
+JSON on the same connection, before any text record.  The server encodes them on the GPU (Encoder.encode_pcm: the PCM
+front-end pinned to scipy.signal.resample_poly's float64 result, then the speech-tokenizer encoder), keeps the first K
+frames, and from there on the request IS the request with "prompt_codes" equal to those ids: the same checks, the same prefix
+key, the same reply bit for bit.  What the JSON alone shows to be wrong (no encoder, a malformed descriptor, a rate, channel
+count or length outside the front-end's limits or beyond --prompt_audio_seconds, "prompt_audio" beside "prompt_codes" /
+"voice") is answered -2 before any payload byte is read, and the connection closes; a payload that ends early fails that
+request alone.  Encoded ids are kept in an LRU (PromptAudioCache, --prompt_audio_cache entries) under a digest of the
+descriptor and the payload: a repeated clip runs no encode.  "register_voice": "NAME" (with one "prompt_audio" object) stores
+the ids and the prompt's text under NAME for later "voice": "NAME" requests; with "texts": [] the request only registers and is
+answered i32 0.  A --voice name cannot be replaced, a run-time one can, and at most --max_voices run-time names are kept.
 """
 from __future__ import annotations
 
+import collections
 import dataclasses
 import hashlib
+import math
 import os
 import struct
+import threading
 
 import numpy as np
 
 VOCODER_MODES = ("walk", "incremental")
 VOCODER_ARITHMETICS = ("exact", "split")
-PROMPT_KEYS = ("prompt_codes", "prompt_token_ids", "prompt_text", "voice")
+PROMPT_KEYS = ("prompt_codes", "prompt_token_ids", "prompt_text", "voice", "prompt_audio", "register_voice")
+PROMPT_AUDIO_FORMATS = {"s16": np.dtype("<i2"), "f32": np.dtype("<f4")}
+# the PCM front-end's limits (include/qwen3tts_enc_pcm.h, csrc/q3_enc_pcm_host.h)
+PCM_RATE, PCM_MIN_RATE, PCM_MAX_RATE, PCM_MAX_CHANNELS, PCM_MAX_FACTOR = 24000, 8000, 192000, 8, 640
 _PARAM_KEYS = ("temperature", "top_k", "top_p", "cp_temperature", "cp_top_k", "seed")   # request keys = SlotParams fields
 # request key -> SlotRules field
 _RULE_KEYS = {"repetition_penalty": "rep_penalty", "repetition_window": "rep_window", "eos_boost": "eos_boost",
@@ -136,6 +156,149 @@ def request_prompt_codes(codes, n_utts, cp_vocab=2048):
     if len(codes) != n_utts:
         raise ValueError(f'"prompt_codes" holds {len(codes)} prompts for {n_utts} utterances')
     return [one(c) for c in codes]
+
+
+@dataclasses.dataclass(frozen=True)
+class AudioDescriptor:
+    """One clip of a request's "prompt_audio", checked."""
+    format: str
+    rate: int
+    channels: int
+    frames: int
+    max_frames: int = None          # keep the first K ids (None: all)
+
+    @property
+    def dtype(self):
+        return PROMPT_AUDIO_FORMATS[self.format]
+
+    @property
+    def nbytes(self):
+        return self.frames * self.channels * self.dtype.itemsize
+
+    @property
+    def samples_24k(self):
+        """the clip's length after the front-end: ceil(frames * up / down)"""
+        g = math.gcd(self.rate, PCM_RATE)
+        return -(-self.frames * (PCM_RATE // g) // (self.rate // g))
+
+    def array(self, payload):
+        """the payload's bytes -> the clip as Encoder.encode_pcm takes it"""
+        a = np.frombuffer(payload, self.dtype)
+        return a if self.channels == 1 else a.reshape(-1, self.channels)
+
+
+def request_prompt_audio(spec, n_utts, max_samples):
+    """A request's "prompt_audio" -> (its AudioDescriptors, shared): one object shared by the utterances (shared = True), or a
+    list of n_utts objects.  max_samples: the 24 kHz samples the server's encoder takes per clip (--prompt_audio_seconds).
+    Raises ValueError on anything the front-end or the server would refuse -- all of it visible in the JSON alone."""
+    def integer(d, key, lo, hi, required=True):
+        v = d.get(key)
+        if v is None and not required:
+            return None
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f'"prompt_audio": "{key}" is an integer in {lo}..{hi} (got {v!r})')
+        return v
+
+    def one(d):
+        if not isinstance(d, dict):
+            raise ValueError('"prompt_audio" is an object (or a list of objects, one per utterance)')
+        unknown = set(d) - {"format", "rate", "channels", "frames", "max_frames"}
+        if unknown:
+            raise ValueError(f'"prompt_audio": unknown keys {sorted(unknown)}')
+        fmt = d.get("format")
+        if not isinstance(fmt, str) or fmt not in PROMPT_AUDIO_FORMATS:
+            raise ValueError(f'"prompt_audio": "format" is one of {tuple(PROMPT_AUDIO_FORMATS)} (got {fmt!r})')
+        rate = integer(d, "rate", PCM_MIN_RATE, PCM_MAX_RATE)
+        g = math.gcd(rate, PCM_RATE)
+        if max(PCM_RATE // g, rate // g) > PCM_MAX_FACTOR:
+            raise ValueError(f'"prompt_audio": {rate} Hz resamples by {PCM_RATE // g}/{rate // g}, a factor above {PCM_MAX_FACTOR}')
+        desc = AudioDescriptor(fmt, rate, integer(d, "channels", 1, PCM_MAX_CHANNELS), integer(d, "frames", 1, 2 ** 31 - 1),
+                               integer(d, "max_frames", 1, 2 ** 31 - 1, required=False))
+        if desc.samples_24k > max_samples:
+            raise ValueError(f'"prompt_audio": {desc.frames} frames at {rate} Hz are {desc.samples_24k / PCM_RATE:.2f} s, the '
+                             f"server takes {max_samples / PCM_RATE:.2f} s (--prompt_audio_seconds)")
+        return desc
+    if isinstance(spec, list):
+        if len(spec) != n_utts:
+            raise ValueError(f'"prompt_audio" holds {len(spec)} clips for {n_utts} utterances')
+        return [one(d) for d in spec], False
+    return [one(spec)], True
+
+
+def prompt_audio_digest(desc, payload):
+    """The id cache's key of a clip: SHA-256 over (format, channels, rate, K, the payload's bytes)."""
+    head = struct.pack("<4siiq", desc.format.encode(), desc.channels, desc.rate, -1 if desc.max_frames is None else desc.max_frames)
+    return hashlib.sha256(head + bytes(payload)).digest()
+
+
+class PromptAudioCache:
+    """LRU of encoded prompts: digest -> int64 ids [T][16] (after "max_frames").  Only the thread that resolves audio
+    prompts touches it.  n = 0: nothing is kept (every clip is a miss)."""
+
+    def __init__(self, n):
+        if int(n) < 0:
+            raise ValueError("--prompt_audio_cache takes a number of entries >= 0")
+        self.n, self.hits, self.misses, self.evictions = int(n), 0, 0, 0
+        self._lru = collections.OrderedDict()
+
+    def get(self, key):
+        ids = self._lru.get(key)
+        if ids is None:
+            self.misses += 1
+            return None
+        self._lru.move_to_end(key)
+        self.hits += 1
+        return ids
+
+    def put(self, key, ids):
+        if not self.n:
+            return
+        self._lru[key] = ids
+        self._lru.move_to_end(key)
+        while len(self._lru) > self.n:
+            self._lru.popitem(last=False)
+            self.evictions += 1
+
+    def __len__(self):
+        return len(self._lru)
+
+
+class VoiceTable:
+    """The voices a request may name: the start-up ones (--voice NAME=DIR, fixed) and up to max_runtime registered at run time
+    ("register_voice", replaceable).  name -> (codes as "prompt_codes" takes them, the prompt's text: a str, token ids, or
+    None).  Read and written under one lock."""
+
+    def __init__(self, startup=None, max_runtime=64):
+        if int(max_runtime) < 0:
+            raise ValueError("--max_voices takes a number >= 0")
+        self._startup, self._runtime, self.max_runtime = dict(startup or {}), {}, int(max_runtime)
+        self._lock = threading.Lock()
+
+    def get(self, name):
+        with self._lock:
+            return self._startup.get(name) or self._runtime.get(name)
+
+    def __contains__(self, name):
+        return self.get(name) is not None
+
+    def check_register(self, name):
+        """raises ValueError if `name` cannot be registered now"""
+        if not isinstance(name, str) or not name:
+            raise ValueError('"register_voice" is a non-empty string')
+        with self._lock:
+            if name in self._startup:
+                raise ValueError(f"voice {name!r} was given at start-up (--voice): it cannot be replaced")
+            if name not in self._runtime and len(self._runtime) >= self.max_runtime:
+                raise ValueError(f"{len(self._runtime)} voices are registered (--max_voices {self.max_runtime})")
+
+    def register(self, name, codes, text):
+        self.check_register(name)
+        with self._lock:
+            self._runtime[name] = (codes, text)
+
+    def runtime_names(self):
+        with self._lock:
+            return list(self._runtime)
 
 
 def load_voice(prompt_dir):

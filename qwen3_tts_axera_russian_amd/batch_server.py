@@ -50,6 +50,19 @@ push is redone exactly -- is bit for bit the reply without the flag; requests wi
 nothing.  The counters voice_warm_hits / voice_warm_misses / voice_warm_evictions are on the server object, hits and misses in the
 per-request line.  Only the vocoder worker touches the cache.
 
+`--encoder ENC.q3w` (with `--concurrent`): a request may carry its codec prompt as AUDIO -- "prompt_audio" and the clip's raw PCM
+behind the JSON (batch_wire, batch_request) -- and the server encodes it itself: one Encoder sized by `--prompt_audio_seconds`
+(default 20), one caller at a time under its own lock, the PCM front-end and the speech-tokenizer encoder both on the GPU
+(Encoder.encode_pcm).  The accept thread checks the descriptor (-2 before any payload byte is read), reads the payload, looks
+the clip up in the id cache (`--prompt_audio_cache N`, default 16: an LRU keyed by a digest of format, channels, rate,
+"max_frames" and the bytes; a hit runs no encode), encodes what is missing -- the clips of one request that share format,
+channels and rate in one enc_encode_pcm call -- and hands the scheduler the request with "prompt_codes" equal to the ids: the
+same checks, prefix key and reply, so `--prefix_cache`, `--voice_warm` and `--text_voice` work unchanged.  "register_voice":
+"NAME" keeps the ids and the prompt's text for later "voice": "NAME" requests (at most `--max_voices` run-time names, default
+64; a --voice name cannot be replaced); with "texts": [] the request only registers and is answered i32 0.  The counters
+prompt_audio_hits / prompt_audio_misses / prompt_audio_evictions are on the server object, hits and misses in the per-request
+line.  Without the flag such a request is answered -2.
+
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
 vocoder then launches one persistent workgroup per compute unit (voc_set_max_workgroups(-1)), which leaves the frame loop's
@@ -62,6 +75,8 @@ import dataclasses
 import os
 import signal
 import socket
+import struct
+import threading
 import time
 from concurrent.futures import ThreadPoolExecutor
 
@@ -69,8 +84,9 @@ import numpy as np
 
 from . import hiplib
 from . import protocol as P
-from .batch_request import (PROMPT_KEYS, VOCODER_ARITHMETICS, VOCODER_MODES, Utterance, load_voice, prefix_key,  # noqa: F401
-                            request_has_prompt, request_prompt_codes, request_slot_params, request_slot_rules, request_vocoder,
+from .batch_request import (PROMPT_KEYS, VOCODER_ARITHMETICS, VOCODER_MODES, PromptAudioCache, Utterance, VoiceTable,  # noqa: F401
+                            load_voice, prefix_key, prompt_audio_digest, request_has_prompt, request_prompt_audio,
+                            request_prompt_codes, request_slot_params, request_slot_rules, request_vocoder,
                             request_vocoder_arithmetic)
 from .batch_scheduler import ConcurrentScheduler, PushEntry, ReplyState, TextFeed, new_entries  # noqa: F401
 from .batch_wire import (REC_AUDIO, REC_END, pack_batch_reply, pack_batch_request, pack_stream_audio,  # noqa: F401
@@ -85,12 +101,15 @@ from .weights import ModelConfig, read_pack
 
 class BatchSynthesisServer:
     sampler_rules = False      # --sampler_rules: requests may carry sampler rules (set by __init__)
+    encoder = None             # --encoder: the Encoder audio prompts go through (set by __init__)
+    runtime_voices = None      # the VoiceTable "register_voice" writes (set by __init__)
 
     def __init__(self, model_path, vocoder_path, socket_path="/tmp/qwen3_batch.sock", max_batch=32, n_ctx=512,
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
                  cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=0,
-                 prefix_cache_rows=64, voices=None, text_voice=False, voice_warm=0, sampler_rules=False):
+                 prefix_cache_rows=64, voices=None, text_voice=False, voice_warm=0, sampler_rules=False, encoder=None,
+                 prompt_audio_seconds=20.0, prompt_audio_cache=16, max_voices=64):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens, self.n_ctx = socket_path, max_batch, max_tokens, n_ctx
@@ -111,6 +130,8 @@ class BatchSynthesisServer:
                 (voices and alone, "--voice names codec prompts of the shared frame loop's admissions: it needs --concurrent"),
                 (text_voice and alone, "--text_voice lets text slots of the shared frame loop continue a codec prompt: it needs --concurrent"),
                 (sampler_rules and alone, "--sampler_rules sets the sampler rules of the shared frame loop's slots: it needs --concurrent"),
+                (encoder and alone, "--encoder encodes the audio prompts of the shared frame loop's admissions: it needs --concurrent"),
+                (not float(prompt_audio_seconds) > 0, "--prompt_audio_seconds takes a number > 0"),
                 (int(voice_warm) < 0, "--voice_warm takes a number of snapshot slots >= 0"),
                 (voice_warm and alone, "--voice_warm caches the vocoder warm-up of the shared frame loop's codec prompts: it needs --concurrent")):
             if bad:
@@ -119,6 +140,10 @@ class BatchSynthesisServer:
         self.sampler_rules = bool(sampler_rules)
         self.prefix_cache, self.prefix_cache_rows = int(prefix_cache), int(prefix_cache_rows)
         self.voices = {name: load_voice(d) for name, d in dict(voices or {}).items()}   # name -> (codes [T][16], text or None)
+        self.runtime_voices = VoiceTable(self.voices, max_voices)
+        self._prompt_audio = PromptAudioCache(prompt_audio_cache)
+        self._encoder_lock = threading.Lock()
+        self._encoder_path, self._encoder_samples = encoder, int(round(float(prompt_audio_seconds) * 24000))
         self.sched = None
         # utterances one request may queue (the server is single-threaded: an unbounded request holds it indefinitely)
         self.max_request = int(max_request) if max_request else 8 * max_batch
@@ -136,6 +161,9 @@ class BatchSynthesisServer:
         self.eng.set_sampling(temperature, top_k, top_p, cp_temperature, cp_top_k, seed)
         self._lib = hiplib.load()
         self.voc = Vocoder(vocoder_path, 64, min(max_batch, 32))
+        if encoder:
+            from .encoder import Encoder
+            self.encoder = Encoder(encoder, max_batch=min(max_batch, 4), max_samples=self._encoder_samples)
         # --voice_warm N: N snapshot slots on the vocoder handle, and the LRU over them (the vocoder worker's, like the handle)
         self._voice_warm = VoiceWarmCache(int(voice_warm))
         if self._voice_warm.n_slots:
@@ -386,9 +414,14 @@ class BatchSynthesisServer:
             if codes is not None or text is not None or head is not None:
                 raise ValueError('"voice" stands for "prompt_codes" and the prompt text: give one or the other')
             name = msg["voice"]
-            if not isinstance(name, str) or name not in self.voices:
+            entry = self.voices.get(name) if isinstance(name, str) else None
+            if entry is None and isinstance(name, str) and self.runtime_voices is not None:
+                entry = self.runtime_voices.get(name)           # (registered at run time: "register_voice")
+            if entry is None:
                 raise ValueError(f"unknown voice {name!r}")
-            codes, text = self.voices[name]
+            codes, text = entry
+            if isinstance(text, list):                          # (registered with "prompt_token_ids")
+                head, text = text, None
         if codes is None:
             raise ValueError('a prompt text needs "prompt_codes" (or a "voice")')
         if head is not None and text is not None:
@@ -443,7 +476,66 @@ class BatchSynthesisServer:
         note = ""
         if self.prefix_cache and self.sched is not None:
             note = f" (prefix cache: {self.sched.prefix_hits} hits, {self.sched.prefix_misses} misses so far)"
+        if self.encoder is not None:
+            note += f" (prompt audio: {self._prompt_audio.hits} hits, {self._prompt_audio.misses} misses so far)"
         return note + self._voice_warm.note()
+
+    prompt_audio_hits = property(lambda self: self._prompt_audio.hits)
+    prompt_audio_misses = property(lambda self: self._prompt_audio.misses)
+    prompt_audio_evictions = property(lambda self: self._prompt_audio.evictions)
+
+    def _resolve_prompt_audio(self, conn, msg):
+        """Accept side, --concurrent: a request with "prompt_audio" / "register_voice" becomes the request with "prompt_codes"
+        equal to the encoder's ids -- the descriptors checked from the JSON alone, then the payload read from conn, the clips
+        looked up in the id cache and the missing ones encoded (one library call per format / channels / rate).  -> True when
+        the request only registered a voice and has been answered; raises on anything malformed (the caller answers -2)."""
+        spec, name = msg.get("prompt_audio"), msg.get("register_voice")
+        if self.encoder is None:
+            raise ValueError('"prompt_audio" needs a server started with --encoder')
+        if spec is None:
+            raise ValueError('"register_voice" needs "prompt_audio"')
+        if msg.get("prompt_codes") is not None or msg.get("voice") is not None:
+            raise ValueError('"prompt_audio" takes the place of "prompt_codes" / "voice": give one')
+        utts = msg["token_ids"] if msg.get("token_ids") is not None else msg.get("texts", [])
+        if not isinstance(utts, list):
+            raise ValueError("texts / token_ids is a list")
+        if name is not None:
+            if isinstance(spec, list):
+                raise ValueError('"register_voice" takes a single "prompt_audio" object')
+            self.runtime_voices.check_register(name)
+        elif not utts:
+            raise ValueError("a request needs at least one utterance")
+        descs, shared = request_prompt_audio(spec, len(utts), self._encoder_samples)
+        payloads = [P.recv_payload(conn, d.nbytes) for d in descs]
+        keys = [prompt_audio_digest(d, raw) for d, raw in zip(descs, payloads)]
+        ids, missing = [None] * len(descs), {}
+        for k, (d, key) in enumerate(zip(descs, keys)):
+            first = next((j for j in range(k) if keys[j] == key), None)
+            ids[k] = self._prompt_audio.get(key) if first is None else ids[first]
+            if ids[k] is None and first is None:
+                missing.setdefault((d.format, d.channels, d.rate), []).append(k)
+        for (fmt, channels, rate), ks in missing.items():
+            with self._encoder_lock:
+                got = self.encoder.encode_pcm([descs[k].array(payloads[k]) for k in ks], rate, channels)
+            for k, c in zip(ks, got):
+                ids[k] = np.ascontiguousarray(c[:descs[k].max_frames], np.int64)
+                self._prompt_audio.put(keys[k], ids[k])
+        for k in range(len(descs)):                # (a clip the request repeats: encoded once)
+            if ids[k] is None:
+                ids[k] = ids[keys.index(keys[k])]
+        del msg["prompt_audio"]
+        msg.pop("register_voice", None)
+        msg["prompt_codes"] = ids[0].tolist() if shared else [c.tolist() for c in ids]
+        if name is not None:
+            text = msg.get("prompt_token_ids") if msg.get("prompt_token_ids") is not None else msg.get("prompt_text")
+            self._request_prompts(dict(msg, text_stream=False), 1)      # (the checks a later "voice" request would fail)
+            self.runtime_voices.register(name, msg["prompt_codes"], text)
+            print(f"  voice {name!r} registered: {len(ids[0])} frames")
+            if not utts:
+                conn.sendall(struct.pack("<i", 0))
+                conn.close()
+                return True
+        return False
 
     voice_warm_hits = property(lambda self: self._voice_warm.hits)
     voice_warm_misses = property(lambda self: self._voice_warm.misses)
@@ -554,6 +646,9 @@ class BatchSynthesisServer:
                     if msg is None:
                         conn.close()
                         continue
+                    if msg.get("prompt_audio") is not None or msg.get("register_voice") is not None:
+                        if self._resolve_prompt_audio(conn, msg):     # (reads the payload behind the JSON)
+                            continue
                     conn.settimeout(None)
                 except Exception as e:
                     print(f"Error: {e}")
@@ -576,6 +671,9 @@ class BatchSynthesisServer:
         self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
         if self.pipeline:
             self._lib.voc_set_max_workgroups(0)
+        if self.encoder is not None:
+            self.encoder.close()
+            self.encoder = None
         self.voc.close()               # frees the streaming chunk walk first
         self._vstream, self._istreams = None, {}
         self.eng.destroy()
@@ -622,6 +720,13 @@ def main():
     ap.add_argument("--voice_warm", type=int, default=0,
                     help="with --concurrent: cache the incremental vocoder's warm-up per codec prompt in N snapshot slots of the "
                          "vocoder (a known voice then costs one copy launch instead of decoding its prompt; default 0 = off)")
+    ap.add_argument("--encoder", default=None,
+                    help="--concurrent: speech-tokenizer encoder container; requests may then carry their codec prompt as audio "
+                         "(\"prompt_audio\" + the raw PCM behind the JSON), encoded on the GPU")
+    ap.add_argument("--prompt_audio_seconds", type=float, default=20.0, help="--encoder: the longest audio prompt, in seconds")
+    ap.add_argument("--prompt_audio_cache", type=int, default=16,
+                    help="--encoder: entries of the LRU of encoded audio prompts (a repeated clip runs no encode)")
+    ap.add_argument("--max_voices", type=int, default=64, help="--encoder: voices \"register_voice\" may keep at run time")
     ap.add_argument("--text_voice", action="store_true",
                     help="--concurrent: a text-stream request may carry a codec prompt (\"voice\" / \"prompt_codes\"): streamed "
                          "text in the prompt's voice")
@@ -634,7 +739,9 @@ def main():
                                send_timeout=a.send_timeout, text_wait_ms=a.text_wait_ms, text_hold=a.text_hold,
                                prefix_cache=a.prefix_cache, prefix_cache_rows=a.prefix_cache_rows,
                                voices=dict(v.split("=", 1) for v in a.voice), text_voice=a.text_voice,
-                               voice_warm=a.voice_warm, sampler_rules=a.sampler_rules)
+                               voice_warm=a.voice_warm, sampler_rules=a.sampler_rules, encoder=a.encoder,
+                               prompt_audio_seconds=a.prompt_audio_seconds, prompt_audio_cache=a.prompt_audio_cache,
+                               max_voices=a.max_voices)
     try:
         srv.serve()
     finally:

@@ -22,6 +22,11 @@ client goes on sending the rest on the same connection, as records
               i32 0, i32 0                                     end of text
 
 while the audio records already come back.  The request's other keys: batch_request.
+
+Audio prompt (`--concurrent --encoder`): a request that carries "prompt_audio" (one descriptor {"format", "rate", "channels",
+"frames"[, "max_frames"]}, or a list of them, one per utterance) is followed on the same connection by the clips' raw
+little-endian interleaved PCM -- frames * channels * itemsize bytes per descriptor, in order, no framing -- before any text
+record.  A request with "register_voice" and "texts": [] is answered i32 0.
 """
 from __future__ import annotations
 
@@ -41,13 +46,16 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
                        top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None,
                        vocoder_arithmetic=None, text_stream=False, prompt_codes=None, prompt_token_ids=None, prompt_text=None,
                        voice=None, sampler=None, repetition_penalty=None, repetition_window=None, eos_boost=None, eos_force=None,
-                       min_tokens=None, cp_top_p=None) -> bytes:
+                       min_tokens=None, cp_top_p=None, prompt_audio=None, prompt_audio_max_frames=None, register_voice=None) -> bytes:
     """The request of the batched protocol; the sampling keys (honoured by --concurrent), the vocoder mode ("walk" /
     "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given.  text_stream: the
     request carries only the first piece of its one utterance's text; the rest follows as text records.  prompt_codes ([T][16], or
     one such per utterance), prompt_token_ids / prompt_text, voice: the codec prompt the utterances continue (--concurrent).
     sampler ("reference" / "upstream"), repetition_penalty, repetition_window, eos_boost, eos_force, min_tokens, cp_top_p: the
-    request's sampler rules (--concurrent --sampler_rules; batch_request)"""
+    request's sampler rules (--concurrent --sampler_rules; batch_request).  prompt_audio: (array, rate) -- a numpy int16 or float32
+    array [n] or [n][channels] -- or a list of such pairs, one per utterance: the audio whose voice the utterances continue
+    (--concurrent --encoder); its descriptor goes into the JSON ("max_frames": prompt_audio_max_frames) and its bytes behind
+    it, so the result is JSON plus payload.  register_voice: the name the server keeps that prompt under."""
     msg = {"language": language}
     if stream:
         msg["stream"] = True
@@ -72,8 +80,28 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
                    ("min_tokens", min_tokens), ("cp_top_p", cp_top_p)):
         if v is not None:
             msg[key] = v
+    payload = b""
+    if prompt_audio is not None:
+        shared = isinstance(prompt_audio, tuple)
+        descs, parts = zip(*(prompt_audio_descriptor(a, r, prompt_audio_max_frames) for a, r in ([prompt_audio] if shared else prompt_audio)))
+        msg["prompt_audio"] = descs[0] if shared else list(descs)
+        payload = b"".join(parts)
+    if register_voice is not None:
+        msg["register_voice"] = register_voice
     raw = json.dumps(msg).encode()
-    return struct.pack("<I", len(raw)) + raw
+    return struct.pack("<I", len(raw)) + raw + payload
+
+
+def prompt_audio_descriptor(array, rate, max_frames=None):
+    """A clip as a client has it (numpy int16 / float32, [n] or [n][channels]) -> (its "prompt_audio" descriptor, its bytes)"""
+    a = np.asarray(array)
+    fmt = {np.dtype(np.int16): "s16", np.dtype(np.float32): "f32"}.get(a.dtype)
+    if fmt is None or a.ndim not in (1, 2):
+        raise TypeError("prompt audio is an int16 or float32 array of shape [n] or [n][channels]")
+    d = {"format": fmt, "rate": int(rate), "channels": 1 if a.ndim == 1 else int(a.shape[1]), "frames": int(a.shape[0])}
+    if max_frames is not None:
+        d["max_frames"] = int(max_frames)
+    return d, np.ascontiguousarray(a, dtype=a.dtype.newbyteorder("<")).tobytes()
 
 
 def pack_batch_reply(results) -> bytes:
@@ -136,6 +164,15 @@ def read_stream_record(conn):
     return ("end", utt, np.frombuffer(exact(n * 16 * 4), dtype="<i4").reshape(n, 16))
 
 
+def _send_request(s, raw):
+    """The request and its payload.  A server that refuses a "prompt_audio" request from its JSON answers -2 and closes without
+    reading the payload: the rest of the send then fails, and the answer is still there to be read."""
+    try:
+        s.sendall(raw)
+    except (BrokenPipeError, ConnectionResetError):
+        pass
+
+
 def _stream_records(s):
     """The records of a streamed reply on `s` until the request is done."""
     while True:
@@ -153,18 +190,21 @@ def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="r
     keys of pack_batch_request."""
     with socket.socket(socket.AF_UNIX, socket.SOCK_STREAM) as s:
         s.connect(socket_path)
-        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, stream=True, vocoder=vocoder,
-                                     vocoder_arithmetic=vocoder_arithmetic, **sampling))
+        _send_request(s, pack_batch_request(texts, token_ids, language, max_tokens, stream=True, vocoder=vocoder,
+                                            vocoder_arithmetic=vocoder_arithmetic, **sampling))
         yield from _stream_records(s)
 
 
 def synthesize_text_stream(socket_path, pieces, language="russian", max_tokens=None, vocoder=None, vocoder_arithmetic=None,
-                           voice=None, prompt_codes=None, prompt_token_ids=None, prompt_text=None, **sampling):
+                           voice=None, prompt_codes=None, prompt_token_ids=None, prompt_text=None, prompt_audio=None,
+                           register_voice=None, **sampling):
     """Client side of a "text_stream" request (--concurrent servers): `pieces` is an iterable of the text's pieces as they
     become available -- str / bytes (UTF-8, cut anywhere; the server tokenises) or sequences of token ids.  The first piece
     goes out with the request (it must give at least one token), the others as text records from a sender thread that walks
     the iterable, then the end-of-text record.  Yields the records of synthesize_batch_stream, utterance 0.  voice, or
-    prompt_codes with prompt_token_ids / prompt_text: the codec prompt the utterance continues (--text_voice servers)."""
+    prompt_codes with prompt_token_ids / prompt_text: the codec prompt the utterance continues (--text_voice servers);
+    prompt_audio=(array, rate): that prompt as audio (--encoder servers; its bytes go out before any text record), kept under
+    register_voice if given."""
     it = iter(pieces)
     first = next(it)
     as_text = isinstance(first, (str, bytes, bytearray))
@@ -185,10 +225,10 @@ def synthesize_text_stream(socket_path, pieces, language="russian", max_tokens=N
 
     th = threading.Thread(target=sender, daemon=True)
     try:
-        s.sendall(pack_batch_request([first] if as_text else None, None if as_text else [list(first)], language, max_tokens,
-                                     stream=True, vocoder=vocoder, vocoder_arithmetic=vocoder_arithmetic, text_stream=True,
-                                     prompt_codes=prompt_codes, prompt_token_ids=prompt_token_ids, prompt_text=prompt_text,
-                                     voice=voice, **sampling))
+        _send_request(s, pack_batch_request([first] if as_text else None, None if as_text else [list(first)], language, max_tokens,
+                                            stream=True, vocoder=vocoder, vocoder_arithmetic=vocoder_arithmetic, text_stream=True,
+                                            prompt_codes=prompt_codes, prompt_token_ids=prompt_token_ids, prompt_text=prompt_text,
+                                            voice=voice, prompt_audio=prompt_audio, register_voice=register_voice, **sampling))
         th.start()
         yield from _stream_records(s)
     finally:
@@ -199,8 +239,8 @@ def synthesize_text_stream(socket_path, pieces, language="russian", max_tokens=N
 
 def synthesize_batch(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, **sampling):
     """Client side of the batched request.  sampling: the optional keys of pack_batch_request (vocoder and vocoder_arithmetic
-    among them)."""
+    among them; prompt_audio=(array, rate) and register_voice too -- with texts=[] the request only registers: -> [])."""
     with socket.socket(socket.AF_UNIX, socket.SOCK_STREAM) as s:
         s.connect(socket_path)
-        s.sendall(pack_batch_request(texts, token_ids, language, max_tokens, **sampling))
+        _send_request(s, pack_batch_request(texts, token_ids, language, max_tokens, **sampling))
         return read_batch_reply(s)

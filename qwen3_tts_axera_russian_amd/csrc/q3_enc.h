@@ -41,6 +41,18 @@ struct Enc {
     int64_t* d_codes = nullptr;     // [max_batch][max frames][nq]
     size_t codes_cap = 0;
     float last_ms = 0.f;
+    // the PCM front-end (q3_enc_pcm.hip): the payload as the client sent it, the clips' geometry, the tap tables built so far
+    struct PcmTable {
+        int up = 0, down = 0;
+        double* taps = nullptr;     // [per_phase][up], q3_enc_pcm_host.h
+        uint64_t used = 0;          // the call that read it last (the least recent one goes when a fifth comes)
+    };
+    void* pcm_raw = nullptr;
+    size_t pcm_raw_bytes = 0;
+    long long* pcm_meta = nullptr;  // [max_batch][3]: first frame, input frames, output samples
+    std::vector<long long> pcm_meta_host;
+    std::vector<PcmTable> pcm_tables;
+    uint64_t pcm_calls = 0;
 };
 
 static inline void enc_bind(const Enc* e) {
@@ -93,6 +105,16 @@ static inline bool enc_rvq_geometry(int nq, int cb, int dim, int n_sem) {
 // the quantiser's device tables from the host codebook [nq][cb][dim] (finite; op.nq, op.cb and op.dim set): op.cbk the codebook,
 // op.cbt its transpose [nq][dim][cb], op.n2 [nq][cb] = (float) of the double sum of squares.  -> false: an allocation or a copy failed
 bool enc_rvq_tables(DeviceAllocs& mem, const float* codebook, EncOp& op);
+
+// ---- what enc_encode and enc_encode_pcm share (q3_enc.hip) ----
+// runs ops [0, n_ops) (n_ops < 0: all) on the B clips already in e->pcm: rows of pitch enc_pitch(longest), each zero past its
+// own lens[b] samples.  -> the buffer of the last activation (nullptr after the quantiser), its channels and longest length
+int enc_run(Enc* e, int B, const std::vector<int>& lens, int n_ops, float** out, int* outC, long* outL);
+// after enc_run's quantiser: the ids to the host, e1 recorded, the stream drained, last_ms = e0 -> e1, codes_out / n_frames
+// filled as enc_encode documents them (T: enc_run's outL)
+int enc_collect_codes(Enc* e, int B, const std::vector<int>& lens, long T, int64_t* codes_out, int max_frames, int32_t* n_frames);
+// enc_destroy's part for the front-end's own allocations (q3_enc_pcm.hip)
+void enc_pcm_release(Enc* e);
 
 // ---- streaming encode: the column counts of every level from a stream's running total ----
 // Level l is the input of the l-th strided op (level 0: samples); cols[n_levels] are frames.  A strided op of stride s turns

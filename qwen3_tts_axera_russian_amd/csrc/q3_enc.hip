@@ -266,6 +266,7 @@ bool enc_rvq_tables(DeviceAllocs& mem, const float* cbk, EncOp& op) {
 static void enc_destroy(Enc* e) {
     if (!e) return;
     if (e->s) hipStreamSynchronize(e->s);
+    enc_pcm_release(e);
     e->mem.release();
     if (e->e0) hipEventDestroy(e->e0);
     if (e->e1) hipEventDestroy(e->e1);
@@ -275,7 +276,7 @@ static void enc_destroy(Enc* e) {
 
 // Runs ops [0, n_ops) on the clips already in e->pcm (lens = their sample counts).  -> the buffer holding the last
 // activation, its channels and (longest) length.
-static int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, float** out, int* outC, long* outL) {
+int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, float** out, int* outC, long* outL) {
     std::vector<int> lens(lens0);
     std::vector<int> tab((size_t)e->ops.size() * e->max_batch, 0);
     long L = *std::max_element(lens.begin(), lens.begin() + B);
@@ -337,6 +338,22 @@ static int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, floa
     *out = src;
     *outC = nrun ? e->ops[nrun - 1].c_act : 1;
     *outL = L;
+    return 0;
+}
+
+int enc_collect_codes(Enc* e, int B, const std::vector<int>& lens, long T, int64_t* codes_out, int max_frames, int32_t* n_frames) {
+    std::vector<int64_t> hc((size_t)B * T * e->nq);
+    Q3_HIP(hipMemcpyAsync(hc.data(), e->d_codes, hc.size() * sizeof(int64_t), hipMemcpyDeviceToHost, e->s), -1);
+    Q3_HIP(hipEventRecord(e->e1, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    hipEventElapsedTime(&e->last_ms, e->e0, e->e1);
+    for (int b = 0; b < B; b++) {
+        const int f = (int)enc_cols_after(e->ops, e->ops.size(), lens[b]);
+        n_frames[b] = f;
+        int64_t* dst = codes_out + (size_t)b * max_frames * e->nq;
+        std::copy(hc.begin() + (size_t)b * T * e->nq, hc.begin() + ((size_t)b * T + f) * e->nq, dst);
+        std::fill(dst + (size_t)f * e->nq, dst + (size_t)max_frames * e->nq, (int64_t)-1);
+    }
     return 0;
 }
 
@@ -623,19 +640,7 @@ int enc_encode(void* h, const float* pcm, const int32_t* n_samples, int B, int64
     int C = 0;
     long T = 0;
     if (enc_run(e, B, lens, -1, &out, &C, &T)) return -1;
-    std::vector<int64_t> hc((size_t)B * T * e->nq);
-    Q3_HIP(hipMemcpyAsync(hc.data(), e->d_codes, hc.size() * sizeof(int64_t), hipMemcpyDeviceToHost, e->s), -1);
-    Q3_HIP(hipEventRecord(e->e1, e->s), -1);
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
-    hipEventElapsedTime(&e->last_ms, e->e0, e->e1);
-    for (int b = 0; b < B; b++) {
-        const int f = enc_frames(e, lens[b]);
-        n_frames[b] = f;
-        int64_t* dst = codes_out + (size_t)b * max_frames * e->nq;
-        std::copy(hc.begin() + (size_t)b * T * e->nq, hc.begin() + ((size_t)b * T + f) * e->nq, dst);
-        std::fill(dst + (size_t)f * e->nq, dst + (size_t)max_frames * e->nq, (int64_t)-1);
-    }
-    return 0;
+    return enc_collect_codes(e, B, lens, T, codes_out, max_frames, n_frames);
 }
 
 // test hook (not in the header, like voc_debug_run): run the first n_ops ops on the clips and return the activation

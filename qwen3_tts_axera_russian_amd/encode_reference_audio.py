@@ -3,6 +3,7 @@ scripts/encode_reference_audio.py, on the GPU encoder).
 
     python -m qwen3_tts_axera_russian_amd.encode_reference_audio --audio ref.wav --model enc.q3w --output_dir prompt/ \
         [--ref_text "..."] [--max_tokens 256] [--decode_back ref_decoded.wav --vocoder voc.q3w] [--stream_seconds 1.0]
+        [--resample host|device]
 
 Writes ref_codec_tokens.npy (int64 [min(T, max_tokens)][16], the semantic id first) to --output, or, with --output_dir,
 a prompt_dir holding ref_codec_tokens.npy and (with --ref_text) ref_text.txt.  --model is an encoder container
@@ -11,8 +12,13 @@ encodes the clip in pushes of S seconds through the streaming encode (Encoder.en
 one push, whatever the WAV's length.
 
 WAV loading follows the reference's load_wav: int16 / 32768, int32 / 2^31, any other dtype cast to float32 unscaled,
-channels averaged.  Audio at another rate than the encoder's is resampled on the host with scipy.signal.resample_poly;
-qwen_tts's own resampler is not available here, so that step is not pinned to it."""
+channels averaged.  Audio at another rate than the encoder's is resampled on the host with scipy.signal.resample_poly in
+float32 (--resample host, the default: unchanged, bit for bit), or, with --resample device, handed to the encoder as the
+file holds it -- int16 or float32 samples, the channels interleaved -- and decoded, downmixed and resampled on the GPU
+(Encoder.encode_pcm / enc_encode_pcm).  The device path is pinned: scipy.signal.resample_poly's rules evaluated in float64 and
+rounded once to float32, so every host that opens the library gets the same ids for the same file; the host path depends on
+the host's scipy and its float32 arithmetic and is pinned to nothing.  qwen_tts's own resampler is not available here:
+neither path is pinned to it."""
 from __future__ import annotations
 
 import argparse
@@ -39,6 +45,15 @@ def load_wav(path):
     if data.ndim > 1:
         data = data.mean(axis=1)
     return np.ascontiguousarray(data, dtype=np.float32), int(sr)
+
+
+def load_wav_raw(path):
+    """-> (the samples as the file holds them, int16 or float32, [n] or [n][channels]; sample rate) for --resample device"""
+    import scipy.io.wavfile as wavfile
+    sr, data = wavfile.read(path)
+    if data.dtype not in (np.dtype(np.int16), np.dtype(np.float32)):
+        raise ValueError(f"--resample device takes int16 or float32 WAV data, this file holds {data.dtype} (use --resample host)")
+    return np.ascontiguousarray(data), int(sr)
 
 
 def resample(x, sr, target):
@@ -82,50 +97,7 @@ def decode_back(codes, vocoder, out_wav):
     return len(pcm)
 
 
-def main(argv=None, encoder_factory=open_encoder):
-    p = argparse.ArgumentParser(description="Encode reference audio to codec tokens (GPU speech-tokenizer encoder)")
-    p.add_argument("--audio", required=True, help="reference audio WAV file")
-    p.add_argument("--model", "--model_dir", dest="model", required=True,
-                   help="encoder container (.q3w) or a speech_tokenizer/ directory")
-    p.add_argument("--output", default="ref_codec_tokens.npy")
-    p.add_argument("--output_dir", default=None, help="output directory (creates the prompt_dir structure)")
-    p.add_argument("--ref_text", default=None, help="text spoken in the reference audio")
-    p.add_argument("--max_tokens", type=int, default=256)
-    p.add_argument("--decode_back", default=None, help="also decode the saved ids to this WAV through the vocoder")
-    p.add_argument("--vocoder", default=None, help="vocoder container for --decode_back")
-    p.add_argument("--stream_seconds", type=float, default=None,
-                   help="encode in pushes of this many seconds through the streaming encode (a WAV of any length)")
-    a = p.parse_args(argv)
-    if a.decode_back and not a.vocoder:
-        p.error("--decode_back needs --vocoder")
-    if a.stream_seconds is not None and not a.stream_seconds > 0:
-        p.error("--stream_seconds must be > 0")
-    if a.max_tokens < 1:
-        p.error("--max_tokens must be >= 1")
-    try:
-        x, sr = load_wav(a.audio)
-    except Exception as e:   # (missing, unreadable, not a WAV)
-        print(f"error: cannot read {a.audio}: {e}", file=sys.stderr)
-        return 2
-    if x.size == 0:
-        print(f"error: {a.audio} holds no samples", file=sys.stderr)
-        return 2
-    print(f"Audio: {a.audio}\n  Duration: {x.size / sr:.2f}s, SR: {sr}")
-    x = resample(x, sr, 24000)
-    if a.stream_seconds is None:
-        enc = encoder_factory(a.model, max(int(x.size), 1))
-    else:   # the handle's whole-clip buffers are not used: sized for one push
-        enc = encoder_factory(a.model, max(int(round(a.stream_seconds * 24000)), 1))
-    if enc.sample_rate != 24000:
-        x = resample(x, 24000, enc.sample_rate)
-    t0 = time.time()
-    if a.stream_seconds is None:
-        codes = enc.encode([x])[0]
-        print(f"Encode time: {time.time() - t0:.3f}s (GPU {enc.last_ms():.2f} ms)")
-    else:
-        push = max(int(round(a.stream_seconds * enc.sample_rate)), 1)
-        codes = enc.encode_streaming(x, push)
-        print(f"Encode time: {time.time() - t0:.3f}s (streamed, {-(-x.size // push)} pushes of {push} samples)")
+def _save(a, codes):
     n_tokens, n_groups = codes.shape
     print(f"Tokens: {n_tokens}, Groups: {n_groups}")
     keep = np.ascontiguousarray(codes[:min(n_tokens, a.max_tokens)], dtype=np.int64)
@@ -143,6 +115,68 @@ def main(argv=None, encoder_factory=open_encoder):
         n = decode_back(keep, a.vocoder, a.decode_back)
         print(f"Saved decoded: {a.decode_back} ({n} samples)")
     return 0
+
+
+def main(argv=None, encoder_factory=open_encoder):
+    p = argparse.ArgumentParser(description="Encode reference audio to codec tokens (GPU speech-tokenizer encoder)")
+    p.add_argument("--audio", required=True, help="reference audio WAV file")
+    p.add_argument("--model", "--model_dir", dest="model", required=True,
+                   help="encoder container (.q3w) or a speech_tokenizer/ directory")
+    p.add_argument("--output", default="ref_codec_tokens.npy")
+    p.add_argument("--output_dir", default=None, help="output directory (creates the prompt_dir structure)")
+    p.add_argument("--ref_text", default=None, help="text spoken in the reference audio")
+    p.add_argument("--max_tokens", type=int, default=256)
+    p.add_argument("--decode_back", default=None, help="also decode the saved ids to this WAV through the vocoder")
+    p.add_argument("--vocoder", default=None, help="vocoder container for --decode_back")
+    p.add_argument("--stream_seconds", type=float, default=None,
+                   help="encode in pushes of this many seconds through the streaming encode (a WAV of any length)")
+    p.add_argument("--resample", choices=("host", "device"), default="host",
+                   help="host: scipy.signal.resample_poly in float32 before the encoder (default); device: decode, downmix and "
+                        "resample on the GPU, pinned to resample_poly's float64 result")
+    a = p.parse_args(argv)
+    if a.resample == "device" and a.stream_seconds is not None:
+        p.error("--resample device encodes the whole clip (the streaming encode has no front-end)")
+    if a.decode_back and not a.vocoder:
+        p.error("--decode_back needs --vocoder")
+    if a.stream_seconds is not None and not a.stream_seconds > 0:
+        p.error("--stream_seconds must be > 0")
+    if a.max_tokens < 1:
+        p.error("--max_tokens must be >= 1")
+    try:
+        x, sr = load_wav(a.audio) if a.resample == "host" else load_wav_raw(a.audio)
+    except Exception as e:   # (missing, unreadable, not a WAV)
+        print(f"error: cannot read {a.audio}: {e}", file=sys.stderr)
+        return 2
+    if x.size == 0:
+        print(f"error: {a.audio} holds no samples", file=sys.stderr)
+        return 2
+    print(f"Audio: {a.audio}\n  Duration: {x.shape[0] / sr:.2f}s, SR: {sr}")
+    if a.resample == "device":
+        enc = encoder_factory(a.model, -(-x.shape[0] * 24000 // sr))
+        t0 = time.time()
+        try:
+            codes = enc.encode_pcm([x], sr, channels=1 if x.ndim == 1 else x.shape[1])[0]
+        except (ValueError, RuntimeError) as e:
+            print(f"error: {e}", file=sys.stderr)
+            return 2
+        print(f"Encode time: {time.time() - t0:.3f}s (GPU {enc.last_ms():.2f} ms, front-end on the device)")
+        return _save(a, codes)
+    x = resample(x, sr, 24000)
+    if a.stream_seconds is None:
+        enc = encoder_factory(a.model, max(int(x.size), 1))
+    else:   # the handle's whole-clip buffers are not used: sized for one push
+        enc = encoder_factory(a.model, max(int(round(a.stream_seconds * 24000)), 1))
+    if enc.sample_rate != 24000:
+        x = resample(x, 24000, enc.sample_rate)
+    t0 = time.time()
+    if a.stream_seconds is None:
+        codes = enc.encode([x])[0]
+        print(f"Encode time: {time.time() - t0:.3f}s (GPU {enc.last_ms():.2f} ms)")
+    else:
+        push = max(int(round(a.stream_seconds * enc.sample_rate)), 1)
+        codes = enc.encode_streaming(x, push)
+        print(f"Encode time: {time.time() - t0:.3f}s (streamed, {-(-x.size // push)} pushes of {push} samples)")
+    return _save(a, codes)
 
 
 if __name__ == "__main__":

@@ -19,6 +19,7 @@ class Encoder:
         self.n_q = self.lib.enc_num_quantizers(self.h)
         self.sample_rate = self.lib.enc_sample_rate(self.h)
         self.samples_per_frame = self.lib.enc_samples_per_frame(self.h)
+        self.pcm_calls = 0              # enc_encode_pcm calls so far (a server's id cache shows its hits by it)
 
     def frames(self, n_samples):
         return int(self.lib.enc_frames(self.h, int(n_samples)))
@@ -41,6 +42,55 @@ class Encoder:
                                      mf, hiplib.iptr(nf))
             if rc != 0:
                 raise RuntimeError(f"enc_encode failed ({rc}); see the log")
+            out += [codes[b, :nf[b]].copy() for b in range(len(part))]
+        return out
+
+    def pcm_frames(self, n_in, rate):
+        """frames a clip of n_in input frames at `rate` gives through encode_pcm (< 0: refused)"""
+        return int(self.lib.enc_pcm_frames(self.h, int(n_in), int(rate)))
+
+    @staticmethod
+    def _pcm_payload(clips, channels):
+        """numpy int16 / float32 clips [n] or [n][channels] -> (format, frame counts, the interleaved frames concatenated)"""
+        channels = int(channels)
+        if not clips:
+            raise ValueError("no clips")
+        arrs = [np.asarray(c) for c in clips]
+        dt = arrs[0].dtype
+        if dt not in (np.dtype(np.int16), np.dtype(np.float32)) or any(a.dtype != dt for a in arrs):
+            raise TypeError("clips are int16 or float32 arrays, one dtype per call")
+        for a in arrs:
+            if not ((a.ndim == 1 and channels == 1) or (a.ndim == 2 and a.shape[1] == channels)):
+                raise ValueError(f"a clip of shape {a.shape} is not [n] (mono) or [n][{channels}]")
+        n = np.array([a.shape[0] for a in arrs], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in arrs]))
+        if flat.size == 0:
+            flat = np.zeros(1, dt)
+        return (0 if dt == np.dtype(np.int16) else 1), n, flat
+
+    def encode_pcm(self, clips, rate, channels=1):
+        """PCM as a client has it -> list of int64 [frames, n_q]: numpy int16 or float32 arrays of shape [n] or [n][channels]
+        at `rate` Hz, decoded, downmixed and resampled to 24 kHz on the device (enc_encode_pcm: pinned to
+        scipy.signal.resample_poly's float64 result, the same ids on every host), max_batch clips per library call."""
+        fmt, n, flat = self._pcm_payload(clips, channels)
+        channels = int(channels)
+        out, at = [], 0
+        for i in range(0, len(n), self.max_batch):
+            part = n[i:i + self.max_batch]
+            fr = [self.pcm_frames(x, rate) for x in part]
+            if min(fr) < 0:
+                raise ValueError(f"encode_pcm refused a clip of {part.tolist()} frames at {rate} Hz (see the log)")
+            mf = max(fr)
+            codes = np.empty((len(part), mf, self.n_q), np.int64)
+            nf = np.zeros(len(part), np.int32)
+            buf = flat[at:at + int(part.sum()) * channels]
+            at += int(part.sum()) * channels
+            self.pcm_calls += 1
+            rc = self.lib.enc_encode_pcm(self.h, buf.ctypes.data, fmt, channels, int(rate),
+                                         hiplib.iptr(np.ascontiguousarray(part)), len(part), codes.ctypes.data_as(hiplib.i64p), mf,
+                                         hiplib.iptr(nf))
+            if rc != 0:
+                raise RuntimeError(f"enc_encode_pcm failed ({rc}); see the log")
             out += [codes[b, :nf[b]].copy() for b in range(len(part))]
         return out
 

@@ -183,6 +183,9 @@ def load(path: str | None = None):
     _sig(lib, "enc_frames", c_int, [c_void_p, c_int])
     _sig(lib, "enc_encode", c_int, [c_void_p, f32p, i32p, c_int, i64p_, c_int, i32p])
     _sig(lib, "enc_last_ms", c_float, [c_void_p])
+    _sig(lib, "enc_pcm_frames", c_int, [c_void_p, c_int, c_int])
+    _sig(lib, "enc_encode_pcm", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, i32p, c_int, i64p_, c_int, i32p])
+    _sig(lib, "enc_debug_pcm", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, i32p, c_int, f32p, i32p, i32p])
     _sig(lib, "enc_debug_shape", c_int, [c_void_p, i32p, c_int, c_int, i32p, i32p])
     _sig(lib, "enc_debug_run", c_int, [c_void_p, f32p, i32p, c_int, c_int, f32p, i32p, i32p])
     # include/qwen3tts_enc_stream.h

@@ -29,6 +29,15 @@ def recv_exact(conn, n: int) -> bytes:
     return bytes(buf)
 
 
+def recv_payload(conn, n: int) -> bytes:
+    """The n raw bytes that follow a request's JSON on the same connection (batch_server's "prompt_audio": the clips' interleaved
+    little-endian PCM, too large for the JSON's MAX_REQUEST_BYTES); raises ValueError if the peer closes before they are there."""
+    raw = recv_exact(conn, n)
+    if len(raw) < n:
+        raise ValueError(f"payload ended after {len(raw)} of {n} bytes")
+    return raw
+
+
 # client -> talker: u32 len + UTF-8 JSON {"text", "language"}  (+ optional "token_ids" extension)
 def pack_talker_request(text: str, language: str = "russian", token_ids=None) -> bytes:
     msg = {"text": text, "language": language}
