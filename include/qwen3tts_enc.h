@@ -53,5 +53,7 @@ float enc_last_ms(void* h);
 #include "qwen3tts_enc_stream.h"
 /* PCM front-end: s16 / f32 PCM of any channel count at the client's rate, decoded, downmixed and resampled on the device */
 #include "qwen3tts_enc_pcm.h"
+/* The two together: a stream's pushes as s16 / f32 PCM at the client's rate, the same samples bit for bit */
+#include "qwen3tts_enc_stream_pcm.h"
 
 #endif /* QWEN3TTS_ENC_H */

@@ -19,7 +19,9 @@
  * longer than the window: not the same bits), ids equal except at near-ties.  Exact-fp32 arithmetic only.
  *
  * One caller thread per encoder handle and the objects on it; every entry point binds the thread to the handle's device.
- * All device memory is allocated by enc_stream_create.
+ * All device memory is allocated by enc_stream_create (the carry rows of the PCM front-end, qwen3tts_enc_stream_pcm.h, by
+ * its first push; a clip is fed by enc_stream_push or by enc_stream_push_pcm, not both: the other one is refused until
+ * enc_stream_reset).
  */
 #ifndef QWEN3TTS_ENC_STREAM_H
 #define QWEN3TTS_ENC_STREAM_H

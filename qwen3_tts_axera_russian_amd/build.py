@@ -23,7 +23,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
 SOURCES = ["q3_common.cpp", "q3_formats.cpp", "q3_kernels.hip", "q3_model.hip", "q3_talker_api.hip", "q3_cp_api.hip",
            "q3_engine.hip", "q3_voc_kernels.hip", "q3_voc.hip", "q3_voc_stream.hip", "q3_enc.hip", "q3_enc_pcm.hip", "q3_enc_stream.hip",
-           "q3_text_api.hip"]
+           "q3_enc_stream_pcm.hip", "q3_text_api.hip"]
 TEST_SOURCES = ["q3_test_api.hip"]
 ARCH = os.environ.get("Q3_OFFLOAD_ARCH", "gfx950")
 # kernarg preload: the leading scalar kernel arguments arrive in SGPRs at wave launch (gfx940+)
@@ -42,7 +42,8 @@ def _newer(dst: str, srcs) -> bool:
 NO_SPILL = ("resunit_kernel", "linear_kernelILi1ELi1E", "linear_kernelILi1ELi2E", "linear_kernelILi2ELi1E",
             "linear_kernelILi2ELi2E", "attn_kernel", "attn_short_kernel", "cp_argmax_kernel", "talker_sample_kernel",
             "voc_attn_incr_kernel", "voc_incr_prepend_kernel", "voc_incr_emit_kernel", "voc_incr_prepend_split_kernel",
-            "enc_conv_in_kernel", "enc_stream_unfold_kernel", "enc_stream_emit_kernel",
+            "enc_conv_in_kernel", "enc_stream_unfold_kernel", "enc_stream_emit_kernel", "enc_stream_pcm_kernel",
+            "enc_stream_pcm_carry_kernel",
             # (the name the stream's first conv had before it became enc_conv_in_kernel's hist != nullptr case:
             # tests/test_enc_stream_contract.py still asks for it, and a kernel that comes back under it is held too)
             "enc_stream_conv_in_kernel")

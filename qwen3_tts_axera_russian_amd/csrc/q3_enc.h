@@ -142,10 +142,62 @@ static inline void enc_stream_plan(const int* ks, const int* strides, int n_leve
     for (int l = 0; l < n_levels; l++) carry[l] = (ks[l] - strides[l]) + before_cols[l] % strides[l];
 }
 
-struct EncStream;
+// ---- the streaming encode's object (q3_enc_stream.hip; q3_enc_stream_pcm.hip feeds it) ----
+struct EncStreamPcm;
+enum { ENC_SRC_NONE = 0, ENC_SRC_F32 = 1, ENC_SRC_PCM = 2 };   // what has fed a stream since its reset
+struct EncStream {
+    Enc* e = nullptr;
+    int max_streams = 0, max_push = 0;
+    std::vector<long long> total;         // samples a stream has taken since its reset
+    std::vector<char> finished;
+    std::vector<char> source;             // ENC_SRC_*: enc_stream_push and enc_stream_push_pcm do not mix on one clip
+    std::vector<int> lev_k, lev_s;        // the strided ops' taps and strides, in order
+    std::vector<int> level_of;            // per op: the level of its input
+    std::vector<int> H;                   // per op: carried columns (0: nothing)
+    std::vector<size_t> hoff;             // per op: offset of its [channels][H] block inside a stream's state
+    size_t state_floats = 0;
+    float* d_hist = nullptr;              // [max_streams][state_floats]
+    float* buf[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t buf_elems = 0, kv_elems = 0;   // floats of one work buffer / of d_kv (without the slack)
+    float* d_kv = nullptr;                // attention: [carried window | new] k and v rows
+    float* d_pcm = nullptr;               // [max_batch][pitch(max_push)]
+    int* d_meta = nullptr;                // [2 + n_ops][max_batch]: streams, per op the columns its level had taken, frame offsets
+    float* d_z = nullptr;                 // [frames_cap][2 * dim]: the quantiser's input of the whole push
+    float* d_emb = nullptr;               // [frames_cap][emb_C]: the pre-quantiser embedding (test hook)
+    int64_t* d_codes = nullptr;           // [frames_cap][nq]
+    size_t frames_cap = 0;
+    int emb_op = -1, emb_C = 0;           // the op whose input is the embedding (the projection before the quantiser)
+    DeviceAllocs mem;
+    float last_ms = 0.f;
+    int last_launches = 0;
+    EncStreamPcm* pcm = nullptr;          // the PCM front-end's carry rows, from the first enc_stream_push_pcm on (not in `mem`)
+};
+
+// A push whose samples do not come from the host: the feed writes entry b's n 24 kHz samples into row b of d_pcm, from
+// column 0 on, where the walk's first conv reads them.  Each call returns the kernel launches it made, or < 0.
+struct EncStreamFeed {
+    virtual ~EncStreamFeed() = default;
+    virtual int begin() = 0;   // the push is valid and nothing has been written yet: uploads (a failure refuses the push)
+    virtual int fill(const std::vector<int>& members, long long n) = 0;   // one group (entry indices) of n > 0 samples each
+    virtual int end() = 0;     // after the last group's walk
+};
+
 // enc_stream_push with one more output (the test library's q3t_enc_stream_embeddings): emb_out, when given, receives the
-// pre-quantiser embedding columns of the push, [frames][channels] packed like the codes
+// pre-quantiser embedding columns of the push, [frames][channels] packed like the codes.  feed: n_new are the 24 kHz counts
+// of a push the feed supplies (pcm is not read)
 int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const float* pcm, const int32_t* n_new, const int32_t* finish,
-                         int64_t* codes_out, int64_t out_capacity_frames, int64_t* offsets, float* emb_out, int* emb_channels);
+                         int64_t* codes_out, int64_t out_capacity_frames, int64_t* offsets, float* emb_out, int* emb_channels,
+                         EncStreamFeed* feed = nullptr);
+// enc_stream_push_max_frames for a push from `source`; < 0 refused (logged)
+int enc_stream_plan_frames(const EncStream* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish, int source);
+// enc_stream_free's part for the front-end's allocations (q3_enc_stream_pcm.hip)
+void enc_stream_pcm_release(EncStream* s);
+
+// ---- the PCM front-end's device tables, shared by enc_encode_pcm and enc_stream_push_pcm (q3_enc_pcm.hip) ----
+struct EncPcmPlan;
+// the device table of the plan: one the handle kept, or built now in place of the least recently used
+const double* enc_pcm_table(Enc* e, const EncPcmPlan& p);
+// e->pcm_raw holds at least `bytes` (it grows to the largest payload seen); false: no memory, logged under `who`
+bool enc_pcm_raw_reserve(Enc* e, size_t bytes, const char* who);
 
 }  // namespace q3

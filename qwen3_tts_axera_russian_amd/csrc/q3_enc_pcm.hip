@@ -84,7 +84,7 @@ void enc_pcm_release(Enc* e) {
 }
 
 // the device table of the plan: one the handle kept, or built now in place of the least recently used of ENC_PCM_TABLES
-static const double* enc_pcm_table(Enc* e, const EncPcmPlan& p) {
+const double* enc_pcm_table(Enc* e, const EncPcmPlan& p) {
     e->pcm_calls++;
     for (auto& t : e->pcm_tables)
         if (t.up == p.up && t.down == p.down) {
@@ -114,6 +114,20 @@ static const double* enc_pcm_table(Enc* e, const EncPcmPlan& p) {
     t.used = e->pcm_calls;
     e->pcm_tables.push_back(t);
     return d;
+}
+
+bool enc_pcm_raw_reserve(Enc* e, size_t bytes, const char* who) {
+    if (bytes <= e->pcm_raw_bytes) return true;
+    // grows to the largest payload seen (at most 8 channels x 8 input frames per sample)
+    if (e->pcm_raw) hipFree(e->pcm_raw);
+    e->pcm_raw = nullptr;
+    e->pcm_raw_bytes = 0;
+    if (hipMalloc(&e->pcm_raw, bytes) != hipSuccess) {
+        Q3_LOG("%s: no device memory for a payload of %zu bytes", who, bytes);
+        return false;
+    }
+    e->pcm_raw_bytes = bytes;
+    return true;
 }
 
 // checks the call, uploads the payload in its wire form and launches the front-end -> lens = the clips' 24 kHz lengths; 0 / <0
@@ -158,16 +172,7 @@ static int enc_pcm_prepare(Enc* e, const void* pcm, int format, int channels, in
     const double* taps = enc_pcm_table(e, p);
     if (!taps) return -1;
     if (!e->pcm_meta) Q3_HIP(hipMalloc((void**)&e->pcm_meta, (size_t)e->max_batch * 3 * sizeof(long long)), -1);
-    if (bytes > e->pcm_raw_bytes) {   // grows to the largest payload seen (at most 8 channels x 8 input frames per sample)
-        if (e->pcm_raw) hipFree(e->pcm_raw);
-        e->pcm_raw = nullptr;
-        e->pcm_raw_bytes = 0;
-        if (hipMalloc(&e->pcm_raw, bytes) != hipSuccess) {
-            Q3_LOG("%s: no device memory for a payload of %zu bytes", who, bytes);
-            return -1;
-        }
-        e->pcm_raw_bytes = bytes;
-    }
+    if (!enc_pcm_raw_reserve(e, bytes, who)) return -1;
     const long L = *std::max_element(lens.begin(), lens.begin() + B), ld = enc_pitch(L);
     const int W = (int)enc_pcm_window(p, ENC_PCM_OUTPUTS);
     const size_t lds = ((size_t)p.per_phase * p.up + (size_t)W) * sizeof(double);

@@ -12,6 +12,8 @@
 //   enc_stream_emit_kernel      columns of a group's activation -> rows of the push's packed [frame][channel] buffer
 // An activation is buf[cur] = [B][C][pitch(skip + n)]: `skip` leading columns are outputs of carried columns (nothing reads
 // them), n are the new ones.  No rule looks at n, skip or B, so a column's bits are those of any other split.
+// A push's samples are the host's float32 (enc_stream_push), or an EncStreamFeed writes them into d_pcm's rows on the device
+// (enc_stream_push_pcm, q3_enc_stream_pcm.hip); plan, walk and hand-out are the same for both.
 #include "../../include/qwen3tts_enc.h"
 #include "q3_enc.h"
 
@@ -67,32 +69,6 @@ __global__ void __launch_bounds__(256) enc_stream_emit_kernel(const float* __res
     if (c < C) out[((size_t)off[b] + j) * C + c] = y[((size_t)b * C + c) * ld + skip + j];
 }
 
-struct EncStream {
-    Enc* e = nullptr;
-    int max_streams = 0, max_push = 0;
-    std::vector<long long> total;         // samples a stream has taken since its reset
-    std::vector<char> finished;
-    std::vector<int> lev_k, lev_s;        // the strided ops' taps and strides, in order
-    std::vector<int> level_of;            // per op: the level of its input
-    std::vector<int> H;                   // per op: carried columns (0: nothing)
-    std::vector<size_t> hoff;             // per op: offset of its [channels][H] block inside a stream's state
-    size_t state_floats = 0;
-    float* d_hist = nullptr;              // [max_streams][state_floats]
-    float* buf[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t buf_elems = 0, kv_elems = 0;   // floats of one work buffer / of d_kv (without the slack)
-    float* d_kv = nullptr;                // attention: [carried window | new] k and v rows
-    float* d_pcm = nullptr;               // [max_batch][pitch(max_push)]
-    int* d_meta = nullptr;                // [2 + n_ops][max_batch]: streams, per op the columns its level had taken, frame offsets
-    float* d_z = nullptr;                 // [frames_cap][2 * dim]: the quantiser's input of the whole push
-    float* d_emb = nullptr;               // [frames_cap][emb_C]: the pre-quantiser embedding (test hook)
-    int64_t* d_codes = nullptr;           // [frames_cap][nq]
-    size_t frames_cap = 0;
-    int emb_op = -1, emb_C = 0;           // the op whose input is the embedding (the projection before the quantiser)
-    DeviceAllocs mem;
-    float last_ms = 0.f;
-    int last_launches = 0;
-};
-
 namespace {
 
 struct Plan {
@@ -100,7 +76,7 @@ struct Plan {
     PushGroups groups;                 // keys: n_in[0 .. n_levels], then the finish flag
 };
 
-int make_plan(const EncStream* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish, Plan& p) {
+int make_plan(const EncStream* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish, int source, Plan& p) {
     if (n < 0 || (n > 0 && (!streams || !n_new))) {
         Q3_LOG("enc_stream_push: NULL streams or n_new");
         return -1;
@@ -119,6 +95,10 @@ int make_plan(const EncStream* s, int n, const int32_t* streams, const int32_t* 
         seen[k] = 1;
         if (s->finished[k]) {
             Q3_LOG("enc_stream_push: stream %d has finished (enc_stream_reset starts the next clip)", k);
+            return -1;
+        }
+        if (s->source[k] != ENC_SRC_NONE && s->source[k] != source) {
+            Q3_LOG("enc_stream_push: stream %d: enc_stream_push and enc_stream_push_pcm do not mix on one clip (enc_stream_reset starts the next)", k);
             return -1;
         }
         if (s->total[k] + n_new[i] > 0x7fffffffLL) {
@@ -289,7 +269,7 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
 }  // namespace
 
 int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const float* pcm, const int32_t* n_new, const int32_t* finish,
-                         int64_t* codes_out, int64_t cap, int64_t* offsets, float* emb_out, int* emb_channels) {
+                         int64_t* codes_out, int64_t cap, int64_t* offsets, float* emb_out, int* emb_channels, EncStreamFeed* feed) {
     if (!s || !offsets) {
         Q3_LOG("enc_stream_push: NULL object or offsets");
         return -1;
@@ -297,7 +277,8 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
     Enc* e = s->e;
     enc_bind(e);
     Plan p;
-    if (make_plan(s, n, streams, n_new, finish, p)) return -1;
+    const int source = feed ? ENC_SRC_PCM : ENC_SRC_F32;
+    if (make_plan(s, n, streams, n_new, finish, source, p)) return -1;
     long long frames = 0;
     size_t samples = 0;
     std::vector<size_t> poff(n, 0);
@@ -306,11 +287,11 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
         samples += (size_t)n_new[i];
         frames += p.n_frames[i];
     }
-    if (frames > cap || (frames > 0 && !codes_out) || (samples > 0 && !pcm) || (size_t)frames > s->frames_cap) {
+    if (frames > cap || (frames > 0 && !codes_out) || (samples > 0 && !pcm && !feed) || (size_t)frames > s->frames_cap) {
         Q3_LOG("enc_stream_push: %lld frames do not fit the caller's buffer of %lld (or no samples given)", frames, (long long)cap);
         return -1;
     }
-    for (size_t i = 0; i < samples; i++)
+    for (size_t i = 0; !feed && i < samples; i++)
         if (!std::isfinite(pcm[i])) {
             Q3_LOG("enc_stream_push: sample %zu is not finite", i);
             return -1;
@@ -321,6 +302,7 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
             Q3_LOG("enc_stream_push: a push does not fit the object's work buffers");
             return -1;
         }
+    if (feed && feed->begin() < 0) return -1;
     // the push is valid
     long long at = 0;
     for (int i = 0; i < n; i++) offsets[i] = at, at += p.n_frames[i];
@@ -346,11 +328,21 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
             meta[b] = k;
             for (size_t i = 0; i < nops; i++) meta[(1 + i) * mb + b] = (int)bc[s->level_of[i]];
             meta[(1 + nops) * mb + b] = (int)offsets[en];
-            if (n_new[en] > 0)
+            if (n_new[en] > 0 && !feed)
                 Q3_HIP(hipMemcpyAsync(s->d_pcm + (size_t)b * ldp, pcm + poff[en], sizeof(float) * (size_t)n_new[en], hipMemcpyHostToDevice, e->s), -1);
         }
         Q3_HIP(hipMemcpyAsync(s->d_meta, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice, e->s), -1);
+        if (feed && p.groups.keys[g][0] > 0) {
+            const int r = feed->fill(mem, p.groups.keys[g][0]);
+            if (r < 0) return -1;
+            s->last_launches += r;
+        }
         if (walk(s, p.groups.keys[g], B, false, emb_out != nullptr, &s->last_launches)) return -1;
+    }
+    if (feed) {
+        const int r = feed->end();
+        if (r < 0) return -1;
+        s->last_launches += r;
     }
     if (frames > 0) {
         const EncOp& q = e->ops.back();
@@ -365,9 +357,18 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
     if (!p.groups.keys.empty()) hipEventElapsedTime(&s->last_ms, e->e0, e->e1);
     for (int i = 0; i < n; i++) {
         s->total[streams[i]] += n_new[i];
+        s->source[streams[i]] = (char)source;
         if (finish && finish[i]) s->finished[streams[i]] = 1;
     }
     return 0;
+}
+
+int enc_stream_plan_frames(const EncStream* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish, int source) {
+    Plan p;
+    if (!s || make_plan(s, n, streams, n_new, finish, source, p)) return -1;
+    long long t = 0;
+    for (int i = 0; i < n; i++) t += p.n_frames[i];
+    return (int)t;
 }
 
 }  // namespace q3
@@ -381,6 +382,7 @@ void enc_stream_free(void* ss) {
     if (!s) return;
     enc_bind(s->e);
     hipStreamSynchronize(s->e->s);
+    enc_stream_pcm_release(s);
     delete s;   // (its allocations go with it: DeviceAllocs)
 }
 
@@ -397,6 +399,7 @@ void* enc_stream_create(void* h, int max_streams, int max_push_samples) {
     s->max_push = max_push_samples;
     s->total.assign(max_streams, 0);
     s->finished.assign(max_streams, 0);
+    s->source.assign(max_streams, ENC_SRC_NONE);
     const size_t nops = e->ops.size();
     s->H.assign(nops, 0);
     s->hoff.assign(nops, 0);
@@ -492,16 +495,12 @@ int enc_stream_reset(void* ss, int stream) {
         Q3_HIP(hipMemsetAsync(s->d_hist + (size_t)stream * s->state_floats, 0, sizeof(float) * s->state_floats, s->e->s), -1);
     s->total[stream] = 0;
     s->finished[stream] = 0;
+    s->source[stream] = ENC_SRC_NONE;
     return 0;
 }
 
-int enc_stream_push_max_frames(void* ss, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish) {
-    EncStream* s = (EncStream*)ss;
-    Plan p;
-    if (!s || make_plan(s, n, streams, n_new, finish, p)) return -1;
-    long long t = 0;
-    for (int i = 0; i < n; i++) t += p.n_frames[i];
-    return (int)t;
+int enc_stream_push_max_frames(void* s, int n, const int32_t* streams, const int32_t* n_new, const int32_t* finish) {
+    return enc_stream_plan_frames((EncStream*)s, n, streams, n_new, finish, ENC_SRC_F32);
 }
 
 int enc_stream_push(void* s, int n, const int32_t* streams, const float* pcm, const int32_t* n_new, const int32_t* finish,

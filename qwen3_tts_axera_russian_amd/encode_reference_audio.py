@@ -3,7 +3,7 @@ scripts/encode_reference_audio.py, on the GPU encoder).
 
     python -m qwen3_tts_axera_russian_amd.encode_reference_audio --audio ref.wav --model enc.q3w --output_dir prompt/ \
         [--ref_text "..."] [--max_tokens 256] [--decode_back ref_decoded.wav --vocoder voc.q3w] [--stream_seconds 1.0]
-        [--resample host|device]
+        [--resample host|device] [--push_seconds 0.5]
 
 Writes ref_codec_tokens.npy (int64 [min(T, max_tokens)][16], the semantic id first) to --output, or, with --output_dir,
 a prompt_dir holding ref_codec_tokens.npy and (with --ref_text) ref_text.txt.  --model is an encoder container
@@ -17,7 +17,10 @@ float32 (--resample host, the default: unchanged, bit for bit), or, with --resam
 file holds it -- int16 or float32 samples, the channels interleaved -- and decoded, downmixed and resampled on the GPU
 (Encoder.encode_pcm / enc_encode_pcm).  The device path is pinned: scipy.signal.resample_poly's rules evaluated in float64 and
 rounded once to float32, so every host that opens the library gets the same ids for the same file; the host path depends on
-the host's scipy and its float32 arithmetic and is pinned to nothing.  qwen_tts's own resampler is not available here:
+the host's scipy and its float32 arithmetic and is pinned to nothing.  --resample device --push_seconds S sends the file's own
+frames through the streaming encode in pushes of round(S * the file's rate) frames (Encoder.encode_streaming_pcm /
+enc_stream_push_pcm): the same pinned samples bit for bit whatever S, device memory that of one push, a WAV of any length.
+qwen_tts's own resampler is not available here:
 neither path is pinned to it."""
 from __future__ import annotations
 
@@ -133,9 +136,15 @@ def main(argv=None, encoder_factory=open_encoder):
     p.add_argument("--resample", choices=("host", "device"), default="host",
                    help="host: scipy.signal.resample_poly in float32 before the encoder (default); device: decode, downmix and "
                         "resample on the GPU, pinned to resample_poly's float64 result")
+    p.add_argument("--push_seconds", type=float, default=None,
+                   help="with --resample device: stream the file's own frames in pushes of this many seconds (a WAV of any length)")
     a = p.parse_args(argv)
     if a.resample == "device" and a.stream_seconds is not None:
-        p.error("--resample device encodes the whole clip (the streaming encode has no front-end)")
+        p.error("--resample device streams with --push_seconds (--stream_seconds pushes host-resampled 24 kHz samples)")
+    if a.push_seconds is not None and a.resample != "device":
+        p.error("--push_seconds needs --resample device (--stream_seconds streams the host path)")
+    if a.push_seconds is not None and not a.push_seconds > 0:
+        p.error("--push_seconds must be > 0")
     if a.decode_back and not a.vocoder:
         p.error("--decode_back needs --vocoder")
     if a.stream_seconds is not None and not a.stream_seconds > 0:
@@ -151,6 +160,18 @@ def main(argv=None, encoder_factory=open_encoder):
         print(f"error: {a.audio} holds no samples", file=sys.stderr)
         return 2
     print(f"Audio: {a.audio}\n  Duration: {x.shape[0] / sr:.2f}s, SR: {sr}")
+    if a.resample == "device" and a.push_seconds is not None:
+        push = max(int(round(a.push_seconds * sr)), 1)
+        room = -(-push * 24000 // sr) + 32          # 24 kHz samples one push may settle (32: the filter's tail at a finish)
+        enc = encoder_factory(a.model, room)        # (the handle's whole-clip buffers are not used: sized for one push)
+        t0 = time.time()
+        try:
+            codes = enc.encode_streaming_pcm(x, sr, channels=1 if x.ndim == 1 else x.shape[1], push_frames=push, max_push_samples=room)
+        except (ValueError, RuntimeError) as e:
+            print(f"error: {e}", file=sys.stderr)
+            return 2
+        print(f"Encode time: {time.time() - t0:.3f}s (streamed, pushes of up to {push} frames at {sr} Hz, front-end on the device)")
+        return _save(a, codes)
     if a.resample == "device":
         enc = encoder_factory(a.model, -(-x.shape[0] * 24000 // sr))
         t0 = time.time()

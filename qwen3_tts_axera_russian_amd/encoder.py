@@ -119,6 +119,26 @@ class Encoder:
         finally:
             st.close()
 
+    def encode_streaming_pcm(self, x, rate, channels=1, push_frames=None, max_push_samples=24000):
+        """One clip of any length as a client has it (int16 or float32, [n] or [n][channels], at `rate` Hz) through the
+        streaming encode in pushes of push_frames input frames (default and cap: what one push of max_push_samples takes at
+        this rate) -> int64 [frames, n_q].  The front-end runs on the device; max_samples does not bound the clip."""
+        x = np.asarray(x)
+        st = self.stream(1, int(max_push_samples))
+        try:
+            most = st.pcm_max_frames_in(rate)
+            if most < 1:
+                raise ValueError(f"encode_streaming_pcm: {rate} Hz is refused, or a push of {max_push_samples} samples is too short for it")
+            push = most if push_frames is None else min(int(push_frames), most)
+            if push <= 0:
+                raise ValueError("push_frames must be positive")
+            parts = []
+            for at in range(0, max(x.shape[0], 1), push):
+                parts.append(st.push_pcm([(0, x[at:at + push], at + push >= x.shape[0])], rate, channels)[0])
+            return np.concatenate(parts, axis=0)
+        finally:
+            st.close()
+
     def close(self):
         if self.h:
             self.lib.enc_free(self.h)
@@ -172,6 +192,41 @@ class EncoderStream:
                                       codes.ctypes.data_as(hiplib.i64p), cap, off.ctypes.data_as(hiplib.i64p))
         if rc != 0:
             raise RuntimeError(f"enc_stream_push failed ({rc}); see the log")
+        self.last_launches = int(self.lib.enc_stream_last_launches(self.h))
+        self.last_ms = float(self.lib.enc_stream_last_ms(self.h))
+        return [codes[off[i]:off[i + 1]].copy() for i in range(len(st))]
+
+    def pcm_max_frames_in(self, rate):
+        """the most input frames one entry of one push_pcm may bring at `rate` (< 0: a rate the front-end refuses)"""
+        return int(self.lib.enc_stream_pcm_max_frames_in(self.h, int(rate)))
+
+    def pcm_samples(self, rate, n_in_total, finished=False):
+        """24 kHz samples a stream has handed to the encoder after n_in_total input frames at `rate`"""
+        return int(self.lib.enc_stream_pcm_samples(self.h, int(rate), int(n_in_total), int(bool(finished))))
+
+    def pcm_device_bytes(self):
+        """device memory of the PCM front-end (carry rows; 0 until the first push_pcm, constant after it)"""
+        return int(self.lib.enc_stream_pcm_device_bytes(self.h))
+
+    def push_pcm(self, entries, rate, channels=1):
+        """push() for PCM as a client has it: entries (stream, int16 or float32 array [n] or [n][channels] at `rate` Hz, finish),
+        one dtype per call, at most pcm_max_frames_in(rate) frames each.  Decoded, downmixed and resampled on the device
+        (enc_stream_push_pcm): joined, a stream's samples are the bits Encoder.encode_pcm prepares for the whole clip, whatever
+        the split.  Returns what push returns."""
+        channels = int(channels)
+        st = np.array([e[0] for e in entries], np.int32)
+        fin = np.array([int(bool(e[2])) for e in entries], np.int32)
+        fmt, n_in, flat = Encoder._pcm_payload([e[1] for e in entries], channels)
+        args = (self.h, len(st), hiplib.iptr(st))
+        cap = int(self.lib.enc_stream_push_pcm_max_frames(*args, fmt, channels, int(rate), hiplib.iptr(n_in), hiplib.iptr(fin)))
+        if cap < 0:
+            raise RuntimeError("enc_stream_push_pcm: invalid push (see the log)")
+        codes = np.empty((max(cap, 1), self.n_q), np.int64)
+        off = np.zeros(len(st) + 1, np.int64)
+        rc = self.lib.enc_stream_push_pcm(*args, flat.ctypes.data, fmt, channels, int(rate), hiplib.iptr(n_in), hiplib.iptr(fin),
+                                          codes.ctypes.data_as(hiplib.i64p), cap, off.ctypes.data_as(hiplib.i64p))
+        if rc != 0:
+            raise RuntimeError(f"enc_stream_push_pcm failed ({rc}); see the log")
         self.last_launches = int(self.lib.enc_stream_last_launches(self.h))
         self.last_ms = float(self.lib.enc_stream_last_ms(self.h))
         return [codes[off[i]:off[i + 1]].copy() for i in range(len(st))]

@@ -198,6 +198,15 @@ def load(path: str | None = None):
     _sig(lib, "enc_stream_last_launches", c_int, [c_void_p])
     _sig(lib, "enc_stream_state_bytes", ctypes.c_int64, [c_void_p])
     _sig(lib, "enc_stream_device_bytes", ctypes.c_int64, [c_void_p])
+    # include/qwen3tts_enc_stream_pcm.h (and the hook enc_stream_debug_push_pcm beside enc_debug_pcm)
+    _sig(lib, "enc_stream_pcm_samples", ctypes.c_int64, [c_void_p, c_int, ctypes.c_int64, c_int])
+    _sig(lib, "enc_stream_pcm_max_frames_in", c_int, [c_void_p, c_int])
+    _sig(lib, "enc_stream_push_pcm_max_frames", c_int, [c_void_p, c_int, i32p, c_int, c_int, c_int, i32p, i32p])
+    _sig(lib, "enc_stream_push_pcm", c_int, [c_void_p, c_int, i32p, c_void_p, c_int, c_int, c_int, i32p, i32p, i64p_, ctypes.c_int64,
+                                             i64p_])
+    _sig(lib, "enc_stream_pcm_device_bytes", ctypes.c_int64, [c_void_p])
+    _sig(lib, "enc_stream_debug_push_pcm", c_int, [c_void_p, c_int, i32p, c_void_p, c_int, c_int, c_int, i32p, i32p, i64p_,
+                                                   ctypes.c_int64, i64p_, f32p, i64p_])
     # include/qwen3tts_text.h
     _sig(lib, "tfe_load", c_void_p, [c_char_p, c_char_p, c_int])
     _sig(lib, "tfe_free", None, [c_void_p])
