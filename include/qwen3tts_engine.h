@@ -76,6 +76,10 @@ int q3e_start(void* e, int B, const float* prefix, const int32_t* n_rows, const 
  * steps executed, <0 on error. */
 int q3e_run(void* e, int n_frames);
 
+/* Nodes of the captured frame (the first chain's graph): 0 before the first capture or after a call that dropped it, <0 on
+ * error.  A diagnostic: the count is the same with and without q3e_scores_reserve. */
+int q3e_graph_nodes(void* e);
+
 /* GPU time of the last q3e_run / q3e_start in milliseconds (HIP events on the engine's stream). */
 float q3e_last_run_ms(void* e);
 float q3e_last_prefill_ms(void* e);
@@ -83,6 +87,29 @@ float q3e_last_prefill_ms(void* e);
 /* Codes so far: out[f][b][16] for f < returned frame count (<= max_out_frames); rows of finished
  * utterances hold -1 in column 0.  n_frames_per_utt[b] = frames utterance b really emitted. */
 int q3e_get_codes(void* e, int32_t* out, int max_out_frames, int32_t* n_frames_per_utt);
+
+/* Log-probabilities of the emitted ids (opt-in; DESIGN.md 2 "The score of an emitted id").
+ *
+ * For each of a frame's 16 sampling decisions the device records one f32: the model's log-probability, at temperature 1, of
+ * THE ID THE STREAM CONTINUES WITH -- the id that is fed back: the forced one where q3e_set_forced_codes replaces the
+ * decision, else the chosen one.  With z = the raw logit (NaN read as +inf) and m the maximum over the set,
+ *     lp = z_u - m - log(sum_v exp(z_v - m)),
+ * for column 0 over the talker's allowed set {v < cp_vocab} + {codec_eos} (an id outside it scores -inf), for columns 1..15
+ * over all cp_vocab logits of the group's head.  It is the model's distribution, not the sampler's: temperature, top-k /
+ * top-p, the repetition penalty, the EOS boost and masks, ignore_eos, forcing and the per-slot rules leave it unchanged.
+ * Degenerate rows give the IEEE result of the formula (m = +inf, or nothing above -inf: NaN; a -inf id beside finite ones:
+ * -inf).  fp32, expf / logf, one fixed reduction order: the same bits run to run.
+ *
+ * q3e_scores_reserve(e, 1): allocates the scores [max_frames][max_batch][16] (laid out like the codes) and makes the pointer
+ * an argument of the frame's 16 sampling launches, which are then kernels of their own (*_scores); the next q3e_run
+ * captures again.  No launch and no graph node is added.  0 releases.  <0 with nothing changed while a per-slot batch is
+ * open (call before q3e_open, like q3e_rules_reserve).  An engine that never calls it launches the kernels it always did,
+ * and with or without it the codes are the same bits in every mode.  A slot's scores are zeroed wherever its codes are reset.
+ *
+ * q3e_get_scores: out[f][b][16], the frame count and n_frames_per_utt of q3e_get_codes.  Every entry of a frame whose
+ * column 0 of the codes is < 0, and of a frame at or past the utterance's count, reads 0.0f.  <0 without a reservation. */
+int q3e_scores_reserve(void* e, int on);
+int q3e_get_scores(void* e, float* out, int max_out_frames, int32_t* n_frames_per_utt);
 
 /* Continuous batching (no counterpart in the reference, whose servers take one request at a time: SURVEY.md 8f2).
  * q3e_get_done: done[b] = 1 once utterance b has ended (EOS, or its frame budget); frames[b] (may be NULL) = frames it

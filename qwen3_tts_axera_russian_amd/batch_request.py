@@ -46,6 +46,13 @@ request alone.  Encoded ids are kept in an LRU (PromptAudioCache, --prompt_audio
 descriptor and the payload: a repeated clip runs no encode.  "register_voice": "NAME" (with one "prompt_audio" object) stores
 the ids and the prompt's text under NAME for later "voice": "NAME" requests; with "texts": [] the request only registers and is
 answered i32 0.  A --voice name cannot be replaced, a run-time one can, and at most --max_voices run-time names are kept.
+
+Log-probabilities (`--concurrent --logprobs`): a request may carry "logprobs": true, and its reply then holds, beside every
+utterance's codes, one float32 per id: the model's log-probability, at temperature 1, of the id the stream continued with
+(include/qwen3tts_engine.h, q3e_scores_reserve: the model's distribution, not the sampler's -- no sampling key or sampler
+rule enters it).  They align with the codes the reply holds: a prompted utterance's generated frames, not its prompt's.
+batch_wire says where they stand in the reply; "logprobs": false is a request without the key.  The key without the flag (in
+any other mode too), or with a value that is not a boolean, is answered -2 for that request alone.
 """
 from __future__ import annotations
 
@@ -312,6 +319,19 @@ def load_voice(prompt_dir):
         with open(os.path.join(prompt_dir, "ref_text.txt")) as f:
             text = f.read()
     return codes.astype(np.int64).tolist(), text
+
+
+def request_logprobs(msg, enabled):
+    """A request's "logprobs" key -> whether its reply carries the log-probabilities.  Raises ValueError on the key when the
+    server runs without --logprobs (`enabled` false) and on a value that is not a boolean."""
+    v = msg.get("logprobs")
+    if v is None:
+        return False
+    if not isinstance(v, bool):
+        raise ValueError(f"logprobs must be true or false (got {v!r})")
+    if not enabled:
+        raise ValueError("logprobs need a --concurrent --logprobs server")
+    return v
 
 
 def request_has_rules(msg):

@@ -45,7 +45,7 @@ import typing
 import numpy as np
 
 from . import protocol as P
-from .batch_request import request_vocoder, request_vocoder_arithmetic
+from .batch_request import request_logprobs, request_vocoder, request_vocoder_arithmetic
 
 
 @dataclasses.dataclass
@@ -59,6 +59,9 @@ class ReplyState:
     prompts: dict = dataclasses.field(default_factory=dict)   # by slot: set by the engine thread on admission, popped by the reset's push
     drop: dict = dataclasses.field(default_factory=dict)      # by slot: samples of a prompt still to drop; the worker's alone
     utt_prompts: list = None        # codec prompts per request index (None: none), for the unstreamed reply
+    logprobs: bool = False          # the request asked for the log-probabilities of its ids
+    utt_scores: list = None         # with logprobs: float32 [frames][16] per request index, written by the engine thread as each
+                                    # utterance ends, before the push that ends it (or its reply) is submitted to the worker
 
 
 class PushEntry(typing.NamedTuple):
@@ -147,12 +150,14 @@ class TextFeed:
 class _Request:
     """A request of --concurrent in flight: its connection and what has come back so far."""
 
-    def __init__(self, conn, items, stream, t0, vocoder, arithmetic):
+    def __init__(self, conn, items, stream, t0, vocoder, arithmetic, logprobs=False):
         self.conn, self.stream, self.t0 = conn, bool(stream), t0
         self.n = self.left = len(items)         # (left: utterances that have not ended)
         self.codes = [None] * self.n            # per request index
         prompts = {it.utt: it.prompt for it in items}
-        self.state = ReplyState(self.n, vocoder, arithmetic)
+        self.state = ReplyState(self.n, vocoder, arithmetic, logprobs=bool(logprobs))
+        if logprobs:
+            self.state.utt_scores = [None] * self.n
         if any(p is not None for p in prompts.values()):
             self.state.utt_prompts = [prompts.get(i) for i in range(self.n)]
         self.gone = False                       # the client went away or the request failed: its slots are released
@@ -177,10 +182,15 @@ class ConcurrentScheduler:
     called positionally as it always was; keys=[each utterance's prefix_key; None: admitted uncached] is added only with
     prefix_cache (prefix_hits / prefix_misses count the flags it returns), prompts=[each utterance's prompt or None] only when
     an utterance of the admission has one, so an engine without either argument serves everything else.  A streamed request's
-    push worker finds the prompt of a slot it resets in state.prompts[slot], an unstreamed reply in state.utt_prompts."""
+    push worker finds the prompt of a slot it resets in state.prompts[slot], an unstreamed reply in state.utt_prompts.
+
+    logprobs: the engine was told eng.scores_reserve() before this scheduler opens the batch, and a request may carry
+    "logprobs": true (without it the key is refused).  eng.scores() is then read, beside eng.codes(), at the checks where an
+    utterance of such a request ends: its log-probabilities go into state.utt_scores[utt], where the unstreamed reply, the
+    push that ends a streamed utterance and the per-request line find them."""
 
     def __init__(self, eng, max_batch, max_queue, prepare, reply, push, close_stream, send_error, check_every=8,
-                 send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=False):
+                 send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=False, logprobs=False):
         from concurrent.futures import ThreadPoolExecutor
         self.eng, self.B, self.max_queue, self.check_every = eng, int(max_batch), int(max_queue), int(check_every)
         self._prepare, self._reply, self._push, self._close_stream, self._send_error = prepare, reply, push, close_stream, send_error
@@ -192,6 +202,7 @@ class ConcurrentScheduler:
         self.frame_steps = 0                    # frame steps the engine has run
         self.send_timeout, self.text_wait_ms = float(send_timeout), float(text_wait_ms)
         self.text_hold, self.prefix_cache = bool(text_hold), bool(prefix_cache)
+        self.logprobs = bool(logprobs)
         self.starved_checks = 0                 # checks that ran no frame because a text slot waited for its text
         self.held_steps = 0                     # text_hold: frame steps text slots were held for, summed over requests
         self.prefix_hits = self.prefix_misses = 0   # prefix_cache: admitted utterances that came from the cache / were prefilled
@@ -209,6 +220,7 @@ class ConcurrentScheduler:
         try:
             items = self._prepare(msg)
             vocoder, arithmetic = request_vocoder(msg), request_vocoder_arithmetic(msg)
+            logprobs = request_logprobs(msg, self.logprobs)
         except Exception as e:
             print(f"Error: {e}")
             return self._refuse(conn)
@@ -217,7 +229,7 @@ class ConcurrentScheduler:
                 print(f"Error: queue full ({len(self._queue)} of {self.max_queue} utterances queued)" if self.alive else
                       "Error: the engine has stopped")
                 return self._refuse(conn)
-            req = _Request(conn, items, msg.get("stream"), time.time() if t0 is None else t0, vocoder, arithmetic)
+            req = _Request(conn, items, msg.get("stream"), time.time() if t0 is None else t0, vocoder, arithmetic, logprobs)
             self._queue.extend((req, it) for it in items)
             self._cv.notify()
         return True
@@ -474,6 +486,12 @@ class ConcurrentScheduler:
                 raise RuntimeError("the engine ran no frame and no utterance ended")
             return
         codes, _ = self.eng.codes()
+        # the log-probabilities, when an utterance that asked for them ends at this check
+        scores = self.eng.scores()[0] if any(owner[b][0].state.logprobs for b in fin) else None
+        for b in fin:
+            req, utt = owner[b]
+            if req.state.logprobs:
+                req.state.utt_scores[utt] = np.ascontiguousarray(scores[:int(per[b]), b, :], dtype=np.float32)
         pushes = []
         for key, (req, slots) in streamed.items():
             entries = new_entries(codes, per, slots, self._pushed, fin)

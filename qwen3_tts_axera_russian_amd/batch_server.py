@@ -42,6 +42,13 @@ keys, or with the default values spelled out, gets the reply it gets without the
 names a rule set that is not the default.  Without the flag a request that carries any of the keys is answered -2; the wire
 protocol has no new record.
 
+`--logprobs` (with `--concurrent`): the engine reserves one float32 beside every id of the codes (q3e_scores_reserve, before
+the scheduler opens the batch), and a request may then carry "logprobs": true: its reply holds, for every id it holds, the
+model's log-probability at temperature 1 of that id (batch_request, batch_wire) -- what a client that asked for k takes ranks
+them by.  The ids and the PCM are those of the request without the key, bit for bit, and a reply to a request without the key
+is byte for byte the reply of a server without the flag.  The per-request line names the mean log-probability of each
+utterance's code_0.  Without the flag the key is answered -2.
+
 `--voice_warm N` (with `--concurrent`; default 0 = off): the incremental vocoder's warm-up per codec prompt is cached in N
 snapshot slots of the vocoder handle (voice_warm.VoiceWarmCache, which says how).  A hit pushes no prompt frame: all hits of one
 check go into one voc_incr_restore, and an unstreamed reply starts from the slot (synthesize_incremental(start_slot=)).  Several slots admitted together with the same new
@@ -86,11 +93,11 @@ from . import hiplib
 from . import protocol as P
 from .batch_request import (PROMPT_KEYS, VOCODER_ARITHMETICS, VOCODER_MODES, PromptAudioCache, Utterance, VoiceTable,  # noqa: F401
                             load_voice, prefix_key, prompt_audio_digest, request_has_prompt, request_prompt_audio,
-                            request_prompt_codes, request_slot_params, request_slot_rules, request_vocoder,
+                            request_logprobs, request_prompt_codes, request_slot_params, request_slot_rules, request_vocoder,
                             request_vocoder_arithmetic)
 from .batch_scheduler import ConcurrentScheduler, PushEntry, ReplyState, TextFeed, new_entries  # noqa: F401
-from .batch_wire import (REC_AUDIO, REC_END, pack_batch_reply, pack_batch_request, pack_stream_audio,  # noqa: F401
-                         pack_stream_end, read_batch_reply, read_stream_record, synthesize_batch, synthesize_batch_stream,
+from .batch_wire import (REC_AUDIO, REC_END, REC_SCORES, pack_batch_reply, pack_batch_request, pack_stream_audio,  # noqa: F401
+                         pack_stream_end, pack_stream_scores, read_batch_reply, read_stream_record, synthesize_batch, synthesize_batch_stream,
                          synthesize_text_stream)
 from .engine import FrameEngine, SlotParams
 from .frontend import TextFrontEnd
@@ -101,6 +108,7 @@ from .weights import ModelConfig, read_pack
 
 class BatchSynthesisServer:
     sampler_rules = False      # --sampler_rules: requests may carry sampler rules (set by __init__)
+    logprobs = False           # --logprobs: requests may ask for the log-probabilities of their ids (set by __init__)
     encoder = None             # --encoder: the Encoder audio prompts go through (set by __init__)
     runtime_voices = None      # the VoiceTable "register_voice" writes (set by __init__)
 
@@ -109,7 +117,7 @@ class BatchSynthesisServer:
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
                  cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=0,
                  prefix_cache_rows=64, voices=None, text_voice=False, voice_warm=0, sampler_rules=False, encoder=None,
-                 prompt_audio_seconds=20.0, prompt_audio_cache=16, max_voices=64):
+                 prompt_audio_seconds=20.0, prompt_audio_cache=16, max_voices=64, logprobs=False):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens, self.n_ctx = socket_path, max_batch, max_tokens, n_ctx
@@ -130,6 +138,7 @@ class BatchSynthesisServer:
                 (voices and alone, "--voice names codec prompts of the shared frame loop's admissions: it needs --concurrent"),
                 (text_voice and alone, "--text_voice lets text slots of the shared frame loop continue a codec prompt: it needs --concurrent"),
                 (sampler_rules and alone, "--sampler_rules sets the sampler rules of the shared frame loop's slots: it needs --concurrent"),
+                (logprobs and alone, "--logprobs records the log-probabilities of the shared frame loop's decisions: it needs --concurrent"),
                 (encoder and alone, "--encoder encodes the audio prompts of the shared frame loop's admissions: it needs --concurrent"),
                 (not float(prompt_audio_seconds) > 0, "--prompt_audio_seconds takes a number > 0"),
                 (int(voice_warm) < 0, "--voice_warm takes a number of snapshot slots >= 0"),
@@ -138,6 +147,7 @@ class BatchSynthesisServer:
                 raise ValueError(message)
         self.text_hold, self.text_voice = bool(text_hold), bool(text_voice)
         self.sampler_rules = bool(sampler_rules)
+        self.logprobs = bool(logprobs)
         self.prefix_cache, self.prefix_cache_rows = int(prefix_cache), int(prefix_cache_rows)
         self.voices = {name: load_voice(d) for name, d in dict(voices or {}).items()}   # name -> (codes [T][16], text or None)
         self.runtime_voices = VoiceTable(self.voices, max_voices)
@@ -298,6 +308,8 @@ class BatchSynthesisServer:
                 if len(a):
                     out.append(pack_stream_audio(entry.utt, a))
                 if entry.finished:
+                    if state.logprobs:                    # (the engine thread wrote them before it submitted this push)
+                        out.append(pack_stream_scores(entry.utt, state.utt_scores[entry.utt]))
                     out.append(pack_stream_end(entry.utt, entry.codes))
             if out:
                 conn.sendall(b"".join(out))
@@ -311,7 +323,8 @@ class BatchSynthesisServer:
         try:
             if not state.failed:
                 conn.sendall(P.pack_sentinel(P.SENTINEL_DONE))
-                print(f"  {state.n} utterances, {state.frames} frames streamed in {time.time() - t0:.3f}s{self._prefix_note()}")
+                print(f"  {state.n} utterances, {state.frames} frames streamed in {time.time() - t0:.3f}s{self._prefix_note()}"
+                      f"{self._logprob_note(state)}")
         except OSError:
             pass
         finally:
@@ -380,6 +393,7 @@ class BatchSynthesisServer:
         request_vocoder_arithmetic(msg)      # (checks "vocoder" too)
         base = request_slot_params(msg, self.defaults, self.max_tokens)
         rules = request_slot_rules(msg, self.sampler_rules)
+        request_logprobs(msg, self.logprobs)
         if rules is not None and not rules.is_default():
             print(f"  sampler rules: {rules}")
         prompted = request_has_prompt(msg)
@@ -541,12 +555,21 @@ class BatchSynthesisServer:
     voice_warm_misses = property(lambda self: self._voice_warm.misses)
     voice_warm_evictions = property(lambda self: self._voice_warm.evictions)
 
+    @staticmethod
+    def _logprob_note(state):
+        """The per-request line of a "logprobs" request: the mean log-probability of code_0 over each utterance's frames."""
+        if not state.logprobs or state.utt_scores is None:
+            return ""
+        means = [float(np.mean(s[:, 0])) if s is not None and len(s) else float("nan") for s in state.utt_scores]
+        return ", mean logprob " + " ".join(f"{m:.3f}" for m in means)
+
     def _finish(self, conn, cs, t0, state):
         """Worker side of an unstreamed reply (--pipeline, --concurrent): vocode as `state` says, reply on conn, close it."""
         try:
             res = self.vocode(cs, state.vocoder, state.arithmetic, state.utt_prompts)
-            conn.sendall(pack_batch_reply(res))
-            print(f"  {len(res)} utterances, {sum(len(c) for c, _ in res)} frames in {time.time() - t0:.3f}s{self._prefix_note()}")
+            conn.sendall(pack_batch_reply(res, state.utt_scores if state.logprobs else None))
+            print(f"  {len(res)} utterances, {sum(len(c) for c, _ in res)} frames in {time.time() - t0:.3f}s{self._prefix_note()}"
+                  f"{self._logprob_note(state)}")
         except Exception as e:
             print(f"Error: {e}")
             self._send_error(conn)
@@ -584,6 +607,7 @@ class BatchSynthesisServer:
                 if request_has_prompt(msg):
                     raise ValueError("a codec prompt needs a --concurrent server")
                 request_slot_rules(msg, False)
+                request_logprobs(msg, False)
                 if msg.get("stream"):
                     # streamed reply: the worker writes every record and closes the connection
                     ids = self._token_ids(msg)
@@ -625,10 +649,12 @@ class BatchSynthesisServer:
             self.eng.prefix_cache(self.prefix_cache, self.prefix_cache_rows)
         if self.sampler_rules:
             self.eng.rules()                     # the rules entry and the emitted-id set of every slot: arguments of the frame
+        if self.logprobs:
+            self.eng.scores_reserve()            # one f32 beside every id of the codes: an argument of the frame's sampling launches
         self.sched = ConcurrentScheduler(self.eng, self.max_batch, self.max_queue, self._prepare, self._finish, self._push,
                                          self._close_stream, self._send_error, check_every=self.check_every,
                                          send_timeout=self.send_timeout, text_wait_ms=self.text_wait_ms,
-                                         text_hold=self.text_hold, prefix_cache=bool(self.prefix_cache))
+                                         text_hold=self.text_hold, prefix_cache=bool(self.prefix_cache), logprobs=self.logprobs)
         self.sched.start()
         print(f"Batch synthesis server listening on {self.socket_path} (--concurrent: {self.max_batch} slots shared by every "
               f"request, up to {self.max_queue} queued utterances)")
@@ -714,6 +740,8 @@ def main():
     ap.add_argument("--sampler_rules", action="store_true",
                     help="--concurrent: requests may set their sampler rules (repetition_penalty, repetition_window, eos_boost, "
                          "eos_force, min_tokens, cp_top_p, sampler: reference / upstream)")
+    ap.add_argument("--logprobs", action="store_true",
+                    help="--concurrent: requests may ask for the log-probability of every id of their reply (\"logprobs\": true)")
     ap.add_argument("--voice", action="append", default=[], metavar="NAME=DIR",
                     help="--concurrent: a codec prompt requests may name with \"voice\": \"NAME\"; DIR as "
                          "encode_reference_audio --output_dir writes it (repeatable)")
@@ -741,7 +769,7 @@ def main():
                                voices=dict(v.split("=", 1) for v in a.voice), text_voice=a.text_voice,
                                voice_warm=a.voice_warm, sampler_rules=a.sampler_rules, encoder=a.encoder,
                                prompt_audio_seconds=a.prompt_audio_seconds, prompt_audio_cache=a.prompt_audio_cache,
-                               max_voices=a.max_voices)
+                               max_voices=a.max_voices, logprobs=a.logprobs)
     try:
         srv.serve()
     finally:

@@ -13,6 +13,17 @@ the same connection (in the order they are ready; `utt` indexes the request's ut
               i32 2, i32 utt, i32 n_frames, i32[n_frames*16]  utterance utt has ended: all its codes
               i32 -1                                          the request is done   (i32 -2: error, as above)
 
+Log-probabilities (`--concurrent --logprobs`; the request carries "logprobs": true -- batch_request): in the unstreamed reply
+every utterance's block is followed by
+
+              i32 n_frames, f32[n_frames*16]                  the log-probability of every id of its codes
+
+and in the streamed reply one record, immediately before that utterance's end record:
+
+              i32 3, i32 utt, i32 n_frames, f32[n_frames*16]
+
+A reply to a request without the key is byte for byte what it always was.
+
 Streamed TEXT (`--concurrent` only; the request carries "text_stream": true, which needs "stream": true and exactly one
 utterance, else -2): the request's texts / token_ids hold only the first piece of the text (at least one token), and the
 client goes on sending the rest on the same connection, as records
@@ -39,14 +50,15 @@ import numpy as np
 
 from . import protocol as P
 
-REC_AUDIO, REC_END = 1, 2     # the records of a streamed reply
+REC_AUDIO, REC_END, REC_SCORES = 1, 2, 3     # the records of a streamed reply
 
 
 def pack_batch_request(texts=None, token_ids=None, language="russian", max_tokens=None, stream=False, temperature=None,
                        top_k=None, top_p=None, cp_temperature=None, cp_top_k=None, seed=None, vocoder=None,
                        vocoder_arithmetic=None, text_stream=False, prompt_codes=None, prompt_token_ids=None, prompt_text=None,
                        voice=None, sampler=None, repetition_penalty=None, repetition_window=None, eos_boost=None, eos_force=None,
-                       min_tokens=None, cp_top_p=None, prompt_audio=None, prompt_audio_max_frames=None, register_voice=None) -> bytes:
+                       min_tokens=None, cp_top_p=None, prompt_audio=None, prompt_audio_max_frames=None, register_voice=None,
+                       logprobs=None) -> bytes:
     """The request of the batched protocol; the sampling keys (honoured by --concurrent), the vocoder mode ("walk" /
     "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given.  text_stream: the
     request carries only the first piece of its one utterance's text; the rest follows as text records.  prompt_codes ([T][16], or
@@ -55,7 +67,8 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
     request's sampler rules (--concurrent --sampler_rules; batch_request).  prompt_audio: (array, rate) -- a numpy int16 or float32
     array [n] or [n][channels] -- or a list of such pairs, one per utterance: the audio whose voice the utterances continue
     (--concurrent --encoder); its descriptor goes into the JSON ("max_frames": prompt_audio_max_frames) and its bytes behind
-    it, so the result is JSON plus payload.  register_voice: the name the server keeps that prompt under."""
+    it, so the result is JSON plus payload.  register_voice: the name the server keeps that prompt under.  logprobs: True
+    asks for the log-probability of every emitted id (--concurrent --logprobs)."""
     msg = {"language": language}
     if stream:
         msg["stream"] = True
@@ -77,7 +90,7 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
                    ("prompt_codes", prompt_codes), ("prompt_token_ids", prompt_token_ids), ("prompt_text", prompt_text),
                    ("voice", voice), ("sampler", sampler), ("repetition_penalty", repetition_penalty),
                    ("repetition_window", repetition_window), ("eos_boost", eos_boost), ("eos_force", eos_force),
-                   ("min_tokens", min_tokens), ("cp_top_p", cp_top_p)):
+                   ("min_tokens", min_tokens), ("cp_top_p", cp_top_p), ("logprobs", logprobs)):
         if v is not None:
             msg[key] = v
     payload = b""
@@ -104,17 +117,24 @@ def prompt_audio_descriptor(array, rate, max_frames=None):
     return d, np.ascontiguousarray(a, dtype=a.dtype.newbyteorder("<")).tobytes()
 
 
-def pack_batch_reply(results) -> bytes:
+def pack_batch_reply(results, scores=None) -> bytes:
+    """scores (a "logprobs" request): one float32 [n_frames][16] per utterance, written behind its block."""
     parts = [struct.pack("<i", len(results))]
-    for codes, pcm in results:
+    for u, (codes, pcm) in enumerate(results):
         c = np.ascontiguousarray(codes, dtype="<i4").reshape(-1, 16)
         a = np.ascontiguousarray(pcm, dtype="<i2")
         parts += [struct.pack("<i", c.shape[0]), c.tobytes(), struct.pack("<i", a.shape[0]), a.tobytes()]
+        if scores is not None:
+            s = np.ascontiguousarray(scores[u], dtype="<f4").reshape(-1, 16)
+            if s.shape[0] != c.shape[0]:
+                raise ValueError(f"utterance {u}: {s.shape[0]} frames of log-probabilities for {c.shape[0]} frames of codes")
+            parts += [struct.pack("<i", s.shape[0]), s.tobytes()]
     return b"".join(parts)
 
 
-def read_batch_reply(conn):
-    """-> list of (codes [n][16] int32, pcm int16); raises on the error sentinel / a short read."""
+def read_batch_reply(conn, logprobs=False):
+    """-> list of (codes [n][16] int32, pcm int16), with logprobs (the request asked for them) of (codes, pcm, scores [n][16]
+    float32); raises on the error sentinel / a short read."""
     head = P.recv_exact(conn, 4)
     if len(head) < 4:
         raise RuntimeError("connection closed")
@@ -127,7 +147,11 @@ def read_batch_reply(conn):
         codes = np.frombuffer(P.recv_exact(conn, nf * 16 * 4), dtype="<i4").reshape(nf, 16)
         (ns,) = struct.unpack("<i", P.recv_exact(conn, 4))
         pcm = np.frombuffer(P.recv_exact(conn, ns * 2), dtype="<i2")
-        out.append((codes, pcm))
+        if logprobs:
+            (nl,) = struct.unpack("<i", P.recv_exact(conn, 4))
+            out.append((codes, pcm, np.frombuffer(P.recv_exact(conn, nl * 16 * 4), dtype="<f4").reshape(nl, 16)))
+        else:
+            out.append((codes, pcm))
     return out
 
 
@@ -141,9 +165,15 @@ def pack_stream_end(utt, codes) -> bytes:
     return struct.pack("<iii", REC_END, int(utt), c.shape[0]) + c.tobytes()
 
 
+def pack_stream_scores(utt, scores) -> bytes:
+    s = np.ascontiguousarray(scores, dtype="<f4").reshape(-1, 16)
+    return struct.pack("<iii", REC_SCORES, int(utt), s.shape[0]) + s.tobytes()
+
+
 def read_stream_record(conn):
-    """One record of a streamed reply -> ("audio", utt, pcm int16) / ("end", utt, codes [n][16] int32) / ("done",); raises on
-    the error sentinel, an unknown record or a short read."""
+    """One record of a streamed reply -> ("audio", utt, pcm int16) / ("end", utt, codes [n][16] int32) / ("scores", utt,
+    log-probabilities [n][16] float32: a "logprobs" request, right before the utterance's "end") / ("done",); raises on the
+    error sentinel, an unknown record or a short read."""
     def exact(n):
         b = P.recv_exact(conn, n)
         if len(b) < n:
@@ -154,13 +184,15 @@ def read_stream_record(conn):
         return ("done",)
     if kind == P.SENTINEL_ERROR:
         raise RuntimeError(f"server error ({kind})")
-    if kind not in (REC_AUDIO, REC_END):
+    if kind not in (REC_AUDIO, REC_END, REC_SCORES):
         raise RuntimeError(f"unknown record {kind} in a streamed reply")
     utt, n = struct.unpack("<ii", exact(8))
     if n < 0:
         raise RuntimeError(f"record of {n} entries")
     if kind == REC_AUDIO:
         return ("audio", utt, np.frombuffer(exact(n * 2), dtype="<i2"))
+    if kind == REC_SCORES:
+        return ("scores", utt, np.frombuffer(exact(n * 16 * 4), dtype="<f4").reshape(n, 16))
     return ("end", utt, np.frombuffer(exact(n * 16 * 4), dtype="<i4").reshape(n, 16))
 
 
@@ -184,8 +216,9 @@ def _stream_records(s):
 
 def synthesize_batch_stream(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, vocoder=None,
                             vocoder_arithmetic=None, **sampling):
-    """Client side of the streamed request: yields its records as they arrive -- ("audio", utt, pcm) and ("end", utt, codes)
-    -- until the request is done; raises on the error sentinel.  vocoder="incremental": the carry-state decode (audio from the
+    """Client side of the streamed request: yields its records as they arrive -- ("audio", utt, pcm) and ("end", utt, codes),
+    with logprobs=True also ("scores", utt, log-probabilities) right before each "end" -- until the request is done; raises
+    on the error sentinel.  vocoder="incremental": the carry-state decode (audio from the
     first check on) instead of the chunk walk, vocoder_arithmetic="split": on its split-fp16 convolutions.  sampling: the optional
     keys of pack_batch_request."""
     with socket.socket(socket.AF_UNIX, socket.SOCK_STREAM) as s:
@@ -239,8 +272,9 @@ def synthesize_text_stream(socket_path, pieces, language="russian", max_tokens=N
 
 def synthesize_batch(socket_path, texts=None, token_ids=None, language="russian", max_tokens=None, **sampling):
     """Client side of the batched request.  sampling: the optional keys of pack_batch_request (vocoder and vocoder_arithmetic
-    among them; prompt_audio=(array, rate) and register_voice too -- with texts=[] the request only registers: -> [])."""
+    among them; prompt_audio=(array, rate) and register_voice too -- with texts=[] the request only registers: -> []).
+    logprobs=True: -> (codes, pcm, log-probabilities [n][16] float32) per utterance."""
     with socket.socket(socket.AF_UNIX, socket.SOCK_STREAM) as s:
         s.connect(socket_path)
         _send_request(s, pack_batch_request(texts, token_ids, language, max_tokens, **sampling))
-        return read_batch_reply(s)
+        return read_batch_reply(s, logprobs=bool(sampling.get("logprobs")))

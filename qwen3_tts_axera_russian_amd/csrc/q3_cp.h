@@ -26,6 +26,7 @@ struct CpFrameIO {
     const int* forced = nullptr;                   // teacher forcing (tests): see TalkerSampleArgs
     const SlotParams* slots = nullptr;             // per-slot mode (engine): overrides temperature / top_k / seed per row
     const SlotRules* rules = nullptr;              // per-slot sampler rules (see CpArgmaxArgs); null = none
+    float* scores = nullptr;                       // log-probabilities of the emitted ids (see CpArgmaxArgs); null = none
 };
 
 // Runs positions 0..n_groups, writes columns 1..n_groups of each row's frame.  Rows row0..row0+R-1 of a batch of

@@ -130,6 +130,7 @@ int cp_frame(hipStream_t s, const Model& m, Work& w, KVCache& kv, int R, const C
         x.slots = io.slots;
         x.held = io.held;
         x.rules = io.rules;
+        x.scores = io.scores;
         if (g + 1 < G) {
             x.next_table = m.cp_emb[g];  // group g+1 embeds token g with CP table g (:134)
             x.h_out = w.h;

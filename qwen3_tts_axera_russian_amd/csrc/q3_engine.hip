@@ -81,6 +81,11 @@ struct Engine {
     int seen_words = 0;                     // (cp_vocab + 31) / 32: one bit per audio id
     std::vector<SlotRules> h_rules_default; // [max_batch] defaults, the source of reset_rows' uploads (outlives the stream's copies)
     int graph_rules = -1;
+    // log-probabilities of the emitted ids (q3e_scores_reserve / q3e_get_scores): one f32 beside every entry of d_codes,
+    // written by the frame's 16 sampling launches; null without a reservation, and then no argument of the frame
+    float* d_scores = nullptr;              // [max_frames][max_batch][16]
+    float* h_scores = nullptr;              // pinned, as large: the scores on their way to the caller
+    int graph_scores = -1;
     // prefix cache of the per-slot admissions (q3e_prefix_cache / q3e_admit_keyed): a device pool of entries, each the KV
     // rows of one prefix and the residual row its final norm reads; the index keeps the keys and the use order
     // (q3_engine_host.h).  Nothing of it is an argument of the captured frame.
@@ -180,6 +185,7 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
         sa.rules = e->d_rules;
         sa.seen = e->d_seen;
     }
+    sa.scores = e->d_scores;
     if (launch_talker_sample(st, sa)) return -1;
     CpFrameIO io;
     io.codes = e->d_codes;
@@ -203,6 +209,7 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     io.forced = e->forced_on ? e->d_forced : nullptr;
     io.slots = e->slot_mode ? e->d_slots : nullptr;
     io.rules = e->slot_mode ? e->d_rules : nullptr;
+    io.scores = e->d_scores;
     if (cp_frame(st, m, e->wc, e->kv_c, R, io, row0, e->B)) return -1;
     RowMap rm;
     rm.slot_base = 0;        // row r of the batch owns KV slot r (no table: one dependent load less in front of every attention)
@@ -300,11 +307,12 @@ void q3e_free(void* ee) {
     work_free(e->wc);
     void* ps[] = {e->d_tiles, e->d_slot, e->d_pos,  e->d_iota,   e->d_past,    e->d_npast, e->d_ntext, e->d_done,
                   e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots,
-                  e->d_text, e->d_tavail, e->d_held, e->d_pfx, e->d_pfx_state, e->d_prompt, e->d_rules, e->d_seen};
+                  e->d_text, e->d_tavail, e->d_held, e->d_pfx, e->d_pfx_state, e->d_prompt, e->d_rules, e->d_seen, e->d_scores};
     for (void* p : ps)
         if (p) hipFree(p);
     if (e->h_done) hipHostFree(e->h_done);
     if (e->h_read) hipHostFree(e->h_read);
+    if (e->h_scores) hipHostFree(e->h_scores);
     for (int c = 0; c < 8; c++) {
         if (e->cs[c]) hipStreamDestroy(e->cs[c]);
         if (e->ev_join[c]) hipEventDestroy(e->ev_join[c]);
@@ -564,6 +572,12 @@ static int reset_rows(Engine* e, int b0, int n, RowStart how, const int32_t* n_r
         Q3_HIP(hipMemsetAsync(e->d_codes, 0xff, sizeof(int) * 16 * (size_t)e->B * e->max_frames, e->s), -1);
     else
         Q3_HIP(hipMemset2DAsync(e->d_codes + 16 * (size_t)b0, sizeof(int) * 16 * (size_t)e->B, 0xff, 16 * bytes, e->max_frames, e->s), -1);
+    if (e->d_scores) {   // the rows' columns of the scores, zeroed wherever their codes are reset
+        if (n == e->B)
+            Q3_HIP(hipMemsetAsync(e->d_scores, 0, sizeof(float) * 16 * (size_t)e->B * e->max_frames, e->s), -1);
+        else
+            Q3_HIP(hipMemset2DAsync(e->d_scores + 16 * (size_t)b0, sizeof(float) * 16 * (size_t)e->B, 0, 16 * bytes, e->max_frames, e->s), -1);
+    }
     if (idle || !n_text) Q3_HIP(hipMemsetAsync(e->d_ntext + b0, 0, bytes, e->s), -1);
     else Q3_HIP(hipMemcpyAsync(e->d_ntext + b0, n_text, bytes, hipMemcpyHostToDevice, e->s), -1);
     if (idle) {
@@ -649,7 +663,8 @@ int q3e_run(void* ee, int n_frames) {
     static const bool no_graph = getenv("Q3_NO_GRAPH") && atoi(getenv("Q3_NO_GRAPH")) != 0;
     const bool need_capture = !e->graph[0].e || e->graph_B != e->B || e->graph_ignore != e->ignore_eos ||
                               e->graph_cap != e->cap_frames || e->graph_chains != nc ||
-                              e->graph_slots != (int)e->slot_mode || e->graph_rules != (int)(e->d_rules != nullptr);
+                              e->graph_slots != (int)e->slot_mode || e->graph_rules != (int)(e->d_rules != nullptr) ||
+                              e->graph_scores != (int)(e->d_scores != nullptr);
     if (no_graph) {
         for (; done_frames < n_frames; done_frames++)
             if (frame_eager(e)) return -1;
@@ -671,6 +686,7 @@ int q3e_run(void* ee, int n_frames) {
         e->graph_chains = nc;
         e->graph_slots = (int)e->slot_mode;
         e->graph_rules = (int)(e->d_rules != nullptr);
+        e->graph_scores = (int)(e->d_scores != nullptr);
     }
     const int check_every = 16;
     const auto th0 = std::chrono::steady_clock::now();
@@ -704,6 +720,15 @@ int q3e_run(void* ee, int n_frames) {
     return done_frames;
 }
 
+int q3e_graph_nodes(void* ee) {
+    Engine* e = (Engine*)ee;
+    if (!e) return -1;
+    if (!e->graph[0].g) return 0;
+    size_t n = 0;
+    Q3_HIP(hipGraphGetNodes(e->graph[0].g, nullptr, &n), -1);
+    return (int)n;
+}
+
 float q3e_last_run_ms(void* ee) { return ee ? ((Engine*)ee)->last_run_ms : -1.f; }
 float q3e_last_host_launch_ms(void* ee) { return ee ? ((Engine*)ee)->last_host_launch_ms : -1.f; }
 float q3e_last_prefill_ms(void* ee) { return ee ? ((Engine*)ee)->last_prefill_ms : -1.f; }
@@ -723,6 +748,67 @@ int q3e_get_codes(void* ee, int32_t* out, int max_out_frames, int32_t* n_frames_
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     if (n_codes) memcpy(out, h_codes, sizeof(int) * n_codes);
     if (n_frames_per_utt)   // (a prompted slot's n_past began at its prompt's length)
+        for (int b = 0; b < e->B; b++) n_frames_per_utt[b] = e->slot_mode ? e->book.generated(b, h_np[b]) : h_np[b];
+    return nf;
+}
+
+int q3e_scores_reserve(void* ee, int on) {
+    Engine* e = (Engine*)ee;
+    if (!e) return -1;
+    if (e->slot_mode) {
+        Q3_LOG("q3e_scores_reserve: a per-slot batch is open (call before q3e_open)");
+        return -1;
+    }
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    if ((on != 0) == (e->d_scores != nullptr)) return 0;
+    for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointer (and are other kernels)
+    if (e->d_scores) hipFree(e->d_scores);
+    if (e->h_scores) hipHostFree(e->h_scores);
+    e->d_scores = nullptr;
+    e->h_scores = nullptr;
+    if (!on) return 0;
+    const size_t bytes = sizeof(float) * 16 * (size_t)e->max_frames * e->max_batch;
+    if (hipMalloc((void**)&e->d_scores, bytes) != hipSuccess || hipHostMalloc((void**)&e->h_scores, bytes, 0) != hipSuccess) {
+        Q3_LOG("q3e_scores_reserve: allocation of %zu bytes failed", bytes);
+        if (e->d_scores) hipFree(e->d_scores);
+        e->d_scores = nullptr;
+        e->h_scores = nullptr;
+        return -1;
+    }
+    Q3_HIP(hipMemsetAsync(e->d_scores, 0, bytes, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    return 0;
+}
+
+int q3e_get_scores(void* ee, float* out, int max_out_frames, int32_t* n_frames_per_utt) {
+    Engine* e = (Engine*)ee;
+    if (!e || !out || e->B <= 0) return -1;
+    if (!e->d_scores) {
+        Q3_LOG("q3e_get_scores: no scores are reserved (q3e_scores_reserve)");
+        return -1;
+    }
+    int nf = e->frames_hi < e->max_frames ? e->frames_hi : e->max_frames;   // (the frames of q3e_get_codes)
+    if (e->slot_mode) nf = std::min(e->book.frames_hi(), e->max_frames);
+    if (nf > max_out_frames) nf = max_out_frames;
+    int* h_np = e->h_read;
+    int* h_codes = e->h_read + e->max_batch;
+    const size_t n = 16 * (size_t)e->B * (nf > 0 ? nf : 0);
+    if (n) {
+        Q3_HIP(hipMemcpyAsync(h_codes, e->d_codes, sizeof(int) * n, hipMemcpyDeviceToHost, e->s), -1);
+        Q3_HIP(hipMemcpyAsync(e->h_scores, e->d_scores, sizeof(float) * n, hipMemcpyDeviceToHost, e->s), -1);
+    }
+    Q3_HIP(hipMemcpyAsync(h_np, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    // what the kernels leave for a row that has ended is unspecified: a frame without a code_0 (column 0 < 0), and every
+    // frame at or past the utterance's count, reads 0
+    for (int f = 0; f < nf; f++)
+        for (int b = 0; b < e->B; b++) {
+            const size_t at = ((size_t)f * e->B + b) * 16;
+            const int count = e->slot_mode ? e->book.generated(b, h_np[b]) : h_np[b];
+            const bool live = h_codes[at] >= 0 && f < count;
+            for (int g = 0; g < 16; g++) out[at + g] = live ? e->h_scores[at + g] : 0.f;
+        }
+    if (n_frames_per_utt)
         for (int b = 0; b < e->B; b++) n_frames_per_utt[b] = e->slot_mode ? e->book.generated(b, h_np[b]) : h_np[b];
     return nf;
 }

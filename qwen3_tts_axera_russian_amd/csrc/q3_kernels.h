@@ -213,6 +213,12 @@ struct TalkerSampleArgs {
     // outside the launch write nothing.  rep_window == 0 reads it, and so needs it.
     const SlotRules* rules = nullptr;   // [R_total]
     unsigned* seen = nullptr;           // [R_total][(audio_vocab + 31) / 32]
+    // log-probabilities of the emitted ids (q3e_scores_reserve; null: none, and the kernels of a launch without them).  Laid
+    // out like `codes`; column 0 of the row's frame gets the model's log-probability, at temperature 1, of the id the
+    // stream continues with (the forced id where one replaces the decision): z_u - m - log(sum_A exp(z_v - m)) over the
+    // allowed set A = {v < audio_vocab} + {eos} of the RAW logits (z = NaN read as +inf, m their maximum), -inf for an id
+    // outside A.  No sampler setting enters it.  Written where column 0 of `codes` gets an id, nowhere else.
+    float* scores = nullptr;
 };
 int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a);
 
@@ -265,6 +271,10 @@ struct CpArgmaxArgs {
     // per-slot mode with sampler rules (null: none): rules[r].cp_top_p is the nucleus cut of row r's stochastic draw
     // (block_sample_topk's top_p; without rules there is none).  The arg-max path ignores it.
     const SlotRules* rules = nullptr;   // [R_total]
+    // log-probabilities of the emitted ids (see TalkerSampleArgs::scores; null: none): column group+1 of the row's frame
+    // gets the log-softmax, over all V raw logits, of the id the stream continues with.  Written where that column of
+    // `codes` is written: never for a held row (it keeps the score recorded with its id) or a frame beyond the array.
+    float* scores = nullptr;
 };
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a);
 

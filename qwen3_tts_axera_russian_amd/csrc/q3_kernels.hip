@@ -2089,11 +2089,17 @@ __device__ __forceinline__ SlotRules uniform_rules(const SlotRules* p, int r) {
 // SLOTS: per-slot mode -- budget, temperature, top-k, top-p and draw key of the row come from a.slots[r]
 // RULES (with SLOTS): a.rules[r] / a.seen[r] where given (TalkerSampleArgs); a kernel of its own, so that a launch without
 // them runs the code it always did
-template <bool SLOTS, bool RULES = false>
+// SCORES: a.scores gets the log-probability of the id the stream continues with (TalkerSampleArgs::scores); kernels of their
+// own again.  Every thread carries an online (max, sum of exp) pair of the RAW allowed logits through the loop that reads
+// them; the pairs meet in the wave (wave_max, wave_sum), then in LDS in wave order, so the value has one summation order
+// and is the same bits run to run.  The barriers of the winner's reduction order the LDS words: no barrier is added.
+template <bool SLOTS, bool RULES = false, bool SCORES = false>
 __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
     Q3_TL(42);
     __shared__ float sv[16];
     __shared__ int si[16];
+    __shared__ float sc_wm[SCORES ? 16 : 1], sc_ws[SCORES ? 16 : 1];   // per wave: maximum, sum of exp(z - maximum)
+    float sc_m = -INFINITY, sc_s = 0.f;
     __shared__ int win[32];
     __shared__ int nwin;
     const int r = a.row0 + blockIdx.x;
@@ -2171,6 +2177,17 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
     const bool stochastic = temperature > 1e-6f;
     for (int v = threadIdx.x; v < a.V; v += blockDim.x) {
         float l = nan_as_inf(a.logits[(size_t)r * a.V + v]);
+        if constexpr (SCORES) {
+            // (a -inf entry adds exp(-inf) = 0 whatever the maximum: skipping it keeps -inf - -inf out of the pair)
+            if ((v < a.audio_vocab || v == a.eos) && l > -INFINITY) {
+                if (l > sc_m) {
+                    sc_s = sc_s * expf(sc_m - l) + 1.f;
+                    sc_m = l;
+                } else {
+                    sc_s += expf(l - sc_m);
+                }
+            }
+        }
         if (v >= a.audio_vocab && v != a.eos) l = -1e10f;
         if (v == a.eos) {
             if (eos_masked) l = -1e10f;
@@ -2185,6 +2202,14 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
         if (l > best || (l == best && v < bidx)) {
             best = l;
             bidx = v;
+        }
+    }
+    if constexpr (SCORES) {
+        const float wm = wave_max(sc_m);
+        const float ws = wave_sum(sc_m > -INFINITY ? sc_s * expf(sc_m - wm) : 0.f);
+        if ((threadIdx.x & 63) == 0) {
+            sc_wm[threadIdx.x >> 6] = wm;
+            sc_ws[threadIdx.x >> 6] = ws;
         }
     }
     if (stochastic) {
@@ -2222,6 +2247,19 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
             if (keep) fc[0] = -1;
         } else {
             fc[0] = code;
+            if constexpr (SCORES) {
+                if (a.scores) {
+                    const int nw = blockDim.x >> 6;
+                    float m = sc_wm[0], sum = 0.f;
+                    for (int i = 1; i < nw; i++) m = fmaxf(m, sc_wm[i]);
+                    for (int i = 0; i < nw; i++) sum += sc_wm[i] > -INFINITY ? sc_ws[i] * expf(sc_wm[i] - m) : 0.f;
+                    float zu = -INFINITY;   // an id outside the allowed set
+                    if (used >= 0 && used < a.V && (used < a.audio_vocab || used == a.eos))
+                        zu = nan_as_inf(a.logits[(size_t)r * a.V + used]);
+                    // m = +inf, or nothing above -inf: the formula's own inf - inf
+                    a.scores[((size_t)f * RT + r) * 16] = (m < INFINITY && m > -INFINITY) ? zu - m - logf(sum) : __builtin_nanf("");
+                }
+            }
             a.past[r * 32 + (np & 31)] = used;
             if constexpr (RULES)   // one workgroup owns the row: a plain read-modify-write (every read of the loop above is
                                    // behind the barriers of the winner's reduction)
@@ -2235,6 +2273,9 @@ __device__ __forceinline__ void talker_sample_row(const TalkerSampleArgs& a) {
 __global__ void talker_sample_kernel(TalkerSampleArgs a) { talker_sample_row<false>(a); }
 __global__ void talker_sample_kernel_slots(TalkerSampleArgs a) { talker_sample_row<true>(a); }
 __global__ void talker_sample_kernel_rules(TalkerSampleArgs a) { talker_sample_row<true, true>(a); }
+__global__ void talker_sample_kernel_scores(TalkerSampleArgs a) { talker_sample_row<false, false, true>(a); }
+__global__ void talker_sample_kernel_slots_scores(TalkerSampleArgs a) { talker_sample_row<true, false, true>(a); }
+__global__ void talker_sample_kernel_rules_scores(TalkerSampleArgs a) { talker_sample_row<true, true, true>(a); }
 
 // per-slot mode: any row may take the sort path, so its LDS is reserved whatever the rows ask for (admitting a request
 // never changes the captured launch)
@@ -2266,7 +2307,11 @@ int launch_talker_sample(hipStream_t s, const TalkerSampleArgs& a) {
     const size_t lds = a.slots ? sample_lds_bytes_slots(a.V) : sample_lds_bytes(a.V, a.top_k, a.temperature);
     TalkerSampleArgs a2 = a;
     a2.tl_node = tl_next_node();
-    if (a.rules || a.seen) hipLaunchKernelGGL(talker_sample_kernel_rules, dim3(a.R), dim3(256), lds, s, a2);
+    if (a.scores) {   // (q3e_scores_reserve: the same choice among the kernels that also score)
+        if (a.rules || a.seen) hipLaunchKernelGGL(talker_sample_kernel_rules_scores, dim3(a.R), dim3(256), lds, s, a2);
+        else if (a.slots) hipLaunchKernelGGL(talker_sample_kernel_slots_scores, dim3(a.R), dim3(256), lds, s, a2);
+        else hipLaunchKernelGGL(talker_sample_kernel_scores, dim3(a.R), dim3(256), lds, s, a2);
+    } else if (a.rules || a.seen) hipLaunchKernelGGL(talker_sample_kernel_rules, dim3(a.R), dim3(256), lds, s, a2);
     else if (a.slots) hipLaunchKernelGGL(talker_sample_kernel_slots, dim3(a.R), dim3(256), lds, s, a2);
     else hipLaunchKernelGGL(talker_sample_kernel, dim3(a.R), dim3(256), lds, s, a2);
     Q3_HIP(hipGetLastError(), -1);
@@ -2315,7 +2360,10 @@ __device__ __forceinline__ void feedback_row(const int* codes, int r, const floa
 // One workgroup per row: the 2048 logits arrive as two float4 per thread (one round trip), one barrier
 // picks the winner, then the next embedding row is gathered (second round trip).
 // RULES (with SLOTS): a.rules[r].cp_top_p cuts the stochastic draw; a kernel of its own, as for the talker
-template <bool SLOTS, bool RULES = false>
+// SCORES: a.scores gets the log-softmax of the id the stream continues with (CpArgmaxArgs::scores); kernels of their own.
+// The block arg-max over the raw logits is the maximum; the sum of exp(z - max) comes from the registers that hold the
+// logits, through one more block reduction (wave_sum, four LDS words added in wave order, one barrier).
+template <bool SLOTS, bool RULES = false, bool SCORES = false>
 __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     if constexpr (SLOTS)
         Q3_FETCH_ARGS("s"(a.logits), "s"(a.V), "s"(a.H), "s"(a.row0), "s"(a.R_total), "s"(a.R), "s"(a.group), "s"(a.codes), "s"(a.n_frames),
@@ -2388,6 +2436,27 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
             best = sv[i];
             bidx = si[i];
         }
+    const float sc_m = best;   // (SCORES) the maximum of the raw logits, before a draw replaces the winner
+    float sc_sum = 0.f;
+    if constexpr (SCORES) {
+        __shared__ float sc_ws[4];
+        const float e[8] = {nan_as_inf(l0.x), nan_as_inf(l0.y), nan_as_inf(l0.z), nan_as_inf(l0.w),
+                            nan_as_inf(l1.x), nan_as_inf(l1.y), nan_as_inf(l1.z), nan_as_inf(l1.w)};
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 8; j++) s += expf(e[j] - sc_m);   // (a lane's padding is -inf: exp(-inf) = 0)
+        for (int v4 = tid + 512; v4 < n4; v4 += 256) {         // vocabularies beyond 2048: read again
+            const float4 l = lg[v4];
+            s += expf(nan_as_inf(l.x) - sc_m);
+            s += expf(nan_as_inf(l.y) - sc_m);
+            s += expf(nan_as_inf(l.z) - sc_m);
+            s += expf(nan_as_inf(l.w) - sc_m);
+        }
+        s = wave_sum(s);
+        if ((tid & 63) == 0) sc_ws[tid >> 6] = s;
+        __syncthreads();
+        sc_sum = ((sc_ws[0] + sc_ws[1]) + sc_ws[2]) + sc_ws[3];
+    }
     if (temperature > 1e-6f) {   // code_predictor_server.py:87-92: top-k, softmax((l-max)/T), categorical draw
         extern __shared__ float slg[];
         __shared__ float selv[64];
@@ -2420,6 +2489,14 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
     } else if (tid == 0 && keep) fc[1 + a.group] = bidx;
     const int* fz = (a.forced && keep) ? a.forced + ((size_t)f * RT + r) * 16 : nullptr;
     if (fz && fz[1 + a.group] >= 0) bidx = fz[1 + a.group];   // teacher forcing (tests): continue with the forced id
+    if constexpr (SCORES) {
+        if (a.scores && tid == 0 && keep && !(SLOTS && held)) {   // where fc[1 + group] was written, of the id used
+            const float zu = bidx >= 0 && bidx < a.V ? nan_as_inf(a.logits[(size_t)r * a.V + bidx]) : -INFINITY;
+            // a maximum of +inf, or nothing above -inf: the formula's own inf - inf
+            a.scores[((size_t)f * RT + r) * 16 + 1 + a.group] =
+                (sc_m < INFINITY && sc_m > -INFINITY) ? zu - sc_m - logf(sc_sum) : __builtin_nanf("");
+        }
+    }
     Q3_PH(2);
     if (a.talker_emb) {
         // text slot: row f of the slot's text stands where the pad stands (f from the slot's own start, before the clamps
@@ -2484,6 +2561,9 @@ __device__ __forceinline__ void cp_argmax_row(const CpArgmaxArgs& a) {
 __global__ void __launch_bounds__(256) cp_argmax_kernel(CpArgmaxArgs a) { cp_argmax_row<false>(a); }
 __global__ void __launch_bounds__(256) cp_argmax_kernel_slots(CpArgmaxArgs a) { cp_argmax_row<true>(a); }
 __global__ void __launch_bounds__(256) cp_argmax_kernel_rules(CpArgmaxArgs a) { cp_argmax_row<true, true>(a); }
+__global__ void __launch_bounds__(256) cp_argmax_kernel_scores(CpArgmaxArgs a) { cp_argmax_row<false, false, true>(a); }
+__global__ void __launch_bounds__(256) cp_argmax_kernel_slots_scores(CpArgmaxArgs a) { cp_argmax_row<true, false, true>(a); }
+__global__ void __launch_bounds__(256) cp_argmax_kernel_rules_scores(CpArgmaxArgs a) { cp_argmax_row<true, true, true>(a); }
 
 int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a) {
     if (a.R <= 0) return 0;
@@ -2514,7 +2594,11 @@ int launch_cp_argmax(hipStream_t s, const CpArgmaxArgs& a) {
     const size_t lds = a.slots ? sample_lds_bytes_slots(a.V) : sample_lds_bytes(a.V, a.top_k, a.temperature);
     CpArgmaxArgs a2 = a;
     a2.tl_node = tl_next_node();
-    if (a.rules) hipLaunchKernelGGL(cp_argmax_kernel_rules, dim3(a.R), dim3(256), lds, s, a2);
+    if (a.scores) {   // (q3e_scores_reserve: the same choice among the kernels that also score)
+        if (a.rules) hipLaunchKernelGGL(cp_argmax_kernel_rules_scores, dim3(a.R), dim3(256), lds, s, a2);
+        else if (a.slots) hipLaunchKernelGGL(cp_argmax_kernel_slots_scores, dim3(a.R), dim3(256), lds, s, a2);
+        else hipLaunchKernelGGL(cp_argmax_kernel_scores, dim3(a.R), dim3(256), lds, s, a2);
+    } else if (a.rules) hipLaunchKernelGGL(cp_argmax_kernel_rules, dim3(a.R), dim3(256), lds, s, a2);
     else if (a.slots) hipLaunchKernelGGL(cp_argmax_kernel_slots, dim3(a.R), dim3(256), lds, s, a2);
     else hipLaunchKernelGGL(cp_argmax_kernel, dim3(a.R), dim3(256), lds, s, a2);
     Q3_HIP(hipGetLastError(), -1);

@@ -531,14 +531,15 @@ static int talker_sample_case(const float* logits, int V, int R_total, int row0,
                               int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos, int max_frames,
                               float rep_penalty, float temperature, int top_k, float top_p, unsigned long long seed,
                               const unsigned long long* seed_ptr, const void* slots, const int* text_avail, int* held,
-                              const void* rules = nullptr, unsigned* seen = nullptr) {
+                              const void* rules = nullptr, unsigned* seen = nullptr, float* scores = nullptr) {
     if (!logits || V <= 0 || R < 0 || row0 < 0 || row0 + R > R_total || frame_cap < 0 || eos < 0 || eos >= V) return -2;
     if (seen && audio_vocab <= 0) return -2;
     const size_t seen_words = seen ? (size_t)R_total * ((audio_vocab + 31) / 32) : 0;
     for (int r = row0; r < row0 + R; r++)
         if (n_frames[r] < 0 || n_past[r] < 0) return -2;
     const size_t rt = (size_t)R_total, nc = (size_t)frame_cap * rt * 16;
-    DBuf dl, dpast, dn, dnt, ddone, dcodes, dnf, dpos0, dpos, dforced, dseed, dslots, dtav, dheld, drules, dseen;
+    DBuf dl, dpast, dn, dnt, ddone, dcodes, dnf, dpos0, dpos, dforced, dseed, dslots, dtav, dheld, drules, dseen, dscores;
+    if (scores && !dscores.up(scores, nc * 4)) return -1000;
     if (rules && !drules.up(rules, rt * sizeof(SlotRules))) return -1000;
     if (seen && !dseen.up(seen, seen_words * 4)) return -1000;
     if (text_avail && !dtav.up(text_avail, rt * 4)) return -1000;
@@ -581,6 +582,7 @@ static int talker_sample_case(const float* logits, int V, int R_total, int row0,
     a.held = held ? (int*)dheld.p : nullptr;
     a.rules = rules ? (const SlotRules*)drules.p : nullptr;
     a.seen = seen ? (unsigned*)dseen.p : nullptr;
+    a.scores = scores ? (float*)dscores.p : nullptr;
     if (const int rc = launch_talker_sample(nullptr, a)) return rc;
     Q3_HIP(hipDeviceSynchronize(), -1000);
     Q3_HIP(hipMemcpy(past, dpast.p, rt * 32 * 4, hipMemcpyDeviceToHost), -1000);
@@ -591,6 +593,7 @@ static int talker_sample_case(const float* logits, int V, int R_total, int row0,
     Q3_HIP(hipMemcpy(codes, dcodes.p, nc * 4, hipMemcpyDeviceToHost), -1000);
     if (held) Q3_HIP(hipMemcpy(held, dheld.p, rt * 4, hipMemcpyDeviceToHost), -1000);
     if (seen) Q3_HIP(hipMemcpy(seen, dseen.p, seen_words * 4, hipMemcpyDeviceToHost), -1000);
+    if (scores) Q3_HIP(hipMemcpy(scores, dscores.p, nc * 4, hipMemcpyDeviceToHost), -1000);
     return 0;
 }
 extern "C" int q3t_talker_sample_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
@@ -627,6 +630,20 @@ extern "C" int q3t_talker_sample_rules_case(const float* logits, int V, int R_to
                               seed_ptr, slots, text_avail, held, rules, seen);
 }
 
+// q3t_talker_sample_rules_case with the log-probability of the id the stream continues with (TalkerSampleArgs::scores):
+// scores[frame_cap][R_total][16] in and out, whole -- entries the launch leaves alone come back as they went in.  Null:
+// q3t_talker_sample_rules_case itself.
+extern "C" int q3t_talker_score_case(const float* logits, int V, int R_total, int row0, int R, int* past, int* n_past,
+                                     const int* n_text, int* done, int* n_frames, const int* pos0, int* pos, int* codes,
+                                     int frame_cap, const int* forced, int audio_vocab, int eos, int ignore_eos,
+                                     int max_frames, float rep_penalty, float temperature, int top_k, float top_p,
+                                     unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
+                                     const int* text_avail, int* held, const void* rules, unsigned* seen, float* scores) {
+    return talker_sample_case(logits, V, R_total, row0, R, past, n_past, n_text, done, n_frames, pos0, pos, codes, frame_cap,
+                              forced, audio_vocab, eos, ignore_eos, max_frames, rep_penalty, temperature, top_k, top_p, seed,
+                              seed_ptr, slots, text_avail, held, rules, seen, scores);
+}
+
 // One launch_cp_argmax, state in and out on host arrays (layouts as in q3t_talker_sample_case).  epilogue 0: none;
 // 1: gather of next_table[V][H] (+ next_qkv[V][qkv_ld] -> qkv_out[R_total][qkv_ld] when non-null); 2: the feedback sum
 // over talker_emb[talker_vocab][H], cp_tables[n_groups][V][H] (one contiguous array) and pad[H] (or null).
@@ -639,7 +656,8 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
                           const float* next_table, const float* next_qkv, int qkv_ld, const float* gamma,
                           const float* talker_emb, int talker_vocab, const float* cp_tables, int n_groups, const float* pad,
                           float* h_out, float* ssq_out, uint16_t* xh_out, float* qkv_out, const float* text_rows,
-                          const int* text_avail, int text_cap, const int* held, const void* rules = nullptr) {
+                          const int* text_avail, int text_cap, const int* held, const void* rules = nullptr,
+                          float* scores = nullptr) {
     if (!logits || V <= 0 || R < 0 || row0 < 0 || row0 + R > R_total || frame_cap < 1 || group < 0 || group > 14 ||
         epilogue < 0 || epilogue > 2)
         return -2;
@@ -657,7 +675,8 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
             if (text_avail[r] < 0 || text_avail[r] > text_cap) return -2;
     const size_t rt = (size_t)R_total, nc = (size_t)frame_cap * rt * 16;
     const int Rp = (R_total + 15) / 16 * 16;   // fragment order: blocks of 16 rows
-    DBuf dl, dcodes, dnf, dforced, dseed, dslots, dtab, dqkv, dgam, dtemb, dcpt, dcptp, dpad, dh, dssq, dxh, dqo, dtrows, dtav, dheld, drules;
+    DBuf dl, dcodes, dnf, dforced, dseed, dslots, dtab, dqkv, dgam, dtemb, dcpt, dcptp, dpad, dh, dssq, dxh, dqo, dtrows, dtav, dheld, drules, dscores;
+    if (scores && !dscores.up(scores, nc * 4)) return -1000;
     if (rules && !drules.up(rules, rt * sizeof(SlotRules))) return -1000;
     if (text_rows && !dtrows.up(text_rows, rt * (size_t)(text_cap > 0 ? text_cap : 1) * (H > 0 ? H : 1) * 4)) return -1000;
     if (text_avail && !dtav.up(text_avail, rt * 4)) return -1000;
@@ -688,6 +707,7 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
     a.text_cap = text_cap;
     a.held = held ? (const int*)dheld.p : nullptr;
     a.rules = rules ? (const SlotRules*)drules.p : nullptr;
+    a.scores = scores ? (float*)dscores.p : nullptr;
     std::vector<float> hh;
     std::vector<uint16_t> hx;
     if (epilogue) {
@@ -731,6 +751,7 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
     if (const int rc = launch_cp_argmax(nullptr, a)) return rc;
     Q3_HIP(hipDeviceSynchronize(), -1000);
     Q3_HIP(hipMemcpy(codes, dcodes.p, nc * 4, hipMemcpyDeviceToHost), -1000);
+    if (scores) Q3_HIP(hipMemcpy(scores, dscores.p, nc * 4, hipMemcpyDeviceToHost), -1000);
     if (epilogue) {
         Q3_HIP(hipMemcpy(hh.data(), dh.p, hh.size() * 4, hipMemcpyDeviceToHost), -1000);
         for (int r = 0; r < R_total; r++)
@@ -782,6 +803,20 @@ extern "C" int q3t_cp_sample_rules_case(const float* logits, int V, int R_total,
     return cp_sample_case(logits, V, R_total, row0, R, group, codes, n_frames, frame_cap, forced, temperature, top_k, seed,
                           seed_ptr, slots, epilogue, H, next_table, next_qkv, qkv_ld, gamma, talker_emb, talker_vocab, cp_tables,
                           n_groups, pad, h_out, ssq_out, xh_out, qkv_out, text_rows, text_avail, text_cap, held, rules);
+}
+// q3t_cp_sample_rules_case with the log-probability of the id the stream continues with (CpArgmaxArgs::scores):
+// scores[frame_cap][R_total][16] in and out, whole.  Null: q3t_cp_sample_rules_case itself.
+extern "C" int q3t_cp_score_case(const float* logits, int V, int R_total, int row0, int R, int group, int* codes,
+                                 const int* n_frames, int frame_cap, const int* forced, float temperature, int top_k,
+                                 unsigned long long seed, const unsigned long long* seed_ptr, const void* slots,
+                                 int epilogue, int H, const float* next_table, const float* next_qkv, int qkv_ld,
+                                 const float* gamma, const float* talker_emb, int talker_vocab, const float* cp_tables,
+                                 int n_groups, const float* pad, float* h_out, float* ssq_out, uint16_t* xh_out,
+                                 float* qkv_out, const float* text_rows, const int* text_avail, int text_cap,
+                                 const int* held, const void* rules, float* scores) {
+    return cp_sample_case(logits, V, R_total, row0, R, group, codes, n_frames, frame_cap, forced, temperature, top_k, seed,
+                          seed_ptr, slots, epilogue, H, next_table, next_qkv, qkv_ld, gamma, talker_emb, talker_vocab, cp_tables,
+                          n_groups, pad, h_out, ssq_out, xh_out, qkv_out, text_rows, text_avail, text_cap, held, rules, scores);
 }
 
 // ---- launch-boundary microbenchmark: a dependent chain of n small kernels, captured as a graph ----

@@ -153,6 +153,11 @@ class FrameEngine:
         return rc
 
     @property
+    def graph_nodes(self):
+        """Nodes of the captured frame (q3e_graph_nodes; 0 before the first capture)."""
+        return int(self._lib.q3e_graph_nodes(self.h))
+
+    @property
     def last_run_ms(self):
         return float(self._lib.q3e_last_run_ms(self.h))
 
@@ -172,6 +177,35 @@ class FrameEngine:
         if nf < 0:
             raise RuntimeError("q3e_get_codes failed")
         return out[:nf], per
+
+    def scores_reserve(self, on=True):
+        """Reserve (or release) the per-decision log-probabilities (q3e_scores_reserve; before open()): scores() then
+        returns them.  The codes are the same bits with or without.  Raises ValueError when the engine refuses (a per-slot
+        batch is open): nothing changes."""
+        rc = self._lib.q3e_scores_reserve(self.h, int(bool(on)))
+        if rc != 0:
+            raise ValueError(f"q3e_scores_reserve refused: {rc}")
+
+    def scores(self):
+        """-> (scores[frames][B][16] float32, frames emitted per utterance): beside every id of codes(), the model's
+        log-probability at temperature 1 of the id the stream continued with (the forced id under teacher forcing); 0.0
+        in the frames of an utterance at or past its count.  Needs scores_reserve()."""
+        out = np.zeros((self.max_frames, self.B, 16), np.float32)
+        per = np.zeros(self.B, np.int32)
+        nf = self._lib.q3e_get_scores(self.h, hiplib.fptr(out), self.max_frames, hiplib.iptr(per))
+        if nf < 0:
+            raise RuntimeError("q3e_get_scores failed (no scores_reserve()?)")
+        return out[:nf], per
+
+    def score(self, prefixes, n_text, codes, ignore_eos=True):
+        """Teacher-forced log-likelihood of given ids: starts a batch of the prefixes, forces codes[f][B][16], runs
+        len(codes) frames -> scores[len(codes)][B][16] float32 (scores()).  Needs scores_reserve()."""
+        forced = np.ascontiguousarray(codes, dtype=np.int32)
+        assert forced.ndim == 3 and forced.shape[1] == len(prefixes) and forced.shape[2] == 16
+        self.start(prefixes, n_text, ignore_eos=ignore_eos, max_frames=forced.shape[0])
+        self.set_forced_codes(forced)
+        self.run(forced.shape[0])
+        return self.scores()[0]
 
     def done(self):
         """-> (done[B] bool: the utterance has ended (EOS or its frame budget), frames emitted per utterance)."""

@@ -99,9 +99,12 @@ def load(path: str | None = None):
     _sig(lib, "q3e_set_forced_codes", c_int, [c_void_p, i32p, c_int])
     _sig(lib, "q3e_start", c_int, [c_void_p, c_int, f32p, i32p, i32p, c_int, c_int])
     _sig(lib, "q3e_run", c_int, [c_void_p, c_int])
+    _sig(lib, "q3e_graph_nodes", c_int, [c_void_p])
     _sig(lib, "q3e_last_run_ms", c_float, [c_void_p])
     _sig(lib, "q3e_last_prefill_ms", c_float, [c_void_p])
     _sig(lib, "q3e_get_codes", c_int, [c_void_p, i32p, c_int, i32p])
+    _sig(lib, "q3e_scores_reserve", c_int, [c_void_p, c_int])
+    _sig(lib, "q3e_get_scores", c_int, [c_void_p, f32p, c_int, i32p])
     _sig(lib, "q3e_get_done", c_int, [c_void_p, i32p, i32p])
     _sig(lib, "q3e_refill", c_int, [c_void_p, c_int, i32p, f32p, i32p, i32p])
     _sig(lib, "q3e_open", c_int, [c_void_p, c_int, c_int])
@@ -261,6 +264,8 @@ def load_test():
     u32p = ctypes.POINTER(ctypes.c_uint32)
     _sig(lib, "q3t_talker_sample_rules_case", c_int, talker_case + [i32p, i32p, c_void_p, u32p])
     _sig(lib, "q3t_cp_sample_rules_case", c_int, cp_case + [f32p, i32p, c_int, i32p, c_void_p])
+    _sig(lib, "q3t_talker_score_case", c_int, talker_case + [i32p, i32p, c_void_p, u32p, f32p])
+    _sig(lib, "q3t_cp_score_case", c_int, cp_case + [f32p, i32p, c_int, i32p, c_void_p, f32p])
     _sig(lib, "q3t_prompt_rows_seen_case", c_int, [i32p, c_int, i32p, i32p, f32p, c_int, f32p, c_int, c_int, c_int, f32p, c_int,
                                                    c_int, c_int, c_int, c_int, f32p, f32p, f32p, u16p, c_int, u32p, c_int])
     _sig(lib, "q3t_final_norm_case", c_int, [f32p, f32p, c_int, c_int, c_int, f32p, c_float, c_int, c_int, i32p, c_int, c_int,
