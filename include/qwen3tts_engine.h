@@ -76,8 +76,9 @@ int q3e_start(void* e, int B, const float* prefix, const int32_t* n_rows, const 
  * steps executed, <0 on error. */
 int q3e_run(void* e, int n_frames);
 
-/* Nodes of the captured frame (the first chain's graph): 0 before the first capture or after a call that dropped it, <0 on
- * error.  A diagnostic: the count is the same with and without q3e_scores_reserve. */
+/* Nodes of the captured frame (the first chain's graph): 0 before the first capture, <0 on error.  Between a call that
+ * changes what the frame takes and the q3e_run that captures again it still reports the last capture.  A diagnostic: the
+ * count is the same with and without q3e_scores_reserve. */
 int q3e_graph_nodes(void* e);
 
 /* GPU time of the last q3e_run / q3e_start in milliseconds (HIP events on the engine's stream). */

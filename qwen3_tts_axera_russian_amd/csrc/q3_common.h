@@ -112,7 +112,7 @@ float h2f(uint16_t h);
 uint16_t f2h_sat(float f);
 
 // ---------------------------------------------------------------------------
-// What the carry-state objects (VocIncr, EncStream) and the encoder handle share
+// What the carry-state objects (VocIncr, EncStream), the encoder handle and the engine share
 // ---------------------------------------------------------------------------
 // Owner of device allocations: it frees what it handed out, and `bytes` is the sum of the sizes asked for.
 struct DeviceAllocs {
@@ -143,6 +143,23 @@ struct DeviceAllocs {
         for (void* p : ptrs) hipFree(p);
         ptrs.clear();
         bytes = 0;
+    }
+};
+
+// The same for pinned host memory (the engine's read-back staging): it frees what it handed out.
+struct PinnedAllocs {
+    std::vector<void*> ptrs;
+    PinnedAllocs() = default;
+    PinnedAllocs(const PinnedAllocs&) = delete;
+    PinnedAllocs& operator=(const PinnedAllocs&) = delete;
+    ~PinnedAllocs() {
+        for (void* p : ptrs) hipHostFree(p);
+    }
+    template <class T>
+    bool alloc(T** p, size_t n) {
+        if (hipHostMalloc((void**)p, n, 0) != hipSuccess) return false;
+        ptrs.push_back(*p);
+        return true;
     }
 };
 

@@ -11,10 +11,75 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <memory>
+#include <tuple>
 
 using namespace q3;
 
 namespace {
+
+struct Sampling {   // q3e_set_sampling (0 temperature = greedy, the reference's --temperature 0 limit)
+    float t_temp = 0.f, t_top_p = 0.95f, c_temp = 0.f;
+    int t_top_k = 50, c_top_k = 50;
+};
+// Everything frame_chain takes from the mutable part of the engine: what a captured frame has baked into its kernel
+// arguments.  q3e_run captures again exactly when the state it would launch with differs from the one its graphs hold.
+struct FrameState {
+    int B = 0, ignore_eos = 0, cap_frames = 0, chains = 0;   // chains: the effective count (the row ranges follow from it)
+    int text_cap = 0;
+    Sampling smp;
+    unsigned long long seed = 0;
+    const int* forced = nullptr;         // null: free-running
+    const SlotParams* slots = nullptr;   // null outside the per-slot mode, as everything below but the scores
+    const float* text_rows = nullptr;
+    const int* text_avail = nullptr;
+    int* held = nullptr;                 // null unless q3e_text_hold is on
+    const SlotRules* rules = nullptr;
+    unsigned* seen = nullptr;
+    float* scores = nullptr;
+    auto key() const {
+        return std::tie(B, ignore_eos, cap_frames, chains, text_cap, smp.t_temp, smp.t_top_p, smp.c_temp, smp.t_top_k, smp.c_top_k,
+                        seed, forced, slots, text_rows, text_avail, held, rules, seen, scores);
+    }
+    bool operator==(const FrameState& o) const { return key() == o.key(); }
+};
+// (no padding: a field added without its place in key() changes the size)
+static_assert(sizeof(FrameState) == 10 * 4 + 8 + 8 * sizeof(void*), "FrameState: a new field belongs in key() too");
+
+// The optional features own their memory; the engine holds each through a unique_ptr, null without a reservation.
+// Text streamed into running utterances (q3e_text_reserve / q3e_push_text): row f of a text slot's rows is added to the
+// feedback of its frame f where the pad stands.  The host writes rows and counters on s between the launches.
+struct TextRows {
+    DeviceAllocs mem;
+    float* rows = nullptr;   // [max_batch][cap][hidden]
+    int* avail = nullptr;    // [max_batch] rows pushed (0: not a text slot)
+    int* held = nullptr;     // [max_batch] the sampler's per-step verdict, read by the frame's cp_argmax launches
+    int cap = 0;
+    bool hold = false;       // q3e_text_hold: a starved text slot is held inside the frame while the other rows step on
+};
+// Per-slot sampler rules (q3e_rules_reserve / q3e_admit_ruled): the rules entry and the set of emitted ids of every slot
+struct RuleSets {
+    DeviceAllocs mem;
+    SlotRules* rules = nullptr;        // [max_batch]
+    unsigned* seen = nullptr;          // [max_batch][seen_words]
+    int seen_words = 0;                // (cp_vocab + 31) / 32: one bit per audio id
+    std::vector<SlotRules> defaults;   // [max_batch], the source of reset_rows' uploads (outlives the stream's copies)
+};
+// Log-probabilities of the emitted ids (q3e_scores_reserve / q3e_get_scores): one f32 beside every entry of d_codes, written
+// by the frame's 16 sampling launches
+struct Scores {
+    DeviceAllocs mem;
+    PinnedAllocs pin;
+    float* d = nullptr;   // [max_frames][max_batch][16]
+    float* h = nullptr;   // pinned, as large: the scores on their way to the caller
+};
+// Device pool of the prefix cache (q3e_prefix_cache / q3e_admit_keyed): per entry the KV rows of one prefix and the residual
+// row its final norm reads.  Nothing of it is an argument of the captured frame.
+struct PrefixPool {
+    DeviceAllocs mem;
+    half_t* kv = nullptr;     // [entries][layers][2][n_kv][max_rows][128]
+    float* state = nullptr;   // [entries][hidden + hidden / 16]
+};
 
 struct Engine {
     Model* m = nullptr;
@@ -23,7 +88,9 @@ struct Engine {
     KVCache kv_t, kv_c;
     Work wt, wc;  // talker / code-predictor activations
     int prefill_rows = 0;
-    // device state
+    // device state: allocated by q3e_create (d_slots and d_forced on first use) and freed with the engine
+    DeviceAllocs mem;
+    PinnedAllocs pin;
     int *d_slot = nullptr, *d_pos = nullptr;       // prefill row maps [prefill_rows]
     int* d_tiles = nullptr;                        // prefill attention tiles, int[4] each (<= prefill_rows of them)
     int* d_prompt = nullptr;                       // codec prompt of the utterance being admitted, [prefill_rows][16] (q3e_admit_prompted)
@@ -31,23 +98,20 @@ struct Engine {
     int *d_past = nullptr, *d_npast = nullptr, *d_ntext = nullptr, *d_done = nullptr, *d_nframes = nullptr;
     int *d_pos0 = nullptr, *d_posdec = nullptr, *d_lastrow = nullptr;
     int* d_codes = nullptr;  // [max_frames][B][16]
-    int* d_forced = nullptr; // [max_frames][B][16] teacher-forced ids (q3e_set_forced_codes), allocated on first use
+    int* d_forced = nullptr; // [max_frames][B][16] teacher-forced ids (q3e_set_forced_codes)
     bool forced_on = false;
     unsigned long long* d_seed = nullptr;  // [max_batch] draw-stream seed of every slot (device array: graph-safe)
     unsigned long long n_requests = 0, req_seed = 0, n_refills = 0;
     float* d_pad = nullptr;
     // run state
-    int B = 0, ignore_eos = 0, cap_frames = 0, frames_run = 0;
-    int frames_hi = 0;    // frames any slot may have recorded since q3e_start (q3e_refill restarts frames_run, not this)
+    int B = 0, ignore_eos = 0;
     GraphExec graph[8];   // one captured frame per chain: a single chain replays on s, parallel chains on their cs[c]
-    int graph_B = 0, graph_ignore = -1, graph_cap = -1, graph_chains = 0;
+    FrameState captured;  // what graph[] was captured with
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_run_ms = 0.f, last_prefill_ms = 0.f, last_host_launch_ms = 0.f;
     int* h_done = nullptr;  // pinned [max_batch]
     int* h_read = nullptr;  // pinned [max_batch + max_frames * max_batch * 16]: n_past and the codes on their way to the caller
-    // sampling (0 temperature = greedy, the reference's --temperature 0 limit)
-    float t_temp = 0.f, t_top_p = 0.95f, c_temp = 0.f;
-    int t_top_k = 50, c_top_k = 50;
+    Sampling smp;
     unsigned long long seed = 0;
     // independent row groups of one frame run as parallel branches of the graph (latency hiding)
     // (one chain is the default and runs on s: the chain streams and their events exist only once more than one was asked for)
@@ -60,39 +124,66 @@ struct Engine {
     // stream from d_slots; the host's view of every slot -- budget, frames emitted, text rows, steps held -- and every rule
     // over it is the book (q3_engine_host.h)
     bool slot_mode = false;
-    int graph_slots = -1;
     SlotParams* d_slots = nullptr;          // [max_batch]
     SlotBook book;
-    // text streamed into running utterances (q3e_text_reserve / q3e_push_text): row f of a text slot's rows is added to
-    // the feedback of its frame f where the pad stands.  The host writes rows and counters on s between the launches.
-    float* d_text = nullptr;                // [max_batch][text_cap][hidden]
-    int* d_tavail = nullptr;                // [max_batch] rows pushed (0: not a text slot)
-    int text_cap = 0;
     std::vector<SlotParams> h_sp;           // the slots' device entries (the final push rewrites the flags)
     int up_i[2] = {0, 0};                   // staging of one-word uploads (synchronised before reuse)
-    // held text slots (q3e_text_hold): a live text slot without a row for its next frame is held inside the frame while
-    // the other rows step on
-    bool hold = false;
-    int* d_held = nullptr;                  // [max_batch] the sampler's per-step verdict, read by the frame's cp_argmax launches
-    // per-slot sampler rules (q3e_rules_reserve / q3e_admit_ruled): the rules entry and the set of emitted ids of every
-    // slot; both null without a reservation, and then no argument of the frame
-    SlotRules* d_rules = nullptr;           // [max_batch]
-    unsigned* d_seen = nullptr;             // [max_batch][seen_words]
-    int seen_words = 0;                     // (cp_vocab + 31) / 32: one bit per audio id
-    std::vector<SlotRules> h_rules_default; // [max_batch] defaults, the source of reset_rows' uploads (outlives the stream's copies)
-    int graph_rules = -1;
-    // log-probabilities of the emitted ids (q3e_scores_reserve / q3e_get_scores): one f32 beside every entry of d_codes,
-    // written by the frame's 16 sampling launches; null without a reservation, and then no argument of the frame
-    float* d_scores = nullptr;              // [max_frames][max_batch][16]
-    float* h_scores = nullptr;              // pinned, as large: the scores on their way to the caller
-    int graph_scores = -1;
-    // prefix cache of the per-slot admissions (q3e_prefix_cache / q3e_admit_keyed): a device pool of entries, each the KV
-    // rows of one prefix and the residual row its final norm reads; the index keeps the keys and the use order
-    // (q3_engine_host.h).  Nothing of it is an argument of the captured frame.
-    half_t* d_pfx = nullptr;                // [pfx.size()][layers][2][n_kv][pfx.max_rows()][128]
-    float* d_pfx_state = nullptr;           // [pfx.size()][hidden + hidden / 16]
+    std::unique_ptr<TextRows> text;
+    std::unique_ptr<RuleSets> rules;
+    std::unique_ptr<Scores> scores;
+    std::unique_ptr<PrefixPool> pool;
+    // keys and use order of the pool's entries (q3_engine_host.h); it outlives a pool: its counters run on over
+    // q3e_prefix_cache, and a keyed admission without a pool is counted as a miss
     PrefixIndex pfx;
     size_t pfx_entry_elems() const { return (size_t)kv_t.n_layers * 2 * kv_t.n_kv * pfx.max_rows() * 128; }
+
+    // The fixed batch counts its frames here, the per-slot batch in the book; the four questions both answer:
+    int cap_frames = 0, frames_run = 0;
+    int frames_hi = 0;    // frames any slot may have recorded since q3e_start (q3e_refill restarts frames_run, not this)
+    bool hold() const { return text && text->hold; }
+    // frames recorded so far (per-slot: those of the slot admitted first)
+    int frames_recorded() const { return std::min(slot_mode ? book.frames_hi() : frames_hi, max_frames); }
+    // frames row b has generated, from its n_past (a prompted slot's began at its prompt's length)
+    int generated(int b, int n_past) const { return slot_mode ? book.generated(b, n_past) : n_past; }
+    int budget(int b) const { return slot_mode ? book[b].budget : cap_frames; }
+    // steps q3e_run may still take (<= 0: none): never past the frames the batch was started for, nor past the codes array
+    int room() const { return slot_mode ? book.room(hold(), max_frames) : std::min(cap_frames, max_frames) - frames_run; }
+    void advance(int steps) {
+        if (slot_mode) return book.advance(steps, hold(), max_frames);
+        frames_run += steps;
+        frames_hi += steps;
+    }
+
+    // chains own contiguous row ranges that must start on a 16-row fragment block
+    int chains_eff() const {
+        const int nc = n_chains < 1 ? 1 : n_chains;
+        return (nc > 1 && B % (16 * nc) == 0) ? nc : 1;
+    }
+    FrameState frame_state() const {
+        FrameState f;
+        f.B = B;
+        f.ignore_eos = ignore_eos;
+        f.cap_frames = cap_frames;
+        f.chains = chains_eff();
+        f.smp = smp;
+        f.seed = seed;
+        f.forced = forced_on ? d_forced : nullptr;
+        if (slot_mode) {
+            f.slots = d_slots;
+            if (text) {
+                f.text_rows = text->rows;
+                f.text_avail = text->avail;
+                f.text_cap = text->cap;
+                if (text->hold) f.held = text->held;
+            }
+            if (rules) {
+                f.rules = rules->rules;
+                f.seen = rules->seen;
+            }
+        }
+        if (scores) f.scores = scores->d;
+        return f;
+    }
 };
 
 // splitmix64 finaliser of (seed + golden * k): the stream derivations of this file
@@ -145,18 +236,17 @@ int codec_head(Engine* e, hipStream_t st, int row0, int R) {
     return launch_linear(st, a, PRO_F16, EPI_STORE);
 }
 
-int talker_tail(Engine* e, hipStream_t st, int row0, int R) {
-    return talker_final_norm(e, st, row0, R, nullptr, cp_seed_row0(e->wc, R, row0, e->B)) || codec_head(e, st, row0, R) ? -1 : 0;
-}
-
-int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
+// One frame of rows row0..row0+R-1 on st.  Every argument that can change between two runs comes from f (what a capture
+// of these launches bakes in, and what q3e_run compares); the rest are the engine's fixed parts -- the model, the work
+// areas, the KV caches and the arrays of q3e_create.
+int frame_chain(Engine* e, const FrameState& f, hipStream_t st, int row0, int R) {
     const Model& m = *e->m;
     TalkerSampleArgs sa;
     sa.logits = e->wt.logits;
     sa.V = m.cfg.talker_vocab;
     sa.R = R;
     sa.row0 = row0;
-    sa.R_total = e->B;
+    sa.R_total = f.B;
     sa.audio_vocab = m.cfg.cp_vocab;
     sa.eos = m.cfg.codec_eos;
     sa.past = e->d_past;
@@ -168,24 +258,20 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     sa.frame_cap = e->max_frames;
     sa.pos0 = e->d_pos0;
     sa.pos = e->d_posdec;
-    sa.ignore_eos = e->ignore_eos;
-    sa.max_frames = e->cap_frames;
-    sa.temperature = e->t_temp;
-    sa.top_k = e->t_top_k;
-    sa.top_p = e->t_top_p;
-    sa.seed = e->seed;
+    sa.ignore_eos = f.ignore_eos;
+    sa.max_frames = f.cap_frames;
+    sa.temperature = f.smp.t_temp;
+    sa.top_k = f.smp.t_top_k;
+    sa.top_p = f.smp.t_top_p;
+    sa.seed = f.seed;
     sa.seed_ptr = e->d_seed;
-    sa.forced = e->forced_on ? e->d_forced : nullptr;
-    sa.slots = e->slot_mode ? e->d_slots : nullptr;
-    if (e->slot_mode && e->d_text && e->hold) {
-        sa.text_avail = e->d_tavail;
-        sa.held = e->d_held;
-    }
-    if (e->slot_mode && e->d_rules) {
-        sa.rules = e->d_rules;
-        sa.seen = e->d_seen;
-    }
-    sa.scores = e->d_scores;
+    sa.forced = f.forced;
+    sa.slots = f.slots;
+    sa.text_avail = f.held ? f.text_avail : nullptr;   // (the sampler reads the rows' counters only to hold a row)
+    sa.held = f.held;
+    sa.rules = f.rules;
+    sa.seen = f.seen;
+    sa.scores = f.scores;
     if (launch_talker_sample(st, sa)) return -1;
     CpFrameIO io;
     io.codes = e->d_codes;
@@ -196,38 +282,30 @@ int frame_chain(Engine* e, hipStream_t st, int row0, int R) {
     io.fb_xh = e->wt.xh;
     io.fb_gamma = m.talker.L[0].in_ln;
     io.pad_embed = e->d_pad;
-    if (e->slot_mode && e->d_text) {
-        io.text_rows = e->d_text;
-        io.text_avail = e->d_tavail;
-        io.text_cap = e->text_cap;
-        if (e->hold) io.held = e->d_held;
-    }
-    io.temperature = e->c_temp;
-    io.top_k = e->c_top_k;
-    io.seed = e->seed ^ 0x5851F42D4C957F2Dull;
+    io.text_rows = f.text_rows;
+    io.text_avail = f.text_avail;
+    io.text_cap = f.text_cap;
+    io.held = f.held;
+    io.temperature = f.smp.c_temp;
+    io.top_k = f.smp.c_top_k;
+    io.seed = f.seed ^ 0x5851F42D4C957F2Dull;
     io.seed_ptr = e->d_seed;   // (the group index separates the talker's and the code predictor's draws)
-    io.forced = e->forced_on ? e->d_forced : nullptr;
-    io.slots = e->slot_mode ? e->d_slots : nullptr;
-    io.rules = e->slot_mode ? e->d_rules : nullptr;
-    io.scores = e->d_scores;
-    if (cp_frame(st, m, e->wc, e->kv_c, R, io, row0, e->B)) return -1;
+    io.forced = f.forced;
+    io.slots = f.slots;
+    io.rules = f.rules;
+    io.scores = f.scores;
+    if (cp_frame(st, m, e->wc, e->kv_c, R, io, row0, f.B)) return -1;
     RowMap rm;
     rm.slot_base = 0;        // row r of the batch owns KV slot r (no table: one dependent load less in front of every attention)
     rm.slot_stride = 1;
     rm.pos = e->d_posdec;
-    rm.rows_total = e->B;    // a chain of a split batch launches its attention as the whole batch would
+    rm.rows_total = f.B;     // a chain of a split batch launches its attention as the whole batch would
     if (run_stack(st, m, m.talker, e->wt, e->kv_t, R, rm, 1024, row0)) return -1;
-    return talker_tail(e, st, row0, R);
-}
-
-int n_chains_eff(const Engine* e) {
-    // chains own contiguous row ranges that must start on a 16-row fragment block
-    const int nc = e->n_chains < 1 ? 1 : e->n_chains;
-    return (nc > 1 && e->B % (16 * nc) == 0) ? nc : 1;
+    return talker_final_norm(e, st, row0, R, nullptr, cp_seed_row0(e->wc, R, row0, f.B)) || codec_head(e, st, row0, R) ? -1 : 0;
 }
 
 void chain_rows(const Engine* e, int c, int& row0, int& R) {
-    const int nc = n_chains_eff(e);
+    const int nc = e->chains_eff();
     row0 = 0;
     for (int i = 0; i < c; i++) row0 += e->B / nc + (i < e->B % nc ? 1 : 0);
     R = e->B / nc + (c < e->B % nc ? 1 : 0);
@@ -250,28 +328,27 @@ int ensure_chains(Engine* e, int n) {
 }
 
 // the stream chain c of the current batch runs on: the engine's own for a single chain
-hipStream_t chain_stream(const Engine* e, int c) { return n_chains_eff(e) == 1 ? e->s : e->cs[c]; }
+hipStream_t chain_stream(const Engine* e, int c) { return e->chains_eff() == 1 ? e->s : e->cs[c]; }
 
 // one frame of every chain, eagerly, each on its own stream
-int frame_eager(Engine* e) {
-    const int nc = n_chains_eff(e);
-    for (int c = 0; c < nc; c++) {
+int frame_eager(Engine* e, const FrameState& f) {
+    for (int c = 0; c < f.chains; c++) {
         int row0, R;
         chain_rows(e, c, row0, R);
-        if (frame_chain(e, chain_stream(e, c), row0, R)) return -1;
+        if (frame_chain(e, f, chain_stream(e, c), row0, R)) return -1;
     }
     return 0;
 }
 
 int fork_chains(Engine* e) {   // chain streams start after everything queued on the main stream (a single chain IS the main stream)
-    const int nc = n_chains_eff(e);
+    const int nc = e->chains_eff();
     if (nc == 1) return 0;
     Q3_HIP(hipEventRecord(e->ev_fork, e->s), -1);
     for (int c = 0; c < nc; c++) Q3_HIP(hipStreamWaitEvent(e->cs[c], e->ev_fork, 0), -1);
     return 0;
 }
 int join_chains(Engine* e) {   // the main stream continues after every chain stream
-    const int nc = n_chains_eff(e);
+    const int nc = e->chains_eff();
     if (nc == 1) return 0;
     for (int c = 0; c < nc; c++) {
         Q3_HIP(hipEventRecord(e->ev_join[c], e->cs[c]), -1);
@@ -305,14 +382,6 @@ void q3e_free(void* ee) {
     kv_free(e->kv_c);
     work_free(e->wt);
     work_free(e->wc);
-    void* ps[] = {e->d_tiles, e->d_slot, e->d_pos,  e->d_iota,   e->d_past,    e->d_npast, e->d_ntext, e->d_done,
-                  e->d_nframes, e->d_pos0, e->d_posdec, e->d_lastrow, e->d_codes, e->d_pad, e->d_forced, e->d_seed, e->d_slots,
-                  e->d_text, e->d_tavail, e->d_held, e->d_pfx, e->d_pfx_state, e->d_prompt, e->d_rules, e->d_seen, e->d_scores};
-    for (void* p : ps)
-        if (p) hipFree(p);
-    if (e->h_done) hipHostFree(e->h_done);
-    if (e->h_read) hipHostFree(e->h_read);
-    if (e->h_scores) hipHostFree(e->h_scores);
     for (int c = 0; c < 8; c++) {
         if (e->cs[c]) hipStreamDestroy(e->cs[c]);
         if (e->ev_join[c]) hipEventDestroy(e->ev_join[c]);
@@ -322,7 +391,7 @@ void q3e_free(void* ee) {
     if (e->ev1) hipEventDestroy(e->ev1);
     if (e->s) hipStreamDestroy(e->s);
     if (e->m) model_free(e->m);
-    delete e;
+    delete e;   // (its owners free the buffers)
 }
 
 void* q3e_create(const char* weights, int max_batch, int n_ctx, int max_frames) {
@@ -365,24 +434,19 @@ void* q3e_create(const char* weights, int max_batch, int n_ctx, int max_frames) 
     ok = ok && kv_alloc(e->kv_c, c.cp_layers, max_batch, c.n_kv, c.cp_groups + 1, e->s) == 0;
     ok = ok && work_alloc(e->wt, c, e->prefill_rows, c.talker_ffn, c.talker_vocab, e->s) == 0;
     ok = ok && work_alloc(e->wc, c, 2 * ((max_batch + 15) / 16 * 16), c.cp_ffn, c.cp_vocab, e->s) == 0;   // two rows per utterance in the CP's first pass
-    auto ialloc = [&](int** p, size_t n) { return hipMalloc((void**)p, sizeof(int) * n) == hipSuccess; };
-    ok = ok && ialloc(&e->d_slot, e->prefill_rows) && ialloc(&e->d_pos, e->prefill_rows);
-    ok = ok && ialloc(&e->d_tiles, (size_t)4 * e->prefill_rows) && ialloc(&e->d_prompt, (size_t)16 * e->prefill_rows);
-    ok = ok && ialloc(&e->d_iota, max_batch) && ialloc(&e->d_past, (size_t)max_batch * 32);
-    ok = ok && ialloc(&e->d_npast, max_batch) && ialloc(&e->d_ntext, max_batch) && ialloc(&e->d_done, max_batch);
-    ok = ok && ialloc(&e->d_nframes, max_batch) && ialloc(&e->d_pos0, max_batch) && ialloc(&e->d_posdec, max_batch);
-    ok = ok && ialloc(&e->d_lastrow, max_batch);
-    ok = ok && ialloc(&e->d_codes, (size_t)max_frames * max_batch * 16);
-    ok = ok && hipMalloc((void**)&e->d_pad, sizeof(float) * c.hidden) == hipSuccess;
-    ok = ok && hipMalloc((void**)&e->d_seed, sizeof(unsigned long long) * max_batch) == hipSuccess;
-    ok = ok && hipMemsetAsync(e->d_seed, 0, sizeof(unsigned long long) * max_batch, e->s) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&e->h_done, sizeof(int) * max_batch, 0) == hipSuccess;
-    ok = ok && hipHostMalloc((void**)&e->h_read, sizeof(int) * ((size_t)max_batch + (size_t)max_frames * max_batch * 16), 0) == hipSuccess;
+    const size_t mb = max_batch, pr = e->prefill_rows;
+    const std::pair<int**, size_t> ints[] = {
+        {&e->d_slot, pr},   {&e->d_pos, pr},   {&e->d_tiles, 4 * pr}, {&e->d_prompt, 16 * pr}, {&e->d_iota, mb},
+        {&e->d_past, 32 * mb}, {&e->d_npast, mb}, {&e->d_ntext, mb}, {&e->d_done, mb}, {&e->d_nframes, mb},
+        {&e->d_pos0, mb},   {&e->d_posdec, mb}, {&e->d_lastrow, mb},   {&e->d_codes, 16 * mb * max_frames}};
+    for (const auto& a : ints) ok = ok && e->mem.alloc(a.first, sizeof(int) * a.second);
+    ok = ok && e->mem.alloc_zeroed(&e->d_pad, sizeof(float) * c.hidden, e->s);
+    ok = ok && e->mem.alloc_zeroed(&e->d_seed, sizeof(unsigned long long) * mb, e->s);
+    ok = ok && e->pin.alloc(&e->h_done, sizeof(int) * mb) && e->pin.alloc(&e->h_read, sizeof(int) * (mb + 16 * mb * max_frames));
     if (ok) {
         std::vector<int> iota(max_batch);
         for (int i = 0; i < max_batch; i++) iota[i] = i;
         ok = hipMemcpyAsync(e->d_iota, iota.data(), sizeof(int) * max_batch, hipMemcpyHostToDevice, e->s) == hipSuccess;
-        ok = ok && hipMemsetAsync(e->d_pad, 0, sizeof(float) * c.hidden, e->s) == hipSuccess;
         ok = hipStreamSynchronize(e->s) == hipSuccess && ok;   // (iota is a local)
     }
     if (!ok) {
@@ -397,14 +461,9 @@ int q3e_set_sampling(void* ee, float talker_temperature, int talker_top_k, float
                      int cp_top_k, uint64_t seed) {
     Engine* e = (Engine*)ee;
     if (!e) return -1;
-    e->t_temp = talker_temperature;
-    e->t_top_k = talker_top_k;
-    e->t_top_p = talker_top_p;
-    e->c_temp = cp_temperature;
-    e->c_top_k = cp_top_k;
+    e->smp = {talker_temperature, talker_top_p, cp_temperature, talker_top_k, cp_top_k};
     e->seed = seed;
     e->n_requests = 0;
-    for (auto& g : e->graph) g.reset();  // the captured kernels carry the old parameters
     return 0;
 }
 
@@ -419,15 +478,15 @@ int q3e_set_forced_codes(void* ee, const int32_t* forced, int n_frames) {
     if (on) {
         if (e->B <= 0 || n_frames > e->max_frames) return -1;
         const size_t total = (size_t)e->max_frames * e->max_batch * 16;
-        if (!e->d_forced) Q3_HIP(hipMalloc((void**)&e->d_forced, sizeof(int) * total), -1);
+        if (!e->d_forced && !e->mem.alloc(&e->d_forced, sizeof(int) * total)) {
+            Q3_LOG("q3e_set_forced_codes: allocation of %zu bytes failed", sizeof(int) * total);
+            return -1;
+        }
         Q3_HIP(hipMemsetAsync(e->d_forced, 0xff, sizeof(int) * total, e->s), -1);   // -1 = free-running
         Q3_HIP(hipMemcpyAsync(e->d_forced, forced, sizeof(int) * 16 * (size_t)e->B * n_frames, hipMemcpyHostToDevice, e->s), -1);
         Q3_HIP(hipStreamSynchronize(e->s), -1);   // the caller's array is its own again on return
     }
-    if (on != e->forced_on) {
-        e->forced_on = on;
-        for (auto& g : e->graph) g.reset();  // the captured kernels carry the old pointer
-    }
+    e->forced_on = on;
     return 0;
 }
 
@@ -437,7 +496,6 @@ int q3e_set_chains(void* ee, int n) {
     if (n != e->n_chains) {
         if (ensure_chains(e, n)) return -1;
         e->n_chains = n;
-        for (auto& g : e->graph) g.reset();  // the captured frames cover the old row ranges
     }
     return 0;
 }
@@ -473,8 +531,8 @@ static int prompt_launch(Engine* e, int slot, int T, int row0, bool rows) {
     a.cp_vocab = m.cfg.cp_vocab;
     a.n_groups = m.cfg.cp_groups;
     a.pad_embed = e->d_pad;
-    if (e->d_seen) {   // (reset_rows has cleared the slot's set)
-        a.seen = e->d_seen + (size_t)(slot < 0 ? 0 : slot) * e->seen_words;
+    if (e->rules) {   // (reset_rows has cleared the slot's set)
+        a.seen = e->rules->seen + (size_t)(slot < 0 ? 0 : slot) * e->rules->seen_words;
         a.seen_vocab = m.cfg.cp_vocab;   // (the sampler's audio_vocab, frame_chain)
     }
     if (rows) {
@@ -554,6 +612,14 @@ static int prefill_ids(Engine* e, int n, const int* ids, const float* prefix, co
     return 0;
 }
 
+// the columns of rows b0..b0+n-1 in every frame of a [max_frames][B][16] array of 4-byte entries, filled with byte v
+static int fill_columns(Engine* e, void* a, int b0, int n, int v) {
+    const size_t pitch = 4 * 16 * (size_t)e->B;
+    if (n == e->B) Q3_HIP(hipMemsetAsync(a, v, pitch * e->max_frames, e->s), -1);
+    else Q3_HIP(hipMemset2DAsync((char*)a + 4 * 16 * (size_t)b0, pitch, v, 4 * 16 * (size_t)n, e->max_frames, e->s), -1);
+    return 0;
+}
+
 // Rows b0..b0+n-1 of every per-slot device array back to a start state, asynchronously on e->s:
 //   fresh  "just started": counters 0, an empty emitted-token ring, positions n_rows[0..n), text lengths n_text[0..n) (null:
 //          0 -- a text slot's comes with its final push); host arrays that must live until the stream is synchronised
@@ -568,16 +634,9 @@ static int reset_rows(Engine* e, int b0, int n, RowStart how, const int32_t* n_r
     Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->d_done + b0), idle ? 1 : 0, n, e->s), -1);
     Q3_HIP(hipMemsetD32Async((hipDeviceptr_t)(e->d_nframes + b0), idle ? e->max_frames : 0, n, e->s), -1);
     Q3_HIP(hipMemsetAsync(e->d_past + 32 * b0, 0, 32 * bytes, e->s), -1);
-    if (n == e->B)
-        Q3_HIP(hipMemsetAsync(e->d_codes, 0xff, sizeof(int) * 16 * (size_t)e->B * e->max_frames, e->s), -1);
-    else
-        Q3_HIP(hipMemset2DAsync(e->d_codes + 16 * (size_t)b0, sizeof(int) * 16 * (size_t)e->B, 0xff, 16 * bytes, e->max_frames, e->s), -1);
-    if (e->d_scores) {   // the rows' columns of the scores, zeroed wherever their codes are reset
-        if (n == e->B)
-            Q3_HIP(hipMemsetAsync(e->d_scores, 0, sizeof(float) * 16 * (size_t)e->B * e->max_frames, e->s), -1);
-        else
-            Q3_HIP(hipMemset2DAsync(e->d_scores + 16 * (size_t)b0, sizeof(float) * 16 * (size_t)e->B, 0, 16 * bytes, e->max_frames, e->s), -1);
-    }
+    if (fill_columns(e, e->d_codes, b0, n, 0xff)) return -1;
+    // the rows' columns of the scores, zeroed wherever their codes are reset
+    if (e->scores && fill_columns(e, e->scores->d, b0, n, 0)) return -1;
     if (idle || !n_text) Q3_HIP(hipMemsetAsync(e->d_ntext + b0, 0, bytes, e->s), -1);
     else Q3_HIP(hipMemcpyAsync(e->d_ntext + b0, n_text, bytes, hipMemcpyHostToDevice, e->s), -1);
     if (idle) {
@@ -588,11 +647,13 @@ static int reset_rows(Engine* e, int b0, int n, RowStart how, const int32_t* n_r
         Q3_HIP(hipMemcpyAsync(e->d_pos0 + b0, n_rows, bytes, hipMemcpyHostToDevice, e->s), -1);
         Q3_HIP(hipMemcpyAsync(e->d_posdec + b0, n_rows, bytes, hipMemcpyHostToDevice, e->s), -1);
     }
-    if (e->d_tavail) Q3_HIP(hipMemsetAsync(e->d_tavail + b0, 0, bytes, e->s), -1);
-    if (e->d_held) Q3_HIP(hipMemsetAsync(e->d_held + b0, 0, bytes, e->s), -1);
-    if (e->d_rules) {
-        Q3_HIP(hipMemsetAsync(e->d_seen + (size_t)b0 * e->seen_words, 0, sizeof(unsigned) * (size_t)n * e->seen_words, e->s), -1);
-        Q3_HIP(hipMemcpyAsync(e->d_rules + b0, e->h_rules_default.data(), sizeof(SlotRules) * n, hipMemcpyHostToDevice, e->s), -1);
+    if (e->text) {
+        Q3_HIP(hipMemsetAsync(e->text->avail + b0, 0, bytes, e->s), -1);
+        Q3_HIP(hipMemsetAsync(e->text->held + b0, 0, bytes, e->s), -1);
+    }
+    if (const RuleSets* r = e->rules.get()) {
+        Q3_HIP(hipMemsetAsync(r->seen + (size_t)b0 * r->seen_words, 0, sizeof(unsigned) * (size_t)n * r->seen_words, e->s), -1);
+        Q3_HIP(hipMemcpyAsync(r->rules + b0, r->defaults.data(), sizeof(SlotRules) * n, hipMemcpyHostToDevice, e->s), -1);
     }
     return 0;
 }
@@ -636,10 +697,7 @@ int q3e_start(void* ee, int B, const float* prefix, const int32_t* n_rows, const
     e->n_refills = 0;
     const std::vector<unsigned long long> seeds(B, e->req_seed);   // (alive until the stream is synchronised)
     Q3_HIP(hipMemcpyAsync(e->d_seed, seeds.data(), sizeof(unsigned long long) * B, hipMemcpyHostToDevice, e->s), -1);
-    if (e->forced_on) {   // forcing belongs to the batch it was set for
-        e->forced_on = false;
-        for (auto& g : e->graph) g.reset();
-    }
+    e->forced_on = false;   // forcing belongs to the batch it was set for
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     std::vector<int> ids(B);
     for (int b = 0; b < B; b++) ids[b] = b;
@@ -649,44 +707,32 @@ int q3e_start(void* ee, int B, const float* prefix, const int32_t* n_rows, const
 int q3e_run(void* ee, int n_frames) {
     Engine* e = (Engine*)ee;
     if (!e || e->B <= 0 || n_frames <= 0) return -1;
-    // never step past the frames the batch was started for (nor past the codes array): a further step would
-    // have no frame to record into
-    int room = (e->cap_frames < e->max_frames ? e->cap_frames : e->max_frames) - e->frames_run;
-    if (e->slot_mode) room = e->book.room(e->hold, e->max_frames);
-    if (room <= 0) return 0;
-    if (n_frames > room) n_frames = room;
+    n_frames = std::min(n_frames, e->room());
+    if (n_frames <= 0) return 0;
     int done_frames = 0;
-    const int nc = n_chains_eff(e);
+    const FrameState cur = e->frame_state();
+    const int nc = cur.chains;
     Q3_HIP(hipEventRecord(e->ev0, e->s), -1);
     if (fork_chains(e)) return -1;
     // Q3_NO_GRAPH=1: eager launches (rocprofv3 --kernel-trace crashes on the graph replay)
     static const bool no_graph = getenv("Q3_NO_GRAPH") && atoi(getenv("Q3_NO_GRAPH")) != 0;
-    const bool need_capture = !e->graph[0].e || e->graph_B != e->B || e->graph_ignore != e->ignore_eos ||
-                              e->graph_cap != e->cap_frames || e->graph_chains != nc ||
-                              e->graph_slots != (int)e->slot_mode || e->graph_rules != (int)(e->d_rules != nullptr) ||
-                              e->graph_scores != (int)(e->d_scores != nullptr);
     if (no_graph) {
         for (; done_frames < n_frames; done_frames++)
-            if (frame_eager(e)) return -1;
-    } else if (need_capture) {
+            if (frame_eager(e, cur)) return -1;
+    } else if (!e->graph[0].e || !(cur == e->captured)) {
         // first frame eagerly (real work; also sets the kernels' LDS attributes), then capture per chain
-        if (frame_eager(e)) return -1;
+        if (frame_eager(e, cur)) return -1;
         done_frames++;
         for (int c = 0; c < nc; c++) Q3_HIP(hipStreamSynchronize(chain_stream(e, c)), -1);
+        e->captured = FrameState();   // (B = 0, no state of a run: a capture that fails half way leaves no graph to replay)
         for (int c = 0; c < nc; c++) {
             int row0, R;
             chain_rows(e, c, row0, R);
             hipStream_t st = chain_stream(e, c);
-            if (e->graph[c].capture(st, hipStreamCaptureModeRelaxed, "q3e_run", [&] { return frame_chain(e, st, row0, R); }))
+            if (e->graph[c].capture(st, hipStreamCaptureModeRelaxed, "q3e_run", [&] { return frame_chain(e, cur, st, row0, R); }))
                 return -1;
         }
-        e->graph_B = e->B;
-        e->graph_ignore = e->ignore_eos;
-        e->graph_cap = e->cap_frames;
-        e->graph_chains = nc;
-        e->graph_slots = (int)e->slot_mode;
-        e->graph_rules = (int)(e->d_rules != nullptr);
-        e->graph_scores = (int)(e->d_scores != nullptr);
+        e->captured = cur;
     }
     const int check_every = 16;
     const auto th0 = std::chrono::steady_clock::now();
@@ -711,12 +757,7 @@ int q3e_run(void* ee, int n_frames) {
     Q3_HIP(hipEventRecord(e->ev1, e->s), -1);
     Q3_HIP(hipStreamSynchronize(e->s), -1);
     hipEventElapsedTime(&e->last_run_ms, e->ev0, e->ev1);
-    if (e->slot_mode) {
-        e->book.advance(done_frames, e->hold, e->max_frames);
-        return done_frames;
-    }
-    e->frames_run += done_frames;
-    e->frames_hi += done_frames;
+    e->advance(done_frames);
     return done_frames;
 }
 
@@ -733,22 +774,27 @@ float q3e_last_run_ms(void* ee) { return ee ? ((Engine*)ee)->last_run_ms : -1.f;
 float q3e_last_host_launch_ms(void* ee) { return ee ? ((Engine*)ee)->last_host_launch_ms : -1.f; }
 float q3e_last_prefill_ms(void* ee) { return ee ? ((Engine*)ee)->last_prefill_ms : -1.f; }
 
+// The getters' read-back: n_past of the batch's rows into h_read[0..B) and, as asked, the first nf recorded frames (at most
+// max_out) of the codes behind them (h_read + max_batch) and of the scores into their pinned buffer, on the engine's own
+// stream (a pageable destination would go through the runtime's staging), synchronised on return.  -> nf, < 0 on error
+static int read_back(Engine* e, int max_out, bool codes, bool scores) {
+    const int nf = std::min(e->frames_recorded(), max_out);
+    const size_t n = 16 * (size_t)e->B * (nf > 0 ? nf : 0);
+    Q3_HIP(hipMemcpyAsync(e->h_read, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
+    if (codes && n) Q3_HIP(hipMemcpyAsync(e->h_read + e->max_batch, e->d_codes, sizeof(int) * n, hipMemcpyDeviceToHost, e->s), -1);
+    if (scores && n) Q3_HIP(hipMemcpyAsync(e->scores->h, e->scores->d, sizeof(float) * n, hipMemcpyDeviceToHost, e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    return nf;
+}
+
 int q3e_get_codes(void* ee, int32_t* out, int max_out_frames, int32_t* n_frames_per_utt) {
     Engine* e = (Engine*)ee;
     if (!e || !out || e->B <= 0) return -1;
-    int nf = e->frames_hi < e->max_frames ? e->frames_hi : e->max_frames;
-    if (e->slot_mode) nf = std::min(e->book.frames_hi(), e->max_frames);   // up to the frames of the slot admitted first
-    if (nf > max_out_frames) nf = max_out_frames;
-    // through the pinned staging on the engine's own stream: a pageable destination would go through the runtime's staging
-    int* h_np = e->h_read;
-    int* h_codes = e->h_read + e->max_batch;
-    const size_t n_codes = 16 * (size_t)e->B * (nf > 0 ? nf : 0);
-    if (n_codes) Q3_HIP(hipMemcpyAsync(h_codes, e->d_codes, sizeof(int) * n_codes, hipMemcpyDeviceToHost, e->s), -1);
-    if (n_frames_per_utt) Q3_HIP(hipMemcpyAsync(h_np, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
-    if (n_codes) memcpy(out, h_codes, sizeof(int) * n_codes);
-    if (n_frames_per_utt)   // (a prompted slot's n_past began at its prompt's length)
-        for (int b = 0; b < e->B; b++) n_frames_per_utt[b] = e->slot_mode ? e->book.generated(b, h_np[b]) : h_np[b];
+    const int nf = read_back(e, max_out_frames, true, false);
+    if (nf < 0) return nf;
+    memcpy(out, e->h_read + e->max_batch, sizeof(int) * 16 * (size_t)e->B * nf);
+    if (n_frames_per_utt)
+        for (int b = 0; b < e->B; b++) n_frames_per_utt[b] = e->generated(b, e->h_read[b]);
     return nf;
 }
 
@@ -760,56 +806,40 @@ int q3e_scores_reserve(void* ee, int on) {
         return -1;
     }
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    if ((on != 0) == (e->d_scores != nullptr)) return 0;
-    for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointer (and are other kernels)
-    if (e->d_scores) hipFree(e->d_scores);
-    if (e->h_scores) hipHostFree(e->h_scores);
-    e->d_scores = nullptr;
-    e->h_scores = nullptr;
+    if ((on != 0) == (e->scores != nullptr)) return 0;
+    e->scores.reset();
     if (!on) return 0;
+    auto sc = std::make_unique<Scores>();
     const size_t bytes = sizeof(float) * 16 * (size_t)e->max_frames * e->max_batch;
-    if (hipMalloc((void**)&e->d_scores, bytes) != hipSuccess || hipHostMalloc((void**)&e->h_scores, bytes, 0) != hipSuccess) {
+    if (!sc->mem.alloc_zeroed(&sc->d, bytes, e->s) || !sc->pin.alloc(&sc->h, bytes)) {
         Q3_LOG("q3e_scores_reserve: allocation of %zu bytes failed", bytes);
-        if (e->d_scores) hipFree(e->d_scores);
-        e->d_scores = nullptr;
-        e->h_scores = nullptr;
         return -1;
     }
-    Q3_HIP(hipMemsetAsync(e->d_scores, 0, bytes, e->s), -1);
     Q3_HIP(hipStreamSynchronize(e->s), -1);
+    e->scores = std::move(sc);
     return 0;
 }
 
 int q3e_get_scores(void* ee, float* out, int max_out_frames, int32_t* n_frames_per_utt) {
     Engine* e = (Engine*)ee;
     if (!e || !out || e->B <= 0) return -1;
-    if (!e->d_scores) {
+    if (!e->scores) {
         Q3_LOG("q3e_get_scores: no scores are reserved (q3e_scores_reserve)");
         return -1;
     }
-    int nf = e->frames_hi < e->max_frames ? e->frames_hi : e->max_frames;   // (the frames of q3e_get_codes)
-    if (e->slot_mode) nf = std::min(e->book.frames_hi(), e->max_frames);
-    if (nf > max_out_frames) nf = max_out_frames;
-    int* h_np = e->h_read;
-    int* h_codes = e->h_read + e->max_batch;
-    const size_t n = 16 * (size_t)e->B * (nf > 0 ? nf : 0);
-    if (n) {
-        Q3_HIP(hipMemcpyAsync(h_codes, e->d_codes, sizeof(int) * n, hipMemcpyDeviceToHost, e->s), -1);
-        Q3_HIP(hipMemcpyAsync(e->h_scores, e->d_scores, sizeof(float) * n, hipMemcpyDeviceToHost, e->s), -1);
-    }
-    Q3_HIP(hipMemcpyAsync(h_np, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    const int nf = read_back(e, max_out_frames, true, true);   // (the frames of q3e_get_codes)
+    if (nf < 0) return nf;
+    const int* h_codes = e->h_read + e->max_batch;
     // what the kernels leave for a row that has ended is unspecified: a frame without a code_0 (column 0 < 0), and every
     // frame at or past the utterance's count, reads 0
     for (int f = 0; f < nf; f++)
         for (int b = 0; b < e->B; b++) {
             const size_t at = ((size_t)f * e->B + b) * 16;
-            const int count = e->slot_mode ? e->book.generated(b, h_np[b]) : h_np[b];
-            const bool live = h_codes[at] >= 0 && f < count;
-            for (int g = 0; g < 16; g++) out[at + g] = live ? e->h_scores[at + g] : 0.f;
+            const bool live = h_codes[at] >= 0 && f < e->generated(b, e->h_read[b]);
+            for (int g = 0; g < 16; g++) out[at + g] = live ? e->scores->h[at + g] : 0.f;
         }
     if (n_frames_per_utt)
-        for (int b = 0; b < e->B; b++) n_frames_per_utt[b] = e->slot_mode ? e->book.generated(b, h_np[b]) : h_np[b];
+        for (int b = 0; b < e->B; b++) n_frames_per_utt[b] = e->generated(b, e->h_read[b]);
     return nf;
 }
 
@@ -817,19 +847,16 @@ int q3e_get_done(void* ee, int32_t* done, int32_t* frames) {
     Engine* e = (Engine*)ee;
     if (!e || !done || e->B <= 0) return -1;
     Q3_HIP(hipMemcpyAsync(e->h_done, e->d_done, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
-    Q3_HIP(hipMemcpyAsync(e->h_read, e->d_npast, sizeof(int) * e->B, hipMemcpyDeviceToHost, e->s), -1);
-    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    if (read_back(e, 0, false, false) < 0) return -1;
     memcpy(done, e->h_done, sizeof(int) * e->B);
-    std::vector<int> np(e->h_read, e->h_read + e->B);
-    if (e->slot_mode)   // frames generated: a prompted slot's n_past began at its prompt's length
-        for (int b = 0; b < e->B; b++) np[b] = e->book.generated(b, np[b]);
     // the device raises done[b] on the step AFTER the budget's last frame, a step q3e_run never takes: an utterance
     // that has emitted its whole budget has ended
     for (int b = 0; b < e->B; b++) {
-        if (np[b] >= (e->slot_mode ? e->book[b].budget : e->cap_frames)) done[b] = 1;
+        const int generated = e->generated(b, e->h_read[b]);
+        if (generated >= e->budget(b)) done[b] = 1;
         if (e->slot_mode && done[b]) e->book.mark_ended(b);
+        if (frames) frames[b] = generated;
     }
-    if (frames) memcpy(frames, np.data(), sizeof(int) * e->B);
     return 0;
 }
 
@@ -874,7 +901,10 @@ int q3e_open(void* ee, int B, int ignore_eos) {
         return -1;
     }
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    if (!e->d_slots) Q3_HIP(hipMalloc((void**)&e->d_slots, sizeof(SlotParams) * e->max_batch), -1);
+    if (!e->d_slots && !e->mem.alloc(&e->d_slots, sizeof(SlotParams) * e->max_batch)) {
+        Q3_LOG("q3e_open: allocation failed");
+        return -1;
+    }
     e->B = B;
     e->ignore_eos = ignore_eos ? 1 : 0;
     e->cap_frames = e->max_frames;
@@ -883,10 +913,7 @@ int q3e_open(void* ee, int B, int ignore_eos) {
     e->slot_mode = true;
     e->book.open(B);
     e->h_sp.assign(B, SlotParams());
-    if (e->forced_on) {
-        e->forced_on = false;
-        for (auto& g : e->graph) g.reset();
-    }
+    e->forced_on = false;
     // idle rows step through the graph with everything else: they have ended (done), their frame counter sits at the end of
     // the codes array (nothing is recorded), and they run at position 0 of zeroed caches and activations (finite values;
     // rows are independent, so what an idle row computes never reaches another row)
@@ -910,16 +937,16 @@ static int prefix_move(Engine* e, int i, int slot, int n_rows, int h_row, int re
     a.n_ctx = e->kv_t.n_ctx;
     a.slot = slot;
     a.n_rows = n_rows;
-    a.entry = e->d_pfx + (size_t)i * e->pfx_entry_elems();
+    a.entry = e->pool->kv + (size_t)i * e->pfx_entry_elems();
     a.max_rows = e->pfx.max_rows();
     const int H = e->m->cfg.hidden;
-    a.state = e->d_pfx_state + (size_t)i * (H + H / 16);
+    a.state = e->pool->state + (size_t)i * (H + H / 16);
     a.h = e->wt.h;
     a.ssq = e->wt.ssq;
     a.h_row = h_row;
     a.H = H;
     a.restore = restore;
-    if (i < 0 || i >= e->pfx.size() || slot >= e->kv_t.n_slots || h_row >= e->wt.max_rows) return -1;
+    if (!e->pool || i < 0 || i >= e->pfx.size() || slot >= e->kv_t.n_slots || h_row >= e->wt.max_rows) return -1;
     return launch_prefix_move(e->s, a);
 }
 
@@ -943,7 +970,7 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
         if (e && !e->slot_mode) Q3_LOG("q3e_admit: the batch was not opened with q3e_open");
         return -1;
     }
-    if (rules && !e->d_rules) {
+    if (rules && !e->rules) {
         Q3_LOG("q3e_admit_ruled: no sampler rules are reserved (q3e_rules_reserve)");
         return -1;
     }
@@ -1007,7 +1034,7 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
             return -1;
         }
         if (p.reserved & 1) {
-            if (!e->d_text) {
+            if (!e->text) {
                 Q3_LOG("q3e_admit: utterance %d is a text slot, but no text rows are reserved (q3e_text_reserve)", u);
                 return -1;
             }
@@ -1027,7 +1054,7 @@ static int admit_slots(Engine* e, int n, const int32_t* slots, const float* pref
             if (reset_rows(e, slots[u], 1, RowStart::fresh, n_rows + u, sp[u].flags ? nullptr : n_text + u)) return -1;
             Q3_HIP(hipMemcpyAsync(e->d_slots + slots[u], &sp[u], sizeof(SlotParams), hipMemcpyHostToDevice, e->s), -1);
             // (reset_rows has written the defaults)
-            if (rules) Q3_HIP(hipMemcpyAsync(e->d_rules + slots[u], &kr[u], sizeof(SlotRules), hipMemcpyHostToDevice, e->s), -1);
+            if (rules) Q3_HIP(hipMemcpyAsync(e->rules->rules + slots[u], &kr[u], sizeof(SlotRules), hipMemcpyHostToDevice, e->s), -1);
         }
         Q3_HIP(hipStreamSynchronize(e->s), -1);
         // one prefill per utterance: the ragged prefill's tiles follow the rows of its pass, so sharing a pass with another
@@ -1113,27 +1140,20 @@ int q3e_rules_reserve(void* ee, int on) {
         return -1;
     }
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    if ((on != 0) == (e->d_rules != nullptr)) return 0;
-    for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointers
-    if (e->d_rules) hipFree(e->d_rules);
-    if (e->d_seen) hipFree(e->d_seen);
-    e->d_rules = nullptr;
-    e->d_seen = nullptr;
+    if ((on != 0) == (e->rules != nullptr)) return 0;
+    e->rules.reset();
     if (!on) return 0;
-    e->seen_words = (e->m->cfg.cp_vocab + 31) / 32;
-    e->h_rules_default.assign(e->max_batch, SlotRules());
-    const size_t seen_bytes = sizeof(unsigned) * (size_t)e->max_batch * e->seen_words;
-    if (hipMalloc((void**)&e->d_rules, sizeof(SlotRules) * e->max_batch) != hipSuccess ||
-        hipMalloc((void**)&e->d_seen, seen_bytes) != hipSuccess) {
+    auto r = std::make_unique<RuleSets>();
+    r->seen_words = (e->m->cfg.cp_vocab + 31) / 32;
+    r->defaults.assign(e->max_batch, SlotRules());
+    if (!r->mem.alloc(&r->rules, sizeof(SlotRules) * e->max_batch) ||
+        !r->mem.alloc_zeroed(&r->seen, sizeof(unsigned) * (size_t)e->max_batch * r->seen_words, e->s)) {
         Q3_LOG("q3e_rules_reserve: allocation failed");
-        if (e->d_rules) hipFree(e->d_rules);
-        e->d_rules = nullptr;
-        e->d_seen = nullptr;
         return -1;
     }
-    Q3_HIP(hipMemcpyAsync(e->d_rules, e->h_rules_default.data(), sizeof(SlotRules) * e->max_batch, hipMemcpyHostToDevice, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_seen, 0, seen_bytes, e->s), -1);
+    Q3_HIP(hipMemcpyAsync(r->rules, r->defaults.data(), sizeof(SlotRules) * e->max_batch, hipMemcpyHostToDevice, e->s), -1);
     Q3_HIP(hipStreamSynchronize(e->s), -1);
+    e->rules = std::move(r);
     return 0;
 }
 
@@ -1146,22 +1166,18 @@ int q3e_prefix_cache(void* ee, int n_entries, int max_rows) {
     if (max_rows > e->n_ctx) max_rows = e->n_ctx;   // a longer prefix fits no slot
     if (n_entries == 0) max_rows = 0;
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    half_t* pool = nullptr;
-    float* state = nullptr;
+    std::unique_ptr<PrefixPool> pool;
     if (n_entries > 0) {
+        pool = std::make_unique<PrefixPool>();
         const int H = e->m->cfg.hidden;
         const size_t elems = (size_t)e->kv_t.n_layers * 2 * e->kv_t.n_kv * max_rows * 128;
-        if (hipMalloc((void**)&pool, sizeof(half_t) * elems * n_entries) != hipSuccess ||
-            hipMalloc((void**)&state, sizeof(float) * (size_t)(H + H / 16) * n_entries) != hipSuccess) {
+        if (!pool->mem.alloc(&pool->kv, sizeof(half_t) * elems * n_entries) ||
+            !pool->mem.alloc(&pool->state, sizeof(float) * (size_t)(H + H / 16) * n_entries)) {
             Q3_LOG("q3e_prefix_cache: allocation of %zu bytes failed", sizeof(half_t) * elems * n_entries);
-            if (pool) hipFree(pool);
             return -1;   // the pool that was there stays
         }
     }
-    if (e->d_pfx) hipFree(e->d_pfx);
-    if (e->d_pfx_state) hipFree(e->d_pfx_state);
-    e->d_pfx = pool;
-    e->d_pfx_state = state;
+    e->pool = std::move(pool);
     e->pfx.resize(n_entries, max_rows);
     return 0;
 }
@@ -1187,36 +1203,26 @@ int q3e_text_reserve(void* ee, int max_rows) {
         return -1;
     }
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    if (max_rows == e->text_cap) return 0;
-    for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointers
-    if (e->d_text) hipFree(e->d_text);
-    if (e->d_tavail) hipFree(e->d_tavail);
-    e->d_text = nullptr;
-    e->d_tavail = nullptr;
-    e->text_cap = 0;
-    if (max_rows == 0) {
-        e->hold = false;   // nothing left to hold a slot for
-        return 0;
-    }
+    if (max_rows == (e->text ? e->text->cap : 0)) return 0;
+    auto t = std::make_unique<TextRows>();
+    t->cap = max_rows;
+    t->hold = e->hold();   // a new size keeps the mode; with no rows left there is nothing to hold a slot for
+    e->text.reset();
+    if (max_rows == 0) return 0;
     const size_t n = (size_t)e->max_batch * max_rows * e->m->cfg.hidden;
-    if (hipMalloc((void**)&e->d_text, sizeof(float) * n) != hipSuccess ||
-        hipMalloc((void**)&e->d_tavail, sizeof(int) * e->max_batch) != hipSuccess) {
+    if (!t->mem.alloc_zeroed(&t->rows, sizeof(float) * n, e->s) || !t->mem.alloc_zeroed(&t->avail, sizeof(int) * e->max_batch, e->s) ||
+        !t->mem.alloc_zeroed(&t->held, sizeof(int) * e->max_batch, e->s)) {
         Q3_LOG("q3e_text_reserve: allocation of %zu bytes failed", sizeof(float) * n);
-        if (e->d_text) hipFree(e->d_text);
-        e->d_text = nullptr;
-        e->d_tavail = nullptr;
         return -1;
     }
-    Q3_HIP(hipMemsetAsync(e->d_text, 0, sizeof(float) * n, e->s), -1);
-    Q3_HIP(hipMemsetAsync(e->d_tavail, 0, sizeof(int) * e->max_batch, e->s), -1);
     Q3_HIP(hipStreamSynchronize(e->s), -1);
-    e->text_cap = max_rows;
+    e->text = std::move(t);
     return 0;
 }
 
 int q3e_push_text(void* ee, int slot, const float* rows, int n, int final, int n_text_total) {
     Engine* e = (Engine*)ee;
-    if (!e || !e->slot_mode || !e->d_text || slot < 0 || slot >= e->B || n < 0 || (n > 0 && !rows)) return -1;
+    if (!e || !e->slot_mode || !e->text || slot < 0 || slot >= e->B || n < 0 || (n > 0 && !rows)) return -1;
     const int have = e->book[slot].text_rows;
     if (!e->book.live_text(slot)) {
         Q3_LOG("q3e_push_text: slot %d holds no live text utterance", slot);
@@ -1226,8 +1232,8 @@ int q3e_push_text(void* ee, int slot, const float* rows, int n, int final, int n
         Q3_LOG("q3e_push_text: the text of slot %d has ended", slot);
         return -1;
     }
-    if (have + n > e->text_cap) {
-        Q3_LOG("q3e_push_text: slot %d: %d + %d rows exceed the reservation of %d", slot, have, n, e->text_cap);
+    if (have + n > e->text->cap) {
+        Q3_LOG("q3e_push_text: slot %d: %d + %d rows exceed the reservation of %d", slot, have, n, e->text->cap);
         return -1;
     }
     if (final && n_text_total < 0) return -1;
@@ -1239,10 +1245,10 @@ int q3e_push_text(void* ee, int slot, const float* rows, int n, int final, int n
         }
     // the rows first, then the counter that makes them visible; q3e_run has synchronised, so no frame is in flight
     if (n > 0)
-        Q3_HIP(hipMemcpyAsync(e->d_text + ((size_t)slot * e->text_cap + have) * H, rows, sizeof(float) * (size_t)n * H,
+        Q3_HIP(hipMemcpyAsync(e->text->rows + ((size_t)slot * e->text->cap + have) * H, rows, sizeof(float) * (size_t)n * H,
                               hipMemcpyHostToDevice, e->s), -1);
     e->up_i[0] = have + n;
-    Q3_HIP(hipMemcpyAsync(e->d_tavail + slot, &e->up_i[0], sizeof(int), hipMemcpyHostToDevice, e->s), -1);
+    Q3_HIP(hipMemcpyAsync(e->text->avail + slot, &e->up_i[0], sizeof(int), hipMemcpyHostToDevice, e->s), -1);
     SlotParams sp = e->h_sp[slot];
     if (final) {   // the reference's EOS rules from the next sampled frame on: mask lifted, n_text known
         sp.flags = 1;
@@ -1269,7 +1275,7 @@ int q3e_text_state(void* ee, int32_t* rows, int32_t* starved) {
 int q3e_text_hold(void* ee, int on) {
     Engine* e = (Engine*)ee;
     if (!e) return -1;
-    if (!e->d_text) {
+    if (!e->text) {
         Q3_LOG("q3e_text_hold: no text rows are reserved (q3e_text_reserve)");
         return -1;
     }
@@ -1277,15 +1283,7 @@ int q3e_text_hold(void* ee, int on) {
         Q3_LOG("q3e_text_hold: a per-slot batch is open (call between q3e_text_reserve and q3e_open)");
         return -1;
     }
-    const bool h = on != 0;
-    if (h == e->hold) return 0;
-    if (h && !e->d_held) {
-        Q3_HIP(hipMalloc((void**)&e->d_held, sizeof(int) * e->max_batch), -1);
-        Q3_HIP(hipMemsetAsync(e->d_held, 0, sizeof(int) * e->max_batch, e->s), -1);
-        Q3_HIP(hipStreamSynchronize(e->s), -1);
-    }
-    e->hold = h;
-    for (auto& g : e->graph) g.reset();   // the captured kernels carry the old pointers
+    e->text->hold = on != 0;
     return 0;
 }
 
