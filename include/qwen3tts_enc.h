@@ -55,5 +55,7 @@ float enc_last_ms(void* h);
 #include "qwen3tts_enc_pcm.h"
 /* The two together: a stream's pushes as s16 / f32 PCM at the client's rate, the same samples bit for bit */
 #include "qwen3tts_enc_stream_pcm.h"
+/* The PCM front-end alone: the 24 kHz samples enc_encode_pcm encodes, for the speaker encoder (qwen3tts_spk.h) */
+#include "qwen3tts_enc_resample.h"
 
 #endif /* QWEN3TTS_ENC_H */

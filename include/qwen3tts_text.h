@@ -58,6 +58,16 @@ int tfe_tts_pad_embed(void* h, float* out /*[hidden]*/);
 int tfe_build_prefix_stream(void* h, int32_t first_token_id, const int32_t* special, float* out /*[8][hidden]*/);
 int tfe_tts_eos_embed(void* h, float* out /*[hidden]*/);
 
+/* The same prefixes with a speaker embedding (qwen3tts_spk.h, spk_embed; spk_dim() must equal the hidden size): ONE row
+ * inserted after the tts_pad + codec_think_eos row (index 5), tts_pad_embed + spk, an f32 add in that order -> n + 10 rows
+ * (stream: 9); every other row is the row of the function above.  spk == NULL is exactly the function above.  <0 also for a
+ * non-finite spk value.  The row's position is a recollection of the model's voice-clone prefix (qwen_tts is not importable
+ * here), not pinned. */
+int tfe_build_prefix_spk(void* h, const int32_t* text_token_ids, int n, const int32_t* special, const float* spk /*[hidden]*/,
+                         float* out);
+int tfe_build_prefix_stream_spk(void* h, int32_t first_token_id, const int32_t* special, const float* spk /*[hidden]*/,
+                                float* out /*[9][hidden]*/);
+
 #ifdef __cplusplus
 }
 #endif

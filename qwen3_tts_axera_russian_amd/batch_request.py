@@ -47,6 +47,22 @@ descriptor and the payload: a repeated clip runs no encode.  "register_voice": "
 the ids and the prompt's text under NAME for later "voice": "NAME" requests; with "texts": [] the request only registers and is
 answered i32 0.  A --voice name cannot be replaced, a run-time one can, and at most --max_voices run-time names are kept.
 
+Speaker embedding (`--concurrent`): a request may carry "speaker_embedding" -- a list of `hidden` finite numbers shared by its
+utterances, or a list of such lists, one per utterance -- and every utterance's prefix then carries ONE more row, tts_pad_embed
++ the embedding, after the tts_pad + codec_think_eos row (frontend.build_prefix(speaker=); the row's position is a
+recollection of the model's voice-clone prefix, not pinned).  Alone it is the "x-vector only" mode, which needs no transcript;
+beside "prompt_codes" / "voice" the utterance gets both halves of a cloned voice.  `--voice NAME=DIR` picks up
+ref_spk_embedding.npy (encode_reference_audio --speaker_model) when DIR has one, and a "voice" request then gets both halves;
+"speaker": "off" in the request leaves the embedding out.  `--speaker_encoder SPK.q3w` (needs `--encoder`): a "prompt_audio"
+request may carry "speaker": "with_prompt" (the embedding of the clip's 24 kHz samples -- enc_resample_pcm, the samples the
+codec prompt is encoded from -- beside its codec prompt), "only" (the clip feeds the speaker encoder alone: no codec prompt, no
+prompt text, no vocoder warm-up) or "off" (the default: today's behaviour); from there on the request IS the request with the
+embedding (and the codes) sent inline.  "register_voice" keeps the embedding with the voice, the prompt-audio LRU keeps it with
+the ids under the same digest and counters.  The prefix key of such an utterance also digests the embedding's bytes.  A wrong
+length, a non-finite value, "speaker" without --speaker_encoder (or without "prompt_audio"), "only" beside "prompt_codes" or
+"register_voice", a clip below the speaker encoder's shortest, and any mode but --concurrent are answered -2 for that request
+alone.  No claim about voice similarity is made.
+
 Log-probabilities (`--concurrent --logprobs`): a request may carry "logprobs": true, and its reply then holds, beside every
 utterance's codes, one float32 per id: the model's log-probability, at temperature 1, of the id the stream continued with
 (include/qwen3tts_engine.h, q3e_scores_reserve: the model's distribution, not the sampler's -- no sampling key or sampler
@@ -72,6 +88,8 @@ PROMPT_KEYS = ("prompt_codes", "prompt_token_ids", "prompt_text", "voice", "prom
 PROMPT_AUDIO_FORMATS = {"s16": np.dtype("<i2"), "f32": np.dtype("<f4")}
 # the PCM front-end's limits (include/qwen3tts_enc_pcm.h, csrc/q3_enc_pcm_host.h)
 PCM_RATE, PCM_MIN_RATE, PCM_MAX_RATE, PCM_MAX_CHANNELS, PCM_MAX_FACTOR = 24000, 8000, 192000, 8, 640
+SPEAKER_KEYS = ("speaker_embedding", "speaker")
+SPEAKER_MODES = ("off", "only", "with_prompt")
 _PARAM_KEYS = ("temperature", "top_k", "top_p", "cp_temperature", "cp_top_k", "seed")   # request keys = SlotParams fields
 # request key -> SlotRules field
 _RULE_KEYS = {"repetition_penalty": "rep_penalty", "repetition_window": "rep_window", "eos_boost": "eos_boost",
@@ -82,16 +100,67 @@ RULE_KEYS = tuple(_RULE_KEYS) + ("sampler",)
 SAMPLER_PRESETS = {"reference": {}, "upstream": dict(rep_penalty=1.05, rep_window=0, eos_boost=0.0, eos_force=0.0, min_frames=2)}
 
 
-def prefix_key(kind, token_ids, prompt_codes=None):
+def prefix_key(kind, token_ids, prompt_codes=None, speaker=None):
     """The prefix cache's key of an utterance: the first 16 bytes of a SHA-256 over the kind of prefix (b"full": the
     dual-stream prefix of the whole text, b"stream": the streaming prefix, b"prompt": the dual-stream prefix followed by
     the rows of a codec prompt) and the int32 token ids that determine its rows -- for b"stream" the first token alone,
-    for b"prompt" the ids (the prompt's text first), their number, and the prompt's [T][16] codes."""
+    for b"prompt" the ids (the prompt's text first), their number, and the prompt's [T][16] codes.  speaker (the float32
+    embedding of a prefix with a speaker row): the kind becomes kind + b"+spk" and a SHA-256 of the embedding's bytes is
+    digested too; None leaves the key as it always was."""
     ids = np.asarray(token_ids, dtype="<i4").reshape(-1)
+    tail = b""
+    if speaker is not None:
+        kind = bytes(kind) + b"+spk"
+        tail = hashlib.sha256(np.ascontiguousarray(speaker, dtype="<f4").tobytes()).digest()
     if prompt_codes is None:
-        return hashlib.sha256(bytes(kind) + b"\0" + ids.tobytes()).digest()[:16]
+        return hashlib.sha256(bytes(kind) + b"\0" + ids.tobytes() + tail).digest()[:16]
     codes = np.asarray(prompt_codes, dtype="<i4").reshape(-1, 16)
-    return hashlib.sha256(bytes(kind) + b"\0" + struct.pack("<i", len(ids)) + ids.tobytes() + codes.tobytes()).digest()[:16]
+    return hashlib.sha256(bytes(kind) + b"\0" + struct.pack("<i", len(ids)) + ids.tobytes() + codes.tobytes() + tail).digest()[:16]
+
+
+def request_has_speaker(msg):
+    """Whether a request carries a speaker key."""
+    return any(msg.get(k) is not None for k in SPEAKER_KEYS)
+
+
+def request_speaker_mode(msg):
+    """A request's "speaker" key -> "off" (the default), "only" or "with_prompt"; raises ValueError on any other value."""
+    v = msg.get("speaker")
+    if v is None:
+        return "off"
+    if not isinstance(v, str) or v not in SPEAKER_MODES:
+        raise ValueError(f"speaker must be one of {SPEAKER_MODES} (got {v!r})")
+    return v
+
+
+def request_speaker_embedding(value, n_utts, hidden):
+    """A request's "speaker_embedding" -> one float32 [hidden] array per utterance: one list of `hidden` finite numbers shared
+    by the utterances, or a list of n_utts such lists.  Raises ValueError on any other shape, type, length or a non-finite value."""
+    def one(v):
+        if isinstance(v, np.ndarray):
+            v = v.tolist()
+        if not isinstance(v, list) or any(isinstance(x, bool) or not isinstance(x, (int, float)) for x in v):
+            raise ValueError("a speaker embedding is a list of numbers")
+        if len(v) != hidden:
+            raise ValueError(f"a speaker embedding of {len(v)} values, the model's hidden size is {hidden}")
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except OverflowError:               # (a JSON integer beyond the doubles)
+            raise ValueError("a speaker embedding value is out of range") from None
+        with np.errstate(over="ignore"):
+            a = a.astype(np.float32)
+        if not np.isfinite(a).all():
+            raise ValueError("a speaker embedding value is not finite (as float32)")
+        return a
+    if isinstance(value, np.ndarray):
+        value = value.tolist()
+    if not isinstance(value, list) or not value:
+        raise ValueError('"speaker_embedding" is a list of numbers, or a list of such lists, one per utterance')
+    if not isinstance(value[0], list):
+        return [one(value)] * n_utts
+    if len(value) != n_utts:
+        raise ValueError(f'"speaker_embedding" holds {len(value)} embeddings for {n_utts} utterances')
+    return [one(v) for v in value]
 
 
 @dataclasses.dataclass(eq=False)
@@ -239,28 +308,39 @@ def prompt_audio_digest(desc, payload):
 
 
 class PromptAudioCache:
-    """LRU of encoded prompts: digest -> int64 ids [T][16] (after "max_frames").  Only the thread that resolves audio
-    prompts touches it.  n = 0: nothing is kept (every clip is a miss)."""
+    """LRU of encoded prompts: digest -> int64 ids [T][16] (after "max_frames") and, beside them under the same digest, the
+    clip's speaker embedding (float32 [hidden]) once a request has asked for it.  Only the thread that resolves audio prompts
+    touches it.  n = 0: nothing is kept (every clip is a miss)."""
 
     def __init__(self, n):
         if int(n) < 0:
             raise ValueError("--prompt_audio_cache takes a number of entries >= 0")
         self.n, self.hits, self.misses, self.evictions = int(n), 0, 0, 0
-        self._lru = collections.OrderedDict()
+        self._lru = collections.OrderedDict()      # digest -> [ids or None, speaker embedding or None]
 
-    def get(self, key):
-        ids = self._lru.get(key)
-        if ids is None:
+    def lookup(self, key, want_ids=True, want_speaker=False):
+        """-> (ids, speaker) as far as the entry holds them (None each otherwise).  A hit when everything wanted is there:
+        nothing then runs on the GPU for this clip; a miss otherwise (the caller computes what is missing and puts it)."""
+        e = self._lru.get(key)
+        if e is None or (want_ids and e[0] is None) or (want_speaker and e[1] is None):
             self.misses += 1
-            return None
+            return (None, None) if e is None else (e[0], e[1])
         self._lru.move_to_end(key)
         self.hits += 1
-        return ids
+        return e[0], e[1]
 
-    def put(self, key, ids):
+    def get(self, key):
+        return self.lookup(key)[0]
+
+    def put(self, key, ids=None, speaker=None):
+        """what has been computed for the clip, beside what its entry already holds"""
         if not self.n:
             return
-        self._lru[key] = ids
+        e = self._lru.setdefault(key, [None, None])
+        if ids is not None:
+            e[0] = ids
+        if speaker is not None:
+            e[1] = speaker
         self._lru.move_to_end(key)
         while len(self._lru) > self.n:
             self._lru.popitem(last=False)
@@ -279,6 +359,7 @@ class VoiceTable:
         if int(max_runtime) < 0:
             raise ValueError("--max_voices takes a number >= 0")
         self._startup, self._runtime, self.max_runtime = dict(startup or {}), {}, int(max_runtime)
+        self._speakers = {}             # name -> the voice's speaker embedding (float32 [hidden]), for the names that have one
         self._lock = threading.Lock()
 
     def get(self, name):
@@ -298,10 +379,22 @@ class VoiceTable:
             if name not in self._runtime and len(self._runtime) >= self.max_runtime:
                 raise ValueError(f"{len(self._runtime)} voices are registered (--max_voices {self.max_runtime})")
 
-    def register(self, name, codes, text):
+    def register(self, name, codes, text, speaker=None):
         self.check_register(name)
         with self._lock:
             self._runtime[name] = (codes, text)
+            self._speakers.pop(name, None)
+            if speaker is not None:
+                self._speakers[name] = np.ascontiguousarray(speaker, np.float32)
+
+    def set_startup_speaker(self, name, speaker):
+        with self._lock:
+            self._speakers[name] = np.ascontiguousarray(speaker, np.float32)
+
+    def speaker(self, name):
+        """the speaker embedding kept with voice `name` (None: it has none)"""
+        with self._lock:
+            return self._speakers.get(name)
 
     def runtime_names(self):
         with self._lock:
@@ -319,6 +412,18 @@ def load_voice(prompt_dir):
         with open(os.path.join(prompt_dir, "ref_text.txt")) as f:
             text = f.read()
     return codes.astype(np.int64).tolist(), text
+
+
+def load_voice_speaker(prompt_dir, hidden):
+    """ref_spk_embedding.npy of a voice directory (encode_reference_audio --speaker_model) -> float32 [hidden], or None when
+    the directory has none; raises ValueError on a wrong shape or a non-finite value."""
+    path = os.path.join(prompt_dir, "ref_spk_embedding.npy")
+    if not os.path.exists(path):
+        return None
+    a = np.load(path)
+    if a.ndim != 1 or a.shape[0] != hidden or not np.issubdtype(a.dtype, np.floating) or not np.isfinite(a).all():
+        raise ValueError(f"{prompt_dir}: ref_spk_embedding.npy is not a finite float array [{hidden}]")
+    return np.ascontiguousarray(a, np.float32)
 
 
 def request_logprobs(msg, enabled):

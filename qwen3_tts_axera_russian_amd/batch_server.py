@@ -70,6 +70,17 @@ same checks, prefix key and reply, so `--prefix_cache`, `--voice_warm` and `--te
 prompt_audio_hits / prompt_audio_misses / prompt_audio_evictions are on the server object, hits and misses in the per-request
 line.  Without the flag such a request is answered -2.
 
+`--speaker_encoder SPK.q3w` (with `--concurrent --encoder`): the other half of a cloned voice.  Any `--concurrent` server takes
+"speaker_embedding" (batch_request: one more prefix row, tts_pad_embed + the embedding), alone -- "x-vector only", no transcript
+needed -- or beside a codec prompt, and `--voice NAME=DIR` picks up DIR's ref_spk_embedding.npy; with this flag the server
+computes the embedding itself from a "prompt_audio" clip: one SpeakerEncoder sized like the encoder, under the encoder's lock,
+fed the clip's 24 kHz samples from the encoder's own front-end (Encoder.resample_pcm: the samples its codec prompt comes from).
+"speaker": "with_prompt" adds the embedding to the clip's codec prompt, "only" takes the embedding alone, and the request then
+IS the request with the embedding (and codes) inline: same checks, same prefix key (which digests the embedding), same reply.
+The prompt-audio LRU keeps the embedding beside the ids (a repeated clip runs no embed), "register_voice" keeps it with the
+voice.  The speaker encoder's dim must equal the model's hidden size.  That the checkpoint's speaker encoder is the pinned class
+at this geometry, its mel parameters and the row's position are recollection; no similarity claim is made.
+
 `--pipeline`: the vocoder of request k runs on a worker thread (and replies on k's connection) while the frame loop of request
 k + 1 already runs -- the reference's client does the same per 64-frame block of ONE utterance (tts_client.py:188-197).  The
 vocoder then launches one persistent workgroup per compute unit (voc_set_max_workgroups(-1)), which leaves the frame loop's
@@ -92,9 +103,9 @@ import numpy as np
 from . import hiplib
 from . import protocol as P
 from .batch_request import (PROMPT_KEYS, VOCODER_ARITHMETICS, VOCODER_MODES, PromptAudioCache, Utterance, VoiceTable,  # noqa: F401
-                            load_voice, prefix_key, prompt_audio_digest, request_has_prompt, request_prompt_audio,
-                            request_logprobs, request_prompt_codes, request_slot_params, request_slot_rules, request_vocoder,
-                            request_vocoder_arithmetic)
+                            load_voice, load_voice_speaker, prefix_key, prompt_audio_digest, request_has_prompt, request_has_speaker,
+                            request_prompt_audio, request_logprobs, request_prompt_codes, request_slot_params, request_slot_rules,
+                            request_speaker_embedding, request_speaker_mode, request_vocoder, request_vocoder_arithmetic)
 from .batch_scheduler import ConcurrentScheduler, PushEntry, ReplyState, TextFeed, new_entries  # noqa: F401
 from .batch_wire import (REC_AUDIO, REC_END, REC_SCORES, pack_batch_reply, pack_batch_request, pack_stream_audio,  # noqa: F401
                          pack_stream_end, pack_stream_scores, read_batch_reply, read_stream_record, synthesize_batch, synthesize_batch_stream,
@@ -111,13 +122,14 @@ class BatchSynthesisServer:
     logprobs = False           # --logprobs: requests may ask for the log-probabilities of their ids (set by __init__)
     encoder = None             # --encoder: the Encoder audio prompts go through (set by __init__)
     runtime_voices = None      # the VoiceTable "register_voice" writes (set by __init__)
+    speaker = None             # --speaker_encoder: the SpeakerEncoder audio prompts' embeddings come from (set by __init__)
 
     def __init__(self, model_path, vocoder_path, socket_path="/tmp/qwen3_batch.sock", max_batch=32, n_ctx=512,
                  max_tokens=200, temperature=0.0, top_k=50, cp_temperature=0.0, tokenizer=None, seed=0,
                  install_signal_handlers=True, max_request=None, pipeline=False, concurrent=False, max_queue=None, top_p=0.95,
                  cp_top_k=None, check_every=8, send_timeout=30.0, text_wait_ms=200.0, text_hold=False, prefix_cache=0,
                  prefix_cache_rows=64, voices=None, text_voice=False, voice_warm=0, sampler_rules=False, encoder=None,
-                 prompt_audio_seconds=20.0, prompt_audio_cache=16, max_voices=64, logprobs=False):
+                 prompt_audio_seconds=20.0, prompt_audio_cache=16, max_voices=64, logprobs=False, speaker_encoder=None):
         if concurrent and pipeline:
             raise ValueError("--concurrent runs its own vocoder worker: it does not combine with --pipeline")
         self.socket_path, self.max_batch, self.max_tokens, self.n_ctx = socket_path, max_batch, max_tokens, n_ctx
@@ -140,6 +152,7 @@ class BatchSynthesisServer:
                 (sampler_rules and alone, "--sampler_rules sets the sampler rules of the shared frame loop's slots: it needs --concurrent"),
                 (logprobs and alone, "--logprobs records the log-probabilities of the shared frame loop's decisions: it needs --concurrent"),
                 (encoder and alone, "--encoder encodes the audio prompts of the shared frame loop's admissions: it needs --concurrent"),
+                (speaker_encoder and not encoder, "--speaker_encoder embeds the samples of the encoder's PCM front-end: it needs --encoder"),
                 (not float(prompt_audio_seconds) > 0, "--prompt_audio_seconds takes a number > 0"),
                 (int(voice_warm) < 0, "--voice_warm takes a number of snapshot slots >= 0"),
                 (voice_warm and alone, "--voice_warm caches the vocoder warm-up of the shared frame loop's codec prompts: it needs --concurrent")):
@@ -166,6 +179,10 @@ class BatchSynthesisServer:
         if tokenizer:
             from .tokenizer import ByteLevelBPE
             self.tokenizer = ByteLevelBPE.from_dir(tokenizer)
+        for name, d in dict(voices or {}).items():          # a voice directory's speaker embedding, when it has one
+            emb = load_voice_speaker(d, self._hidden)
+            if emb is not None:
+                self.runtime_voices.set_startup_speaker(name, emb)
         self.eng = FrameEngine(model_path, max_batch=max_batch, n_ctx=n_ctx, max_frames=max_tokens)
         self.eng.set_pad_embed(self.front.tts_pad_embed)
         self.eng.set_sampling(temperature, top_k, top_p, cp_temperature, cp_top_k, seed)
@@ -174,6 +191,13 @@ class BatchSynthesisServer:
         if encoder:
             from .encoder import Encoder
             self.encoder = Encoder(encoder, max_batch=min(max_batch, 4), max_samples=self._encoder_samples)
+        if speaker_encoder:
+            from .speaker import SpeakerEncoder
+            self.speaker = SpeakerEncoder(speaker_encoder, max_batch=min(max_batch, 4), max_samples=self._encoder_samples)
+            if self.speaker.dim != self._hidden or self.speaker.sample_rate != 24000:
+                dim, rate = self.speaker.dim, self.speaker.sample_rate
+                self.speaker.close()
+                raise ValueError(f"--speaker_encoder gives {dim} values at {rate} Hz, the model takes {self._hidden} at 24000 Hz")
         # --voice_warm N: N snapshot slots on the vocoder handle, and the LRU over them (the vocoder worker's, like the handle)
         self._voice_warm = VoiceWarmCache(int(voice_warm))
         if self._voice_warm.n_slots:
@@ -190,6 +214,8 @@ class BatchSynthesisServer:
             signal.signal(signal.SIGINT, self._signal_handler)
             signal.signal(signal.SIGTERM, self._signal_handler)
 
+    _hidden = property(lambda self: len(self.front.tts_pad_embed))   # the model's hidden size: what a speaker embedding must have
+
     def _signal_handler(self, signum, frame):
         self._running = False
 
@@ -200,15 +226,17 @@ class BatchSynthesisServer:
             raise RuntimeError("no tokenizer configured (--tokenizer DIR) and the request has no token_ids")
         return [self.tokenizer.encode(t, add_special_tokens=False) for t in msg.get("texts", [])]
 
-    def _queue(self, token_ids, max_tokens):
-        """A request's prefixes -> (prefixes, n_text, max_tokens, order): order[k] = request index of the queue's k-th utterance."""
+    def _queue(self, token_ids, max_tokens, speakers=None):
+        """A request's prefixes -> (prefixes, n_text, max_tokens, order): order[k] = request index of the queue's k-th utterance.
+        speakers (one float32 [hidden] or None per utterance): the speaker row of its prefix."""
         B = len(token_ids)
         if B == 0:
             raise ValueError("a request needs at least one utterance")
         if B > self.max_request:
             raise ValueError(f"a request may carry at most {self.max_request} utterances (got {B})")
         max_tokens = min(int(max_tokens or self.max_tokens), self.max_tokens)
-        prefixes = [self.front.build_prefix(ids) for ids in token_ids]
+        speakers = speakers or [None] * B
+        prefixes = [self.front.build_prefix(ids, speaker=spk) for ids, spk in zip(token_ids, speakers)]
         if max(p.shape[0] for p in prefixes) + max_tokens > self.n_ctx:
             raise ValueError("prefix + max_tokens exceed n_ctx")
         n_text = [len(ids) for ids in token_ids]
@@ -398,26 +426,45 @@ class BatchSynthesisServer:
             print(f"  sampler rules: {rules}")
         prompted = request_has_prompt(msg)
         if msg.get("text_stream"):
-            if prompted:
+            if prompted or request_has_speaker(msg):
                 self._check_text_voice(msg)
             return [dataclasses.replace(self._prepare_text_stream(msg, base), rules=rules)]
         ids = self._token_ids(msg)
         prompts = [None] * len(ids)
+        speakers = self._request_speakers(msg, len(ids))
         if prompted:     # a codec prompt: its text (if any) in front of every utterance's, its frames behind every prefix
             prompts, head = self._request_prompts(msg, len(ids))
             ids = [head + u for u in ids]
-        prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames)
+        prefixes, n_text, max_tokens, order = self._queue(ids, base.max_frames, speakers)
         for i in order if prompted else ():
             rows = prefixes[i].shape[0] + len(prompts[i])
             if rows + max_tokens > self.n_ctx or rows > max(self.max_batch, 2048):
                 raise ValueError("prefix + codec prompt + max_tokens exceed n_ctx (or the rows of one prefill pass)")
         return [Utterance(i, prefixes[i], n_text[i], dataclasses.replace(base, max_frames=max_tokens, utt=i),
-                          prefix_key=prefix_key(b"prompt", ids[i], prompts[i]) if prompted and len(prompts[i]) else
-                          prefix_key(b"full", ids[i]), prompt=prompts[i], rules=rules) for i in order]
+                          prefix_key=prefix_key(b"prompt", ids[i], prompts[i], speakers[i]) if prompted and len(prompts[i]) else
+                          prefix_key(b"full", ids[i], speaker=speakers[i]), prompt=prompts[i], rules=rules) for i in order]
 
     def _check_text_voice(self, msg):
         if msg.get("text_stream") and not self.text_voice:
+            if not request_has_prompt(msg):
+                raise ValueError('a speaker embedding does not combine with "text_stream"')
             raise ValueError('a codec prompt does not combine with "text_stream"')
+
+    def _request_speakers(self, msg, n_utts):
+        """A request's speaker embeddings -> one float32 [hidden] (or None) per utterance: "speaker_embedding", else the
+        embedding kept with its "voice" unless "speaker" is "off".  By now a "prompt_audio" request's "speaker" has become
+        "speaker_embedding" (_resolve_prompt_audio): "only" / "with_prompt" still standing here have no clip to come from."""
+        mode = request_speaker_mode(msg)
+        if mode != "off":
+            raise ValueError(f'"speaker": "{mode}" needs "prompt_audio" (and a server started with --speaker_encoder)')
+        if msg.get("speaker_embedding") is not None:
+            return request_speaker_embedding(msg["speaker_embedding"], n_utts, self._hidden)
+        name = msg.get("voice")
+        if isinstance(name, str) and msg.get("speaker") != "off" and self.runtime_voices is not None:
+            emb = self.runtime_voices.speaker(name)
+            if emb is not None:
+                return [emb] * n_utts
+        return [None] * n_utts
 
     def _request_prompts(self, msg, n_utts):
         """A request's codec prompt -> (one [T][16] int32 array per utterance, the prompt text's token ids): from "prompt_codes"
@@ -472,18 +519,20 @@ class BatchSynthesisServer:
         if not first:
             raise ValueError('the first piece of a "text_stream" request must give at least one token')
         prompt, head = None, []
+        (spk,) = self._request_speakers(msg, 1)
+        own = 8 if spk is None else 9                  # rows of the streaming prefix (one more with a speaker row)
         if request_has_prompt(msg):
             (prompt,), head = self._request_prompts(msg, 1)
-            rows = 8 + len(head) + len(prompt)
+            rows = own + len(head) + len(prompt)
             if rows + base.max_frames > self.n_ctx or rows > max(self.max_batch, 2048):
                 raise ValueError("prefix + codec prompt + max_tokens exceed n_ctx (or the rows of one prefill pass)")
-        if 8 + base.max_frames > self.n_ctx:
+        if own + base.max_frames > self.n_ctx:
             raise ValueError("prefix + max_tokens exceed n_ctx")
         feed = TextFeed(lambda ids, final=False: text_stream_rows(self.front, ids, final), encoder,
                         None if self.tokenizer is None else self.tokenizer.incremental, first[1:], 1 + len(head))
         params = dataclasses.replace(base, utt=0, text_stream=True, text_after_prompt=prompt is not None)
-        return Utterance(0, self.front.build_prefix_stream(first[0], head), 0, params, feed,
-                         prefix_key(b"stream", head + first[:1], prompt), prompt)
+        return Utterance(0, self.front.build_prefix_stream(first[0], head, speaker=spk), 0, params, feed,
+                         prefix_key(b"stream", head + first[:1], prompt, spk), prompt)
 
     def _prefix_note(self):
         """The prefix cache's and the voice warm-ups' counters so far, for the per-request line ("" without the flags)."""
@@ -510,6 +559,14 @@ class BatchSynthesisServer:
             raise ValueError('"register_voice" needs "prompt_audio"')
         if msg.get("prompt_codes") is not None or msg.get("voice") is not None:
             raise ValueError('"prompt_audio" takes the place of "prompt_codes" / "voice": give one')
+        mode = request_speaker_mode(msg)           # where the speaker embedding comes from: "off" (none), the clip alone, or both
+        if mode != "off":
+            if self.speaker is None:
+                raise ValueError('"speaker" needs a server started with --speaker_encoder')
+            if msg.get("speaker_embedding") is not None:
+                raise ValueError('"speaker" takes the embedding from the clip: it does not combine with "speaker_embedding"')
+            if mode == "only" and name is not None:
+                raise ValueError('"speaker": "only" keeps no codec prompt: it does not combine with "register_voice"')
         utts = msg["token_ids"] if msg.get("token_ids") is not None else msg.get("texts", [])
         if not isinstance(utts, list):
             raise ValueError("texts / token_ids is a list")
@@ -520,30 +577,50 @@ class BatchSynthesisServer:
         elif not utts:
             raise ValueError("a request needs at least one utterance")
         descs, shared = request_prompt_audio(spec, len(utts), self._encoder_samples)
+        if mode != "off":
+            for d in descs:
+                if d.samples_24k < self.speaker.min_samples:
+                    raise ValueError(f'"prompt_audio": {d.samples_24k} samples at 24 kHz, the speaker encoder needs {self.speaker.min_samples}')
+        want_ids, want_spk = mode != "only", mode != "off"
         payloads = [P.recv_payload(conn, d.nbytes) for d in descs]
         keys = [prompt_audio_digest(d, raw) for d, raw in zip(descs, payloads)]
-        ids, missing = [None] * len(descs), {}
+        ids, embs, missing, missing_spk = [None] * len(descs), [None] * len(descs), {}, {}
         for k, (d, key) in enumerate(zip(descs, keys)):
             first = next((j for j in range(k) if keys[j] == key), None)
-            ids[k] = self._prompt_audio.get(key) if first is None else ids[first]
-            if ids[k] is None and first is None:
+            if first is not None:                  # (a clip the request repeats: encoded and embedded once, below)
+                continue
+            ids[k], embs[k] = self._prompt_audio.lookup(key, want_ids, want_spk)
+            if want_ids and ids[k] is None:
                 missing.setdefault((d.format, d.channels, d.rate), []).append(k)
+            if want_spk and embs[k] is None:
+                missing_spk.setdefault((d.format, d.channels, d.rate), []).append(k)
         for (fmt, channels, rate), ks in missing.items():
             with self._encoder_lock:
                 got = self.encoder.encode_pcm([descs[k].array(payloads[k]) for k in ks], rate, channels)
             for k, c in zip(ks, got):
                 ids[k] = np.ascontiguousarray(c[:descs[k].max_frames], np.int64)
                 self._prompt_audio.put(keys[k], ids[k])
-        for k in range(len(descs)):                # (a clip the request repeats: encoded once)
-            if ids[k] is None:
-                ids[k] = ids[keys.index(keys[k])]
+        for (fmt, channels, rate), ks in missing_spk.items():
+            with self._encoder_lock:               # the front-end's own 24 kHz samples, then the speaker encoder
+                samples = self.encoder.resample_pcm([descs[k].array(payloads[k]) for k in ks], rate, channels)
+                got = self.speaker.embed(samples)
+            for k, e in zip(ks, got):
+                embs[k] = np.ascontiguousarray(e, np.float32)
+                self._prompt_audio.put(keys[k], speaker=embs[k])
+        for k in range(len(descs)):
+            j = keys.index(keys[k])
+            ids[k], embs[k] = ids[j], embs[j]
         del msg["prompt_audio"]
         msg.pop("register_voice", None)
-        msg["prompt_codes"] = ids[0].tolist() if shared else [c.tolist() for c in ids]
+        msg.pop("speaker", None)
+        if want_ids:
+            msg["prompt_codes"] = ids[0].tolist() if shared else [c.tolist() for c in ids]
+        if want_spk:
+            msg["speaker_embedding"] = embs[0].tolist() if shared else [e.tolist() for e in embs]
         if name is not None:
             text = msg.get("prompt_token_ids") if msg.get("prompt_token_ids") is not None else msg.get("prompt_text")
             self._request_prompts(dict(msg, text_stream=False), 1)      # (the checks a later "voice" request would fail)
-            self.runtime_voices.register(name, msg["prompt_codes"], text)
+            self.runtime_voices.register(name, msg["prompt_codes"], text, speaker=embs[0] if want_spk else None)
             print(f"  voice {name!r} registered: {len(ids[0])} frames")
             if not utts:
                 conn.sendall(struct.pack("<i", 0))
@@ -606,6 +683,8 @@ class BatchSynthesisServer:
                     raise ValueError('"text_stream" needs a --concurrent server')
                 if request_has_prompt(msg):
                     raise ValueError("a codec prompt needs a --concurrent server")
+                if request_has_speaker(msg):
+                    raise ValueError("a speaker embedding needs a --concurrent server")
                 request_slot_rules(msg, False)
                 request_logprobs(msg, False)
                 if msg.get("stream"):
@@ -697,6 +776,9 @@ class BatchSynthesisServer:
         self._stream_pool = None       # the push worker of streamed requests (the pipeline's worker when there is one)
         if self.pipeline:
             self._lib.voc_set_max_workgroups(0)
+        if self.speaker is not None:
+            self.speaker.close()
+            self.speaker = None
         if self.encoder is not None:
             self.encoder.close()
             self.encoder = None
@@ -754,6 +836,9 @@ def main():
     ap.add_argument("--prompt_audio_seconds", type=float, default=20.0, help="--encoder: the longest audio prompt, in seconds")
     ap.add_argument("--prompt_audio_cache", type=int, default=16,
                     help="--encoder: entries of the LRU of encoded audio prompts (a repeated clip runs no encode)")
+    ap.add_argument("--speaker_encoder", default=None,
+                    help="--concurrent --encoder: speaker-encoder container; a \"prompt_audio\" request may then carry \"speaker\": "
+                         "\"with_prompt\" / \"only\" and gets the clip's x-vector as one more prefix row")
     ap.add_argument("--max_voices", type=int, default=64, help="--encoder: voices \"register_voice\" may keep at run time")
     ap.add_argument("--text_voice", action="store_true",
                     help="--concurrent: a text-stream request may carry a codec prompt (\"voice\" / \"prompt_codes\"): streamed "
@@ -769,7 +854,7 @@ def main():
                                voices=dict(v.split("=", 1) for v in a.voice), text_voice=a.text_voice,
                                voice_warm=a.voice_warm, sampler_rules=a.sampler_rules, encoder=a.encoder,
                                prompt_audio_seconds=a.prompt_audio_seconds, prompt_audio_cache=a.prompt_audio_cache,
-                               max_voices=a.max_voices, logprobs=a.logprobs)
+                               max_voices=a.max_voices, logprobs=a.logprobs, speaker_encoder=a.speaker_encoder)
     try:
         srv.serve()
     finally:

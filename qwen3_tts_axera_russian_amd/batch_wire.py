@@ -38,6 +38,9 @@ Audio prompt (`--concurrent --encoder`): a request that carries "prompt_audio" (
 "frames"[, "max_frames"]}, or a list of them, one per utterance) is followed on the same connection by the clips' raw
 little-endian interleaved PCM -- frames * channels * itemsize bytes per descriptor, in order, no framing -- before any text
 record.  A request with "register_voice" and "texts": [] is answered i32 0.
+
+Speaker embedding (`--concurrent`): "speaker_embedding" travels in the JSON as numbers (a float32 survives the trip bit for
+bit), "speaker" beside "prompt_audio" names where the server takes it from; there is no new record and no new payload.
 """
 from __future__ import annotations
 
@@ -58,7 +61,7 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
                        vocoder_arithmetic=None, text_stream=False, prompt_codes=None, prompt_token_ids=None, prompt_text=None,
                        voice=None, sampler=None, repetition_penalty=None, repetition_window=None, eos_boost=None, eos_force=None,
                        min_tokens=None, cp_top_p=None, prompt_audio=None, prompt_audio_max_frames=None, register_voice=None,
-                       logprobs=None) -> bytes:
+                       logprobs=None, speaker_embedding=None, speaker=None) -> bytes:
     """The request of the batched protocol; the sampling keys (honoured by --concurrent), the vocoder mode ("walk" /
     "incremental") and the incremental mode's arithmetic ("exact" / "split") are sent only when given.  text_stream: the
     request carries only the first piece of its one utterance's text; the rest follows as text records.  prompt_codes ([T][16], or
@@ -68,7 +71,9 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
     array [n] or [n][channels] -- or a list of such pairs, one per utterance: the audio whose voice the utterances continue
     (--concurrent --encoder); its descriptor goes into the JSON ("max_frames": prompt_audio_max_frames) and its bytes behind
     it, so the result is JSON plus payload.  register_voice: the name the server keeps that prompt under.  logprobs: True
-    asks for the log-probability of every emitted id (--concurrent --logprobs)."""
+    asks for the log-probability of every emitted id (--concurrent --logprobs).  speaker_embedding: [hidden] floats (or one such
+    per utterance), the x-vector whose row the prefix carries (--concurrent; float32 values travel exactly); speaker: "only" /
+    "with_prompt" / "off" -- where a prompt_audio request's embedding comes from (--speaker_encoder; batch_request)."""
     msg = {"language": language}
     if stream:
         msg["stream"] = True
@@ -85,7 +90,10 @@ def pack_batch_request(texts=None, token_ids=None, language="russian", max_token
             [np.asarray(c).tolist() if isinstance(c, np.ndarray) else c for c in prompt_codes]
     if prompt_token_ids is not None:
         prompt_token_ids = [int(t) for t in prompt_token_ids]
-    for key, v in (("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("cp_temperature", cp_temperature),
+    if speaker_embedding is not None:
+        a = np.asarray(speaker_embedding, dtype=np.float32)
+        speaker_embedding = [float(x) for x in a] if a.ndim == 1 else [[float(x) for x in row] for row in a]
+    for key, v in (("speaker_embedding", speaker_embedding), ("speaker", speaker), ("temperature", temperature), ("top_k", top_k), ("top_p", top_p), ("cp_temperature", cp_temperature),
                    ("cp_top_k", cp_top_k), ("seed", seed), ("vocoder", vocoder), ("vocoder_arithmetic", vocoder_arithmetic),
                    ("prompt_codes", prompt_codes), ("prompt_token_ids", prompt_token_ids), ("prompt_text", prompt_text),
                    ("voice", voice), ("sampler", sampler), ("repetition_penalty", repetition_penalty),

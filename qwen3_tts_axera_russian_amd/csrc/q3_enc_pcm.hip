@@ -232,6 +232,35 @@ int enc_encode_pcm(void* h, const void* pcm, int format, int channels, int rate,
     return enc_collect_codes(e, B, lens, T, codes_out, max_frames, n_frames);
 }
 
+int enc_resample_pcm(void* h, const void* pcm, int format, int channels, int rate, const int32_t* n_in, int B, float* out, int out_pitch,
+                     int32_t* n_out) {
+    Enc* e = (Enc*)h;
+    if (!e) {
+        Q3_LOG("enc_resample_pcm: NULL handle");
+        return -1;
+    }
+    enc_bind(e);
+    if (!out || !n_out) {
+        Q3_LOG("enc_resample_pcm: NULL out or n_out");
+        return -1;
+    }
+    std::vector<int> lens;
+    if (enc_pcm_prepare(e, pcm, format, channels, rate, n_in, B, lens, "enc_resample_pcm")) return -1;
+    for (int b = 0; b < B; b++)
+        if (lens[b] > out_pitch) {   // (the launch above only wrote the handle's own rows)
+            Q3_LOG("enc_resample_pcm: clip %d gives %d samples, out holds %d per clip", b, lens[b], out_pitch);
+            hipStreamSynchronize(e->s);
+            return -1;
+        }
+    const long pitch = enc_pitch(*std::max_element(lens.begin(), lens.begin() + B));
+    for (int b = 0; b < B; b++)
+        Q3_HIP(hipMemcpyAsync(out + (size_t)b * out_pitch, e->pcm + (size_t)b * pitch, (size_t)lens[b] * sizeof(float), hipMemcpyDeviceToHost,
+                              e->s), -1);
+    Q3_HIP(hipStreamSynchronize(e->s), -1);
+    for (int b = 0; b < B; b++) n_out[b] = lens[b];
+    return 0;
+}
+
 // test hook (not in the header, beside enc_debug_run): the rows the front-end prepares, whole pitch rows so that the zeros past
 // a clip's length can be seen: out [B][*ld] f32, *ld = the longest clip's 24 kHz length rounded up to 32 (the caller sizes out
 // for that: the lengths follow from n_in and the rate), n_out[B] the clips' lengths

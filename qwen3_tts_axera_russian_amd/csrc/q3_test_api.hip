@@ -3,6 +3,7 @@
 // libqwen3tts.so / llama_wrapper.so.
 #include "q3_enc.h"
 #include "q3_model.h"
+#include "q3_spk.h"
 #include "q3_voc_ops.h"
 #include <chrono>
 #include <cstring>
@@ -1438,4 +1439,14 @@ extern "C" int q3t_prefix_move_case(uint16_t* kc, uint16_t* vc, int n_layers, in
         }
     }
     return outside ? -3 : rc;
+}
+
+// ---- the speaker encoder's stages (q3_spk.hip): the log-mel [B][n_mels][L] and the activation after a stage [B][C][L]
+// (L = the longest clip's frames; the pooled stages asp and fc: [B][C], L = 1).  Stage 0 block0, 1.. the SE-Res2Net blocks,
+// then mfa, asp, fc.  out is sized by the caller for the call's lengths (spk_frames); 0 / <0
+extern "C" int q3t_spk_mel(void* h, const float* pcm, const int32_t* n_samples, int B, float* out, int* C, int* L) {
+    return spk_debug_mel((Spk*)h, pcm, n_samples, B, out, C, L);
+}
+extern "C" int q3t_spk_stage(void* h, const float* pcm, const int32_t* n_samples, int B, int stage, float* out, int* C, int* L) {
+    return spk_debug_stage((Spk*)h, pcm, n_samples, B, stage, out, C, L);
 }

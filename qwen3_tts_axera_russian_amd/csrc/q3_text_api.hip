@@ -3,6 +3,8 @@
 #include "../../include/qwen3tts_text.h"
 #include "q3_model.h"
 
+#include <cmath>
+
 using namespace q3;
 
 namespace {
@@ -264,10 +266,9 @@ int tfe_embed_text(void* hh, const int32_t* token_ids, int n, float* out) {
     return emit(t, ids, src, cod, out) == n ? 0 : -1;
 }
 
-int tfe_build_prefix(void* hh, const int32_t* text_token_ids, int n, const int32_t* special, float* out) {
-    TextFE* t = (TextFE*)hh;
-    if (!t || !out || n < 0 || (n > 0 && !text_token_ids)) return -1;
-    const int* sp = special ? special : t->special;
+// spk (or nullptr): one more row after the tts_pad + codec_think_eos row, tts_pad's projected row alone, to which the caller's
+// speaker embedding is added in f32 once the rows are on the host (tts_pad_embed + spk, in that order)
+static int build_prefix_rows(TextFE* t, const int32_t* text_token_ids, int n, const int* sp, const float* spk, float* out) {
     // projected rows: 0-2 role tokens, 3 tts_pad, 4 tts_bos, 5 tts_eos, 6.. the text
     std::vector<int> ids = {sp[0], sp[1], sp[2], sp[3], sp[4], sp[5]};
     ids.insert(ids.end(), text_token_ids, text_token_ids + n);
@@ -280,6 +281,7 @@ int tfe_build_prefix(void* hh, const int32_t* text_token_ids, int n, const int32
     row(3, sp[8]);                                                  // tts_pad + codec nothink / think_bos / think_eos
     row(3, sp[9]);
     row(3, sp[10]);
+    if (spk) row(3, -1);                                            // tts_pad (+ the speaker embedding, below)
     row(4, sp[6]);                                                  // tts_bos + codec_pad
     for (int i = 0; i < n; i++) row(6 + i, sp[6]);                  // text + codec_pad
     row(5, sp[6]);                                                  // tts_eos + codec_pad
@@ -287,15 +289,60 @@ int tfe_build_prefix(void* hh, const int32_t* text_token_ids, int n, const int32
     return emit(t, ids, src, cod, out);
 }
 
-int tfe_build_prefix_stream(void* hh, int32_t first_token_id, const int32_t* special, float* out) {
-    TextFE* t = (TextFE*)hh;
-    if (!t || !out) return -1;
-    const int* sp = special ? special : t->special;
+static int build_prefix_stream_rows(TextFE* t, int32_t first_token_id, const int* sp, const float* spk, float* out) {
     // rows 0..6 of tfe_build_prefix, then the first text token + codec_bos: the rest of the text follows frame by frame
     // through the feedback (q3e_push_text).  Projected rows: 0-2 role tokens, 3 tts_pad, 4 tts_bos, 5 the first token.
     std::vector<int> ids = {sp[0], sp[1], sp[2], sp[3], sp[4], first_token_id};
     std::vector<int> src = {0, 1, 2, 3, 3, 3, 4, 5}, cod = {-1, -1, -1, sp[8], sp[9], sp[10], sp[6], sp[7]};
+    if (spk) {
+        src.insert(src.begin() + 6, 3);
+        cod.insert(cod.begin() + 6, -1);
+    }
     return emit(t, ids, src, cod, out);
+}
+
+// the speaker row (index 6 of a _spk prefix) += spk; a non-finite value refuses the call before anything runs
+static bool spk_finite(const TextFE* t, const float* spk, const char* who) {
+    for (int i = 0; i < t->H; i++)
+        if (!std::isfinite(spk[i])) {
+            Q3_LOG("%s: speaker embedding value %d is not finite", who, i);
+            return false;
+        }
+    return true;
+}
+static void add_spk_row(const TextFE* t, const float* spk, float* out) {
+    float* r = out + (size_t)6 * t->H;
+    for (int i = 0; i < t->H; i++) r[i] = r[i] + spk[i];
+}
+
+int tfe_build_prefix(void* hh, const int32_t* text_token_ids, int n, const int32_t* special, float* out) {
+    TextFE* t = (TextFE*)hh;
+    if (!t || !out || n < 0 || (n > 0 && !text_token_ids)) return -1;
+    return build_prefix_rows(t, text_token_ids, n, special ? special : t->special, nullptr, out);
+}
+
+int tfe_build_prefix_spk(void* hh, const int32_t* text_token_ids, int n, const int32_t* special, const float* spk, float* out) {
+    TextFE* t = (TextFE*)hh;
+    if (!spk) return tfe_build_prefix(hh, text_token_ids, n, special, out);
+    if (!t || !out || n < 0 || (n > 0 && !text_token_ids) || !spk_finite(t, spk, "tfe_build_prefix_spk")) return -1;
+    const int rows = build_prefix_rows(t, text_token_ids, n, special ? special : t->special, spk, out);
+    if (rows > 0) add_spk_row(t, spk, out);
+    return rows;
+}
+
+int tfe_build_prefix_stream(void* hh, int32_t first_token_id, const int32_t* special, float* out) {
+    TextFE* t = (TextFE*)hh;
+    if (!t || !out) return -1;
+    return build_prefix_stream_rows(t, first_token_id, special ? special : t->special, nullptr, out);
+}
+
+int tfe_build_prefix_stream_spk(void* hh, int32_t first_token_id, const int32_t* special, const float* spk, float* out) {
+    TextFE* t = (TextFE*)hh;
+    if (!spk) return tfe_build_prefix_stream(hh, first_token_id, special, out);
+    if (!t || !out || !spk_finite(t, spk, "tfe_build_prefix_stream_spk")) return -1;
+    const int rows = build_prefix_stream_rows(t, first_token_id, special ? special : t->special, spk, out);
+    if (rows > 0) add_spk_row(t, spk, out);
+    return rows;
 }
 
 int tfe_tts_eos_embed(void* hh, float* out) {

@@ -3,7 +3,7 @@ scripts/encode_reference_audio.py, on the GPU encoder).
 
     python -m qwen3_tts_axera_russian_amd.encode_reference_audio --audio ref.wav --model enc.q3w --output_dir prompt/ \
         [--ref_text "..."] [--max_tokens 256] [--decode_back ref_decoded.wav --vocoder voc.q3w] [--stream_seconds 1.0]
-        [--resample host|device] [--push_seconds 0.5]
+        [--resample host|device] [--push_seconds 0.5] [--speaker_model spk.q3w]
 
 Writes ref_codec_tokens.npy (int64 [min(T, max_tokens)][16], the semantic id first) to --output, or, with --output_dir,
 a prompt_dir holding ref_codec_tokens.npy and (with --ref_text) ref_text.txt.  --model is an encoder container
@@ -21,7 +21,13 @@ the host's scipy and its float32 arithmetic and is pinned to nothing.  --resampl
 frames through the streaming encode in pushes of round(S * the file's rate) frames (Encoder.encode_streaming_pcm /
 enc_stream_push_pcm): the same pinned samples bit for bit whatever S, device memory that of one push, a WAV of any length.
 qwen_tts's own resampler is not available here:
-neither path is pinned to it."""
+neither path is pinned to it.
+
+--speaker_model SPK.q3w (a speaker-encoder container, weights.convert_speaker_encoder / make_synthetic_spk) additionally
+writes ref_spk_embedding.npy, float32 [dim], next to ref_codec_tokens.npy: the x-vector of the SAME 24 kHz samples the ids
+come from (SpeakerEncoder.embed / spk_embed), in every mode above -- the host-resampled samples, or the device front-end's
+(Encoder.resample_pcm / enc_resample_pcm; the streamed modes embed the whole clip once the ids are out, so the clip must
+then fit the device).  The whole clip is embedded, whatever --max_tokens keeps of the ids."""
 from __future__ import annotations
 
 import argparse
@@ -84,6 +90,31 @@ def open_encoder(model, max_samples):
     return Encoder(model, max_batch=1, max_samples=max_samples)
 
 
+def open_speaker(model, max_samples):
+    from .speaker import SpeakerEncoder
+    return SpeakerEncoder(model, max_batch=1, max_samples=max_samples)
+
+
+def embed_speaker(a, samples, speaker_factory):
+    """--speaker_model: the x-vector of the clip's 24 kHz samples -> float32 [dim]; None without the flag"""
+    if not a.speaker_model:
+        return None
+    samples = np.ascontiguousarray(samples, dtype=np.float32).reshape(-1)
+    # (at least a second of room: a clip below the encoder's shortest is then refused by the check below, with its reason)
+    spk = speaker_factory(a.speaker_model, max(int(samples.size), 24000))
+    try:
+        if spk.sample_rate != 24000:
+            raise ValueError(f"the speaker encoder takes {spk.sample_rate} Hz, the samples are at 24000 Hz")
+        if samples.size < spk.min_samples:
+            raise ValueError(f"the clip has {samples.size} samples at 24 kHz, the speaker encoder needs {spk.min_samples}")
+        t0 = time.time()
+        emb = spk.embed([samples])[0]
+        print(f"Speaker embedding: {emb.size} values, {time.time() - t0:.3f}s (GPU {spk.last_ms():.2f} ms, {spk.last_launches()} launches)")
+        return np.ascontiguousarray(emb, dtype=np.float32)
+    finally:
+        spk.close()
+
+
 def decode_back(codes, vocoder, out_wav):
     """The reference's "decode back" step: codes -> voc_synthesize (int16, 24 kHz) -> WAV."""
     from .vocoder import Vocoder
@@ -100,7 +131,7 @@ def decode_back(codes, vocoder, out_wav):
     return len(pcm)
 
 
-def _save(a, codes):
+def _save(a, codes, emb=None):
     n_tokens, n_groups = codes.shape
     print(f"Tokens: {n_tokens}, Groups: {n_groups}")
     keep = np.ascontiguousarray(codes[:min(n_tokens, a.max_tokens)], dtype=np.int64)
@@ -110,17 +141,23 @@ def _save(a, codes):
         if a.ref_text:
             with open(os.path.join(a.output_dir, "ref_text.txt"), "w") as f:
                 f.write(a.ref_text)
+        if emb is not None:
+            np.save(os.path.join(a.output_dir, "ref_spk_embedding.npy"), emb)
         print(f"Saved prompt_dir: {a.output_dir}")
     else:
         np.save(a.output, keep)
         print(f"Saved: {a.output}")
+        if emb is not None:
+            dst = os.path.join(os.path.dirname(os.path.abspath(a.output)), "ref_spk_embedding.npy")
+            np.save(dst, emb)
+            print(f"Saved: {dst}")
     if a.decode_back:
         n = decode_back(keep, a.vocoder, a.decode_back)
         print(f"Saved decoded: {a.decode_back} ({n} samples)")
     return 0
 
 
-def main(argv=None, encoder_factory=open_encoder):
+def main(argv=None, encoder_factory=open_encoder, speaker_factory=open_speaker):
     p = argparse.ArgumentParser(description="Encode reference audio to codec tokens (GPU speech-tokenizer encoder)")
     p.add_argument("--audio", required=True, help="reference audio WAV file")
     p.add_argument("--model", "--model_dir", dest="model", required=True,
@@ -138,6 +175,8 @@ def main(argv=None, encoder_factory=open_encoder):
                         "resample on the GPU, pinned to resample_poly's float64 result")
     p.add_argument("--push_seconds", type=float, default=None,
                    help="with --resample device: stream the file's own frames in pushes of this many seconds (a WAV of any length)")
+    p.add_argument("--speaker_model", default=None,
+                   help="speaker-encoder container (.q3w): also write ref_spk_embedding.npy, the x-vector of the same 24 kHz samples")
     a = p.parse_args(argv)
     if a.resample == "device" and a.stream_seconds is not None:
         p.error("--resample device streams with --push_seconds (--stream_seconds pushes host-resampled 24 kHz samples)")
@@ -171,17 +210,28 @@ def main(argv=None, encoder_factory=open_encoder):
             print(f"error: {e}", file=sys.stderr)
             return 2
         print(f"Encode time: {time.time() - t0:.3f}s (streamed, pushes of up to {push} frames at {sr} Hz, front-end on the device)")
-        return _save(a, codes)
+        emb = None
+        if a.speaker_model:   # the whole clip through the same front-end (the stream's samples bit for bit), then embedded
+            try:
+                whole = encoder_factory(a.model, -(-x.shape[0] * 24000 // sr))
+                emb = embed_speaker(a, whole.resample_pcm([x], sr, channels=1 if x.ndim == 1 else x.shape[1])[0], speaker_factory)
+            except (ValueError, RuntimeError) as e:
+                print(f"error: {e}", file=sys.stderr)
+                return 2
+        return _save(a, codes, emb)
     if a.resample == "device":
         enc = encoder_factory(a.model, -(-x.shape[0] * 24000 // sr))
         t0 = time.time()
         try:
             codes = enc.encode_pcm([x], sr, channels=1 if x.ndim == 1 else x.shape[1])[0]
+            ms = enc.last_ms()
+            emb = embed_speaker(a, enc.resample_pcm([x], sr, channels=1 if x.ndim == 1 else x.shape[1])[0], speaker_factory) \
+                if a.speaker_model else None
         except (ValueError, RuntimeError) as e:
             print(f"error: {e}", file=sys.stderr)
             return 2
-        print(f"Encode time: {time.time() - t0:.3f}s (GPU {enc.last_ms():.2f} ms, front-end on the device)")
-        return _save(a, codes)
+        print(f"Encode time: {time.time() - t0:.3f}s (GPU {ms:.2f} ms, front-end on the device)")
+        return _save(a, codes, emb)
     x = resample(x, sr, 24000)
     if a.stream_seconds is None:
         enc = encoder_factory(a.model, max(int(x.size), 1))
@@ -197,7 +247,12 @@ def main(argv=None, encoder_factory=open_encoder):
         push = max(int(round(a.stream_seconds * enc.sample_rate)), 1)
         codes = enc.encode_streaming(x, push)
         print(f"Encode time: {time.time() - t0:.3f}s (streamed, {-(-x.size // push)} pushes of {push} samples)")
-    return _save(a, codes)
+    try:
+        emb = embed_speaker(a, x, speaker_factory)
+    except (ValueError, RuntimeError) as e:
+        print(f"error: {e}", file=sys.stderr)
+        return 2
+    return _save(a, codes, emb)
 
 
 if __name__ == "__main__":

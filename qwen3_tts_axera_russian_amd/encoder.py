@@ -94,6 +94,25 @@ class Encoder:
             out += [codes[b, :nf[b]].copy() for b in range(len(part))]
         return out
 
+    def resample_pcm(self, clips, rate, channels=1):
+        """The front-end alone (enc_resample_pcm): the 24 kHz mono float32 samples encode_pcm encodes, bit for bit -> list
+        of float32 arrays.  What the speaker encoder embeds, so that both halves of a voice come from one resampler."""
+        fmt, n, flat = self._pcm_payload(clips, channels)
+        channels = int(channels)
+        out, at = [], 0
+        for i in range(0, len(n), self.max_batch):
+            part = np.ascontiguousarray(n[i:i + self.max_batch])
+            buf = flat[at:at + int(part.sum()) * channels]
+            at += int(part.sum()) * channels
+            pcm = np.zeros((len(part), self.max_samples), np.float32)
+            n_out = np.zeros(len(part), np.int32)
+            rc = self.lib.enc_resample_pcm(self.h, buf.ctypes.data, fmt, channels, int(rate), hiplib.iptr(part), len(part),
+                                           hiplib.fptr(pcm), self.max_samples, hiplib.iptr(n_out))
+            if rc != 0:
+                raise RuntimeError(f"enc_resample_pcm failed ({rc}); see the log")
+            out += [pcm[b, :n_out[b]].copy() for b in range(len(part))]
+        return out
+
     def last_ms(self):
         """GPU milliseconds of the last library call"""
         return float(self.lib.enc_last_ms(self.h))

@@ -26,9 +26,14 @@ class TextFrontEnd:
         h = h * (1.0 / (1.0 + np.exp(-h)))          # SiLU
         return (h @ self.fc2_w.T + self.fc2_b).astype(np.float32)
 
-    def build_prefix(self, text_token_ids, language="russian"):
+    def build_prefix(self, text_token_ids, language="russian", speaker=None):
         """Text stream + codec stream, summed per position.  `language` is accepted and unused, as in
-        the reference (parsed, passed, never read)."""
+        the reference (parsed, passed, never read).
+        speaker (float32 [hidden], SpeakerEncoder.embed; tfe_build_prefix_spk): ONE row more, tts_pad_embed + speaker (an f32
+        add in that order) after the tts_pad + codec_think_eos row -- n + 10 rows, every other row unchanged.  The row's
+        position is a recollection of the model's voice-clone prefix, not pinned.  None: today's rows, bit for bit."""
+        if speaker is not None:
+            return _insert_speaker_row(self.build_prefix(text_token_ids, language), self.tts_pad_embed, speaker)
         c, cod = self.cfg, self.codec
         n = len(text_token_ids)
         out = np.empty((n + 9, cod.shape[1]), np.float32)
@@ -41,13 +46,16 @@ class TextFrontEnd:
         out[8 + n] = self.tts_pad_embed + cod[c.codec_bos]
         return out
 
-    def build_prefix_stream(self, first_token_id, head=()):
+    def build_prefix_stream(self, first_token_id, head=(), speaker=None):
         """The 8-row prefix of a text-stream utterance (tfe_build_prefix_stream): rows 0..6 of build_prefix, then the first
         text token + codec_bos.  The rest of the text follows frame by frame (text_stream_rows).
         head (token ids; a text-stream utterance that continues a codec prompt: the text the prompt speaks): one
         `text + codec_pad` row per head token stands between row 6 and the last row, as rows 7.. of build_prefix(head)
         do -- 8 + len(head) rows.  Like the other streamed layouts this is a recollection of the model's in-context mode:
-        parity on real weights is not pinned, the arithmetic is.  Without head: today's 8 rows, bit for bit."""
+        parity on real weights is not pinned, the arithmetic is.  Without head: today's 8 rows, bit for bit.
+        speaker: as in build_prefix, the same row at the same index (tfe_build_prefix_stream_spk) -- 9 + len(head) rows."""
+        if speaker is not None:
+            return _insert_speaker_row(self.build_prefix_stream(first_token_id, head), self.tts_pad_embed, speaker)
         c, cod = self.cfg, self.codec
         n = len(head)
         out = np.empty((8 + n, cod.shape[1]), np.float32)
@@ -58,6 +66,25 @@ class TextFrontEnd:
             out[7:7 + n] = self.embed_text(head) + cod[c.codec_pad]
         out[7 + n] = self.embed_text([int(first_token_id)])[0] + cod[c.codec_bos]
         return out
+
+
+SPEAKER_ROW = 6   # index of the speaker row in a prefix that has one: after tts_pad + codec_think_eos (row 5)
+
+
+def check_speaker(speaker, hidden):
+    """-> float32 [hidden], or ValueError: a wrong length (spk_dim != the hidden size) or a non-finite value"""
+    v = np.ascontiguousarray(np.asarray(speaker, dtype=np.float32).reshape(-1))
+    if v.size != int(hidden):
+        raise ValueError(f"a speaker embedding of {v.size} values, the model's hidden size is {int(hidden)}")
+    if not np.isfinite(v).all():
+        raise ValueError("a speaker embedding with a non-finite value")
+    return v
+
+
+def _insert_speaker_row(rows, tts_pad_embed, speaker):
+    v = check_speaker(speaker, rows.shape[1])
+    row = (np.asarray(tts_pad_embed, np.float32) + v).astype(np.float32)
+    return np.concatenate([rows[:SPEAKER_ROW], row[None], rows[SPEAKER_ROW:]], axis=0)
 
 
 def text_stream_rows(fe, token_ids, final=False):
@@ -97,8 +124,17 @@ class DeviceTextFrontEnd:
             raise RuntimeError("tfe_embed_text failed")
         return out
 
-    def build_prefix(self, text_token_ids, language="russian"):
+    def build_prefix(self, text_token_ids, language="russian", speaker=None):
+        """speaker (float32 [hidden]): tfe_build_prefix_spk, one row more (TextFrontEnd.build_prefix)"""
         ids = np.ascontiguousarray(text_token_ids, dtype=np.int32).reshape(-1)
+        if speaker is not None:
+            v = check_speaker(speaker, self.hidden)   # (spk_dim != hidden is refused here, before the library is called)
+            out = np.empty((len(ids) + 10, self.hidden), np.float32)
+            n = self._lib.tfe_build_prefix_spk(self.h, self._hl.iptr(ids) if len(ids) else None, len(ids),
+                                               self._hl.iptr(self._special), self._hl.fptr(v), self._hl.fptr(out))
+            if n != len(ids) + 10:
+                raise RuntimeError(f"tfe_build_prefix_spk failed: {n}")
+            return out
         out = np.empty((len(ids) + 9, self.hidden), np.float32)
         n = self._lib.tfe_build_prefix(self.h, self._hl.iptr(ids) if len(ids) else None, len(ids),
                                        self._hl.iptr(self._special), self._hl.fptr(out))
@@ -106,16 +142,22 @@ class DeviceTextFrontEnd:
             raise RuntimeError(f"tfe_build_prefix failed: {n}")
         return out
 
-    def build_prefix_stream(self, first_token_id, head=()):
+    def build_prefix_stream(self, first_token_id, head=(), speaker=None):
         """TextFrontEnd.build_prefix_stream: with head, rows 0..6+len(head) of tfe_build_prefix(head), then the last row of
-        tfe_build_prefix_stream(first_token_id)."""
-        out = np.empty((8, self.hidden), np.float32)
-        n = self._lib.tfe_build_prefix_stream(self.h, int(first_token_id), self._hl.iptr(self._special), self._hl.fptr(out))
-        if n != 8:
-            raise RuntimeError(f"tfe_build_prefix_stream failed: {n}")
+        tfe_build_prefix_stream(first_token_id).  speaker: the _spk calls, the speaker row at index 6 of both."""
+        k = 0 if speaker is None else 1
+        out = np.empty((8 + k, self.hidden), np.float32)
+        if speaker is None:
+            n = self._lib.tfe_build_prefix_stream(self.h, int(first_token_id), self._hl.iptr(self._special), self._hl.fptr(out))
+        else:
+            v = check_speaker(speaker, self.hidden)
+            n = self._lib.tfe_build_prefix_stream_spk(self.h, int(first_token_id), self._hl.iptr(self._special), self._hl.fptr(v),
+                                                      self._hl.fptr(out))
+        if n != 8 + k:
+            raise RuntimeError(f"tfe_build_prefix_stream{'_spk' if k else ''} failed: {n}")
         if len(head) == 0:
             return out
-        return np.concatenate([self.build_prefix(head)[:7 + len(head)], out[7:]], axis=0)
+        return np.concatenate([self.build_prefix(head, speaker=speaker)[:7 + k + len(head)], out[7 + k:]], axis=0)
 
     def destroy(self):
         if self.h:

@@ -191,6 +191,17 @@ def load(path: str | None = None):
     _sig(lib, "enc_debug_pcm", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, i32p, c_int, f32p, i32p, i32p])
     _sig(lib, "enc_debug_shape", c_int, [c_void_p, i32p, c_int, c_int, i32p, i32p])
     _sig(lib, "enc_debug_run", c_int, [c_void_p, f32p, i32p, c_int, c_int, f32p, i32p, i32p])
+    _sig(lib, "enc_resample_pcm", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, i32p, c_int, f32p, c_int, i32p])
+    # include/qwen3tts_spk.h
+    _sig(lib, "spk_load", c_void_p, [c_char_p, c_int, c_int])
+    _sig(lib, "spk_free", None, [c_void_p])
+    _sig(lib, "spk_dim", c_int, [c_void_p])
+    _sig(lib, "spk_sample_rate", c_int, [c_void_p])
+    _sig(lib, "spk_min_samples", c_int, [c_void_p])
+    _sig(lib, "spk_frames", c_int, [c_void_p, c_int])
+    _sig(lib, "spk_embed", c_int, [c_void_p, f32p, i32p, c_int, f32p])
+    _sig(lib, "spk_last_ms", c_float, [c_void_p])
+    _sig(lib, "spk_last_launches", c_int, [c_void_p])
     # include/qwen3tts_enc_stream.h
     _sig(lib, "enc_stream_create", c_void_p, [c_void_p, c_int, c_int])
     _sig(lib, "enc_stream_free", None, [c_void_p])
@@ -220,6 +231,8 @@ def load(path: str | None = None):
     _sig(lib, "tfe_tts_pad_embed", c_int, [c_void_p, f32p])
     _sig(lib, "tfe_build_prefix_stream", c_int, [c_void_p, ctypes.c_int32, i32p, f32p])
     _sig(lib, "tfe_tts_eos_embed", c_int, [c_void_p, f32p])
+    _sig(lib, "tfe_build_prefix_spk", c_int, [c_void_p, i32p, c_int, i32p, f32p, f32p])
+    _sig(lib, "tfe_build_prefix_stream_spk", c_int, [c_void_p, ctypes.c_int32, i32p, f32p, f32p])
     # test hook of csrc/q3_text_api.hip (not in the header): ids, n -> x16, h1, a16, h2 in fragment order, dims[4]
     _sig(lib, "tfe_debug_stages", c_int, [c_void_p, i32p, c_int, u16p, f32p, u16p, f32p, i32p])
     _sig(lib, "q3_device_count", c_int, [])
@@ -302,6 +315,8 @@ def load_test():
     _sig(lib, "q3t_enc_rvq_tile", c_int, [c_int])
     _sig(lib, "q3t_enc_rvq_case", c_int, [f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, f32p, i64p])
     _sig(lib, "q3t_enc_conv_in_case", c_int, [f32p, c_int, c_int, f32p, f32p, c_int, c_int, f32p, c_int, i32p, f32p])
+    _sig(lib, "q3t_spk_mel", c_int, [c_void_p, f32p, i32p, c_int, f32p, i32p, i32p])
+    _sig(lib, "q3t_spk_stage", c_int, [c_void_p, f32p, i32p, c_int, c_int, f32p, i32p, i32p])
     _test_lib = lib
     return lib
 

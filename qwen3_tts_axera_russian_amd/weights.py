@@ -1318,3 +1318,212 @@ def convert_speech_tokenizer_encoder(src_dir: str, out_path: str):
     ec, t, rep = state_to_enc(T, cfgj, n_q, where=src_dir)
     write_pack(out_path, {"enc_sample_rate": float(ec.sample_rate)}, t)
     return ec, rep + report
+
+
+# ----------------------------------------------------------------------------
+# speaker encoder (ECAPA-TDNN x-vector, csrc/q3_spk.hip, include/qwen3tts_spk.h)
+# ----------------------------------------------------------------------------
+# Pinned by tests/golden/spk_golden.npz: the network to transformers' ECAPA_TimeDelayNet (models/qwen2_5_omni) in float64,
+# the log-mel to float64 torch.stft + the slaney filter bank.  Recollection (qwen_tts is not importable here): that the TTS
+# checkpoint's `speaker_encoder` is that class at the defaults below with enc_dim = the talker's hidden size, and the mel
+# parameters.  Both are parameters of the container, not code.
+@dataclass
+class SpkConfig:
+    sample_rate: int = 24000
+    n_fft: int = 1024
+    hop: int = 256
+    win: int = 1024
+    pad: int = 384
+    n_mels: int = 128
+    mel_floor: float = 1e-5
+    mag_eps: float = 1e-9
+    fmin: float = 0.0
+    fmax: float = 12000.0
+    channels: tuple = (512, 512, 512, 512, 1536)
+    kernel_sizes: tuple = (5, 3, 3, 3, 1)
+    dilations: tuple = (1, 2, 3, 4, 1)
+    res2net_scale: int = 8
+    se_channels: int = 128
+    attention_channels: int = 128
+    dim: int = 1024
+
+
+def tiny_spk_config() -> SpkConfig:
+    return SpkConfig(n_fft=64, hop=16, win=64, pad=24, n_mels=16, channels=(32, 32, 32, 32, 96), res2net_scale=4,
+                     se_channels=8, attention_channels=8, dim=32)
+
+
+def spk_min_frames(sc: SpkConfig) -> int:
+    """columns the widest "same" reflect padding of the network needs (padding p on at least p + 1 columns): 5"""
+    return 1 + max(d * (k - 1) // 2 for k, d in zip(sc.kernel_sizes, sc.dilations))
+
+
+def spk_frames(sc: SpkConfig, n_samples: int) -> int:
+    """frames of a clip (spk_frames of the library): 1 + (n + 2 pad - n_fft) // hop; -1 when refused"""
+    if n_samples <= sc.pad or n_samples + 2 * sc.pad < sc.n_fft:
+        return -1
+    f = 1 + (n_samples + 2 * sc.pad - sc.n_fft) // sc.hop
+    return f if f >= spk_min_frames(sc) else -1
+
+
+def spk_min_samples(sc: SpkConfig) -> int:
+    return max(sc.pad + 1, (spk_min_frames(sc) - 1) * sc.hop + sc.n_fft - 2 * sc.pad)
+
+
+def spk_mel_filter_bank(sc: SpkConfig) -> np.ndarray:
+    """f64 [n_fft / 2 + 1][n_mels]: the library knows no mel formula, it reads this tensor"""
+    from transformers.audio_utils import mel_filter_bank
+    return np.asarray(mel_filter_bank(sc.n_fft // 2 + 1, sc.n_mels, sc.fmin, sc.fmax, sc.sample_rate, norm="slaney",
+                                      mel_scale="slaney"), dtype=np.float64)
+
+
+def spk_meta(sc: SpkConfig) -> dict:
+    """The container's meta holds numbers only, so `spk.config` is these scalar entries plus the int32 tensor spk.geometry
+    ([3][blocks]: channels, kernel sizes, dilations); spk_config_of() puts them together again."""
+    return {"spk_sample_rate": sc.sample_rate, "spk_n_fft": sc.n_fft, "spk_hop": sc.hop, "spk_win": sc.win, "spk_pad": sc.pad,
+            "spk_n_mels": sc.n_mels, "spk_mel_floor": sc.mel_floor, "spk_mag_eps": sc.mag_eps, "spk_fmin": sc.fmin,
+            "spk_fmax": sc.fmax, "spk_res2net_scale": sc.res2net_scale, "spk_se_channels": sc.se_channels,
+            "spk_attention_channels": sc.attention_channels, "spk_dim": sc.dim}
+
+
+def spk_config_of(meta: dict, tensors: dict) -> SpkConfig:
+    g = np.asarray(tensors["spk.geometry"])
+    ints = ("sample_rate", "n_fft", "hop", "win", "pad", "n_mels", "res2net_scale", "se_channels", "attention_channels", "dim")
+    kw = {k: int(meta["spk_" + k]) for k in ints}
+    kw.update({k: float(meta["spk_" + k]) for k in ("mel_floor", "mag_eps", "fmin", "fmax")})
+    return SpkConfig(channels=tuple(int(x) for x in g[0]), kernel_sizes=tuple(int(x) for x in g[1]),
+                     dilations=tuple(int(x) for x in g[2]), **kw)
+
+
+def spk_state_shapes(sc: SpkConfig) -> list:
+    """(key, shape) of an ECAPA_TimeDelayNet state dict at this geometry, in the module's order"""
+    ch, ks = sc.channels, sc.kernel_sizes
+    nb = len(ch)
+    out = []
+
+    def conv(p, cout, cin, k):
+        out.append((p + ".weight", (cout, cin, k)))
+        out.append((p + ".bias", (cout,)))
+    conv("blocks.0.conv", ch[0], sc.n_mels, ks[0])
+    for i in range(1, nb - 1):
+        cw = ch[i] // sc.res2net_scale
+        conv(f"blocks.{i}.tdnn1.conv", ch[i], ch[i - 1], 1)
+        for j in range(sc.res2net_scale - 1):
+            conv(f"blocks.{i}.res2net_block.blocks.{j}.conv", cw, cw, ks[i])
+        conv(f"blocks.{i}.tdnn2.conv", ch[i], ch[i], 1)
+        conv(f"blocks.{i}.se_block.conv1", sc.se_channels, ch[i], 1)
+        conv(f"blocks.{i}.se_block.conv2", ch[i], sc.se_channels, 1)
+    conv("mfa.conv", ch[-1], ch[-1], ks[-1])
+    conv("asp.tdnn.conv", sc.attention_channels, 3 * ch[-1], 1)
+    conv("asp.conv", ch[-1], sc.attention_channels, 1)
+    conv("fc", sc.dim, 2 * ch[-1], 1)
+    return out
+
+
+def synthetic_spk_state(sc: SpkConfig, seed: int = 1234) -> dict:
+    """A seeded ECAPA_TimeDelayNet state dict at torch's default Conv1d scale: uniform in +-1 / sqrt(fan_in), biases too."""
+    state = {}
+    for k, shp in spk_state_shapes(sc):
+        fan_in = int(np.prod(spk_weight_shape(sc, k)[1:]))
+        state[k] = ((2.0 * _rng_for("spk." + k, seed).random(shp) - 1.0) / np.sqrt(fan_in)).astype(np.float32)
+    return state
+
+
+def spk_weight_shape(sc: SpkConfig, key: str):
+    shapes = dict(spk_state_shapes(sc))
+    return shapes[key[:-len("bias")] + "weight"] if key.endswith("bias") else shapes[key]
+
+
+def _spk_pack_conv(w: np.ndarray) -> np.ndarray:
+    """torch [cout][cin][k] -> conv_kernel's layout (q3_voc_ops.h, wk [Cin/8][K][8][Mp]) of the ONE-tap conv over the
+    cin * k unfolded rows (row ci * k + j): [cin * k / 8][1][8][Mp], Mp = cout rounded up to 4, the pad rows zero."""
+    cout, cin, k = w.shape
+    if (cin * k) % 8:
+        raise ValueError(f"a conv over {cin} x {k} rows: the MFMA conv takes a multiple of 8")
+    mp = (cout + 3) // 4 * 4
+    out = np.zeros((cin * k, mp), np.float32)
+    out[:, :cout] = np.asarray(w, np.float32).reshape(cout, cin * k).T
+    return out.reshape(-1)
+
+
+def convert_speaker_encoder(state_dict: dict, prefix: str = "speaker_encoder.", sc: SpkConfig | None = None, verbose: bool = True):
+    """ECAPA_TimeDelayNet state dict (keys under `prefix`; everything else is left alone) -> (SpkConfig, meta, tensors spk.*).
+    The network's geometry is read from the shapes; the mel parameters (not in a state dict) come from `sc` (default: the
+    recollected ones).  An unknown key under the prefix is refused."""
+    import re
+    sc = sc or SpkConfig()
+    T = {k[len(prefix):]: np.asarray(v) for k, v in state_dict.items() if k.startswith(prefix)}
+    if not T:
+        raise KeyError(f"no tensors under {prefix!r}")
+    pats = [r"blocks\.0\.conv", r"blocks\.\d+\.tdnn[12]\.conv", r"blocks\.\d+\.res2net_block\.blocks\.\d+\.conv",
+            r"blocks\.\d+\.se_block\.conv[12]", r"mfa\.conv", r"asp\.tdnn\.conv", r"asp\.conv", r"fc"]
+    known = re.compile(r"^(" + "|".join(pats) + r")\.(weight|bias)$")
+    for k in T:
+        if not known.match(k):
+            raise KeyError(f"convert_speaker_encoder: unknown key {prefix}{k}")
+    blocks = sorted({int(k.split(".")[1]) for k in T if k.startswith("blocks.")})
+    if blocks != list(range(len(blocks))) or len(blocks) < 2:
+        raise KeyError(f"convert_speaker_encoder: blocks {blocks} are not 0..n")
+    w0 = T["blocks.0.conv.weight"]
+    ch, ks = [w0.shape[0]], [w0.shape[2]]
+    scale = None
+    for i in blocks[1:]:
+        res = sorted(int(k.split(".")[4]) for k in T if re.match(rf"blocks\.{i}\.res2net_block\.blocks\.\d+\.conv\.weight$", k))
+        if res != list(range(len(res))) or not res or (scale not in (None, len(res) + 1)):
+            raise KeyError(f"convert_speaker_encoder: block {i}: Res2Net convs {res}")
+        scale = len(res) + 1
+        ch.append(T[f"blocks.{i}.tdnn1.conv.weight"].shape[0])
+        ks.append(T[f"blocks.{i}.res2net_block.blocks.0.conv.weight"].shape[2])
+    ch.append(T["mfa.conv.weight"].shape[0])
+    ks.append(T["mfa.conv.weight"].shape[2])
+    dil = tuple(sc.dilations) if len(sc.dilations) == len(ch) else tuple([1] + list(range(2, len(ch))) + [1])
+    sc = SpkConfig(**{**asdict(sc), "n_mels": int(w0.shape[1]), "channels": tuple(int(c) for c in ch),
+                      "kernel_sizes": tuple(int(k) for k in ks), "dilations": dil, "res2net_scale": int(scale),
+                      "se_channels": int(T["blocks.1.se_block.conv1.weight"].shape[0]),
+                      "attention_channels": int(T["asp.conv.weight"].shape[1]), "dim": int(T["fc.weight"].shape[0])})
+    for k, shp in spk_state_shapes(sc):
+        if k not in T:
+            raise KeyError(f"convert_speaker_encoder: missing {prefix}{k}")
+        if tuple(T[k].shape) != tuple(shp):
+            raise ValueError(f"convert_speaker_encoder: {prefix}{k} is {tuple(T[k].shape)}, the geometry gives {tuple(shp)}")
+    f32 = lambda k: np.ascontiguousarray(np.asarray(T[k], np.float32))
+    t = {"spk.geometry": np.asarray([sc.channels, sc.kernel_sizes, sc.dilations], np.int32),
+         # (the container has no f64 type: the doubles' bit patterns in an int64 tensor)
+         "spk.mel_fb": np.ascontiguousarray(spk_mel_filter_bank(sc)).view(np.int64)}
+
+    def conv(dst, src):
+        t[dst + ".w"] = _spk_pack_conv(f32(src + ".weight"))
+        t[dst + ".b"] = f32(src + ".bias")
+    conv("spk.block0", "blocks.0.conv")
+    for i in blocks[1:]:
+        conv(f"spk.block{i}.tdnn1", f"blocks.{i}.tdnn1.conv")
+        for j in range(scale - 1):
+            conv(f"spk.block{i}.res{j}", f"blocks.{i}.res2net_block.blocks.{j}.conv")
+        conv(f"spk.block{i}.tdnn2", f"blocks.{i}.tdnn2.conv")
+        for n in ("1", "2"):   # per-clip matvecs: plain [out][in]
+            t[f"spk.block{i}.se{n}.w"] = f32(f"blocks.{i}.se_block.conv{n}.weight")[:, :, 0].copy()
+            t[f"spk.block{i}.se{n}.b"] = f32(f"blocks.{i}.se_block.conv{n}.bias")
+    conv("spk.mfa", "mfa.conv")
+    cm = sc.channels[-1]
+    wa = f32("asp.tdnn.conv.weight")   # [A][x | mean | std][1]: the x columns stay a conv, mean | std become a per-clip bias
+    t["spk.asp.tdnn.w"] = _spk_pack_conv(wa[:, :cm, :])
+    t["spk.asp.tdnn.wstat"] = wa[:, cm:, 0].copy()
+    t["spk.asp.tdnn.b"] = f32("asp.tdnn.conv.bias")
+    conv("spk.asp.conv", "asp.conv")
+    t["spk.fc.w"] = f32("fc.weight")[:, :, 0].copy()
+    t["spk.fc.b"] = f32("fc.bias")
+    if verbose:
+        print(f"speaker encoder: mel {sc.n_mels} -> channels {list(sc.channels)} (kernels {list(sc.kernel_sizes)}, dilations "
+              f"{list(sc.dilations)}), Res2Net scale {sc.res2net_scale}, SE {sc.se_channels}, attention {sc.attention_channels}, "
+              f"dim {sc.dim}; {sc.n_fft}-point frames every {sc.hop} samples at {sc.sample_rate} Hz, at least "
+              f"{spk_min_samples(sc)} samples per clip")
+    return sc, spk_meta(sc), t
+
+
+def make_synthetic_spk(path: str, cfg: SpkConfig | None = None, seed: int = 1234) -> SpkConfig:
+    """A speaker-encoder container of seeded weights (synthetic_spk_state through the converter) for spk_load()."""
+    cfg = cfg or SpkConfig()
+    state = {"speaker_encoder." + k: v for k, v in synthetic_spk_state(cfg, seed).items()}
+    sc, meta, t = convert_speaker_encoder(state, sc=cfg, verbose=False)
+    write_pack(path, meta, t)
+    return sc
