@@ -21,7 +21,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
-SOURCES = ["q3_common.cpp", "q3_formats.cpp", "q3_kernels.hip", "q3_model.hip", "q3_talker_api.hip", "q3_cp_api.hip",
+SOURCES = ["q3_common.cpp", "q3_formats.cpp", "q3_linear.hip", "q3_attn.hip", "q3_sample.hip", "q3_rows.hip", "q3_timeline.hip", "q3_model.hip", "q3_talker_api.hip", "q3_cp_api.hip",
            "q3_engine.hip", "q3_voc_kernels.hip", "q3_voc.hip", "q3_voc_stream.hip", "q3_enc.hip", "q3_enc_pcm.hip", "q3_enc_stream.hip",
            "q3_enc_stream_pcm.hip", "q3_spk.hip", "q3_text_api.hip"]
 TEST_SOURCES = ["q3_test_api.hip"]
@@ -49,15 +49,10 @@ NO_SPILL = ("resunit_kernel", "linear_kernelILi1ELi1E", "linear_kernelILi1ELi2E"
             "enc_stream_conv_in_kernel")
 
 
-def kernel_resources(lib_path: str):
-    """-> {kernel symbol: (vgprs, agprs, spilled vgprs, scratch bytes)} of the gfx950 code objects inside a built
-    shared library (the metadata notes of the fat binary's AMDGPU ELF images)."""
-    import re
+def code_objects(lib_path: str):
+    """Yield the gfx950 code objects (AMDGPU ELF images, as bytes) of the fat binaries inside a built shared library."""
     import struct
-    import tempfile
-    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
     d = open(lib_path, "rb").read()
-    res = {}
     i = d.find(b"__CLANG_OFFLOAD_BUNDLE__")
     while i >= 0:
         n = struct.unpack_from("<Q", d, i + 24)[0]
@@ -68,17 +63,34 @@ def kernel_resources(lib_path: str):
             triple = d[off:off + ts].decode()
             off += ts
             if ARCH in triple and sz:
-                with tempfile.NamedTemporaryFile(suffix=".elf") as f:
-                    f.write(d[i + o:i + o + sz])
-                    f.flush()
-                    notes = subprocess.run([readelf, "--notes", f.name], capture_output=True, text=True).stdout
-                for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
-                    def g(key, blk=blk):
-                        m = re.search(r"\." + key + r":\s+(\S+)", blk)
-                        return m.group(1) if m else "0"
-                    res[g("name")] = (int(g("vgpr_count")), int(blk.split()[0]), int(g("vgpr_spill_count")),
-                                      int(g("private_segment_fixed_size")))
+                yield d[i + o:i + o + sz]
         i = d.find(b"__CLANG_OFFLOAD_BUNDLE__", i + 1)
+
+
+def kernel_notes(elf: bytes):
+    """-> {kernel symbol: {metadata key: text}} from the metadata notes of one code object."""
+    import re
+    import tempfile
+    with tempfile.NamedTemporaryFile(suffix=".elf") as f:
+        f.write(elf)
+        f.flush()
+        notes = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", f.name], capture_output=True, text=True).stdout
+    res = {}
+    for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
+        kv = dict(re.findall(r"\.(\w+):\s+(\S+)", blk))
+        kv["agpr_count"] = blk.split()[0]
+        res[kv.get("name", "0")] = kv
+    return res
+
+
+def kernel_resources(lib_path: str):
+    """-> {kernel symbol: (vgprs, agprs, spilled vgprs, scratch bytes)} of the gfx950 code objects inside a built
+    shared library (the metadata notes of the fat binary's AMDGPU ELF images)."""
+    res = {}
+    for elf in code_objects(lib_path):
+        for name, kv in kernel_notes(elf).items():
+            res[name] = (int(kv.get("vgpr_count", 0)), int(kv["agpr_count"]), int(kv.get("vgpr_spill_count", 0)),
+                         int(kv.get("private_segment_fixed_size", 0)))
     return res
 
 

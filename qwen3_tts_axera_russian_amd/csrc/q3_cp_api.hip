@@ -322,7 +322,7 @@ int cp_lm_head(void* hh, int group, const float* hidden, float* logits_out) {
     const int H = m.cfg.hidden, V = m.cfg.cp_vocab;
     if (group < 0 || group >= m.cfg.cp_groups) return -1;
     std::vector<uint16_t> h16((size_t)16 * H, 0);
-    for (int i = 0; i < H; i++) h16[frag_idx_host(0, i, H)] = f2h_sat(hidden[i]);
+    for (int i = 0; i < H; i++) h16[frag_idx(0, i, H)] = f2h_sat(hidden[i]);
     Q3_HIP(hipMemcpyAsync(h->w.hidden_f16, h16.data(), h16.size() * 2, hipMemcpyHostToDevice, h->s), -1);
     LinArgs a;
     a.wp = m.cp_head[group].wp;

@@ -1,4 +1,4 @@
-// q3_kernels.h -- launch interface of the gfx950 kernels (q3_kernels.hip).
+// q3_kernels.h -- launch interface of the gfx950 kernels (q3_linear.hip, q3_attn.hip, q3_sample.hip, q3_rows.hip).
 //
 // Numerics contract shared with oracle/q3_oracle.c (DESIGN.md "Numerics"):
 //   * projection weights fp16, residual stream / norms / softmax / tables f32,
@@ -8,6 +8,7 @@
 //   * K/V cache fp16, q kept f32.
 #pragma once
 #include "q3_common.h"
+#include "q3_frag.h"
 
 namespace q3 {
 
@@ -80,7 +81,7 @@ struct AttnArgs {
 };
 int launch_attn(hipStream_t s, const AttnArgs& a, int mode);
 
-// Uploaded row-major rows[R][H] -> residual stream h in fragment order (see frag_idx in q3_kernels.hip)
+// Uploaded row-major rows[R][H] -> residual stream h in fragment order (see frag_idx in q3_frag.h)
 // + ssq[m][p] = sum_{k in 16-block p} rows[m][k]^2  (H/16 partials per row)
 // + xh = fp16((rows*gamma)/16), the pre-scaled GEMM input of the layer whose norm weight is gamma (null: none)
 int launch_ssq_rows(hipStream_t s, const float* rows, float* h, float* ssq, int R, int H, half_t* xh = nullptr,
@@ -314,5 +315,16 @@ int launch_prompt_rows(hipStream_t s, const PromptRowsArgs& a);
 
 // diagnostic timeline build: node numbering of the launches that follow (no-op otherwise)
 int tl_next_node();
+
+// ---- dispatch knobs (tests and probes) ----
+int set_linear_tuning(int K, int mt16, int kbw);   // k-blocks per wave for (K, row tile); -1: no such entry
+int set_linear_split_rows(int on);
+int set_linear_narrow8(int on);
+int set_linear_wide_tiles(int on);
+int set_attn_short(int on);
+int set_gemm_min_rows(int n);
+int set_gemm_glds(int on);
+int reset_linear_knobs();
+const char* last_linear_variant();
 
 }  // namespace q3

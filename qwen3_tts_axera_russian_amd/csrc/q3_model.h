@@ -71,12 +71,7 @@ int kv_alloc(KVCache& kv, int n_layers, int n_slots, int n_kv, int n_ctx, hipStr
 void kv_free(KVCache& kv);
 int kv_zero(hipStream_t s, KVCache& kv);   // every slot's keys and values to 0 (asynchronous on s)
 
-// Activations of one stack pass over up to max_rows rows.
-// host mirror of frag_idx (q3_kernels.hip): position of element (m, k) of a [rows][K] GEMM-input matrix
-inline size_t frag_idx_host(int m, int k, int K) {
-    return ((((size_t)(m >> 4) * (K >> 5) + (k >> 5)) * 64 + (m & 15) + 16 * ((k >> 3) & 3)) << 3) + (k & 7);
-}
-
+// Activations of one stack pass over up to max_rows rows (fragment order: frag_idx, q3_frag.h).
 struct Work {
     int max_rows = 0, hidden = 0;   // max_rows is padded to a multiple of 128 (largest row tile)
     float* rows_in = nullptr;       // row-major staging of uploaded embedding rows

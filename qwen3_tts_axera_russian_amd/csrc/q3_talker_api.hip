@@ -243,7 +243,7 @@ int wrapper_codec_head(void* ctx, const float* hidden, int n_rows, float* logits
     const int H = m.cfg.hidden, V = m.cfg.talker_vocab;
     std::vector<uint16_t> h16((size_t)((n_rows + 15) / 16 * 16) * H, 0);
     for (int r = 0; r < n_rows; r++)
-        for (int k = 0; k < H; k++) h16[frag_idx_host(r, k, H)] = f2h_sat(hidden[(size_t)r * H + k]);
+        for (int k = 0; k < H; k++) h16[frag_idx(r, k, H)] = f2h_sat(hidden[(size_t)r * H + k]);
     Q3_HIP(hipMemcpyAsync(c->w.hidden_f16, h16.data(), h16.size() * 2, hipMemcpyHostToDevice, c->s), -1);
     LinArgs a;
     a.wp = m.talker_head.wp;

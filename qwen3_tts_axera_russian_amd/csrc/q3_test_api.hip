@@ -5,6 +5,7 @@
 #include "q3_model.h"
 #include "q3_spk.h"
 #include "q3_voc_ops.h"
+#include "q3_xlane.h"
 #include <chrono>
 #include <cstring>
 #include <vector>
@@ -12,17 +13,49 @@
 using namespace q3;
 
 namespace q3 {
-int set_linear_tuning(int K, int mt16, int kbw);
-int set_linear_split_rows(int on);
-int set_linear_narrow8(int on);
-int set_linear_wide_tiles(int on);
-int set_attn_short(int on);
-int launch_xlane_case(hipStream_t s, int op, int width, int n, const float* in, float* out_new, float* out_shfl);
-int set_gemm_min_rows(int n);
-int set_gemm_glds(int on);
-int reset_linear_knobs();
-const char* last_linear_variant();
+// ---------------------------------------------------------------------------
+// test hook of the cross-lane helpers (q3t_xlane_case): one kernel applies a butterfly built on xlane_xor and the same
+// butterfly built on __shfl_xor to the same registers.  op 0: sum, 1: max, 2: the (value, index) arg-max exchange of
+// block_argmax (index = the element's position in `in`); stages WIDTH/2 .. 1.  n is a multiple of 64 (whole waves, the
+// helpers' contract); out_* hold n words, for op 2 another n with the winning indices behind them.
+// ---------------------------------------------------------------------------
+template <int OP, int WIDTH>
+__global__ void __launch_bounds__(256) xlane_case_kernel(const float* __restrict__ in, int n, float* __restrict__ out_new,
+                                                         float* __restrict__ out_shfl) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // grid * block == n
+    const float v = in[i];
+    if (OP == 0) {
+        out_new[i] = group_sum_down<WIDTH, WIDTH / 2, XlDpp>(v);
+        out_shfl[i] = group_sum_down<WIDTH, WIDTH / 2, XlShfl>(v);
+    } else if (OP == 1) {
+        out_new[i] = group_max_down<WIDTH, WIDTH / 2, XlDpp>(v);
+        out_shfl[i] = group_max_down<WIDTH, WIDTH / 2, XlShfl>(v);
+    } else {
+        float va = v, vb = v;
+        int ia = i, ib = i;
+        group_argmax_down<WIDTH, WIDTH / 2, XlDpp>(va, ia);
+        group_argmax_down<WIDTH, WIDTH / 2, XlShfl>(vb, ib);
+        out_new[i] = va;
+        out_new[n + i] = __int_as_float(ia);
+        out_shfl[i] = vb;
+        out_shfl[n + i] = __int_as_float(ib);
+    }
 }
+int launch_xlane_case(hipStream_t s, int op, int width, int n, const float* in, float* out_new, float* out_shfl) {
+    if (op < 0 || op > 2 || (width != 4 && width != 16 && width != 64) || n <= 0 || n % 64) return -2;
+    const int threads = n % 256 ? 64 : 256;
+    const dim3 grid(n / threads), block(threads);
+#define Q3_XLANE(OP_, W_)                                                                                   \
+    if (op == OP_ && width == W_)                                                                           \
+        hipLaunchKernelGGL((xlane_case_kernel<OP_, W_>), grid, block, 0, s, in, n, out_new, out_shfl);
+    Q3_XLANE(0, 4) Q3_XLANE(0, 16) Q3_XLANE(0, 64)
+    Q3_XLANE(1, 4) Q3_XLANE(1, 16) Q3_XLANE(1, 64)
+    Q3_XLANE(2, 4) Q3_XLANE(2, 16) Q3_XLANE(2, 64)
+#undef Q3_XLANE
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+}  // namespace q3
 
 namespace {
 struct DBuf {
@@ -77,7 +110,7 @@ int q3t_linear(int M, int N, int K, const uint16_t* W, int gateup, int pro, int 
     if (pro == PRO_F16) {
         std::vector<uint16_t> xp((size_t)Mp * K, 0);   // host rows -> fragment order
         for (int m = 0; m < M; m++)
-            for (int k = 0; k < K; k++) xp[frag_idx_host(m, k, K)] = x16[(size_t)m * K + k];
+            for (int k = 0; k < K; k++) xp[frag_idx(m, k, K)] = x16[(size_t)m * K + k];
         if (!dx.up(xp.data(), xp.size() * 2)) return -1;
         a.x16 = (const half_t*)dx.p;
     } else {
@@ -102,7 +135,7 @@ int q3t_linear(int M, int N, int K, const uint16_t* W, int gateup, int pro, int 
     } else if (epi == EPI_RESID) {
         hp.assign((size_t)Mp * N, 0.f);
         for (int m = 0; m < M; m++)
-            for (int n = 0; n < N; n++) hp[frag_idx_host(m, n, N)] = y_or_h_io[(size_t)m * N + n];
+            for (int n = 0; n < N; n++) hp[frag_idx(m, n, N)] = y_or_h_io[(size_t)m * N + n];
         if (!dy.up(hp.data(), hp.size() * 4) || !dso.alloc((size_t)Mp * (N / 16) * 4)) return -1;
         a.h_out = (float*)dy.p;
         a.ssq_out = (float*)dso.p;
@@ -116,14 +149,14 @@ int q3t_linear(int M, int N, int K, const uint16_t* W, int gateup, int pro, int 
     if (epi == EPI_RESID) {
         Q3_HIP(hipMemcpy(hp.data(), dy.p, hp.size() * 4, hipMemcpyDeviceToHost), -1);
         for (int m = 0; m < M; m++)
-            for (int n = 0; n < N; n++) y_or_h_io[(size_t)m * N + n] = hp[frag_idx_host(m, n, N)];
+            for (int n = 0; n < N; n++) y_or_h_io[(size_t)m * N + n] = hp[frag_idx(m, n, N)];
         if (ssq_out) Q3_HIP(hipMemcpy(ssq_out, dso.p, (size_t)M * (N / 16) * 4, hipMemcpyDeviceToHost), -1);
     }
     if (epi == EPI_SWIGLU) {
         std::vector<uint16_t> ap((size_t)Mp * (N / 2));
         Q3_HIP(hipMemcpy(ap.data(), dact.p, ap.size() * 2, hipMemcpyDeviceToHost), -1);
         for (int m = 0; m < M; m++)
-            for (int j = 0; j < N / 2; j++) act_out[(size_t)m * (N / 2) + j] = ap[frag_idx_host(m, j, N / 2)];
+            for (int j = 0; j < N / 2; j++) act_out[(size_t)m * (N / 2) + j] = ap[frag_idx(m, j, N / 2)];
     }
     return 0;
 }
@@ -178,7 +211,7 @@ int q3t_linear_case(int M, int m_begin, int N, int K, const uint16_t* W, int gat
     std::vector<uint16_t> xp((size_t)Mp * K, POISON16);
     if (pro == PRO_F16) {
         for (int m = 0; m < M; m++)
-            for (int k = 0; k < K; k++) xp[frag_idx_host(m, k, K)] = x16[(size_t)m * K + k];
+            for (int k = 0; k < K; k++) xp[frag_idx(m, k, K)] = x16[(size_t)m * K + k];
         if (!dx.up(xp.data(), xp.size() * 2)) return -1;
         a.x16 = (const half_t*)dx.p;
     } else {
@@ -194,8 +227,8 @@ int q3t_linear_case(int M, int m_begin, int N, int K, const uint16_t* W, int gat
         Q3_HIP(hipMemcpy(pro_ssq, dssq.p, (size_t)M * (K / 16) * 4, hipMemcpyDeviceToHost), -1);
         for (int m = 0; m < M; m++)
             for (int k = 0; k < K; k++) {
-                pro_h[(size_t)m * K + k] = hpz[frag_idx_host(m, k, K)];
-                pro_xh[(size_t)m * K + k] = xp[frag_idx_host(m, k, K)];
+                pro_h[(size_t)m * K + k] = hpz[frag_idx(m, k, K)];
+                pro_xh[(size_t)m * K + k] = xp[frag_idx(m, k, K)];
             }
         a.x16 = (const half_t*)dx.p;
         a.ssq = (const float*)dssq.p;
@@ -213,7 +246,7 @@ int q3t_linear_case(int M, int m_begin, int N, int K, const uint16_t* W, int gat
         hh.assign((size_t)Mp * N, GUARD32);
         hs.assign((size_t)Mp * (N / 16), GUARD32);
         for (int m = m_begin; m < M; m++)
-            for (int n = 0; n < N; n++) memcpy(&hh[frag_idx_host(m, n, N)], &h_io[(size_t)m * N + n], 4);
+            for (int n = 0; n < N; n++) memcpy(&hh[frag_idx(m, n, N)], &h_io[(size_t)m * N + n], 4);
         if (!dho.up(hh.data(), hh.size() * 4) || !dso.up(hs.data(), hs.size() * 4)) return -1;
         a.h_out = (float*)dho.p;
         a.ssq_out = (float*)dso.p;
@@ -251,7 +284,7 @@ int q3t_linear_case(int M, int m_begin, int N, int K, const uint16_t* W, int gat
         if (xh_out) Q3_HIP(hipMemcpy(hx.data(), dxo.p, hx.size() * 2, hipMemcpyDeviceToHost), -1);
         for (int m = 0; m < Mp; m++) {
             for (int n = 0; n < N; n++) {
-                const size_t fi = frag_idx_host(m, n, N);
+                const size_t fi = frag_idx(m, n, N);
                 if (inside(m)) {
                     memcpy(&h_io[(size_t)m * N + n], &hh[fi], 4);
                     if (xh_out) xh_out[(size_t)m * N + n] = hx[fi];
@@ -269,7 +302,7 @@ int q3t_linear_case(int M, int m_begin, int N, int K, const uint16_t* W, int gat
         Q3_HIP(hipMemcpy(ha.data(), dact.p, ha.size() * 2, hipMemcpyDeviceToHost), -1);
         for (int m = 0; m < Mp; m++)
             for (int j = 0; j < NA; j++) {
-                const uint16_t v = ha[frag_idx_host(m, j, NA)];
+                const uint16_t v = ha[frag_idx(m, j, NA)];
                 if (inside(m)) act[(size_t)m * NA + j] = v;
                 else if (v != GUARD16) outside++;
             }
@@ -332,7 +365,7 @@ int q3t_attn(int mode, int R, int row0, const float* qkv, const float* q_norm, c
     memcpy(hq.data() + (size_t)row0 * LD, qkv, (size_t)R * LD * 4);
     std::vector<uint16_t> ho((size_t)Rp * OW, GUARD);
     for (int r = row0; r < rows; r++)
-        for (int k = 0; k < OW; k++) ho[frag_idx_host(r, k, OW)] = out[(size_t)(r - row0) * OW + k];
+        for (int k = 0; k < OW; k++) ho[frag_idx(r, k, OW)] = out[(size_t)(r - row0) * OW + k];
     std::vector<int> hs((size_t)Rp, 0), hp((size_t)Rp, 0);
     for (int r = row0; r < rows; r++) {
         if (slot) hs[r] = slot[r - row0];
@@ -384,11 +417,11 @@ int q3t_attn(int mode, int R, int row0, const float* qkv, const float* q_norm, c
     Q3_HIP(hipMemcpy(vc, dvc.p, cache * 2, hipMemcpyDeviceToHost), -1);
     Q3_HIP(hipMemcpy(ho.data(), dout.p, ho.size() * 2, hipMemcpyDeviceToHost), -1);
     for (int r = row0; r < rows; r++)
-        for (int k = 0; k < OW; k++) out[(size_t)(r - row0) * OW + k] = ho[frag_idx_host(r, k, OW)];
+        for (int k = 0; k < OW; k++) out[(size_t)(r - row0) * OW + k] = ho[frag_idx(r, k, OW)];
     for (int r = 0; r < Rp; r++) {
         if (r >= row0 && r < rows) continue;
         for (int k = 0; k < OW; k++)
-            if (ho[frag_idx_host(r, k, OW)] != GUARD) return -3;
+            if (ho[frag_idx(r, k, OW)] != GUARD) return -3;
     }
     return 0;
 }
@@ -419,7 +452,7 @@ int q3t_voc_attn(int kernel, const float* x, float* y, int B, int H, int D, int 
     return 0;
 }
 
-// The cross-lane helpers of q3_kernels.hip (xlane_xor) against __shfl_xor, both applied to the same registers by one
+// The cross-lane helpers of q3_xlane.h (xlane_xor) against __shfl_xor, both applied to the same registers by one
 // kernel.  op 0: sum, 1: max, 2: the (value, index) arg-max exchange of block_argmax; width 4, 16 or 64 lanes; n values
 // (a multiple of 64).  out_new / out_shfl: n words each, for op 2 another n int32 words (the winning indices) behind them.
 int q3t_xlane_case(int op, int width, int n, const float* in, float* out_new, float* out_shfl) {
@@ -714,14 +747,14 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
     if (epilogue) {
         hh.assign((size_t)Rp * H, 0.f);
         for (int r = 0; r < R_total; r++)
-            for (int k = 0; k < H; k++) hh[frag_idx_host(r, k, H)] = h_out[(size_t)r * H + k];
+            for (int k = 0; k < H; k++) hh[frag_idx(r, k, H)] = h_out[(size_t)r * H + k];
         if (!dh.up(hh.data(), hh.size() * 4) || !dssq.up(ssq_out, rt * (H / 16) * 4)) return -1000;
         a.h_out = (float*)dh.p;
         a.ssq_out = (float*)dssq.p;
         if (xh_out) {
             hx.assign((size_t)Rp * H, 0);
             for (int r = 0; r < R_total; r++)
-                for (int k = 0; k < H; k++) hx[frag_idx_host(r, k, H)] = xh_out[(size_t)r * H + k];
+                for (int k = 0; k < H; k++) hx[frag_idx(r, k, H)] = xh_out[(size_t)r * H + k];
             if (!dxh.up(hx.data(), hx.size() * 2) || !dgam.up(gamma, (size_t)H * 4)) return -1000;
             a.xh_out = (half_t*)dxh.p;
             a.gamma_next = (const float*)dgam.p;
@@ -756,12 +789,12 @@ static int cp_sample_case(const float* logits, int V, int R_total, int row0, int
     if (epilogue) {
         Q3_HIP(hipMemcpy(hh.data(), dh.p, hh.size() * 4, hipMemcpyDeviceToHost), -1000);
         for (int r = 0; r < R_total; r++)
-            for (int k = 0; k < H; k++) h_out[(size_t)r * H + k] = hh[frag_idx_host(r, k, H)];
+            for (int k = 0; k < H; k++) h_out[(size_t)r * H + k] = hh[frag_idx(r, k, H)];
         Q3_HIP(hipMemcpy(ssq_out, dssq.p, rt * (H / 16) * 4, hipMemcpyDeviceToHost), -1000);
         if (xh_out) {
             Q3_HIP(hipMemcpy(hx.data(), dxh.p, hx.size() * 2, hipMemcpyDeviceToHost), -1000);
             for (int r = 0; r < R_total; r++)
-                for (int k = 0; k < H; k++) xh_out[(size_t)r * H + k] = hx[frag_idx_host(r, k, H)];
+                for (int k = 0; k < H; k++) xh_out[(size_t)r * H + k] = hx[frag_idx(r, k, H)];
         }
         if (a.qkv_out) Q3_HIP(hipMemcpy(qkv_out, dqo.p, rt * qkv_ld * 4, hipMemcpyDeviceToHost), -1000);
     }
@@ -1118,7 +1151,7 @@ struct RowOut {
     float* ph() { return h.empty() ? nullptr : (float*)dh.p; }
     float* ps() { return s.empty() ? nullptr : (float*)ds.p; }
     half_t* px() { return x.empty() ? nullptr : (half_t*)dx.p; }
-    size_t at(int r, int k) const { return frag ? frag_idx_host(r, k, H) : (size_t)r * H + k; }
+    size_t at(int r, int k) const { return frag ? frag_idx(r, k, H) : (size_t)r * H + k; }
     // Rows own(r) go to the host arrays (row-major, rows of the caller's own count); -> the number of words of every other
     // row that no longer hold their guard, or -1 on a HIP error.
     template <class F>
@@ -1133,10 +1166,10 @@ struct RowOut {
                 const size_t i = at(r, k);
                 if (mine) {
                     if (!h.empty()) memcpy(&h_out[(size_t)r * H + k], &h[i], 4);
-                    if (!x.empty()) xh_out[(size_t)r * H + k] = x[frag_idx_host(r, k, H)];
+                    if (!x.empty()) xh_out[(size_t)r * H + k] = x[frag_idx(r, k, H)];
                 } else {
                     if (!h.empty() && h[i] != ROW_GUARD32) outside++;
-                    if (!x.empty() && x[frag_idx_host(r, k, H)] != ROW_GUARD16) outside++;
+                    if (!x.empty() && x[frag_idx(r, k, H)] != ROW_GUARD16) outside++;
                 }
             }
             if (!s.empty())
@@ -1185,7 +1218,7 @@ extern "C" int q3t_final_norm_case(const float* h, const float* ssq, int rows, i
     const int Rp = (rows + 15) / 16 * 16;
     std::vector<float> hp((size_t)Rp * H, 3.0e4f), sp((size_t)Rp * parts, 1.0e9f);
     for (int r = 0; r < rows; r++) {
-        for (int k = 0; k < H; k++) hp[frag_idx_host(r, k, H)] = h[(size_t)r * H + k];
+        for (int k = 0; k < H; k++) hp[frag_idx(r, k, H)] = h[(size_t)r * H + k];
         memcpy(&sp[(size_t)r * parts], &ssq[(size_t)r * parts], (size_t)parts * 4);
     }
     DBuf dh, ds, dg, dmap, dcg;
@@ -1387,7 +1420,7 @@ extern "C" int q3t_prefix_move_case(uint16_t* kc, uint16_t* vc, int n_layers, in
     memcpy(hpool.data(), pool, np * 2);
     std::vector<uint32_t> hh((size_t)Rp * H, ROW_GUARD32), hs((size_t)Rp * parts, ROW_GUARD32);
     for (int r = 0; r < h_rows; r++) {
-        for (int k = 0; k < H; k++) memcpy(&hh[frag_idx_host(r, k, H)], &h[(size_t)r * H + k], 4);
+        for (int k = 0; k < H; k++) memcpy(&hh[frag_idx(r, k, H)], &h[(size_t)r * H + k], 4);
         memcpy(&hs[(size_t)r * parts], &ssq[(size_t)r * parts], (size_t)parts * 4);
     }
     const size_t nst = (size_t)n_entries * (H + parts);
@@ -1428,7 +1461,7 @@ extern "C" int q3t_prefix_move_case(uint16_t* kc, uint16_t* vc, int n_layers, in
     for (size_t i = 0; i < TAIL; i++) outside += (hk[nc + i] != ROW_GUARD16) + (hv[nc + i] != ROW_GUARD16) + (hpool[np + i] != ROW_GUARD16);
     for (int r = 0; r < Rp; r++) {
         for (int k = 0; k < H; k++) {
-            const uint32_t v = hh[frag_idx_host(r, k, H)];
+            const uint32_t v = hh[frag_idx(r, k, H)];
             if (r < h_rows) memcpy(&h[(size_t)r * H + k], &v, 4);
             else outside += v != ROW_GUARD32;
         }

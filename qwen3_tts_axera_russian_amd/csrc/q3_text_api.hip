@@ -11,10 +11,6 @@ namespace {
 
 typedef _Float16 h8v __attribute__((ext_vector_type(8)));
 
-__device__ __forceinline__ size_t fidx(int m, int k, int K) {   // frag_idx of q3_kernels.hip
-    return ((((size_t)(m >> 4) * (K >> 5) + (k >> 5)) * 64 + (m & 15) + 16 * ((k >> 3) & 3)) << 3) + (k & 7);
-}
-
 // row r of the GEMM input (fp16, fragment order) = text table row ids[r]; an id outside the table gives zeros
 __global__ void __launch_bounds__(256) text_gather_kernel(const half_t* __restrict__ table, int V, int TD,
                                                           const int* __restrict__ ids, half_t* __restrict__ x16) {
@@ -22,13 +18,13 @@ __global__ void __launch_bounds__(256) text_gather_kernel(const half_t* __restri
     for (int k8 = threadIdx.x; k8 < TD / 8; k8 += 256) {
         h8v v = {0, 0, 0, 0, 0, 0, 0, 0};
         if (t >= 0 && t < V) v = *(const h8v*)(table + (size_t)t * TD + k8 * 8);
-        *(h8v*)(x16 + fidx(r, k8 * 8, TD)) = v;
+        *(h8v*)(x16 + frag_idx(r, k8 * 8, TD)) = v;
     }
 }
 // accumulator seed of a biased linear layer: h[r][n] = bias[n] (f32, fragment order)
 __global__ void __launch_bounds__(256) bias_rows_kernel(const float* __restrict__ bias, int N, float* __restrict__ h) {
     const int r = blockIdx.x;
-    for (int n4 = threadIdx.x; n4 < N / 4; n4 += 256) *(float4*)(h + fidx(r, n4 * 4, N)) = *(const float4*)(bias + n4 * 4);
+    for (int n4 = threadIdx.x; n4 < N / 4; n4 += 256) *(float4*)(h + frag_idx(r, n4 * 4, N)) = *(const float4*)(bias + n4 * 4);
 }
 // x16 = fp16(silu(h)), same (fragment) order on both sides
 __global__ void __launch_bounds__(256) silu_f16_kernel(const float* __restrict__ h, half_t* __restrict__ x16, size_t n) {
@@ -45,7 +41,7 @@ __global__ void __launch_bounds__(256) prefix_rows_kernel(const float* __restric
                                                           int codec_vocab, float* __restrict__ out) {
     const int j = blockIdx.x, s = src[j], c = cod[j];
     for (int k4 = threadIdx.x; k4 < H / 4; k4 += 256) {
-        float4 v = *(const float4*)(proj + fidx(s, k4 * 4, H));
+        float4 v = *(const float4*)(proj + frag_idx(s, k4 * 4, H));
         if (c >= 0 && c < codec_vocab) {
             const float4 e = *(const float4*)(codec + (size_t)c * H + k4 * 4);
             v.x += e.x;

@@ -1,5 +1,5 @@
-// q3_xlane.h -- the cross-lane exchange helpers and the butterflies built on them (device code; q3_kernels.hip's reductions
-// and the speaker encoder's, q3_spk.hip).
+// q3_xlane.h -- the cross-lane exchange helpers and the butterflies built on them (device code; the reductions of
+// q3_linear.hip, q3_attn.hip, q3_sample.hip, q3_rows.hip and the speaker encoder's, q3_spk.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,7 +1,7 @@
 // engine_host_text_prompt_driver.cpp -- the slot book (csrc/q3_engine_host.h) for text slots that continue a codec prompt,
 // beside the DEVICE's rule for the same slots, for tests/test_engine_host_text_prompt.py.  tests/engine_host_driver.cpp's
 // slot events, with the prompt's length at admit; every step of `run` is also taken by a stand-in for the sampler's
-// counters (talker_sample_row<true> of csrc/q3_kernels.hip, as its contract in csrc/q3_kernels.h words it): n_past starts
+// counters (talker_sample_row<true> of csrc/q3_sample.hip, as its contract in csrc/q3_kernels.h words it): n_past starts
 // at the prompt's length, the budget the device sees is prompt + budget, and a row is held when it is a text slot before
 // its final push, has not ended, n_past < its budget and g = n_past - prompt satisfies g >= 1 and g >= the rows pushed.
 //

@@ -1,7 +1,7 @@
 """Plain-numpy reference of every device sampling decision -- TEST INFRASTRUCTURE ONLY.
 
 Written from the contracts (the comments above block_sample_topk, TalkerSampleArgs, CpArgmaxArgs and SlotParams in
-csrc/q3_kernels.{h,hip}; oracle/frontend.py's restatement of the reference servers), not from the kernels' code.
+csrc/q3_kernels.h and csrc/q3_sample.hip; oracle/frontend.py's restatement of the reference servers), not from the kernels' code.
 
 The draw is a counter-based integer hash and a decision is a pure function of (logits, state, parameters, u), so the
 device is graded exactly: processed logits, state and gathered rows bit for bit; a stochastic pick against the SET of

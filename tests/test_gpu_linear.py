@@ -2,7 +2,7 @@
 (tests/linear_ref.py), one launch at a time through the hook q3t_linear_case (csrc/q3_test_api.hip).
 
 Coverage is part of the assertion: VARIANTS below is the literal list of instantiations (a CPU test compares it with the
-Q3_LIN_MT lines and the launch_linear_narrow_t / launch_gemm_t calls of csrc/q3_kernels.hip), every GPU case asserts the
+Q3_LIN_MT lines and the launch_linear_narrow_t / launch_gemm_t calls of csrc/q3_linear.hip), every GPU case asserts the
 name launch_linear reports for the kernel it picked, and a final check asserts that every entry was observed.
 
 Tolerances are derived, never tuned.  fp16 x fp16 products are exact in f32, so against the float64 product of the fp16
@@ -34,7 +34,7 @@ from tests import linear_ref as L
 
 gpu = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = os.path.join(ROOT, "qwen3_tts_axera_russian_amd", "csrc", "q3_kernels.hip")
+KERNELS = os.path.join(ROOT, "qwen3_tts_axera_russian_amd", "csrc", "q3_linear.hip")
 PRO = {"F16": 0, "NORM": 1}
 EPI = {"STORE": 0, "RESID": 1, "SWIGLU": 2}
 U = L.U24

@@ -1,4 +1,4 @@
-"""The register-file cross-lane exchanges of csrc/q3_kernels.hip (xlane_xor: DPP inside a row of 16 lanes, permlane swaps
+"""The register-file cross-lane exchanges of csrc/q3_xlane.h (xlane_xor: DPP inside a row of 16 lanes, permlane swaps
 across rows) against __shfl_xor, and the attention kernels built on them at the shapes where an exchange inside the
 per-group branches of the softmax walk could go wrong (groups with no key, one group's worth, the prefetch edge).
 

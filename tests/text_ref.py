@@ -42,7 +42,7 @@ SPECIAL_KEYS = ("im_start", "assistant", "newline", "tts_pad", "tts_bos", "tts_e
 
 # ------------------------------------------------------------------------------------------------------------------------
 # fragment order (csrc/q3_kernels.h "A operands are stored in MFMA fragment order"; the layout is spelled out above frag_idx in
-# q3_kernels.hip): 16-row x 32-k blocks, row blocks outermost; inside a block lane (m % 16) + 16 * ((k % 32) / 8) owns 8
+# q3_frag.h): 16-row x 32-k blocks, row blocks outermost; inside a block lane (m % 16) + 16 * ((k % 32) / 8) owns 8
 # consecutive k.  Written from that text, not from the C expression.
 # ------------------------------------------------------------------------------------------------------------------------
 def frag_index(m, k, K):
