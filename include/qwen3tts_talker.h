@@ -17,8 +17,13 @@
  * see DESIGN.md), or -- parsed natively, no Python -- the safetensors file the
  * reference's own converter writes before its GGUF step (re-keyed Qwen3 talker,
  * scripts/extract_talker_as_qwen3.py:53-71), or the HF snapshot's
- * model.safetensors / its directory; not a GGUF.  There is no CPU fallback: if no HIP device is
- * usable, wrapper_load_model returns NULL after printing the reason.
+ * model.safetensors / its directory, or the GGUF the reference's server is
+ * started with (llamacpp_talker_server.py:379; v2 / v3, F32 / F16 / BF16 /
+ * Q4_0 / Q8_0 / Q4_K / Q5_K / Q6_K: a Q4_K_M or Q5_K_M file as deployed), or a
+ * directory holding exactly that one .gguf.  Quantised blocks are dequantised
+ * on the GPU at load into the same fp16 weights; nothing stays quantised.
+ * There is no CPU fallback: if no HIP device is usable, wrapper_load_model
+ * returns NULL after printing the reason.
  */
 #ifndef QWEN3TTS_TALKER_H
 #define QWEN3TTS_TALKER_H
@@ -74,6 +79,12 @@ int wrapper_decode_embd(void* ctx, const float* embd, int n_tokens, int n_embd,
 /* ---- extensions (not in the reference; seq_id is hard-wired to 0 there,
  * llama_wrapper.c:139-141) ------------------------------------------------ */
 
+/* wrapper_load_model with the server's --embeddings_dir: codec_embedding.npy /
+ * codec_head.npy found there are used in place of the tables inside `path`
+ * (the exact tables instead of a GGUF's quantised token_embd / output, as the
+ * reference applies codec_head.npy in Python: llamacpp_talker_server.py:79-93).
+ * embeddings_dir == NULL: wrapper_load_model. */
+void* wrapper_load_model_aux(const char* path, const char* embeddings_dir, int n_gpu_layers);
 /* Number of independent sequences (KV slots) a context was created with. */
 int wrapper_ctx_n_slots(void* ctx);
 /* Re-create semantics: like wrapper_create_context but with n_slots sequences. */

@@ -21,7 +21,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib")
-SOURCES = ["q3_common.cpp", "q3_formats.cpp", "q3_linear.hip", "q3_attn.hip", "q3_sample.hip", "q3_rows.hip", "q3_timeline.hip", "q3_model.hip", "q3_talker_api.hip", "q3_cp_api.hip",
+SOURCES = ["q3_common.cpp", "q3_formats.cpp", "q3_linear.hip", "q3_attn.hip", "q3_sample.hip", "q3_rows.hip", "q3_timeline.hip", "q3_model.hip", "q3_dequant.hip", "q3_talker_api.hip", "q3_cp_api.hip",
            "q3_engine.hip", "q3_voc_kernels.hip", "q3_voc.hip", "q3_voc_stream.hip", "q3_enc.hip", "q3_enc_pcm.hip", "q3_enc_stream.hip",
            "q3_enc_stream_pcm.hip", "q3_spk.hip", "q3_text_api.hip"]
 TEST_SOURCES = ["q3_test_api.hip"]

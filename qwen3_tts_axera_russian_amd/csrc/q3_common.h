@@ -33,7 +33,20 @@ typedef _Float16 half_t;
 // ---------------------------------------------------------------------------
 // Q3TTSW1 container (written by weights.py)
 // ---------------------------------------------------------------------------
-enum DType : uint32_t { F32 = 0, F16 = 1, I32 = 2, I64 = 3, BF16 = 4 };   // BF16: safetensors only (q3_formats.cpp)
+enum DType : uint32_t {
+    F32 = 0, F16 = 1, I32 = 2, I64 = 3,
+    BF16 = 4,                                           // safetensors and GGUF only (q3_formats.cpp)
+    Q4_0 = 5, Q8_0 = 6, Q4_K = 7, Q5_K = 8, Q6_K = 9    // ggml block types, GGUF only: raw blocks, dequantised on the GPU at load
+};
+// Elements and bytes of one block of a dtype (1 element for the plain types); {0, 0} for an unknown dtype.
+struct BlockGeom {
+    uint32_t elems, bytes;
+};
+inline BlockGeom block_geom(uint32_t dtype) {
+    static const BlockGeom g[10] = {{1, 4}, {1, 2}, {1, 4}, {1, 8}, {1, 2}, {32, 18}, {32, 34}, {256, 144}, {256, 176}, {256, 210}};
+    return dtype < 10 ? g[dtype] : BlockGeom{0, 0};
+}
+inline bool is_block_dtype(uint32_t dtype) { return dtype >= Q4_0 && dtype <= Q6_K; }
 
 struct PackTensor {
     std::string name;
@@ -45,6 +58,11 @@ struct PackTensor {
         uint64_t n = 1;
         for (uint32_t i = 0; i < ndim; i++) n *= shape[i];
         return n;
+    }
+    // bytes of one row (the innermost dimension) of a validated tensor; a block type's K is a multiple of its block
+    uint64_t row_bytes() const {
+        const BlockGeom g = block_geom(dtype);
+        return ndim && g.elems ? shape[ndim - 1] / g.elems * g.bytes : 0;
     }
     // The same for a shape that has not been validated yet (a file's): false when the product does not fit 64 bits.
     bool numel_checked(uint64_t* out) const {
@@ -69,18 +87,20 @@ struct Pack {
     int fd = -1;
 
     bool open(const char* path);
-    // the reference's deployed files instead of a container (q3_formats.cpp): .npy / .npz / .safetensors
+    // the reference's deployed files instead of a container (q3_formats.cpp): .npy / .npz / .safetensors / .gguf
     // parsed natively, names mapped to the container's; `aux_dir` = the servers' --embeddings_dir
     bool open_auto(const char* path, const char* aux_dir = nullptr);
     bool add_npy(const char* path, const std::string& name);
     bool add_npz(const char* path, std::string (*rename)(const std::string&));
     bool add_safetensors(const char* path, std::string (*rename)(const std::string&));
+    bool add_gguf(const char* path, std::string (*rename)(const std::string&));   // the talker's GGUF (v2 / v3, little-endian)
     // The parsers proper: everything above maps its file and calls one of these on the mapping.  They read nothing outside
     // [p, p + n), refuse (false, with a Q3_LOG line) what does not fit there, and let no exception out.  Tensors point into
     // [p, p + n) or into `owned`, so the bytes must outlive the Pack's use.
     bool add_npy_bytes(const uint8_t* p, size_t n, const std::string& name, const char* what);
     bool add_npz_bytes(const uint8_t* p, size_t n, const char* what, std::string (*rename)(const std::string&));
     bool add_safetensors_bytes(const uint8_t* p, size_t n, const char* what, std::string (*rename)(const std::string&));
+    bool add_gguf_bytes(const uint8_t* p, size_t n, const char* what, std::string (*rename)(const std::string&));
     bool open_bytes(const uint8_t* p, size_t n, const char* what);   // a Q3TTSW1 container
     const uint8_t* map_file(const char* path, size_t* size);
     std::vector<std::pair<uint8_t*, size_t>> extra_maps;   // files mapped by the add_* readers
@@ -99,6 +119,7 @@ struct Pack {
 
 std::string map_cp_npz_key(const std::string& k);
 std::string map_safetensors_key(const std::string& k);
+std::string map_gguf_key(const std::string& k);   // llama.cpp's qwen3 tensor names
 
 inline float bf16_to_f32(uint16_t b) {
     uint32_t u = (uint32_t)b << 16;

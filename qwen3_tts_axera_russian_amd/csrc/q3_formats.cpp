@@ -5,12 +5,15 @@
 //   .npz  zip of .npy members, stored (np.savez: scripts/export_code_predictor_weights.py:76) or deflated
 //         (np.savez_compressed: scripts/extract_embeddings.py:93), zip64 extras tolerated
 //   .safetensors  8-byte header length + JSON table + raw tensors (F32 / F16 / BF16), zero-copy from the mapping
+//   .gguf  v2 / v3 little-endian: the talker file the reference's server is started with (llamacpp_talker_server.py:379);
+//         F32 / F16 / BF16 and the raw blocks of Q4_0 / Q8_0 / Q4_K / Q5_K / Q6_K, zero-copy (dequantised on the GPU at load)
 // and the key maps from the reference's names to the container names (weights.py):
 //   code_predictor_weights.npz   layer_{i}_{part}, final_norm, codec_emb_{g}, lm_head_{g}
 //                                (scripts/export_code_predictor_weights.py:51-74)
 //   model.safetensors            HF keys talker.model.layers.*, talker.code_predictor.* (scripts/extract_embeddings.py:47-98)
 //                                or the re-keyed Qwen3 talker model.layers.* (scripts/extract_talker_as_qwen3.py:53-71)
 //   embeddings/*.npy             codec_embedding.npy, codec_head.npy (scripts/extract_embeddings.py:62-72)
+//   *.gguf                       llama.cpp's qwen3 names blk.{i}.attn_q.weight, token_embd.weight, ... (map_gguf_key)
 #include "q3_common.h"
 
 #include <exception>
@@ -612,8 +615,335 @@ bool Pack::add_safetensors_bytes(const uint8_t* p, size_t n, const char* path, s
     return false;
 }
 
+// ---- GGUF (v2 / v3, little-endian): the talker file the reference's server is started with ----------------------
+// llama.cpp's qwen3 tensor names -> container names.  Q and K are taken as stored: the converter does not permute them for
+// qwen3 (NEOX rope = the rotate-half pairing of DESIGN.md 2).
+std::string map_gguf_key(const std::string& k) {
+    static const char* const kGgufParts[11] = {"attn_norm", "attn_q", "attn_k", "attn_v", "attn_output", "attn_q_norm",
+                                               "attn_k_norm", "ffn_norm", "ffn_gate", "ffn_up", "ffn_down"};
+    if (k == "output_norm.weight") return "talker.norm";
+    if (k == "token_embd.weight") return "talker.codec_embedding";
+    if (k == "output.weight") return "talker.codec_head";
+    if (k.compare(0, 4, "blk.") != 0) return "";
+    size_t nx = 4;
+    while (nx < k.size() && k[nx] >= '0' && k[nx] <= '9') nx++;
+    if (nx == 4 || nx - 4 > 6 || nx >= k.size() || k[nx] != '.') return "";   // (a layer number of <= 6 digits: no overflow)
+    const int i = atoi(k.c_str() + 4);
+    const std::string rest = k.substr(nx + 1);
+    for (int p = 0; p < 11; p++)
+        if (rest == std::string(kGgufParts[p]) + ".weight") return "talker.layers." + std::to_string(i) + "." + kLayerParts[p];
+    return "";
+}
+
+namespace {
+
+// A cursor over [p, p + n): every read says whether its bytes were there.
+struct GgufCursor {
+    const uint8_t* p;
+    size_t n, o = 0;
+    bool have(uint64_t k) const { return k <= n - o; }   // o <= n always
+    template <class T>
+    bool get(T* v) {
+        if (!have(sizeof(T))) return false;
+        memcpy(v, p + o, sizeof(T));
+        o += sizeof(T);
+        return true;
+    }
+    bool str(std::string* s) {   // u64 length + bytes
+        uint64_t len;
+        if (!get(&len) || !have(len)) return false;
+        if (s) s->assign((const char*)p + o, (size_t)len);
+        o += (size_t)len;
+        return true;
+    }
+};
+
+// size of a scalar GGUF value type, 0 for string / array / unknown
+size_t gguf_scalar_size(uint32_t t) {
+    static const size_t sz[13] = {1, 1, 2, 2, 4, 4, 4, 1, 0, 0, 8, 8, 8};
+    return t < 13 ? sz[t] : 0;
+}
+
+// a scalar value as a double (exact for everything this reader looks at); false when its bytes are not there
+bool gguf_scalar(GgufCursor& c, uint32_t t, double* out) {
+    switch (t) {
+        case 0: { uint8_t v; if (!c.get(&v)) return false; *out = v; return true; }
+        case 1: { int8_t v; if (!c.get(&v)) return false; *out = v; return true; }
+        case 2: { uint16_t v; if (!c.get(&v)) return false; *out = v; return true; }
+        case 3: { int16_t v; if (!c.get(&v)) return false; *out = v; return true; }
+        case 4: { uint32_t v; if (!c.get(&v)) return false; *out = v; return true; }
+        case 5: { int32_t v; if (!c.get(&v)) return false; *out = v; return true; }
+        case 6: { float v; if (!c.get(&v)) return false; *out = v; return true; }
+        case 7: { uint8_t v; if (!c.get(&v)) return false; *out = v != 0; return true; }
+        case 10: { uint64_t v; if (!c.get(&v)) return false; *out = (double)v; return true; }
+        case 11: { int64_t v; if (!c.get(&v)) return false; *out = (double)v; return true; }
+        case 12: { double v; if (!c.get(&v)) return false; *out = v; return true; }
+    }
+    return false;
+}
+
+const char* ggml_type_name(uint32_t t) {
+    static const char* const names[40] = {"F32", "F16", "Q4_0", "Q4_1", "(removed Q4_2)", "(removed Q4_3)", "Q5_0", "Q5_1", "Q8_0", "Q8_1",
+                                          "Q2_K", "Q3_K", "Q4_K", "Q5_K", "Q6_K", "Q8_K", "IQ2_XXS", "IQ2_XS", "IQ3_XXS", "IQ1_S",
+                                          "IQ4_NL", "IQ3_S", "IQ2_S", "IQ4_XS", "I8", "I16", "I32", "I64", "F64", "IQ1_M",
+                                          "BF16", "(removed Q4_0_4_4)", "(removed Q4_0_4_8)", "(removed Q4_0_8_8)", "TQ1_0", "TQ2_0",
+                                          "(removed IQ4_NL_4_4)", "(removed IQ4_NL_4_8)", "(removed IQ4_NL_8_8)", "MXFP4"};
+    return t < 40 ? names[t] : "unknown";
+}
+
+// ggml type -> DType, or -1
+int ggml_to_dtype(uint32_t t) {
+    switch (t) {
+        case 0: return F32;
+        case 1: return F16;
+        case 30: return BF16;
+        case 2: return Q4_0;
+        case 8: return Q8_0;
+        case 12: return Q4_K;
+        case 13: return Q5_K;
+        case 14: return Q6_K;
+    }
+    return -1;
+}
+
+}  // namespace
+
+bool Pack::add_gguf(const char* path, std::string (*rename)(const std::string&)) {
+    size_t n = 0;
+    const uint8_t* p = map_file(path, &n);
+    if (!p) {
+        Q3_LOG("cannot open %s", path);
+        return false;
+    }
+    return add_gguf_bytes(p, n, path, rename);
+}
+
+bool Pack::add_gguf_bytes(const uint8_t* p, size_t n, const char* path, std::string (*rename)(const std::string&)) try {
+    GgufCursor c{p, n};
+    uint32_t magic = 0, version = 0;
+    uint64_t n_tensors = 0, n_kv = 0;
+    if (!c.get(&magic) || memcmp(&magic, "GGUF", 4) != 0) {
+        Q3_LOG("%s: not a GGUF file (bad magic)", path);
+        return false;
+    }
+    if (!c.get(&version) || (version != 2 && version != 3)) {
+        Q3_LOG("%s: GGUF version %u is not supported (2 and 3, little-endian, are)", path, version);
+        return false;
+    }
+    if (!c.get(&n_tensors) || !c.get(&n_kv)) {
+        Q3_LOG("%s: truncated GGUF header", path);
+        return false;
+    }
+    // every KV takes >= 12 bytes and every tensor info >= 28: counts the file cannot hold are refused before any loop
+    if (n_kv > (n - c.o) / 12 || n_tensors > (n - c.o) / 28) {
+        Q3_LOG("%s: GGUF header claims %llu key/value pairs and %llu tensors, more than the file can hold", path,
+               (unsigned long long)n_kv, (unsigned long long)n_tensors);
+        return false;
+    }
+    // the keys read: "<arch>.<suffix>" -> the container's meta key
+    static const char* const kMetaKeys[8][2] = {{"qwen3.block_count", "talker_layers"},
+                                                {"qwen3.embedding_length", "hidden"},
+                                                {"qwen3.feed_forward_length", "talker_ffn"},
+                                                {"qwen3.attention.head_count", "n_heads"},
+                                                {"qwen3.attention.head_count_kv", "n_kv_heads"},
+                                                {"qwen3.attention.layer_norm_rms_epsilon", "rms_eps"},
+                                                {"qwen3.rope.freq_base", "rope_theta"},
+                                                {"qwen3.attention.key_length", "head_dim"}};
+    std::map<std::string, double> found;
+    double alignment = 32;
+    bool have_arch = false;
+    for (uint64_t i = 0; i < n_kv; i++) {
+        std::string key;
+        uint32_t type;
+        if (!c.str(&key) || !c.get(&type)) {
+            Q3_LOG("%s: GGUF key/value %llu runs past the end of the file", path, (unsigned long long)i);
+            return false;
+        }
+        bool ok = true;
+        if (type == 8) {
+            std::string v;
+            ok = c.str(&v);
+            if (ok && key == "general.architecture") {
+                have_arch = true;
+                if (v != "qwen3") {
+                    Q3_LOG("%s: general.architecture is \"%.40s\"; this library reads the qwen3 talker only", path, v.c_str());
+                    return false;
+                }
+            }
+        } else if (type == 9) {   // arrays (the tokenizer's) are stepped over, inside the file
+            uint32_t et;
+            uint64_t cnt;
+            ok = c.get(&et) && c.get(&cnt);
+            if (ok && et == 9) {
+                Q3_LOG("%s: GGUF key %.60s is an array of arrays (not supported)", path, key.c_str());
+                return false;
+            }
+            if (ok && et == 8) {
+                for (uint64_t e = 0; e < cnt && ok; e++) ok = c.str(nullptr);   // >= 8 bytes each: this ends
+            } else if (ok) {
+                const size_t es = gguf_scalar_size(et);
+                if (!es) {
+                    Q3_LOG("%s: GGUF key %.60s has element type %u (unknown)", path, key.c_str(), et);
+                    return false;
+                }
+                ok = cnt <= (n - c.o) / es;
+                if (ok) c.o += (size_t)cnt * es;
+            }
+        } else {
+            double v;
+            if (!gguf_scalar_size(type)) {
+                Q3_LOG("%s: GGUF key %.60s has value type %u (unknown)", path, key.c_str(), type);
+                return false;
+            }
+            ok = gguf_scalar(c, type, &v);
+            if (ok && key == "general.alignment") alignment = v;
+            for (const auto& mk : kMetaKeys)
+                if (ok && key == mk[0]) found[mk[1]] = v;
+        }
+        if (!ok) {
+            Q3_LOG("%s: the value of GGUF key %.60s runs past the end of the file", path, key.c_str());
+            return false;
+        }
+    }
+    if (!have_arch) {
+        Q3_LOG("%s: GGUF lacks general.architecture (qwen3 is read)", path);
+        return false;
+    }
+    if (!(alignment >= 8 && alignment <= 1048576) || alignment != (double)(uint64_t)alignment ||
+        ((uint64_t)alignment & ((uint64_t)alignment - 1))) {
+        Q3_LOG("%s: general.alignment %g is not a power of two >= 8", path, alignment);
+        return false;
+    }
+    const uint64_t align = (uint64_t)alignment;
+    // what the kernels are built for (ModelCfg): other values are an unsupported model, like any unsupported geometry
+    if (found.count("rope_theta") && found["rope_theta"] != 1e6) {
+        Q3_LOG("%s: qwen3.rope.freq_base %g is not the 1e6 this build's RoPE tables are made for", path, found["rope_theta"]);
+        return false;
+    }
+    if (found.count("rms_eps") && (float)found["rms_eps"] != 1e-6f) {
+        Q3_LOG("%s: qwen3.attention.layer_norm_rms_epsilon %g is not the 1e-6 this build computes with", path, found["rms_eps"]);
+        return false;
+    }
+    struct Info {
+        std::string raw;
+        uint32_t ggml = 0;
+        PackTensor t;
+    };
+    std::vector<Info> infos;
+    std::map<std::string, int> seen;
+    for (uint64_t i = 0; i < n_tensors; i++) {
+        Info in;
+        uint32_t nd, type;
+        uint64_t ne[4] = {1, 1, 1, 1};
+        if (!c.str(&in.raw) || !c.get(&nd)) {
+            Q3_LOG("%s: GGUF tensor info %llu runs past the end of the file", path, (unsigned long long)i);
+            return false;
+        }
+        if (nd < 1 || nd > 4) {
+            Q3_LOG("%s: tensor %.80s has %u dimensions (1..4 are read)", path, in.raw.c_str(), nd);
+            return false;
+        }
+        bool ok = true;
+        for (uint32_t d = 0; d < nd && ok; d++) ok = c.get(&ne[d]);
+        ok = ok && c.get(&type) && c.get(&in.t.offset);
+        if (!ok) {
+            Q3_LOG("%s: GGUF tensor info of %.80s runs past the end of the file", path, in.raw.c_str());
+            return false;
+        }
+        if (seen[in.raw]++) {
+            Q3_LOG("%s: tensor %.80s appears twice", path, in.raw.c_str());
+            return false;
+        }
+        const int dt = ggml_to_dtype(type);
+        if (dt < 0) {
+            Q3_LOG("%s: tensor %.80s has ggml type %u (%s); F32, F16, BF16, Q4_0, Q8_0, Q4_K, Q5_K, Q6_K are read", path,
+                   in.raw.c_str(), type, ggml_type_name(type));
+            return false;
+        }
+        in.ggml = type;
+        in.t.dtype = (uint32_t)dt;
+        in.t.ndim = nd;
+        for (uint32_t d = 0; d < nd; d++) in.t.shape[d] = ne[nd - 1 - d];   // ne[0] is the innermost: row-major order
+        const BlockGeom g = block_geom(in.t.dtype);
+        uint64_t numel;
+        if (!in.t.numel_checked(&numel) || ne[0] % g.elems ||
+            __builtin_mul_overflow(numel / g.elems, (uint64_t)g.bytes, &in.t.nbytes)) {
+            Q3_LOG("%s: tensor %.80s: its dimensions overflow, or the row length %llu is no multiple of the %u-element block", path,
+                   in.raw.c_str(), (unsigned long long)ne[0], g.elems);
+            return false;
+        }
+        if (in.t.offset % align) {
+            Q3_LOG("%s: tensor %.80s: offset %llu is not aligned to %llu", path, in.raw.c_str(), (unsigned long long)in.t.offset,
+                   (unsigned long long)align);
+            return false;
+        }
+        infos.push_back(std::move(in));
+    }
+    const uint64_t data0 = (c.o + align - 1) / align * align;   // c.o <= n and align <= 2^20: no wrap
+    int added = 0;
+    for (Info& in : infos) {
+        PackTensor& t = in.t;
+        if (data0 > n || t.offset > n - data0 || t.nbytes > n - data0 - t.offset) {
+            Q3_LOG("%s: tensor %.80s runs past the end of the file", path, in.raw.c_str());
+            return false;
+        }
+        const std::string name = rename(in.raw);
+        if (name.empty()) continue;
+        if (is_block_dtype(t.dtype) && t.ndim != 2) {
+            Q3_LOG("%s: tensor %.80s is %s with %u dimensions (a quantised tensor of this model is a matrix)", path, in.raw.c_str(),
+                   ggml_type_name(in.ggml), t.ndim);
+            return false;
+        }
+        t.name = name;
+        t.data = p + data0 + t.offset;
+        t.offset += data0;
+        tensors[name] = t;
+        added++;
+    }
+    if (!added) {
+        Q3_LOG("%s: no tensor of the qwen3 talker in this GGUF", path);
+        return false;
+    }
+    // tied embeddings: no output.weight -> the head is token_embd
+    if (!tensors.count("talker.codec_head") && tensors.count("talker.codec_embedding")) {
+        PackTensor t = tensors["talker.codec_embedding"];
+        t.name = "talker.codec_head";
+        tensors[t.name] = t;
+    }
+    // geometry comes from the tensors; metadata that contradicts them is a damaged or foreign file
+    auto dim = [&](const char* nm, uint32_t d) -> double {
+        const PackTensor* t = find(nm);
+        return t && d < t->ndim ? (double)t->shape[d] : -1;
+    };
+    int layers = 0;
+    while (tensors.count("talker.layers." + std::to_string(layers) + ".q_proj")) layers++;
+    const double hd = found.count("head_dim") ? found["head_dim"] : -1;
+    const struct {
+        const char* key;
+        double have;
+        bool comparable;
+    } checks[] = {{"talker_layers", (double)layers, layers > 0},
+                  {"hidden", dim("talker.layers.0.q_proj", 1), dim("talker.layers.0.q_proj", 1) >= 0},
+                  {"talker_ffn", dim("talker.layers.0.gate_proj", 0), dim("talker.layers.0.gate_proj", 0) >= 0},
+                  {"head_dim", dim("talker.layers.0.q_norm", 0), dim("talker.layers.0.q_norm", 0) >= 0},
+                  {"n_heads", hd > 0 ? dim("talker.layers.0.q_proj", 0) / hd : -1, hd > 0 && dim("talker.layers.0.q_proj", 0) >= 0},
+                  {"n_kv_heads", hd > 0 ? dim("talker.layers.0.k_proj", 0) / hd : -1, hd > 0 && dim("talker.layers.0.k_proj", 0) >= 0}};
+    for (const auto& ck : checks)
+        if (ck.comparable && found.count(ck.key) && found[ck.key] != ck.have) {
+            Q3_LOG("%s: GGUF metadata says %s = %g, the tensors say %g", path, ck.key, found[ck.key], ck.have);
+            return false;
+        }
+    for (const auto& kv : found) meta[kv.first] = kv.second;
+    meta["gguf_version"] = version;
+    meta["gguf_alignment"] = alignment;
+    return true;
+} catch (const std::exception& e) {
+    Q3_LOG("%s: %s", path, e.what());
+    return false;
+}
+
 // A Q3TTSW1 container, or the reference's deployed files: `path` may be a container file, a
-// .safetensors / .npz / file, or a directory holding model.safetensors and/or
+// .safetensors / .npz / .gguf file, or a directory holding model.safetensors (or, without one, exactly one *.gguf) and/or
 // code_predictor_weights.npz; `aux_dir` (the servers' --embeddings_dir) adds codec_embedding.npy /
 // codec_head.npy and the text front-end's text_embedding / text_projection_* files.  Geometry (layer counts, vocabularies) is taken from what was found.
 bool Pack::open_auto(const char* path, const char* aux_dir) {
@@ -631,32 +961,77 @@ bool Pack::open_auto(const char* path, const char* aux_dir) {
         Q3_LOG("cannot open %s", path ? path : "(null)");
         return false;
     }
+    bool from_gguf = false;   // the talker's tables came out of a GGUF: quantised copies, which exact .npy tables replace
     auto try_file = [&](const std::string& f) -> int {   // 1 added, 0 absent, -1 error
         struct stat s2;
         if (stat(f.c_str(), &s2) != 0 || !S_ISREG(s2.st_mode)) return 0;
         if (ends_with(f, ".safetensors")) return add_safetensors(f.c_str(), map_safetensors_key) ? 1 : -1;
         if (ends_with(f, ".npz")) return add_npz(f.c_str(), map_cp_npz_key) ? 1 : -1;
+        if (ends_with(f, ".gguf")) {
+            from_gguf = true;
+            return add_gguf(f.c_str(), map_gguf_key) ? 1 : -1;
+        }
         return 0;
     };
     auto try_npy = [&](const std::string& dir, const char* file, const char* name) -> int {
         const std::string f = dir + "/" + file;
         struct stat s2;
-        if (tensors.count(name) || stat(f.c_str(), &s2) != 0) return 0;
+        const bool over_gguf = from_gguf && (!strcmp(name, "talker.codec_embedding") || !strcmp(name, "talker.codec_head"));
+        if ((tensors.count(name) && !over_gguf) || stat(f.c_str(), &s2) != 0) return 0;
+        if (over_gguf && tensors.count(name)) {
+            // the reference applies the .npy head in Python (llamacpp_talker_server.py:79-93): the exact table, not the
+            // GGUF's quantised token_embd / output
+            Q3_LOG("%s: taken from %s, not from the GGUF's quantised copy", name, f.c_str());
+            tensors.erase(name);
+        }
         return add_npy(f.c_str(), name) ? 1 : -1;
+    };
+    auto begins_with_gguf_magic = [](const char* f) {
+        char m[4] = {0, 0, 0, 0};
+        FILE* fp = fopen(f, "rb");
+        if (!fp) return false;
+        const bool is = fread(m, 1, 4, fp) == 4 && memcmp(m, "GGUF", 4) == 0;
+        fclose(fp);
+        return is;
     };
     int found = 0;
     if (S_ISREG(st.st_mode)) {
         const std::string f(path);
-        if (!ends_with(f, ".safetensors") && !ends_with(f, ".npz")) return open(path);
-        const int r = try_file(f);
-        if (r < 0) return false;
-        found += r;
+        if (ends_with(f, ".gguf") || begins_with_gguf_magic(path)) {
+            from_gguf = true;
+            if (!add_gguf(path, map_gguf_key)) return false;
+            found++;
+        } else {
+            if (!ends_with(f, ".safetensors") && !ends_with(f, ".npz")) return open(path);
+            const int r = try_file(f);
+            if (r < 0) return false;
+            found += r;
+        }
     } else if (S_ISDIR(st.st_mode)) {
         const std::string d(path);
         for (const char* f : {"model.safetensors", "code_predictor_weights.npz"}) {
             const int r = try_file(d + "/" + f);
             if (r < 0) return false;
             found += r;
+        }
+        struct stat s2;
+        if (stat((d + "/model.safetensors").c_str(), &s2) != 0) {   // a deployment that holds only the talker's GGUF
+            std::vector<std::string> ggufs;
+            if (DIR* dh = opendir(path)) {
+                while (const dirent* e = readdir(dh))
+                    if (ends_with(e->d_name, ".gguf")) ggufs.push_back(e->d_name);
+                closedir(dh);
+            }
+            if (ggufs.size() > 1) {
+                Q3_LOG("%s holds %zu .gguf files (%s, %s, ...): name the talker's file itself", path, ggufs.size(), ggufs[0].c_str(),
+                       ggufs[1].c_str());
+                return false;
+            }
+            if (ggufs.size() == 1) {
+                const int r = try_file(d + "/" + ggufs[0]);
+                if (r < 0) return false;
+                found += r;
+            }
         }
         for (const auto& e : kNpyTables) {
             const int r = try_npy(d, e[0], e[1]);
@@ -672,7 +1047,7 @@ bool Pack::open_auto(const char* path, const char* aux_dir) {
         }
     }
     if (!found) {
-        Q3_LOG("%s: no Q3TTSW1 container, model.safetensors or code_predictor_weights.npz found", path);
+        Q3_LOG("%s: no Q3TTSW1 container, model.safetensors, talker .gguf or code_predictor_weights.npz found", path);
         return false;
     }
     // geometry from the tensors: layers present, vocabulary rows (the re-keyed talker pads both

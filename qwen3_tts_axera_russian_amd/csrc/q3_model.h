@@ -61,6 +61,13 @@ struct Model {
 Model* model_load(const char* path, bool want_talker, bool want_cp, const char* aux_dir = nullptr, hipStream_t s = nullptr);
 void model_free(Model* m);
 
+// ggml blocks of `type` (Q4_0 .. Q6_K of DType), already on the device -> n_rows x K row-major values, as fp16 (round to
+// nearest even, saturating at +-65504) when out_f16 is set or as the fp32 value itself when out_f32 is: exactly one of the
+// two.  K is a multiple of the block; both outputs are 16-byte aligned.  *flag (device) is set to 1 when a block's scale is
+// Inf or NaN, and is otherwise left alone: the caller zeroes it.  Asynchronous on s.  (csrc/q3_dequant.hip)
+int launch_dequant(hipStream_t s, uint32_t type, const uint8_t* blocks, size_t n_rows, size_t K, half_t* out_f16, float* out_f32,
+                   int* flag);
+
 struct KVCache {
     half_t *k = nullptr, *v = nullptr;
     int n_layers = 0, n_slots = 0, n_kv = 0, n_ctx = 0, head_dim = 128;

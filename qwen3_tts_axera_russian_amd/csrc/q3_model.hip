@@ -14,6 +14,12 @@ struct Loader {
     half_t* stage = nullptr;  // device staging for one row-major matrix
     size_t stage_elems = 0;
     std::vector<uint16_t> host16;
+    uint8_t* raw = nullptr;   // device staging for one tensor's ggml blocks, and the dequantiser's flag behind them
+    size_t raw_bytes = 0;
+    hipEvent_t dq_ev[2] = {nullptr, nullptr};   // around every dequantiser launch: its GPU time is part of the load's one log line
+    int dq_launches = 0;
+    float dq_ms = 0.f;
+    size_t dq_bytes = 0;
     bool ok = true;
 
     // host -> device on the loader's stream, complete on return (the source may be a temporary)
@@ -39,12 +45,45 @@ struct Loader {
             return nullptr;
         }
         if (t->ndim != ndim || t->shape[0] != d0 || (ndim > 1 && t->shape[1] != d1) ||
-            (t->dtype != F32 && t->dtype != F16 && t->dtype != BF16)) {
+            (t->dtype != F32 && t->dtype != F16 && t->dtype != BF16 && !(is_block_dtype(t->dtype) && ndim == 2))) {
             Q3_LOG("tensor %s: unexpected shape/dtype", n.c_str());
             ok = false;
             return nullptr;
         }
         return t;
+    }
+    // a GGUF tensor's raw blocks -> the device, dequantised there into out16 (fp16) or out32 (f32); complete on return
+    bool dequant_into(const PackTensor* t, half_t* out16, float* out32) {
+        const size_t need_bytes = (size_t)t->nbytes + 16;   // the flag sits 16-byte aligned behind the blocks
+        if (need_bytes > raw_bytes) {
+            if (raw) hipFree(raw);
+            raw = nullptr;
+            raw_bytes = 0;
+            if (hipMalloc((void**)&raw, need_bytes + 16) != hipSuccess) {
+                Q3_LOG("hipMalloc(%zu) failed", need_bytes + 16);
+                return ok = false;
+            }
+            raw_bytes = need_bytes;
+        }
+        int* flag = (int*)(raw + ((size_t)t->nbytes + 15) / 16 * 16);
+        int bad = 0;
+        if (!dq_ev[0] && (hipEventCreate(&dq_ev[0]) != hipSuccess || hipEventCreate(&dq_ev[1]) != hipSuccess)) return ok = false;
+        if (hipMemsetAsync(flag, 0, sizeof(int), s) != hipSuccess ||
+            hipMemcpyAsync(raw, t->data, t->nbytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+            hipEventRecord(dq_ev[0], s) != hipSuccess ||
+            launch_dequant(s, t->dtype, raw, t->shape[0], t->shape[1], out16, out32, flag) != 0 ||
+            hipEventRecord(dq_ev[1], s) != hipSuccess ||
+            hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+            return ok = false;
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, dq_ev[0], dq_ev[1]) == hipSuccess) dq_ms += ms;
+        dq_launches++;
+        dq_bytes += t->nbytes;
+        if (bad) {
+            Q3_LOG("tensor %s: a block's scale is Inf or NaN (a damaged GGUF): refusing the file", t->name.c_str());
+            return ok = false;
+        }
+        return true;
     }
     // any float tensor -> device f32
     float* up_f32(const std::string& n, uint32_t ndim, uint64_t d0, uint64_t d1 = 0) {
@@ -55,6 +94,8 @@ struct Loader {
         if (!d) return nullptr;
         if (t->dtype == F32) {
             if (!up(d, t->data, ne * 4)) ok = false;
+        } else if (is_block_dtype(t->dtype)) {
+            dequant_into(t, nullptr, d);
         } else {
             std::vector<float> tmp(ne);
             const uint16_t* src = (const uint16_t*)t->data;
@@ -81,7 +122,10 @@ struct Loader {
             stage_elems = ne;
         }
         const void* src = t->data;
-        if (t->dtype == F32) {
+        if (is_block_dtype(t->dtype)) {
+            if (!dequant_into(t, stage, nullptr)) return false;
+            src = nullptr;   // already staged
+        } else if (t->dtype == F32) {
             host16.resize(ne);
             const float* f = (const float*)t->data;
             for (size_t i = 0; i < ne; i++) host16[i] = f2h_sat(f[i]);
@@ -92,7 +136,7 @@ struct Loader {
             for (size_t i = 0; i < ne; i++) host16[i] = f2h_sat(bf16_to_f32(b[i]));
             src = host16.data();
         }
-        if (!up(stage, src, ne * 2)) {
+        if (src && !up(stage, src, ne * 2)) {
             ok = false;
             return false;
         }
@@ -286,6 +330,12 @@ Model* model_load(const char* path, bool want_talker, bool want_cp, const char* 
     }
     hipStreamSynchronize(L.s);
     if (L.stage) hipFree(L.stage);
+    if (L.raw) hipFree(L.raw);
+    for (hipEvent_t e : L.dq_ev)
+        if (e) hipEventDestroy(e);
+    if (L.dq_launches && L.ok)
+        Q3_LOG("%s: %d quantised tensors (%.1f MB of blocks) dequantised on the GPU: %d launches, %.3f ms of GPU time", path,
+               L.dq_launches, L.dq_bytes / 1e6, L.dq_launches, L.dq_ms);
     if (!stream) hipStreamDestroy(L.s);   // the loader's own stream ends with the load: it holds no hardware queue afterwards
     if (!L.ok) {
         model_free(m);

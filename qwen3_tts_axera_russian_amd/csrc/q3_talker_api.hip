@@ -66,15 +66,17 @@ void wrapper_backend_init(void) {
 
 void wrapper_backend_free(void) {}
 
-void* wrapper_load_model(const char* path, int n_gpu_layers) {
+void* wrapper_load_model_aux(const char* path, const char* embeddings_dir, int n_gpu_layers) {
     (void)n_gpu_layers;
     if (!path) return nullptr;
-    Model* m = model_load(path, true, false);
+    Model* m = model_load(path, true, false, embeddings_dir);
     if (!m) return nullptr;
     TalkerModel* tm = new TalkerModel();
     tm->m = m;
     return tm;
 }
+
+void* wrapper_load_model(const char* path, int n_gpu_layers) { return wrapper_load_model_aux(path, nullptr, n_gpu_layers); }
 
 void wrapper_free_model(void* model) {
     TalkerModel* tm = (TalkerModel*)model;

@@ -1483,3 +1483,34 @@ extern "C" int q3t_spk_mel(void* h, const float* pcm, const int32_t* n_samples, 
 extern "C" int q3t_spk_stage(void* h, const float* pcm, const int32_t* n_samples, int B, int stage, float* out, int* C, int* L) {
     return spk_debug_stage((Spk*)h, pcm, n_samples, B, stage, out, C, L);
 }
+
+// ---- launch_dequant (q3_dequant.hip) on rows [row0, row0 + rows) of a tensor of rows_total x K elements of a ggml block
+// type (DType Q4_0 .. Q6_K), whose raw blocks are `blocks` (nbytes = rows_total * K / block * block bytes).  out16 (fp16
+// bits) or out32, whichever is not null: [rows][K].  *flag: what the launch left in its device flag (zeroed before).
+// 0, -1 HIP, -2 arguments, -3 something was written behind the rows asked for.
+extern "C" int q3t_dequant_case(int type, const uint8_t* blocks, long long nbytes, int rows_total, int K, int row0, int rows,
+                                uint16_t* out16, float* out32, int* flag) {
+    const BlockGeom g = block_geom((uint32_t)type);
+    if (!is_block_dtype((uint32_t)type) || !blocks || !flag || (out16 != nullptr) == (out32 != nullptr) || K <= 0 || K % (int)g.elems ||
+        rows_total < 1 || rows < 1 || row0 < 0 || row0 + rows > rows_total)
+        return -2;
+    const size_t row_bytes = (size_t)K / g.elems * g.bytes;
+    if ((long long)(row_bytes * rows_total) != nbytes) return -2;
+    constexpr uint32_t GUARD = 0x7fc5a5a5u;
+    const size_t n = (size_t)rows * K, esz = out16 ? 2 : 4, tail = 64;
+    std::vector<uint32_t> ho((n * esz + tail) / 4 + 1, GUARD);
+    DBuf db, dout, df;
+    int zero = 0;
+    if (!db.up(blocks, (size_t)nbytes) || !dout.up(ho.data(), ho.size() * 4) || !df.up(&zero, 4)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (launch_dequant(nullptr, (uint32_t)type, (const uint8_t*)db.p + (size_t)row0 * row_bytes, (size_t)rows, (size_t)K,
+                       out16 ? (half_t*)dout.p : nullptr, out32 ? (float*)dout.p : nullptr, (int*)df.p))
+        return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    Q3_HIP(hipMemcpy(ho.data(), dout.p, ho.size() * 4, hipMemcpyDeviceToHost), -1);
+    Q3_HIP(hipMemcpy(flag, df.p, 4, hipMemcpyDeviceToHost), -1);
+    memcpy(out16 ? (void*)out16 : (void*)out32, ho.data(), n * esz);
+    for (size_t i = n * esz / 4; i < ho.size(); i++)   // n * esz is a multiple of 16
+        if (ho[i] != GUARD) return -3;
+    return 0;
+}

@@ -68,6 +68,7 @@ def load(path: str | None = None):
     _sig(lib, "wrapper_backend_init", None, [])
     _sig(lib, "wrapper_backend_free", None, [])
     _sig(lib, "wrapper_load_model", c_void_p, [c_char_p, c_int])
+    _sig(lib, "wrapper_load_model_aux", c_void_p, [c_char_p, c_char_p, c_int])
     _sig(lib, "wrapper_free_model", None, [c_void_p])
     _sig(lib, "wrapper_model_n_embd", c_int, [c_void_p])
     _sig(lib, "wrapper_create_context", c_void_p, [c_void_p, c_int, c_int, c_int, c_int])
@@ -315,6 +316,8 @@ def load_test():
     _sig(lib, "q3t_enc_rvq_tile", c_int, [c_int])
     _sig(lib, "q3t_enc_rvq_case", c_int, [f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, f32p, i64p])
     _sig(lib, "q3t_enc_conv_in_case", c_int, [f32p, c_int, c_int, f32p, f32p, c_int, c_int, f32p, c_int, i32p, f32p])
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    _sig(lib, "q3t_dequant_case", c_int, [c_int, u8p, ctypes.c_longlong, c_int, c_int, c_int, c_int, u16p, f32p, i32p])
     _sig(lib, "q3t_spk_mel", c_int, [c_void_p, f32p, i32p, c_int, f32p, i32p, i32p])
     _sig(lib, "q3t_spk_stage", c_int, [c_void_p, f32p, i32p, c_int, c_int, f32p, i32p, i32p])
     _test_lib = lib

@@ -2,7 +2,8 @@
 dual_npu/llama_cpp_bindings.py (same class, method names, argument meaning and errors), bound
 to the HIP build of the wrapper_* ABI (include/qwen3tts_talker.h) instead of llama.cpp.
 
-`model_path` is a Q3TTSW1 weight container (weights.py), not a GGUF.  If the shared library is
+`model_path` is a Q3TTSW1 weight container (weights.py), the re-keyed talker safetensors, or the GGUF the
+reference's server is started with (Q4_K_M, Q8_0, ...: dequantised on the GPU at load).  If the shared library is
 missing or no GPU is usable this raises RuntimeError -- there is no CPU path.
 """
 from __future__ import annotations
@@ -39,11 +40,16 @@ class LlamaCppModel:
     _STATE_IO = {"state_save": ("wrapper_state_save_file", "saved"),
                  "state_load": ("wrapper_state_load_file", "restored")}
 
-    def __init__(self, model_path, n_ctx=512, n_threads=4):
+    def __init__(self, model_path, n_ctx=512, n_threads=4, embeddings_dir=None):
+        """embeddings_dir (extension): the server's --embeddings_dir; its codec_embedding.npy / codec_head.npy replace the
+        tables inside model_path (a GGUF's are quantised), so wrapper_codec_head applies the exact head."""
         self._abi = _talker_library()
         self.model = self.ctx = None
         self._abi.wrapper_backend_init()
-        self.model = self._abi.wrapper_load_model(os.fsencode(str(model_path)), 0)
+        if embeddings_dir:
+            self.model = self._abi.wrapper_load_model_aux(os.fsencode(str(model_path)), os.fsencode(str(embeddings_dir)), 0)
+        else:
+            self.model = self._abi.wrapper_load_model(os.fsencode(str(model_path)), 0)
         if not self.model:
             raise RuntimeError(f"talker weights could not be loaded from {model_path} (see stderr of the library)")
         self.n_embd = int(self._abi.wrapper_model_n_embd(self.model))

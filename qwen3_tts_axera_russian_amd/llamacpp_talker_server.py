@@ -51,7 +51,9 @@ class Qwen3TTSTalkerServer:
             from .tokenizer import ByteLevelBPE
             self.tokenizer = ByteLevelBPE.from_dir(tokenizer)
         print(f"Loading talker: {model_path}")
-        self.llm = LlamaCppModel(model_path, n_ctx=n_ctx, n_threads=n_threads)
+        # with --embeddings the talker samples from that directory's exact codec_head.npy, as the reference does, whatever
+        # copy of it --model holds (a GGUF's output.weight is quantised)
+        self.llm = LlamaCppModel(model_path, n_ctx=n_ctx, n_threads=n_threads, embeddings_dir=embeddings_dir)
         self._running = True
         if install_signal_handlers:
             signal.signal(signal.SIGINT, self._signal_handler)
@@ -175,7 +177,8 @@ class Qwen3TTSTalkerServer:
 
 def main():
     ap = argparse.ArgumentParser(description="Qwen3-TTS Talker Server (MI355X / HIP)")
-    ap.add_argument("--model", required=True, help="Q3TTSW1 container, or the re-keyed talker model.safetensors / its directory")
+    ap.add_argument("--model", required=True, help="Q3TTSW1 container, the re-keyed talker model.safetensors / its directory, or the reference's talker .gguf "
+                                                    "(Q4_K_M, Q8_0, ...)")
     ap.add_argument("--embeddings", default=None, help="the reference's embeddings/ directory of .npy tables (default: the text.* tensors of --model)")
     ap.add_argument("--socket", default="/tmp/qwen3_talker.sock")
     ap.add_argument("--temperature", type=float, default=0.8)

@@ -246,12 +246,16 @@ def write_synthetic(path: str, cfg: ModelConfig, seed: int = 1234, parts=("talke
 # ----------------------------------------------------------------------------
 
 def from_reference_dirs(embeddings_dir: str, cp_dir: str, talker_safetensors: str | None,
-                        out_path: str, cfg: ModelConfig | None = None) -> None:
+                        out_path: str, cfg: ModelConfig | None = None, talker_gguf: str | None = None) -> None:
     """Pack the reference's deployed files (README.md:108-122):
     embeddings/{text_embedding,codec_embedding,codec_head,text_projection_*}.npy
     (scripts/extract_embeddings.py:47-72), code_predictor_weights.npz
     (scripts/export_code_predictor_weights.py:51-78) and the re-keyed talker
-    safetensors (scripts/extract_talker_as_qwen3.py:53-71) into one container."""
+    safetensors (scripts/extract_talker_as_qwen3.py:53-71) into one container.
+    talker_gguf: the talker's layers from the deployed GGUF instead (Q4_K_M, Q8_0, ...: gguf.py dequantises to the fp16
+    weights the native loader makes); the codec tables stay the exact .npy ones of embeddings_dir."""
+    if talker_safetensors and talker_gguf:
+        raise ValueError("give the talker as safetensors or as a GGUF, not both")
     cfg = cfg or ModelConfig()
     t = {}
     e = lambda n: np.load(os.path.join(embeddings_dir, n))
@@ -273,6 +277,13 @@ def from_reference_dirs(embeddings_dir: str, cp_dir: str, talker_safetensors: st
         t[f"cp.lm_head.{g}"] = w[f"lm_head_{g}"].astype(np.float16)
     if talker_safetensors:
         t.update(_talker_from_safetensors(talker_safetensors, cfg, "model.layers.", "model.norm.weight"))
+    if talker_gguf:
+        from .gguf import talker_tensors
+        _, g = talker_tensors(talker_gguf, cfg.talker_vocab)
+        n_layers = sum(1 for k in g if k.endswith(".q_proj"))
+        if n_layers != cfg.talker_layers:
+            raise ValueError(f"{talker_gguf} holds {n_layers} talker layers, the configuration says {cfg.talker_layers}")
+        t.update({k: v for k, v in g.items() if k not in ("talker.codec_embedding", "talker.codec_head")})
     write_pack(out_path, cfg.meta(), t)
 
 
