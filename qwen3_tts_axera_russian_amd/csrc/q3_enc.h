@@ -93,6 +93,18 @@ static inline ConvArgs enc_conv_args(const EncOp& op, long cols, bool unfolded) 
 // of column 0); else entry b continues stream streams[b], whose last k - 1 samples are at hist + streams[b] * state_floats
 int enc_launch_conv_in(hipStream_t s, const float* x, int ldx, const EncOp& op, float* y, int ldy, int n, int B, float* hist,
                        long long state_floats, const int* streams);
+// a strided conv's input of whole clips: x [B][Cin][ldx], clip b's own length lens[b] (device) -> y [B][Cin * k][pitch(Lout)],
+// columns below Lout (enc_unfold_kernel states the padding)
+int enc_launch_unfold(hipStream_t st, const float* x, int ldx, int Cin, const int* lens, float* y, int Lout, int k, int s, int replicate,
+                      int elu, int B);
+// the same of one push (q3_enc_stream.hip, enc_stream_unfold_kernel): n_in new columns of x [B][Cin][ldx] from column skip behind
+// the carry of stream streams[b], `before[b]` columns taken so far -> y [B][Cin * k][pitch(n_out)]; the carry row
+// hist + streams[b] * state_floats + ci * (k - 1) moves on unless the push finishes
+int enc_stream_launch_unfold(hipStream_t st, const float* x, int ldx, int skip, int Cin, int n_in, float* y, int n_out, int k, int s,
+                             int replicate, int elu, int finish, float* hist, long long state_floats, const int* streams, const int* before,
+                             int B);
+// columns [skip, skip + n) of y [B][C][ld] -> rows off[b] + j of out [frames][C]
+int enc_stream_launch_emit(hipStream_t st, const float* y, int C, int ld, int skip, int n, const int* off, float* out, int B);
 // the split residual VQ over n_frames frames, frame g = b * T + t read from z [B][2 * dim][ld] -> codes [n_frames][nq]
 int enc_launch_rvq(hipStream_t s, const float* z, int ld, int T, int n_frames, const EncOp& op, int64_t* codes);
 // frames per workgroup of that launch: enc_rvq_kernel<16> from 2048 frames, enc_rvq_kernel<4> below.  A frame's ids do not

@@ -94,9 +94,17 @@ __global__ void __launch_bounds__(256) enc_unfold_kernel(const float* __restrict
         } else if (i >= 0 && i < len) {
             v = xr[i];
         }
-        if (elu && v <= 0.f) v = expm1f(v);
+        if (elu && v < 0.f) v = expm1f(v);   // (not <=: the device's expm1f turns -0 into +0, ELU leaves it)
     }
     y[((size_t)b * Cin * k + r) * ldy + u] = v;
+}
+
+int enc_launch_unfold(hipStream_t st, const float* x, int ldx, int Cin, const int* lens, float* y, int Lout, int k, int s, int replicate,
+                      int elu, int B) {
+    hipLaunchKernelGGL(enc_unfold_kernel, dim3((unsigned)((Lout + 255) / 256), Cin * k, B), dim3(256), 0, st, x, ldx, Cin, lens, y,
+                       (int)enc_pitch(Lout), Lout, k, s, replicate, elu);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -310,10 +318,9 @@ int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, float** out
             const bool strided = op.op == EOP_CONV_S;
             const long Lo = enc_cols_out(op, L);
             if (strided) {
-                hipLaunchKernelGGL(enc_unfold_kernel, dim3((unsigned)((Lo + 255) / 256), op.cin * op.k, B), dim3(256), 0, e->s, src,
-                                   (int)ld, op.cin, e->d_lens + i * e->max_batch, e->buf[3], (int)enc_pitch(Lo), (int)Lo, op.k,
-                                   op.p0, (op.flags & EF_REPLICATE) ? 1 : 0, (op.flags & EF_ELU) ? 1 : 0);
-                Q3_HIP(hipGetLastError(), -1);
+                if (enc_launch_unfold(e->s, src, (int)ld, op.cin, e->d_lens + i * e->max_batch, e->buf[3], (int)Lo, op.k, op.p0,
+                                      (op.flags & EF_REPLICATE) ? 1 : 0, (op.flags & EF_ELU) ? 1 : 0, B))
+                    return -1;
             }
             ConvArgs a = enc_conv_args(op, Lo, strided);
             a.x = strided ? e->buf[3] : src;

@@ -53,7 +53,7 @@ __global__ void __launch_bounds__(256) enc_stream_unfold_kernel(const float* __r
     for (int t = 0; t < k; t++)
         for (int u = tid; u < n_out; u += 256) {
             float v = V(u * s + t);
-            if (elu && v <= 0.f) v = expm1f(v);
+            if (elu && v < 0.f) v = expm1f(v);   // (as enc_unfold_kernel: -0 stays -0)
             yb[(size_t)t * ldy + u] = v;
         }
     if (!finish) {
@@ -67,6 +67,20 @@ __global__ void __launch_bounds__(256) enc_stream_emit_kernel(const float* __res
                                                               const int* __restrict__ off, float* __restrict__ out) {
     const int c = blockIdx.x * 256 + threadIdx.x, j = blockIdx.y, b = blockIdx.z;
     if (c < C) out[((size_t)off[b] + j) * C + c] = y[((size_t)b * C + c) * ld + skip + j];
+}
+
+int enc_stream_launch_unfold(hipStream_t st, const float* x, int ldx, int skip, int Cin, int n_in, float* y, int n_out, int k, int s,
+                             int replicate, int elu, int finish, float* hist, long long state_floats, const int* streams, const int* before,
+                             int B) {
+    hipLaunchKernelGGL(enc_stream_unfold_kernel, dim3(Cin, B), dim3(256), 0, st, x, ldx, skip, Cin, n_in, y, (int)enc_pitch(n_out), n_out, k, s,
+                       replicate, elu, finish, hist, state_floats, streams, before);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+int enc_stream_launch_emit(hipStream_t st, const float* y, int C, int ld, int skip, int n, const int* off, float* out, int B) {
+    hipLaunchKernelGGL(enc_stream_emit_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)n, B), dim3(256), 0, st, y, C, ld, skip, n, off, out);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
 }
 
 namespace {
@@ -141,11 +155,7 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
     };
     auto emit = [&](int C, float* out) -> int {
         (*launches)++;
-        if (dry) return 0;
-        hipLaunchKernelGGL(enc_stream_emit_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)n, B), dim3(256), 0, e->s, s->buf[cur], C,
-                           (int)enc_pitch(skip + n), skip, (int)n, d_foff, out);
-        Q3_HIP(hipGetLastError(), -1);
-        return 0;
+        return dry ? 0 : enc_stream_launch_emit(e->s, s->buf[cur], C, (int)enc_pitch(skip + n), skip, (int)n, d_foff, out, B);
     };
     for (size_t i = 0; i < nops; i++) {
         const EncOp& op = e->ops[i];
@@ -157,13 +167,11 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
                 const int u = pick();
                 if (!fits(op.cin * op.k, n_out)) return -1;
                 (*launches)++;
-                if (!dry) {
-                    hipLaunchKernelGGL(enc_stream_unfold_kernel, dim3(op.cin, B), dim3(256), 0, e->s, cur >= 0 ? s->buf[cur] : s->buf[0],
-                                       (int)enc_pitch(skip + n), skip, op.cin, (int)n, s->buf[u], (int)enc_pitch(n_out), (int)n_out, op.k,
-                                       op.p0, (op.flags & EF_REPLICATE) ? 1 : 0, (op.flags & EF_ELU) ? 1 : 0, fin ? 1 : 0,
-                                       s->d_hist + s->hoff[i], (long long)s->state_floats, d_streams, before(i));
-                    Q3_HIP(hipGetLastError(), -1);
-                }
+                if (!dry && enc_stream_launch_unfold(e->s, cur >= 0 ? s->buf[cur] : s->buf[0], (int)enc_pitch(skip + n), skip, op.cin, (int)n,
+                                                     s->buf[u], (int)n_out, op.k, op.p0, (op.flags & EF_REPLICATE) ? 1 : 0,
+                                                     (op.flags & EF_ELU) ? 1 : 0, fin ? 1 : 0, s->d_hist + s->hoff[i],
+                                                     (long long)s->state_floats, d_streams, before(i), B))
+                    return -1;
                 if (n_out > 0) {
                     const int d = pick(u);
                     if (d < 0 || !fits(op.cout, n_out)) return -1;

@@ -85,6 +85,30 @@ static inline void spk_bind(const Spk* e) {
     if (e && (hipGetDevice(&d) != hipSuccess || d != e->device)) hipSetDevice(e->device);
 }
 
+// rows are [clip][channel] at a pitch of the call's longest clip's frames rounded up to 32 floats
+static inline long spk_pitch(long L) { return (L + 31) & ~31L; }
+
+// One launch of each of the network's own kernels (q3_spk.hip states them), on B clips of pitch ld whose frame counts are
+// n_f [B] on the device: the walk's grids, shared with the one-op test hooks (q3t_spk_*_case).  0 / <0.
+// y [B][C * K][ld] = reflect-unfold of channels [c0, c0 + C) of x [B][Cx][ld] (+ channels [c02, c02 + C) of x2 [B][Cx2][ld])
+int spk_launch_unfold(hipStream_t s, const float* x, int Cx, int c0, const float* x2, int Cx2, int c02, const int* n_f, float* y, int C,
+                      int K, int dil, int ld, int B);
+// channels [c0y, c0y + C) of y [B][Cy][ld] = relu?(channels [c0x, c0x + C) of x [B][Cx][ld]), every column of the pitch
+int spk_launch_place(hipStream_t s, const float* x, int Cx, int c0x, float* y, int Cy, int c0y, int C, int ld, int relu, int B);
+// out [B][C] = the mean of x [B][C][ld] over the clip's own columns
+int spk_launch_rowmean(hipStream_t s, const float* x, int C, int ld, const int* n_f, float* out, int B);
+// out [B][O] = act(bias + w [O][I] in [B][I]); bias may be null; act 0 none, 1 ReLU, 2 sigmoid
+int spk_launch_matvec(hipStream_t s, const float* w, const float* bias, const float* in, float* out, int I, int O, int act, int B);
+// y1 [B][C][ld] and channels [c02, c02 + C) of y2 [B][Cy2][ld] = h * gate [B][C] + res, every column of the pitch
+int spk_launch_se_apply(hipStream_t s, const float* h, const float* gate, const float* res, float* y1, float* y2, int Cy2, int c02, int C,
+                        int ld, int B);
+// stat [B][2 C] = mean | std of x [B][C][ld] over the clip's own columns
+int spk_launch_rowstat(hipStream_t s, const float* x, int C, int ld, const int* n_f, float* stat, int B);
+// y = tanh(relu(x + bias [B][C])), every column of the pitch
+int spk_launch_att_act(hipStream_t s, const float* x, const float* bias, float* y, int C, int ld, int B);
+// pooled [B][2 C] = softmax(z)-weighted mean | std of x over the clip's own columns
+int spk_launch_attnpool(hipStream_t s, const float* z, const float* x, int C, int ld, const int* n_f, float* pooled, int B);
+
 // test hooks' back ends (q3_test_api.hip wraps them as q3t_spk_mel / q3t_spk_stage): run spk_embed's walk on the clips and
 // return the log-mel dense [B][n_mels][L] / the activation after `stage` dense [B][C][L] (L: the longest clip's frames;
 // pooled stages: [B][C], L = 1).  Stage 0 block0, 1.. the SE-Res2Net blocks, then mfa, asp, fc.  0 / <0.

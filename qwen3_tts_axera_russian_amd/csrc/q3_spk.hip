@@ -34,8 +34,6 @@
 
 namespace q3 {
 
-static inline long spk_pitch(long L) { return (L + 31) & ~31L; }
-
 // ---------------------------------------------------------------------------
 // Log-mel, float64.  Workgroup = FT frames of one clip; thread t owns the bins t, t + 256, t + 512 (n_fft <= 1024: spk_load).
 // LDS: the windowed frames [FT][N] (then the magnitudes [FT][N / 2 + 1] over them), cos and sin of 2 pi j / N.
@@ -248,13 +246,61 @@ __global__ void __launch_bounds__(256) spk_attnpool_kernel(const float* __restri
 }
 
 // ---------------------------------------------------------------------------
+// the launchers: the grid of every kernel above, for the walk and for the one-op test hooks (q3_test_api.hip)
+// ---------------------------------------------------------------------------
+static inline dim3 spk_cols(int ld, int rows, int B) { return dim3((unsigned)((ld + 255) / 256), (unsigned)rows, (unsigned)B); }
+static inline dim3 spk_waves(int rows, int B) { return dim3((unsigned)((rows + 3) / 4), (unsigned)B); }
+
+int spk_launch_unfold(hipStream_t s, const float* x, int Cx, int c0, const float* x2, int Cx2, int c02, const int* n_f, float* y, int C,
+                      int K, int dil, int ld, int B) {
+    hipLaunchKernelGGL(spk_unfold_kernel, spk_cols(ld, C * K, B), dim3(256), 0, s, x, Cx, c0, x2, Cx2, c02, n_f, y, C, K, dil, ld);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+int spk_launch_place(hipStream_t s, const float* x, int Cx, int c0x, float* y, int Cy, int c0y, int C, int ld, int relu, int B) {
+    hipLaunchKernelGGL(spk_place_kernel, spk_cols(ld, C, B), dim3(256), 0, s, x, Cx, c0x, y, Cy, c0y, ld, relu);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+int spk_launch_rowmean(hipStream_t s, const float* x, int C, int ld, const int* n_f, float* out, int B) {
+    hipLaunchKernelGGL(spk_rowmean_kernel, spk_waves(C, B), dim3(256), 0, s, x, C, ld, n_f, out);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+int spk_launch_matvec(hipStream_t s, const float* w, const float* bias, const float* in, float* out, int I, int O, int act, int B) {
+    hipLaunchKernelGGL(spk_matvec_kernel, spk_waves(O, B), dim3(256), 0, s, w, bias, in, out, I, O, act);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+int spk_launch_se_apply(hipStream_t s, const float* h, const float* gate, const float* res, float* y1, float* y2, int Cy2, int c02, int C,
+                        int ld, int B) {
+    hipLaunchKernelGGL(spk_se_apply_kernel, spk_cols(ld, C, B), dim3(256), 0, s, h, gate, res, y1, y2, Cy2, c02, C, ld);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+int spk_launch_rowstat(hipStream_t s, const float* x, int C, int ld, const int* n_f, float* stat, int B) {
+    hipLaunchKernelGGL(spk_rowstat_kernel, spk_waves(C, B), dim3(256), 0, s, x, C, ld, n_f, stat);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+int spk_launch_att_act(hipStream_t s, const float* x, const float* bias, float* y, int C, int ld, int B) {
+    hipLaunchKernelGGL(spk_att_act_kernel, spk_cols(ld, C, B), dim3(256), 0, s, x, bias, y, C, ld);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+int spk_launch_attnpool(hipStream_t s, const float* z, const float* x, int C, int ld, const int* n_f, float* pooled, int B) {
+    hipLaunchKernelGGL(spk_attnpool_kernel, spk_waves(C, B), dim3(256), 0, s, z, x, C, ld, n_f, pooled);
+    Q3_HIP(hipGetLastError(), -1);
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
 // the walk
 // ---------------------------------------------------------------------------
 struct SpkWalk {
     Spk* e;
     int B, L, ld, launches = 0;
     const int* d_f;   // per-clip frames
-    dim3 cols(int rows) const { return dim3((unsigned)((ld + 255) / 256), (unsigned)rows, (unsigned)B); }
     int conv1(const SpkConv& c, const float* x, float* y, bool bias) {
         ConvArgs a;
         a.Cin = c.cin * c.k;
@@ -273,16 +319,12 @@ struct SpkWalk {
         return voc_launch_conv(e->s, a, B);
     }
     int unfold(const SpkConv& c, const float* x, int Cx, int c0, const float* x2, int Cx2, int c02) {
-        hipLaunchKernelGGL(spk_unfold_kernel, cols(c.cin * c.k), dim3(256), 0, e->s, x, Cx, c0, x2, Cx2, c02, d_f, e->unf, c.cin, c.k, c.dil, ld);
         launches++;
-        Q3_HIP(hipGetLastError(), -1);
-        return 0;
+        return spk_launch_unfold(e->s, x, Cx, c0, x2, Cx2, c02, d_f, e->unf, c.cin, c.k, c.dil, ld, B);
     }
     int place(const float* x, int Cx, int c0x, float* y, int Cy, int c0y, int C, int relu) {
-        hipLaunchKernelGGL(spk_place_kernel, cols(C), dim3(256), 0, e->s, x, Cx, c0x, y, Cy, c0y, ld, relu);
         launches++;
-        Q3_HIP(hipGetLastError(), -1);
-        return 0;
+        return spk_launch_place(e->s, x, Cx, c0x, y, Cy, c0y, C, ld, relu, B);
     }
     // relu(conv(x)) of channels [c0, c0 + cin) of x (+ x2's), into channels [c0y, c0y + cout) of y
     int tdnn(const SpkConv& c, const float* x, int Cx, int c0, const float* x2, int Cx2, int c02, float* y, int Cy, int c0y) {
@@ -295,10 +337,8 @@ struct SpkWalk {
         return place(e->raw, c.cout, 0, y, Cy, c0y, c.cout, 1);
     }
     int matvec(const SpkLin& m, const float* in, float* out, int act) {
-        hipLaunchKernelGGL(spk_matvec_kernel, dim3((unsigned)((m.out + 3) / 4), (unsigned)B), dim3(256), 0, e->s, m.w, m.b, in, out, m.in, m.out, act);
         launches++;
-        Q3_HIP(hipGetLastError(), -1);
-        return 0;
+        return spk_launch_matvec(e->s, m.w, m.b, in, out, m.in, m.out, act, B);
     }
 };
 
@@ -345,32 +385,26 @@ static int spk_run(Spk* e, int B, const std::vector<int>& ns, const std::vector<
         for (int j = 1; j < e->scale; j++)                          // chunk 1: conv(chunk); chunk j >= 2: conv(chunk_j + out_{j-1})
             if (w.tdnn(k.res[j - 1], e->h1, C, j * cw, j >= 2 ? e->r2 : nullptr, C, (j - 1) * cw, e->r2, C, j * cw)) return -1;
         if (w.tdnn(k.tdnn2, e->r2, C, 0, nullptr, 0, 0, e->h2, C, 0)) return -1;
-        hipLaunchKernelGGL(spk_rowmean_kernel, dim3((unsigned)((C + 3) / 4), (unsigned)B), dim3(256), 0, e->s, e->h2, C, w.ld, w.d_f, e->semean);
         w.launches++;
-        Q3_HIP(hipGetLastError(), -1);
+        if (spk_launch_rowmean(e->s, e->h2, C, w.ld, w.d_f, e->semean, B)) return -1;
         if (w.matvec(k.se1, e->semean, e->sehid, 1) || w.matvec(k.se2, e->sehid, e->gate, 2)) return -1;
-        hipLaunchKernelGGL(spk_se_apply_kernel, w.cols(C), dim3(256), 0, e->s, e->h2, e->gate, cur, nxt, e->cat, Cm, i * C, C, w.ld);
         w.launches++;
-        Q3_HIP(hipGetLastError(), -1);
+        if (spk_launch_se_apply(e->s, e->h2, e->gate, cur, nxt, e->cat, Cm, i * C, C, w.ld, B)) return -1;
         cur = nxt;
         if (stage == i + 1) return done(cur, C, 0, C, 0);
     }
     if (w.tdnn(e->mfa, e->cat, Cm, 0, nullptr, 0, 0, e->xm, Cm, 0)) return -1;
     if (stage == nb + 1) return done(e->xm, Cm, 0, Cm, 0);
-    hipLaunchKernelGGL(spk_rowstat_kernel, dim3((unsigned)((Cm + 3) / 4), (unsigned)B), dim3(256), 0, e->s, e->xm, Cm, w.ld, w.d_f, e->stat);
     w.launches++;
-    Q3_HIP(hipGetLastError(), -1);
+    if (spk_launch_rowstat(e->s, e->xm, Cm, w.ld, w.d_f, e->stat, B)) return -1;
     if (w.matvec(e->asp_stat, e->stat, e->abias, 0)) return -1;
     if (w.conv1(e->asp_tdnn, e->xm, e->raw, false)) return -1;
     const int A = e->asp_tdnn.cout;
-    hipLaunchKernelGGL(spk_att_act_kernel, w.cols(A), dim3(256), 0, e->s, e->raw, e->abias, e->att, A, w.ld);
     w.launches++;
-    Q3_HIP(hipGetLastError(), -1);
+    if (spk_launch_att_act(e->s, e->raw, e->abias, e->att, A, w.ld, B)) return -1;
     if (w.conv1(e->asp_conv, e->att, e->logit, true)) return -1;
-    hipLaunchKernelGGL(spk_attnpool_kernel, dim3((unsigned)((Cm + 3) / 4), (unsigned)B), dim3(256), 0, e->s, e->logit, e->xm, Cm, w.ld, w.d_f,
-                       e->pooled);
     w.launches++;
-    Q3_HIP(hipGetLastError(), -1);
+    if (spk_launch_attnpool(e->s, e->logit, e->xm, Cm, w.ld, w.d_f, e->pooled, B)) return -1;
     if (stage == nb + 2) return done(e->pooled, 2 * Cm, 0, 2 * Cm, 1);
     if (w.matvec(e->fc, e->pooled, e->emb, 0)) return -1;
     return done(e->emb, e->dim, 0, e->dim, 1);

@@ -1514,3 +1514,293 @@ extern "C" int q3t_dequant_case(int type, const uint8_t* blocks, long long nbyte
         if (ho[i] != GUARD) return -3;
     return 0;
 }
+
+// ---- the speaker encoder's own kernels (csrc/q3_spk.hip), one launch each (tests/test_gpu_spk_ops.py) ----------------
+// Conventions of q3t_enc_conv_in_case.  Activations are dense on the host and rows of the production pitch on the device
+// (ld = spk_pitch of the call's longest clip).  A kernel that stops at the clip's own length (unfold, rowmean, rowstat,
+// attnpool) takes [B][C][Lmax] and finds NaN in the pad columns [Lmax, ld); a kernel that runs over every column of the
+// pitch (place, se_apply, att_act) takes and returns [B][C][ld], ld = spk_pitch(L).  Every output is the guard pattern
+// before the launch: 32 words behind each buffer and the channels of a sliced destination outside the slice must keep it
+// (-3).  -2: arguments the walk never passes, before anything launches; -1: a HIP error.
+namespace {
+constexpr uint32_t OP_GUARD = 0x7fc5a5a5u;
+constexpr long long OP_MAX_WORDS = 1LL << 27;
+
+std::vector<float> op_padded(const float* src, size_t rows, int n, int ld) {
+    std::vector<float> h(rows * ld, std::nanf(""));
+    for (size_t r = 0; r < rows; r++) memcpy(h.data() + r * ld, src + r * n, (size_t)n * 4);
+    return h;
+}
+struct OpOut {
+    std::vector<uint32_t> h;
+    DBuf d;
+    size_t words = 0;
+    bool init(size_t w) {
+        words = w;
+        h.assign(w + 32, OP_GUARD);
+        return d.up(h.data(), h.size() * 4);
+    }
+    float* p() { return (float*)d.p; }
+    bool down() { return hipMemcpy(h.data(), d.p, h.size() * 4, hipMemcpyDeviceToHost) == hipSuccess; }
+    int tail() const {
+        int n = 0;
+        for (size_t i = words; i < h.size(); i++) n += h[i] != OP_GUARD;
+        return n;
+    }
+    // channels [c0, c0 + C) of [B][Ct][ld] go to dst [B][C][ld]; -> the words outside them that lost their guard
+    int slice(float* dst, int B, int Ct, int c0, int C, int ld) const {
+        int n = tail();
+        for (int b = 0; b < B; b++)
+            for (int c = 0; c < Ct; c++) {
+                const uint32_t* row = h.data() + ((size_t)b * Ct + c) * ld;
+                if (c >= c0 && c < c0 + C) memcpy(dst + ((size_t)b * C + c - c0) * ld, row, (size_t)ld * 4);
+                else
+                    for (int l = 0; l < ld; l++) n += row[l] != OP_GUARD;
+            }
+        return n;
+    }
+};
+// the clips' frame counts: all >= lo -> the longest, or -1
+int op_longest(const int* n_f, int B, int lo) {
+    if (!n_f || B < 1 || B > 65535) return -1;
+    int L = 0;
+    for (int b = 0; b < B; b++) {
+        if (n_f[b] < lo || n_f[b] > (1 << 20)) return -1;
+        L = std::max(L, n_f[b]);
+    }
+    return L;
+}
+}  // namespace
+
+// x [B][Cx][Lmax] (+ x2 [B][Cx2][Lmax] or null) -> y [B][C * K][ld], every column of the pitch
+extern "C" int q3t_spk_unfold_case(const float* x, int Cx, int c0, const float* x2, int Cx2, int c02, const int* n_f, int B, int C, int K,
+                                   int dil, float* y) {
+    if (!x || !y || C < 1 || K < 1 || K > 15 || !(K & 1) || dil < 1 || dil > 64 || c0 < 0 || Cx < 1 || c0 + C > Cx) return -2;
+    if (x2 && (c02 < 0 || Cx2 < 1 || c02 + C > Cx2)) return -2;
+    const int L = op_longest(n_f, B, dil * (K - 1) / 2 + 1);   // (the reflection stays inside the clip: spk_load's min_frames)
+    if (L < 0 || (long long)C * K > 65535) return -2;
+    const int ld = (int)spk_pitch(L);
+    if ((long long)B * std::max(std::max(Cx, Cx2), C * K) * ld > OP_MAX_WORDS) return -2;
+    const std::vector<float> hx = op_padded(x, (size_t)B * Cx, L, ld);
+    DBuf dx, dx2, dn;
+    OpOut o;
+    if (!dx.up(hx.data(), hx.size() * 4) || !dn.up(n_f, (size_t)B * 4) || !o.init((size_t)B * C * K * ld)) return -1;
+    if (x2) {
+        const std::vector<float> hx2 = op_padded(x2, (size_t)B * Cx2, L, ld);
+        if (!dx2.up(hx2.data(), hx2.size() * 4)) return -1;
+    }
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (spk_launch_unfold(nullptr, (const float*)dx.p, Cx, c0, x2 ? (const float*)dx2.p : nullptr, Cx2, c02, (const int*)dn.p, o.p(), C, K, dil,
+                          ld, B))
+        return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o.down()) return -1;
+    memcpy(y, o.h.data(), o.words * 4);
+    return o.tail() ? -3 : 0;
+}
+
+// channels [c0x, c0x + C) of x [B][Cx][ld] -> channels [c0y, c0y + C) of a [B][Cy][ld] destination; y [B][C][ld] is that slice
+extern "C" int q3t_spk_place_case(const float* x, int Cx, int c0x, int Cy, int c0y, int C, int L, int relu, int B, float* y) {
+    if (!x || !y || B < 1 || B > 65535 || C < 1 || C > 65535 || L < 1 || L > (1 << 20) || c0x < 0 || c0x + C > Cx || c0y < 0 || c0y + C > Cy ||
+        (relu != 0 && relu != 1))
+        return -2;
+    const int ld = (int)spk_pitch(L);
+    if ((long long)B * std::max(Cx, Cy) * ld > OP_MAX_WORDS) return -2;
+    DBuf dx;
+    OpOut o;
+    if (!dx.up(x, (size_t)B * Cx * ld * 4) || !o.init((size_t)B * Cy * ld)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (spk_launch_place(nullptr, (const float*)dx.p, Cx, c0x, o.p(), Cy, c0y, C, ld, relu, B)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o.down()) return -1;
+    return o.slice(y, B, Cy, c0y, C, ld) ? -3 : 0;
+}
+
+// the three one-wave-per-row reductions.  which 0: spk_rowmean -> out [B][C]; 1: spk_rowstat -> out [B][2 C];
+// 2: spk_attnpool (z = the logits) -> out [B][2 C].  x (and z) [B][C][Lmax]
+static int spk_reduce_case(int which, const float* z, const float* x, int C, const int* n_f, int B, float* out) {
+    if (!x || !out || (which == 2 && !z) || C < 1 || C > 4 * 65535) return -2;
+    const int L = op_longest(n_f, B, 1);
+    if (L < 0) return -2;
+    const int ld = (int)spk_pitch(L);
+    if ((long long)B * C * ld > OP_MAX_WORDS) return -2;
+    const std::vector<float> hx = op_padded(x, (size_t)B * C, L, ld);
+    DBuf dx, dz, dn;
+    OpOut o;
+    if (!dx.up(hx.data(), hx.size() * 4) || !dn.up(n_f, (size_t)B * 4) || !o.init((size_t)B * C * (which ? 2 : 1))) return -1;
+    if (which == 2) {
+        const std::vector<float> hz = op_padded(z, (size_t)B * C, L, ld);
+        if (!dz.up(hz.data(), hz.size() * 4)) return -1;
+    }
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    const float* X = (const float*)dx.p;
+    const int* N = (const int*)dn.p;
+    const int rc = which == 0 ? spk_launch_rowmean(nullptr, X, C, ld, N, o.p(), B)
+                   : which == 1 ? spk_launch_rowstat(nullptr, X, C, ld, N, o.p(), B)
+                                : spk_launch_attnpool(nullptr, (const float*)dz.p, X, C, ld, N, o.p(), B);
+    if (rc) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o.down()) return -1;
+    memcpy(out, o.h.data(), o.words * 4);
+    return o.tail() ? -3 : 0;
+}
+extern "C" int q3t_spk_rowmean_case(const float* x, int C, const int* n_f, int B, float* out) { return spk_reduce_case(0, nullptr, x, C, n_f, B, out); }
+extern "C" int q3t_spk_rowstat_case(const float* x, int C, const int* n_f, int B, float* stat) { return spk_reduce_case(1, nullptr, x, C, n_f, B, stat); }
+extern "C" int q3t_spk_attnpool_case(const float* z, const float* x, int C, const int* n_f, int B, float* pooled) {
+    return spk_reduce_case(2, z, x, C, n_f, B, pooled);
+}
+
+// w [O][I], bias [O] or null, in [B][I] -> out [B][O]
+extern "C" int q3t_spk_matvec_case(const float* w, const float* bias, const float* in, int I, int O, int act, int B, float* out) {
+    if (!w || !in || !out || I < 1 || O < 1 || O > 4 * 65535 || B < 1 || B > 65535 || act < 0 || act > 2 || (long long)I * O > OP_MAX_WORDS ||
+        (long long)B * std::max(I, O) > OP_MAX_WORDS)
+        return -2;
+    DBuf dw, db, di;
+    OpOut o;
+    if (!dw.up(w, (size_t)I * O * 4) || !di.up(in, (size_t)B * I * 4) || !o.init((size_t)B * O)) return -1;
+    if (bias && !db.up(bias, (size_t)O * 4)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (spk_launch_matvec(nullptr, (const float*)dw.p, bias ? (const float*)db.p : nullptr, (const float*)di.p, o.p(), I, O, act, B)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o.down()) return -1;
+    memcpy(out, o.h.data(), o.words * 4);
+    return o.tail() ? -3 : 0;
+}
+
+// h, res [B][C][ld], gate [B][C] -> y1 [B][C][ld] and channels [c02, c02 + C) of a [B][Cy2][ld] aggregate; y2 [B][C][ld] is that slice
+extern "C" int q3t_spk_se_apply_case(const float* h, const float* gate, const float* res, int C, int L, int Cy2, int c02, int B, float* y1,
+                                     float* y2) {
+    if (!h || !gate || !res || !y1 || !y2 || B < 1 || B > 65535 || C < 1 || C > 65535 || L < 1 || L > (1 << 20) || c02 < 0 || c02 + C > Cy2)
+        return -2;
+    const int ld = (int)spk_pitch(L);
+    if ((long long)B * Cy2 * ld > OP_MAX_WORDS) return -2;
+    const size_t n = (size_t)B * C * ld;
+    DBuf dh, dg, dr;
+    OpOut o1, o2;
+    if (!dh.up(h, n * 4) || !dg.up(gate, (size_t)B * C * 4) || !dr.up(res, n * 4) || !o1.init(n) || !o2.init((size_t)B * Cy2 * ld)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (spk_launch_se_apply(nullptr, (const float*)dh.p, (const float*)dg.p, (const float*)dr.p, o1.p(), o2.p(), Cy2, c02, C, ld, B)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o1.down() || !o2.down()) return -1;
+    memcpy(y1, o1.h.data(), n * 4);
+    return (o1.tail() + o2.slice(y2, B, Cy2, c02, C, ld)) ? -3 : 0;
+}
+
+// x [B][C][ld], bias [B][C] -> y [B][C][ld]
+extern "C" int q3t_spk_att_act_case(const float* x, const float* bias, int C, int L, int B, float* y) {
+    if (!x || !bias || !y || B < 1 || B > 65535 || C < 1 || C > 65535 || L < 1 || L > (1 << 20)) return -2;
+    const int ld = (int)spk_pitch(L);
+    if ((long long)B * C * ld > OP_MAX_WORDS) return -2;
+    const size_t n = (size_t)B * C * ld;
+    DBuf dx, db;
+    OpOut o;
+    if (!dx.up(x, n * 4) || !db.up(bias, (size_t)B * C * 4) || !o.init(n)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (spk_launch_att_act(nullptr, (const float*)dx.p, (const float*)db.p, o.p(), C, ld, B)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o.down()) return -1;
+    memcpy(y, o.h.data(), n * 4);
+    return o.tail() ? -3 : 0;
+}
+
+// ---- the encoder's unfold and emit kernels (csrc/q3_enc.hip, csrc/q3_enc_stream.hip), one launch each (tests/test_gpu_enc_unfold.py) ----
+// x [B][Cin][Lmax] (Lmax = the longest of lens; NaN in the pad columns of the pitch) -> y [B][Cin * k][Lout], Lout = ceil(Lmax / s);
+// the columns of y's pitch from Lout on keep their guard (-3)
+extern "C" int q3t_enc_unfold_case(const float* x, int B, int Cin, const int* lens, int k, int s, int replicate, int elu, float* y) {
+    if (!x || !y || Cin < 1 || s < 1 || k < s || k > 64 || (long long)Cin * k > 65535 || (replicate & ~1) || (elu & ~1)) return -2;
+    const int L = op_longest(lens, B, 1);
+    if (L < 0) return -2;
+    const int Lout = (L + s - 1) / s, ldx = (int)enc_pitch(L), ldy = (int)enc_pitch(Lout);
+    const size_t rows = (size_t)B * Cin * k;
+    if ((long long)rows * ldy > OP_MAX_WORDS || (long long)B * Cin * ldx > OP_MAX_WORDS) return -2;
+    const std::vector<float> hx = op_padded(x, (size_t)B * Cin, L, ldx);
+    DBuf dx, dn;
+    OpOut o;
+    if (!dx.up(hx.data(), hx.size() * 4) || !dn.up(lens, (size_t)B * 4) || !o.init(rows * ldy)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (enc_launch_unfold(nullptr, (const float*)dx.p, ldx, Cin, (const int*)dn.p, o.p(), Lout, k, s, replicate, elu, B)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o.down()) return -1;
+    int outside = o.tail();
+    for (size_t r = 0; r < rows; r++) {
+        memcpy(y + r * Lout, o.h.data() + r * ldy, (size_t)Lout * 4);
+        for (int l = Lout; l < ldy; l++) outside += o.h[r * ldy + l] != OP_GUARD;
+    }
+    return outside ? -3 : 0;
+}
+
+// One push of enc_stream_unfold_kernel.  x [B][Cin][skip + n_in] (the skipped columns are the caller's; NaN in the pad),
+// entry b continues stream streams[b] (distinct, < max_streams) that had taken before[b] columns; hist [max_streams][Cin][k - 1]
+// goes in and the named streams' rows come back as the launch left them (the other streams' rows hold the guard on the device
+// and must keep it).  -> y [B][Cin * k][n_out].  -2 also: a before[b] that does not give n_out, and n_in = n_out = 0 (the walk
+// launches nothing then).
+extern "C" int q3t_enc_stream_unfold_case(const float* x, int B, int Cin, int skip, int n_in, int n_out, int k, int s, int replicate, int elu,
+                                          int finish, float* hist, int max_streams, const int* streams, const int* before, float* y) {
+    if (!x || !y || !hist || !streams || !before || B < 1 || B > 65535 || Cin < 1 || Cin > 65535 || s < 1 || k < s || k - 1 > 32 || skip < 0 ||
+        n_in < 0 || n_out < 0 || (n_in == 0 && n_out == 0) || max_streams < B || (replicate & ~1) || (elu & ~1) || (finish & ~1))
+        return -2;
+    if ((long long)skip + n_in > (1 << 20) || (long long)max_streams * Cin * (k - 1) > OP_MAX_WORDS) return -2;
+    std::vector<char> seen((size_t)max_streams, 0);
+    for (int b = 0; b < B; b++) {
+        if (streams[b] < 0 || streams[b] >= max_streams || seen[(size_t)streams[b]]++ || before[b] < 0 || before[b] > 0x7fffffff - n_in) return -2;
+        const long long after = (long long)before[b] + n_in;
+        if ((finish ? (after + s - 1) / s : after / s) - before[b] / s != n_out) return -2;
+    }
+    const int cols = skip + n_in, ldx = (int)enc_pitch(cols), ldy = (int)enc_pitch(n_out), H = k - 1;
+    const size_t rows = (size_t)B * Cin * k, sf = (size_t)Cin * H, nh = (size_t)max_streams * sf;
+    if ((long long)rows * ldy > OP_MAX_WORDS || (long long)B * Cin * ldx > OP_MAX_WORDS) return -2;
+    const std::vector<float> hx = op_padded(x, (size_t)B * Cin, cols, ldx);
+    OpOut o, oh;
+    DBuf dx, ds, db;
+    if (!dx.up(hx.data(), hx.size() * 4) || !ds.up(streams, (size_t)B * 4) || !db.up(before, (size_t)B * 4) || !o.init(rows * ldy)) return -1;
+    oh.words = nh;
+    oh.h.assign(nh + 32, OP_GUARD);
+    for (int b = 0; b < B; b++) memcpy(oh.h.data() + (size_t)streams[b] * sf, hist + (size_t)streams[b] * sf, sf * 4);
+    if (!oh.d.up(oh.h.data(), oh.h.size() * 4)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (enc_stream_launch_unfold(nullptr, (const float*)dx.p, ldx, skip, Cin, n_in, o.p(), n_out, k, s, replicate, elu, finish, oh.p(),
+                                 (long long)sf, (const int*)ds.p, (const int*)db.p, B))
+        return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o.down() || !oh.down()) return -1;
+    int outside = o.tail() + oh.tail();
+    for (size_t r = 0; r < rows; r++) {
+        memcpy(y + r * n_out, o.h.data() + r * ldy, (size_t)n_out * 4);
+        for (int l = n_out; l < ldy; l++) outside += o.h[r * ldy + l] != OP_GUARD;
+    }
+    for (int st = 0; st < max_streams; st++) {
+        if (seen[(size_t)st]) memcpy(hist + (size_t)st * sf, oh.h.data() + (size_t)st * sf, sf * 4);
+        else
+            for (size_t i = 0; i < sf; i++) outside += oh.h[(size_t)st * sf + i] != OP_GUARD;
+    }
+    return outside ? -3 : 0;
+}
+
+// columns [skip, skip + n) of y [B][C][skip + n] -> rows off[b] .. off[b] + n - 1 of out [rows][C] (disjoint, inside `rows`); out comes
+// back whole: the rows no entry owns hold the guard pattern, and must (-3)
+extern "C" int q3t_enc_stream_emit_case(const float* y, int B, int C, int skip, int n, const int* off, int rows, float* out) {
+    if (!y || !off || !out || B < 1 || B > 65535 || C < 1 || skip < 0 || n < 1 || n > 65535 || rows < 1 || (long long)rows * C > OP_MAX_WORDS ||
+        (long long)B * C * enc_pitch((long)skip + n) > OP_MAX_WORDS)
+        return -2;
+    std::vector<char> owned((size_t)rows, 0);
+    for (int b = 0; b < B; b++) {
+        if (off[b] < 0 || (long long)off[b] + n > rows) return -2;
+        for (int j = 0; j < n; j++)
+            if (owned[(size_t)off[b] + j]++) return -2;
+    }
+    const int cols = skip + n, ld = (int)enc_pitch(cols);
+    const std::vector<float> hy = op_padded(y, (size_t)B * C, cols, ld);
+    DBuf dy, dn;
+    OpOut o;
+    if (!dy.up(hy.data(), hy.size() * 4) || !dn.up(off, (size_t)B * 4) || !o.init((size_t)rows * C)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (enc_stream_launch_emit(nullptr, (const float*)dy.p, C, ld, skip, n, (const int*)dn.p, o.p(), B)) return -1;
+    Q3_HIP(hipDeviceSynchronize(), -1);
+    if (!o.down()) return -1;
+    memcpy(out, o.h.data(), o.words * 4);
+    int outside = o.tail();
+    for (int r = 0; r < rows; r++)
+        if (!owned[(size_t)r])
+            for (int c = 0; c < C; c++) outside += o.h[(size_t)r * C + c] != OP_GUARD;
+    return outside ? -3 : 0;
+}

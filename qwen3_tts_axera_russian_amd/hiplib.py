@@ -320,6 +320,19 @@ def load_test():
     _sig(lib, "q3t_dequant_case", c_int, [c_int, u8p, ctypes.c_longlong, c_int, c_int, c_int, c_int, u16p, f32p, i32p])
     _sig(lib, "q3t_spk_mel", c_int, [c_void_p, f32p, i32p, c_int, f32p, i32p, i32p])
     _sig(lib, "q3t_spk_stage", c_int, [c_void_p, f32p, i32p, c_int, c_int, f32p, i32p, i32p])
+    # one launch of each of the speaker encoder's own kernels and of the encoder's unfold / emit kernels
+    _sig(lib, "q3t_spk_unfold_case", c_int, [f32p, c_int, c_int, f32p, c_int, c_int, i32p, c_int, c_int, c_int, c_int, f32p])
+    _sig(lib, "q3t_spk_place_case", c_int, [f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, f32p])
+    _sig(lib, "q3t_spk_rowmean_case", c_int, [f32p, c_int, i32p, c_int, f32p])
+    _sig(lib, "q3t_spk_rowstat_case", c_int, [f32p, c_int, i32p, c_int, f32p])
+    _sig(lib, "q3t_spk_attnpool_case", c_int, [f32p, f32p, c_int, i32p, c_int, f32p])
+    _sig(lib, "q3t_spk_matvec_case", c_int, [f32p, f32p, f32p, c_int, c_int, c_int, c_int, f32p])
+    _sig(lib, "q3t_spk_se_apply_case", c_int, [f32p, f32p, f32p, c_int, c_int, c_int, c_int, c_int, f32p, f32p])
+    _sig(lib, "q3t_spk_att_act_case", c_int, [f32p, f32p, c_int, c_int, c_int, f32p])
+    _sig(lib, "q3t_enc_unfold_case", c_int, [f32p, c_int, c_int, i32p, c_int, c_int, c_int, c_int, f32p])
+    _sig(lib, "q3t_enc_stream_unfold_case", c_int, [f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, f32p, c_int,
+                                                    i32p, i32p, f32p])
+    _sig(lib, "q3t_enc_stream_emit_case", c_int, [f32p, c_int, c_int, c_int, c_int, i32p, c_int, f32p])
     _test_lib = lib
     return lib
 

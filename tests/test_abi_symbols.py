@@ -45,7 +45,9 @@ def test_test_hooks_are_not_in_the_product_library(lib):
               "q3t_talker_sample_case", "q3t_cp_sample_case", "q3t_bench_linear", "q3t_inspect_weights", "q3t_attn", "q3t_voc_attn",
               "q3t_enc_rvq_tile", "q3t_enc_rvq_case", "q3t_enc_conv_in_case", "q3t_talker_sample_text_case",
               "q3t_cp_sample_text_case", "q3t_final_norm_case", "q3t_gather_embed_case", "q3t_feedback_case",
-              "q3t_prompt_rows_case", "q3t_prefix_move_case"):
+              "q3t_prompt_rows_case", "q3t_prefix_move_case", "q3t_spk_unfold_case", "q3t_spk_place_case", "q3t_spk_rowmean_case",
+              "q3t_spk_matvec_case", "q3t_spk_se_apply_case", "q3t_spk_rowstat_case", "q3t_spk_att_act_case", "q3t_spk_attnpool_case",
+              "q3t_enc_unfold_case", "q3t_enc_stream_unfold_case", "q3t_enc_stream_emit_case"):
         assert n in hooks
     assert {"q3_device_count", "q3_set_device"} <= prod
 
