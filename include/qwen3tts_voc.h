@@ -132,7 +132,8 @@ float voc_stream_last_ms(void* s);
  *  - Invariance: joined per stream, the samples are the same bits for any split of the frames across pushes, any n_new pattern,
  *    any set of other streams in the same calls, and any stream index: every launcher rule that looks at a length reads the
  *    full-chunk length, and a column's sums depend on neither its tile nor its batch.
- *  - Arithmetic: the exact-fp32 kernels by default, whatever voc_set_exact_fp32 selects process-wide; voc_set_fused_units applies.
+ *  - Arithmetic: the exact-fp32 kernels by default, whatever voc_set_exact_fp32 has set for the process; voc_set_fused_units applies,
+ *    with the value it had when the push began (the settings' contract, at voc_set_exact_fp32).
  *    voc_incr_set_arithmetic (below) moves one object to the split-fp16 convolutions.
  *  - Limits: 0 <= n_new <= chunk_tokens per entry and push; frames per stream unbounded (2^31, the RoPE position).  Device memory
  *    is constant: per stream the carried columns, voc_incr_state_bytes() = 5 193 984 B (4.95 MiB) at the default table (of which
@@ -225,12 +226,17 @@ float voc_incr_last_restore_ms(void* s);
  * vs 4.0e-7 (exact f32 MFMA) vs 2.1e-7 (torch CPU f32) of full scale -- the split path is fp32-grade, and
  * 2.8x faster at 32 chunks.  Values beyond the fp16 range cannot be split: an op with such a weight stays
  * exact, and a call in which an activation leaves the range is redone on the exact path before it returns (voc_decode,
- * voc_synthesize*: the whole call).  Process-wide; env Q3_VOC_EXACT=1 selects the exact path at load. */
+ * voc_synthesize*: the whole call).  Env Q3_VOC_EXACT=1 selects the exact path at load.
+ * The settings' contract (this call, voc_set_fused_units, voc_set_max_workgroups): the setting is process-wide -- one value for
+ * every handle -- and may be set from any thread, also while other threads are inside the library.  It takes effect from the next
+ * voc_* call on: every call reads the settings once, as it begins, and a call in flight finishes under the settings it started
+ * with -- planning, every launch and the fp16-range check of one call see one arithmetic, so the redo above cannot be missed. */
 int voc_set_exact_fp32(int on);
 
 /* 1 (default): on the exact-f32 path a residual unit of the 96- / 192-channel decoder blocks (Snake, dilated 7-tap
  * conv, Snake, 1x1 conv, + input) runs as ONE launch whose intermediate stays in MFMA accumulators; 0: one launch
- * per conv (the 1x1 conv then sums its channels in a different order: results differ in the last f32 bit). */
+ * per conv (the 1x1 conv then sums its channels in a different order: results differ in the last f32 bit).
+ * Process-wide, any thread, from the next voc_* call on (voc_set_exact_fp32's contract). */
 int voc_set_fused_units(int on);
 
 /* Cap the workgroups each vocoder kernel launch occupies (0 = one per output tile, the default and the fastest for a decode that
@@ -240,7 +246,10 @@ int voc_set_fused_units(int on);
  * on MI355X, 32 utterances, frame loop of step s + 1 beside the decode of step s: exactly one workgroup per CU is the optimum
  * (the decode alone 89 -> 125 ms, the frame step beside it 2.40 -> 2.9 ms instead of starving, the whole step 244 -> 209 ms with the
  * frame loop's waves at raised priority, which the library's kernels set themselves); 320 / 384 / 512 / 768 workgroups: 239 / 228 /
- * 234 / 245 ms.  Returns the cap in effect.  Process-wide. */
+ * 234 / 245 ms.  Returns the cap in effect.
+ * Process-wide, any thread, from the next call on (voc_set_exact_fp32's contract) -- the next voc_*, and the next enc_* / spk_*
+ * call too: the encoders' convs run on the vocoder's exact-f32 launcher and follow the cap.  A call in flight keeps its grid.
+ * (n = -1 asks the HIP runtime for the current device's compute units, on the calling thread.) */
 int voc_set_max_workgroups(int n);
 
 /* GPU milliseconds of the last voc_decode (HIP events on the library's stream; voc_synthesize* leave it alone) and its FLOP

@@ -29,6 +29,7 @@ struct EncOp {
 
 struct Enc {
     int device = 0;
+    VocSettings cfg;                // the call's snapshot of the process-wide settings (enc_enter): voc_launch_conv's grid cap and fill
     int max_batch = 1, max_samples = 0, sample_rate = 24000, hop = 1, nq = 0;
     std::vector<EncOp> ops;
     DeviceAllocs mem;
@@ -55,9 +56,13 @@ struct Enc {
     uint64_t pcm_calls = 0;
 };
 
-static inline void enc_bind(const Enc* e) {
+// every entry point that touches the GPU: binds the thread to the handle's device and takes the call's one settings snapshot
+// (q3_voc_settings.h; the walks pass it to voc_launch_conv)
+static inline void enc_enter(Enc* e) {
+    if (!e) return;
     int d = -1;
-    if (e && (hipGetDevice(&d) != hipSuccess || d != e->device)) hipSetDevice(e->device);
+    if (hipGetDevice(&d) != hipSuccess || d != e->device) hipSetDevice(e->device);
+    e->cfg = voc_settings.load();
 }
 
 // the columns an op hands on from L: a strided conv pads a clip's end to whole strides, ceil(L / s)

@@ -326,7 +326,7 @@ int enc_run(Enc* e, int B, const std::vector<int>& lens0, int n_ops, float** out
             a.x = strided ? e->buf[3] : src;
             a.y = dst;
             if (op.flags & EF_RES_ADD) a.res = res;
-            if (voc_launch_conv(e->s, a, B)) return -1;
+            if (voc_launch_conv(e->s, a, B, e->cfg)) return -1;
             L = Lo;
             ld = enc_pitch(L);
         } else if (op.op == EOP_NORM) {
@@ -371,7 +371,7 @@ using namespace q3;
 extern "C" {
 
 void enc_free(void* h) {
-    enc_bind((Enc*)h);
+    enc_enter((Enc*)h);
     enc_destroy((Enc*)h);
 }
 
@@ -626,7 +626,7 @@ int enc_encode(void* h, const float* pcm, const int32_t* n_samples, int B, int64
         Q3_LOG("enc_encode: NULL handle");
         return -1;
     }
-    enc_bind(e);
+    enc_enter(e);
     if (!codes_out || !n_frames) {
         Q3_LOG("enc_encode: NULL codes_out or n_frames");
         return -1;
@@ -666,7 +666,7 @@ int enc_debug_shape(void* h, const int32_t* n_samples, int B, int n_ops, int* C,
 int enc_debug_run(void* h, const float* pcm, const int32_t* n_samples, int B, int n_ops, float* out, int* C, int* L) {
     Enc* e = (Enc*)h;
     if (!e || !out || n_ops < 1 || n_ops >= (int)e->ops.size()) return -1;
-    enc_bind(e);
+    enc_enter(e);
     std::vector<int> lens;
     if (enc_upload(e, pcm, n_samples, B, lens, "enc_debug_run")) return -1;
     float* act = nullptr;

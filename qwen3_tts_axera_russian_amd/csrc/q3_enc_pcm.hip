@@ -209,7 +209,7 @@ int enc_encode_pcm(void* h, const void* pcm, int format, int channels, int rate,
         Q3_LOG("enc_encode_pcm: NULL handle");
         return -1;
     }
-    enc_bind(e);
+    enc_enter(e);
     if (!codes_out || !n_frames) {
         Q3_LOG("enc_encode_pcm: NULL codes_out or n_frames");
         return -1;
@@ -239,7 +239,7 @@ int enc_resample_pcm(void* h, const void* pcm, int format, int channels, int rat
         Q3_LOG("enc_resample_pcm: NULL handle");
         return -1;
     }
-    enc_bind(e);
+    enc_enter(e);
     if (!out || !n_out) {
         Q3_LOG("enc_resample_pcm: NULL out or n_out");
         return -1;
@@ -268,7 +268,7 @@ int enc_debug_pcm(void* h, const void* pcm, int format, int channels, int rate, 
                   int32_t* n_out, int* ld) {
     Enc* e = (Enc*)h;
     if (!e || !out || !n_out || !ld) return -1;
-    enc_bind(e);
+    enc_enter(e);
     std::vector<int> lens;
     if (enc_pcm_prepare(e, pcm, format, channels, rate, n_in, B, lens, "enc_debug_pcm")) return -1;
     const long pitch = enc_pitch(*std::max_element(lens.begin(), lens.begin() + B));

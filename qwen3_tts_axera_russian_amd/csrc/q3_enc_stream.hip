@@ -179,7 +179,7 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
                     a.x = s->buf[u];
                     a.y = s->buf[d];
                     (*launches)++;
-                    if (!dry && voc_launch_conv(e->s, a, B)) return -1;
+                    if (!dry && voc_launch_conv(e->s, a, B, e->cfg)) return -1;
                     cur = d;
                 }
             }
@@ -233,7 +233,7 @@ int walk(EncStream* s, const std::vector<long long>& key, int B, bool dry, bool 
             a.x = s->buf[cur];
             a.y = s->buf[d];
             (*launches)++;
-            if (!dry && voc_launch_conv(e->s, a, B)) return -1;
+            if (!dry && voc_launch_conv(e->s, a, B, e->cfg)) return -1;
             if (op.flags & EF_RES_ADD) res = -1;
             if (op.flags & EF_TO_RES) {   // a conv shortcut: the activation stays
                 res = d;
@@ -283,7 +283,7 @@ int enc_stream_push_impl(EncStream* s, int n, const int32_t* streams, const floa
         return -1;
     }
     Enc* e = s->e;
-    enc_bind(e);
+    enc_enter(e);
     Plan p;
     const int source = feed ? ENC_SRC_PCM : ENC_SRC_F32;
     if (make_plan(s, n, streams, n_new, finish, source, p)) return -1;
@@ -388,7 +388,7 @@ extern "C" {
 void enc_stream_free(void* ss) {
     EncStream* s = (EncStream*)ss;
     if (!s) return;
-    enc_bind(s->e);
+    enc_enter(s->e);
     hipStreamSynchronize(s->e->s);
     enc_stream_pcm_release(s);
     delete s;   // (its allocations go with it: DeviceAllocs)
@@ -400,7 +400,7 @@ void* enc_stream_create(void* h, int max_streams, int max_push_samples) {
         Q3_LOG("enc_stream_create: needs an encoder handle, max_streams > 0 and max_push_samples > 0");
         return nullptr;
     }
-    enc_bind(e);
+    enc_enter(e);
     EncStream* s = new EncStream;
     s->e = e;
     s->max_streams = max_streams;
@@ -498,7 +498,7 @@ void* enc_stream_create(void* h, int max_streams, int max_push_samples) {
 int enc_stream_reset(void* ss, int stream) {
     EncStream* s = (EncStream*)ss;
     if (!s || stream < 0 || stream >= s->max_streams) return -1;
-    enc_bind(s->e);
+    enc_enter(s->e);
     if (s->state_floats)   // the causal padding again (ordered before the next push on the handle's stream)
         Q3_HIP(hipMemsetAsync(s->d_hist + (size_t)stream * s->state_floats, 0, sizeof(float) * s->state_floats, s->e->s), -1);
     s->total[stream] = 0;

@@ -269,8 +269,7 @@ int push_pcm(EncStream* s, int n, const int32_t* streams, const void* pcm, int f
         Q3_LOG("%s: NULL object or offsets", WHO);
         return -1;
     }
-    enc_bind(s->e);
-    Feed f;
+    Feed f;   // (host work up to enc_stream_push_impl, which enters the handle)
     std::vector<int32_t> n_new;
     if (!check_push(s, n, streams, format, channels, rate, n_in, finish, &f.p, n_new)) return -1;
     f.first.assign(n, 0);

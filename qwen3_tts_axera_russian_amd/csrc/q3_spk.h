@@ -59,6 +59,7 @@ struct SpkBlock {
 
 struct Spk {
     int device = 0, max_batch = 1, max_samples = 0, max_frames = 0, min_frames = 5;
+    VocSettings cfg;   // the call's snapshot of the process-wide settings (spk_enter): voc_launch_conv's grid cap and fill
     int sample_rate = 24000, n_fft = 1024, hop = 256, pad = 384, n_mels = 128;
     double mel_floor = 1e-5, mag_eps = 1e-9;
     int C = 0, Cm = 0, scale = 8, dim = 0;   // block width, aggregated width (the SE blocks' outputs side by side)
@@ -80,9 +81,12 @@ struct Spk {
     int run_B = 0, run_L = 0, run_ld = 0;
 };
 
-static inline void spk_bind(const Spk* e) {
+// every entry point that touches the GPU: binds the thread to the handle's device and takes the call's one settings snapshot
+static inline void spk_enter(Spk* e) {
+    if (!e) return;
     int d = -1;
-    if (e && (hipGetDevice(&d) != hipSuccess || d != e->device)) hipSetDevice(e->device);
+    if (hipGetDevice(&d) != hipSuccess || d != e->device) hipSetDevice(e->device);
+    e->cfg = voc_settings.load();
 }
 
 // rows are [clip][channel] at a pitch of the call's longest clip's frames rounded up to 32 floats

@@ -316,7 +316,7 @@ struct SpkWalk {
         a.x = x;
         a.y = y;
         launches++;
-        return voc_launch_conv(e->s, a, B);
+        return voc_launch_conv(e->s, a, B, e->cfg);
     }
     int unfold(const SpkConv& c, const float* x, int Cx, int c0, const float* x2, int Cx2, int c02) {
         launches++;
@@ -464,7 +464,7 @@ static int spk_upload(Spk* e, const float* pcm, const int32_t* n, int B, std::ve
 
 static int spk_debug(Spk* e, const float* pcm, const int32_t* n, int B, int stage, float* out, int* C, int* L, const char* who) {
     if (!e || !out || !C || !L) return -1;
-    spk_bind(e);
+    spk_enter(e);
     const int last = (int)e->blocks.size() + 3;
     if (stage > last) {
         Q3_LOG("%s: stage %d past the last (%d)", who, stage, last);
@@ -503,7 +503,7 @@ using namespace q3;
 extern "C" {
 
 void spk_free(void* h) {
-    spk_bind((Spk*)h);
+    spk_enter((Spk*)h);
     spk_destroy((Spk*)h);
 }
 
@@ -716,7 +716,7 @@ int spk_embed(void* h, const float* pcm, const int32_t* n_samples, int B, float*
         Q3_LOG("spk_embed: NULL handle");
         return -1;
     }
-    spk_bind(e);
+    spk_enter(e);
     if (!out) {
         Q3_LOG("spk_embed: NULL out");
         return -1;

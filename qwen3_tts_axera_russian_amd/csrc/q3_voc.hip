@@ -18,9 +18,6 @@
 
 namespace q3 {
 
-int g_voc_split = 1;          // (q3_voc_program.h)
-static int g_voc_fuse = 1;    // 1 (default): residual units at 96 / 192 channels run fused on the exact path
-
 // host -> device on the handle's stream, complete on return (loading: the source may be a temporary)
 static bool voc_upload(Voc* v, void* d, const void* src, size_t bytes) {
     return hipMemcpyAsync(d, src, bytes, hipMemcpyHostToDevice, v->s) == hipSuccess && hipStreamSynchronize(v->s) == hipSuccess;
@@ -94,7 +91,7 @@ using namespace q3;
 extern "C" {
 
 void voc_free(void* vv) {
-    voc_bind((Voc*)vv);
+    voc_enter((Voc*)vv);
     voc_destroy((Voc*)vv);
 }
 
@@ -113,7 +110,7 @@ void* voc_load(const char* weights, int chunk_tokens, int max_batch) {
         return nullptr;
     }
     // (any chunk length decodes; the chunk walk needs chunk > 32 and says so itself: plan_walk)
-    if (const char* ex = getenv("Q3_VOC_EXACT")) g_voc_split = atoi(ex) ? 0 : 1;
+    if (const char* ex = getenv("Q3_VOC_EXACT")) voc_settings.set_exact_fp32(atoi(ex));
     Voc* v = new Voc();
     hipGetDevice(&v->device);
     v->chunk = chunk_tokens > 0 ? chunk_tokens : 64;
@@ -438,14 +435,22 @@ void* voc_load(const char* weights, int chunk_tokens, int max_batch) {
     return v;
 }
 
-// 1: every call decodes on the exact-fp32 MFMA path; 0 (default): the split-precision fp16 path where it is built.  Process-wide.
+}  // extern "C"
+
+// the process's settings: written here and by the setters of q3_voc_kernels.hip, loaded by entry points only (q3_voc_settings.h)
+q3::VocSettingsStore q3::voc_settings;
+
+extern "C" {
+
+// 1: every call decodes on the exact-fp32 MFMA path; 0 (default): the split-precision fp16 path where it is built.  Process-wide,
+// from the next call on (q3_voc_settings.h).
 int voc_set_exact_fp32(int on) {
-    g_voc_split = on ? 0 : 1;
+    voc_settings.set_exact_fp32(on);
     return 0;
 }
 
 int voc_set_fused_units(int on) {   // 1 (default): residual units at 96 / 192 channels run as one launch (exact path)
-    g_voc_fuse = on ? 1 : 0;
+    voc_settings.set_fused_units(on);
     return 0;
 }
 
@@ -526,7 +531,7 @@ ResUnitArgs voc_resunit_args(const VocOp& op, const VocOp& op1, const float* in,
 
 bool voc_fused_unit(const Voc* v, size_t i, size_t n_ops) {
     const VocOp& op = v->ops[i];
-    return g_voc_fuse && op.op == VOP_CONV && op.k == 7 && (op.flags & VF_RES_SAVE) && (op.flags & VF_SNAKE) && op.cin == op.cout &&
+    return v->cfg.fuse && op.op == VOP_CONV && op.k == 7 && (op.flags & VF_RES_SAVE) && (op.flags & VF_SNAKE) && op.cin == op.cout &&
            resunit_channels(op.cin) && i + 1 < n_ops && v->ops[i + 1].w1p;
 }
 
@@ -603,7 +608,7 @@ static int voc_conv_split(Voc* v, const VocOp& op, const VocOp* next, bool last,
         sa.y = v->buf[out_f32];
     }
     if (want_planes) voc_split_out_planes(sa, *next, v->plane[2 * (in_set ^ 1)], v->plane[2 * (in_set ^ 1) + 1]);
-    if (launch_conv_split(v->s, sa, voc_split_taps(op), B)) return -1;
+    if (launch_conv_split(v->s, sa, voc_split_taps(op), B, v->cfg)) return -1;
     if (want_f32) {
         st.f32_idx = out_f32;
         st.f32_cur = true;
@@ -666,7 +671,7 @@ int voc_run(Voc* v, int B, float** out_dev, int n_ops, int* outC, long* outL, fl
             }
             C = op.cout;
             wrote_f32();
-        } else if (g_voc_split && !force_exact && op.w_hi) {
+        } else if (v->cfg.split && !force_exact && op.w_hi) {
             const bool last = i + 1 == nrun;
             const VocOp* next = (i + 1 < v->ops.size()) ? &v->ops[i + 1] : nullptr;
             if (voc_conv_split(v, op, last ? nullptr : next, last, B, L, st)) {
@@ -679,7 +684,7 @@ int voc_run(Voc* v, int B, float** out_dev, int n_ops, int* outC, long* outL, fl
         } else if (voc_fused_unit(v, i, nrun) && st.f32_cur) {
             // a whole residual unit (this 7-tap conv + the 1x1 conv that closes it) in one launch
             cur = st.f32_idx;
-            if (launch_resunit(v->s, voc_resunit_args(op, v->ops[i + 1], v->buf[cur], v->buf[cur ^ 1], L), op.cin, B)) return -1;
+            if (launch_resunit(v->s, voc_resunit_args(op, v->ops[i + 1], v->buf[cur], v->buf[cur ^ 1], L), op.cin, B, v->cfg)) return -1;
             wrote_f32();
             i++;   // the 1x1 conv is done
             if (op_ms) op_ms[i] = 0.f;
@@ -690,7 +695,7 @@ int voc_run(Voc* v, int B, float** out_dev, int n_ops, int* outC, long* outL, fl
             a.y = v->buf[cur ^ 1];
             a.x = (op.flags & VF_RES_SAVE) ? save_res() : v->buf[cur];
             if (op.flags & VF_RES_ADD) a.res = res ? res : st.res;
-            if (voc_launch_conv(v->s, a, B)) return -1;
+            if (voc_launch_conv(v->s, a, B, v->cfg)) return -1;
             C = op.cout;
             if (op.op == VOP_CONVT) L = convt_out(op, L), Lf = convt_out(op, Lf);
             wrote_f32();
@@ -714,7 +719,7 @@ extern "C" {
 
 int voc_decode(void* vv, const int64_t* codes, int B, float* out) {
     Voc* v = (Voc*)vv;
-    voc_bind(v);
+    voc_enter(v);
     if (!v || !codes || !out || B <= 0 || B > v->max_batch) return -1;
     Q3_HIP(hipMemcpyAsync(v->d_codes, codes, sizeof(int64_t) * 16 * (size_t)v->chunk * B, hipMemcpyHostToDevice, v->s), -1);
     // rows of chunk_samples floats at the device pitch -> dense [B][chunk_samples] in the pinned staging -> out
@@ -726,7 +731,7 @@ int voc_decode(void* vv, const int64_t* codes, int B, float* out) {
         if (voc_run(v, B, &res, -1, nullptr, nullptr, nullptr, exact)) return -1;
         Q3_HIP(hipEventRecord(v->e1, v->s), -1);
         if (!exact) *v->h_ovf = 0;
-        if (!exact && g_voc_split) Q3_HIP(hipMemcpyAsync(v->h_ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
+        if (!exact && v->cfg.split) Q3_HIP(hipMemcpyAsync(v->h_ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
         Q3_HIP(hipMemcpy2DAsync(v->h_stage, row, res, dpitch, row, (size_t)B, hipMemcpyDeviceToHost, v->s), -1);
         Q3_HIP(hipStreamSynchronize(v->s), -1);
         return 0;
@@ -748,7 +753,7 @@ int voc_decode(void* vv, const int64_t* codes, int B, float* out) {
 // test hook: per-op GPU milliseconds of one decode of B chunks (codes already uploaded by a previous voc_decode)
 int voc_debug_profile(void* vv, int B, float* op_ms, int max_ops) {
     Voc* v = (Voc*)vv;
-    voc_bind(v);
+    voc_enter(v);
     if (!v || B <= 0 || B > v->max_batch || (int)v->ops.size() > max_ops) return -1;
     float* res = nullptr;
     if (voc_run(v, B, &res, -1, nullptr, nullptr, op_ms)) return -1;
@@ -758,7 +763,7 @@ int voc_debug_profile(void* vv, int B, float* op_ms, int max_ops) {
 // test hook: run only the first n_ops ops, return the activation [B][C][L]
 int voc_debug_run(void* vv, const int64_t* codes, int B, int n_ops, float* out, int* C, int* L) {
     Voc* v = (Voc*)vv;
-    voc_bind(v);
+    voc_enter(v);
     if (!v || B <= 0 || B > v->max_batch) return -1;
     Q3_HIP(hipMemcpyAsync(v->d_codes, codes, sizeof(int64_t) * 16 * (size_t)v->chunk * B, hipMemcpyHostToDevice, v->s), -1);
     float* res = nullptr;

@@ -20,20 +20,17 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float elu1(float x) { return x > 0.f ? x : expm1f(x); }   // ELU, alpha = 1
 
-static int g_voc_max_wgs = 0;  // 0 = one workgroup per tile; >0 caps the grid (persistent tile loop)
-// test hooks (voc_set_fill, voc_debug_last_variant at the end of this file; host side only)
-static int g_voc_fill = -1;    // < 0: the built-in workgroup target of the tile-height rules (512); >= 0 replaces it
-// the instantiation the last conv (or full-chunk attention) launch of this process took (a few plain stores per launch; named on
-// request)
+// test hook (voc_debug_last_variant at the end of this file; host side only): the instantiation the last conv (or full-chunk
+// attention) launch of this thread took (a few plain stores per launch; named on request)
 enum { VV_NONE, VV_CONV, VV_OUT1, VV_RESUNIT, VV_SNAKE_SPLIT, VV_SPLIT, VV_ATTN_TILE, VV_ATTN };
-static struct {
+static thread_local struct {
     int kind = VV_NONE, p[5] = {0, 0, 0, 0, 0};
     bool after_pass = false;   // split conv: its planes came from snake_split_kernel right before it
-} g_voc_variant;
+} voc_variant;
 static inline void voc_note_variant(int kind, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0) {
-    g_voc_variant.after_pass = kind == VV_SPLIT && g_voc_variant.kind == VV_SNAKE_SPLIT;
-    g_voc_variant.kind = kind;
-    g_voc_variant.p[0] = a, g_voc_variant.p[1] = b, g_voc_variant.p[2] = c, g_voc_variant.p[3] = d, g_voc_variant.p[4] = e;
+    voc_variant.after_pass = kind == VV_SPLIT && voc_variant.kind == VV_SNAKE_SPLIT;
+    voc_variant.kind = kind;
+    voc_variant.p[0] = a, voc_variant.p[1] = b, voc_variant.p[2] = c, voc_variant.p[3] = d, voc_variant.p[4] = e;
 }
 constexpr int VKC = 8;     // input channels per LDS stage
 constexpr int VTN = 128;   // output columns per workgroup (4 waves x 32)
@@ -302,13 +299,13 @@ __global__ void __launch_bounds__(256, (KC >= 32 && MT >= 3) ? 2 : (MT >= 4 ? 3 
 }
 
 template <int MT, int KT, int KC, bool CT = false, int ACT = -1>
-static int launch_conv_t(hipStream_t s, const ConvArgs& a, int B) {
+static int launch_conv_t(hipStream_t s, const ConvArgs& a, int B, const VocSettings& cfg) {
     if constexpr (!CT && KT <= 2) {
-        if (a.stride > 1 && a.res == nullptr) return launch_conv_t<MT, KT, KC, true, ACT>(s, a, B);
+        if (a.stride > 1 && a.res == nullptr) return launch_conv_t<MT, KT, KC, true, ACT>(s, a, B, cfg);
     }
     if constexpr (ACT < 0) {      // the input activation becomes a template argument
         if (a.elu) {
-            if constexpr (!CT && KC == 16 && (KT == 1 || KT == 3)) return launch_conv_t<MT, KT, KC, CT, 4>(s, a, B);
+            if constexpr (!CT && KC == 16 && (KT == 1 || KT == 3)) return launch_conv_t<MT, KT, KC, CT, 4>(s, a, B, cfg);
             Q3_LOG("voc conv: ELU input is built for 1- and 3-tap convs at 16 channels per stage only");
             return -1;
         }
@@ -317,9 +314,9 @@ static int launch_conv_t(hipStream_t s, const ConvArgs& a, int B) {
             return -1;
         }
         // (only the variant the long Snake 1 x 1 convs run is specialised: every further one is another kernel to compile)
-        if constexpr (!(KT == 1 && KC == 16 && MT == 4 && !CT)) return launch_conv_t<MT, KT, KC, CT, 3>(s, a, B);
-        else return a.alpha ? launch_conv_t<MT, KT, KC, CT, 1>(s, a, B) : a.gelu ? launch_conv_t<MT, KT, KC, CT, 2>(s, a, B)
-                                                                             : launch_conv_t<MT, KT, KC, CT, 0>(s, a, B);
+        if constexpr (!(KT == 1 && KC == 16 && MT == 4 && !CT)) return launch_conv_t<MT, KT, KC, CT, 3>(s, a, B, cfg);
+        else return a.alpha ? launch_conv_t<MT, KT, KC, CT, 1>(s, a, B, cfg) : a.gelu ? launch_conv_t<MT, KT, KC, CT, 2>(s, a, B, cfg)
+                                                                             : launch_conv_t<MT, KT, KC, CT, 0>(s, a, B, cfg);
     } else {
     constexpr int TM = 32 * MT, TMP = voc_wpitch(TM);
     const int halo = (KT - 1) * a.dil;
@@ -357,7 +354,7 @@ static int launch_conv_t(hipStream_t s, const ConvArgs& a, int B) {
     c.tiles_m = (a.M + TM - 1) / TM;
     c.n_tiles = c.tiles_l * c.tiles_m * (c.flat_B > 0 ? 1 : B);
     int grid = c.n_tiles;
-    if (g_voc_max_wgs > 0 && grid > g_voc_max_wgs) grid = g_voc_max_wgs;
+    if (cfg.max_wgs > 0 && grid > cfg.max_wgs) grid = cfg.max_wgs;
     voc_note_variant(VV_CONV, MT, KT, KC, CT ? 1 : 0, ACT);
     hipLaunchKernelGGL((conv_kernel<MT, KT, KC, CT, ACT>), dim3(grid), dim3(256), lds, s, c);
     Q3_HIP(hipGetLastError(), -1);
@@ -366,7 +363,7 @@ static int launch_conv_t(hipStream_t s, const ConvArgs& a, int B) {
 }
 
 template <int KT, int KC>
-static int launch_conv_mt(hipStream_t s, const ConvArgs& a, int B) {
+static int launch_conv_mt(hipStream_t s, const ConvArgs& a, int B, const VocSettings& cfg) {
     const int t32 = (a.M + 31) / 32;  // 32-row MFMA tiles needed
     int mt = 4;
     if (t32 % 4 != 0) mt = (t32 % 3 == 0) ? 3 : (t32 % 2 == 0) ? 2 : (t32 < 4 ? t32 : 4);
@@ -375,17 +372,17 @@ static int launch_conv_mt(hipStream_t s, const ConvArgs& a, int B) {
     // covers the chip
     // covers the chip twice (measured, 32 chunks: pre-transformer 5.8 -> 4.2 ms, the 4096 -> 1024 ConvNeXt conv 0.83 -> 0.62)
     static const int fill_env = getenv("Q3_VOC_FILL") ? atoi(getenv("Q3_VOC_FILL")) : 512;
-    const int fill = g_voc_fill >= 0 ? g_voc_fill : fill_env;
+    const int fill = cfg.fill >= 0 ? cfg.fill : fill_env;
     if (fill > 0) {
         const long cols = (KT == 1 && a.stride == 1) ? (long)a.ldx * B : (long)a.Lc;
         const long col_tiles = (cols + VTN - 1) / VTN * ((KT == 1 && a.stride == 1) ? 1 : B);
         while (mt > 1 && col_tiles * ((t32 + mt - 1) / mt) < fill) mt = (mt == 4 || mt == 2) ? mt / 2 : 1;
     }
     switch (mt) {
-        case 1: return launch_conv_t<1, KT, KC>(s, a, B);
-        case 2: return launch_conv_t<2, KT, KC>(s, a, B);
-        case 3: return launch_conv_t<3, KT, KC>(s, a, B);
-        default: return launch_conv_t<4, KT, KC>(s, a, B);
+        case 1: return launch_conv_t<1, KT, KC>(s, a, B, cfg);
+        case 2: return launch_conv_t<2, KT, KC>(s, a, B, cfg);
+        case 3: return launch_conv_t<3, KT, KC>(s, a, B, cfg);
+        default: return launch_conv_t<4, KT, KC>(s, a, B, cfg);
     }
 }
 
@@ -446,7 +443,7 @@ __global__ void __launch_bounds__(256) conv_out1_kernel(ConvArgs a) {
     }
 }
 
-int voc_launch_conv(hipStream_t s, const ConvArgs& a, int B) {
+int voc_launch_conv(hipStream_t s, const ConvArgs& a, int B, const VocSettings& cfg) {
     const int c = a.Cin;
     if (c % 8) {
         Q3_LOG("voc conv: Cin=%d is not a multiple of 8", c);
@@ -457,7 +454,7 @@ int voc_launch_conv(hipStream_t s, const ConvArgs& a, int B) {
             Q3_LOG("voc conv: ELU input needs a 1- or 3-tap stride-1 conv over a multiple of 16 channels (got %d taps, %d channels)", a.K, c);
             return -1;
         }
-        return a.K == 1 ? launch_conv_mt<1, 16>(s, a, B) : launch_conv_mt<3, 16>(s, a, B);
+        return a.K == 1 ? launch_conv_mt<1, 16>(s, a, B, cfg) : launch_conv_mt<3, 16>(s, a, B, cfg);
     }
     static const int out1 = getenv("Q3_VOC_OUT1") ? atoi(getenv("Q3_VOC_OUT1")) : 1;
     if (out1 && a.M == 1 && a.K == 7 && a.dil == 1 && a.stride == 1 && !a.res && !a.gelu && (a.ldx & 3) == 0 &&
@@ -482,12 +479,12 @@ int voc_launch_conv(hipStream_t s, const ConvArgs& a, int B) {
     // batch, and with two taps the stage width changes the order in which taps and channels are summed)
     const bool short_act = (a.Lrule > 0 ? a.Lrule : a.Lc) <= 512 && a.M <= 4096 && c % 32 == 0 && a.K <= 2;   // (not the 1536 -> 768 x 8 transposed conv: 2.92 -> 3.10 ms)
     if (kc_max < 32 && !short_act && c % 16 == 0 && (a.K == 1 || a.K == 2))
-        return a.K == 1 ? launch_conv_mt<1, 16>(s, a, B) : launch_conv_mt<2, 16>(s, a, B);
+        return a.K == 1 ? launch_conv_mt<1, 16>(s, a, B, cfg) : launch_conv_mt<2, 16>(s, a, B, cfg);
     switch (a.K) {
-        case 1: return c % 32 == 0 ? launch_conv_mt<1, 32>(s, a, B) : c % 16 == 0 ? launch_conv_mt<1, 16>(s, a, B) : launch_conv_mt<1, 8>(s, a, B);
-        case 2: return c % 32 == 0 ? launch_conv_mt<2, 32>(s, a, B) : c % 16 == 0 ? launch_conv_mt<2, 16>(s, a, B) : launch_conv_mt<2, 8>(s, a, B);
-        case 3: return c % 16 == 0 ? launch_conv_mt<3, 16>(s, a, B) : launch_conv_mt<3, 8>(s, a, B);
-        case 7: return launch_conv_mt<7, 8>(s, a, B);
+        case 1: return c % 32 == 0 ? launch_conv_mt<1, 32>(s, a, B, cfg) : c % 16 == 0 ? launch_conv_mt<1, 16>(s, a, B, cfg) : launch_conv_mt<1, 8>(s, a, B, cfg);
+        case 2: return c % 32 == 0 ? launch_conv_mt<2, 32>(s, a, B, cfg) : c % 16 == 0 ? launch_conv_mt<2, 16>(s, a, B, cfg) : launch_conv_mt<2, 8>(s, a, B, cfg);
+        case 3: return c % 16 == 0 ? launch_conv_mt<3, 16>(s, a, B, cfg) : launch_conv_mt<3, 8>(s, a, B, cfg);
+        case 7: return launch_conv_mt<7, 8>(s, a, B, cfg);
         default:
             Q3_LOG("voc conv: kernel with %d taps is not built (1, 2, 3, 7 are)", a.K);
             return -1;
@@ -647,7 +644,7 @@ __global__ void __launch_bounds__(256, MT <= 3 ? 3 : 2) resunit_kernel(ResUnitAr
 }
 
 template <int MT>
-static int launch_resunit_t(hipStream_t s, ResUnitArgs a, int B) {
+static int launch_resunit_t(hipStream_t s, ResUnitArgs a, int B, const VocSettings& cfg) {
     constexpr int C = 32 * MT;
     const int halo = 6 * a.dil;
     if (a.dil > 9) return -1;
@@ -655,7 +652,7 @@ static int launch_resunit_t(hipStream_t s, ResUnitArgs a, int B) {
     a.tiles_l = (a.Lin + VTN - 1) / VTN;
     a.n_tiles = a.tiles_l * B;
     int grid = a.n_tiles;
-    if (g_voc_max_wgs > 0 && grid > g_voc_max_wgs) grid = g_voc_max_wgs;
+    if (cfg.max_wgs > 0 && grid > cfg.max_wgs) grid = cfg.max_wgs;
     voc_note_variant(VV_RESUNIT, MT);
     hipLaunchKernelGGL((resunit_kernel<MT>), dim3(grid), dim3(256), lds, s, a);
     Q3_HIP(hipGetLastError(), -1);
@@ -664,8 +661,8 @@ static int launch_resunit_t(hipStream_t s, ResUnitArgs a, int B) {
 
 bool resunit_channels(int c) { return c == 96 || c == 192; }
 
-int launch_resunit(hipStream_t s, const ResUnitArgs& a, int C, int B) {
-    return C == 96 ? launch_resunit_t<3>(s, a, B) : C == 192 ? launch_resunit_t<6>(s, a, B) : -1;
+int launch_resunit(hipStream_t s, const ResUnitArgs& a, int C, int B, const VocSettings& cfg) {
+    return C == 96 ? launch_resunit_t<3>(s, a, B, cfg) : C == 192 ? launch_resunit_t<6>(s, a, B, cfg) : -1;
 }
 
 // ---------------------------------------------------------------------------
@@ -895,7 +892,7 @@ __global__ void __launch_bounds__(256, NJ == 1 ? 3 : 2) conv_split_kernel(SplitA
 }
 
 template <int KT, int KS, int MW, int NJ>
-static int launch_conv_split_t(hipStream_t s, const SplitArgs& a, int B) {
+static int launch_conv_split_t(hipStream_t s, const SplitArgs& a, int B, const VocSettings& cfg) {
     constexpr int STM = 32 * MW, STN = 128 * NJ;
     if (a.dil > 9) return -1;
     const int halo = (KT - 1) * a.dil;
@@ -915,42 +912,40 @@ static int launch_conv_split_t(hipStream_t s, const SplitArgs& a, int B) {
     c.my_fast = c.tiles_m > 1 && (size_t)a.Cin * a.Mp * KT * 4 <= (size_t)2 << 20;
     if (c.my_fast) c.n_tiles = (c.tiles_l * B + 7) / 8 * 8 * c.tiles_m;
     int grid = c.n_tiles;
-    if (g_voc_max_wgs > 0 && grid > g_voc_max_wgs) grid = g_voc_max_wgs;
+    if (cfg.max_wgs > 0 && grid > cfg.max_wgs) grid = cfg.max_wgs;
     voc_note_variant(VV_SPLIT, KT, KS, MW, NJ, c.my_fast);
     hipLaunchKernelGGL((conv_split_kernel<KT, KS, MW, NJ>), dim3(grid), dim3(256), lds, s, c);
     Q3_HIP(hipGetLastError(), -1);
     return 0;
 }
 
-static int g_voc_narrow_k1 = 1;   // 128-column tiles (three workgroups per CU) for the 1-tap convs
-
 template <int MW>
-static int launch_conv_split_m(hipStream_t s, const SplitArgs& a, int K, int B) {
+static int launch_conv_split_m(hipStream_t s, const SplitArgs& a, int K, int B, const VocSettings& cfg) {
     const int c16 = a.Cin / 16;
     switch (K) {
         case 1:
-            if (g_voc_narrow_k1 && MW == 3)
-                return c16 % 3 == 0 ? launch_conv_split_t<1, 3, MW, 1>(s, a, B) : c16 % 2 == 0 ? launch_conv_split_t<1, 2, MW, 1>(s, a, B) : launch_conv_split_t<1, 1, MW, 1>(s, a, B);
-            return c16 % 3 == 0 ? launch_conv_split_t<1, 3, MW, 2>(s, a, B) : c16 % 2 == 0 ? launch_conv_split_t<1, 2, MW, 2>(s, a, B) : launch_conv_split_t<1, 1, MW, 2>(s, a, B);
+            if (cfg.narrow_k1 && MW == 3)
+                return c16 % 3 == 0 ? launch_conv_split_t<1, 3, MW, 1>(s, a, B, cfg) : c16 % 2 == 0 ? launch_conv_split_t<1, 2, MW, 1>(s, a, B, cfg) : launch_conv_split_t<1, 1, MW, 1>(s, a, B, cfg);
+            return c16 % 3 == 0 ? launch_conv_split_t<1, 3, MW, 2>(s, a, B, cfg) : c16 % 2 == 0 ? launch_conv_split_t<1, 2, MW, 2>(s, a, B, cfg) : launch_conv_split_t<1, 1, MW, 2>(s, a, B, cfg);
         case 2:
-            if (g_voc_narrow_k1 && MW == 3 && a.Cin <= 384)   // the HBM-bound transposed convs (measured: 1536 -> 768 loses)
-                return c16 % 2 == 0 ? launch_conv_split_t<2, 2, MW, 1>(s, a, B) : launch_conv_split_t<2, 1, MW, 1>(s, a, B);
-            return c16 % 2 == 0 ? launch_conv_split_t<2, 2, MW, 2>(s, a, B) : launch_conv_split_t<2, 1, MW, 2>(s, a, B);
-        case 3: return c16 % 2 == 0 && MW == 2 ? launch_conv_split_t<3, 2, MW, 2>(s, a, B) : launch_conv_split_t<3, 1, MW, 2>(s, a, B);
+            if (cfg.narrow_k1 && MW == 3 && a.Cin <= 384)   // the HBM-bound transposed convs (measured: 1536 -> 768 loses)
+                return c16 % 2 == 0 ? launch_conv_split_t<2, 2, MW, 1>(s, a, B, cfg) : launch_conv_split_t<2, 1, MW, 1>(s, a, B, cfg);
+            return c16 % 2 == 0 ? launch_conv_split_t<2, 2, MW, 2>(s, a, B, cfg) : launch_conv_split_t<2, 1, MW, 2>(s, a, B, cfg);
+        case 3: return c16 % 2 == 0 && MW == 2 ? launch_conv_split_t<3, 2, MW, 2>(s, a, B, cfg) : launch_conv_split_t<3, 1, MW, 2>(s, a, B, cfg);
         case 7:
-            if (g_voc_narrow_k1 && a.Cin <= 192) return launch_conv_split_t<7, 1, MW, 1>(s, a, B);   // the HBM-bound blocks: -4..9 %
-            return launch_conv_split_t<7, 1, MW, 2>(s, a, B);
+            if (cfg.narrow_k1 && a.Cin <= 192) return launch_conv_split_t<7, 1, MW, 1>(s, a, B, cfg);   // the HBM-bound blocks: -4..9 %
+            return launch_conv_split_t<7, 1, MW, 2>(s, a, B, cfg);
         default: return -1;
     }
 }
 
-int launch_conv_split(hipStream_t s, const SplitArgs& a, int K, int B) {
+int launch_conv_split(hipStream_t s, const SplitArgs& a, int K, int B, const VocSettings& cfg) {
     // 96-row tiles where they tile the rows exactly (every channel count of the decoder blocks) and still
     // give the chip enough workgroups: the input tile is read by Cout/96 workgroups instead of Cout/64
     const long tiles96 = (long)((a.Lc + 255) / 256) * (a.M / 96) * B;
     const bool fits96 = a.M % 96 == 0 && a.Mp % 96 == 0;
-    const bool use96 = fits96 && (a.Mp % 64 != 0 || tiles96 >= (g_voc_fill >= 0 ? g_voc_fill : 512));
-    return use96 ? launch_conv_split_m<3>(s, a, K, B) : launch_conv_split_m<2>(s, a, K, B);
+    const bool use96 = fits96 && (a.Mp % 64 != 0 || tiles96 >= (cfg.fill >= 0 ? cfg.fill : 512));
+    return use96 ? launch_conv_split_m<3>(s, a, K, B, cfg) : launch_conv_split_m<2>(s, a, K, B, cfg);
 }
 
 // ---------------------------------------------------------------------------
@@ -1601,7 +1596,7 @@ using namespace q3;
 extern "C" {
 
 int voc_set_narrow_k1(int on) {   // test hook: 128-column tiles for the 1-tap convs (default on)
-    g_voc_narrow_k1 = on ? 1 : 0;
+    voc_settings.set_narrow_k1(on);
     return 0;
 }
 
@@ -1609,17 +1604,16 @@ int voc_set_narrow_k1(int on) {   // test hook: 128-column tiles for the 1-tap c
 // Q3_VOC_FILL for the exact path).  n >= 0 replaces it for the process (0: tile height follows divisibility alone), n < 0
 // restores the default.  -> the value set.
 int voc_set_fill(int n) {
-    g_voc_fill = n < 0 ? -1 : n;
-    return g_voc_fill;
+    return voc_settings.set_fill(n);
 }
 
-// test hook: the instantiation the last conv launch took ("conv<4,1,16,ct0,act1>", "out1", "resunit<3>",
+// test hook: the instantiation the last conv launch of the calling thread took ("conv<4,1,16,ct0,act1>", "out1", "resunit<3>",
 // "split<7,1,3,1>/myfast", "snake_split", or "snake_split+split<...>" for a split conv that read the separate pass's planes;
 // "attn_tile" / "attn" after a full-chunk attention launch; "" before the first one)
 const char* voc_debug_last_variant() {
-    static char name[64];
-    const int* p = g_voc_variant.p;
-    switch (g_voc_variant.kind) {
+    static thread_local char name[64];
+    const int* p = voc_variant.p;
+    switch (voc_variant.kind) {
         case VV_CONV: snprintf(name, sizeof(name), "conv<%d,%d,%d,ct%d,act%d>", p[0], p[1], p[2], p[3], p[4]); break;
         case VV_OUT1: snprintf(name, sizeof(name), "out1"); break;
         case VV_RESUNIT: snprintf(name, sizeof(name), "resunit<%d>", p[0]); break;
@@ -1627,7 +1621,7 @@ const char* voc_debug_last_variant() {
         case VV_ATTN_TILE: snprintf(name, sizeof(name), "attn_tile"); break;
         case VV_ATTN: snprintf(name, sizeof(name), "attn"); break;
         case VV_SPLIT:
-            snprintf(name, sizeof(name), "%ssplit<%d,%d,%d,%d>%s", g_voc_variant.after_pass ? "snake_split+" : "", p[0], p[1], p[2], p[3],
+            snprintf(name, sizeof(name), "%ssplit<%d,%d,%d,%d>%s", voc_variant.after_pass ? "snake_split+" : "", p[0], p[1], p[2], p[3],
                      p[4] ? "/myfast" : "");
             break;
         default: name[0] = 0;
@@ -1642,8 +1636,7 @@ int voc_set_max_workgroups(int n) {   // -> the cap in effect (0 = none)
         hipDeviceProp_t p;
         n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 0;
     }
-    g_voc_max_wgs = n;
-    return n;
+    return voc_settings.set_max_workgroups(n);
 }
 
 }  // extern "C"

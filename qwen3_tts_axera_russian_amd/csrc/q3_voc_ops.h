@@ -1,8 +1,11 @@
 // q3_voc_ops.h -- the launchers of q3_voc_kernels.hip (a kernel and its launcher share that file) and their argument blocks.
 // Used by the vocoder's program (q3_voc.hip), its streaming entry points (q3_voc_stream.hip) and the speech-tokenizer encoder
-// (q3_enc.hip, the f32 launchers; its own kernels live in q3_enc.hip).  Every launcher: 0 ok / <0 error (logged).
+// (q3_enc.hip, the f32 launchers; its own kernels live in q3_enc.hip).  Every launcher: 0 ok / <0 error (logged).  The conv
+// launchers take the caller's settings snapshot (q3_voc_settings.h): the grid cap and the tile rules' knobs.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "q3_voc_settings.h"
 
 namespace q3 {
 
@@ -40,7 +43,7 @@ struct ConvArgs {
 };
 
 // causal Conv1d / polyphase ConvTranspose1d on the exact-fp32 MFMA (conv_kernel and its one-row form)
-int voc_launch_conv(hipStream_t s, const ConvArgs& a, int B);
+int voc_launch_conv(hipStream_t s, const ConvArgs& a, int B, const VocSettings& cfg);
 // RMSNorm (kind 0) / LayerNorm (kind 1) over the C channels of every column of x [B][C][ld] (L columns)
 int voc_launch_norm(hipStream_t s, const float* x, const float* w, const float* bias, float* y, int C, int L, int ld,
                     int kind, float eps, int B);
@@ -64,7 +67,7 @@ struct ResUnitArgs {
     int Lin = 0, ld = 0, dil = 1, tiles_l = 0, n_tiles = 0;   // ld: row pitch of x and y (ConvArgs)
 };
 bool resunit_channels(int c);
-int launch_resunit(hipStream_t s, const ResUnitArgs& a, int C, int B);
+int launch_resunit(hipStream_t s, const ResUnitArgs& a, int C, int B, const VocSettings& cfg);
 
 // split-precision conv on the fp16 MFMA (conv_split_kernel) over {hi, lo} fp16 planes; K taps
 struct SplitArgs {
@@ -88,7 +91,7 @@ struct SplitArgs {
     int n_tiles = 0, tiles_l = 0, tiles_m = 0;
     int my_fast = 0;   // tile order, see conv_split_kernel
 };
-int launch_conv_split(hipStream_t s, const SplitArgs& a, int K, int B);
+int launch_conv_split(hipStream_t s, const SplitArgs& a, int K, int B, const VocSettings& cfg);
 // x f32 [B][C][ld] -> Snake / GELU -> the planes a split conv reads; ovf[b * ovf_stride] = 1 when a value of entry b leaves the
 // fp16 range (SplitArgs::ovf_stride)
 int voc_launch_snake_split(hipStream_t s, const float* x, const float* alpha, const float* inv_beta, _Float16* xh, _Float16* xl, int C,

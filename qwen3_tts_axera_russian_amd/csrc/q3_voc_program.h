@@ -37,6 +37,7 @@ static inline long convt_cols(const VocOp& op, long L) {
 
 struct Voc {
     int device = 0;           // the HIP device the handle was loaded on (q3_set_device before voc_load); entry points bind their thread to it
+    VocSettings cfg;          // the settings of the call in flight (voc_enter): all that planning, walks and launchers read
     int chunk = 64, max_batch = 1, upsample = 1;
     long chunk_samples = 0;   // what one decode of `chunk` frames yields (<= chunk * upsample: the transposed convs trim)
     std::vector<VocOp> ops;
@@ -74,13 +75,14 @@ struct Voc {
 
 // A handle's buffers, stream and events live on the device it was loaded on.  The HIP current device is a per-THREAD setting that
 // starts at 0: a worker thread of a process that drives GPU k (one rank of a multi-GPU job, all GPUs visible) would otherwise launch
-// the decode's kernels with the wrong device current.  Every entry point that touches the GPU binds its thread first.
-static inline void voc_bind(const Voc* v) {
+// the decode's kernels with the wrong device current.  Every entry point that touches the GPU binds its thread first, and takes
+// the call's one snapshot of the process-wide settings (q3_voc_settings.h): nothing below an entry point loads the store.
+static inline void voc_enter(Voc* v) {
+    if (!v) return;
     int d = -1;
-    if (v && (hipGetDevice(&d) != hipSuccess || d != v->device)) hipSetDevice(v->device);
+    if (hipGetDevice(&d) != hipSuccess || d != v->device) hipSetDevice(v->device);
+    v->cfg = voc_settings.load();
 }
-
-extern int g_voc_split;   // 1 (default): split-precision fp16 MFMA path where Cin % 16 == 0; 0: exact-fp32 MFMA everywhere
 
 // device -> the caller's (pageable) memory through the handle's pinned staging, complete on return
 int voc_read_back(Voc* v, void* out, const void* dev, size_t bytes);

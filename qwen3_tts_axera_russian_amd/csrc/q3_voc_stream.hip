@@ -17,7 +17,7 @@ extern "C" {
 static int voc_decode_frames(const Voc* v, int len) {
     static const int full = getenv("Q3_VOC_FULL_CHUNKS") ? atoi(getenv("Q3_VOC_FULL_CHUNKS")) : 0;
     static const int rnd = getenv("Q3_VOC_FRAME_ROUND") ? atoi(getenv("Q3_VOC_FRAME_ROUND")) : 8;
-    if (full || g_voc_split || len >= v->chunk) return v->chunk;
+    if (full || v->cfg.split || len >= v->chunk) return v->chunk;
     const int r = rnd > 0 ? rnd : 1;
     const int t = (len + 1 + r - 1) / r * r;
     return t < v->chunk ? t : v->chunk;
@@ -115,7 +115,7 @@ int decode_walk(Voc* v, const std::vector<WalkChunk>& walk, ChunkCodes chunk_cod
         }
         Q3_HIP(hipEventRecord(v->e1, v->s), -1);
         *v->h_ovf = 0;
-        if (g_voc_split && !redo_exact) Q3_HIP(hipMemcpyAsync(v->h_ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
+        if (v->cfg.split && !redo_exact) Q3_HIP(hipMemcpyAsync(v->h_ovf, v->d_ovf, sizeof(int), hipMemcpyDeviceToHost, v->s), -1);
         Q3_HIP(hipStreamSynchronize(v->s), -1);
         *n_calls = calls;
         if (!*v->h_ovf) break;
@@ -143,7 +143,7 @@ int grow(T** p, size_t* cap, size_t n) {
 }  // extern "C++"
 
 int synth_batch(Voc* v, const int64_t* codes, const int32_t* n_tokens, int U, int64_t* offsets, bool want16, void* out, int64_t cap) {
-    voc_bind(v);
+    voc_enter(v);
     if (!v || !codes || !n_tokens || !offsets || !out || U <= 0) return -1;
     std::vector<WalkChunk> walk;
     std::vector<size_t> code_off(U);
@@ -268,7 +268,7 @@ int stream_push(VocStream* s, int n, const int32_t* streams, const int64_t* code
                 bool want16, void* out, int64_t cap, int64_t* offsets) {
     if (!s || !offsets) return -1;
     Voc* v = s->v;
-    voc_bind(v);
+    voc_enter(v);
     const int CH = v->chunk, OV = 16 * v->upsample;
     PushPlan p;
     if (plan_push(s, n, streams, n_new, finish, p)) return -1;
@@ -393,7 +393,7 @@ int voc_synthesize(void* vv, const int64_t* codes, int n, int16_t* out, int32_t*
 void* voc_stream_create(void* vv, int max_streams) {
     Voc* v = (Voc*)vv;
     if (!v || max_streams <= 0) return nullptr;
-    voc_bind(v);
+    voc_enter(v);
     VocStream* s = new VocStream;
     s->v = v;
     s->max_streams = max_streams;
@@ -411,7 +411,7 @@ void* voc_stream_create(void* vv, int max_streams) {
 void voc_stream_free(void* ss) {
     VocStream* s = (VocStream*)ss;
     if (!s) return;
-    voc_bind(s->v);
+    voc_enter(s->v);
     hipStreamSynchronize(s->v->s);
     for (void* p : {(void*)s->d_tail, (void*)s->d_work, (void*)s->d_out, (void*)s->d_out16, (void*)s->d_win})
         if (p) hipFree(p);
@@ -684,7 +684,7 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
             if (want_f32) sa.y = s->buf[cur ^ 1];
             if (want_planes) voc_split_out_planes(sa, *next, s->plane[2 * (in_set ^ 1)], s->plane[2 * (in_set ^ 1) + 1]);
             if (want_planes) note(op.cout, cols);
-            if (!dry && launch_conv_split(v->s, sa, voc_split_taps(op), B)) return -1;
+            if (!dry && launch_conv_split(v->s, sa, voc_split_taps(op), B, v->cfg)) return -1;
             if (!dry) s->last_split++;
             f32_cur = want_f32;
             planes = want_planes ? (in_set ^ 1) : -1;
@@ -696,7 +696,7 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
             continue;
         } else if (!split && voc_fused_unit(v, i, nend)) {
             if (prepend_act(i)) return -1;
-            if (!dry && launch_resunit(v->s, voc_resunit_args(op, v->ops[i + 1], s->buf[cur], s->buf[cur ^ 1], skip + n), op.cin, B)) return -1;
+            if (!dry && launch_resunit(v->s, voc_resunit_args(op, v->ops[i + 1], s->buf[cur], s->buf[cur ^ 1], skip + n), op.cin, B, v->cfg)) return -1;
             i++;   // the 1x1 conv is done
             if (nc[i] != n) return -1;
         } else {
@@ -733,7 +733,7 @@ int incr_walk(VocIncr* s, const std::vector<long long>& key, int B, bool dry, si
             }
             a.x = (op.flags & VF_RES_SAVE) ? res : s->buf[cur];
             a.y = s->buf[cur ^ 1];
-            if (!dry && voc_launch_conv(v->s, a, B)) return -1;
+            if (!dry && voc_launch_conv(v->s, a, B, v->cfg)) return -1;
             n = n_next;
             skip = skip_next;
         }
@@ -793,7 +793,7 @@ int incr_push(VocIncr* s, int n, const int32_t* streams, const int64_t* codes, c
               bool want16, void* out, int64_t cap, int64_t* offsets, int n_stop = -1, int32_t* out_C = nullptr) {
     if (!s || !offsets) return -1;
     Voc* v = s->v;
-    voc_bind(v);
+    voc_enter(v);
     IncrPlan p;
     if (incr_plan(s, n, streams, n_new, p)) return -1;
     const bool debug = n_stop >= 0;
@@ -925,7 +925,7 @@ int64_t voc_incr_samples(void* vv, int64_t n_frames) {
 void voc_incr_free(void* ss) {
     VocIncr* s = (VocIncr*)ss;
     if (!s) return;
-    voc_bind(s->v);
+    voc_enter(s->v);
     hipStreamSynchronize(s->v->s);
     incr_destroy(s);
 }
@@ -933,7 +933,7 @@ void voc_incr_free(void* ss) {
 void* voc_incr_create(void* vv, int max_streams) {
     Voc* v = (Voc*)vv;
     if (!v || max_streams <= 0) return nullptr;
-    voc_bind(v);
+    voc_enter(v);
     VocIncr* s = new VocIncr;
     s->v = v;
     s->max_streams = max_streams;
@@ -998,7 +998,7 @@ void* voc_incr_create(void* vv, int max_streams) {
 int voc_incr_reset(void* ss, int stream) {
     VocIncr* s = (VocIncr*)ss;
     if (!s || stream < 0 || stream >= s->max_streams) return -1;
-    voc_bind(s->v);
+    voc_enter(s->v);
     if (s->state_floats)   // the stream's history is the zero padding again (ordered before the next push on the handle's stream)
         Q3_HIP(hipMemsetAsync(s->d_hist + (size_t)stream * s->state_floats, 0, sizeof(float) * s->state_floats, s->v->s), -1);
     if (s->state_floats && s->d_hist1)   // (both buffers: an op a short first push does not reach reads the other one next time)
@@ -1052,6 +1052,8 @@ int voc_incr_set_arithmetic(void* ss, int split) {
             return -1;
         }
     if (split && !s->d_hist1) {
+        Voc* v = s->v;
+        voc_enter(v);
         // the split walk's activations and planes must fit what voc_incr_create sized from the exact walk (the same ops over the
         // same columns: a table where they do not is refused here, not overrun)
         size_t need = 0, need_kv = 0;
@@ -1067,8 +1069,6 @@ int voc_incr_set_arithmetic(void* ss, int split) {
         }
         // the second history buffer, the plane sets and the per-entry flags.  Every stream is idle, and an idle stream's next
         // utterance starts with voc_incr_reset (or is the first of a fresh object): both buffers zero, parity 0.
-        Voc* v = s->v;
-        voc_bind(v);
         const size_t mb = (size_t)v->max_batch, hist = sizeof(float) * std::max<size_t>(1, s->state_floats * s->max_streams);
         DeviceAllocs got;   // all or nothing: the object adopts it once every buffer is there and filled
         float* hist1 = nullptr;
@@ -1104,7 +1104,7 @@ int voc_incr_last_redone(void* s) { return s ? ((VocIncr*)s)->last_redone : -1; 
 int voc_incr_snapshots(void* vv, int n_slots) {
     Voc* v = (Voc*)vv;
     if (!v || n_slots < 0) return -1;
-    voc_bind(v);
+    voc_enter(v);
     float* pool = nullptr;
     const size_t pitch = (incr_state_floats(v) + 3) / 4 * 4;
     if (n_slots > 0 && hipMalloc((void**)&pool, sizeof(float) * std::max<size_t>(4, pitch * (size_t)n_slots)) != hipSuccess) {
@@ -1131,7 +1131,7 @@ int voc_incr_save(void* ss, int stream, int slot) {
     if (!s || stream < 0 || stream >= s->max_streams || s->finished[stream]) return -1;
     Voc* v = s->v;
     if (!v->d_snap || slot < 0 || slot >= (int)v->snap_frames.size()) return -1;
-    voc_bind(v);
+    voc_enter(v);
     // the committed history: in a double-buffered object the buffer the stream's parity selects
     const float* hist = (s->d_hist1 && s->parity[stream] ? s->d_hist1 : s->d_hist) + (size_t)stream * s->state_floats;
     if (s->state_floats)
@@ -1166,7 +1166,7 @@ int voc_incr_restore(void* ss, int n, const int32_t* streams, const int32_t* slo
     }
     s->last_restore_ms = 0.f;
     if (n == 0) return 0;
-    voc_bind(v);
+    voc_enter(v);
     if (grow(&v->d_snap_tab, &v->snap_tab_cap, (size_t)std::max(n, s->max_streams))) return -1;
     std::vector<SnapCopy> tab(n);
     for (int i = 0; i < n; i++) {

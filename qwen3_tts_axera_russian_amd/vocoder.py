@@ -1,5 +1,6 @@
 """Host side of the vocoder (include/qwen3tts_voc.h): codec ids [frames][16] -> 24 kHz waveform.  voc_set_exact_fp32 and
-voc_set_max_workgroups act on the whole process, not on one handle: they stay plain library calls."""
+voc_set_max_workgroups act on the whole process, not on one handle: they stay plain library calls.  They may be made from any
+thread and take effect from the next call on: a decode in flight finishes under the settings it started with."""
 from __future__ import annotations
 
 import numpy as np
